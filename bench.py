@@ -22,8 +22,11 @@ N > 1 (launched by torch.distributed.run): barcode groups are independent, so ev
 its own replica of the index with no data-path collective (weak scaling: each rank gets a full slice with its own
 seed); torch.distributed (RCCL) is used for the barriers and the max-over-ranks time only.
 
-The same job times the reference's C core on the host cores beside the GPU (cpu_baseline) and checks a sample of the GPU
-results against it bit for bit; a mismatch makes the run fail (parity_ok false, exit code 1).
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs DIR (the last timed step's results for a seeded
+sample of the reads) and prints the result line.  With --full the same job also reports per-kernel times, the boundary
+pass, the kernels alone, the rooflines and the end-to-end FASTQ -> BAM pass, and times the reference's C core on the host
+cores beside the GPU (cpu_baseline) and checks a sample of the GPU results against it bit for bit; a mismatch makes the
+run fail (parity_ok false, exit code 1).
 
 Prints ONE JSON line on rank 0.
 """
@@ -80,22 +83,45 @@ def log(*a):
 
 
 def prepare_index(cache, name, lens, seed, families, rank, barrier, setup, in_child=False, alt_spec=None, decoy_spec=None):
+    """Synthetic genome + index, cached on disk (see start_index) -> prefix, once the index exists."""
+    prefix, wait = start_index(cache, name, lens, seed, families, rank, barrier, setup, in_child=in_child, alt_spec=alt_spec, decoy_spec=decoy_spec)
+    wait()
+    return prefix
+
+
+def start_index(cache, name, lens, seed, families, rank, barrier, setup, in_child=False, alt_spec=None, decoy_spec=None):
     """Synthetic genome + index (built by the product's own `bwa index` equivalent: suffix sorting in HBM), cached on disk.
     The work is done by a child process (bench.py --prepare-only): a process that has synthesised a 3 GB genome and sorted 6.2 G
     suffixes through 125 GB of HBM runs the timed region ~25 % slower afterwards (host-side round trips of the stage loops take longer;
-    measured in round 2) -- the measuring process stays clean."""
+    measured in round 2) -- the measuring process stays clean.
+    -> (prefix, wait): the genome's files exist on return; wait() returns once the index does.  The child marks the genome's files
+    done before it builds the index, so that the caller synthesises its reads while the index is built."""
     from arachne_amd import api, synth
     total = int(sum(lens))
     prefix = os.path.join(cache, f"{name}_{total}.fa")
     done = prefix + ".done"
+    genome_done = prefix + ".genome.done"
     if rank == 0 and not os.path.exists(done) and not in_child:
         import subprocess
         os.makedirs(cache, exist_ok=True)
         spec = prefix + ".spec.json"
         json.dump(dict(cache=cache, name=name, lens=[int(x) for x in lens], seed=int(seed), families=families, alt_spec=alt_spec, decoy_spec=decoy_spec), open(spec, "w"))
-        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--prepare-only", spec])
-        setup.update(json.load(open(prefix + ".setup.json")))
+        if os.path.exists(genome_done):
+            os.remove(genome_done)
+        child = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--prepare-only", spec])
+        while not os.path.exists(genome_done) and child.poll() is None:
+            time.sleep(0.05)
+
+        def wait():
+            if child.wait() != 0:
+                raise subprocess.CalledProcessError(child.returncode, child.args)
+            setup.update(json.load(open(prefix + ".setup.json")))
+            barrier()
+        if child.poll() not in (None, 0):
+            wait()
+        return prefix, wait
     if rank == 0 and not os.path.exists(done):
+        import threading
         os.makedirs(cache, exist_ok=True)
         t = time.time()
         g = synth.make_genome(seed, lens, repeat_families=families, fast=total > 500_000_000, alt_spec=alt_spec, decoy_spec=decoy_spec)
@@ -104,23 +130,36 @@ def prepare_index(cache, name, lens, seed, families, rank, barrier, setup, in_ch
         g.write_fasta(prefix)
         if any(g.alt):
             g.write_alt(prefix + ".alt")                 # read by arx_open like bns_restore reads it (bntseq.c:98-206)
+        # the index is built from the FASTA while the codes the read synthesis needs are written beside it
+        failed = []
+
+        def build():
+            try:
+                api.index_build(prefix, prefix)
+            except BaseException as e:  # re-raised below
+                failed.append(e)
+        t_index = time.time()
+        builder = threading.Thread(target=build)
+        builder.start()
         np.save(prefix + ".codes.npy", np.concatenate(g.seqs))
         np.save(prefix + ".lens.npy", np.array([len(x) for x in g.seqs], dtype=np.int64))
         np.save(prefix + ".copies.npy", g.copies)
         json.dump(dict(names=g.names, alt=[bool(a) for a in g.alt], fam_weight=[float(x) for x in g.fam_weight]), open(prefix + ".contigs.json", "w"))
         del g
+        open(genome_done, "w").write("ok")
         setup["genome_write_s"] = round(time.time() - t, 2)
         log(f"genome {total} bp synthesised and written in {setup['genome_synth_s'] + setup['genome_write_s']:.1f}s")
-        t = time.time()
-        api.index_build(prefix, prefix)
-        setup["index_build_s"] = round(time.time() - t, 2)
-        log(f"index built in {time.time() - t:.1f}s (arx_index_build: FASTA -> .pac/.ann/.amb on the host, BWT + SA in HBM)")
+        builder.join()
+        if failed:
+            raise failed[0]
+        setup["index_build_s"] = round(time.time() - t_index, 2)
+        log(f"index built in {setup['index_build_s']:.1f}s (arx_index_build: FASTA -> .pac/.ann/.amb on the host, BWT + SA in HBM)")
         if total > 500_000_000:
             os.remove(prefix)          # the codes are kept as .npy; the FASTA of a GRCh38-size genome is 3 GB
         json.dump(setup, open(prefix + ".setup.json", "w"))
         open(done, "w").write("ok")
     barrier()
-    return prefix
+    return prefix, lambda: None
 
 
 def load_genome(prefix):
@@ -230,7 +269,7 @@ def algorithmic_bytes(prefix, rs, n_sample):
 
 
 def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--prepare-only":   # the child of prepare_index()
+    if len(sys.argv) == 3 and sys.argv[1] == "--prepare-only":   # the child of start_index()
         sp = json.load(open(sys.argv[2]))
         fam = [tuple(f) for f in sp["families"]] if sp["families"] is not None else None
         prepare_index(sp["cache"], sp["name"], sp["lens"], sp["seed"], fam, 0, lambda: None, {}, in_child=True, alt_spec=sp.get("alt_spec"), decoy_spec=sp.get("decoy_spec"))
@@ -263,6 +302,11 @@ def main():
     ap.add_argument("--no-stagger", dest="stagger", action="store_false",
                     help="(diagnostics) all batches start together instead of one seeding stage after the other (about 5 %% more throughput, "
                          "but three seeding stages then compete for HBM latency at once and the roofline kernel's time doubles)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline figure: per-kernel times, the boundary "
+                    "pass, the kernels alone, the scatter / gather pass (N > 1), the rooflines, the CPU baseline with its parity gate and the end-to-end "
+                    "FASTQ -> BAM pass.  Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (regions, "
+                    "alignment records, CIGARs, placed candidates with MAPQ) for a fixed, seeded sample of the reads as DIR/<name>.npy (float64)")
     ap.add_argument("--cache", default="/tmp/arx_bench_cache")
     ap.add_argument("--lib", default=None, help="(dry runs of this script only) alternative library exporting the C ABI")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo for the CPU dry run of the sharding logic)")
@@ -309,7 +353,7 @@ def main():
     setup = {}
     if args.lib:
         api.LIB_PATH = args.lib
-    prefix = prepare_index(args.cache, args.workload if not args.genome_len else "custom", wl["lens"], SEED0, wl["families"], rank, barrier, setup,
+    prefix, index_ready = start_index(args.cache, args.workload if not args.genome_len else "custom", wl["lens"], SEED0, wl["families"], rank, barrier, setup,
                            alt_spec=wl.get("alt_spec"), decoy_spec=wl.get("decoy_spec"))
     genome = load_genome(prefix)
     t = time.time()
@@ -317,6 +361,7 @@ def main():
     setup["reads_synth_s"] = round(time.time() - t, 2)
     log(f"rank {rank}: {rs.n_pairs} pairs synthesised in {time.time() - t:.1f}s")
     del genome
+    index_ready()
 
     t = time.time()
     if args.lib:
@@ -340,7 +385,8 @@ def main():
                 end += 1
             p0, p1 = int(po[start]), int(po[end])
             b = ref.batch(rs.seqs[2 * p0:2 * p1], rs.lens[2 * p0:2 * p1])
-            b.host = (b.pin(np.array(rs.seqs[2 * p0:2 * p1], copy=True).reshape(-1)), np.ascontiguousarray(rs.lens[2 * p0:2 * p1]))   # the caller's own, page-locked read buffer
+            if args.full:   # the boundary pass reads from the caller's own, page-locked read buffer
+                b.host = (b.pin(np.array(rs.seqs[2 * p0:2 * p1], copy=True).reshape(-1)), np.ascontiguousarray(rs.lens[2 * p0:2 * p1]))
             b.out = {}
             b.bc_pair_off = (po[start:end + 1] - po[start]).astype(np.int64)
             b.do_rfa = np.array([api.worth_running_rfa(rs.barcodes[i], int(po[i + 1] - po[i])) for i in range(start, end)], dtype=np.uint8)
@@ -447,7 +493,7 @@ def main():
     setup["prime_handles_s"] = round(time.time() - t, 2)
     run_steps(args.warmup)
     phase_s[False].clear()
-    ref.kernel_times_reset(True)   # HIP events around every launch on the launch stream, resolved after the timed region
+    ref.kernel_times_reset(args.full)   # --full: HIP events around every launch on the launch stream, resolved after the timed region
     barrier()
     t0 = time.time()
     run_steps(args.steps)
@@ -458,11 +504,13 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    ktimes = ref.kernel_times()
+    ktimes = ref.kernel_times() if args.full else {}
     counts = [b.counts() for b in batches]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ref, sets[(args.steps - 1) % len(sets)], with_cands=not args.no_rfa)
     # the same steps boundary to boundary: host arrays in (arx_batch_reset), host arrays out (arx_batch_fetch, arx_batch_rfa_fetch)
     boundary = None
-    if args.boundary_steps > 0 and args.stagger:
+    if args.full and args.boundary_steps > 0 and args.stagger:
         ref.kernel_times_reset(False)
         run_steps(1, boundary=True)                       # sizes the reused host arrays and the staging
         phase_s[True].clear()
@@ -476,25 +524,27 @@ def main():
             tt = torch.tensor([boundary], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             boundary = float(tt.item())
-    # the seeding kernel alone on the chip, same inputs, outside the timed region
-    ref.kernel_times_reset(True)
-    for b in batches:
-        b.run(api.STAGE_SEED)
-    ktimes_iso = ref.kernel_times()
-    # every kernel with the chip to itself: the same batches through the whole path one after the other (in the timed region three batches'
-    # streams overlap, and the elapsed time of a launch there includes what it waits for)
-    ref.kernel_times_reset(True)
-    for b in batches:
-        b.run(api.STAGE_SEED)
-        b.run(api.STAGE_ALN)
-        if not args.no_rfa:
-            b.rfa(b.bc_pair_off, b.do_rfa, fetch=False)
-    ktimes_alone = ref.kernel_times()
-    ref.kernel_times_reset(False)
+    ktimes_iso, ktimes_alone = {}, {}
+    if args.full:
+        # the seeding kernel alone on the chip, same inputs, outside the timed region
+        ref.kernel_times_reset(True)
+        for b in batches:
+            b.run(api.STAGE_SEED)
+        ktimes_iso = ref.kernel_times()
+        # every kernel with the chip to itself: the same batches through the whole path one after the other (in the timed region three batches'
+        # streams overlap, and the elapsed time of a launch there includes what it waits for)
+        ref.kernel_times_reset(True)
+        for b in batches:
+            b.run(api.STAGE_SEED)
+            b.run(api.STAGE_ALN)
+            if not args.no_rfa:
+                b.rfa(b.bc_pair_off, b.do_rfa, fetch=False)
+        ktimes_alone = ref.kernel_times()
+        ref.kernel_times_reset(False)
     # what every rank did (control plane only; the data path has no collective): pairs and regions per step
     # SURVEY.md s8e as written: one ingest rank, LPT assignment of whole barcodes, scatter of packed batches, gather of result slabs
     scatter_info = None
-    if args.scatter_steps > 0 and dist is not None and args.stagger:
+    if args.full and args.scatter_steps > 0 and dist is not None and args.stagger:
         from arachne_amd import shard
         xch = shard.Exchange(dist, "cuda" if args.backend == "nccl" else "cpu")
         nb = len(batches)
@@ -555,7 +605,7 @@ def main():
         out["per_rank"] = per_rank
         # how often the whole path ran over the read set in this process (profilers sum over all of it): priming of every handle, warm-up, timed
         # steps, the boundary pass (one sizing step + its steps), the "alone" pass
-        out["whole_path_passes"] = len(sets) + args.warmup + args.steps + (1 + args.boundary_steps if (args.boundary_steps > 0 and args.stagger) else 0) + 1
+        out["whole_path_passes"] = len(sets) + args.warmup + args.steps + (((1 + args.boundary_steps if (args.boundary_steps > 0 and args.stagger) else 0) + 1) if args.full else 0)
         out["setup_s"] = setup
         out["index"] = index_info
         if boundary:
@@ -574,142 +624,143 @@ def main():
         out["host_phase_ms_per_batch"] = dict(resident=per_batch(phase_s[False]), boundary=per_batch(phase_s[True]),
                                               note="wall time of a batch's host thread per phase (three batches in flight: the phases of different batches overlap); "
                                                    "wait_turn = waiting for the batch ahead to leave the seeding stage (the staggered schedule)")
-        # where the FM-index lives decides what the seeding kernels are bound by: a table under 256 MiB stays in the Infinity Cache
-        occ_bytes = index_bytes["bwt"]
-        in_hbm = occ_bytes > INFINITY_CACHE_BYTES
-        bound = "hbm" if in_hbm else "infinity-cache"
-        bound_note = ("Occ/BWT table %.2f GB in HBM, scattered 64-byte block reads" % (occ_bytes / 1e9)) if in_hbm else \
-            ("Occ/BWT table %.0f MB fits the 256 MiB Infinity Cache: the fraction below is against the HBM peak for comparison only, it is not an HBM measurement" % (occ_bytes / 1e6))
-        # roofline of the seeding kernel (the HBM-bound headline)
-        try:
-            ab = algorithmic_bytes(prefix, rs, 10_000)
-            reads_per_launch = 2.0 * rs.n_pairs / len(batches)
-            # The roofline kernel: the backward sweeps of bwt_smem1a, the largest of the seeding kernels (k_seed_bwd finishes its
-            # longest sweeps in k_seed_bwd_wave: the pair is one launch here; each batch launches it for the first pass and for
-            # the re-seeding pass, with half of the batch's backward bytes on average).
-            BWD = ["seed_bwd", "seed_bwd32", "seed_bwd64", "seed_bwd_wave"]   # one "launch" of the backward sweeps = the group kernels of the three list-length bins + the wave kernel
+        if args.full:   # per-kernel times, rooflines and the figures derived from them
+            # where the FM-index lives decides what the seeding kernels are bound by: a table under 256 MiB stays in the Infinity Cache
+            occ_bytes = index_bytes["bwt"]
+            in_hbm = occ_bytes > INFINITY_CACHE_BYTES
+            bound = "hbm" if in_hbm else "infinity-cache"
+            bound_note = ("Occ/BWT table %.2f GB in HBM, scattered 64-byte block reads" % (occ_bytes / 1e9)) if in_hbm else \
+                ("Occ/BWT table %.0f MB fits the 256 MiB Infinity Cache: the fraction below is against the HBM peak for comparison only, it is not an HBM measurement" % (occ_bytes / 1e6))
+            # roofline of the seeding kernel (the HBM-bound headline)
+            try:
+                ab = algorithmic_bytes(prefix, rs, 10_000)
+                reads_per_launch = 2.0 * rs.n_pairs / len(batches)
+                # The roofline kernel: the backward sweeps of bwt_smem1a, the largest of the seeding kernels (k_seed_bwd finishes its
+                # longest sweeps in k_seed_bwd_wave: the pair is one launch here; each batch launches it for the first pass and for
+                # the re-seeding pass, with half of the batch's backward bytes on average).
+                BWD = ["seed_bwd", "seed_bwd32", "seed_bwd64", "seed_bwd_wave"]   # one "launch" of the backward sweeps = the group kernels of the three list-length bins + the wave kernel
 
-            def group(kt, names):
-                ms = sum(kt[n]["ms"] for n in names if n in kt)
-                calls = kt[names[0]]["calls"] if names[0] in kt else 0
-                return ms, calls
-            ms, calls = group(ktimes, BWD)
-            if calls:
-                launches_per_batch = 2.0
-                avg_ms = ms / calls
-                bytes_per_launch = ab["bwd"] * reads_per_launch / launches_per_batch
-                achieved = bytes_per_launch / max(avg_ms * 1e-3, 1e-12) / 1e9
-                # memory-side bytes of the same kernels from the committed rocprofv3 --pmc FETCH_SIZE pass of this command (counters
-                # cannot be read from inside the process); null when no such pass is committed
-                traffic, traffic_src = None, None
-                rel = os.path.join("profiles", "r03", "seed_traffic_%s.json" % args.workload)
-                if not os.path.exists(os.path.join(ROOT, rel)):
-                    rel = os.path.join("profiles", "r02", "seed_traffic_%s.json" % args.workload)
-                tf = os.path.join(ROOT, rel)
-                if os.path.exists(tf):
-                    tj = json.load(open(tf))
-                    if "bwd_fabric_bytes_per_read" in tj:
-                        traffic = tj["bwd_fabric_bytes_per_read"] * reads_per_launch / launches_per_batch
-                        traffic_src = rel
-                out["roofline"] = dict(kernel="seed_bwd (k_seed_bwd_g<16/32/64> + k_seed_bwd_wave: backward sweeps of bwt_smem1a, bwt_extend/bwt_2occ4)", bound=bound, bound_note=bound_note,
-                                       achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS, traffic=traffic,
-                                       traffic_unit="bytes per launch", traffic_source=traffic_src, algorithmic_bytes_per_read=ab["bwd"],
-                                       reads_per_launch=reads_per_launch, launches_per_batch=launches_per_batch, avg_launch_ms=avg_ms)
-                ims, icalls = group(ktimes_iso, BWD)
-                if icalls:
-                    iso_ms = ims / icalls
-                    iso = bytes_per_launch / max(iso_ms * 1e-3, 1e-12) / 1e9
-                    out["roofline"]["isolated"] = dict(achieved=iso, frac=iso / HBM_PEAK_GBS, avg_launch_ms=iso_ms,
-                                                       note="same kernels, same inputs, launched alone after the timed region (in the timed region they co-run with the other batches' DP kernels)")
-            # the whole seeding stage (forward extensions, backward sweeps, third pass, gathers) against its algorithmic bytes
-            stage = ["seed_pack", "seed_fwd", "seed_bwd", "seed_bwd32", "seed_bwd64", "seed_bwd_wave", "seed_gather", "seed_strat", "seed_merge"]
-            for key, kt in (("roofline_seeding_stage", ktimes), ("roofline_seeding_stage_isolated", ktimes_iso)):
-                sms = sum(kt[n]["ms"] for n in stage if n in kt)
-                runs = kt["seed_strat"]["calls"] if "seed_strat" in kt else 0
-                if runs:
-                    tot = (ab["seed"] + ab["strat"]) * reads_per_launch
-                    ach = tot / max(sms / runs * 1e-3, 1e-12) / 1e9
-                    out[key] = dict(kernels=stage, bound=bound, achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS,
-                                    algorithmic_bytes_per_read=ab["seed"] + ab["strat"], ms_per_batch=sms / runs)
-            ms, calls = group(ktimes, ["seed_fwd"])
-            if calls:
-                avg_ms = ms / calls
-                ach = ab["fwd"] * reads_per_launch / 2.0 / max(avg_ms * 1e-3, 1e-12) / 1e9
-                out["roofline_fwd"] = dict(kernel="seed_fwd (k_seed_fwd1 / k_seed_fwd2: forward extensions of bwt_smem1a)", bound=bound, achieved=ach, peak=HBM_PEAK_GBS,
-                                           unit="GB/s", frac=ach / HBM_PEAK_GBS, algorithmic_bytes_per_read=ab["fwd"], avg_launch_ms=avg_ms)
-            ks3 = ktimes.get("seed_strat")
-            if ks3 and ks3["calls"]:
-                avg_ms = ks3["ms"] / ks3["calls"]
-                ach = ab["strat"] * reads_per_launch / max(avg_ms * 1e-3, 1e-12) / 1e9
-                out["roofline_strat"] = dict(kernel="seed_strat (k_strat_dyn: bwt_seed_strategy1, third seeding pass)", bound=bound, achieved=ach, peak=HBM_PEAK_GBS,
-                                             unit="GB/s", frac=ach / HBM_PEAK_GBS, algorithmic_bytes_per_read=ab["strat"], avg_launch_ms=avg_ms)
-            kl = ktimes.get("locate")
-            if kl and kl["calls"]:
-                avg_ms = kl["ms"] / kl["calls"]
-                # the bytes of the walk the kernel does: the same lookups, each walked to the first row that is a multiple of the
-                # device's sample interval (counted by the restatement for 8; the reference's own walk to every 32nd row beside it)
-                dense = index_info["sa_rows_per_entry"]
-                per_read = ab["locate1"] if dense == 1 else ab["locate4"] if dense == 4 else ab["locate8"] if dense == 8 else ab["locate"]
-                ach = per_read * reads_per_launch / max(avg_ms * 1e-3, 1e-12) / 1e9
-                out["roofline_locate"] = dict(kernel=("locate (KLocate: one entry of the resident suffix array per occurrence, no walk)" if dense == 1 else
-                                                      "locate (k_locate_dyn: bwt_sa LF walk to the suffix-array sample every %d-th row)" % dense), bound=bound,
-                                              achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS, algorithmic_bytes_per_read=per_read,
-                                              reference_walk_bytes_per_read=ab["locate"], avg_launch_ms=avg_ms)
-            out["work_per_read"] = ab["counters"]
-            cw = ab["counters"]
-            # SURVEY.md s8d's path-level figure: pairs/s x algorithmic bytes per pair / HBM peak, bytes per read =
-            # 64 (E1 + 2 E2) + (64 S + 8 N_sa) + L/4 + 88 N_reg, all counted by the instrumented restatement on a sample of the same reads
-            per_read = 64.0 * (cw["ext_same_block"] + 2 * cw["ext_two_block"]) + 64.0 * cw["sa_lf_steps"] + 8.0 * cw["sa_lookups"] + float(np.mean(rs.lens)) / 4 + 88.0 * cw["n_regs"]
-            out["roofline_path"] = dict(definition="SURVEY.md s8d: pairs/s x algorithmic bytes per pair / HBM peak; bytes per read = 64(E1+2E2) + 64 S + 8 N_sa + L/4 + 88 N_reg "
-                                                   "(the reference's own walks, incl. its suffix-array sample every 32nd row)",
-                                        algorithmic_bytes_per_pair=2 * per_read, achieved=value * 2 * per_read / 1e9, peak=HBM_PEAK_GBS, unit="GB/s",
-                                        frac=value * 2 * per_read / 1e9 / HBM_PEAK_GBS)
-            # Smith-Waterman kernels: cell updates per second (the reference's cells, counted by the restatement: band cells of ksw_extend2,
-            # query x window cells of both ksw_u8 passes, band cells of ksw_global2) against the VALU; instruction counters from the committed
-            # rocprofv3 --pmc pass of this command (profiles/r03/sw_counters_<workload>.json, tools/prof_summary.py), null when none is committed
-            swc = {}
-            rel_sw = os.path.join("profiles", "r03", "sw_counters_%s.json" % args.workload)
-            if os.path.exists(os.path.join(ROOT, rel_sw)):
-                swc = json.load(open(os.path.join(ROOT, rel_sw)))
-            sw = {}
-            for key, kern, cells_key, what in (("extend", "extend", "cells_extend", "ksw_extend2 band cells (k_extend_g16)"), ("sw_u8", "sw_u8", "cells_u8", "ksw_u8 cells, both passes (k_sw_u8_g16)"),
-                                               ("reg2aln_nw", "reg2aln_nw", "cells_global", "ksw_global2 band cells (k_reg2aln_nw_g16)")):
-                cells_step = cw[cells_key] * 2.0 * rs.n_pairs
-                e = dict(cells=what, cells_per_read=cw[cells_key])
-                if kern in ktimes and ktimes[kern]["ms"] > 0:
-                    e["gcups_timed"] = cells_step * args.steps / (ktimes[kern]["ms"] * 1e-3) / 1e9
-                if kern in ktimes_alone and ktimes_alone[kern]["ms"] > 0:
-                    e["gcups_alone"] = cells_step / (ktimes_alone[kern]["ms"] * 1e-3) / 1e9
-                e.update(swc.get(kern, dict(valu_busy=None, lane_ops_per_cell=None, lds_insts_per_valu=None)))
-                sw[key] = e
-            out["roofline_sw"] = dict(kernels=sw, bound="valu", counters_source=rel_sw if swc else None,
-                                      peak_note="gfx950: 256 CUs x 4 SIMDs; valu_busy = rocprofv3's VALUBusy (SQ_ACTIVE_INST_VALU x 4 / SIMDs / cycles at %.1f GHz); "
-                                                "lane_ops_per_cell = SQ_INSTS_VALU x 64 / reference cells; max-plus DP, no MFMA" % 2.4)
-            if "roofline" in out:   # what the committed counters say the roofline kernel is bound by
-                rc = swc.get("seed_bwd")
-                if rc and rc.get("valu_busy") is not None:
-                    out["roofline"]["valu_busy"] = rc["valu_busy"]
-                    if rc["valu_busy"] >= 0.6 and in_hbm:
-                        out["roofline"]["bound"] = "valu"
-                        out["roofline"]["bound_note"] += "; the kernel's vector instructions keep the SIMDs busy %.0f %% of its time (VALUBusy, committed --pmc pass): instruction issue, not HBM, bounds it; frac stays the HBM-roofline figure the metric asks for" % (100 * rc["valu_busy"])
-        except Exception as e:  # the roofline needs the oracle library; never fail the throughput line over it
-            log("roofline skipped:", repr(e))
-        tot = sum(v["ms"] for v in ktimes.values()) or 1.0
-        out["kernel_ms_per_step"] = {k: round(v["ms"] / args.steps, 3) for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1]["ms"])}
-        out["kernel_share"] = {k: round(v["ms"] / tot, 4) for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1]["ms"])}
-        tot_a = sum(v["ms"] for v in ktimes_alone.values()) or 1.0
-        out["kernel_ms_per_step_alone"] = {k: round(v["ms"], 3) for k, v in sorted(ktimes_alone.items(), key=lambda kv: -kv[1]["ms"])}
-        out["kernel_share_alone"] = {k: round(v["ms"] / tot_a, 4) for k, v in sorted(ktimes_alone.items(), key=lambda kv: -kv[1]["ms"])}
-        book = ("chain", "chain_heavy", "ext_step", "rescue_step", "rescue_heavy", "dedup", "dedup_heavy", "scan")
-        out["bookkeeping_share"] = dict(kernels=list(book), overlapped=round(sum(ktimes.get(k, {"ms": 0.0})["ms"] for k in book) / tot, 4),
-                                        alone=round(sum(ktimes_alone.get(k, {"ms": 0.0})["ms"] for k in book) / tot_a, 4),
-                                        note="list bookkeeping (chaining, extension state machines, rescue replay, de-duplication, scans) as a share of the "
-                                             "summed kernel time; round 1: 0.31 overlapped on the chr20-size workload")
-        out["kernel_share_note"] = ("kernel_share: elapsed time per launch (HIP events on the launch stream) summed over the timed region, where the "
-                                    "streams of %d device batches overlap -- a launch that shares or waits for CUs counts for as long as it is in flight, "
-                                    "so one-wavefront tails (rescue_heavy, chain_heavy) weigh far more than the resources they hold; "
-                                    "kernel_share_alone: one step's batches run one after the other after the timed region, every launch alone on the chip"
-                                    % len(batches))
+                def group(kt, names):
+                    ms = sum(kt[n]["ms"] for n in names if n in kt)
+                    calls = kt[names[0]]["calls"] if names[0] in kt else 0
+                    return ms, calls
+                ms, calls = group(ktimes, BWD)
+                if calls:
+                    launches_per_batch = 2.0
+                    avg_ms = ms / calls
+                    bytes_per_launch = ab["bwd"] * reads_per_launch / launches_per_batch
+                    achieved = bytes_per_launch / max(avg_ms * 1e-3, 1e-12) / 1e9
+                    # memory-side bytes of the same kernels from the committed rocprofv3 --pmc FETCH_SIZE pass of this command (counters
+                    # cannot be read from inside the process); null when no such pass is committed
+                    traffic, traffic_src = None, None
+                    rel = os.path.join("profiles", "r03", "seed_traffic_%s.json" % args.workload)
+                    if not os.path.exists(os.path.join(ROOT, rel)):
+                        rel = os.path.join("profiles", "r02", "seed_traffic_%s.json" % args.workload)
+                    tf = os.path.join(ROOT, rel)
+                    if os.path.exists(tf):
+                        tj = json.load(open(tf))
+                        if "bwd_fabric_bytes_per_read" in tj:
+                            traffic = tj["bwd_fabric_bytes_per_read"] * reads_per_launch / launches_per_batch
+                            traffic_src = rel
+                    out["roofline"] = dict(kernel="seed_bwd (k_seed_bwd_g<16/32/64> + k_seed_bwd_wave: backward sweeps of bwt_smem1a, bwt_extend/bwt_2occ4)", bound=bound, bound_note=bound_note,
+                                           achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS, traffic=traffic,
+                                           traffic_unit="bytes per launch", traffic_source=traffic_src, algorithmic_bytes_per_read=ab["bwd"],
+                                           reads_per_launch=reads_per_launch, launches_per_batch=launches_per_batch, avg_launch_ms=avg_ms)
+                    ims, icalls = group(ktimes_iso, BWD)
+                    if icalls:
+                        iso_ms = ims / icalls
+                        iso = bytes_per_launch / max(iso_ms * 1e-3, 1e-12) / 1e9
+                        out["roofline"]["isolated"] = dict(achieved=iso, frac=iso / HBM_PEAK_GBS, avg_launch_ms=iso_ms,
+                                                           note="same kernels, same inputs, launched alone after the timed region (in the timed region they co-run with the other batches' DP kernels)")
+                # the whole seeding stage (forward extensions, backward sweeps, third pass, gathers) against its algorithmic bytes
+                stage = ["seed_pack", "seed_fwd", "seed_bwd", "seed_bwd32", "seed_bwd64", "seed_bwd_wave", "seed_gather", "seed_strat", "seed_merge"]
+                for key, kt in (("roofline_seeding_stage", ktimes), ("roofline_seeding_stage_isolated", ktimes_iso)):
+                    sms = sum(kt[n]["ms"] for n in stage if n in kt)
+                    runs = kt["seed_strat"]["calls"] if "seed_strat" in kt else 0
+                    if runs:
+                        tot = (ab["seed"] + ab["strat"]) * reads_per_launch
+                        ach = tot / max(sms / runs * 1e-3, 1e-12) / 1e9
+                        out[key] = dict(kernels=stage, bound=bound, achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS,
+                                        algorithmic_bytes_per_read=ab["seed"] + ab["strat"], ms_per_batch=sms / runs)
+                ms, calls = group(ktimes, ["seed_fwd"])
+                if calls:
+                    avg_ms = ms / calls
+                    ach = ab["fwd"] * reads_per_launch / 2.0 / max(avg_ms * 1e-3, 1e-12) / 1e9
+                    out["roofline_fwd"] = dict(kernel="seed_fwd (k_seed_fwd1 / k_seed_fwd2: forward extensions of bwt_smem1a)", bound=bound, achieved=ach, peak=HBM_PEAK_GBS,
+                                               unit="GB/s", frac=ach / HBM_PEAK_GBS, algorithmic_bytes_per_read=ab["fwd"], avg_launch_ms=avg_ms)
+                ks3 = ktimes.get("seed_strat")
+                if ks3 and ks3["calls"]:
+                    avg_ms = ks3["ms"] / ks3["calls"]
+                    ach = ab["strat"] * reads_per_launch / max(avg_ms * 1e-3, 1e-12) / 1e9
+                    out["roofline_strat"] = dict(kernel="seed_strat (k_strat_dyn: bwt_seed_strategy1, third seeding pass)", bound=bound, achieved=ach, peak=HBM_PEAK_GBS,
+                                                 unit="GB/s", frac=ach / HBM_PEAK_GBS, algorithmic_bytes_per_read=ab["strat"], avg_launch_ms=avg_ms)
+                kl = ktimes.get("locate")
+                if kl and kl["calls"]:
+                    avg_ms = kl["ms"] / kl["calls"]
+                    # the bytes of the walk the kernel does: the same lookups, each walked to the first row that is a multiple of the
+                    # device's sample interval (counted by the restatement for 8; the reference's own walk to every 32nd row beside it)
+                    dense = index_info["sa_rows_per_entry"]
+                    per_read = ab["locate1"] if dense == 1 else ab["locate4"] if dense == 4 else ab["locate8"] if dense == 8 else ab["locate"]
+                    ach = per_read * reads_per_launch / max(avg_ms * 1e-3, 1e-12) / 1e9
+                    out["roofline_locate"] = dict(kernel=("locate (KLocate: one entry of the resident suffix array per occurrence, no walk)" if dense == 1 else
+                                                          "locate (k_locate_dyn: bwt_sa LF walk to the suffix-array sample every %d-th row)" % dense), bound=bound,
+                                                  achieved=ach, peak=HBM_PEAK_GBS, unit="GB/s", frac=ach / HBM_PEAK_GBS, algorithmic_bytes_per_read=per_read,
+                                                  reference_walk_bytes_per_read=ab["locate"], avg_launch_ms=avg_ms)
+                out["work_per_read"] = ab["counters"]
+                cw = ab["counters"]
+                # SURVEY.md s8d's path-level figure: pairs/s x algorithmic bytes per pair / HBM peak, bytes per read =
+                # 64 (E1 + 2 E2) + (64 S + 8 N_sa) + L/4 + 88 N_reg, all counted by the instrumented restatement on a sample of the same reads
+                per_read = 64.0 * (cw["ext_same_block"] + 2 * cw["ext_two_block"]) + 64.0 * cw["sa_lf_steps"] + 8.0 * cw["sa_lookups"] + float(np.mean(rs.lens)) / 4 + 88.0 * cw["n_regs"]
+                out["roofline_path"] = dict(definition="SURVEY.md s8d: pairs/s x algorithmic bytes per pair / HBM peak; bytes per read = 64(E1+2E2) + 64 S + 8 N_sa + L/4 + 88 N_reg "
+                                                       "(the reference's own walks, incl. its suffix-array sample every 32nd row)",
+                                            algorithmic_bytes_per_pair=2 * per_read, achieved=value * 2 * per_read / 1e9, peak=HBM_PEAK_GBS, unit="GB/s",
+                                            frac=value * 2 * per_read / 1e9 / HBM_PEAK_GBS)
+                # Smith-Waterman kernels: cell updates per second (the reference's cells, counted by the restatement: band cells of ksw_extend2,
+                # query x window cells of both ksw_u8 passes, band cells of ksw_global2) against the VALU; instruction counters from the committed
+                # rocprofv3 --pmc pass of this command (profiles/r03/sw_counters_<workload>.json, tools/prof_summary.py), null when none is committed
+                swc = {}
+                rel_sw = os.path.join("profiles", "r03", "sw_counters_%s.json" % args.workload)
+                if os.path.exists(os.path.join(ROOT, rel_sw)):
+                    swc = json.load(open(os.path.join(ROOT, rel_sw)))
+                sw = {}
+                for key, kern, cells_key, what in (("extend", "extend", "cells_extend", "ksw_extend2 band cells (k_extend_g16)"), ("sw_u8", "sw_u8", "cells_u8", "ksw_u8 cells, both passes (k_sw_u8_g16)"),
+                                                   ("reg2aln_nw", "reg2aln_nw", "cells_global", "ksw_global2 band cells (k_reg2aln_nw_g16)")):
+                    cells_step = cw[cells_key] * 2.0 * rs.n_pairs
+                    e = dict(cells=what, cells_per_read=cw[cells_key])
+                    if kern in ktimes and ktimes[kern]["ms"] > 0:
+                        e["gcups_timed"] = cells_step * args.steps / (ktimes[kern]["ms"] * 1e-3) / 1e9
+                    if kern in ktimes_alone and ktimes_alone[kern]["ms"] > 0:
+                        e["gcups_alone"] = cells_step / (ktimes_alone[kern]["ms"] * 1e-3) / 1e9
+                    e.update(swc.get(kern, dict(valu_busy=None, lane_ops_per_cell=None, lds_insts_per_valu=None)))
+                    sw[key] = e
+                out["roofline_sw"] = dict(kernels=sw, bound="valu", counters_source=rel_sw if swc else None,
+                                          peak_note="gfx950: 256 CUs x 4 SIMDs; valu_busy = rocprofv3's VALUBusy (SQ_ACTIVE_INST_VALU x 4 / SIMDs / cycles at %.1f GHz); "
+                                                    "lane_ops_per_cell = SQ_INSTS_VALU x 64 / reference cells; max-plus DP, no MFMA" % 2.4)
+                if "roofline" in out:   # what the committed counters say the roofline kernel is bound by
+                    rc = swc.get("seed_bwd")
+                    if rc and rc.get("valu_busy") is not None:
+                        out["roofline"]["valu_busy"] = rc["valu_busy"]
+                        if rc["valu_busy"] >= 0.6 and in_hbm:
+                            out["roofline"]["bound"] = "valu"
+                            out["roofline"]["bound_note"] += "; the kernel's vector instructions keep the SIMDs busy %.0f %% of its time (VALUBusy, committed --pmc pass): instruction issue, not HBM, bounds it; frac stays the HBM-roofline figure the metric asks for" % (100 * rc["valu_busy"])
+            except Exception as e:  # the roofline needs the oracle library; never fail the throughput line over it
+                log("roofline skipped:", repr(e))
+            tot = sum(v["ms"] for v in ktimes.values()) or 1.0
+            out["kernel_ms_per_step"] = {k: round(v["ms"] / args.steps, 3) for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1]["ms"])}
+            out["kernel_share"] = {k: round(v["ms"] / tot, 4) for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1]["ms"])}
+            tot_a = sum(v["ms"] for v in ktimes_alone.values()) or 1.0
+            out["kernel_ms_per_step_alone"] = {k: round(v["ms"], 3) for k, v in sorted(ktimes_alone.items(), key=lambda kv: -kv[1]["ms"])}
+            out["kernel_share_alone"] = {k: round(v["ms"] / tot_a, 4) for k, v in sorted(ktimes_alone.items(), key=lambda kv: -kv[1]["ms"])}
+            book = ("chain", "chain_heavy", "ext_step", "rescue_step", "rescue_heavy", "dedup", "dedup_heavy", "scan")
+            out["bookkeeping_share"] = dict(kernels=list(book), overlapped=round(sum(ktimes.get(k, {"ms": 0.0})["ms"] for k in book) / tot, 4),
+                                            alone=round(sum(ktimes_alone.get(k, {"ms": 0.0})["ms"] for k in book) / tot_a, 4),
+                                            note="list bookkeeping (chaining, extension state machines, rescue replay, de-duplication, scans) as a share of the "
+                                                 "summed kernel time; round 1: 0.31 overlapped on the chr20-size workload")
+            out["kernel_share_note"] = ("kernel_share: elapsed time per launch (HIP events on the launch stream) summed over the timed region, where the "
+                                        "streams of %d device batches overlap -- a launch that shares or waits for CUs counts for as long as it is in flight, "
+                                        "so one-wavefront tails (rescue_heavy, chain_heavy) weigh far more than the resources they hold; "
+                                        "kernel_share_alone: one step's batches run one after the other after the timed region, every launch alone on the chip"
+                                        % len(batches))
         out["rounds"] = dict(ext=max(c["ext_rounds"] for c in counts), rescue=max(c["rescue_rounds"] for c in counts),
                              ext_dp_per_pair=sum(c["n_ext"] for c in counts) / rs.n_pairs, sw_per_pair=sum(c["n_sw"] for c in counts) / rs.n_pairs,
                              regs_per_read=sum(c["n_regs"] for c in counts) / (2.0 * rs.n_pairs))
@@ -729,11 +780,13 @@ def main():
             if not same:
                 parity_failed = "boundary pass (arx_batch_reset / fetch_into) differs from the resident run on the first device batch"
         out["parity_ok"] = None if parity_failed is None else False
-        if world != 1:
+        if not args.full:
+            out["parity_skipped"] = "the CPU leg and the parity gate run under --full"
+        elif world != 1:
             out["parity_skipped"] = "N > 1: the CPU leg and the parity gate run on the N = 1 line only"
         elif args.no_cpu_baseline:
             out["parity_skipped"] = "--no-cpu-baseline"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cores = os.cpu_count() or 1
             n_sample = args.cpu_sample or min(rs.n_pairs, 2000 * cores)
             _n, offs, _l, _a, l_pac = ref.contigs()
@@ -772,7 +825,7 @@ def main():
         # End to end (SURVEY.md s8d "reported separately"): the same read set as barcode-sorted FASTQ files on disk -> arx_feeder -> the path ->
         # arx_recbuf (AppendBam's record logic) -> arx_bam (BGZF), the loop of Arachne() (aligner.go:335-371, bamwriter.go:615-658) as
         # arachne_amd/e2e.py drives it through the C ABI; one worker thread per file pair.  Never `value`.
-        if args.end_to_end and world == 1 and not args.no_rfa:
+        if args.full and args.end_to_end and world == 1 and not args.no_rfa:
             try:
                 from arachne_amd import e2e
                 import shutil
@@ -816,6 +869,64 @@ def main():
     if rank == 0 and parity_failed:
         log("PARITY MISMATCH between the GPU path and the CPU path:", parity_failed)
         sys.exit(1)
+
+
+DUMP_SEED = 20251016
+DUMP_READS = 16384                 # reads in the sample (fewer when the workload has fewer)
+DUMP_MAX_BYTES = 60 << 20          # the sample is halved until its arrays fit
+
+
+def dump_outputs(out_dir, ref, batches, with_cands=True):
+    """What the last timed step handed its caller, for a fixed, seeded sample of the reads (the same reads whatever the results):
+    per sampled read its regions (REG_DTYPE fields as columns), alignment records (ALN_DTYPE), CIGAR operations and placed candidates
+    with MAPQ (CAND_DTYPE), as DIR/<name>.npy in float64 (every field is exact in it).  The offsets of a read's rows are the running sums
+    of reg_count / cand_count, its CIGAR operations follow each other in the order of its alignment records (n_cigar of each)."""
+    from arachne_amd import api
+    fetched = []
+    for b in batches:
+        r = b.fetch()
+        if with_cands:
+            r["cand_off"] = np.zeros(b.n_reads + 1, dtype=np.int32)
+            r["cands"] = np.zeros(b._n_cands, dtype=api.CAND_DTYPE)
+            ref._check(ref.lib.arx_batch_rfa_fetch(ref.h, b.h, r["cand_off"].ctypes.data, r["cands"].ctypes.data))
+        fetched.append(r)
+    first = np.cumsum([0] + [b.n_reads for b in batches])
+    order = np.random.default_rng(DUMP_SEED).permutation(int(first[-1]))
+
+    def cols(rows, dt):
+        return np.stack([rows[f].astype(np.float64) for f in dt.names], axis=1) if len(rows) else np.zeros((0, len(dt.names)))
+
+    n = min(DUMP_READS, len(order))
+    while True:
+        pick = np.sort(order[:n])
+        res = dict(read_index=[], reg_count=[], regs=[], alns=[], cigars=[], cand_count=[], cands=[])
+        for g in pick:
+            k = int(np.searchsorted(first, g, side="right")) - 1
+            r, i = fetched[k], int(g - first[k])
+            r0, r1 = int(r["reg_off"][i]), int(r["reg_off"][i + 1])
+            al = r["alns"][r0:r1]
+            res["read_index"].append(g)
+            res["reg_count"].append(r1 - r0)
+            res["regs"].append(cols(r["regs"][r0:r1], api.REG_DTYPE))
+            res["alns"].append(cols(al, api.ALN_DTYPE))
+            res["cigars"].extend(r["cigars"][int(a["cigar_off"]):int(a["cigar_off"]) + int(a["n_cigar"])] for a in al)
+            if with_cands:
+                c0, c1 = int(r["cand_off"][i]), int(r["cand_off"][i + 1])
+                res["cand_count"].append(c1 - c0)
+                res["cands"].append(cols(r["cands"][c0:c1], api.CAND_DTYPE))
+        arrays = dict(read_index=np.array(res["read_index"], dtype=np.float64), reg_count=np.array(res["reg_count"], dtype=np.float64),
+                      regs=np.concatenate(res["regs"]), alns=np.concatenate(res["alns"]),
+                      cigars=np.concatenate(res["cigars"] or [np.zeros(0)]).astype(np.float64))
+        if with_cands:
+            arrays["cand_count"] = np.array(res["cand_count"], dtype=np.float64)
+            arrays["cands"] = np.concatenate(res["cands"])
+        if sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES or n == 1:
+            break
+        n = max(1, n // 2)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs of the last timed step: {n} sampled reads, {len(arrays['regs'])} regions written to {out_dir}")
 
 
 def refdrv_slice(out, n_reads):

@@ -23,7 +23,7 @@ def _free_port():
 
 def _bench(tmp, n):
     args = ["bench.py", "--gpus", str(n), "--steps", "1", "--warmup", "0", "--lib", SIM, "--backend", "gloo", "--genome-len", "300000",
-            "--barcodes", "3", "--pairs-per-barcode", "40", "--chunk-pairs", "80", "--cache", str(tmp), "--no-cpu-baseline", "--scatter-steps", "1"]
+            "--barcodes", "3", "--pairs-per-barcode", "40", "--chunk-pairs", "80", "--cache", str(tmp), "--no-cpu-baseline", "--scatter-steps", "1", "--full"]
     if n == 1:
         cmd = [sys.executable] + args
     else:

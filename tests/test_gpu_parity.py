@@ -60,29 +60,48 @@ def test_ragged_and_degenerate_reads(env):
     parity.check_final(ref.mem_mate_sw(flat, lens), o.batch(flat, lens))
 
 
+NASTY_SEEDS = (21, 22, 23)
+
+
+def nasty_inputs(seed):
+    """The seeded genome and reads of a fresh nasty workload (tests/golden/make_ref_live_golden.py runs the reference on the same ones)."""
+    g = workloads.nasty_genome(seed, contig_lens=(200000, 120000, 50000), alt_contigs=2)
+    rs = workloads.nasty_reads(seed, g, n_barcodes=8, pairs_per_barcode=500)
+    return g, rs
+
+
 @pytest.mark.parametrize("seed,no_ahead,sw_filter", [(21, False, False), (22, False, False), (22, True, False), (21, False, True), (23, False, True)])
 def test_fresh_nasty_workload_matches_oracle_and_reference(built, seed, no_ahead, sw_filter, monkeypatch):
     """no_ahead: every rescue SW takes the one-at-a-time path instead of the queued-ahead launch (pipeline.h stage_rescue).
-    sw_filter: rescue alignments that provably stay below min_seed_len never reach the DP (k_sw_filter_g16; off by default)."""
+    sw_filter: rescue alignments that provably stay below min_seed_len never reach the DP (k_sw_filter_g16; off by default).
+    The reference: its C core live where oracle/_ref/libbwaref.so travelled, else its index digests and results for the same
+    workload (tests/golden/ref_nasty<seed>_v1.npz)."""
+    import hashlib
     import oradrv
     if no_ahead:
         monkeypatch.setenv("ARX_RESCUE_NO_AHEAD", "1")
     if sw_filter:
         monkeypatch.setenv("ARX_SW_FILTER", "1")
-    g = workloads.nasty_genome(seed, contig_lens=(200000, 120000, 50000), alt_contigs=2)
-    rs = workloads.nasty_reads(seed, g, n_barcodes=8, pairs_per_barcode=500)
+    g, rs = nasty_inputs(seed)
     tmp = tempfile.mkdtemp(prefix="arx_gpu_nasty_")
     prefix = os.path.join(tmp, "g.fa")
     g.write_fasta(prefix)
     g.write_alt(prefix + ".alt")
-    if not refdrv.available():
-        pytest.skip("oracle/_ref/libbwaref.so did not travel; index builder of the reference unavailable")
-    r = refdrv.Ref()
-    r.index_build(prefix, prefix)
-    r.open(prefix)
+    if refdrv.available():
+        r = refdrv.Ref()
+        r.index_build(prefix, prefix)
+        r.open(prefix)
+        ref_out = r.batch(rs.seqs, rs.lens, n_threads=8)
+    else:   # the product's builder writes the reference's index byte for byte (test_index_build*.py)
+        z = np.load(os.path.join(workloads.GOLDEN_DIR, "ref_nasty%d_v1.npz" % seed))
+        api.index_build(prefix, prefix)
+        for ext in ("bwt", "sa", "pac", "ann", "amb"):
+            with open(prefix + "." + ext, "rb") as f:
+                assert hashlib.sha256(f.read()).hexdigest() == str(z["nasty%d_idx_%s" % (seed, ext)]), ext
+        ref_out = {k: z["nasty%d_%s" % (seed, k)].astype(np.int64 if k != "cigars" else np.uint32) for k in ("reg_off", "regs", "alns", "cigars")}
     ref = api.load_reference(prefix, 0)
     dev = ref.mem_mate_sw(rs.seqs, rs.lens)
-    parity.check_final(dev, r.batch(rs.seqs, rs.lens, n_threads=8))
+    parity.check_final(dev, ref_out)
     parity.check_final(dev, oradrv.Oracle(prefix).batch(rs.seqs, rs.lens, n_threads=8))
     assert len(dev["regs"]) > 5000
     ref.close()

@@ -1,6 +1,6 @@
 """The 16-bit element size of ksw_align2 (ksw.c:232-334): mem_matesw takes it for mates of 250 bases and more (bwamem_pair.c:150).  CPU
-tests: the oracle's restatement against the fixture the compiled reference wrote (tests/golden/ksw_i16_v1.npz, make_i16_golden.py) and, where
-oracle/_ref is present, against the reference live; the device logic (host-compiled test double) against the same fixture."""
+tests: the oracle's restatement against the fixtures the compiled reference wrote (tests/golden/ksw_i16_v1.npz, make_i16_golden.py;
+tests/golden/ref_live_v1.npz, make_ref_live_golden.py) and, where oracle/_ref is present, against the reference live; the device logic (host-compiled test double) against the same fixture."""
 import os
 import subprocess
 import tempfile
@@ -103,10 +103,8 @@ def test_device_logic_refuses_256_bases(gold):
     ref.close()
 
 
-@pytest.mark.skipif(not refdrv.available(), reason="oracle/_ref/libbwaref.so not built")
-def test_oracle_ksw_i16_against_the_reference_live(gold):
-    z, o, prefix = gold
-    r = refdrv.Ref(prefix)
+def live_cases():
+    """The seeded (query, target, xtra) calls of the live comparison, in order (make_ref_live_golden.py stores the reference's results)."""
     rng = np.random.default_rng(77)
     for it in range(400):
         ql = int(rng.integers(1, 256))
@@ -117,5 +115,20 @@ def test_oracle_ksw_i16_against_the_reference_live(gold):
         if it % 7 == 0:
             t = np.delete(t, slice(len(t) // 2, len(t) // 2 + int(rng.integers(1, 12))))
         for x in (KSW_XSUBO | KSW_XSTART | 19, KSW_XSUBO | 40):
-            assert (o.ksw_align2(q, t, x) == r.ksw_align2(q, t, x)).all(), (it, x)
-    r.close()
+            yield it, q, t, x
+
+
+def test_oracle_ksw_i16_against_the_reference_live(gold):
+    """Against the reference's results for the same calls (tests/golden/ref_live_v1.npz) and, where oracle/_ref is present, live."""
+    z, o, prefix = gold
+    want = np.load(os.path.join(workloads.GOLDEN_DIR, "ref_live_v1.npz"))["ksw_live"]
+    r = refdrv.Ref(prefix) if refdrv.available() else None
+    n = 0
+    for n, (it, q, t, x) in enumerate(live_cases()):
+        got = o.ksw_align2(q, t, x)
+        assert (got == want[n]).all(), (it, x)
+        if r is not None:
+            assert (got == r.ksw_align2(q, t, x)).all(), (it, x)
+    assert n + 1 == len(want)
+    if r is not None:
+        r.close()

@@ -13,7 +13,7 @@ bash tools/gpu_profile.sh > $O/profile.log 2>&1; echo "profile rc=$?"; grep -E "
 if grep -rq "HSA_STATUS_ERROR" gpurun_out/prof/*.err; then echo "GPU FAULT in the profile passes"; exit 1; fi
 for w in grch38 vxmix chr20 alt_repeat; do
   extra=""; [ $w = alt_repeat ] && extra="--steps 6 --cpu-sample 60000"
-  timeout -k 10 700 python bench.py --workload $w $extra > $O/bench_$w.json 2> $O/bench_$w.err; echo "$w rc=$?"
+  timeout -k 10 700 python bench.py --full --workload $w $extra > $O/bench_$w.json 2> $O/bench_$w.err; echo "$w rc=$?"
   if grep -q "HSA_STATUS_ERROR\|out of memory" $O/bench_$w.err; then echo "GPU FAULT / OOM in $w"; tail -n 3 $O/bench_$w.err; exit 1; fi
 done
 python3 - <<'PY'

@@ -64,7 +64,7 @@ try:
         raw = sum(pmc[k]["FETCH_SIZE"] for k in names if k in pmc and "FETCH_SIZE" in pmc[k])
         disp = max(pmc[k]["dispatches_pmc_fetch"] for k in names if k in pmc)
         return raw * 1024.0 * cal / (disp / launches_per_batch) / reads_per_launch
-    traffic = dict(source="rocprofv3 --pmc FETCH_SIZE over `python3 " + "bench.py --no-cpu-baseline --boundary-steps 0" + "` (its own pass, tools/gpu_profile.sh); FETCH_SIZE x 1024 x calibration factor, per seeding-stage run of %d reads" % reads_per_launch,
+    traffic = dict(source="rocprofv3 --pmc FETCH_SIZE over `python3 " + "bench.py --full --no-cpu-baseline --boundary-steps 0" + "` (its own pass, tools/gpu_profile.sh); FETCH_SIZE x 1024 x calibration factor, per seeding-stage run of %d reads" % reads_per_launch,
                    calibration=res.get("fetch_calibration"), workload=bp["config"]["workload"],
                    bwd_fabric_bytes_per_read=per_read(["k_seed_bwd_g", "k_seed_bwd_g<16>", "k_seed_bwd_g<32>", "k_seed_bwd_g<64>", "k_seed_bwd", "k_seed_bwd2", "k_seed_bwd_wave", "KSeedBwdTail"], 2.0), fwd_fabric_bytes_per_read=per_read(["k_seed_fwd1", "k_seed_fwd2"], 1.0),
                    strat_fabric_bytes_per_read=per_read(["k_strat_dyn"], 1.0), locate_fabric_bytes_per_read=per_read(["k_locate_dyn", "KLocate"], 1.0),
