@@ -111,6 +111,21 @@ def _load(path):
     return lib
 
 
+# the DP self-test entries (include/arachne_amd.h), bound when first called: the library's test double need not export them
+_SELFTEST_ARGS = {
+    "arx_selftest_extend": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
+    "arx_selftest_rescue_sw": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
+    "arx_selftest_gen_cigar": [C.c_int32, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
+}
+
+
+def _selftest_fn(lib, name):
+    fn = getattr(lib, name)
+    fn.argtypes = _SELFTEST_ARGS[name]
+    return fn
+
+
 def selftest_wave_sort(n_cases: int, seed: int = 1, device: int = 0, lib_path: str = LIB_PATH) -> int:
     """klib's introsort as the wavefront kernels reproduce it against the one-thread original on random index arrays -> arrays that differ."""
     lib = _load(lib_path)
@@ -119,6 +134,70 @@ def selftest_wave_sort(n_cases: int, seed: int = 1, device: int = 0, lib_path: s
     if rc != 0:
         raise ArachneError("arx_selftest_wave_sort: code %d" % rc)
     return int(bad.value)
+
+
+def _arr(a, dt, shape=None):
+    a = np.ascontiguousarray(a, dtype=dt)
+    if shape is not None and a.shape != shape:
+        raise ValueError(f"expected shape {shape}, got {a.shape}")
+    return a
+
+
+def selftest_extend(pac, l_pac: int, bases, tasks, mode: int = 0, grid_cap: int = 0, device: int = 0, lib_path: str = LIB_PATH) -> np.ndarray:
+    """ksw_extend2 by the extension kernels (include/arachne_amd.h: arx_selftest_extend).  tasks: n x 8 (tpos, qoff, qlen, tlen, qdir, tdir, w, h0);
+    mode 0 per-class launches, 1 the merged launch, 2 round 2's kernel, 3 the one-thread form -> n x 6 (score, qle, tle, gtle, gscore, max_off)."""
+    lib = _load(lib_path)
+    pac, bases = _arr(pac, np.uint8), _arr(bases, np.uint8)
+    tasks = _arr(tasks, np.int64).reshape(-1, 8)
+    if len(pac) < (l_pac + 3) // 4:
+        raise ValueError("pac shorter than l_pac")
+    out = np.zeros((len(tasks), 6), dtype=np.int32)
+    rc = _selftest_fn(lib, "arx_selftest_extend")(device, pac.ctypes.data, l_pac, bases.ctypes.data, len(bases), len(tasks), tasks.ctypes.data, mode, grid_cap, out.ctypes.data)
+    if rc != 0:
+        raise ArachneError("arx_selftest_extend: code %d" % rc)
+    return out
+
+
+def selftest_rescue_sw(pac, l_pac: int, mates, mate_off, mate_len, windows, max_len: int, filter: bool = False, sw_simple: bool = False, grid_cap: int = 0,
+                       device: int = 0, lib_path: str = LIB_PATH) -> np.ndarray:
+    """The rescue SW by its kernels (arx_selftest_rescue_sw): forward mates, windows n x 2 (rb, re) -> n x 7 (score, te, qe, score2, te2, tb, qb)."""
+    lib = _load(lib_path)
+    pac, mates = _arr(pac, np.uint8), _arr(mates, np.uint8)
+    n = len(mate_len)
+    mate_off, mate_len, windows = _arr(mate_off, np.int32, (n,)), _arr(mate_len, np.int32, (n,)), _arr(windows, np.int64, (n, 2))
+    if len(pac) < (l_pac + 3) // 4:
+        raise ValueError("pac shorter than l_pac")
+    out = np.zeros((n, 7), dtype=np.int32)
+    rc = _selftest_fn(lib, "arx_selftest_rescue_sw")(device, pac.ctypes.data, l_pac, mates.ctypes.data, len(mates), n, mate_off.ctypes.data, mate_len.ctypes.data,
+                                    windows.ctypes.data, max_len, int(filter), int(sw_simple), grid_cap, out.ctypes.data)
+    if rc != 0:
+        raise ArachneError("arx_selftest_rescue_sw: code %d" % rc)
+    return out
+
+
+def selftest_gen_cigar(queries, targets, w, klass: int, cap=None, cig_w: int = 0, device: int = 0, lib_path: str = LIB_PATH):
+    """bwa_gen_cigar2 by the CIGAR kernel of band class klass (0..4; 5: the <1,16> kernel) on oriented (query, target) pairs, band w each
+    (arx_selftest_gen_cigar) -> (n x 4 (score, n_cigar, NM, punted), n x cig_w CIGAR words)."""
+    lib = _load(lib_path)
+    n = len(queries)
+    assert len(targets) == n
+    ql = np.array([len(x) for x in queries], dtype=np.int32)
+    tl = np.array([len(x) for x in targets], dtype=np.int32)
+    qo = np.concatenate([[0], np.cumsum(ql)[:-1]]).astype(np.int32) if n else np.zeros(0, np.int32)
+    to = np.concatenate([[0], np.cumsum(tl)[:-1]]).astype(np.int32) if n else np.zeros(0, np.int32)
+    qs = _arr(np.concatenate(list(queries)) if n else np.zeros(1), np.uint8)
+    ts = _arr(np.concatenate(list(targets)) if n else np.zeros(1), np.uint8)
+    w = _arr(w, np.int32, (n,))
+    if cig_w <= 0:
+        cig_w = 1024
+    cap = _arr(np.full(n, cig_w) if cap is None else cap, np.int32, (n,))
+    out = np.zeros((n, 4), dtype=np.int32)
+    cig = np.zeros((n, cig_w), dtype=np.uint32)
+    rc = _selftest_fn(lib, "arx_selftest_gen_cigar")(device, n, qs.ctypes.data, qo.ctypes.data, ql.ctypes.data, ts.ctypes.data, to.ctypes.data, tl.ctypes.data,
+                                    w.ctypes.data, cap.ctypes.data, cig_w, klass, out.ctypes.data, cig.ctypes.data)
+    if rc != 0:
+        raise ArachneError("arx_selftest_gen_cigar: code %d" % rc)
+    return out, cig
 
 
 def index_build(fasta: str, prefix: str, lib_path: str = LIB_PATH) -> None:

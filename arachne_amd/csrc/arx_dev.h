@@ -41,7 +41,7 @@ constexpr int MAX_READ_LEN = 255;   // 249 until round 3: mates of 250 bases and
 // Extensions are binned by query length so that a wavefront's four 16-lane groups run the same register tiling
 // (hip_sw_coop.h: C columns per lane, 16 * C > qlen; C = 2, 3, 4, 6, 8, 10, 16)
 constexpr int EXT_CLASSES = 7;
-ARX_DEVI int ext_class(int qlen) { return qlen < 32 ? 0 : qlen < 48 ? 1 : qlen < 64 ? 2 : qlen < 96 ? 3 : qlen < 128 ? 4 : qlen < 160 ? 5 : 6; }
+ARX_HDI int ext_class(int qlen) { return qlen < 32 ? 0 : qlen < 48 ? 1 : qlen < 64 ? 2 : qlen < 96 ? 3 : qlen < 128 ? 4 : qlen < 160 ? 5 : 6; }
 constexpr int CAP_INTV = 256;       // SMEM intervals kept per read (overflow is reported, never truncated silently)
 
 // error bits raised by kernels into Pipeline::d_err

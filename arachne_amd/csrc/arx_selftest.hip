@@ -1,0 +1,194 @@
+// arx_selftest.hip -- the self-test entries of the three DP kernel families (include/arachne_amd.h: arx_selftest_extend,
+// arx_selftest_rescue_sw, arx_selftest_gen_cigar).  They take plain host arrays, build what the pipeline would hand the kernels (an IndexView
+// with only the packed text set, class-binned extension tasks, rescue tasks with their mates, staged CIGAR regions) and launch the production
+// code through HipRT, so that tests/test_dp_kernels_gpu.py can compare every output field with ksw_extend2 / ksw_align2 / ksw_global2.
+// Its own unit so that the unit of the list-bookkeeping kernels does not grow.
+#include <climits>
+#include <vector>
+#include "../../include/arachne_amd.h"
+#include "hip_rt.h"
+#include "pipeline.h"
+
+namespace arx {
+
+// the target (and query) of a region staged the way k_reg2aln_nw_g16 stages them, then bwa_gen_cigar2 by the class kernel's tilings
+template <int LO, int HI>
+static __global__ void __launch_bounds__(64) k_selftest_gen_cigar(const uint8_t *q, const int32_t *q_off, const int32_t *qlen, const uint8_t *t,
+                                                                  const int32_t *t_off, const int32_t *tlen, const int32_t *w, const int32_t *cap,
+                                                                  int cig_w, uint8_t *z, const int64_t *z_off, int n, int32_t *out, uint32_t *cig)
+{
+	__shared__ uint8_t lds_q[4][NW_Q_CAP];
+	__shared__ uint8_t lds_t[4][NW_T_CAP];
+	__shared__ __attribute__((aligned(16))) uint8_t lds_z[4][NW_ZL_BYTES];
+	const int grp = threadIdx.x >> 4, l = threadIdx.x & 15;
+	for (int i = blockIdx.x * 4 + grp; i < n; i += gridDim.x * 4) {
+		NwSeg sg; sg.q = lds_q[grp]; sg.t = lds_t[grp]; sg.qlen = qlen[i]; sg.tlen = tlen[i];
+		for (int k = l; k < sg.qlen; k += 16) lds_q[grp][k] = q[q_off[i] + k];
+		for (int k = l; k < sg.tlen; k += 16) lds_t[grp][k] = t[t_off[i] + k];
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+		__builtin_amdgcn_wave_barrier();
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+		int score = 0, n_cigar = 0, NM = -1;
+		const bool done = gen_cigar2_g16<LO, HI>(sg, w[i], z + z_off[i], lds_z[grp], cig + (size_t)i * cig_w, cap[i], &score, &n_cigar, &NM);
+		if (l == 0) { out[4 * i] = done ? score : 0; out[4 * i + 1] = done ? n_cigar : 0; out[4 * i + 2] = done ? NM : -1; out[4 * i + 3] = done ? 0 : 1; }
+		__builtin_amdgcn_wave_barrier(); // the LDS rows are reused by the group's next region
+	}
+}
+
+static bool one_strand(int64_t a, int64_t b, int64_t l_pac) // both ends inside the same strand of [0, 2 * l_pac)
+{
+	if (a < 0 || b < 0 || a >= 2 * l_pac || b >= 2 * l_pac) return false;
+	return (a < l_pac) == (b < l_pac);
+}
+
+static IndexView pac_view(HipRT &rt, const uint8_t *pac, int64_t l_pac)
+{
+	IndexView ix = IndexView();
+	const size_t bytes = (size_t)((l_pac + 3) / 4);
+	uint8_t *d = rt.alloc<uint8_t>(bytes);
+	rt.h2d(d, pac, bytes);
+	ix.pac = d; ix.l_pac = l_pac;
+	return ix;
+}
+
+} // namespace arx
+
+extern "C" int arx_selftest_extend(int32_t device, const uint8_t *pac, int64_t l_pac, const uint8_t *bases, int64_t n_bases, int32_t n, const int64_t *task8,
+                                   int32_t mode, int32_t grid_cap, int32_t *res6)
+{
+	using namespace arx;
+	if (n < 0 || mode < 0 || mode > 3 || l_pac < 1 || n_bases < 0 || n_bases > INT_MAX || (n > 0 && (!pac || !bases || !task8 || !res6))) return ARX_E_ARG;
+	std::vector<ExtTask> tk((size_t)EXT_CLASSES * (n + 1));
+	int32_t n_class[EXT_CLASSES] = {0};
+	for (int i = 0; i < n; ++i) {
+		const int64_t *r = task8 + 8 * (size_t)i;
+		const int64_t tpos = r[0], qoff = r[1], qlen = r[2], tlen = r[3], qdir = r[4], tdir = r[5], w = r[6], h0 = r[7];
+		if (qlen < 1 || qlen > MAX_READ_LEN || (qdir != 1 && qdir != -1) || (tdir != 1 && tdir != -1)) return ARX_E_ARG;
+		const int64_t qlast = qoff + (qlen - 1) * qdir;
+		if (qoff < 0 || qoff >= n_bases || qlast < 0 || qlast >= n_bases) return ARX_E_ARG;
+		if (tlen < 1 || tlen > 2 * l_pac || !one_strand(tpos, tpos + (tlen - 1) * tdir, l_pac)) return ARX_E_ARG;
+		if (w < 1 || w > INT_MAX || h0 < 1 || h0 > MAX_READ_LEN * OPT_A) return ARX_E_ARG;
+		ExtTask t;
+		t.tpos = tpos; t.owner = i; t.qoff = (int32_t)qoff; t.qlen = (int32_t)qlen; t.tlen = (int32_t)tlen;
+		t.qdir = (int32_t)qdir; t.tdir = (int32_t)tdir; t.w = (int32_t)w; t.h0 = (int32_t)h0;
+		const int c = ext_class(t.qlen);
+		tk[(size_t)c * (n + 1) + n_class[c]++] = t; // stride-spaced class slots, as pipeline.h's stage_extend bins them
+	}
+	if (n == 0) return ARX_OK;
+	try {
+		HipRT rt;
+		if (!rt.init(device).empty()) return ARX_E_DEVICE;
+		rt.timing = false;
+		rt.ext_merge_below = mode == 1 ? INT_MAX : 0;
+		rt.ext_old = mode == 2;
+		rt.sw_simple = mode == 3;
+		if (grid_cap > 0) { rt.n_cu = 1; rt.coop_bpc = grid_cap; rt.bpc = grid_cap; } // (the one-thread form: max_blocks() = grid_cap)
+		KExtend f{pac_view(rt, pac, l_pac), rt.alloc<uint8_t>((size_t)n_bases + 1), rt.alloc<ExtTask>(tk.size()), rt.alloc<ExtRes>((size_t)n)};
+		rt.h2d((void *)f.bases, bases, (size_t)n_bases);
+		rt.h2d((void *)f.tasks, tk.data(), tk.size() * sizeof(ExtTask));
+		rt.memset_bytes(f.res, 0x80, (size_t)n * sizeof(ExtRes)); // a task that is never run shows up as a mismatch
+		rt.run_extend("selftest_extend", n_class, n + 1, f);
+		ARX_HIP_CHECK(hipStreamSynchronize(rt.stream));
+		static_assert(sizeof(ExtRes) == 6 * sizeof(int32_t), "ExtRes is six int32");
+		rt.d2h(res6, f.res, (size_t)n * sizeof(ExtRes));
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}
+
+extern "C" int arx_selftest_rescue_sw(int32_t device, const uint8_t *pac, int64_t l_pac, const uint8_t *mates, int64_t n_bases, int32_t n, const int32_t *mate_off,
+                                      const int32_t *mate_len, const int64_t *win2, int32_t max_len, int32_t filter, int32_t sw_simple, int32_t grid_cap, int32_t *res7)
+{
+	using namespace arx;
+	if (n < 0 || l_pac < 1 || n_bases < 0 || n_bases > INT_MAX || max_len < 1 || max_len > MAX_READ_LEN) return ARX_E_ARG;
+	if (n > 0 && (!pac || !mates || !mate_off || !mate_len || !win2 || !res7)) return ARX_E_ARG;
+	std::vector<SwTask> tk((size_t)n);
+	for (int i = 0; i < n; ++i) {
+		const int64_t rb = win2[2 * (size_t)i], re = win2[2 * (size_t)i + 1];
+		if (mate_len[i] < 1 || mate_len[i] > max_len || mate_off[i] < 0 || (int64_t)mate_off[i] + mate_len[i] > n_bases) return ARX_E_ARG;
+		if (re - rb < 1 || re - rb > SW_T_CAP || !one_strand(rb, re - 1, l_pac)) return ARX_E_ARG;
+		SwTask t;
+		t.rb = rb; t.re = re; t.pair = i >> 1; t.o = i & 1; t.slot = i; t.pad = 0; // read 2 * pair + o is mate i
+		tk[i] = t;
+	}
+	if (n == 0) return ARX_OK;
+	try {
+		HipRT rt;
+		if (!rt.init(device).empty()) return ARX_E_DEVICE;
+		rt.timing = false;
+		rt.sw_filter = filter ? 1 : 0;
+		rt.sw_filter_stats = 0;
+		rt.sw_simple = sw_simple != 0;
+		if (grid_cap > 0) { rt.n_cu = 1; rt.coop_bpc = grid_cap; rt.bpc = grid_cap; }
+		// the one-thread form keeps its mate, window and row maxima in per-slot scratch: one slot per thread of its grid
+		const int q_cap = (max_len + 15) & ~15, t_cap = SW_T_CAP;
+		const int slots = ((n + 63) / 64 < rt.max_blocks() ? (n + 63) / 64 : rt.max_blocks()) * 64;
+		KSwU8 f{pac_view(rt, pac, l_pac), rt.alloc<uint8_t>((size_t)n_bases + 1), rt.alloc<int32_t>((size_t)n), rt.alloc<int32_t>((size_t)n),
+		        rt.alloc<SwTask>((size_t)n), rt.alloc<U8Res>((size_t)n), rt.sw_simple ? rt.alloc<uint8_t>((size_t)slots * (q_cap + 2 * t_cap)) : nullptr, q_cap, t_cap};
+		rt.h2d((void *)f.bases, mates, (size_t)n_bases);
+		rt.h2d((void *)f.base_off, mate_off, (size_t)n * 4);
+		rt.h2d((void *)f.lens, mate_len, (size_t)n * 4);
+		rt.h2d((void *)f.tasks, tk.data(), tk.size() * sizeof(SwTask));
+		rt.memset_bytes(f.res, 0x80, (size_t)n * sizeof(U8Res));
+		rt.run_sw_u8("selftest_sw_u8", n, f, max_len);
+		ARX_HIP_CHECK(hipStreamSynchronize(rt.stream));
+		static_assert(sizeof(U8Res) == 7 * sizeof(int32_t), "U8Res is seven int32");
+		rt.d2h(res7, f.res, (size_t)n * sizeof(U8Res));
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}
+
+extern "C" int arx_selftest_gen_cigar(int32_t device, int32_t n, const uint8_t *q, const int32_t *q_off, const int32_t *qlen, const uint8_t *t, const int32_t *t_off,
+                                      const int32_t *tlen, const int32_t *w, const int32_t *cap, int32_t cig_w, int32_t klass, int32_t *out4, uint32_t *cigar)
+{
+	using namespace arx;
+	static const int HI[6] = {2, 4, 8, 16, 16, 16}; // columns per lane of the widest tiling each kernel holds: rows of 16 * HI bytes of traceback matrix
+	if (n < 0 || klass < 0 || klass > 5 || cig_w < 1) return ARX_E_ARG;
+	if (n > 0 && (!q || !q_off || !qlen || !t || !t_off || !tlen || !w || !cap || !out4 || !cigar)) return ARX_E_ARG;
+	std::vector<int64_t> z_off((size_t)n + 1, 0);
+	int64_t nq = 0, nt = 0;
+	for (int i = 0; i < n; ++i) {
+		if (qlen[i] < 1 || qlen[i] > NW_Q_CAP || tlen[i] < 1 || tlen[i] > NW_T_CAP || w[i] < 0 || cap[i] < 1 || cap[i] > cig_w) return ARX_E_ARG;
+		if (q_off[i] < 0 || t_off[i] < 0) return ARX_E_ARG;
+		nq = nq > (int64_t)q_off[i] + qlen[i] ? nq : (int64_t)q_off[i] + qlen[i];
+		nt = nt > (int64_t)t_off[i] + tlen[i] ? nt : (int64_t)t_off[i] + tlen[i];
+		z_off[i + 1] = z_off[i] + (((int64_t)tlen[i] * 16 * HI[klass] + 63) & ~(int64_t)63);
+	}
+	if (n == 0) return ARX_OK;
+	try {
+		HipRT rt;
+		if (!rt.init(device).empty()) return ARX_E_DEVICE;
+		uint8_t *dq = rt.alloc<uint8_t>((size_t)nq), *dt = rt.alloc<uint8_t>((size_t)nt), *dz = rt.alloc<uint8_t>((size_t)z_off[n] + 64);
+		int32_t *di = rt.alloc<int32_t>((size_t)n * 6), *dout = rt.alloc<int32_t>((size_t)n * 4);
+		int64_t *dzo = rt.alloc<int64_t>((size_t)n);
+		uint32_t *dcig = rt.alloc<uint32_t>((size_t)n * cig_w);
+		rt.h2d(dq, q, (size_t)nq); rt.h2d(dt, t, (size_t)nt);
+		const int32_t *src[6] = {q_off, qlen, t_off, tlen, w, cap};
+		for (int k = 0; k < 6; ++k) rt.h2d(di + (size_t)k * n, src[k], (size_t)n * 4);
+		rt.h2d(dzo, z_off.data(), (size_t)n * 8);
+		rt.memset_bytes(dout, 0x80, (size_t)n * 16);
+		rt.memset0(dcig, (size_t)n * cig_w * 4);
+		const int blocks = (n + 3) / 4 < rt.n_cu * 4 ? (n + 3) / 4 : rt.n_cu * 4;
+#define ARX_NW_SELFTEST(LO_, HI_) hipLaunchKernelGGL((k_selftest_gen_cigar<LO_, HI_>), dim3(blocks), dim3(64), 0, rt.stream, dq, di, di + n, dt, di + 2 * (size_t)n, \
+                                                    di + 3 * (size_t)n, di + 4 * (size_t)n, di + 5 * (size_t)n, cig_w, dz, dzo, n, dout, dcig)
+		switch (klass) { // the instantiations of HipRT::run_reg2aln_nw
+		case 0: ARX_NW_SELFTEST(1, 2); break;
+		case 1: ARX_NW_SELFTEST(2, 4); break;
+		case 2: ARX_NW_SELFTEST(4, 8); break;
+		case 3: ARX_NW_SELFTEST(8, 16); break;
+		case 4: ARX_NW_SELFTEST(16, 16); break;
+		default: ARX_NW_SELFTEST(1, 16); break;
+		}
+#undef ARX_NW_SELFTEST
+		ARX_HIP_CHECK(hipGetLastError());
+		ARX_HIP_CHECK(hipStreamSynchronize(rt.stream));
+		rt.d2h(out4, dout, (size_t)n * 16);
+		rt.d2h(cigar, dcig, (size_t)n * cig_w * 4);
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}

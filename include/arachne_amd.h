@@ -261,6 +261,37 @@ int arx_batch_debug_core(arx_ctx *ctx, arx_batch *b, int32_t *n_core, arx_reg *r
  * abound.  *n_bad = arrays on which the two differ. */
 int arx_selftest_wave_sort(int32_t device, int32_t n_cases, int64_t seed, int64_t *n_bad);
 
+/* self-tests of the three DP kernel families on plain host arrays (csrc/arx_selftest.hip; tests/test_dp_kernels_gpu.py): each entry
+ * uploads the tasks, launches the production code on them and returns one result row per task, in input order.  The reference text is
+ * passed in bwa's .pac layout (pac: (l_pac + 3) / 4 bytes, 2 bits per base, first base in the top bits); coordinates are doubled, so a
+ * position >= l_pac reads the reverse strand as the path does.  Input outside what the pipeline guarantees is refused with ARX_E_ARG before
+ * anything is launched.
+ *
+ * arx_selftest_extend: ksw_extend2 (end bonus 5, z-drop 100) by HipRT::run_extend.  task8: n rows of (tpos, qoff, qlen, tlen, qdir, tdir,
+ * w, h0); the query base j is bases[qoff + j * qdir], the target base i is at doubled coordinate tpos + i * tdir.  Contract: 1 <= qlen <= 255,
+ * qdir, tdir = +1 / -1, the query inside bases[0, n_bases), tlen >= 1 with the whole target on one strand of [0, 2 * l_pac), w >= 1,
+ * 1 <= h0 <= 255.  mode 0: one launch per query-length class, 1: all classes in one launch, 2: round 2's kernel (per class), 3: the
+ * one-thread form.  grid_cap > 0: at most that many workgroups per launch (the grid-stride loops then take several tasks per group).
+ * res6: n rows of (score, qle, tle, gtle, gscore, max_off).
+ *
+ * arx_selftest_rescue_sw: the rescue Smith-Waterman of mem_matesw (ksw_align2 of the reverse-complemented mate against the window, bwamem_pair.c:
+ * 150) by HipRT::run_sw_u8.  Mate k is mates[mate_off[k], + mate_len[k]) in forward orientation, its window [win2[2k], win2[2k + 1]).  Contract:
+ * 1 <= mate_len <= max_len <= 255, 1 <= window length <= 800, the window on one strand of [0, 2 * l_pac).  max_len picks the kernel as a batch's
+ * longest read does; filter = 1 runs the pre-filter in front; sw_simple = 1 the one-thread form.  res7: (score, te, qe, score2, te2, tb, qb);
+ * a task the pre-filter drops gets (0, -1, -1, -1, -1, -1, -1).
+ *
+ * arx_selftest_gen_cigar: bwa_gen_cigar2 on regions already oriented (query and target as ksw_global2 reads them) by the 16-lane CIGAR kernel of
+ * band class klass (0..4: <1,2> <2,4> <4,8> <8,16> <16,16> columns per lane), or 5 for the <1,16> kernel that takes the punted regions.  w: the
+ * band bwa_gen_cigar2 is called with.  Contract: 1 <= qlen <= 256, 1 <= tlen <= 1024, w >= 0, 1 <= cap[k] <= cig_w.  out4: (score, n_cigar,
+ * NM, punted); cigar: cig_w words per task.  punted = 1: the band needs a wider tiling than the kernel holds (nothing else is set); NM = -1 when
+ * n_cigar > cap. */
+int arx_selftest_extend(int32_t device, const uint8_t *pac, int64_t l_pac, const uint8_t *bases, int64_t n_bases, int32_t n, const int64_t *task8,
+                        int32_t mode, int32_t grid_cap, int32_t *res6);
+int arx_selftest_rescue_sw(int32_t device, const uint8_t *pac, int64_t l_pac, const uint8_t *mates, int64_t n_bases, int32_t n, const int32_t *mate_off,
+                           const int32_t *mate_len, const int64_t *win2, int32_t max_len, int32_t filter, int32_t sw_simple, int32_t grid_cap, int32_t *res7);
+int arx_selftest_gen_cigar(int32_t device, int32_t n, const uint8_t *q, const int32_t *q_off, const int32_t *qlen, const uint8_t *t, const int32_t *t_off,
+                           const int32_t *tlen, const int32_t *w, const int32_t *cap, int32_t cig_w, int32_t klass, int32_t *out4, uint32_t *cigar);
+
 /* per-kernel device time (HIP events on the launch stream), accumulated since the last reset */
 int arx_kernel_times(arx_ctx *ctx, int32_t cap, char *names, int32_t name_w, double *ms, int64_t *calls, int64_t *items);
 void arx_kernel_times_reset(arx_ctx *ctx, int32_t enable);

@@ -400,3 +400,26 @@ extern "C" long arx_test_text_match_back(unsigned seed, int iters)
 
 // the wavefront routines exist on the GPU only (include/arachne_amd.h): nothing to test here
 extern "C" int arx_selftest_wave_sort(int32_t, int32_t, int64_t, int64_t *n_bad) { if (n_bad) *n_bad = 0; return ARX_E_DEVICE; }
+extern "C" int arx_selftest_extend(int32_t, const uint8_t *, int64_t, const uint8_t *, int64_t, int32_t, const int64_t *, int32_t, int32_t, int32_t *) { return ARX_E_DEVICE; }
+extern "C" int arx_selftest_rescue_sw(int32_t, const uint8_t *, int64_t, const uint8_t *, int64_t, int32_t, const int32_t *, const int32_t *, const int64_t *, int32_t, int32_t,
+                                      int32_t, int32_t, int32_t *) { return ARX_E_DEVICE; }
+extern "C" int arx_selftest_gen_cigar(int32_t, int32_t, const uint8_t *, const int32_t *, const int32_t *, const uint8_t *, const int32_t *, const int32_t *, const int32_t *,
+                                      const int32_t *, int32_t, int32_t, int32_t *, uint32_t *) { return ARX_E_DEVICE; }
+
+// test entry: the one-thread extension (dev_sw.h ext2_task, what ARX_SW_SIMPLE runs) on tasks laid out as arx_selftest_extend takes them --
+// text in .pac layout, doubled coordinates, both directions (tests/test_dp_cases_hostsim.py compares it with the oracle's ksw_extend2)
+extern "C" void arx_test_ext2_task(const uint8_t *pac, int64_t l_pac, const uint8_t *bases, int32_t n, const int64_t *task8, int32_t *res6)
+{
+	arx::IndexView ix = arx::IndexView();
+	ix.pac = pac; ix.l_pac = l_pac;
+	std::vector<uint32_t> row(arx::MAX_READ_LEN + 2);
+	for (int i = 0; i < n; ++i) {
+		const int64_t *r = task8 + 8 * (size_t)i;
+		arx::ExtTask t;
+		t.tpos = r[0]; t.owner = i; t.qoff = (int32_t)r[1]; t.qlen = (int32_t)r[2]; t.tlen = (int32_t)r[3]; t.qdir = (int32_t)r[4]; t.tdir = (int32_t)r[5];
+		t.w = (int32_t)r[6]; t.h0 = (int32_t)r[7];
+		const arx::ExtRes e = arx::ext2_task(ix, bases, t, row.data(), 1);
+		int32_t *o = res6 + 6 * (size_t)i;
+		o[0] = e.score; o[1] = e.qle; o[2] = e.tle; o[3] = e.gtle; o[4] = e.gscore; o[5] = e.max_off;
+	}
+}
