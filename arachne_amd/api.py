@@ -38,6 +38,7 @@ STAGE_SEED, STAGE_CHAIN, STAGE_EXTEND, STAGE_RESCUE, STAGE_ALN = 1, 2, 3, 4, 5
 POST_DTYPE = np.dtype([("qb", "<i4"), ("qe", "<i4"), ("matches", "<i4"), ("n_mm", "<i4"), ("mm_off", "<i4"), ("duplicate", "<i4")])
 SPLIT_DTYPE = np.dtype([("split", "<i4"), ("mapq", "<i4"), ("is_proper", "<i4"), ("n_split_cand", "<i4"), ("order_pinned", "<i4"),
                         ("second_best2", "<i4"), ("score2", "<i4"), ("pad", "<i4")])
+TAGS_DTYPE = np.dtype([("active", "<i4"), ("second_best", "<i4"), ("xs", "<i4"), ("as", "<i4"), ("xm", "<i4"), ("xt", "<i4"), ("dm_n", "<i4"), ("dm_sum", "<i4")])
 _NT4 = np.full(256, 4, dtype=np.uint8)
 for _i, _c in enumerate("ACGT"):
     _NT4[ord(_c)] = _i
@@ -87,6 +88,11 @@ def _load(path):
     lib.arx_batch_rfa_fetch.argtypes = [vp, vp, vp, vp]
     lib.arx_batch_post.argtypes = [vp, vp, vp]
     lib.arx_batch_post_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.arx_batch_tags.argtypes = [vp, vp]
+    lib.arx_batch_tags_fetch.argtypes = [vp, vp, vp]
+    lib.arx_bam_write_select.argtypes = [vp, vp, vp, i64]
+    lib.arx_bucket_table.argtypes = [i32, vp, vp, i64, vp, vp, vp, i32, i32]
+    lib.arx_recbuf_build_full.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
     lib.arx_feeder_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp), C.c_char_p, i32]
     lib.arx_feeder_next.argtypes = [vp, i64, vp]
     lib.arx_feeder_close.argtypes = [vp]
@@ -385,6 +391,16 @@ class Batch:
         self.ref._check(self.ref.lib.arx_batch_post_fetch(self.ref.h, self.h, post.ctypes.data, split.ctypes.data, mm_ref.ctypes.data, mm_read.ctypes.data))
         return dict(post=post, split=split, mm_ref=mm_ref[:n.value], mm_read=mm_read[:n.value])
 
+    def tags(self, fetch=True):
+        """arx_batch_tags (needs rfa(); call it after post(), which discards it): per read what estimateMapQualities leaves in mapq_data
+        for the BAM tags -> TAGS_DTYPE array of n_reads (see arx_read_tags); fetch=False leaves it in the library."""
+        self.ref._check(self.ref.lib.arx_batch_tags(self.ref.h, self.h))
+        if not fetch:
+            return None
+        out = np.zeros(self.n_reads, dtype=TAGS_DTYPE)
+        self.ref._check(self.ref.lib.arx_batch_tags_fetch(self.ref.h, self.h, out.ctypes.data))
+        return out
+
     def free(self):
         if self.h:
             self.ref.lib.arx_batch_free(self.ref.h, self.h)
@@ -518,6 +534,12 @@ class BamWriter:
         if self.lib.arx_bam_write(self.h, C.byref(view)) != 0:
             raise ArachneError("arx_bam_write: " + self.lib.arx_bam_error(self.h).decode())
 
+    def write_select(self, view, idx):
+        """arx_bam_write_select: records idx (int64, in that order) of a _BamBatch view"""
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        if self.lib.arx_bam_write_select(self.h, C.byref(view), idx.ctypes.data if len(idx) else None, len(idx)) != 0:
+            raise ArachneError("arx_bam_write_select: " + self.lib.arx_bam_error(self.h).decode())
+
     def close(self):
         st = np.zeros(4, dtype=np.int64)
         if self.h:
@@ -526,6 +548,37 @@ class BamWriter:
             if rc != 0:
                 raise ArachneError("arx_bam_close failed")
         return dict(records=int(st[0]), blocks=int(st[1]), bytes_in=int(st[2]), bytes_out=int(st[3]))
+
+
+class _RecbufFull(C.Structure):
+    _fields_ = [("split", C.c_void_p), ("mm_ref", C.c_void_p), ("mm_read", C.c_void_p), ("tags", C.c_void_p), ("n_contigs", C.c_int32), ("pad", C.c_int32),
+                ("contig_names", C.c_void_p), ("contig_file", C.c_void_p), ("chunk", C.c_int64), ("unmapped_file", C.c_int32), ("pad2", C.c_int32)]
+
+
+class BucketTable:
+    """The reference's position buckets (CreateBAMs, bamwriter.go:134-188; arx_bucket_table): files[k] is the k-th file name, a mapped record of
+    contig rid at pos goes to files[contig_file[rid] + pos // chunk], an unmapped one to files[-1] (ZZZ_unmapped_pos_bucketed.bam)."""
+
+    def __init__(self, contig_names, contig_lens, chunk: int = 40_000_000, lib_path: str = LIB_PATH):
+        lib = _load(lib_path)
+        n = len(contig_names)
+        self.contig_names, self.chunk = list(contig_names), int(chunk)
+        self._names_keep = [x.encode() for x in contig_names]
+        self._names_c = C.cast((C.c_char_p * max(n, 1))(*self._names_keep), C.c_void_p) if n else None
+        lens = np.ascontiguousarray(contig_lens, dtype=np.int32)
+        self.contig_file = np.zeros(max(n, 1), dtype=np.int32)
+        nf = C.c_int32()
+        if lib.arx_bucket_table(n, self._names_c, lens.ctypes.data, self.chunk, self.contig_file.ctypes.data, C.byref(nf), None, 0, 0) != 0:
+            raise ArachneError("arx_bucket_table: bad arguments")
+        w = max(len(x) for x in self._names_keep) + 48 if n else 64
+        buf = C.create_string_buffer(nf.value * w)
+        if lib.arx_bucket_table(n, self._names_c, lens.ctypes.data, self.chunk, self.contig_file.ctypes.data, C.byref(nf), buf, nf.value, w) != 0:
+            raise ArachneError("arx_bucket_table: bad arguments")
+        self.files = [buf.raw[k * w:(k + 1) * w].split(b"\0", 1)[0].decode() for k in range(nf.value)]
+
+
+def bucket_table(contig_names, contig_lens, chunk: int = 40_000_000, lib_path: str = LIB_PATH) -> BucketTable:
+    return BucketTable(contig_names, contig_lens, chunk, lib_path=lib_path)
 
 
 class RecBuf:
@@ -546,6 +599,21 @@ class RecBuf:
         if rc != 0:
             raise ArachneError("arx_recbuf_build: " + self.lib.arx_recbuf_error(self.h).decode())
         return view
+
+    def build_full(self, sb, cand_off, cands, alns, cigars, post, split, mm_ref, mm_read, tags, table: "BucketTable", threads: int = 8):
+        """arx_recbuf_build_full: the reference's record set (primary + split records, full tags, position buckets).  split / mm_ref / mm_read:
+        Batch.post(); tags: Batch.tags(); table: bucket_table(...) -> (_BamBatch view, bucket index of every record (int32, a copy))"""
+        full = _RecbufFull(split.ctypes.data, mm_ref.ctypes.data, mm_read.ctypes.data, tags.ctypes.data, len(table.contig_names), 0, table._names_c,
+                           table.contig_file.ctypes.data, int(table.chunk), len(table.files) - 1, 0)
+        view = _BamBatch()
+        bucket = C.c_void_p()
+        rc = self.lib.arx_recbuf_build_full(self.h, C.byref(sb), cand_off.ctypes.data, cands.ctypes.data, alns.ctypes.data, cigars.ctypes.data, post.ctypes.data,
+                                            C.byref(full), int(threads), C.byref(view), C.byref(bucket))
+        if rc != 0:
+            raise ArachneError("arx_recbuf_build_full: " + self.lib.arx_recbuf_error(self.h).decode())
+        n = int(view.n_records)
+        b = np.ctypeslib.as_array(C.cast(bucket, C.POINTER(C.c_int32)), shape=(n,)).copy() if n else np.zeros(0, dtype=np.int32)
+        return view, b
 
     def free(self):
         if self.h:

@@ -202,6 +202,7 @@ template <class RT> struct Batch {
 	std::vector<int32_t> lens_host;
 	RfaResult rfa;
 	PostResult post; std::vector<size_t> post_mark;
+	TagsResult tags;            // arx_batch_tags: allocated behind arx_batch_post's memory, so a later arx_batch_post discards it
 	std::vector<size_t> rfa_mark; bool rfa_marked = false; // arena state after ARX_STAGE_ALN: a repeated arx_batch_rfa reuses the same memory
 	// arx_batch_detach: the dense results copied aside (device memory of their own, outside the work arena) so that the handle can take its
 	// next reads while a second host thread takes them home through a stream of its own (arx_batch_fetch_detached)
@@ -315,7 +316,7 @@ template <class RT> struct Batch {
 		  if (tot >= ((int64_t)1 << 31) - 64) { c->set_error("batch too large: more than 2^31 bases, split the batch"); return ARX_E_TOO_LARGE; } } \
 		ARX_TRY(c, b->rt.bind();                                                                                                    \
 			b->pipe.free_work(b->work); b->res = arx::BatchResult(); b->done_stage = 0; b->rfa_marked = false;                      \
-			b->rfa = arx::RfaResult(); b->post = arx::PostResult();                                                                 \
+			b->rfa = arx::RfaResult(); b->post = arx::PostResult(); b->tags = arx::TagsResult();                                                                 \
 			b->pipe.upload_into(b->db, bases, lens, n_reads); b->lens_host.assign(lens, lens + n_reads);)                           \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
@@ -327,7 +328,7 @@ template <class RT> struct Batch {
 		bool ok = false;                                                                                                            \
 		ARX_TRY(c, b->rt.bind();                                                                                                    \
 			b->pipe.free_work(b->work); b->res = arx::BatchResult(); b->done_stage = 0; b->rfa_marked = false;                      \
-			b->rfa = arx::RfaResult(); b->post = arx::PostResult();                                                                 \
+			b->rfa = arx::RfaResult(); b->post = arx::PostResult(); b->tags = arx::TagsResult();                                                                 \
 			ok = b->pipe.upload_from_device(b->db, d_bases, d_lens, n_reads, n_bases, 0, b->lens_host);)                            \
 		if (!ok) { c->set_error("device batch: the read lengths do not add up to n_bases, or a length is outside [0, 255]"); return ARX_E_ARG; } \
 		return ARX_OK;                                                                                                              \
@@ -395,7 +396,7 @@ template <class RT> struct Batch {
 			b->rt.set_timing(c->timing);                                                                                            \
 			/* stages already done are kept (run(SEED) then run(ALN) resumes); asking for a stage again restarts the batch */       \
 			if (last_stage <= b->done_stage) { b->pipe.free_work(b->work); b->res = arx::BatchResult(); b->done_stage = 0; }        \
-			b->rfa_marked = false; b->post = arx::PostResult();                                                                          \
+			b->rfa_marked = false; b->post = arx::PostResult(); b->tags = arx::TagsResult();                                                                          \
 			if (b->done_stage < ARX_STAGE_SEED) {                                                                                   \
 				int rc = b->pipe.stage_seed(b->db, b->work);                                                                        \
 				if (rc == -2) { c->set_error("batch too large: seed occurrences exceed 2^30, split the batch"); return ARX_E_TOO_LARGE; } \
@@ -445,7 +446,7 @@ template <class RT> struct Batch {
 		ARX_TRY(c, b->rt.bind(); b->rt.set_timing(c->timing);                                                                       \
 			if (b->rfa_marked) b->rt.arena_rewind(b->rfa_mark); else { b->rfa_mark = b->rt.arena_mark(); b->rfa_marked = true; }    \
 			arx::RfaStage<RT>::run(b->pipe, b->db, b->work, n_barcodes, bc_pair_off, do_rfa, penalty, cen_start, cen_end, b->lens_host.data(), b->rfa); \
-			b->post = arx::PostResult(); b->post_mark = b->rt.arena_mark();                                                         \
+			b->post = arx::PostResult(); b->tags = arx::TagsResult(); b->post_mark = b->rt.arena_mark();                                                         \
 			*n_cands = b->rfa.n_cands;)                                                                               \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
@@ -456,6 +457,7 @@ template <class RT> struct Batch {
 		static_assert(sizeof(arx_cand_post) == sizeof(arx::CandPost) && sizeof(arx_split) == sizeof(arx::SplitRec), "C-ABI structs must mirror the device structs"); \
 		ARX_TRY(c, b->rt.bind(); b->rt.set_timing(c->timing);                                                                       \
 			b->rt.arena_rewind(b->post_mark);                                                                                       \
+			b->tags = arx::TagsResult();                                                                                            \
 			arx::PostStage<RT>::run(b->pipe, b->db, b->work, b->rfa, b->post);                                                      \
 			b->rt.sync();                                                                                                           \
 			*n_mm = b->post.n_mm;)                                                                                                  \
@@ -466,6 +468,25 @@ template <class RT> struct Batch {
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
 		if (!b->post.done || !b->rfa_marked) { c->set_error("arx_batch_post_fetch before arx_batch_post"); return ARX_E_ARG; }      \
 		ARX_TRY(c, b->rt.bind(); arx::PostStage<RT>::fetch(b->pipe, b->db, b->rfa, b->post, (arx::CandPost *)post, (arx::SplitRec *)split, mm_ref, mm_read);) \
+		return ARX_OK;                                                                                                              \
+	}                                                                                                                               \
+	int arx_batch_tags(arx_ctx *h, arx_batch *bh)                                                                                   \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
+		if (b->rfa.cand_off.empty() || !b->rfa_marked) { c->set_error("arx_batch_tags before arx_batch_rfa"); return ARX_E_ARG; }   \
+		static_assert(sizeof(arx_read_tags) == sizeof(arx::ReadTags), "C-ABI structs must mirror the device structs");             \
+		ARX_TRY(c, b->rt.bind(); b->rt.set_timing(c->timing);                                                                       \
+			if (b->tags.marked) b->rt.arena_rewind(b->tags.mark); else { b->tags.mark = b->rt.arena_mark(); b->tags.marked = true; } \
+			b->tags.done = false;                                                                                                   \
+			arx::TagsStage<RT>::run(b->pipe, b->db, b->rfa, b->tags);                                                               \
+			b->rt.sync();)                                                                                                          \
+		return ARX_OK;                                                                                                              \
+	}                                                                                                                               \
+	int arx_batch_tags_fetch(arx_ctx *h, arx_batch *bh, arx_read_tags *out)                                                         \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
+		if (!b->tags.done || !b->rfa_marked) { c->set_error("arx_batch_tags_fetch before arx_batch_tags (or after a later arx_batch_rfa / arx_batch_post)"); return ARX_E_ARG; } \
+		ARX_TRY(c, b->rt.bind(); arx::TagsStage<RT>::fetch(b->pipe, b->db, b->tags, (arx::ReadTags *)out);)                         \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_rfa_fetch(arx_ctx *h, arx_batch *bh, int32_t *cand_off, arx_cand *cands)                                          \

@@ -37,6 +37,19 @@ int arx_bam_write(arx_bam *h, const arx_bam_batch *batch)
 	}
 }
 
+int arx_bam_write_select(arx_bam *h, const arx_bam_batch *batch, const int64_t *idx, int64_t n)
+{
+	arx::BamSink *w = (arx::BamSink *)h;
+	if (n < 0 || (n > 0 && !idx)) { w->error = "bad record selection"; return ARX_E_ARG; }
+	try {
+		static const int64_t none = 0; // n = 0: an empty selection, not "all records"
+		return w->write(*batch, idx ? idx : &none, n) ? ARX_OK : ARX_E_IO;
+	} catch (const std::exception &e) {
+		w->error = e.what();
+		return ARX_E_IO;
+	}
+}
+
 int arx_bam_close(arx_bam *h, int64_t *stats)
 {
 	arx::BamSink *w = (arx::BamSink *)h;
@@ -63,6 +76,36 @@ int arx_recbuf_build(arx_recbuf *h, const arx_super_batch *sb, const int32_t *ca
 	try {
 		return rb->buf.build(*sb, cand_off, cands, alns, cigars, post, threads, view, rb->error) ? ARX_OK : ARX_E_ARG;
 	} catch (const std::exception &e) { rb->error = e.what(); return ARX_E_IO; }
+}
+int arx_recbuf_build_full(arx_recbuf *h, const arx_super_batch *sb, const int32_t *cand_off, const arx_cand *cands, const arx_aln *alns, const uint32_t *cigars,
+                          const arx_cand_post *post, const arx_recbuf_full *full, int32_t threads, arx_bam_batch *view, const int32_t **bucket)
+{
+	RecBufHandle *rb = (RecBufHandle *)h;
+	if (!sb || !cand_off || !cands || !alns || !cigars || !post || !full || !full->split || !full->tags || !full->contig_names || !full->contig_file || !view) {
+		rb->error = "null argument"; return ARX_E_ARG;
+	}
+	if (full->chunk <= 0) { rb->error = "chunk must be positive"; return ARX_E_ARG; }
+	try {
+		if (!rb->buf.build(*sb, cand_off, cands, alns, cigars, post, threads, view, rb->error, full)) return ARX_E_ARG;
+		if (bucket) *bucket = rb->buf.bucket.data();
+		return ARX_OK;
+	} catch (const std::exception &e) { rb->error = e.what(); return ARX_E_IO; }
+}
+int arx_bucket_table(int32_t n_contigs, const char *const *names, const int32_t *lens, int64_t chunk, int32_t *contig_file, int32_t *n_files, char *file_names,
+                     int32_t cap_files, int32_t name_w)
+{
+	if (n_contigs < 0 || chunk <= 0 || !names || !lens || !contig_file || !n_files) return ARX_E_ARG;
+	std::vector<std::string> fn;
+	arx::bucket_table(n_contigs, names, lens, chunk, contig_file, fn);
+	*n_files = (int32_t)fn.size();
+	if (file_names) {
+		if ((int64_t)fn.size() > cap_files) return ARX_E_ARG;
+		for (size_t i = 0; i < fn.size(); ++i) {
+			if ((int64_t)fn[i].size() + 1 > name_w) return ARX_E_ARG;
+			memcpy(file_names + i * (size_t)name_w, fn[i].c_str(), fn[i].size() + 1);
+		}
+	}
+	return ARX_OK;
 }
 const char *arx_recbuf_error(arx_recbuf *h) { return ((RecBufHandle *)h)->error.c_str(); }
 void arx_recbuf_free(arx_recbuf *h) { delete (RecBufHandle *)h; }

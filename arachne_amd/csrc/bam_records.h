@@ -2,20 +2,43 @@
 // that turns the placed candidate of every read into a record, for a whole super-batch at a time, on host threads.  Host code of
 // libarachne_amd.so (C ABI: arx_recbuf_* in include/arachne_amd.h); the sink that takes the records is bam_sink.h.
 //
-// One record per read: its ACTIVE candidate (what DoDumpToBam writes as `primary`, bamwriter.go:635-658), with
+// Two modes over the same size / scan / fill passes.
+//
+// arx_recbuf_build (kept as it was first written; tests/test_e2e.py pins it): one record per read, its ACTIVE candidate (what DoDumpToBam
+// writes as `primary`, bamwriter.go:635-658), with
 //   flags      paired 0x1, proper 0x2, unmapped 0x4, mate unmapped 0x8, reverse 0x10, mate reverse 0x20, first / second 0x40 / 0x80,
-//              duplicate 0x400, as AppendBam sets them (:286-366); "unmapped" is the reference's rule: not proper and score - 17 < 19
-//              (:287-290, aligner.go:140-145) or the placeholder of a read without hits (pos -1)
+//              duplicate 0x400; "unmapped" is the reference's rule: not proper and score - 17 < 19 (:287-290, aligner.go:140-145) or the
+//              placeholder of a read without hits (pos -1)
 //   pos / mapq / mate / template length  as :287-346 (the candidate's pos is 0-based already; reverse-strand candidates carry the
 //              swapped pos/aend of aligner.go:1577-1582, so TempLen reads the same fields the reference reads)
 //   CIGAR      BWA's op codes MIDSH -> BAM's M I D S H (fixCigar's table, :248-276); read and qualities reversed for reverse-strand
 //              records (:372-375; reverseComp / reverseQual)
-//   aux        RG:Z (the R1 header's last field, reader.go:144-153), AS:i (score), XM:Z:0, AM:Z:0|1, XT:i:0 (:398-458 for a read without
-//              mapq_data), and for a unique barcode set whose barcode holds a '-' BX:Z + VX:i:1 (:555-559).
-// Left to the caller (documented, not emitted): the split / supplementary records and their SA / XS / XC / AC tags (they come from
-// arx_split + the mismatch lists of arx_batch_post_fetch), the debug tags, DM (molecule_difference).
+//   aux        RG:Z (the R1 header's last field, reader.go:144-153), AS:i (score), XM:Z:0, AM:Z:0|1, XT:C:0, and for a unique barcode set
+//              whose barcode holds a '-' BX:Z + VX:C:1 (:555-559).
+// That is NOT the reference's tag set: the reference never writes a read without mapq_data -- every Alignment is created with one
+// (aligner.go:1601) and estimateMapQualities fills it for every barcode, with or without RFA (aligner.go:471, 496).  Its AS also is the
+// BWA score rather than mapq_data.score, and its mate / TempLen rules read the mate's own is_proper.  Those stay as they are in this mode.
+//
+// arx_recbuf_build_full: the reference's record set.  Every read's primary record, then its split record (Alignment.secondary from
+// arx_split: flag 0x100, TempLen 0, HardClip of :660-689 after the reverse-complement), with
+//   flags / mate / TempLen  as :286-366 with AppendBam's in-place mutation: a record the score rule unmaps gets pos = -1, mapq = 0 before
+//              anything is computed, and every record written later sees that -- read 2p is written before 2p+1, so 2p+1 sees its mate
+//              at pos -1 (mate unmapped, TempLen 0), a split record's SA is left out when its primary was unmapped, and a forward primary
+//              the rule unmaps while its mate stays mapped on the same contig gets TempLen mate.aend - (-1), the reference's form.  The
+//              mate-unmapped test is the reference's `mate.pos == -1 || (!primary.is_proper && mate.score - 17 < 19)`.
+//   aux        RG XS XC AC AS XM AM XT SA BX VX DM in the reference's order (:390-563), integers as `i` (auxify_int), strings NUL-ended.
+//              XS / AS / XM / XT / XC's second best / DM's inputs come from arx_batch_tags; XC / AC list "ref,read,1;" per mismatch location
+//              of the second best / the record's own alignment (arx_batch_post's lists); SA (:462-494) "contig,pos,strand,cigar,mapq,NM;"
+//              with the raw BWA ops (reversed for '-', S printed as H only on the primary's SA), NM = mismatches + I/D lengths.
+//              Split records: XS / AS = second_best2 / 2, score2 / 2 (truncated), XC empty, XM:Z:0, XT:i:0.
+//   DM         written on primary records only.  A split candidate is never active, so the reference's molecule_difference on it is
+//              whatever the FIRST setMoleculeDifferences call (aligner.go:483, before Optimize) left there, or 0; reproducing that needs a
+//              snapshot taken inside the RFA kernel on the timed path.  Split records carry no DM here.
+//   bucket     per record the position bucket of arx_bucket_table, chosen by IsUnmapped() (the score rule alone) as AppendBams does (:280).
+// Left out in both modes: the -debug tags (:495-553), which no command-line path reaches.
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
 #include <string>
 #include <thread>
@@ -24,6 +47,39 @@
 
 namespace arx {
 
+// CreateBAMs' files (bamwriter.go:134-188), in creation order; contig_file[i]: the file of contig i's first chunk
+inline void bucket_table(int n_contigs, const char *const *names, const int32_t *lens, int64_t chunk, int32_t *contig_file, std::vector<std::string> &files)
+{
+	files.clear();
+	int64_t running = 0;
+	int32_t last = -1;
+	char buf[64];
+	for (int i = 0; i < n_contigs; ++i) {
+		const int64_t len = lens[i], n_chunks = (len + chunk - 1) / chunk;
+		snprintf(buf, sizeof buf, "%06d-", i);
+		const std::string stem = std::string(buf) + names[i] + "_";
+		if (n_chunks > 1) {
+			contig_file[i] = (int32_t)files.size();
+			for (int64_t k = 0; k < n_chunks; ++k) { snprintf(buf, sizeof buf, "%010lld", (long long)(k * chunk)); files.push_back(stem + buf + "_pos_bucketed.bam"); }
+		} else {
+			if (running == 0 || running + len > chunk) { last = (int32_t)files.size(); files.push_back(stem + "0000000000_pos_bucketed.bam"); running = len; }
+			else running += len;
+			contig_file[i] = last;
+		}
+	}
+	files.push_back("ZZZ_unmapped_pos_bucketed.bam");
+}
+
+// aux bytes of the full mode, counted (p == null) or written
+struct AuxOut {
+	uint8_t *p; int64_t n = 0;
+	void put(const void *s, size_t l) { if (p) memcpy(p + n, s, l); n += (int64_t)l; }
+	void tag(const char *t, char type) { const char h[3] = {t[0], t[1], type}; put(h, 3); }
+	void i32(const char *t, int32_t v) { tag(t, 'i'); put(&v, 4); }
+	void z(const char *t, const char *s, size_t l) { tag(t, 'Z'); put(s, l); put("", 1); }
+	void zs(const char *t, const std::string &s) { z(t, s.data(), s.size()); }
+};
+
 struct RecBuf {
 	std::vector<int64_t> name_off, cigar_off, seq_off, aux_off;
 	std::vector<char> names;
@@ -31,19 +87,43 @@ struct RecBuf {
 	std::vector<uint8_t> mapq, seq, qual, aux;
 	std::vector<uint32_t> cigars;
 	std::vector<int32_t> act; // active candidate of every read
+	std::vector<int64_t> rbase; // full mode: record of every read's primary (its split record follows it)
+	std::vector<int32_t> bucket; // full mode: position bucket of every record
 
 	static inline bool unmapped(const arx_cand &a) { return a.pos == -1 || (!a.is_proper && a.score - 17 < 19); }
 
+	// What AppendBam sees when it writes read r's records (full mode): the mutation of the score rule applied in write order
+	static inline bool rule(const arx_cand &a) { return !a.is_proper && a.score - 17 < 19; } // IsUnmapped (aligner.go:140-145)
+	static inline bool pair_at(const arx_cand &a, int64_t apos, const arx_cand &b, int64_t bpos) // isPair (aligner.go:1032) on positions as mutated
+	{
+		if (a.reversed == b.reversed || a.rid != b.rid) return false;
+		const int64_t dist = a.reversed ? apos - bpos : bpos - apos;
+		return dist >= -35 && dist < 750;
+	}
+	struct ReadState {
+		int a, am, s;          // active candidate, the mate's, the split candidate (-1: none)
+		int64_t cpos, mpos;    // the primary's pos as written; the mate's pos when r's records are written (2p+1 sees 2p's mutation)
+		bool mate_un;          // flag 0x8 of both records
+		int64_t spos;          // the split record's pos as written
+		int hc0, hc1;          // HardClip: bases cut at the front / the back of the split record
+	};
+	static inline uint8_t mapq_byte(int32_t q) { return (uint8_t)(q < 0 ? 0 : (q > 255 ? 255 : q)); }
+
 	// sb: the super-batch the batch was created from; cand_off / cands: arx_batch_rfa_fetch; alns / cigars: arx_batch_fetch (cands[].reg indexes
-	// them); post: arx_batch_post_fetch's per-candidate records or NULL (then no duplicate flags)
+	// them); post: arx_batch_post_fetch's per-candidate records or NULL (then no duplicate flags); full: null for arx_recbuf_build's record set
 	bool build(const arx_super_batch &sb, const int32_t *cand_off, const arx_cand *cands, const arx_aln *alns, const uint32_t *cigs, const arx_cand_post *post,
-	           int threads, arx_bam_batch *view, std::string &err)
+	           int threads, arx_bam_batch *view, std::string &err, const arx_recbuf_full *full = nullptr)
 	{
 		const int64_t NP = sb.n_pairs, NR = 2 * NP;
 		if (threads < 1) threads = 1;
 		act.assign((size_t)NR, -1);
-		name_off.assign((size_t)NR + 1, 0); cigar_off.assign((size_t)NR + 1, 0); seq_off.assign((size_t)NR + 1, 0); aux_off.assign((size_t)NR + 1, 0);
-		flag.resize((size_t)NR); rid.resize((size_t)NR); pos.resize((size_t)NR); mate_rid.resize((size_t)NR); mate_pos.resize((size_t)NR); tlen.resize((size_t)NR); mapq.resize((size_t)NR);
+		// records: one per read, and in the full mode the split record right behind its primary
+		rbase.assign((size_t)NR + 1, 0);
+		for (int64_t r = 0; r < NR; ++r) rbase[(size_t)r + 1] = rbase[(size_t)r] + 1 + (full && full->split[r].split >= 0 ? 1 : 0);
+		const int64_t NRec = rbase[(size_t)NR];
+		name_off.assign((size_t)NRec + 1, 0); cigar_off.assign((size_t)NRec + 1, 0); seq_off.assign((size_t)NRec + 1, 0); aux_off.assign((size_t)NRec + 1, 0);
+		flag.resize((size_t)NRec); rid.resize((size_t)NRec); pos.resize((size_t)NRec); mate_rid.resize((size_t)NRec); mate_pos.resize((size_t)NRec); tlen.resize((size_t)NRec); mapq.resize((size_t)NRec);
+		if (full) bucket.assign((size_t)NRec, 0);
 		std::vector<int64_t> base_off((size_t)NR + 1, 0), pair_set((size_t)NP);
 		for (int64_t r = 0; r < NR; ++r) base_off[(size_t)r + 1] = base_off[(size_t)r] + sb.lens[r];
 		for (int s = 0; s < sb.n_sets; ++s) for (int64_t p = sb.set_pair_off[s]; p < sb.set_pair_off[s + 1]; ++p) pair_set[(size_t)p] = s;
@@ -59,32 +139,175 @@ struct RecBuf {
 			for (int t = 0; t < threads; ++t) th.emplace_back([&, t]() { const int64_t lo = NR * t / threads, hi = NR * (t + 1) / threads; for (int64_t r = lo; r < hi; ++r) fn(r); });
 			for (auto &x : th) x.join();
 		};
+		auto active_of = [&](int64_t r) { int a = -1; for (int i = cand_off[r]; i < cand_off[r + 1]; ++i) if (cands[i].active) a = i; return a; };
+		auto state = [&](int64_t r) { // full mode
+			ReadState st;
+			st.a = act[(size_t)r]; st.am = act[(size_t)(r ^ 1)]; st.s = full->split[r].split;
+			const arx_cand &c = cands[st.a], &m = cands[st.am];
+			st.cpos = rule(c) ? -1 : c.pos;
+			st.mpos = ((r & 1) && rule(m)) ? -1 : m.pos;
+			st.mate_un = st.mpos == -1 || (!c.is_proper && m.score - 17 < 19);
+			st.spos = -1; st.hc0 = st.hc1 = 0;
+			if (st.s >= 0) {
+				const arx_cand &x = cands[st.s];
+				st.spos = (!full->split[r].is_proper && x.score - 17 < 19) ? -1 : x.pos;
+				const arx_aln &al = alns[x.reg];
+				const uint32_t *w = cigs + al.cigar_off;
+				if (al.n_cigar >= 1 && (w[0] & 15u) == 3) st.hc0 = (int)(w[0] >> 4);                                  // BWA's S = 3 (BAM's 4)
+				if (al.n_cigar >= 2 && (w[al.n_cigar - 1] & 15u) == 3) st.hc1 = (int)(w[al.n_cigar - 1] >> 4);
+			}
+			return st;
+		};
+		// "ref,read,1;" per mismatch location of candidate i (XC / AC)
+		auto mm_string = [&](int i) {
+			std::string out;
+			if (i < 0) return out;
+			char b[48];
+			for (int k = 0; k < post[i].n_mm; ++k) { snprintf(b, sizeof b, "%d,%d,1;", full->mm_ref[post[i].mm_off + k], full->mm_read[post[i].mm_off + k]); out += b; }
+			return out;
+		};
+		// SA:Z pointing at candidate i written at position p with MAPQ q; hard: S printed as H (the primary's SA, :478-480)
+		auto sa_string = [&](int i, int64_t p, int q, bool hard) {
+			const arx_cand &x = cands[i];
+			const arx_aln &al = alns[x.reg];
+			std::string out = (x.rid >= 0 && x.rid < full->n_contigs) ? full->contig_names[x.rid] : "";
+			char b[48];
+			snprintf(b, sizeof b, ",%lld,%c,", (long long)p, x.reversed ? '-' : '+'); out += b;
+			int indel = 0;
+			for (int k = 0; k < al.n_cigar; ++k) {
+				const uint32_t w = cigs[al.cigar_off + (x.reversed ? al.n_cigar - 1 - k : k)];
+				const int op = (int)(w & 15u);
+				if (op == 1 || op == 2) indel += (int)(w >> 4);
+				snprintf(b, sizeof b, "%u%c", w >> 4, op == 3 ? (hard ? 'H' : 'S') : "MIDSH"[op < 5 ? op : 4]); out += b;
+			}
+			snprintf(b, sizeof b, ",%d,%d;", q, post[i].n_mm + indel); out += b;
+			return out;
+		};
+		// the aux fields of read r's primary (split = false) or split record (full mode), counted or written
+		auto full_aux = [&](int64_t r, const ReadState &st, bool split, AuxOut &o) {
+			const int64_t p = r >> 1; const int s = (int)pair_set[(size_t)p];
+			const arx_read_tags &T = full->tags[r];
+			const arx_split &S = full->split[r];
+			const arx_cand &x = cands[split ? st.s : st.a];
+			const int64_t rgl = sb.rg_off[p + 1] - sb.rg_off[p];
+			if (rgl > 0) o.z("RG", sb.rgs + sb.rg_off[p], (size_t)rgl);
+			o.i32("XS", split ? S.second_best2 / 2 : T.xs);
+			o.zs("XC", split ? std::string() : mm_string(T.second_best));
+			o.zs("AC", mm_string(split ? st.s : st.a));
+			o.i32("AS", split ? S.score2 / 2 : T.as);
+			o.z("XM", (!split && T.xm) ? "1" : "0", 1);
+			o.z("AM", x.active_molecule ? "1" : "0", 1);
+			o.i32("XT", split ? 0 : T.xt);
+			if (!split && st.s >= 0) o.zs("SA", sa_string(st.s, cands[st.s].pos, S.mapq, true));        // the split is written after: not mutated yet
+			if (split && st.cpos > -1) o.zs("SA", sa_string(st.a, st.cpos, cands[st.a].mapq, false));
+			if (set_bx[(size_t)s]) {
+				o.z("BX", sb.barcodes + sb.barcode_off[s], (size_t)(sb.barcode_off[s + 1] - sb.barcode_off[s]));
+				o.i32("VX", 1);
+				if (!split && x.active_molecule && T.dm_n > 0) {
+					char b[64];
+					const int l = snprintf(b, sizeof b, "%.6f", (double)T.dm_sum / (double)T.dm_n); // strconv.FormatFloat(x, 'f', 6, 64)
+					o.z("DM", b, (size_t)l);
+				}
+			}
+		};
 		// pass 1: the active candidate and the sizes of every record
 		par([&](int64_t r) {
-			int a = -1;
-			for (int i = cand_off[r]; i < cand_off[r + 1]; ++i) if (cands[i].active) a = i; // exactly one per read
+			int a = active_of(r); // exactly one per read
 			if (a < 0) { bad = true; a = cand_off[r]; }
 			act[(size_t)r] = a;
-			const arx_cand &c = cands[a];
-			const int64_t p = r >> 1; const int s = (int)pair_set[(size_t)p];
-			name_off[(size_t)r + 1] = sb.name_off[p + 1] - sb.name_off[p];
-			cigar_off[(size_t)r + 1] = c.reg >= 0 ? alns[c.reg].n_cigar : 0;
-			seq_off[(size_t)r + 1] = sb.lens[r];
-			const int64_t rgl = sb.rg_off[p + 1] - sb.rg_off[p];
-			int64_t ax = (rgl > 0 ? 3 + rgl + 1 : 0) + 7 /* AS:i as int32 */ + 5 /* XM:Z:0 */ + 5 /* AM:Z:x */ + 4 /* XT:C:0 */;
-			if (set_bx[(size_t)s]) ax += 3 + (sb.barcode_off[s + 1] - sb.barcode_off[s]) + 1 + 4 /* VX:C:1 */;
-			aux_off[(size_t)r + 1] = ax;
 		});
 		if (bad) { err = "a read without an active candidate: arx_batch_rfa must have run on this batch"; return false; }
-		for (int64_t r = 0; r < NR; ++r) { name_off[(size_t)r + 1] += name_off[(size_t)r]; cigar_off[(size_t)r + 1] += cigar_off[(size_t)r]; seq_off[(size_t)r + 1] += seq_off[(size_t)r]; aux_off[(size_t)r + 1] += aux_off[(size_t)r]; }
-		names.resize((size_t)name_off[(size_t)NR] + 1); cigars.resize((size_t)cigar_off[(size_t)NR] + 1); seq.resize((size_t)seq_off[(size_t)NR] + 1); qual.resize((size_t)seq_off[(size_t)NR] + 1);
-		aux.resize((size_t)aux_off[(size_t)NR] + 1);
+		if (full) for (int64_t r = 0; r < NR; ++r) {
+			const int sp = full->split[r].split;
+			if (sp >= 0 && (sp < cand_off[r] || sp >= cand_off[r + 1] || cands[sp].reg < 0)) { err = "arx_split names a candidate of another read"; return false; }
+		}
+		par([&](int64_t r) {
+			const int64_t q = rbase[(size_t)r];
+			const arx_cand &c = cands[act[(size_t)r]];
+			const int64_t p = r >> 1; const int s = (int)pair_set[(size_t)p];
+			name_off[(size_t)q + 1] = sb.name_off[p + 1] - sb.name_off[p];
+			cigar_off[(size_t)q + 1] = c.reg >= 0 ? alns[c.reg].n_cigar : 0;
+			seq_off[(size_t)q + 1] = sb.lens[r];
+			if (!full) {
+				const int64_t rgl = sb.rg_off[p + 1] - sb.rg_off[p];
+				int64_t ax = (rgl > 0 ? 3 + rgl + 1 : 0) + 7 /* AS:i as int32 */ + 5 /* XM:Z:0 */ + 5 /* AM:Z:x */ + 4 /* XT:C:0 */;
+				if (set_bx[(size_t)s]) ax += 3 + (sb.barcode_off[s + 1] - sb.barcode_off[s]) + 1 + 4 /* VX:C:1 */;
+				aux_off[(size_t)q + 1] = ax;
+				return;
+			}
+			const ReadState st = state(r);
+			AuxOut o{nullptr};
+			full_aux(r, st, false, o);
+			aux_off[(size_t)q + 1] = o.n;
+			if (st.s >= 0) {
+				name_off[(size_t)q + 2] = name_off[(size_t)q + 1];
+				cigar_off[(size_t)q + 2] = alns[cands[st.s].reg].n_cigar;
+				const int64_t kept = (int64_t)sb.lens[r] - st.hc0 - st.hc1;
+				seq_off[(size_t)q + 2] = kept > 0 ? kept : 0;
+				AuxOut o2{nullptr};
+				full_aux(r, st, true, o2);
+				aux_off[(size_t)q + 2] = o2.n;
+			}
+		});
+		for (int64_t q = 0; q < NRec; ++q) { name_off[(size_t)q + 1] += name_off[(size_t)q]; cigar_off[(size_t)q + 1] += cigar_off[(size_t)q]; seq_off[(size_t)q + 1] += seq_off[(size_t)q]; aux_off[(size_t)q + 1] += aux_off[(size_t)q]; }
+		names.resize((size_t)name_off[(size_t)NRec] + 1); cigars.resize((size_t)cigar_off[(size_t)NRec] + 1); seq.resize((size_t)seq_off[(size_t)NRec] + 1); qual.resize((size_t)seq_off[(size_t)NRec] + 1);
+		aux.resize((size_t)aux_off[(size_t)NRec] + 1);
 		// pass 2: fill
 		static const uint32_t op_table[5] = {0, 1, 2, 4, 5}; // fixCigar (bamwriter.go:248-254): BWA's MIDSH -> BAM's M I D S H
 		static const char comp[5] = {'T', 'G', 'C', 'A', 'N'}, fwd[5] = {'A', 'C', 'G', 'T', 'N'};
+		// name, CIGAR (BAM codes; S -> H at both ends for a split record), bases and qualities of record q from candidate x of read r
+		auto fill_body = [&](int64_t r, int64_t q, const arx_cand &x, int hc0, int hc1, bool hard) {
+			const int64_t p = r >> 1;
+			memcpy(names.data() + name_off[(size_t)q], sb.names + sb.name_off[p], (size_t)(sb.name_off[p + 1] - sb.name_off[p]));
+			if (x.reg >= 0) {
+				const arx_aln &al = alns[x.reg];
+				uint32_t *dst = cigars.data() + cigar_off[(size_t)q];
+				for (int k = 0; k < al.n_cigar; ++k) { const uint32_t w = cigs[al.cigar_off + k]; const uint32_t op = w & 15u; dst[k] = (w & ~15u) | (op < 5 ? op_table[op] : op); }
+				if (hard && al.n_cigar >= 1 && (dst[0] & 15u) == 4) dst[0] = (dst[0] & ~15u) | 5u;                                   // HardClip (:660-689)
+				if (hard && al.n_cigar >= 2 && (dst[al.n_cigar - 1] & 15u) == 4) dst[al.n_cigar - 1] = (dst[al.n_cigar - 1] & ~15u) | 5u;
+			}
+			const int L = sb.lens[r];
+			const uint8_t *b = sb.bases + base_off[(size_t)r]; const char *qs = sb.quals + base_off[(size_t)r];
+			uint8_t *so = seq.data() + seq_off[(size_t)q], *qo = qual.data() + seq_off[(size_t)q];
+			const int lo = hc0, hi = L - hc1;
+			for (int k = lo; k < hi; ++k) {
+				if (x.reversed) { const uint8_t y = b[L - 1 - k]; so[k - lo] = (uint8_t)comp[y > 4 ? 4 : y]; qo[k - lo] = (uint8_t)qs[L - 1 - k]; }
+				else { const uint8_t y = b[k]; so[k - lo] = (uint8_t)fwd[y > 4 ? 4 : y]; qo[k - lo] = (uint8_t)qs[k]; }
+			}
+		};
 		par([&](int64_t r) {
+			const int64_t q = rbase[(size_t)r];
 			const arx_cand &c = cands[act[(size_t)r]], &m = cands[act[(size_t)(r ^ 1)]];
 			const int64_t p = r >> 1; const int s = (int)pair_set[(size_t)p];
+			if (full) {
+				const ReadState st = state(r);
+				const int32_t base_fl = 0x1 | ((r & 1) ? 0x80 : 0x40) | (st.mate_un ? 0x8 : (m.reversed ? 0x20 : 0));
+				const int32_t mrid = st.mate_un ? -1 : m.rid, mpos = st.mate_un ? -1 : (int32_t)st.mpos;
+				int32_t fl = base_fl | (c.is_proper ? 0x2 : 0) | (post[st.a].duplicate ? 0x400 : 0) | (st.cpos == -1 ? 0x4 : 0) | (c.reversed ? 0x10 : 0);
+				flag[(size_t)q] = fl;
+				rid[(size_t)q] = st.cpos == -1 ? -1 : c.rid; pos[(size_t)q] = (int32_t)st.cpos; mapq[(size_t)q] = st.cpos == -1 ? 0 : mapq_byte(c.mapq);
+				mate_rid[(size_t)q] = mrid; mate_pos[(size_t)q] = mpos;
+				int32_t tl = 0;
+				if (st.mpos != -1 && c.rid == m.rid && (c.is_proper || m.score - 17 >= 19)) tl = c.reversed ? -(int32_t)(c.aend - st.mpos) : (int32_t)(m.aend - st.cpos); // :329-343
+				tlen[(size_t)q] = tl;
+				bucket[(size_t)q] = rule(c) ? full->unmapped_file : full->contig_file[c.rid] + (int32_t)(c.pos / full->chunk);
+				fill_body(r, q, c, 0, 0, false);
+				AuxOut o{aux.data() + aux_off[(size_t)q]};
+				full_aux(r, st, false, o);
+				if (st.s >= 0) {
+					const arx_cand &x = cands[st.s];
+					const arx_split &S = full->split[r];
+					fl = base_fl | ((S.is_proper && pair_at(x, st.spos, m, st.mpos)) ? 0x2 : 0) | (post[st.s].duplicate ? 0x400 : 0) | 0x100 | (st.spos == -1 ? 0x4 : 0) | (x.reversed ? 0x10 : 0);
+					flag[(size_t)q + 1] = fl;
+					rid[(size_t)q + 1] = st.spos == -1 ? -1 : x.rid; pos[(size_t)q + 1] = (int32_t)st.spos; mapq[(size_t)q + 1] = st.spos == -1 ? 0 : mapq_byte(S.mapq);
+					mate_rid[(size_t)q + 1] = mrid; mate_pos[(size_t)q + 1] = mpos; tlen[(size_t)q + 1] = 0;
+					bucket[(size_t)q + 1] = st.spos == -1 ? full->unmapped_file : full->contig_file[x.rid] + (int32_t)(x.pos / full->chunk);
+					fill_body(r, q + 1, x, st.hc0, st.hc1, true);
+					AuxOut o2{aux.data() + aux_off[(size_t)q + 1]};
+					full_aux(r, st, true, o2);
+				}
+				return;
+			}
 			const bool un = unmapped(c), mun = unmapped(m);
 			int32_t fl = 0x1 | ((r & 1) ? 0x80 : 0x40);
 			if (c.is_proper) fl |= 0x2;
@@ -92,24 +315,14 @@ struct RecBuf {
 			if (post && post[act[(size_t)r]].duplicate) fl |= 0x400;
 			if (un) fl |= 0x4;
 			if (c.reversed) fl |= 0x10;
-			flag[(size_t)r] = fl;
-			rid[(size_t)r] = un ? -1 : c.rid; pos[(size_t)r] = un ? -1 : (int32_t)c.pos; mapq[(size_t)r] = un ? 0 : (uint8_t)(c.mapq < 0 ? 0 : (c.mapq > 255 ? 255 : c.mapq));
-			mate_rid[(size_t)r] = mun ? -1 : m.rid; mate_pos[(size_t)r] = mun ? -1 : (int32_t)m.pos;
+			flag[(size_t)q] = fl;
+			rid[(size_t)q] = un ? -1 : c.rid; pos[(size_t)q] = un ? -1 : (int32_t)c.pos; mapq[(size_t)q] = un ? 0 : mapq_byte(c.mapq);
+			mate_rid[(size_t)q] = mun ? -1 : m.rid; mate_pos[(size_t)q] = mun ? -1 : (int32_t)m.pos;
 			int32_t tl = 0;
 			if (m.pos != -1 && c.rid == m.rid && (c.is_proper || m.score - 17 >= 19)) tl = c.reversed ? -(int32_t)(c.aend - m.pos) : (int32_t)(m.aend - c.pos); // bamwriter.go:329-343
-			tlen[(size_t)r] = tl;
-			memcpy(names.data() + name_off[(size_t)r], sb.names + sb.name_off[p], (size_t)(sb.name_off[p + 1] - sb.name_off[p]));
-			if (c.reg >= 0) {
-				const arx_aln &al = alns[c.reg];
-				uint32_t *dst = cigars.data() + cigar_off[(size_t)r];
-				for (int k = 0; k < al.n_cigar; ++k) { const uint32_t w = cigs[al.cigar_off + k]; const uint32_t op = w & 15u; dst[k] = (w & ~15u) | (op < 5 ? op_table[op] : op); }
-			}
-			const int L = sb.lens[r];
-			const uint8_t *b = sb.bases + base_off[(size_t)r]; const char *q = sb.quals + base_off[(size_t)r];
-			uint8_t *so = seq.data() + seq_off[(size_t)r], *qo = qual.data() + seq_off[(size_t)r];
-			if (c.reversed) for (int k = 0; k < L; ++k) { const uint8_t x = b[L - 1 - k]; so[k] = (uint8_t)comp[x > 4 ? 4 : x]; qo[k] = (uint8_t)q[L - 1 - k]; }
-			else for (int k = 0; k < L; ++k) { const uint8_t x = b[k]; so[k] = (uint8_t)fwd[x > 4 ? 4 : x]; qo[k] = (uint8_t)q[k]; }
-			uint8_t *a = aux.data() + aux_off[(size_t)r];
+			tlen[(size_t)q] = tl;
+			fill_body(r, q, c, 0, 0, false);
+			uint8_t *a = aux.data() + aux_off[(size_t)q];
 			const int64_t rgl = sb.rg_off[p + 1] - sb.rg_off[p];
 			if (rgl > 0) { *a++ = 'R'; *a++ = 'G'; *a++ = 'Z'; memcpy(a, sb.rgs + sb.rg_off[p], (size_t)rgl); a += rgl; *a++ = 0; }
 			*a++ = 'A'; *a++ = 'S'; *a++ = 'i'; { const int32_t v = c.score; memcpy(a, &v, 4); a += 4; }
@@ -122,7 +335,7 @@ struct RecBuf {
 				*a++ = 'V'; *a++ = 'X'; *a++ = 'C'; *a++ = 1;
 			}
 		});
-		view->n_records = NR;
+		view->n_records = NRec;
 		view->name_off = name_off.data(); view->names = names.data(); view->flag = flag.data(); view->rid = rid.data(); view->pos = pos.data(); view->mapq = mapq.data();
 		view->mate_rid = mate_rid.data(); view->mate_pos = mate_pos.data(); view->tlen = tlen.data(); view->cigar_off = cigar_off.data(); view->cigars = cigars.data();
 		view->seq_off = seq_off.data(); view->seq = seq.data(); view->qual = qual.data(); view->qual_offset = 33; view->aux_off = aux_off.data(); view->aux = aux.data();

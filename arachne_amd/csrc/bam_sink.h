@@ -127,20 +127,24 @@ struct BamSink {
 		for (auto &x : th) x.join();
 	}
 
-	bool write(const arx_bam_batch &b)
+	// idx: the records to write, in this order (arx_bam_write_select), or null for all of them
+	bool write(const arx_bam_batch &b, const int64_t *idx = nullptr, int64_t n_sel = 0)
 	{
-		const int64_t n = b.n_records;
-		for (int64_t i = 0; i < n; ++i) {
+		const int64_t n = idx ? n_sel : b.n_records;
+		auto rec = [&](int64_t k) { return idx ? idx[k] : k; };
+		for (int64_t k = 0; k < n; ++k) {
+			const int64_t i = rec(k);
+			if (i < 0 || i >= b.n_records) { error = "record index " + std::to_string(i) + " outside the batch"; return false; }
 			const int64_t ln = b.name_off[i + 1] - b.name_off[i], nc = b.cigar_off[i + 1] - b.cigar_off[i];
 			if (ln < 1 || ln > 254) { error = "read name of record " + std::to_string(i) + " must be 1..254 bytes"; return false; }
 			if (nc < 0 || nc > 65535) { error = "record " + std::to_string(i) + " has more than 65535 CIGAR operations"; return false; }
 		}
 		std::vector<size_t> off((size_t)n + 1, 0);
-		for (int64_t i = 0; i < n; ++i) off[i + 1] = off[i] + record_size(b, i);
+		for (int64_t k = 0; k < n; ++k) off[k + 1] = off[k] + record_size(b, rec(k));
 		const size_t base = pending.size();
 		pending.resize(base + off[n]);
 		uint8_t *dst = pending.data() + base;
-		parallel((size_t)n, [&](size_t lo, size_t hi) { for (size_t i = lo; i < hi; ++i) encode(b, (int64_t)i, dst + off[i]); });
+		parallel((size_t)n, [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; ++k) encode(b, rec((int64_t)k), dst + off[k]); });
 		n_records += n;
 		return flush(false);
 	}

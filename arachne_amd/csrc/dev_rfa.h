@@ -172,6 +172,54 @@ ARX_HDI int rfa_mapq_final(double v, const Cand &a, const int64_t *cen_start, co
 	return (mapq != mapq) ? (int)0x80000000 : (int)mapq;
 }
 
+// ---- what estimateMapQualities leaves in mapq_data of a read's active alignment for AppendBam's tags (aligner.go:847-889)
+struct ReadTags {
+	int32_t active;      // the read's active candidate (batch-global index)
+	int32_t second_best; // mapq_data.second_best: candidate index (batch-global), -1 for none
+	int32_t xs, as;      // int(mapq_data.second_best_score), int(mapq_data.score): truncated toward zero as Go's int() does
+	int32_t xm, xt;      // second_best.active_molecule; second_best in the active alignment's molecule (ids compared as they are, -1 == -1)
+	int32_t dm_n, dm_sum; // active alignments of the active alignment's molecule and the sum of their mismatches (0, 0: no molecule)
+};
+// One read: the (i, j) double loop of :863-883 over the read's and the mate's filtered candidates, collapsed as rfa_pair_best2 does --
+// for a fixed non-active i the molecule term is a constant, so the first j that reaches i's maximum is the one that sets the score,
+// and the raw score (molecule penalty 0) is 0.5 * pair_best[i] for that same j.  Evaluated in double in this form: 0.5 * x is exact,
+// so contraction cannot change a comparison.  cands / pair_best are the batch's arrays, [lo, hi) the read's and [m_lo, m_hi) the mate's.
+ARX_HDI ReadTags rfa_read_tags(const Cand *c, const int32_t *pair_best, int lo, int hi, int m_lo, int m_hi, int len_r, double log_mol_pen, int penalty)
+{
+	const double pen = (double)penalty, NEG = -1.7976931348623157e308;
+	ReadTags t;
+	t.active = -1; t.second_best = -1; t.xm = 0; t.xt = 0; t.dm_n = 0; t.dm_sum = 0;
+	int am = -1;
+	for (int j = m_lo; j < m_hi; ++j) if (c[j].in_filtered && c[j].active) am = j;
+	double best = -1000.0;
+	for (int i = lo; i < hi; ++i) {
+		if (!c[i].in_filtered) continue;
+		if (c[i].active) { t.active = i; continue; }
+		const int pb = pair_best[i];
+		if (pb == RFA_NO_PAIR) continue;
+		const double s = 0.5 * pb + (c[i].active_molecule ? 0.0 : log_mol_pen);
+		if (s > best) { best = s; t.second_best = i; }
+	}
+	if (t.second_best >= 0) t.xs = (int)(0.5 * pair_best[t.second_best]);
+	else { // scores[0] of appendPsuedocountAlignmentScore (aligner.go:781-790): the first value rfa_mapq_value pushes, same operations
+		double best_single = NEG;
+		for (int j = m_lo; j < m_hi; ++j) {
+			if (!c[j].in_filtered) continue;
+			const double s = 0.5 * c[j].lap2 + pen;
+			if (s > best_single) best_single = s;
+		}
+		const double pseudo = -10.0 - ((double)len_r - 25.0) * 0.5 + log_mol_pen;
+		t.xs = (int)(best_single + pseudo);
+	}
+	const int a = t.active;
+	t.as = (a >= 0 && am >= 0) ? (int)(0.5 * cand_pair_score2(c[a], c[am], 2 * penalty)) : 0;
+	if (t.second_best >= 0) {
+		t.xm = c[t.second_best].active_molecule ? 1 : 0;
+		t.xt = (a >= 0 && c[a].mol == c[t.second_best].mol) ? 1 : 0;
+	}
+	return t;
+}
+
 // ---- one barcode per workgroup
 //
 // The block handle B (hip_rt.h: HipBlock, 256 lanes; tests/hostsim: a sequential stand-in) provides

@@ -55,11 +55,48 @@ struct KMapq { // one read per lane: MAPQ of its active candidate; values a few 
 };
 struct KMapqPatch { Cand *cands; const int32_t *idx, *val; ARX_DEV void operator()(int k, int) const { cands[idx[k]].mapq = val[k]; } };
 
+ARX_HDI int rfa_barcode_of(const int32_t *bc_read_off, int n_barcodes, int r)
+{
+	int lo = 0, hi = n_barcodes;
+	while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (bc_read_off[mid] <= r) lo = mid; else hi = mid; }
+	return lo;
+}
+// setMoleculeDifferences as updateAlignmentsMoleculeStatus last applies it (aligner.go:526-545, 646): per (barcode, molecule) the number
+// of active alignments and the sum of their mismatches.  A molecule's active_alignments are the reads whose active candidate lies in it
+// (the count the RFA kernel keeps as mol_nact and oracle/arx_oracle_rfa.c as n_active).  One read per lane; slots at mol_off[barcode] + mol.
+struct KTagsMol {
+	const Cand *cands; const int32_t *cand_off, *bc_read_off; int n_barcodes; const int32_t *mol_off; int32_t *mol_n, *mol_sum;
+	ARX_DEV void operator()(int r, int) const
+	{
+		for (int i = cand_off[r]; i < cand_off[r + 1]; ++i) {
+			if (!cands[i].active) continue;
+			const int m = cands[i].mol;
+			if (m < 0) return;
+			const int s = mol_off[rfa_barcode_of(bc_read_off, n_barcodes, r)] + m;
+			ARX_ATOMIC_INC(&mol_n[s]); ARX_ATOMIC_ADD(&mol_sum[s], cands[i].mismatches);
+			return;
+		}
+	}
+};
+// One read per lane: rfa_read_tags on the pair scores KMapqPair left (RfaResult::d_pair_best), then the DM inputs of its molecule
+struct KTags {
+	const Cand *cands; const int32_t *cand_off, *bc_read_off; int n_barcodes; const double *log_mol_pen; const int32_t *lens, *pair_best; int penalty;
+	const int32_t *mol_off, *mol_n, *mol_sum; ReadTags *out;
+	ARX_DEV void operator()(int r, int) const
+	{
+		const int b = rfa_barcode_of(bc_read_off, n_barcodes, r), mr = r ^ 1;
+		ReadTags t = rfa_read_tags(cands, pair_best, cand_off[r], cand_off[r + 1], cand_off[mr], cand_off[mr + 1], lens[r], log_mol_pen[b], penalty);
+		if (t.active >= 0 && cands[t.active].mol >= 0) { const int s = mol_off[b] + cands[t.active].mol; t.dm_n = mol_n[s]; t.dm_sum = mol_sum[s]; }
+		out[r] = t;
+	}
+};
+
 struct RfaResult {
 	std::vector<int32_t> cand_off; std::vector<RfaBarcodeOut> bc;
 	Cand *d_cands = nullptr; int64_t n_cands = 0; int64_t n_host_mapq = 0;
-	// kept in HBM for the passes that follow (pipeline_post.h)
+	// kept in HBM for the passes that follow (pipeline_post.h, TagsStage)
 	int32_t *d_cand_off = nullptr, *d_bc_read_off = nullptr; int64_t *d_cen_start = nullptr, *d_cen_end = nullptr; int n_barcodes = 0, penalty = 0;
+	int32_t *d_pair_best = nullptr; double *d_lmp = nullptr; // KMapqPair's pair scores; calculateLogMoleculePenalty per barcode
 };
 
 template <class RT> struct RfaStage {
@@ -139,6 +176,7 @@ template <class RT> struct RfaStage {
 		if (nf > 0) host_mapq(rt, nf, d_flag, cands, res, bro, lmp, penalty, cen_start, cen_end, lens_host);
 		res.d_cands = cands; res.n_cands = NC;
 		res.d_cand_off = cand_off; res.d_bc_read_off = d_bro; res.d_cen_start = d_cs; res.d_cen_end = d_ce; res.n_barcodes = n_barcodes; res.penalty = penalty;
+		res.d_pair_best = pair_best; res.d_lmp = d_lmp;
 		return 0;
 	}
 
@@ -170,6 +208,33 @@ template <class RT> struct RfaStage {
 	{
 		memcpy(cand_off, res.cand_off.data(), 4 * ((size_t)b.n_reads + 1));
 		pipe.rt.d2h(cands, res.d_cands, sizeof(Cand) * (size_t)res.n_cands);
+	}
+};
+
+// arx_batch_tags: the per-read values of mapq_data that AppendBam writes (XS, AS, XM, XT, the second best for XC, DM), on the candidate
+// records and pair scores the RFA stage left in HBM.  Not part of arx_batch_rfa: callers that write no tags pay nothing for it.
+struct TagsResult { ReadTags *d_tags = nullptr; bool done = false; std::vector<size_t> mark; bool marked = false; };
+template <class RT> struct TagsStage {
+	static void run(Pipeline<RT> &pipe, const typename Pipeline<RT>::DeviceBatch &b, const RfaResult &rfa, TagsResult &res)
+	{
+		RT &rt = pipe.rt;
+		const int R = b.n_reads, NB = rfa.n_barcodes;
+		std::vector<int32_t> mol_off(NB + 1, 0);
+		for (int i = 0; i < NB; ++i) mol_off[i + 1] = mol_off[i] + rfa.bc[i].n_mol;
+		const int NM = mol_off[NB];
+		int32_t *d_mol_off = rt.template alloc<int32_t>(NB + 1), *mol_n = rt.template alloc<int32_t>(NM + 1), *mol_sum = rt.template alloc<int32_t>(NM + 1);
+		rt.h2d(d_mol_off, mol_off.data(), 4 * (size_t)(NB + 1));
+		rt.memset0(mol_n, 4 * (size_t)(NM + 1)); rt.memset0(mol_sum, 4 * (size_t)(NM + 1));
+		ReadTags *tags = rt.template alloc<ReadTags>(R + 1);
+		KTagsMol km{rfa.d_cands, rfa.d_cand_off, rfa.d_bc_read_off, NB, d_mol_off, mol_n, mol_sum};
+		rt.launch_wide("tags_mol", R, km);
+		KTags kt{rfa.d_cands, rfa.d_cand_off, rfa.d_bc_read_off, NB, rfa.d_lmp, b.lens, rfa.d_pair_best, rfa.penalty, d_mol_off, mol_n, mol_sum, tags};
+		rt.launch_wide("tags", R, kt);
+		res.d_tags = tags; res.done = true;
+	}
+	static void fetch(Pipeline<RT> &pipe, const typename Pipeline<RT>::DeviceBatch &b, const TagsResult &res, ReadTags *out)
+	{
+		pipe.rt.d2h(out, res.d_tags, sizeof(ReadTags) * (size_t)b.n_reads);
 	}
 };
 

@@ -7,8 +7,14 @@ barcode sets, `-t` workers calling DoRFAForOneBarcode, one BamThread writing, ba
         logic on host threads)  ->  arx_bam_write (BGZF on host threads) into the worker's own BAM
 
 Everything between the file reads and the file writes goes through the C ABI of include/arachne_amd.h; this module is the host-side
-mirror of the Go driver (Python here because the image has no Go toolchain; INTEGRATION.md has the Go form).  The split /
-supplementary records and the position-bucketed second copy of every record the reference writes (bamwriter.go:279-281) are not produced.
+mirror of the Go driver (Python here because the image has no Go toolchain; INTEGRATION.md has the Go form).
+
+Two layouts.  layout="workers" (the default): one `<out_prefix>.k.bam` per worker with the primary record of every read (arx_recbuf_build).
+layout="reference": the reference's output directory (CreateBAMs, bamwriter.go:127-190) -- bc_sorted_bam.bam, the position buckets of
+`chunk` bases and ZZZ_unmapped_pos_bucketed.bam -- with the reference's record set (arx_batch_tags + arx_recbuf_build_full: split records,
+full tags) and every record written twice, to bc_sorted_bam.bam and to its bucket (AppendBams, :279-281).  All workers append to shared
+writers, one lock per writer: a batch's records are contiguous and in order inside every file, the order of batches across workers is
+as arbitrary as the reference's goroutines make it.
 """
 from __future__ import annotations
 
@@ -25,11 +31,19 @@ _TRACE = bool(os.environ.get("ARX_E2E_TRACE"))
 
 
 def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int = 250_000, bam_threads: int = 8, rec_threads: int = 8, level: int = 1,
-        penalty: float = -4, lib_path: str = api.LIB_PATH, warm_passes: int = 0):
+        penalty: float = -4, lib_path: str = api.LIB_PATH, warm_passes: int = 0, layout: str = "workers", chunk: int = 40_000_000,
+        read_groups: str = "", sample_id: str = ""):
     """fastq_pairs: [(r1, r2), ...] barcode-sorted files (plain or gzip), one worker each.  -> stats dict (pairs, seconds, pairs/s, per-stage
     seconds summed over workers).  warm_passes: untimed passes over the same files first, through the same batch handles -- a handle's first
     batch pays for its work memory (hipMalloc of several GiB: seconds once a 69 GB k-mer table sits beside it), which a run over a whole
-    read set pays once; the stats are those of the last pass."""
+    read set pays once; the stats are those of the last pass.  layout="reference": out_prefix is the output directory of the reference's
+    layout (see the module docstring; chunk = -p/--partitions, read_groups / sample_id as the reference's flags); warm_passes must be 0."""
+    if layout == "reference":
+        if warm_passes:
+            raise ValueError("layout='reference' writes its files once: warm_passes must be 0")
+        return _run_reference(ref, fastq_pairs, out_prefix, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, chunk, read_groups, sample_id)
+    if layout != "workers":
+        raise ValueError(f"unknown layout {layout!r}")
     names, offs, clens, alt, l_pac = ref.contigs()
     stats = dict(pairs=0, records=0, batches=0, feeder_s=0.0, device_s=0.0, fetch_s=0.0, records_s=0.0, bam_s=0.0)
     lock = threading.Lock()
@@ -146,4 +160,98 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
     stats["warm_passes"] = warm_passes
     stats["pairs_per_s"] = stats["pairs"] / stats["seconds"] if stats["seconds"] > 0 else 0.0
     stats["workers"] = len(fastq_pairs)
+    return stats
+
+
+def reference_header(read_groups: str = "", date: str | None = None) -> str:
+    """The header lines CreateBAM adds to every file (bamwriter.go:74-109): one @RG per comma-separated read group of at least five ':' fields
+    (sample:library:gem_group:flowcell:lane -> ID, LB = library.gem_group, PL ILLUMINA, PU = ID, SM = sample, DT = the run time), then @PG."""
+    if date is None:
+        date = time.strftime("%Y-%m-%dT%H:%M:%S%z")
+    out = ""
+    for rg in read_groups.split(",") if read_groups else []:
+        f = rg.split(":")
+        if len(f) < 5:
+            continue
+        out += f"@RG\tID:{rg}\tPL:ILLUMINA\tPU:{rg}\tLB:{f[1]}.{f[2]}\tSM:{f[0]}\tDT:{date}\n"
+    return out + "@PG\tID:arachne\tPN:arachne\tCL:arachne_amd\n"
+
+
+def _run_reference(ref, fastq_pairs, out_dir, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, chunk, read_groups, sample_id):
+    names, offs, clens, alt, l_pac = ref.contigs()
+    table = api.bucket_table(names, clens, chunk, lib_path=lib_path)
+    os.makedirs(out_dir, exist_ok=True)
+    hdr = reference_header(read_groups)
+    files = ["bc_sorted_bam.bam"] + table.files
+    writers = [api.BamWriter(os.path.join(out_dir, f), names, clens, extra_header=hdr, threads=bam_threads, level=level, lib_path=lib_path) for f in files]
+    locks = [threading.Lock() for _ in writers]
+    stats = dict(pairs=0, records=0, batches=0, feeder_s=0.0, device_s=0.0, fetch_s=0.0, records_s=0.0, bam_s=0.0)
+    slock = threading.Lock()
+    errors = []
+
+    def worker(k, r1, r2):
+        batch = None
+        fd = api.Feeder(r1, r2, lib_path=lib_path)
+        rb = api.RecBuf(lib_path=lib_path)
+        loc = dict(pairs=0, records=0, batches=0, feeder_s=0.0, device_s=0.0, fetch_s=0.0, records_s=0.0, bam_s=0.0)
+        buf = {}
+        try:
+            while True:
+                t0 = time.time()
+                nx = fd.next_raw(pairs_per_batch)
+                t1 = time.time()
+                if nx is None:
+                    break
+                sb, v = nx
+                batch = batch.reset(v["bases"], v["lens"]) if batch is not None else ref.batch(v["bases"], v["lens"])
+                batch.run(api.STAGE_ALN)
+                batch.rfa(v["set_pair_off"], v["do_rfa"], penalty=penalty, fetch=False)
+                t2 = time.time()
+                batch.fetch_into(buf)
+                post = batch.post()                      # arx_batch_post, then the tags on top of it (a later post would discard them)
+                tags = batch.tags()
+                t3 = time.time()
+                view, bucket = rb.build_full(sb, buf["cand_off"], buf["cands"], buf["alns"], buf["cigars"], post["post"], post["split"], post["mm_ref"],
+                                             post["mm_read"], tags, table, threads=rec_threads)
+                order = np.argsort(bucket, kind="stable")
+                cuts = np.searchsorted(bucket[order], np.arange(len(table.files) + 1))
+                t4 = time.time()
+                with locks[0]:
+                    writers[0].write_view(view)
+                for f in range(len(table.files)):
+                    if cuts[f + 1] > cuts[f]:
+                        with locks[f + 1]:
+                            writers[f + 1].write_select(view, order[cuts[f]:cuts[f + 1]])
+                t5 = time.time()
+                loc["pairs"] += int(v["n_pairs"]); loc["records"] += int(view.n_records); loc["batches"] += 1
+                loc["feeder_s"] += t1 - t0; loc["device_s"] += t2 - t1; loc["fetch_s"] += t3 - t2; loc["records_s"] += t4 - t3; loc["bam_s"] += t5 - t4
+        except BaseException as e:  # noqa: BLE001 -- reported by the caller's thread
+            errors.append(e)
+        finally:
+            if batch is not None:
+                batch.free()
+            rb.free()
+            fd.close()
+        with slock:
+            for key, val in loc.items():
+                stats[key] += val
+
+    t = time.time()
+    th = [threading.Thread(target=worker, args=(k, r1, r2)) for k, (r1, r2) in enumerate(fastq_pairs)]
+    for x in th:
+        x.start()
+    for x in th:
+        x.join()
+    t5 = time.time()
+    stats["bam_bytes"] = 0
+    for w in writers:
+        stats["bam_bytes"] += w.close()["bytes_out"]
+    stats["bam_s"] += time.time() - t5
+    if errors:
+        raise errors[0]
+    stats["seconds"] = time.time() - t
+    stats["warm_passes"] = 0
+    stats["pairs_per_s"] = stats["pairs"] / stats["seconds"] if stats["seconds"] > 0 else 0.0
+    stats["workers"] = len(fastq_pairs)
+    stats["files"] = files
     return stats

@@ -164,6 +164,24 @@ int arx_batch_post(arx_ctx *ctx, arx_batch *b, int64_t *n_mm);
 /* post[n_cands], split[n_reads], mm_ref[n_mm], mm_read[n_mm]; any of them may be NULL */
 int arx_batch_post_fetch(arx_ctx *ctx, arx_batch *b, arx_cand_post *post, arx_split *split, int32_t *mm_ref, int32_t *mm_read);
 
+/* ---- what estimateMapQualities leaves in mapq_data of every read's active alignment (aligner.go:847-889) and AppendBam writes as
+ * XS / AS / XC / XM / XT / DM (bamwriter.go:390-460, 555-563), on the candidates arx_batch_rfa left on the device (needs arx_batch_rfa
+ * first; a later arx_batch_rfa or arx_batch_post discards the result, so call it after arx_batch_post).  Not part of arx_batch_rfa: a
+ * caller that writes no tags pays nothing.  second_best: the first non-active filtered candidate, in candidate order, whose best pair
+ * score with the molecule term beats the running maximum (start -1000); xs = int(0.5 * its best pair score), or without one int(the
+ * pseudo-count score of appendPsuedocountAlignmentScore, log_molecule_penalty included); as = int(0.5 * the pair score of the active
+ * pair); integers truncated toward zero as Go's int() does.  dm_n / dm_sum: setMoleculeDifferences' inputs for the active candidate's
+ * molecule (molecule_difference = dm_sum / dm_n). */
+typedef struct {
+	int32_t active;                 /* the read's active candidate (index into arx_batch_rfa_fetch's cands) */
+	int32_t second_best;            /* mapq_data.second_best: candidate index, -1 for none */
+	int32_t xs, as;                 /* int(mapq_data.second_best_score), int(mapq_data.score) */
+	int32_t xm, xt;                 /* second_best.active_molecule; second_best.molecule_id == molecule_id (0 without a second best) */
+	int32_t dm_n, dm_sum;           /* active alignments in the active candidate's molecule, sum of their mismatches (0, 0: no molecule) */
+} arx_read_tags;
+int arx_batch_tags(arx_ctx *ctx, arx_batch *b);
+int arx_batch_tags_fetch(arx_ctx *ctx, arx_batch *b, arx_read_tags *out /* n_reads */);
+
 /* ---- in front of the path: the reference's paired FASTQ reader (src/fastqreader/reader.go) re-shaped to deliver super-batches of
  * whole barcode sets -- what its producer loop (aligner.go:335-358) hands to one worker per set, one read pair per cgo call.
  * A set is what ReadBarcodeSet (reader.go:209-300) returns: consecutive records of one barcode, at most 30000, 201-record chunks
@@ -212,6 +230,9 @@ typedef struct {
 int arx_bam_open(const char *path, int32_t n_contigs, const char *const *names, const int32_t *lens, const char *extra_header, int32_t threads, int32_t level,
                  arx_bam **out, char *msg, int32_t msg_cap);
 int arx_bam_write(arx_bam *w, const arx_bam_batch *batch);
+/* encodes and writes only records idx[0..n) of the batch, in that order (the position buckets of the reference's layout: every record
+ * goes to the barcode-sorted BAM and to one bucket, bamwriter.go:279-281); the bytes of a record are those arx_bam_write writes for it */
+int arx_bam_write_select(arx_bam *w, const arx_bam_batch *batch, const int64_t *idx, int64_t n);
 /* stats[4] (may be NULL): records, BGZF blocks, uncompressed bytes, file bytes */
 int arx_bam_close(arx_bam *w, int64_t *stats);
 const char *arx_bam_error(arx_bam *w);
@@ -226,6 +247,30 @@ typedef struct arx_recbuf arx_recbuf;
 int arx_recbuf_create(arx_recbuf **out);
 int arx_recbuf_build(arx_recbuf *rb, const arx_super_batch *sb, const int32_t *cand_off, const arx_cand *cands, const arx_aln *alns, const uint32_t *cigars,
                      const arx_cand_post *post, int32_t threads, arx_bam_batch *view);
+/* The reference's position buckets (CreateBAMs, bamwriter.go:134-188): a contig longer than chunk gets ceil(len / chunk) files of its own,
+ * "%06d-<name>_%010d_pos_bucketed.bam" (contig index, chunk start); shorter contigs are packed into the current file while the running
+ * size + len <= chunk (a multi-chunk contig does not reset the running size); "ZZZ_unmapped_pos_bucketed.bam" comes last.  A mapped record
+ * of contig rid at pos goes to file contig_file[rid] + pos / chunk, an unmapped one to *n_files - 1.  file_names: cap_files rows of
+ * name_w bytes (NUL-terminated), may be NULL; ARX_E_ARG when the table needs more rows or a longer row. */
+int arx_bucket_table(int32_t n_contigs, const char *const *names, const int32_t *lens, int64_t chunk, int32_t *contig_file /* n_contigs */,
+                     int32_t *n_files, char *file_names, int32_t cap_files, int32_t name_w);
+/* The whole record set of DoDumpToBam (bamwriter.go:278-566, 635-689): every read's primary record, then its split record (flag 0x100,
+ * hard-clipped) when arx_split names one, with the full tag set RG XS XC AC AS XM AM XT SA BX VX DM in the reference's order, and the
+ * order effects of AppendBam's in-place "unmapped" mutation (pos = -1, mapq = 0 on a record the score rule unmaps, seen by every record
+ * written after it).  n_records = 2 * n_pairs + splits.  DM is written on primary records only (see csrc/bam_records.h).  post is
+ * required; bucket[n_records] (pointer into the buffer, valid with the view): the position bucket of every record per arx_bucket_table. */
+typedef struct {
+	const arx_split *split;         /* arx_batch_post_fetch: n_reads */
+	const int32_t *mm_ref, *mm_read;/* arx_batch_post_fetch: the mismatch lists */
+	const arx_read_tags *tags;      /* arx_batch_tags_fetch: n_reads */
+	int32_t n_contigs, pad;
+	const char *const *contig_names;/* for SA:Z */
+	const int32_t *contig_file;     /* arx_bucket_table */
+	int64_t chunk;
+	int32_t unmapped_file, pad2;
+} arx_recbuf_full;
+int arx_recbuf_build_full(arx_recbuf *rb, const arx_super_batch *sb, const int32_t *cand_off, const arx_cand *cands, const arx_aln *alns, const uint32_t *cigars,
+                          const arx_cand_post *post, const arx_recbuf_full *full, int32_t threads, arx_bam_batch *view, const int32_t **bucket);
 const char *arx_recbuf_error(arx_recbuf *rb);
 void arx_recbuf_free(arx_recbuf *rb);
 
