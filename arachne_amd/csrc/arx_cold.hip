@@ -13,6 +13,7 @@ __device__ unsigned long long g_cstat[24];
 #include "pipeline.h"
 #include "dev_regs_wave.h"
 #include "dev_chain_wave.h"
+#include "dev_chain_group.h"
 #ifdef ARX_WSORT_CHECK
 static void wsort_report(hipStream_t st, const char *who) { unsigned long long h[2]; hipStreamSynchronize(st); hipMemcpyFromSymbol(h, HIP_SYMBOL(arx::g_wsort_bad), sizeof h); fprintf(stderr, "wsort check after %s: %llu sorts so far, %llu differ from ks_introsort\n", who, h[1], h[0]); }
 #else
@@ -125,10 +126,16 @@ template <> void HipRT::run_rescue_heavy<KRescueStep>(const char *nm, int n, con
 // lane 0 alone runs chain_and_filter(), kept for A/B runs); the kept chains and their seeds go to HBM as from KChain.
 struct ChainLds { // carved out of the dynamic LDS block for a read with n occurrences
 	Seed *occ; int32_t *rid, *next; Chain *ctmp; BtNode *nodes; int32_t *iscr, *xch; int cap_nodes;
-	static __host__ __device__ size_t bytes(int n) { return (size_t)n * (sizeof(Seed) + 4 + 4 + sizeof(Chain) + 28) + ((size_t)n / 3 + 4) * sizeof(BtNode) + 64; }
-	__device__ void carve(unsigned char *p, int n)
+	// B-tree nodes: n / 3 + 4 for the heavy kernel; group_nodes(n) for the 16-lane groups, whose four reads share a workgroup's LDS.  A B-tree
+	// of minimum degree 5 holding k keys has at most (k - 1) / 4 + 1 nodes (every node but the root holds at least 4 keys, and a node is only
+	// ever added by a split), so neither pool can run out.
+	static __host__ __device__ int group_nodes(int n) { return n / 4 + 2; }
+	static __host__ __device__ size_t bytes(int n, int nodes = -1) { return (size_t)n * (sizeof(Seed) + 4 + 4 + sizeof(Chain) + 28) + (size_t)(nodes < 0 ? n / 3 + 4 : nodes) * sizeof(BtNode) + 64; }
+	// one group's share, 16-byte aligned, with the B-tree traversal's stack (48 ints) at its end
+	static __host__ __device__ size_t group_bytes(int n) { return ((bytes(n, group_nodes(n)) + 15) & ~(size_t)15) + 48 * 4; }
+	__device__ void carve(unsigned char *p, int n, int n_nodes = -1)
 	{
-		cap_nodes = n / 3 + 4;
+		cap_nodes = n_nodes < 0 ? n / 3 + 4 : n_nodes;
 		occ = (Seed *)p; p += (size_t)n * sizeof(Seed);
 		ctmp = (Chain *)p; p += (size_t)n * sizeof(Chain);
 		nodes = (BtNode *)p; p += (size_t)cap_nodes * sizeof(BtNode);
@@ -199,6 +206,63 @@ template <> void HipRT::run_chain_heavy<KChain>(const char *nm, int n_reads, con
 	  fprintf(stderr, "cstat reads %llu | sums (100 MHz ticks): chaining %llu traverse+weights %llu sort %llu filter %llu output %llu | worst read: total %llu = %llu %llu %llu %llu %llu, n_occ %llu kept %llu\n",
 	          h[5], h[0], h[1], h[2], h[3], h[4], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15]); }
 #endif
+}
+
+// Reads with lo .. cap occurrences (dev_chain_group.h): one read per 16-lane group, four per 64-lane workgroup, each group with its own
+// `cap`-occurrence share of the dynamic LDS block, no workgroup barrier.  list = null (the first launch, 1-16 occurrences): a group walks the
+// batch 16 reads at a time (grid-stride over tiles of 16) -- its lanes load the 16 occurrence counts side by side, a ballot masked to the
+// group names the reads of the class, the group chains them one after the other.  list != null (the second launch): the groups take the
+// listed reads grid-stride.
+static_assert(CHAIN_G16_MAX < OPT_MAX_OCC, "g16_chain_and_filter takes frac_rep = 0: no interval of its reads has more than max_occ occurrences");
+static __global__ void __launch_bounds__(64) k_chain_g16(KChain f, int n_reads, int lo, int cap, const int32_t *list, const int32_t *n_list)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds_g16[];
+	const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4, gid = blockIdx.x * 4 + grp, n_groups = gridDim.x * 4;
+	unsigned char *mine = lds_g16 + (size_t)grp * ChainLds::group_bytes(cap);
+	int32_t *tst = (int32_t *)(mine + ChainLds::group_bytes(cap) - 48 * 4);
+	const int n_items = list ? *n_list : (n_reads + 15) / 16; // listed reads, or tiles of 16 reads
+	for (int t = gid; t < n_items; t += n_groups) {
+		const int rl = list ? (sub == 0 ? list[t] : 0) : t * 16 + sub;
+		int gl = 0, nl = 0, ll = 0;
+		if ((list ? sub == 0 : true) && rl < n_reads) { gl = f.occ_off[rl]; nl = f.occ_off[rl + 1] - gl; ll = f.lens[rl]; }
+		const unsigned mask = (unsigned)(__ballot(rl < n_reads && nl >= lo && nl <= cap) >> (grp * 16)) & 0xffffu;
+		for (unsigned mm = mask; mm; mm &= mm - 1) { // group-uniform
+			const int j = __builtin_ctz(mm), r = __shfl(rl, j, 16);
+			const int g0 = __shfl(gl, j, 16), n = __shfl(nl, j, 16), len = __shfl(ll, j, 16);
+			ChainLds L; L.carve(mine, n, ChainLds::group_nodes(n));
+			{ // in: the occurrences (16 bytes each), their contigs and the contigs' ALT flags
+				const uint32_t *src = (const uint32_t *)(f.occ_seed + g0);
+				uint32_t *dst = (uint32_t *)L.occ;
+				for (int k = sub; k < n * (int)(sizeof(Seed) / 4); k += 16) dst[k] = src[k];
+				for (int k = sub; k < n; k += 16) { const int rid = f.occ_rid[g0 + k]; L.rid[k] = rid; L.iscr[k] = rid >= 0 && f.ix.ann_alt[rid] ? 1 : 0; }
+			}
+			g16_sync();
+			int m = g16_chain_and_filter(f.ix, len, L.occ, L.rid, n, L.next, L.ctmp, L.nodes, L.cap_nodes, L.iscr, f.cout + g0, f.sout + g0, g0, L.xch, tst);
+			if (sub == 0) {
+				if (m < 0) { raise_err(f.err, ERR_POOL_OVERFLOW); m = 0; }
+				f.n_chain[r] = m;
+			}
+			g16_sync(); // the group's next read overwrites this one's LDS share
+		}
+	}
+}
+template <> void HipRT::run_chain_group<KChain>(const char *nm, int n_reads, const KChain &f)
+{
+	if (f.grp_max < 1 || n_reads <= 0) return;
+	Scope sc(*this, nm, n_reads);
+	static const size_t lds_cu = 160 << 10; // LDS of one CU: the workgroups a CU holds are what this latency-bound kernel scales with
+	if (!chain_group_attr_set) { ARX_HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_g16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * ChainLds::group_bytes(CHAIN_G16_MAX)))); chain_group_attr_set = true; }
+	// two classes by LDS footprint: 1-16 occurrences (11 KB per workgroup: 14 per CU) and 17 .. grp_max (36 KB at 63: 4 per CU)
+	const int tiles = (n_reads + 15) / 16;
+	for (int c = 0; c < 2; ++c) {
+		const int lo = c == 0 ? 1 : CHAIN_G16_SMALL + 1, cap = c == 0 ? (f.grp_max < CHAIN_G16_SMALL ? f.grp_max : CHAIN_G16_SMALL) : f.grp_max;
+		if (c == 1 && cap < lo) continue;
+		const size_t lds = 4 * ChainLds::group_bytes(cap < lo ? lo : cap);
+		const int per_cu = lds_cu / lds < 16 ? (int)(lds_cu / lds) : 16, blocks = c == 1 || (tiles + 3) / 4 > n_cu * per_cu ? n_cu * per_cu : (tiles + 3) / 4;
+		hipLaunchKernelGGL(k_chain_g16, dim3(blocks), dim3(64), lds, stream, f, n_reads, lo, cap, c == 0 ? (const int32_t *)nullptr : (const int32_t *)f.mid_list,
+		                   (const int32_t *)f.n_mid);
+	}
+	ARX_HIP_CHECK(hipGetLastError());
 }
 
 // One read with a long region list per 64-lane workgroup: the list goes to LDS, the wavefront runs mem_sort_dedup_patch on it

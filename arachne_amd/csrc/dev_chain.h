@@ -117,10 +117,10 @@ ARX_DEV bool bt_put(BTree &b, int ci) // kb_putp + __kb_putp_aux (kbtree.h:193-2
 	}
 }
 
-// in-order traversal (kbtree.h:352-375) with an explicit stack; the tree height is tiny (<= 8 for 10^5 keys)
-ARX_DEV int bt_traverse(const BTree &b, int *out)
+// in-order traversal (kbtree.h:352-375) with an explicit stack of 3 x 16 ints at st; the tree height is tiny (<= 8 for 10^5 keys)
+ARX_DEVI int bt_traverse_st(const BTree &b, int *out, int *st)
 {
-	int st_x[16], st_i[16], st_p[16], top = 0, n = 0;
+	int *st_x = st, *st_i = st + 16, *st_p = st + 32, top = 0, n = 0;
 	st_x[0] = b.root; st_i[0] = 0; st_p[0] = 0;
 	while (top >= 0) {
 		const BtNode &x = b.nodes[st_x[top]];
@@ -134,6 +134,7 @@ ARX_DEV int bt_traverse(const BTree &b, int *out)
 	}
 	return n;
 }
+ARX_DEV int bt_traverse(const BTree &b, int *out) { int st[48]; return bt_traverse_st(b, out, st); }
 
 // test_and_merge (bwamem.c:190-211) on a chain whose seeds form a linked list (head = seeds[0], tail = last)
 ARX_DEVI int test_and_merge(int64_t l_pac, Chain &c, const Seed *occ, int *next, int g, int seed_rid)
@@ -187,8 +188,9 @@ ARX_DEV float chain_frac_rep(int len, const Biv *intv, int n_intv)
 // mem_chain's loop (bwamem.c:273-307): every occurrence, in order, joins the chain the B-tree finds for it or starts a new one.
 // occ_rid[g] = bns_intv2rid of occurrence g (KOccRid: computed for all occurrences of the batch side by side -- two binary searches
 // over the contig table that this one-thread loop used to wait for, occurrence after occurrence).  Returns the number of chains, -1 on
-// pool exhaustion; bt is left ready for bt_traverse.
-ARX_DEV int chain_build(const IndexView &ix, const Seed *occ, const int32_t *occ_rid, int n_occ, int *next, Chain *ctmp, BTree &bt, BtNode *nodes, int cap_nodes, float frac_rep)
+// pool exhaustion; bt is left ready for bt_traverse.  occ_alt (optional): ann_alt of every occurrence's contig, looked up beforehand.
+ARX_DEV int chain_build(const IndexView &ix, const Seed *occ, const int32_t *occ_rid, int n_occ, int *next, Chain *ctmp, BTree &bt, BtNode *nodes, int cap_nodes, float frac_rep,
+                        const int32_t *occ_alt = nullptr)
 {
 	bt.nodes = nodes; bt.ch = ctmp; bt.n_nodes = 0; bt.cap_nodes = cap_nodes; bt.n_keys = 0;
 	bt.root = bt_new(bt);
@@ -205,7 +207,7 @@ ARX_DEV int chain_build(const IndexView &ix, const Seed *occ, const int32_t *occ
 		if (to_add) {
 			Chain &c = ctmp[n_ch];
 			c.pos = s.rbeg; c.rid = rid; c.n = 1; c.head = c.tail = g; next[g] = -1;
-			c.is_alt = ix.ann_alt[rid] ? 1 : 0;
+			c.is_alt = occ_alt ? occ_alt[g] : ix.ann_alt[rid] ? 1 : 0;
 			c.w = 0; c.kept = 0; c.first = -1; c.seed_off = 0; c.frac_rep = frac_rep;
 			if (!bt_put(bt, n_ch)) return -1;
 			++n_ch;
@@ -229,25 +231,13 @@ ARX_DEV int chain_emit(int n, const int *ord, const Chain *ctmp, const Seed *occ
 	return m;
 }
 
-// One read: occurrences [g0, g1) (already located, in interval order) -> filtered chains + their seeds, compacted.
-// Pools are per-read slices: ctmp/cout/sout/next have g1-g0 slots, iscr 7*(g1-g0) ints, nodes cap_nodes entries.
-// Returns the number of chains kept (mem_chain + mem_chain_flt), or -1 on pool exhaustion.
-ARX_DEV int chain_and_filter(const IndexView &ix, int len, const Biv *intv, int n_intv, const Seed *occ, const int32_t *occ_rid, int n_occ,
-                             int *next, Chain *ctmp, BtNode *nodes, int cap_nodes, int *iscr, Chain *cout, Seed *sout, int sout_base)
+// mem_chain_flt's ranking and filter (bwamem.c:327-371) on the n chains of ord = iscr[0, n) whose weights are set: sorts ord by weight
+// (klib's introsort: its order of equal weights is part of the result) and sets every chain's `kept` and `first`.
+// iscr: 7 * n_occ ints (ord, then the filter's arrays by rank).
+ARX_DEV void chain_rank_filter(int n, int n_occ, Chain *ctmp, const Seed *occ, int *iscr)
 {
-	if (len < OPT_MIN_SEED_LEN || n_occ == 0) return 0;
-	ARX_CHAIN_T(0);
-	BTree bt;
-	const int n_ch = chain_build(ix, occ, occ_rid, n_occ, next, ctmp, bt, nodes, cap_nodes, chain_frac_rep(len, intv, n_intv));
-	if (n_ch < 0) return -1;
-	ARX_CHAIN_T(1);
-	if (n_ch == 0) return 0;
-	int *ord = iscr, *kept_idx = iscr + n_occ; // iscr: 7 * n_occ ints
+	int *ord = iscr, *kept_idx = iscr + n_occ;
 	int *qb_ = iscr + 2 * n_occ, *qe_ = iscr + 3 * n_occ, *w_ = iscr + 4 * n_occ, *alt_ = iscr + 5 * n_occ, *first_ = iscr + 6 * n_occ; // by rank in `ord`
-	int n = bt_traverse(bt, ord); // chains in key order = the array mem_chain returns
-	// mem_chain_flt (bwamem.c:327-385)
-	for (int i = 0; i < n; ++i) { Chain &c = ctmp[ord[i]]; c.first = -1; c.kept = 0; c.w = chain_weight(c, occ, next); }
-	ARX_CHAIN_T(2);
 	WeightGt gt; gt.c = ctmp;
 	ks_introsort(n, ord, gt);
 	ARX_CHAIN_T(3);
@@ -294,6 +284,27 @@ ARX_DEV int chain_and_filter(const IndexView &ix, int len, const Biv *intv, int 
 		ctmp[ord[kept_idx[i]]].first = f;
 		if (f >= 0) ctmp[ord[f]].kept = 1;
 	}
+}
+
+// One read: occurrences [g0, g1) (already located, in interval order) -> filtered chains + their seeds, compacted.
+// Pools are per-read slices: ctmp/cout/sout/next have g1-g0 slots, iscr 7*(g1-g0) ints, nodes cap_nodes entries.
+// Returns the number of chains kept (mem_chain + mem_chain_flt), or -1 on pool exhaustion.
+ARX_DEV int chain_and_filter(const IndexView &ix, int len, const Biv *intv, int n_intv, const Seed *occ, const int32_t *occ_rid, int n_occ,
+                             int *next, Chain *ctmp, BtNode *nodes, int cap_nodes, int *iscr, Chain *cout, Seed *sout, int sout_base)
+{
+	if (len < OPT_MIN_SEED_LEN || n_occ == 0) return 0;
+	ARX_CHAIN_T(0);
+	BTree bt;
+	const int n_ch = chain_build(ix, occ, occ_rid, n_occ, next, ctmp, bt, nodes, cap_nodes, chain_frac_rep(len, intv, n_intv));
+	if (n_ch < 0) return -1;
+	ARX_CHAIN_T(1);
+	if (n_ch == 0) return 0;
+	int *ord = iscr; // iscr: 7 * n_occ ints
+	int n = bt_traverse(bt, ord); // chains in key order = the array mem_chain returns
+	// mem_chain_flt (bwamem.c:327-385)
+	for (int i = 0; i < n; ++i) { Chain &c = ctmp[ord[i]]; c.first = -1; c.kept = 0; c.w = chain_weight(c, occ, next); }
+	ARX_CHAIN_T(2);
+	chain_rank_filter(n, n_occ, ctmp, occ, iscr);
 	ARX_CHAIN_T(4);
 	const int m = chain_emit(n, ord, ctmp, occ, next, cout, sout, sout_base);
 	ARX_CHAIN_T(5);

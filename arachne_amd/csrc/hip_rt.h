@@ -289,8 +289,14 @@ struct HipRT {
 	// chaining of the reads with many seed occurrences, one wavefront per read on a working set in LDS (arx_cold.hip); f.heavy_list / f.n_heavy
 	bool chain_heavy_ok() const { return !(getenv("ARX_CHAIN_HEAVY") && atoi(getenv("ARX_CHAIN_HEAVY")) == 0); }
 	template <class F> void run_chain_heavy(const char *nm, int n_reads, const F &f);
+	// opt-in (ARX_CHAIN_GROUP=1): chaining of the reads below the heavy kernel's threshold, one 16-lane group per read on a working set in LDS
+	// (arx_cold.hip: k_chain_g16; f.grp_max, f.mid_list / f.n_mid).  Default: every such read is chained by its own thread in HBM (KChain /
+	// KChainMid) -- the group form measured no faster (profiles/chain_group/)
+	bool chain_group_ok() const { return getenv("ARX_CHAIN_GROUP") && atoi(getenv("ARX_CHAIN_GROUP")) != 0; }
+	template <class F> void run_chain_group(const char *nm, int n_reads, const F &f);
 	bool rescue_heavy_attr_set = false;
 	bool chain_heavy_attr_set = false; // the 128 KB dynamic-LDS opt-in of k_chain_heavy was made on this runtime's device
+	bool chain_group_attr_set = false; // likewise the dynamic-LDS opt-in of k_chain_g16 (above 64 KB when ARX_CHAIN_HEAVY_MIN is raised)
 	bool dedup_heavy_ok() const { return !(getenv("ARX_DEDUP_HEAVY") && atoi(getenv("ARX_DEDUP_HEAVY")) == 0); }
 	template <class F> void run_dedup_heavy(const char *nm, int n_reads, const F &f); // likewise the region lists of such reads (f.eh_words ints of scratch per workgroup)
 	template <class F> void launch_cold_impl(const char *nm, int n, const F &f, bool wide = false)

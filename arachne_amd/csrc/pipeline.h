@@ -13,6 +13,7 @@
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 #include "arx_dev.h"
 #include "dev_fm.h"
 #include "dev_chain.h"
@@ -222,6 +223,10 @@ struct KOccRid {
 // round trips -- while the other 99.9 % finish in a quarter of it.  KChain hands such a read to k_chain_heavy (arx_cold.hip): one
 // wavefront per read, the read's working set in LDS.
 constexpr int CHAIN_HEAVY_MIN = 64, CHAIN_LDS_OCC = 832; // 832 occurrences x 154 B of working set = 128 KB of a CU's 160 KB LDS
+// Opt-in (ARX_CHAIN_GROUP=1, where the runtime has it): the reads below that threshold go to k_chain_g16 (arx_cold.hip, dev_chain_group.h),
+// one read per 16-lane group with its working set in LDS, in two classes -- 1-16 occurrences and 17 up to the threshold, at most
+// CHAIN_G16_MAX (18 KB of LDS per read).  Not the default: measured, it is no faster (profiles/chain_group/).
+constexpr int CHAIN_G16_SMALL = 16, CHAIN_G16_MAX = 127;
 struct KChain {
 	IndexView ix; const int32_t *lens; const Biv *intv; const int32_t *n_intv, *occ_off; const Seed *occ_seed; const int32_t *occ_rid;
 	int32_t *next; Chain *ctmp; BtNode *nodes; int32_t *iscr; Chain *cout; Seed *sout; int32_t *n_chain; uint32_t *err;
@@ -229,10 +234,20 @@ struct KChain {
 	// reads between the typical few occurrences and the heavy ones (99 % of a GRCh38-size batch has at most 15, 0.6 % has 16-63): listed and
 	// chained by a launch of their own, so that a wavefront of 64 typical reads does not wait for the one read with 40 (null / 0: off)
 	int32_t *mid_list = nullptr, *n_mid = nullptr; int32_t mid_min = 0, mid_cap = 0;
+	// the group path (k_chain_g16; grp_max = 0: off): the reads with 1-16 occurrences (99 %) are k_chain_g16's, which finds them itself, 16
+	// reads' counts per round trip (an atomic per read on a list counter made this pass 30 ms); those with 17 .. grp_max are listed in mid_list
+	// for its second launch; every other read that no heavy launch takes (no occurrences, or beyond the heavy kernel's cap) is chained here
+	int32_t grp_max = 0;
 	ARX_DEV void operator()(int r, int) const
 	{
 		const int g0 = occ_off[r], n = occ_off[r + 1] - g0;
 		if (heavy_list && n >= heavy_min && n <= CHAIN_LDS_OCC) { heavy_list[ARX_ATOMIC_ADD(n_heavy, 1)] = r; return; }
+		if (grp_max > 0) {
+			if (n >= 1 && n <= CHAIN_G16_SMALL && n <= grp_max) return;
+			if (n > CHAIN_G16_SMALL && n <= grp_max) { mid_list[ARX_ATOMIC_ADD(n_mid, 1)] = r; return; } // (the list has room for every read)
+			one(r);
+			return;
+		}
 		if (mid_list && n >= mid_min) { const int at = ARX_ATOMIC_ADD(n_mid, 1); if (at < mid_cap) { mid_list[at] = r; return; } } // (a full list: chained here)
 		one(r);
 	}
@@ -246,6 +261,10 @@ struct KChain {
 		n_chain[r] = m;
 	}
 };
+
+// HipRT has the group kernel (chain_group_ok / run_chain_group); the host test double chains every read on the serial path
+template <class R, class = void> struct HasChainGroup { static constexpr bool value = false; };
+template <class R> struct HasChainGroup<R, decltype((void)std::declval<const R &>().chain_group_ok())> { static constexpr bool value = true; };
 
 struct KChainMid { // the listed reads of KChain, one thread each; the list's length stays on the device
 	KChain f;
@@ -699,11 +718,22 @@ public:
 		KChain k{ix, b.lens, w.intv, w.n_intv, w.occ_off, w.occ_seed, w.occ_rid, w.next, w.ctmp, w.nodes, w.iscr, w.cout, w.sout, w.n_chain, w.err, nullptr, nullptr,
 		         getenv("ARX_CHAIN_HEAVY_MIN") ? atoi(getenv("ARX_CHAIN_HEAVY_MIN")) : CHAIN_HEAVY_MIN};
 		if (rt.chain_heavy_ok()) { k.heavy_list = rt.template alloc<int32_t>(R + 4); k.n_heavy = k.heavy_list + R; rt.memset0(k.n_heavy, 16); }
+		if constexpr (HasChainGroup<RT>::value) {
+			// the group path: KChain leaves the reads below the heavy threshold to k_chain_g16 (KChainMid is not launched); the reads
+			// beyond CHAIN_G16_MAX and below the threshold, and those above the heavy kernel's cap, are chained by KChain in place
+			const int gmax = k.heavy_min - 1 < CHAIN_G16_MAX ? k.heavy_min - 1 : CHAIN_G16_MAX;
+			if (rt.chain_group_ok() && gmax >= 1) {
+				k.grp_max = gmax;
+				k.mid_list = rt.template alloc<int32_t>((size_t)R + 4); k.n_mid = k.mid_list + R; k.mid_cap = R;
+				rt.memset0(k.n_mid, 16);
+			}
+		}
 		const int mid_min = getenv("ARX_CHAIN_MID_MIN") ? atoi(getenv("ARX_CHAIN_MID_MIN")) : 16; // 0: no launch of their own for the reads in between
 		const int mid_cap = R / 4 + 64; // the list holds a quarter of the reads; a read beyond that is chained where it is found
-		if (mid_min > 0 && k.heavy_list) { k.mid_list = rt.template alloc<int32_t>((size_t)mid_cap + 4); k.n_mid = k.mid_list + mid_cap; k.mid_min = mid_min; k.mid_cap = mid_cap; rt.memset0(k.n_mid, 16); }
+		if (mid_min > 0 && k.heavy_list && !k.grp_max) { k.mid_list = rt.template alloc<int32_t>((size_t)mid_cap + 4); k.n_mid = k.mid_list + mid_cap; k.mid_min = mid_min; k.mid_cap = mid_cap; rt.memset0(k.n_mid, 16); }
 		rt.launch_wide("chain", R, k);
-		if (k.mid_list) { KChainMid km{k}; rt.launch_wide("chain", mid_cap, km); } // (the list's length is not on the host: threads beyond it return at once)
+		if (k.mid_list && !k.grp_max) { KChainMid km{k}; rt.launch_wide("chain", mid_cap, km); } // (the list's length is not on the host: threads beyond it return at once)
+		if constexpr (HasChainGroup<RT>::value) { if (k.grp_max) rt.run_chain_group("chain", R, k); }
 		if (k.heavy_list) rt.run_chain_heavy("chain_heavy", R, k); // the list's length stays on the device: no host round trip
 	}
 
