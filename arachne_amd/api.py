@@ -82,6 +82,7 @@ def _load(path):
     lib.arx_batch_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.arx_batch_free.argtypes = [vp, vp]
     lib.arx_batch_debug_intv.argtypes = [vp, vp, vp, vp]
+    lib.arx_batch_debug_seed_census.argtypes = [vp, vp, i32, vp]
     lib.arx_batch_debug_chains.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.arx_batch_debug_core.argtypes = [vp, vp, vp, vp]
     lib.arx_batch_rfa.argtypes = [vp, vp, i32, vp, vp, C.c_double, vp, vp, vp]
@@ -340,6 +341,14 @@ class Batch:
         iv = np.zeros((self.n_reads, CAP_INTV, 4), dtype=np.uint64)
         self.ref._check(self.ref.lib.arx_batch_debug_intv(self.ref.h, self.h, n.ctypes.data, iv.ctypes.data))
         return n, iv
+
+    SEED_CENSUS_FIELDS = ["launches", "bin16", "bin21", "bin32", "bin64", "to_wave", "to_tail", "wave_list"]
+
+    def seed_census(self, enable=None):
+        """arx_batch_debug_seed_census: the sums so far as a dict; enable = True / False then switches the census on / off and clears them."""
+        c = np.zeros(8, dtype=np.int64)
+        self.ref._check(self.ref.lib.arx_batch_debug_seed_census(self.ref.h, self.h, -1 if enable is None else int(bool(enable)), c.ctypes.data))
+        return dict(zip(self.SEED_CENSUS_FIELDS, c.tolist()))
 
     def debug_chains(self):
         T = self.counts()["n_occ"]

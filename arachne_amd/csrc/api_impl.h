@@ -10,6 +10,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <type_traits>
 #include "../../include/arachne_amd.h"
 #include "index_io.h"
 #include "index_build.h"
@@ -20,6 +21,17 @@
 namespace arx {
 
 template <class RT> struct Batch;
+
+// arx_batch_debug_seed_census: a runtime that keeps the census (HipRT: seed_census_on, seed_census[8]) is read and switched; one that does
+// not (the host test double has no bins, hand-offs or tails) reports zeros
+template <class RT, class = void> struct SeedCensus {
+	static void read(const RT &, int64_t *c8) { for (int i = 0; i < 8; ++i) c8[i] = 0; }
+	static void set(RT &, bool) {}
+};
+template <class RT> struct SeedCensus<RT, std::void_t<decltype(std::declval<RT &>().seed_census_on)>> {
+	static void read(const RT &rt, int64_t *c8) { for (int i = 0; i < 8; ++i) c8[i] = rt.seed_census[i]; }
+	static void set(RT &rt, bool on) { rt.seed_census_on = on; for (int i = 0; i < 8; ++i) rt.seed_census[i] = 0; }
+};
 
 // SA[i * d] for every i: the suffix-array sample the locate kernel walks to.  The files sample every 32nd row (bwt.c:62,
 // bwtindex.c:309); bwt_sa's LF walk from a row to the next sampled one (bwt.c:86-96) is what locating a seed costs, 15.5 steps on
@@ -504,6 +516,14 @@ template <class RT> struct Batch {
 		ARX_TRY(c, b->rt.bind();                                                                                                    \
 			b->rt.d2h(n_intv, b->work.n_intv, 4 * (size_t)b->db.n_reads);                                                           \
 			b->rt.d2h(intv4, b->work.intv, sizeof(arx::Biv) * (size_t)b->db.n_reads * arx::CAP_INTV);)                              \
+		return ARX_OK;                                                                                                              \
+	}                                                                                                                               \
+	int arx_batch_debug_seed_census(arx_ctx *h, arx_batch *bh, int32_t enable, int64_t *census8)                                    \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
+		if (!b) { c->set_error("arx_batch_debug_seed_census without a batch"); return ARX_E_ARG; }                                  \
+		if (census8) arx::SeedCensus<RT>::read(b->rt, census8);                                                                     \
+		if (enable >= 0) arx::SeedCensus<RT>::set(b->rt, enable != 0);                                                              \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_debug_chains(arx_ctx *h, arx_batch *bh, int32_t *occ_off, int32_t *n_chain, arx_chain *chains, arx_seed *seeds)   \

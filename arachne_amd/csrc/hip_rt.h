@@ -376,7 +376,7 @@ struct HipRT {
 	// Backward sweeps: 2 (default) = row-parallel, one task per 16/32/64-lane group with the row's entries in registers (k_seed_bwd_g<GL>,
 	// tasks binned by list length): 21.5 -> 10 ms per 667 k-read batch at GRCh38 size.  1 = the pipelined one-lane-per-task kernel
 	// k_seed_bwd2 (51-61 of 64 lanes extending instead of 25-32, but no faster: profiles/r02/README.md).  0 = round 1's k_seed_bwd.
-	// All three are bit-identical.
+	// 3 = entry-parallel (k_seed_bwd_e).  All four are held to the CPU restatement interval for interval (tests/test_seed_variants_gpu.py).
 	int seed_bwd2 = getenv("ARX_SEED_BWD2") ? atoi(getenv("ARX_SEED_BWD2")) : 2;
 	int seed_grant = getenv("ARX_SEED_GRANT") ? atoi(getenv("ARX_SEED_GRANT")) : 4; // first forward pass: lanes parked for a pool slice that trigger the hand-out (5.36 ms with none, 5.17 at 16, 4.94 at 4, 5.08 at 1)
 	int seed_bwd_batch = getenv("ARX_SEED_BWD_BATCH") ? atoi(getenv("ARX_SEED_BWD_BATCH")) : 0; // 0: seed_batch
@@ -396,6 +396,26 @@ struct HipRT {
 		d2h(h, seed_dbg_buf, 32);
 		fprintf(stderr, "[arx seed stats] %s: %d items, %llu waves, %.0f iterations/wave, %.1f lanes extending per iteration, %.0f slow-path entries/wave\n", nm, n, h[3],
 		        h[3] ? (double)h[0] / h[3] : 0.0, h[0] ? (double)h[1] / h[0] : 0.0, h[3] ? (double)h[2] / h[3] : 0.0);
+	}
+	// opt-in census of the backward sweeps (arx_batch_debug_seed_census; tests assert from it which kernel took which task).  Everything it
+	// reports is in device memory after a launch anyway -- the bins' sizes (cnt[0..3]), the hand-off list's length (heavy[n]), the per-task flags
+	// (1: handed to k_seed_bwd_wave, 2: left to KSeedBwdTail) -- so switched on it copies them home after the launch and adds them up; switched
+	// off (the default) it is one untaken branch on the host: no round trip, no kernel argument.
+	// [0] backward launches, [1..4] tasks in the 16 / 21 / 32 / 64-lane bins, [5] tasks flagged for k_seed_bwd_wave, [6] tasks flagged for the
+	// tail, [7] length of the hand-off lists k_seed_bwd_wave was given
+	bool seed_census_on = false;
+	int64_t seed_census[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	void seed_census_add(int n, const int32_t *cnt, const int32_t *n_heavy, const uint8_t *flag)
+	{
+		if (!seed_census_on) return;
+		++seed_census[0];
+		if (cnt) { int32_t h[4]; d2h(h, cnt, 16); for (int c = 0; c < 4; ++c) seed_census[1 + c] += h[c]; }
+		if (n_heavy) { int32_t nh = 0; d2h(&nh, n_heavy, 4); seed_census[7] += nh; }
+		if (flag) {
+			std::vector<uint8_t> fl((size_t)n);
+			d2h(fl.data(), flag, (size_t)n);
+			for (uint8_t f : fl) { seed_census[5] += f == 1; seed_census[6] += f == 2; }
+		}
 	}
 	template <class K> void launch_seed_kernel(const char *nm, K kern, int n, const SeedKArgs &A, int32_t *counter, int bpc_, int chunk_ = 0, int batch_ = 0, int grant_ = 64)
 	{
@@ -447,6 +467,7 @@ struct HipRT {
 			}
 			ARX_HIP_CHECK(hipGetLastError());
 			seed_dbg_report(nm, (int)total);
+			seed_census_add(n, nullptr, nullptr, nullptr);
 			return;
 		}
 		if (seed_bwd2 == 2 && seed_row <= 132) { // row-parallel sweeps (k_seed_bwd_g<GL>): one task per 16/32/64-lane group, lists in registers
@@ -486,6 +507,7 @@ struct HipRT {
 				}
 				ARX_HIP_CHECK(hipGetLastError());
 			}
+			seed_census_add(n, cnt, heavy + n, flag);
 			return;
 		}
 		if (seed_bwd2) { // pipelined refills (k_seed_bwd2): one wait on memory per iteration
@@ -505,6 +527,7 @@ struct HipRT {
 				hipLaunchKernelGGL(k_seed_bwd_wave, dim3(n_cu * 16), dim3(64), 0, stream, A);
 				ARX_HIP_CHECK(hipGetLastError());
 			}
+			seed_census_add(n, nullptr, heavy + n, flag);
 			return;
 		}
 		launch_seed_kernel(nm, k_seed_bwd, n, A, counter, seed_bpc, seed_bwd_chunk, seed_bwd_batch);
@@ -514,6 +537,7 @@ struct HipRT {
 			hipLaunchKernelGGL(k_seed_bwd_wave, dim3(n_cu * 16), dim3(64), 0, stream, A);
 			ARX_HIP_CHECK(hipGetLastError());
 		}
+		seed_census_add(n, nullptr, heavy + n, nullptr);
 	}
 	template <class F> void run_seed_strat(const char *nm, int n, const F &f, int32_t *counter)
 	{

@@ -297,6 +297,13 @@ void arx_multi_close(arx_multi *m);
 /* intermediate results for parity tests (device -> host copies of stage outputs) */
 #define ARX_CAP_INTV 256
 int arx_batch_debug_intv(arx_ctx *ctx, arx_batch *b, int32_t *n_intv, uint64_t *intv4 /* n_reads*ARX_CAP_INTV*4 */);
+/* Census of the backward sweeps of the SMEM passes (tests: which kernel took which task).  enable = 1 / 0 switches it on / off for the batch's
+ * following arx_batch_run calls and clears the sums, enable < 0 leaves both alone; census8 (may be null) receives the sums as they were before
+ * that: [0] backward launches, [1..4] tasks in the 16 / 21 / 32 / 64-lane bins of the row-parallel kernel, [5] tasks it (or the pipelined
+ * one-lane kernel) flagged for the whole-wavefront kernel, [6] tasks left to text mode's tail, [7] length of the hand-off lists the
+ * whole-wavefront kernel was given.  Off (the default) nothing is counted and nothing is copied; on, each backward launch costs one more
+ * device-to-host copy of its bookkeeping.  The host test double keeps no census and reports zeros. */
+int arx_batch_debug_seed_census(arx_ctx *ctx, arx_batch *b, int32_t enable, int64_t *census8);
 int arx_batch_debug_chains(arx_ctx *ctx, arx_batch *b, int32_t *occ_off /* n_reads+1 */, int32_t *n_chain, arx_chain *chains, arx_seed *seeds /* counts[3] each */);
 int arx_batch_debug_core(arx_ctx *ctx, arx_batch *b, int32_t *n_core, arx_reg *regs /* counts[3] */);
 

@@ -458,10 +458,13 @@ static void bv_reverse(bivec_t *v)
 	for (j = 0; j < v->n >> 1; ++j) { biv_t t = v->a[v->n - 1 - j]; v->a[v->n - 1 - j] = v->a[j]; v->a[j] = t; }
 }
 
-static int smem1(const index_t *ix, int len, const uint8_t *q, int x, int min_intv, bivec_t *mem, bivec_t *v0, bivec_t *v1, ora_counters_t *cnt)
+/* sh (optional): the shape of this call for ora_seed_shapes -- ORA_SHAPE_W numbers, see arx_oracle.h.  kf: depth of the product's per-depth
+ * k-mer tables (0: none); it only enters sh[9], never the search */
+static int smem1(const index_t *ix, int len, const uint8_t *q, int x, int min_intv, bivec_t *mem, bivec_t *v0, bivec_t *v1, ora_counters_t *cnt, int64_t *sh, int kf)
 {
 	if (cnt) ++cnt->n_smem_calls;
 	int i, j, c, ret;
+	int64_t one_depth = -1, n_rows = 0, widest = 0, n_ext = 0, tail = 0, rows16 = 0, s_kf = -1;
 	biv_t ik, ok[4];
 	bivec_t *prev = v0, *curr = v1, *sw;
 	mem->n = 0;
@@ -471,8 +474,10 @@ static int smem1(const index_t *ix, int len, const uint8_t *q, int x, int min_in
 	ik.info = x + 1;
 	memset(ok, 0, sizeof ok);
 	for (i = x + 1, curr->n = 0; i < len; ++i) { /* forward: push an interval every time its size changes */
+		if (i - x == kf) s_kf = (int64_t)ik.s;
 		if (q[i] < 4) {
 			c = 3 - q[i];
+			if (ik.s == 1 && one_depth < 0) one_depth = i - x;
 			extend(ix, &ik, ok, 0, cnt);
 			if (ok[c].s != ik.s) {
 				bv_push(curr, &ik);
@@ -481,12 +486,24 @@ static int smem1(const index_t *ix, int len, const uint8_t *q, int x, int min_in
 			ik = ok[c]; ik.info = i + 1;
 		} else { bv_push(curr, &ik); break; }
 	}
-	if (i == len) bv_push(curr, &ik);
+	if (i == len) { bv_push(curr, &ik); if (i - x == kf) s_kf = (int64_t)ik.s; }
 	bv_reverse(curr); /* longest matches first */
 	ret = (int)curr->a[0].info;
+	if (sh) {
+		int p, code = -1;
+		if (kf > 0) { /* the table jump of the product's forward kernels (dev_fm.h FwdLane::start_jump / take_jump) */
+			code = 0;
+			if (x + kf > len) code = 2;
+			else for (p = 1; p < kf; ++p) if (q[x + p] > 3) { code = 1; break; }
+			if (code == 0 && (s_kf < 0 || s_kf < min_intv)) code = 3; /* (s_kf < 0: the walk ended before depth kf -- sizes only shrink) */
+		}
+		sh[1] = x; sh[2] = min_intv; sh[3] = curr->n; sh[4] = one_depth; sh[9] = code; sh[11] = ret;
+	}
 	sw = curr; curr = prev; prev = sw;
 	for (i = x - 1; i >= -1; --i) { /* backward: keep matches that cannot be extended and are not contained */
 		c = i < 0? -1 : q[i] < 4? q[i] : -1;
+		if (prev->n == 1 && prev->a[0].s == 1 && min_intv == 1) tail = 1;
+		if (c >= 0) n_ext += prev->n;
 		for (j = 0, curr->n = 0; j < prev->n; ++j) {
 			biv_t *p = &prev->a[j];
 			if (c >= 0) extend(ix, p, ok, 1, cnt);
@@ -503,8 +520,10 @@ static int smem1(const index_t *ix, int len, const uint8_t *q, int x, int min_in
 			}
 		}
 		if (curr->n == 0) break;
+		++n_rows; if (curr->n > widest) widest = curr->n; if (curr->n > 16) ++rows16;
 		sw = curr; curr = prev; prev = sw;
 	}
+	if (sh) { sh[5] = n_rows; sh[6] = widest; sh[7] = n_ext; sh[8] = tail; sh[10] = rows16; }
 	bv_reverse(mem); /* sorted by start */
 	return ret;
 }
@@ -535,13 +554,25 @@ static int seed_strategy1(const index_t *ix, int len, const uint8_t *q, int x, i
 
 static int intv_lt(const void *ctx, int a, int b) { const biv_t *v = (const biv_t*)ctx; return v[a].info < v[b].info; }
 
-static void collect_intv(const index_t *ix, int len, const uint8_t *seq, bivec_t *out, ora_counters_t *cnt)
+/* shape recorder of ora_seed_shapes: one row per bwt_smem1a call and per third-pass start */
+typedef struct { int64_t *rows; int n, cap, kf, k3; } shapes_t;
+static int64_t *shape_row(shapes_t *S, int pass)
+{
+	static int64_t spill[ORA_SHAPE_W];
+	int64_t *r = S->n < S->cap? S->rows + (size_t)ORA_SHAPE_W * S->n : spill;
+	memset(r, 0, sizeof(int64_t) * ORA_SHAPE_W);
+	r[0] = pass; r[4] = -1; r[9] = -1;
+	++S->n;
+	return r;
+}
+
+static void collect_intv_sh(const index_t *ix, int len, const uint8_t *seq, bivec_t *out, ora_counters_t *cnt, shapes_t *S)
 {
 	bivec_t mem1 = {0,0,0}, v0 = {0,0,0}, v1 = {0,0,0}, all = {0,0,0};
 	int i, k, x = 0, old_n, split_len = (int)(OPT_MIN_SEED_LEN * OPT_SPLIT_FACTOR + .499);
 	while (x < len) { /* pass 1: all SMEMs */
 		if (seq[x] < 4) {
-			x = smem1(ix, len, seq, x, 1, &mem1, &v0, &v1, cnt);
+			x = smem1(ix, len, seq, x, 1, &mem1, &v0, &v1, cnt, S? shape_row(S, 1) : 0, S? S->kf : 0);
 			for (i = 0; i < mem1.n; ++i) {
 				int slen = (int)((uint32_t)mem1.a[i].info - (mem1.a[i].info >> 32));
 				if (slen >= OPT_MIN_SEED_LEN) bv_push(&all, &mem1.a[i]);
@@ -553,7 +584,7 @@ static void collect_intv(const index_t *ix, int len, const uint8_t *seq, bivec_t
 		biv_t p = all.a[k];
 		int start = (int)(p.info >> 32), end = (int32_t)p.info;
 		if (end - start < split_len || p.s > OPT_SPLIT_WIDTH) continue;
-		smem1(ix, len, seq, (start + end) >> 1, (int)p.s + 1, &mem1, &v0, &v1, cnt);
+		smem1(ix, len, seq, (start + end) >> 1, (int)p.s + 1, &mem1, &v0, &v1, cnt, S? shape_row(S, 2) : 0, S? S->kf : 0);
 		for (i = 0; i < mem1.n; ++i)
 			if ((int)((uint32_t)mem1.a[i].info - (mem1.a[i].info >> 32)) >= OPT_MIN_SEED_LEN) bv_push(&all, &mem1.a[i]);
 	}
@@ -561,7 +592,18 @@ static void collect_intv(const index_t *ix, int len, const uint8_t *seq, bivec_t
 	while (x < len) { /* pass 3: LAST-like */
 		if (seq[x] < 4) {
 			biv_t m;
+			if (S) { /* the table jump of the product's third pass (dev_fm.h StratLane::advance): the next min_seed_len bases inside the read, none ambiguous */
+				int64_t *r = shape_row(S, 3);
+				int p, code = -1;
+				if (S->k3) {
+					code = 0;
+					if (x + OPT_MIN_SEED_LEN >= len) code = 2;
+					else for (p = 1; p <= OPT_MIN_SEED_LEN; ++p) if (seq[x + p] > 3) { code = 1; break; }
+				}
+				r[1] = x; r[9] = code;
+			}
 			x = seed_strategy1(ix, len, seq, x, OPT_MIN_SEED_LEN, OPT_MAX_MEM_INTV, &m, cnt);
+			if (S && S->n <= S->cap) S->rows[(size_t)ORA_SHAPE_W * (S->n - 1) + 11] = x;
 			if (m.s > 0) bv_push(&all, &m);
 		} else ++x;
 	}
@@ -574,6 +616,19 @@ static void collect_intv(const index_t *ix, int len, const uint8_t *seq, bivec_t
 		free(idx);
 	}
 	free(mem1.a); free(v0.a); free(v1.a); free(all.a);
+}
+static void collect_intv(const index_t *ix, int len, const uint8_t *seq, bivec_t *out, ora_counters_t *cnt) { collect_intv_sh(ix, len, seq, out, cnt, 0); }
+
+int ora_seed_shapes(ora_ctx_t *c, int len, const uint8_t *seq, int kf, int k3, int64_t *shapes, int cap_s, uint64_t *intv, int cap_i, int *n_intv)
+{
+	bivec_t v = {0,0,0};
+	shapes_t S = { shapes, 0, cap_s, kf, k3 };
+	int i;
+	collect_intv_sh(&c->ix, len, seq, &v, 0, &S);
+	for (i = 0; i < v.n && i < cap_i; ++i) { intv[4*i] = v.a[i].k; intv[4*i+1] = v.a[i].l; intv[4*i+2] = v.a[i].s; intv[4*i+3] = v.a[i].info; }
+	*n_intv = v.n;
+	free(v.a);
+	return S.n;
 }
 
 int ora_collect_intv(ora_ctx_t *c, int len, const uint8_t *seq, uint64_t *out, int cap)

@@ -59,6 +59,17 @@ void ora_occ4(ora_ctx_t *c, int n, const uint64_t *k, uint64_t *out);
 void ora_extend(ora_ctx_t *c, int n, const uint64_t *ik3, int is_back, uint64_t *ok12);
 void ora_sa(ora_ctx_t *c, int n, const uint64_t *k, uint64_t *out);
 int ora_collect_intv(ora_ctx_t *c, int len, const uint8_t *seq, uint64_t *out, int cap);
+/* The shape of a read's seeding work, from the same run of mem_collect_intv that fills intv (the intervals ora_collect_intv returns): one row
+ * of ORA_SHAPE_W numbers per bwt_smem1a call (passes 1 and 2) and per start of the third pass, in call order.  Tests assert from these rows
+ * that their inputs reach the rare paths of the product's seeding kernels.  Columns:
+ *  0 pass (1, 2, 3)   1 start x   2 min_intv   3 length of the forward list   4 depth (bases from x) at which the forward interval first holds
+ *  one occurrence with a base left to try, -1: never   5 rows of the backward sweep that kept something   6 the widest of them   7 backward
+ *  extensions   8 a row of ONE interval with ONE occurrence occurs (min_intv = 1)   9 the product's table jump at depth kf (passes 1, 2) or of
+ *  the third pass (k3 != 0): 0 taken, 1 refused for an ambiguous base, 2 for the end of the read, 3 because the kf-mer occurs fewer than
+ *  min_intv times, -1 no table   10 rows (as in 5) of more than 16 intervals   11 the call's return value (the next start).
+ * kf and k3 only enter column 9.  Returns the number of rows (rows beyond cap_s are counted, not stored). */
+#define ORA_SHAPE_W 12
+int ora_seed_shapes(ora_ctx_t *c, int len, const uint8_t *seq, int kf, int k3, int64_t *shapes, int cap_s, uint64_t *intv, int cap_i, int *n_intv);
 int ora_chains(ora_ctx_t *c, int len, const uint8_t *seq, int do_flt, int64_t *chains, int cap_c, int64_t *seeds, int cap_s, int *n_seeds_out, uint32_t *frac_rep_bits);
 void ora_ksw_extend2(ora_ctx_t *c, int qlen, const uint8_t *q, int tlen, const uint8_t *t, int w, int end_bonus, int zdrop, int h0, int *out);
 void ora_ksw_align2(ora_ctx_t *c, int qlen, const uint8_t *q, int tlen, const uint8_t *t, int xtra, int *out);

@@ -39,6 +39,7 @@ class Oracle:
         L.ora_batch_run.restype = C.c_double
         L.ora_batch_run.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.ora_collect_intv.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.ora_seed_shapes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.ora_chains.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.ora_ksw_extend2.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.ora_ksw_align2.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -102,6 +103,20 @@ class Oracle:
         n = self.lib.ora_collect_intv(self.h, len(seq), seq.ctypes.data, out.ctypes.data, cap)
         assert n <= cap
         return out[:n]
+
+    SHAPE_FIELDS = ["pass", "x", "min_intv", "fwd_n", "one_depth", "rows", "widest", "ext", "tail", "jump", "rows16", "ret"]
+    JUMP_TAKEN, JUMP_N, JUMP_END, JUMP_NARROW = 0, 1, 2, 3
+
+    def seed_shapes(self, seq, kf=0, k3=0, cap=4096):
+        """ora_seed_shapes: (rows of SHAPE_FIELDS, one per bwt_smem1a call / third-pass start; the intervals of the same run).
+        kf: depth of the forward k-mer tables the jump column is about (0: none), k3: the third pass has a table."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        sh = np.zeros((cap, len(self.SHAPE_FIELDS)), dtype=np.int64)
+        iv = np.zeros((cap, 4), dtype=np.uint64)
+        ni = C.c_int(0)
+        n = self.lib.ora_seed_shapes(self.h, len(seq), seq.ctypes.data, int(kf), int(k3), sh.ctypes.data, cap, iv.ctypes.data, cap, C.byref(ni))
+        assert n <= cap and ni.value <= cap
+        return sh[:n], iv[:ni.value]
 
     def chains(self, seq, do_flt, cap_c=8192, cap_s=65536):
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
