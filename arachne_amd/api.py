@@ -97,6 +97,9 @@ def _load(path):
     lib.arx_feeder_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp), C.c_char_p, i32]
     lib.arx_feeder_next.argtypes = [vp, i64, vp]
     lib.arx_feeder_close.argtypes = [vp]
+    lib.arx_feeder_open_device.argtypes = [vp, C.c_char_p, C.c_char_p, i64, i32, C.POINTER(vp), C.c_char_p, i32]
+    lib.arx_feeder_device_reads.argtypes = [vp, vp, vp, vp]
+    lib.arx_feeder_stats.argtypes = [vp, vp]
     lib.arx_bam_open.argtypes = [C.c_char_p, i32, vp, vp, C.c_char_p, i32, i32, C.POINTER(vp), C.c_char_p, i32]
     lib.arx_bam_write.argtypes = [vp, vp]
     lib.arx_bam_close.argtypes = [vp, vp]
@@ -432,14 +435,38 @@ class _SuperBatch(C.Structure):
 
 class Feeder:
     """The reference's paired FASTQ reader (fastqreader.OpenFastQ / ReadBarcodeSet) delivering super-batches of whole barcode sets
-    (arx_feeder_*).  Host code of the product library; needs no GPU."""
+    (arx_feeder_*).  Host code of the product library; needs no GPU.
 
-    def __init__(self, r1: str, r2: str, lib_path: str = LIB_PATH):
-        self.lib = _load(lib_path)
+    device=<Reference>: the device feeder (arx_feeder_open_device) -- two reader threads, the parse on that reference's GPU; the
+    super-batches are byte for byte the host feeder's.  chunk_bytes: bytes of each file's inflated stream per chunk (0: the default);
+    depth: the arrays of call k stay valid until call k + depth returns (next_raw's views and device_reads)."""
+
+    def __init__(self, r1: str, r2: str, lib_path: str = LIB_PATH, device: "Reference | None" = None, chunk_bytes: int = 0, depth: int = 1):
         self.h = C.c_void_p()
         msg = C.create_string_buffer(512)
+        self.device = device
+        if device is not None:
+            self.lib = device.lib
+            if self.lib.arx_feeder_open_device(device.h, r1.encode(), r2.encode(), int(chunk_bytes), int(depth), C.byref(self.h), msg, 512) != 0:
+                raise ArachneError("arx_feeder_open_device: " + msg.value.decode())
+            return
+        self.lib = _load(lib_path)
         if self.lib.arx_feeder_open(r1.encode(), r2.encode(), C.byref(self.h), msg, 512) != 0:
             raise ArachneError("arx_feeder_open: " + msg.value.decode())
+
+    def device_reads(self):
+        """arx_feeder_device_reads -> (d_bases, d_lens, n_bases): device pointers of the last super-batch's reads, for Batch.reset_device"""
+        db, dl, nb = C.c_void_p(), C.c_void_p(), C.c_int64()
+        if self.lib.arx_feeder_device_reads(self.h, C.byref(db), C.byref(dl), C.byref(nb)) != 0:
+            raise ArachneError("arx_feeder_device_reads: not a device feeder, or no super-batch yet")
+        return db.value or 0, dl.value or 0, nb.value
+
+    def stats(self):
+        """arx_feeder_stats of a device feeder -> dict"""
+        st = (C.c_int64 * 8)()
+        if self.lib.arx_feeder_stats(self.h, st) != 0:
+            raise ArachneError("arx_feeder_stats: not a device feeder")
+        return dict(chunks=st[0], bytes=st[1], records=st[2], bad_lines=st[3], runs=st[4], fallback_chunks=st[5])
 
     def next(self, target_pairs: int):
         """-> dict (numpy copies) or None at the end of the input"""

@@ -20,19 +20,29 @@ int arx_feeder_open(const char *r1_path, const char *r2_path, arx_feeder **out, 
 		delete f;
 		return ARX_E_IO;
 	}
-	*out = (arx_feeder *)f;
+	*out = (arx_feeder *)(arx::FeederBase *)f;
 	return ARX_OK;
 }
 
 int arx_feeder_next(arx_feeder *h, int64_t target_pairs, arx_super_batch *out)
 {
 	try {
-		return ((arx::Feeder *)h)->next(target_pairs, out);
+		return ((arx::FeederBase *)h)->next(target_pairs, out);
 	} catch (const std::exception &) {
 		return ARX_E_IO;
 	}
 }
 
-void arx_feeder_close(arx_feeder *h) { delete (arx::Feeder *)h; }
+void arx_feeder_close(arx_feeder *h)
+{
+	try { delete (arx::FeederBase *)h; } catch (...) {}
+}
+
+int arx_feeder_device_reads(arx_feeder *h, const uint8_t **d_bases, const int32_t **d_lens, int64_t *n_bases)
+{
+	return h ? ((arx::FeederBase *)h)->device_reads(d_bases, d_lens, n_bases) : ARX_E_ARG;
+}
+
+int arx_feeder_stats(arx_feeder *h, int64_t *stats) { return h && stats ? ((arx::FeederBase *)h)->stats(stats) : ARX_E_ARG; }
 
 }

@@ -12,8 +12,12 @@
 // Plain C++ (no device code); compiled into libarachne_amd.so and, for the CPU tests, into the host test double.
 #pragma once
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
+#include <condition_variable>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 #include <zlib.h>
 #include "../../include/arachne_amd.h"
@@ -106,9 +110,93 @@ inline void parse_header(const char *b, const char *e, FastqRecord &r)
 	}
 }
 
-class Feeder {
+// what arx_feeder_next / arx_feeder_close (arx_feeder.cpp) see of a feeder: this one, or the device feeder (device_feeder.h)
+class FeederBase {
 public:
 	std::string error;
+	virtual ~FeederBase() {}
+	virtual int next(int64_t target_pairs, arx_super_batch *o) = 0;
+	// the device feeder's extras; the host feeder has neither
+	virtual int device_reads(const uint8_t **, const int32_t **, int64_t *) { return ARX_E_ARG; }
+	virtual int stats(int64_t *) { return ARX_E_ARG; }
+};
+
+// One file of the device feeder: a thread of its own inflates it (gzread: plain files too) chunk by chunk into one of two buffers
+// while the other one is uploaded and parsed.  Chunk k is bytes [k * chunk_bytes, (k + 1) * chunk_bytes) of the inflated stream;
+// a buffer ("slab") holds a whole number of chunks.  The buffers are the caller's to page-lock (slab(i), slab_cap()).
+class ChunkReader {
+public:
+	struct Slab { char *buf = nullptr; size_t len = 0; int64_t chunks = 0; bool eof = false, err = false, full = false; };
+	bool open(const char *path, size_t chunk_bytes, size_t chunks_per_slab)
+	{
+		f_ = gzopen(path, "rb");
+		if (!f_) return false;
+		gzbuffer(f_, 1 << 20);
+		chunk_ = chunk_bytes; cap_ = chunk_bytes * chunks_per_slab;
+		for (Slab &s : slab_) { if (posix_memalign((void **)&s.buf, 4096, cap_ + 64)) { s.buf = nullptr; return false; } }
+		return true;
+	}
+	void start() { th_ = std::thread([this] { run(); }); }
+	~ChunkReader()
+	{
+		{ std::lock_guard<std::mutex> g(mu_); stop_ = true; }
+		cv_.notify_all();
+		if (th_.joinable()) th_.join();
+		if (f_) gzclose(f_);
+		for (Slab &s : slab_) free(s.buf);
+	}
+	char *slab(int i) const { return slab_[i].buf; }
+	size_t slab_cap() const { return cap_ + 64; }
+	// the next slab in file order (waits for it); nullptr once the slab that carried eof or an error has been taken
+	const Slab *acquire()
+	{
+		if (done_) return nullptr;
+		std::unique_lock<std::mutex> g(mu_);
+		Slab &s = slab_[take_ & 1];
+		cv_.wait(g, [&] { return s.full; });
+		if (s.eof || s.err) done_ = true;
+		return &s;
+	}
+	void release() // the slab acquire() handed out last may be refilled
+	{
+		{ std::lock_guard<std::mutex> g(mu_); slab_[take_ & 1].full = false; ++take_; }
+		cv_.notify_all();
+	}
+	bool done() const { return done_; }
+private:
+	void run()
+	{
+		for (int k = 0;; ++k) {
+			Slab &s = slab_[k & 1];
+			{
+				std::unique_lock<std::mutex> g(mu_);
+				cv_.wait(g, [&] { return stop_ || !s.full; });
+				if (stop_) return;
+			}
+			size_t len = 0; int64_t chunks = 0; bool eof = false, err = false;
+			while (len < cap_) {
+				const int got = gzread(f_, s.buf + len, (unsigned)chunk_);
+				if (got < 0) { err = true; break; }
+				if (got > 0) { len += (size_t)got; ++chunks; }
+				if ((size_t)got < chunk_) { eof = true; break; }
+			}
+			{ std::lock_guard<std::mutex> g(mu_); s.len = len; s.chunks = chunks; s.eof = eof; s.err = err; s.full = true; }
+			cv_.notify_all();
+			if (eof || err) return;
+		}
+	}
+	gzFile f_ = nullptr;
+	size_t chunk_ = 0, cap_ = 0;
+	Slab slab_[2];
+	std::thread th_;
+	std::mutex mu_;
+	std::condition_variable cv_;
+	int take_ = 0;
+	bool stop_ = false, done_ = false;
+};
+
+class Feeder : public FeederBase {
+public:
 	bool open(const char *r1, const char *r2)
 	{
 		if (!src1_.open(r1)) { error = std::string("cannot open ") + r1; return false; }
@@ -169,7 +257,7 @@ public:
 	}
 
 	// whole sets until at least target_pairs pairs are held (always at least one set); returns the number of sets
-	int next(int64_t target_pairs, arx_super_batch *o)
+	int next(int64_t target_pairs, arx_super_batch *o) override
 	{
 		set_off_.assign(1, 0); unique_.clear(); do_rfa_.clear(); bases_.clear(); quals_.clear(); lens_.clear(); valid_.clear();
 		name_off_.assign(1, 0); names_.clear(); rg_off_.assign(1, 0); rgs_.clear(); bc_off_.assign(1, 0); bcs_.clear();

@@ -15,6 +15,10 @@ layout="reference": the reference's output directory (CreateBAMs, bamwriter.go:1
 full tags) and every record written twice, to bc_sorted_bam.bam and to its bucket (AppendBams, :279-281).  All workers append to shared
 writers, one lock per writer: a batch's records are contiguous and in order inside every file, the order of batches across workers is
 as arbitrary as the reference's goroutines make it.
+
+feeder="device" (opt in): ONE file pair, the reference's own shape -- one producer thread with the device feeder (arx_feeder_open_device: two
+reader threads, the parse in HIP kernels) and `workers` worker threads that take its super-batches from a queue, the reads already in HBM
+(arx_feeder_device_reads -> arx_batch_reset_device); see _run_device.
 """
 from __future__ import annotations
 
@@ -32,12 +36,20 @@ _TRACE = bool(os.environ.get("ARX_E2E_TRACE"))
 
 def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int = 250_000, bam_threads: int = 8, rec_threads: int = 8, level: int = 1,
         penalty: float = -4, lib_path: str = api.LIB_PATH, warm_passes: int = 0, layout: str = "workers", chunk: int = 40_000_000,
-        read_groups: str = "", sample_id: str = ""):
+        read_groups: str = "", sample_id: str = "", feeder: str = "host", workers: int = 3, chunk_bytes: int = 0):
     """fastq_pairs: [(r1, r2), ...] barcode-sorted files (plain or gzip), one worker each.  -> stats dict (pairs, seconds, pairs/s, per-stage
     seconds summed over workers).  warm_passes: untimed passes over the same files first, through the same batch handles -- a handle's first
     batch pays for its work memory (hipMalloc of several GiB: seconds once a 69 GB k-mer table sits beside it), which a run over a whole
     read set pays once; the stats are those of the last pass.  layout="reference": out_prefix is the output directory of the reference's
-    layout (see the module docstring; chunk = -p/--partitions, read_groups / sample_id as the reference's flags); warm_passes must be 0."""
+    layout (see the module docstring; chunk = -p/--partitions, read_groups / sample_id as the reference's flags); warm_passes must be 0.
+    feeder="device": ONE file pair, parsed on the GPU by one feeder thread (arx_feeder_open_device) that hands super-batches to `workers`
+    worker threads (see _run_device); the default, feeder="host", is one host feeder and one worker per file pair."""
+    if feeder == "device":
+        if warm_passes:
+            raise ValueError("feeder='device' reads its file pair once: warm_passes must be 0")
+        return _run_device(ref, fastq_pairs, out_prefix, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, layout, chunk, read_groups, workers, chunk_bytes)
+    if feeder != "host":
+        raise ValueError(f"unknown feeder {feeder!r}")
     if layout == "reference":
         if warm_passes:
             raise ValueError("layout='reference' writes its files once: warm_passes must be 0")
@@ -254,4 +266,198 @@ def _run_reference(ref, fastq_pairs, out_dir, pairs_per_batch, bam_threads, rec_
     stats["pairs_per_s"] = stats["pairs"] / stats["seconds"] if stats["seconds"] > 0 else 0.0
     stats["workers"] = len(fastq_pairs)
     stats["files"] = files
+    return stats
+
+
+def _run_device(ref, fastq_pairs, out, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, layout, chunk, read_groups, workers, chunk_bytes):
+    """One file pair, the reference's shape (aligner.go:335-358): ONE producer -- the device feeder, whose parse runs on the GPU -- puts
+    super-batches into a queue, `workers` threads take them, each with its own batch handle (arx_batch_reset_device from the feeder's device
+    arrays: the bases never come back to the host for the path's sake) and everything after that as in the host-feeder loops above.
+    layout="workers": worker k writes `<out>.k.bam`; layout="reference": all workers append to the reference's files.  A super-batch's
+    records stay contiguous and in order; which worker takes which super-batch is as free as it is across the reference's goroutines."""
+    import queue
+    if len(fastq_pairs) != 1:
+        raise ValueError("feeder='device' takes exactly one file pair")
+    if layout not in ("workers", "reference"):
+        raise ValueError(f"unknown layout {layout!r}")
+    if workers < 1:
+        raise ValueError("workers must be at least 1")
+    r1, r2 = fastq_pairs[0]
+    names, offs, clens, alt, l_pac = ref.contigs()
+    full = layout == "reference"
+    if full:
+        table = api.bucket_table(names, clens, chunk, lib_path=lib_path)
+        os.makedirs(out, exist_ok=True)
+        files = ["bc_sorted_bam.bam"] + table.files
+        hdr = reference_header(read_groups)
+        writers = [api.BamWriter(os.path.join(out, f), names, clens, extra_header=hdr, threads=bam_threads, level=level, lib_path=lib_path) for f in files]
+    else:
+        files = [f"{out}.{k}.bam" for k in range(workers)]
+        writers = [api.BamWriter(f, names, clens, extra_header="@PG\tID:arachne_amd\n", threads=bam_threads, level=level, lib_path=lib_path) for f in files]
+    locks = [threading.Lock() for _ in writers]
+    stats = dict(pairs=0, records=0, batches=0, feeder_s=0.0, device_s=0.0, fetch_s=0.0, records_s=0.0, bam_s=0.0)
+    slock = threading.Lock()
+    errors = []
+    # The feeder recycles its arrays by AGE: those of its call k hold until its call k + depth returns, however many newer super-batches are
+    # done with.  So the producer makes call m only when every super-batch up to m - depth has been released by its worker (done[j], set
+    # once the records are built): it runs at most depth - 1 calls ahead of the oldest one in use, and a worker that is held up in one
+    # super-batch stops the producer, not the feeder's arrays under it.  depth = workers + 2: one per worker, one in the queue, one in the making.
+    depth = workers + 2
+    done = []                           # done[j]: the worker that took super-batch j no longer needs the feeder's arrays of it
+    q = queue.Queue(maxsize=1)
+    fd = api.Feeder(r1, r2, device=ref, chunk_bytes=chunk_bytes, depth=depth)
+    feeder_stats = {}
+
+    def producer():
+        try:
+            while not errors:
+                m = len(done)
+                while m >= depth and not done[m - depth].wait(0.2):
+                    if errors:
+                        return
+                t0 = time.time()
+                nx = fd.next_raw(pairs_per_batch)
+                if nx is None:
+                    break
+                done.append(threading.Event())
+                item = nx + (fd.device_reads(), done[m])
+                with slock:
+                    stats["feeder_s"] += time.time() - t0
+                while not errors:
+                    try:
+                        q.put(item, timeout=0.2)
+                        break
+                    except queue.Full:
+                        pass
+            feeder_stats.update(fd.stats())
+        except BaseException as e:  # noqa: BLE001 -- reported by the caller's thread
+            errors.append(e)
+        finally:
+            for _ in range(workers):
+                while True:
+                    try:
+                        q.put(None, timeout=0.2)
+                        break
+                    except queue.Full:
+                        if errors:
+                            try:
+                                q.get_nowait()
+                            except queue.Empty:
+                                pass
+
+    def worker(k):
+        batch = None
+        rb = [api.RecBuf(lib_path=lib_path), api.RecBuf(lib_path=lib_path)]     # one is written out while the next is built
+        loc = dict(pairs=0, records=0, batches=0, device_s=0.0, fetch_s=0.0, records_s=0.0, bam_s=0.0)
+        buf = {}
+        wq = queue.Queue(maxsize=1)
+        written = [threading.Event(), threading.Event()]
+        for e_ in written:
+            e_.set()
+        werr = []
+
+        def write(view, bucket):
+            if not full:
+                with locks[k]:
+                    writers[k].write_view(view)
+                return
+            order = np.argsort(bucket, kind="stable")
+            cuts = np.searchsorted(bucket[order], np.arange(len(table.files) + 1))
+            with locks[0]:
+                writers[0].write_view(view)
+            for f in range(len(table.files)):
+                if cuts[f + 1] > cuts[f]:
+                    with locks[f + 1]:
+                        writers[f + 1].write_select(view, order[cuts[f]:cuts[f + 1]])
+
+        def writer():
+            while True:
+                item = wq.get()
+                if item is None:
+                    return
+                slot, view, bucket = item
+                try:
+                    t_ = time.time()
+                    write(view, bucket)
+                    loc["bam_s"] += time.time() - t_
+                except BaseException as e:  # noqa: BLE001
+                    werr.append(e)
+                finally:
+                    written[slot].set()
+        wt = threading.Thread(target=writer)
+        wt.start()
+        try:
+            while True:
+                item = q.get()
+                if item is None:
+                    break
+                if errors:
+                    continue
+                sb, v, (d_bases, d_lens, n_bases), released = item
+                t1 = time.time()
+                if batch is None:
+                    batch = ref.batch(np.zeros(2, np.uint8), np.ones(2, np.int32))      # a handle; its reads come from the device below
+                batch.reset_device(2 * int(v["n_pairs"]), n_bases, d_bases, d_lens)
+                batch.run(api.STAGE_ALN)
+                batch.rfa(v["set_pair_off"], v["do_rfa"], penalty=penalty, fetch=False)
+                t2 = time.time()
+                batch.fetch_into(buf)
+                if full:
+                    post = batch.post()
+                    tags = batch.tags()
+                else:
+                    post = batch.post_into(buf)
+                t3 = time.time()
+                slot = loc["batches"] & 1
+                written[slot].wait()                    # the buffer's last view is on disk
+                if werr:
+                    raise werr[0]
+                if full:
+                    view, bucket = rb[slot].build_full(sb, buf["cand_off"], buf["cands"], buf["alns"], buf["cigars"], post["post"], post["split"], post["mm_ref"],
+                                                       post["mm_read"], tags, table, threads=rec_threads)
+                    bucket = bucket.copy()
+                else:
+                    view, bucket = rb[slot].build(sb, buf["cand_off"], buf["cands"], buf["alns"], buf["cigars"], post, threads=rec_threads), None
+                n_pairs = int(v["n_pairs"])
+                released.set()                          # the feeder's arrays of this super-batch are no longer needed
+                t4 = time.time()
+                written[slot].clear()
+                wq.put((slot, view, bucket))
+                loc["pairs"] += n_pairs; loc["records"] += int(view.n_records); loc["batches"] += 1
+                loc["device_s"] += t2 - t1; loc["fetch_s"] += t3 - t2; loc["records_s"] += t4 - t3
+        except BaseException as e:  # noqa: BLE001 -- reported by the caller's thread
+            errors.append(e)
+        finally:
+            wq.put(None)
+            wt.join()
+            if werr and not errors:
+                errors.append(werr[0])
+            if batch is not None:
+                batch.free()
+            for x in rb:
+                x.free()
+        with slock:
+            for key, val in loc.items():
+                stats[key] += val
+
+    t = time.time()
+    th = [threading.Thread(target=producer)] + [threading.Thread(target=worker, args=(k,)) for k in range(workers)]
+    for x in th:
+        x.start()
+    for x in th:
+        x.join()
+    t5 = time.time()
+    stats["bam_bytes"] = 0
+    for w in writers:
+        stats["bam_bytes"] += w.close()["bytes_out"]
+    stats["bam_s"] += time.time() - t5
+    fd.close()
+    if errors:
+        raise errors[0]
+    stats["seconds"] = time.time() - t
+    stats["warm_passes"] = 0
+    stats["pairs_per_s"] = stats["pairs"] / stats["seconds"] if stats["seconds"] > 0 else 0.0
+    stats["workers"] = workers
+    stats["files"] = files
+    stats["feeder"] = feeder_stats
     return stats

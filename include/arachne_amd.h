@@ -208,6 +208,23 @@ int arx_feeder_open(const char *r1_path, const char *r2_path, arx_feeder **out, 
  * input, < 0 on a read error */
 int arx_feeder_next(arx_feeder *f, int64_t target_pairs, arx_super_batch *out);
 void arx_feeder_close(arx_feeder *f);
+/* arx_feeder_open with the parse on ctx's GPU: two reader threads inflate the files side by side, HIP kernels find the lines, the records,
+ * the header fields, the base codes and the barcode runs in the raw text.  chunk_bytes: bytes of each file's inflated stream per chunk (0: a
+ * default of 8 MiB; at most 2^28); depth >= 1: super-batches whose arrays stay valid -- those of call k until call k + depth returns --, so
+ * that one producer can feed `depth` workers.  arx_feeder_next / arx_feeder_close as for the host feeder; the arx_super_batch is byte for
+ * byte the one arx_feeder_open's feeder delivers for the same files and target_pairs.  Needs the GPU (ARX_E_DEVICE without one; ARX_E_IO: a
+ * file cannot be opened).  Two environment switches, read at open: ARX_FEEDER_PARSE_CHUNKS=n -- chunks of each file one parse takes in
+ * (default: what fills 8 MiB, at most 64; 1 makes every chunk boundary a boundary between parses: what the tests use to put the carry
+ * between parses at every byte offset; results do not depend on it); ARX_FEEDER_TIMES=1 -- diagnostics: arx_feeder_close prints the feeder
+ * thread's seconds per stage and its kernels' times (HIP events) on stderr. */
+int arx_feeder_open_device(arx_ctx *ctx, const char *r1_path, const char *r2_path, int64_t chunk_bytes, int32_t depth, arx_feeder **out, char *msg,
+                           int32_t msg_cap);
+/* the reads of the super-batch the last arx_feeder_next delivered, in device memory, for arx_batch_reset_device (same validity as its host
+ * arrays; the feeder's stream is done with them).  ARX_E_ARG for a host feeder or before the first super-batch. */
+int arx_feeder_device_reads(arx_feeder *f, const uint8_t **d_bases, const int32_t **d_lens, int64_t *n_bases);
+/* stats[8] of a device feeder since open: chunks read (both files), bytes uploaded, records parsed, lines skipped, barcode runs, chunks that
+ * took a host fallback (always 0: there is none), reserved x2.  ARX_E_ARG for a host feeder. */
+int arx_feeder_stats(arx_feeder *f, int64_t *stats);
 
 /* ---- behind the path: the BAM sink.  The reference builds one biogo sam.Record per alignment on a single goroutine and
  * writes it twice (BamThread / AppendBams, src/aligner/bamwriter.go:615-627,279-282), two BGZF goroutines per writer (:118).  Here records
