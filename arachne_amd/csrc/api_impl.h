@@ -102,6 +102,7 @@ template <class RT> struct Context {
 	std::string open(const std::string &prefix, int dev)
 	{
 		device = dev;
+		const IndexSwitches isw; // what to build beside the index files: read here, once per context (switches.h)
 		std::string e = rt.init(dev);
 		if (!e.empty()) return e;
 		e = load_index(prefix, hix);
@@ -137,9 +138,8 @@ template <class RT> struct Context {
 		{ // k-mer table for the third seeding pass (dev_fm.h): K from the genome size -- the largest K with 4^K <= symbols, at most 16 (GRCh38:
 		  // 16, 4.3 G entries = 69 GB of the 288 GB; measured at GRCh38 size: the pass takes 9.7 ms per step without a table, 5.6 at K = 12,
 		  // 4.2 at 14, 3.3 at 16) -- and never more than a third of the device memory that is free; ARX_KMER_K overrides, 0 = no table
-			const char *e = getenv("ARX_KMER_K");
 			int K = 0;
-			if (e) K = atoi(e);
+			if (isw.kmer_k) K = *isw.kmer_k;
 			else { while (K < 16 && ((uint64_t)1 << (2 * (K + 1))) <= ix.seq_len) ++K; }
 			if (K > OPT_MIN_SEED_LEN - 3) K = OPT_MIN_SEED_LEN - 3;
 			while (K >= 4 && ((uint64_t)20 << (2 * K)) > rt.free_bytes() / 3) --K; // 16 bytes per entry, plus the level before it while it is built
@@ -147,8 +147,7 @@ template <class RT> struct Context {
 			if (K >= 4) {
 				// levels 1 .. Kf are kept back to back for the forward extensions of the SMEM pass (every depth of a list prefix is needed there:
 				// dev_fm.h FwdLane); Kf = min(K, 14): 5.7 GB.  ARX_KMER_FWD=0: none (the forward kernels walk base by base)
-				const char *ef = getenv("ARX_KMER_FWD");
-				const int Kf = (ef && atoi(ef) == 0) ? 0 : (K < 14 ? K : 14);
+				const int Kf = !isw.kmer_fwd ? 0 : (K < 14 ? K : 14);
 				uint64_t *lv = nullptr;
 				if (Kf > 0) lv = rt.template palloc<uint64_t>(2 * ((((size_t)1 << (2 * (Kf + 1))) - 4) / 3) + 2);
 				uint64_t *prev = nullptr; bool prev_owned = false;
@@ -171,10 +170,9 @@ template <class RT> struct Context {
 		{ // the whole suffix array and its inverse, 5 bytes per entry each (GRCh38: 2 x 31 GB), when they take no more than half of what is free
 		  // after the tables; ARX_TEXT_INDEX=0: never.  With them locating a seed is one load and the first-pass forward extensions compare
 		  // text once one occurrence is left (dev_fm.h: text mode)
-			const char *e = getenv("ARX_TEXT_INDEX");
 			const uint64_t bytes = 5 * (ix.seq_len + 1) + 64;
 			const uint64_t n_sa = (ix.seq_len + (uint64_t)ix.sa_intv) / (uint64_t)ix.sa_intv;
-			if (!(e && atoi(e) == 0) && (ix.sa_intv & (ix.sa_intv - 1)) == 0 && 2 * bytes <= rt.free_bytes() / 2 && n_sa < 0x7fffffffull) {
+			if (isw.text_index && (ix.sa_intv & (ix.sa_intv - 1)) == 0 && 2 * bytes <= rt.free_bytes() / 2 && n_sa < 0x7fffffffull) {
 				uint8_t *sa40 = rt.template palloc<uint8_t>((size_t)bytes), *isa40 = rt.template palloc<uint8_t>((size_t)bytes);
 				KSaWalk kw{ix, sa40, isa40};
 				rt.launch_wide("sa_walk", (int)n_sa, kw);
@@ -184,8 +182,7 @@ template <class RT> struct Context {
 			}
 		}
 		if (!ix.sa40) { // denser suffix-array sample (ARX_SA_DENSE: rows per sample, a power of two; at least the file's interval switches it off)
-			const char *e = getenv("ARX_SA_DENSE");
-			const int d = e ? atoi(e) : 4; // every 4th row since round 3 (12 GB at GRCh38 size; locate 4.9 -> 2.5 ms per step, arx_open +1.7 s); 8 in round 2
+			const int d = isw.sa_dense; // default: every 4th row (switches.h has the measurement)
 			const uint64_t n2 = (ix.seq_len + (uint64_t)d) / (uint64_t)d;
 			if (d >= 1 && d < ix.sa_intv && (d & (d - 1)) == 0 && n2 < 0x7fffffffull) {
 				uint64_t *dense = rt.template palloc<uint64_t>((size_t)n2 + 8);

@@ -95,11 +95,7 @@ static __global__ void __launch_bounds__(64) k_rescue_heavy(KRescueStep f, const
 template <> void HipRT::run_rescue_heavy<KRescueStep>(const char *nm, int n, const int32_t *list, const KRescueStep &f)
 {
 	if (n <= 0) return;
-	static const int wave = getenv("ARX_RESCUE_WAVE") ? atoi(getenv("ARX_RESCUE_WAVE")) : 1;
-	// 1: three launches by LDS footprint (170 / 340 / 680 records: 5 / 3 / 2 workgroups per CU).  Measured in round 3: slower (36 -> 43 ms per step
-	// alone on the repeat-rich workload, 14 -> 18 on the default one) -- the launches of one stream run one after the other and each ends on
-	// its own longest pair; what bounds this kernel is the serial depth of its longest pairs, not the workgroups a CU holds.  Default: one launch.
-	static const int split = getenv("ARX_RESCUE_LDS_CLASSES") ? atoi(getenv("ARX_RESCUE_LDS_CLASSES")) : 0;
+	const int wave = sw.rescue_wave, split = sw.rescue_lds_classes; // split: three launches by LDS footprint instead of one (measured slower: switches.h)
 	if (!rescue_heavy_attr_set) { ARX_HIP_CHECK(hipFuncSetAttribute((const void *)k_rescue_heavy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(RESCUE_LDS_REGS * sizeof(Reg)))); rescue_heavy_attr_set = true; }
 	int32_t *cur = alloc<int32_t>(4);
 	memset0(cur, 16);
@@ -191,12 +187,12 @@ static __global__ void __launch_bounds__(64) k_chain_heavy(KChain f, int n_lo, i
 template <> void HipRT::run_chain_heavy<KChain>(const char *nm, int n_reads, const KChain &f)
 {
 	Scope sc(*this, nm, n_reads);
-	static const int wave = getenv("ARX_CHAIN_WAVE") ? atoi(getenv("ARX_CHAIN_WAVE")) : 1;
+	const int wave = sw.chain_wave;
 	static const size_t lds_s = ChainLds::bytes(CHAIN_LDS_SMALL), lds_l = ChainLds::bytes(CHAIN_LDS_OCC);
 	// the opt-in applies to the device that is current when it is made: once per runtime (= per device context), not once per process
 	if (!chain_heavy_attr_set) { ARX_HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_heavy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l)); chain_heavy_attr_set = true; }
 	// f.n_heavy[0]: the list's length (stays on the device), [1] and [2]: the two launches' cursors into it
-	static const int l_div = getenv("ARX_CHAIN_L_DIV") ? atoi(getenv("ARX_CHAIN_L_DIV")) : 1; // the long ones' launch holds 128 KB of LDS per workgroup: on n_cu / l_div CUs
+	const int l_div = sw.chain_l_div; // the long ones' launch holds 128 KB of LDS per workgroup: on n_cu / l_div CUs
 	on_aux([&]() { hipLaunchKernelGGL(k_chain_heavy, dim3(n_cu / (l_div > 0 ? l_div : 1)), dim3(64), lds_l, stream, f, CHAIN_LDS_SMALL + 1, CHAIN_LDS_OCC, f.n_heavy + 2, wave); }); // the few long ones (beside the rest with ARX_AUX_STREAM=1)
 	hipLaunchKernelGGL(k_chain_heavy, dim3(n_cu * 4), dim3(64), lds_s, stream, f, 0, CHAIN_LDS_SMALL, f.n_heavy + 1, wave); // (a third launch for reads of up to 128 occurrences at half the LDS changed nothing: round 3)
 	ARX_HIP_CHECK(hipGetLastError());

@@ -8,8 +8,8 @@ namespace arx {
 std::string product_bwt_sa(const uint8_t *pac, size_t pac_bytes, int64_t l_pac, const uint64_t cnt_fwd[4], const std::string &prefix)
 {
 	int ndev = 0;
-	const bool force_host = getenv("ARX_INDEX_HOST") && atoi(getenv("ARX_INDEX_HOST")) != 0;
-	if (force_host || hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return build_bwt_sa_host(pac, pac_bytes, l_pac, cnt_fwd, prefix);
-	return gpuidx::build_bwt_sa_device(pac, pac_bytes, l_pac, cnt_fwd, prefix, getenv("ARX_INDEX_DEVICE") ? atoi(getenv("ARX_INDEX_DEVICE")) : -1);
+	const IndexBuildSwitches sw; // read per arx_index_build call (switches.h)
+	if (sw.host || hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return build_bwt_sa_host(pac, pac_bytes, l_pac, cnt_fwd, prefix);
+	return gpuidx::build_bwt_sa_device(pac, pac_bytes, l_pac, cnt_fwd, prefix, sw);
 }
 } // namespace arx

@@ -79,10 +79,10 @@ extern "C" int arx_selftest_extend(int32_t device, const uint8_t *pac, int64_t l
 		HipRT rt;
 		if (!rt.init(device).empty()) return ARX_E_DEVICE;
 		rt.timing = false;
-		rt.ext_merge_below = mode == 1 ? INT_MAX : 0;
-		rt.ext_old = mode == 2;
-		rt.sw_simple = mode == 3;
-		if (grid_cap > 0) { rt.n_cu = 1; rt.coop_bpc = grid_cap; rt.bpc = grid_cap; } // (the one-thread form: max_blocks() = grid_cap)
+		rt.sw.ext_merge_below = mode == 1 ? INT_MAX : 0;
+		rt.sw.ext_old = mode == 2;
+		rt.sw.sw_simple = mode == 3;
+		if (grid_cap > 0) { rt.n_cu = 1; rt.sw.coop_bpc = grid_cap; rt.sw.bpc = grid_cap; } // (the one-thread form: max_blocks() = grid_cap)
 		KExtend f{pac_view(rt, pac, l_pac), rt.alloc<uint8_t>((size_t)n_bases + 1), rt.alloc<ExtTask>(tk.size()), rt.alloc<ExtRes>((size_t)n)};
 		rt.h2d((void *)f.bases, bases, (size_t)n_bases);
 		rt.h2d((void *)f.tasks, tk.data(), tk.size() * sizeof(ExtTask));
@@ -117,15 +117,15 @@ extern "C" int arx_selftest_rescue_sw(int32_t device, const uint8_t *pac, int64_
 		HipRT rt;
 		if (!rt.init(device).empty()) return ARX_E_DEVICE;
 		rt.timing = false;
-		rt.sw_filter = filter ? 1 : 0;
-		rt.sw_filter_stats = 0;
-		rt.sw_simple = sw_simple != 0;
-		if (grid_cap > 0) { rt.n_cu = 1; rt.coop_bpc = grid_cap; rt.bpc = grid_cap; }
+		rt.sw.sw_filter = filter ? 1 : 0;
+		rt.sw.sw_filter_stats = 0;
+		rt.sw.sw_simple = sw_simple != 0;
+		if (grid_cap > 0) { rt.n_cu = 1; rt.sw.coop_bpc = grid_cap; rt.sw.bpc = grid_cap; }
 		// the one-thread form keeps its mate, window and row maxima in per-slot scratch: one slot per thread of its grid
 		const int q_cap = (max_len + 15) & ~15, t_cap = SW_T_CAP;
 		const int slots = ((n + 63) / 64 < rt.max_blocks() ? (n + 63) / 64 : rt.max_blocks()) * 64;
 		KSwU8 f{pac_view(rt, pac, l_pac), rt.alloc<uint8_t>((size_t)n_bases + 1), rt.alloc<int32_t>((size_t)n), rt.alloc<int32_t>((size_t)n),
-		        rt.alloc<SwTask>((size_t)n), rt.alloc<U8Res>((size_t)n), rt.sw_simple ? rt.alloc<uint8_t>((size_t)slots * (q_cap + 2 * t_cap)) : nullptr, q_cap, t_cap};
+		        rt.alloc<SwTask>((size_t)n), rt.alloc<U8Res>((size_t)n), rt.sw.sw_simple ? rt.alloc<uint8_t>((size_t)slots * (q_cap + 2 * t_cap)) : nullptr, q_cap, t_cap};
 		rt.h2d((void *)f.bases, mates, (size_t)n_bases);
 		rt.h2d((void *)f.base_off, mate_off, (size_t)n * 4);
 		rt.h2d((void *)f.lens, mate_len, (size_t)n * 4);

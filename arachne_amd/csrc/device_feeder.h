@@ -21,6 +21,7 @@
 #include <vector>
 #include "feeder.h"
 #include "dev_fastq.h"
+#include "switches.h"
 
 namespace arx {
 
@@ -37,14 +38,14 @@ public:
 		// every chunk boundary a boundary between parses)
 		size_t per = SLAB_TARGET / chunk_;
 		per = per < 1 ? 1 : per > 64 ? 64 : per;
-		if (const char *e = getenv("ARX_FEEDER_PARSE_CHUNKS")) { const long v = atol(e); if (v >= 1 && (size_t)v * chunk_ <= MAX_CHUNK) per = (size_t)v; }
+		if (sw_.parse_chunks) { const long v = *sw_.parse_chunks; if (v >= 1 && (size_t)v * chunk_ <= MAX_CHUNK) per = (size_t)v; }
 		const char *path[2] = {r1, r2};
 		for (int f = 0; f < 2; ++f)
 			if (!rd_[f].open(path[f], chunk_, per)) { error = std::string("cannot open ") + path[f]; return ARX_E_IO; }
 		const std::string e = rt.init(device_);
 		if (!e.empty()) { error = e; return ARX_E_DEVICE; }
 		ready_ = true;
-		if (getenv("ARX_FEEDER_TIMES")) rt.set_timing(true);
+		if (sw_.times) rt.set_timing(true);
 		for (int f = 0; f < 2; ++f)
 			for (int i = 0; i < 2; ++i) registered_[f][i] = RT::host_register(rd_[f].slab(i), rd_[f].slab_cap()) == 0;
 		meta_ = rt.template palloc<int32_t>(16);
@@ -55,7 +56,7 @@ public:
 	~DeviceFeeder() override
 	{
 		if (!ready_) return; // open() failed before the runtime was initialised: nothing on the device, the readers free their own buffers
-		if (getenv("ARX_FEEDER_TIMES")) { // diagnostics: where the feeder thread's time went, and the kernels' own times (HIP events)
+		if (sw_.times) { // diagnostics: where the feeder thread's time went, and the kernels' own times (HIP events)
 			rt.bind();
 			for (auto &kv : rt.timers()) fprintf(stderr, "[arx feeder] %-16s %8.3f ms in %lld launches\n", kv.first.c_str(), kv.second.ms, (long long)kv.second.calls);
 			fprintf(stderr, "[arx feeder] %lld records: waiting for the readers %.3f s, upload %.3f, line index %.3f, records %.3f, fields + scan %.3f, fill + copy home %.3f, "
@@ -359,6 +360,7 @@ private:
 	}
 
 	RT rt;
+	const FeederSwitches sw_; // read when the feeder is created (switches.h)
 	int device_;
 	size_t chunk_;
 	ChunkReader rd_[2];

@@ -58,6 +58,7 @@ static __global__ void __launch_bounds__(256) k_locate_dyn(IndexView ix, Seed *o
 // until `batch` of them do (or nobody can extend), and the wave runs that code once for all of them.
 constexpr int SEED_ROW = 132; // bytes per lane for the longest read: 256 bases + pad
 // The row is as long as the batch's longest read needs (an odd number of words): LDS must not be what limits the waves per SIMD.
+// Never longer than SEED_ROW, which every seeding kernel is laid out for: the host picks a kernel without looking at the row (hip_rt.h run_seed_bwd).
 inline int seed_row_bytes(int max_len) { int w = ((max_len + 1) / 2 + 3) / 4; if (!(w & 1)) ++w; return w * 4 < SEED_ROW ? w * 4 : SEED_ROW; }
 #ifndef ARX_SEED_WPE
 #define ARX_SEED_WPE 4 // waves per SIMD the seeding kernels are compiled for (register budget 512 / WPE)

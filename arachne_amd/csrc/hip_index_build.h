@@ -36,6 +36,7 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include "switches.h"
 
 namespace arx {
 namespace gpuidx {
@@ -331,21 +332,17 @@ struct DeviceBuildStats { double s_text = 0, s_bucket = 0, s_chunks = 0, s_round
 // pac: forward strand (l_pac bases, 4 per byte); cnt_fwd[c]: occurrences of base c on the forward strand.
 // Writes <prefix>.bwt and <prefix>.sa.  Returns "" or an error message.
 inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int64_t l_pac_, const uint64_t cnt_fwd[4], const std::string &prefix,
-                                       int device = -1, DeviceBuildStats *stats = nullptr)
+                                       const IndexBuildSwitches &sw, DeviceBuildStats *stats = nullptr)
 {
 	const u64 l_pac = (u64)l_pac_, n = 2 * l_pac;
-	const bool verbose = getenv("ARX_INDEX_VERBOSE") != nullptr;
-	const bool verify = !(getenv("ARX_INDEX_VERIFY") && atoi(getenv("ARX_INDEX_VERIFY")) == 0);
-	u64 chunk_cap = getenv("ARX_INDEX_CHUNK") ? strtoull(getenv("ARX_INDEX_CHUNK"), nullptr, 10) : (u64)512 << 20;
-	u64 slice_cap = getenv("ARX_INDEX_SLICE") ? strtoull(getenv("ARX_INDEX_SLICE"), nullptr, 10) : (u64)256 << 20;
-	if (chunk_cap < 1) chunk_cap = 1;
-	if (slice_cap < 1) slice_cap = 1;
+	const bool verbose = sw.verbose, verify = sw.verify;
+	const u64 chunk_cap = sw.chunk < 1 ? 1 : sw.chunk, slice_cap = sw.slice < 1 ? 1 : sw.slice;
 	DeviceBuildStats st_;
 	DeviceBuildStats &S = stats ? *stats : st_;
 	try {
 		int ndev = 0;
 		if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return "no HIP device visible";
-		if (device >= 0) ARX_IDX_CHECK(hipSetDevice(device));
+		if (sw.device >= 0) ARX_IDX_CHECK(hipSetDevice(sw.device));
 		hipStream_t st = 0; // the null stream: this is a stand-alone tool step, not part of a batch
 		Timer tm;
 		Scratch sc;

@@ -15,6 +15,7 @@
 #include "hip_nw_coop.h"
 #include "hip_fm_coop.h"
 #include "index_build.h"
+#include "switches.h"
 
 namespace arx {
 
@@ -48,19 +49,16 @@ struct KernelTimer { double ms = 0; int64_t calls = 0, items = 0; };
 std::string product_bwt_sa(const uint8_t *pac, size_t pac_bytes, int64_t l_pac, const uint64_t cnt_fwd[4], const std::string &prefix); // arx_index.hip
 
 struct HipRT {
+	BatchSwitches sw; // the ARX_* environment as it was when this runtime (= its batch handle, context or device feeder) was created (switches.h)
 	static const char *name() { return "hip:gfx950"; }
 	static BwtSaFn bwt_sa_fn() { return product_bwt_sa; } // arx_index_build: the suffix sort runs in HBM
 	hipStream_t stream = 0;
 	// side stream for launches that are one wavefront's tail (the heavy-item kernels): they run beside the launches that follow on the main
-	// stream until aux_join()
+	// stream until aux_join().  Off unless sw.aux_stream
 	hipStream_t aux = 0; hipEvent_t ev_fork = 0, ev_join = 0; bool aux_pending = false;
-	// Off by default: beside each other the launches shorten one batch alone (62.2 -> 59.5 ms) but cost 5-6 % of the throughput with three
-	// batches in flight (7.1 against 7.6 M pairs/s, same box): the other batches' kernels already fill the chip while a tail runs, and the
-	// cross-stream waits add bubbles.  ARX_AUX_STREAM=1 turns it on (latency-bound use: one batch at a time).
-	bool aux_ok = getenv("ARX_AUX_STREAM") && atoi(getenv("ARX_AUX_STREAM")) != 0;
 	template <class L> void on_aux(L f)
 	{
-		if (!aux_ok) { f(); return; }
+		if (!sw.aux_stream) { f(); return; }
 		if (!aux) {
 			ARX_HIP_CHECK(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
 			ARX_HIP_CHECK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming)); ARX_HIP_CHECK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
@@ -97,7 +95,7 @@ struct HipRT {
 	}
 	~HipRT()
 	{
-		if (sw_filter_stats && sw_tasks_seen) fprintf(stderr, "[arx] rescue alignments queued %lld, run after the pre-filter %lld\n", (long long)sw_tasks_seen, (long long)sw_tasks_run);
+		if (sw.sw_filter_stats && sw_tasks_seen) fprintf(stderr, "[arx] rescue alignments queued %lld, run after the pre-filter %lld\n", (long long)sw_tasks_seen, (long long)sw_tasks_run);
 		for (auto &sl : slabs) (void)hipFree(sl.p);
 		if (scan_tmp) hipFree(scan_tmp);
 		if (d_total) hipFree(d_total);
@@ -178,33 +176,22 @@ struct HipRT {
 	void memset_bytes(void *d, int v, size_t bytes) { ARX_HIP_CHECK(hipMemsetAsync(d, v, bytes, stream)); }
 	void sync() { ARX_HIP_CHECK(hipStreamSynchronize(stream)); }
 
-	// 8 resident 64-thread blocks per CU give every SIMD two waves of these latency-bound kernels
-	int bpc = getenv("ARX_BPC") ? atoi(getenv("ARX_BPC")) : 16;           // resident 64-lane blocks per CU of the thread-per-item kernels (sizes their per-slot scratch)
-	int coop_bpc = getenv("ARX_COOP_BPC") ? atoi(getenv("ARX_COOP_BPC")) : 64; // grid cap of the 16-lane DP kernels (no per-slot scratch; grid-stride)
-	int ext_merge_below = getenv("ARX_EXT_MERGE") ? atoi(getenv("ARX_EXT_MERGE")) : 30000; // rounds with fewer extensions run all length classes in one launch
-	int strat_bpc = getenv("ARX_STRAT_BPC") ? atoi(getenv("ARX_STRAT_BPC")) : 4 * ARX_SEED_WPE; // resident blocks per CU of the third seeding pass
-	int max_blocks() const { return n_cu * bpc; }
-	int coop_blocks(int n) const { int b = (n + 3) / 4, cap = n_cu * coop_bpc; return b < cap ? b : cap; }
+	// launch shapes (sw.bpc, sw.coop_bpc, ...: switches.h)
+	int max_blocks() const { return n_cu * sw.bpc; }
+	int coop_blocks(int n) const { int b = (n + 3) / 4, cap = n_cu * sw.coop_bpc; return b < cap ? b : cap; }
 	int max_slots() const { return max_blocks() * 64; }
 	int max_slots_small() const { return n_cu * 64; }
 	// seeding kernels: 4 * ARX_SEED_WPE resident blocks per CU (their register budget is compiled for that many waves per SIMD)
-	int seed_bpc = getenv("ARX_SEED_BPC") ? atoi(getenv("ARX_SEED_BPC")) : 4 * ARX_SEED_WPE;
-	int max_seed_slots() const { return n_cu * seed_bpc * 64; }
-	// the row-parallel backward kernel needs 94 VGPRs: five wavefronts per SIMD fit, not only the four its launch bound asks for, so its grid is
-	// 20 workgroups per CU (4.81 -> 4.62 ms alone; 24 and more lose again, and a build that forces six per SIMD spills: 7.2 ms)
-	int seed_bwd_mid = getenv("ARX_SEED_BWD_MID") ? atoi(getenv("ARX_SEED_BWD_MID")) : 21; // longest list of the 21-lane bin of the backward sweeps (16: none)
-	int seed_bwd_e_bpc = getenv("ARX_SEED_BWD_E_BPC") ? atoi(getenv("ARX_SEED_BWD_E_BPC")) : 32; // its resident workgroups per CU (62 VGPRs: eight wavefronts per SIMD fit)
-	int seed_bwd_e_chunk = getenv("ARX_SEED_BWD_E_CHUNK") ? atoi(getenv("ARX_SEED_BWD_E_CHUNK")) : 256; // list entries a wavefront reserves per atomic (entry-parallel sweeps)
-	bool seed_fit32 = !(getenv("ARX_SEED_FIT32") && atoi(getenv("ARX_SEED_FIT32")) == 0); // 0: the general (40-bit) arithmetic in the backward sweeps whatever the index (A/B)
-	bool text_bwd = !(getenv("ARX_TEXT_BWD") && atoi(getenv("ARX_TEXT_BWD")) == 0);
-	int seed_bwd_bpc = getenv("ARX_SEED_BWD_BPC") ? atoi(getenv("ARX_SEED_BWD_BPC")) : 20;
+	int seed_bpc() const { return sw.seed_bpc.value_or(4 * ARX_SEED_WPE); }
+	int strat_bpc() const { return sw.strat_bpc.value_or(4 * ARX_SEED_WPE); } // the third seeding pass
+	int max_seed_slots() const { return n_cu * seed_bpc() * 64; }
 	int seed_row = SEED_ROW;                                   // LDS bytes per lane for its read
 	void set_seed_read_len(int max_len) { seed_row = seed_row_bytes(max_len); }
 	// the batch's reads as nibble rows of seed_row bytes (hip_fm_coop.h: k_pack_reads): what the seeding kernels stage into LDS
 	const uint32_t *seed_qn = nullptr;
 	void seed_prepare(const uint8_t *bases, const int32_t *base_off, const int32_t *lens, int n_reads)
 	{
-		if (sw_simple || n_reads <= 0) return;
+		if (sw.sw_simple || n_reads <= 0) return;
 		const int rw = seed_row >> 2;
 		uint32_t *q = alloc<uint32_t>((size_t)n_reads * rw + 8);
 		Scope sc(*this, "seed_pack", n_reads);
@@ -224,10 +211,9 @@ struct HipRT {
 		if (!free_events.empty()) { hipEvent_t e = free_events.back(); free_events.pop_back(); return e; }
 		hipEvent_t e; ARX_HIP_CHECK(hipEventCreate(&e)); return e;
 	}
-	bool trace_launches = getenv("ARX_TRACE_LAUNCHES") != nullptr; // diagnostics: name every launch on stderr and wait for it (a fault then names its kernel)
 	struct Scope {
 		HipRT &rt; Pending p; bool on; const char *tn;
-		Scope(HipRT &r, const char *n, int64_t it) : rt(r), on(r.timing), tn(r.trace_launches ? n : nullptr)
+		Scope(HipRT &r, const char *n, int64_t it) : rt(r), on(r.timing), tn(r.sw.trace_launches ? n : nullptr)
 		{
 			if (tn) { fprintf(stderr, "[arx launch] %s (%lld items) ...\n", tn, (long long)it); fflush(stderr); }
 			if (!on) return;
@@ -244,7 +230,7 @@ struct HipRT {
 	{
 		if (pending.empty()) return;
 		(void)hipStreamSynchronize(stream);
-		static FILE *launch_log = getenv("ARX_LAUNCH_LOG") ? fopen(getenv("ARX_LAUNCH_LOG"), "a") : nullptr; // diagnostics: one line per launch
+		static FILE *launch_log = sw_open_launch_log(); // diagnostics: one line per launch; one file per process (switches.h)
 		for (auto &p : pending) {
 			float ms = 0;
 			(void)hipEventElapsedTime(&ms, p.a, p.b);
@@ -260,11 +246,10 @@ struct HipRT {
 
 	// for functors that use no per-slot scratch: one item per lane, as many blocks as that takes -- the hardware hands blocks to CUs
 	// as they free up, which balances kernels whose items differ a lot in cost better than a fixed grid-stride assignment
-	bool wide_ok = !(getenv("ARX_WIDE") && atoi(getenv("ARX_WIDE")) == 0);
 	template <class F> void launch_wide(const char *nm, int n, const F &f)
 	{
 		if (n <= 0) return;
-		if (!wide_ok) { launch(nm, n, f); return; }
+		if (!sw.wide) { launch(nm, n, f); return; }
 		Scope sc(*this, nm, n);
 		hipLaunchKernelGGL(k_items<F>, dim3((n + 63) / 64), dim3(64), 0, stream, f, n);
 		ARX_HIP_CHECK(hipGetLastError());
@@ -284,26 +269,25 @@ struct HipRT {
 	void merge_sort_fail(uint32_t *err) { hipLaunchKernelGGL(k_merge_sort_fail, dim3(1), dim3(1), 0, stream, err); merge_sort_fail_cold(err); }
 	void merge_sort_fail_cold(uint32_t *err); // arx_cold.hip
 	// rescue replay of the pairs with long lists, lists staged in LDS (arx_cold.hip)
-	bool rescue_heavy_ok() const { return !(getenv("ARX_RESCUE_HEAVY") && atoi(getenv("ARX_RESCUE_HEAVY")) == 0); }
+	bool rescue_heavy_ok() const { return sw.rescue_heavy; }
 	template <class F> void run_rescue_heavy(const char *nm, int n, const int32_t *list, const F &f);
 	// chaining of the reads with many seed occurrences, one wavefront per read on a working set in LDS (arx_cold.hip); f.heavy_list / f.n_heavy
-	bool chain_heavy_ok() const { return !(getenv("ARX_CHAIN_HEAVY") && atoi(getenv("ARX_CHAIN_HEAVY")) == 0); }
+	bool chain_heavy_ok() const { return sw.chain_heavy; }
 	template <class F> void run_chain_heavy(const char *nm, int n_reads, const F &f);
 	// opt-in (ARX_CHAIN_GROUP=1): chaining of the reads below the heavy kernel's threshold, one 16-lane group per read on a working set in LDS
-	// (arx_cold.hip: k_chain_g16; f.grp_max, f.mid_list / f.n_mid).  Default: every such read is chained by its own thread in HBM (KChain /
-	// KChainMid) -- the group form measured no faster (profiles/chain_group/)
-	bool chain_group_ok() const { return getenv("ARX_CHAIN_GROUP") && atoi(getenv("ARX_CHAIN_GROUP")) != 0; }
+	// (arx_cold.hip: k_chain_g16; f.grp_max, f.mid_list / f.n_mid)
+	bool chain_group_ok() const { return sw.chain_group; }
 	template <class F> void run_chain_group(const char *nm, int n_reads, const F &f);
 	bool rescue_heavy_attr_set = false;
 	bool chain_heavy_attr_set = false; // the 128 KB dynamic-LDS opt-in of k_chain_heavy was made on this runtime's device
 	bool chain_group_attr_set = false; // likewise the dynamic-LDS opt-in of k_chain_g16 (above 64 KB when ARX_CHAIN_HEAVY_MIN is raised)
-	bool dedup_heavy_ok() const { return !(getenv("ARX_DEDUP_HEAVY") && atoi(getenv("ARX_DEDUP_HEAVY")) == 0); }
+	bool dedup_heavy_ok() const { return sw.dedup_heavy; }
 	template <class F> void run_dedup_heavy(const char *nm, int n_reads, const F &f); // likewise the region lists of such reads (f.eh_words ints of scratch per workgroup)
 	template <class F> void launch_cold_impl(const char *nm, int n, const F &f, bool wide = false)
 	{
 		if (n <= 0) return;
 		Scope sc(*this, nm, n);
-		int blocks = (n + 63) / 64; if (!(wide && wide_ok) && blocks > max_blocks()) blocks = max_blocks();
+		int blocks = (n + 63) / 64; if (!(wide && sw.wide) && blocks > max_blocks()) blocks = max_blocks();
 		hipLaunchKernelGGL(k_items<F>, dim3(blocks), dim3(64), 0, stream, f, n);
 		ARX_HIP_CHECK(hipGetLastError());
 	}
@@ -338,15 +322,14 @@ struct HipRT {
 		hipLaunchKernelGGL(k_items<F>, dim3(blocks), dim3(64), 0, stream, f, n);
 		ARX_HIP_CHECK(hipGetLastError());
 	}
-	// rescue SW: 16 lanes per alignment (hip_sw_coop.h); ARX_SW_SIMPLE=1 selects the one-thread-per-alignment kernel for A/B runs
-	bool sw_simple = getenv("ARX_SW_SIMPLE") != nullptr;
+	// rescue SW: 16 lanes per alignment (hip_sw_coop.h); sw.sw_simple selects the one-thread-per-alignment kernel for A/B runs
 	template <class F> void run_sw_u8(const char *nm, int n, const F &f, int max_len)
 	{
 		if (n <= 0) return;
-		if (sw_simple) { launch_rows(nm, n, f, 16 * ((max_len + 15) / 16)); return; }
+		if (sw.sw_simple) { launch_rows(nm, n, f, 16 * ((max_len + 15) / 16)); return; }
 		const int blocks = coop_blocks(n);
 		int32_t *order = nullptr, *n_order = nullptr;
-		if (sw_filter) { // tasks that provably stay below min_seed_len never reach the DP (dev_sw.h: sw_prefilter_serial)
+		if (sw.sw_filter) { // tasks that provably stay below min_seed_len never reach the DP (dev_sw.h: sw_prefilter_serial)
 			order = alloc<int32_t>((size_t)n + 1); n_order = order + n;
 			memset0(n_order, 4);
 			Scope sc(*this, "sw_filter", n);
@@ -360,38 +343,23 @@ struct HipRT {
 			else hipLaunchKernelGGL(k_sw_u8_g16<32>, dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, f.base_off, f.lens, f.tasks, f.res, n, order, n_order); // mates of 250+ bases: ksw_i16's eight stripes of up to 32 cells; shorter mates of the same batch take the byte form inside
 			ARX_HIP_CHECK(hipGetLastError());
 		}
-		if (sw_filter_stats) { int32_t k = 0; d2h(&k, n_order, 4); sw_tasks_seen += n; sw_tasks_run += k; }
+		if (sw.sw_filter_stats) { int32_t k = 0; d2h(&k, n_order, 4); sw_tasks_seen += n; sw_tasks_run += k; }
 	}
-	// Off by default: on the benchmark workload 99.6 % of the rescue alignments are real hits in repeat copies (nothing to drop, the
-	// filter's 1 ms per batch is lost); on workloads with chimeric or unpaired reads it drops 40 % of them (profiles/r01/README.md).
-	int sw_filter = getenv("ARX_SW_FILTER") ? atoi(getenv("ARX_SW_FILTER")) : 0;
-	int sw_filter_stats = getenv("ARX_SW_FILTER_STATS") ? atoi(getenv("ARX_SW_FILTER_STATS")) : 0; // diagnostics: one extra host round trip per launch
 	int64_t sw_tasks_seen = 0, sw_tasks_run = 0;
 	// seeding: persistent lanes, items handed out in chunks (hip_fm_coop.h); f is one of pipeline.h's KSeedFwd1 / KSeedFwd2 / KSeedBwd,
 	// f.scratch holds max_slots() forward lists
-	int seed_batch = getenv("ARX_SEED_BATCH") ? atoi(getenv("ARX_SEED_BATCH")) : 48; // lanes that queue up before the slow bookkeeping runs
-	int seed_bwd_budget = getenv("ARX_SEED_BWD_BUDGET") ? atoi(getenv("ARX_SEED_BWD_BUDGET")) : 128; // extensions a lane spends on one backward sweep before handing it to a wavefront (0: never)
-	int seed_chunk = getenv("ARX_SEED_CHUNK") ? atoi(getenv("ARX_SEED_CHUNK")) : 64; // items a wavefront reserves per atomic
-	int seed_bwd_chunk = getenv("ARX_SEED_BWD_CHUNK") ? atoi(getenv("ARX_SEED_BWD_CHUNK")) : (getenv("ARX_SEED_CHUNK") ? atoi(getenv("ARX_SEED_CHUNK")) : 32); // backward sweeps vary most in length: smaller reservations even out the end of the launch (64: 10.3 ms, 32: 9.4, 16: 9.7, 8: 10.3 per batch)
-	// Backward sweeps: 2 (default) = row-parallel, one task per 16/32/64-lane group with the row's entries in registers (k_seed_bwd_g<GL>,
-	// tasks binned by list length): 21.5 -> 10 ms per 667 k-read batch at GRCh38 size.  1 = the pipelined one-lane-per-task kernel
-	// k_seed_bwd2 (51-61 of 64 lanes extending instead of 25-32, but no faster: profiles/r02/README.md).  0 = round 1's k_seed_bwd.
-	// 3 = entry-parallel (k_seed_bwd_e).  All four are held to the CPU restatement interval for interval (tests/test_seed_variants_gpu.py).
-	int seed_bwd2 = getenv("ARX_SEED_BWD2") ? atoi(getenv("ARX_SEED_BWD2")) : 2;
-	int seed_grant = getenv("ARX_SEED_GRANT") ? atoi(getenv("ARX_SEED_GRANT")) : 4; // first forward pass: lanes parked for a pool slice that trigger the hand-out (5.36 ms with none, 5.17 at 16, 4.94 at 4, 5.08 at 1)
-	int seed_bwd_batch = getenv("ARX_SEED_BWD_BATCH") ? atoi(getenv("ARX_SEED_BWD_BATCH")) : 0; // 0: seed_batch
 	// diagnostics (ARX_SEED_STATS=1): lane utilisation of the persistent-lane seeding kernels, printed per launch
 	unsigned long long *seed_dbg_buf = nullptr;
 	unsigned long long *seed_dbg()
 	{
-		if (!getenv("ARX_SEED_STATS")) return nullptr;
+		if (!sw.seed_stats) return nullptr;
 		if (!seed_dbg_buf) ARX_HIP_CHECK(hipMalloc((void **)&seed_dbg_buf, 32));
 		memset0(seed_dbg_buf, 32);
 		return seed_dbg_buf;
 	}
 	void seed_dbg_report(const char *nm, int n)
 	{
-		if (!seed_dbg_buf || !getenv("ARX_SEED_STATS")) return;
+		if (!seed_dbg_buf) return; // (only seed_dbg() allocates it: sw.seed_stats is on)
 		unsigned long long h[4];
 		d2h(h, seed_dbg_buf, 32);
 		fprintf(stderr, "[arx seed stats] %s: %d items, %llu waves, %.0f iterations/wave, %.1f lanes extending per iteration, %.0f slow-path entries/wave\n", nm, n, h[3],
@@ -419,8 +387,8 @@ struct HipRT {
 	}
 	template <class K> void launch_seed_kernel(const char *nm, K kern, int n, const SeedKArgs &A, int32_t *counter, int bpc_, int chunk_ = 0, int batch_ = 0, int grant_ = 64)
 	{
-		if (chunk_ <= 0) chunk_ = seed_chunk;
-		if (batch_ <= 0) batch_ = seed_batch;
+		if (chunk_ <= 0) chunk_ = sw.seed_chunk;
+		if (batch_ <= 0) batch_ = sw.seed_batch;
 		memset0(counter, 4);
 		Scope sc(*this, nm, n);
 		int blocks = (n + 63) / 64; if (blocks > n_cu * bpc_) blocks = n_cu * bpc_;
@@ -430,29 +398,29 @@ struct HipRT {
 	template <class F> void run_seed_fwd1(const char *nm, int n, const F &f, int32_t *counter)
 	{
 		if (n <= 0) return;
-		if (sw_simple) { launch(nm, n, f); return; }
+		if (sw.sw_simple) { launch(nm, n, f); return; }
 		SeedKArgs A{f.ix, f.bases, f.base_off, f.lens, f.P, f.scratch, f.list_cap, f.first1, 0, nullptr, nullptr, 0, seed_row, seed_qn, f.read0, seed_dbg()};
-		launch_seed_kernel(nm, k_seed_fwd1, n, A, counter, seed_bpc, 0, 0, seed_grant); // (the re-seeding pass has one extension per item: no grant step of its own)
+		launch_seed_kernel(nm, k_seed_fwd1, n, A, counter, seed_bpc(), 0, 0, sw.seed_grant); // (the re-seeding pass has one extension per item: no grant step of its own)
 		seed_dbg_report(nm, n);
 	}
 	template <class F> void run_seed_fwd2(const char *nm, int n, const F &f, int32_t *counter)
 	{
 		if (n <= 0) return;
-		if (sw_simple) { launch(nm, n, f); return; }
+		if (sw.sw_simple) { launch(nm, n, f); return; }
 		SeedKArgs A{f.ix, f.bases, f.base_off, f.lens, f.P, f.scratch, f.list_cap, nullptr, f.t0, nullptr, nullptr, 0, seed_row, seed_qn, 0, seed_dbg()};
-		launch_seed_kernel(nm, k_seed_fwd2, n, A, counter, seed_bpc);
+		launch_seed_kernel(nm, k_seed_fwd2, n, A, counter, seed_bpc());
 		seed_dbg_report(nm, n);
 	}
 	template <class F> void run_seed_bwd(const char *nm, int n, const F &f, int32_t *counter)
 	{
 		if (n <= 0) return;
-		if (sw_simple) { launch(nm, n, f); return; }
-		// sweeps longer than seed_bwd_budget extensions are finished by whole wavefronts (k_seed_bwd_wave)
+		if (sw.sw_simple) { launch(nm, n, f); return; }
+		// sweeps longer than sw.seed_bwd_budget extensions are finished by whole wavefronts (k_seed_bwd_wave)
 		int32_t *heavy = alloc<int32_t>((size_t)n + 2);
 		memset0(heavy + n, 4);
-		SeedKArgs A{f.ix, f.bases, f.base_off, f.lens, f.P, nullptr, 0, nullptr, f.t0, heavy, heavy + n, seed_bwd_budget, seed_row, seed_qn, 0, seed_dbg()};
-		if (!text_bwd) A.ix.isa40 = nullptr; // ARX_TEXT_BWD=0: every sweep walked to its end (k_seed_bwd_g hands nothing to KSeedBwdTail)
-		if (seed_bwd2 == 3 && seed_row <= 132) { // entry-parallel sweeps (k_seed_bwd_e): one lane per list entry
+		SeedKArgs A{f.ix, f.bases, f.base_off, f.lens, f.P, nullptr, 0, nullptr, f.t0, heavy, heavy + n, sw.seed_bwd_budget, seed_row, seed_qn, 0, seed_dbg()};
+		if (!sw.text_bwd) A.ix.isa40 = nullptr; // ARX_TEXT_BWD=0: every sweep walked to its end (k_seed_bwd_g hands nothing to KSeedBwdTail)
+		if (sw.seed_bwd2 == 3) { // entry-parallel sweeps (k_seed_bwd_e): one lane per list entry
 			int32_t *ecnt = alloc<int32_t>((size_t)n + 2), *eoff = alloc<int32_t>((size_t)n + 2);
 			Scope sc(*this, nm, n);
 			hipLaunchKernelGGL(k_bwd_e_count, dim3((n + 255) / 256), dim3(256), 0, stream, f.P.tasks, f.t0, n, ecnt);
@@ -461,8 +429,8 @@ struct HipRT {
 			hipLaunchKernelGGL(k_bwd_e_expand, dim3((n + 255) / 256), dim3(256), 0, stream, f.P.tasks, f.P.pool, f.t0, n, eoff, items);
 			if (total > 0) {
 				memset0(counter, 4);
-				int64_t blocks = (total + 63) / 64; if (blocks > (int64_t)n_cu * seed_bwd_e_bpc) blocks = (int64_t)n_cu * seed_bwd_e_bpc;
-				hipLaunchKernelGGL(k_seed_bwd_e, dim3((unsigned)blocks), dim3(64), 0, stream, A, items, (int)total, counter, seed_bwd_e_chunk);
+				int64_t blocks = (total + 63) / 64; if (blocks > (int64_t)n_cu * sw.seed_bwd_e_bpc) blocks = (int64_t)n_cu * sw.seed_bwd_e_bpc;
+				hipLaunchKernelGGL(k_seed_bwd_e, dim3((unsigned)blocks), dim3(64), 0, stream, A, items, (int)total, counter, sw.seed_bwd_e_chunk);
 				hipLaunchKernelGGL(k_bwd_e_final, dim3((n + 255) / 256), dim3(256), 0, stream, f.P.tasks, f.P.pool, f.t0, n);
 			}
 			ARX_HIP_CHECK(hipGetLastError());
@@ -470,23 +438,23 @@ struct HipRT {
 			seed_census_add(n, nullptr, nullptr, nullptr);
 			return;
 		}
-		if (seed_bwd2 == 2 && seed_row <= 132) { // row-parallel sweeps (k_seed_bwd_g<GL>): one task per 16/32/64-lane group, lists in registers
+		if (sw.seed_bwd2 == 2) { // row-parallel sweeps (k_seed_bwd_g<GL>): one task per 16/32/64-lane group, lists in registers
 			uint8_t *flag = alloc<uint8_t>((size_t)n + 8);
 			int32_t *bins = alloc<int32_t>(4 * (size_t)n + 8), *cnt = alloc<int32_t>(8); // cnt[0..3]: bin sizes, cnt[4..7]: the bins' item counters
 			memset0(flag, (size_t)n);
 			memset0(cnt, 32);
-			const int cap = n_cu * seed_bwd_bpc;
+			const int cap = n_cu * sw.seed_bwd_bpc;
 			auto blocks_for = [&](int per_wave) { int b = (n + per_wave - 1) / per_wave; return b > cap ? cap : (b < 1 ? 1 : b); };
 			const size_t xch = 64 * 32;
 			{
 				Scope sc(*this, nm, n);
-				hipLaunchKernelGGL(k_bin_tasks, dim3((n + 255) / 256), dim3(256), 0, stream, f.P.tasks, f.t0, n, bins, bins + n, bins + 2 * (size_t)n, bins + 3 * (size_t)n, cnt, seed_bwd_mid);
-				const bool fit32 = seed_fit32 && (((f.ix.L2[1] - f.ix.L2[0]) | (f.ix.L2[2] - f.ix.L2[1]) | (f.ix.L2[3] - f.ix.L2[2]) | (f.ix.L2[4] - f.ix.L2[3])) >> 32) == 0;
+				hipLaunchKernelGGL(k_bin_tasks, dim3((n + 255) / 256), dim3(256), 0, stream, f.P.tasks, f.t0, n, bins, bins + n, bins + 2 * (size_t)n, bins + 3 * (size_t)n, cnt, sw.seed_bwd_mid);
+				const bool fit32 = sw.seed_fit32 && (((f.ix.L2[1] - f.ix.L2[0]) | (f.ix.L2[2] - f.ix.L2[1]) | (f.ix.L2[3] - f.ix.L2[2]) | (f.ix.L2[4] - f.ix.L2[3])) >> 32) == 0;
 				if (fit32) hipLaunchKernelGGL(k_seed_bwd_g<true>, dim3(blocks_for(4)), dim3(64), ((4 * (size_t)seed_row + 31) & ~(size_t)31) + xch, stream, A, bins, n, cnt, flag);
 				else hipLaunchKernelGGL(k_seed_bwd_g<false>, dim3(blocks_for(4)), dim3(64), ((4 * (size_t)seed_row + 31) & ~(size_t)31) + xch, stream, A, bins, n, cnt, flag);
 				ARX_HIP_CHECK(hipGetLastError());
 			}
-			if (getenv("ARX_SEED_HIST")) { // diagnostics: forward-list lengths of this launch's tasks
+			if (sw.seed_hist) { // diagnostics: forward-list lengths of this launch's tasks
 				std::vector<SeedTask> ht((size_t)n);
 				d2h(ht.data(), f.P.tasks + f.t0, (size_t)n * sizeof(SeedTask));
 				long long hist[40] = {0};
@@ -495,7 +463,7 @@ struct HipRT {
 				for (int i = 0; i < 40; ++i) fprintf(stderr, " %lld", hist[i]);
 				fprintf(stderr, "\n");
 			}
-			if (getenv("ARX_SEED_STATS")) { int32_t h[4]; d2h(h, cnt, 16); fprintf(stderr, "[arx seed stats] backward tasks by list length: <= 16: %d, <= %d: %d, <= 32: %d, longer: %d\n", h[0], seed_bwd_mid, h[1], h[2], h[3]); }
+			if (sw.seed_stats) { int32_t h[4]; d2h(h, cnt, 16); fprintf(stderr, "[arx seed stats] backward tasks by list length: <= 16: %d, <= %d: %d, <= 32: %d, longer: %d\n", h[0], sw.seed_bwd_mid, h[1], h[2], h[3]); }
 			seed_dbg_report(nm, n);
 			{
 				Scope sc(*this, "seed_bwd_wave", n);
@@ -510,18 +478,18 @@ struct HipRT {
 			seed_census_add(n, cnt, heavy + n, flag);
 			return;
 		}
-		if (seed_bwd2) { // pipelined refills (k_seed_bwd2): one wait on memory per iteration
+		if (sw.seed_bwd2) { // pipelined refills (k_seed_bwd2): one wait on memory per iteration
 			uint8_t *flag = alloc<uint8_t>((size_t)n + 8);
 			memset0(flag, (size_t)n);
 			memset0(counter, 4);
 			{
 				Scope sc(*this, nm, n);
-				int blocks = (n + 63) / 64; if (blocks > n_cu * seed_bpc) blocks = n_cu * seed_bpc;
-				hipLaunchKernelGGL(k_seed_bwd2, dim3(blocks), dim3(64), 64 * (size_t)seed_row, stream, A, n, counter, seed_bwd_chunk, flag);
+				int blocks = (n + 63) / 64; if (blocks > n_cu * seed_bpc()) blocks = n_cu * seed_bpc();
+				hipLaunchKernelGGL(k_seed_bwd2, dim3(blocks), dim3(64), 64 * (size_t)seed_row, stream, A, n, counter, sw.seed_bwd_chunk, flag);
 				ARX_HIP_CHECK(hipGetLastError());
 			}
 			seed_dbg_report(nm, n);
-			if (seed_bwd_budget > 0) {
+			if (sw.seed_bwd_budget > 0) {
 				Scope sc(*this, "seed_bwd_wave", n);
 				hipLaunchKernelGGL(k_collect_heavy, dim3((n + 255) / 256), dim3(256), 0, stream, flag, n, f.t0, heavy, heavy + n);
 				hipLaunchKernelGGL(k_seed_bwd_wave, dim3(n_cu * 16), dim3(64), 0, stream, A);
@@ -530,9 +498,9 @@ struct HipRT {
 			seed_census_add(n, nullptr, heavy + n, flag);
 			return;
 		}
-		launch_seed_kernel(nm, k_seed_bwd, n, A, counter, seed_bpc, seed_bwd_chunk, seed_bwd_batch);
+		launch_seed_kernel(nm, k_seed_bwd, n, A, counter, seed_bpc(), sw.seed_bwd_chunk, sw.seed_bwd_batch);
 		seed_dbg_report(nm, n);
-		if (seed_bwd_budget > 0) {
+		if (sw.seed_bwd_budget > 0) {
 			Scope sc(*this, "seed_bwd_wave", n);
 			hipLaunchKernelGGL(k_seed_bwd_wave, dim3(n_cu * 16), dim3(64), 0, stream, A);
 			ARX_HIP_CHECK(hipGetLastError());
@@ -542,19 +510,19 @@ struct HipRT {
 	template <class F> void run_seed_strat(const char *nm, int n, const F &f, int32_t *counter)
 	{
 		if (n <= 0) return;
-		if (sw_simple) { launch(nm, n, f); return; }
+		if (sw.sw_simple) { launch(nm, n, f); return; }
 		memset0(counter, 4);
 		Scope sc(*this, nm, n);
 		StratArgs A{f.ix, f.bases, f.base_off, f.lens, f.strat, f.n_strat, seed_row, seed_qn};
-		int blocks = (n + 63) / 64; if (blocks > n_cu * strat_bpc) blocks = n_cu * strat_bpc;
-		hipLaunchKernelGGL(k_strat_dyn, dim3(blocks), dim3(64), 64 * (size_t)seed_row, stream, A, n, counter, seed_chunk);
+		int blocks = (n + 63) / 64; if (blocks > n_cu * strat_bpc()) blocks = n_cu * strat_bpc();
+		hipLaunchKernelGGL(k_strat_dyn, dim3(blocks), dim3(64), 64 * (size_t)seed_row, stream, A, n, counter, sw.seed_chunk);
 		ARX_HIP_CHECK(hipGetLastError());
 	}
 	// locate: persistent lanes with wave-level work distribution (hip_fm_coop.h); 32 waves per CU to cover the miss latency
 	template <class F> void run_locate(const char *nm, int n, const F &f, int32_t *counter)
 	{
 		if (n <= 0) return;
-		if (sw_simple) { launch(nm, n, f); return; }
+		if (sw.sw_simple) { launch(nm, n, f); return; }
 		if (f.ix.sa40) { launch_wide(nm, n, f); return; } // the whole suffix array is resident: one load per occurrence, no walk to balance
 		memset0(counter, 4);
 		Scope sc(*this, nm, n);
@@ -568,18 +536,18 @@ struct HipRT {
 		int total = 0;
 		for (int c = 0; c < EXT_CLASSES; ++c) total += n_class[c];
 		if (total <= 0) return;
-		if (sw_simple) {
+		if (sw.sw_simple) {
 			for (int c = 0; c < EXT_CLASSES; ++c) { F fc = f; fc.tasks = f.tasks + (size_t)c * stride; launch_rows(nm, n_class[c], fc, MAX_READ_LEN + 2); }
 			return;
 		}
-		if (total >= ext_merge_below) { // big round: one launch per class, each at the occupancy its own register tiling allows
+		if (total >= sw.ext_merge_below) { // big round: one launch per class, each at the occupancy its own register tiling allows
 			for (int c = 0; c < EXT_CLASSES; ++c) {
 				const int nc = n_class[c];
 				if (nc <= 0) continue;
 				Scope sc(*this, nm, nc);
 				const ExtTask *tk = f.tasks + (size_t)c * stride;
 				const int blocks = coop_blocks(nc);
-#define ARX_EXT_LAUNCH(CN, CO) do { if (ext_old) hipLaunchKernelGGL((k_extend_b16<CO, true>), dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, tk, f.res, nc); \
+#define ARX_EXT_LAUNCH(CN, CO) do { if (sw.ext_old) hipLaunchKernelGGL((k_extend_b16<CO, true>), dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, tk, f.res, nc); \
                                     else hipLaunchKernelGGL((k_extend_b16<CN, false>), dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, tk, f.res, nc); } while (0)
 				switch (c) {
 				case 0: ARX_EXT_LAUNCH(2, 4); break;
@@ -597,7 +565,7 @@ struct HipRT {
 		}
 		Scope sc(*this, nm, total);
 		ExtClassShape sh;
-		const int cap = n_cu * coop_bpc;
+		const int cap = n_cu * sw.coop_bpc;
 		int blocks = 0;
 		for (int c = 0; c < EXT_CLASSES; ++c) {
 			sh.n[c] = n_class[c];
@@ -605,16 +573,15 @@ struct HipRT {
 			if (nb > 0 && (total + 3) / 4 > cap) { nb = (int)((int64_t)nb * cap / ((total + 3) / 4)); if (nb < 1) nb = 1; } // share the grid cap by class size
 			sh.nb[c] = nb; blocks += nb;
 		}
-		if (ext_old) hipLaunchKernelGGL(k_extend_classes_b<true>, dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, f.tasks, stride, f.res, sh);
+		if (sw.ext_old) hipLaunchKernelGGL(k_extend_classes_b<true>, dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, f.tasks, stride, f.res, sh);
 		else hipLaunchKernelGGL(k_extend_classes_b<false>, dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, f.tasks, stride, f.res, sh);
 		ARX_HIP_CHECK(hipGetLastError());
 	}
-	bool ext_old = getenv("ARX_EXT_OLD") && atoi(getenv("ARX_EXT_OLD")) != 0; // A/B: round 2's extension kernel (ext2_g16) on the same class lists
 	// CIGARs of the gapped regions: 16 lanes per region (hip_nw_coop.h); f is pipeline.h's KReg2Aln
 	template <class F> void run_reg2aln_nw(const char *nm, int n, const int32_t *n_class, const F &f, uint8_t *zbuf, const int32_t *z_off)
 	{
 		if (n <= 0) return;
-		if (sw_simple) { launch_small(nm, n, f); return; }
+		if (sw.sw_simple) { launch_small(nm, n, f); return; }
 		// one launch per band class: the four groups of a wavefront then run the same tiling, and the class kernel holds only the tilings the
 		// class can need (its own and the doubled band's): 5 / 4 / 3 / 2 / 2 wavefronts per SIMD instead of 2 for all
 		int32_t *punt = alloc<int32_t>((size_t)n + 4), *n_punt = punt + n;

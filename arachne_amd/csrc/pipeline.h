@@ -19,6 +19,7 @@
 #include "dev_chain.h"
 #include "dev_sw.h"
 #include "dev_regs.h"
+#include "switches.h"
 
 #ifndef ARX_STAT_BWD
 #define ARX_STAT_BWD(n, ext) ((void)(ext)) // the host test double can histogram the backward tasks here
@@ -530,10 +531,7 @@ template <class RT> class Pipeline {
 public:
 	RT &rt;
 	IndexView ix;
-	bool trace = getenv("ARX_TRACE") != nullptr; // per-round progress on stderr
-	int seed_group_reads = getenv("ARX_SEED_GROUP") ? atoi(getenv("ARX_SEED_GROUP")) : 0; // reads per pass through the first two seeding passes (0: the whole batch at once; groups shrink the interval pool from 12 KB to 12 KB x group / batch per read at the price of under-filled forward launches: 0 / 360 k / 180 k / 90 k reads -> 7.0 / 9.5 / 11.4 / 14.1 ms of seed_fwd per 667 k-read batch, seed_bwd unchanged)
-	int seed_tasks_per_read = getenv("ARX_SEED_TASKS") ? atoi(getenv("ARX_SEED_TASKS")) : 12;   // seeding tasks per read (all three passes), same rule
-	int seed_pool_per_read = getenv("ARX_SEED_POOL") ? atoi(getenv("ARX_SEED_POOL")) : 384; // interval-pool entries per read (3 per forward-list entry); an overflow is reported, never silent
+	const PipelineSwitches sw; // the stages' environment switches as they were when this pipeline (= its batch handle) was created (switches.h)
 	explicit Pipeline(RT &rt_, const IndexView &ix_) : rt(rt_), ix(ix_) {}
 
 	// device-resident input of one batch; the buffers are kept by the handle and reused by arx_batch_reset (cap_*: what they hold)
@@ -643,13 +641,13 @@ public:
 		// Tried in round 2 because scattered 64-byte reads run at 52 G blocks/s while a kernel's footprint stays within ~3.5 GiB and at
 		// 28-34 G/s beyond (tools/calib_random.hip: the reach of the address translation caches) and the GRCh38 Occ table alone is 2.9 GiB;
 		// measured: the pool's footprint is NOT what holds the backward sweeps back (no change), so the default is one group.
-		const int GR = seed_group_reads > 0 ? seed_group_reads : R;
+		const int GR = sw.seed_group_reads > 0 ? sw.seed_group_reads : R;
 		const int Rg_max = GR < R ? GR : R;
 		SeedPools P;
 		// per read, on average: 12 tasks and seed_pool_per_read pool entries for reads of up to 150 bases, in proportion for longer ones
 		// (a 255-base read that matches nowhere yields a first-pass task every ~12 bases on a small genome); an overflow is reported
-		const int64_t len_scale = b.max_len > 150 ? (b.max_len + 149) / 150 : 1, tasks_per_read = (int64_t)seed_tasks_per_read * len_scale;
-		P.pool_cap = (int64_t)Rg_max * seed_pool_per_read * len_scale; P.task_cap = (int32_t)(Rg_max * tasks_per_read < 0x7fffffff ? Rg_max * tasks_per_read : 0x7fffffff);
+		const int64_t len_scale = b.max_len > 150 ? (b.max_len + 149) / 150 : 1, tasks_per_read = (int64_t)sw.seed_tasks_per_read * len_scale;
+		P.pool_cap = (int64_t)Rg_max * sw.seed_pool_per_read * len_scale; P.task_cap = (int32_t)(Rg_max * tasks_per_read < 0x7fffffff ? Rg_max * tasks_per_read : 0x7fffffff);
 		P.pool = rt.template alloc<Biv>((size_t)P.pool_cap + 1); P.tasks = rt.template alloc<SeedTask>((size_t)P.task_cap + 1);
 		P.cursors = rt.template alloc<int32_t>(2); P.err = w.err;
 		int32_t *first1 = rt.template alloc<int32_t>(R + 1), *first2 = rt.template alloc<int32_t>(R + 1);
@@ -661,7 +659,7 @@ public:
 			rt.run_seed_fwd1("seed_fwd", Rg, kf, w.counter);
 			rt.d2h(cur, P.cursors, 8);
 			const int n1 = cur[1] < P.task_cap ? cur[1] : P.task_cap;
-			if (getenv("ARX_SEED_DUMP")) { // diagnostics: the first-pass tasks of the first reads and their forward lists
+			if (sw.seed_dump) { // diagnostics: the first-pass tasks of the first reads and their forward lists
 				for (int r = 0; r < 3 && r < Rg; ++r) {
 					int32_t t = 0;
 					rt.d2h(&t, first1 + g0 + r, 4);
@@ -675,7 +673,7 @@ public:
 				}
 			}
 			KSeedBwd kb{ix, b.bases, b.base_off, b.lens, P, 0};
-			kb.by_entry = getenv("ARX_SEED_BWD_ENTRY") != nullptr; // (only the one-thread form looks at it: the host test double, ARX_SW_SIMPLE)
+			kb.by_entry = sw.seed_bwd_entry; // (only the one-thread form looks at it: the host test double, ARX_SW_SIMPLE)
 			rt.run_seed_bwd("seed_bwd", n1, kb, w.counter);
 			KSeedGather1 kg1{b.bases, b.base_off, P, first1, w.intv, w.n_intv, first2, g0};
 			rt.launch_wide("seed_gather", Rg, kg1);
@@ -716,7 +714,7 @@ public:
 		w.nodes = rt.template alloc<BtNode>(T / 3 + 4 * (size_t)R + 8); w.iscr = rt.template alloc<int32_t>(7 * T + 8); w.sout = rt.template alloc<Seed>(T);
 		w.n_chain = rt.template alloc<int32_t>(R + 1);
 		KChain k{ix, b.lens, w.intv, w.n_intv, w.occ_off, w.occ_seed, w.occ_rid, w.next, w.ctmp, w.nodes, w.iscr, w.cout, w.sout, w.n_chain, w.err, nullptr, nullptr,
-		         getenv("ARX_CHAIN_HEAVY_MIN") ? atoi(getenv("ARX_CHAIN_HEAVY_MIN")) : CHAIN_HEAVY_MIN};
+		         sw.chain_heavy_min.value_or(CHAIN_HEAVY_MIN)};
 		if (rt.chain_heavy_ok()) { k.heavy_list = rt.template alloc<int32_t>(R + 4); k.n_heavy = k.heavy_list + R; rt.memset0(k.n_heavy, 16); }
 		if constexpr (HasChainGroup<RT>::value) {
 			// the group path: KChain leaves the reads below the heavy threshold to k_chain_g16 (KChainMid is not launched); the reads
@@ -728,7 +726,7 @@ public:
 				rt.memset0(k.n_mid, 16);
 			}
 		}
-		const int mid_min = getenv("ARX_CHAIN_MID_MIN") ? atoi(getenv("ARX_CHAIN_MID_MIN")) : 16; // 0: no launch of their own for the reads in between
+		const int mid_min = sw.chain_mid_min; // 0: no launch of their own for the reads in between
 		const int mid_cap = R / 4 + 64; // the list holds a quarter of the reads; a read beyond that is chained where it is found
 		if (mid_min > 0 && k.heavy_list && !k.grp_max) { k.mid_list = rt.template alloc<int32_t>((size_t)mid_cap + 4); k.n_mid = k.mid_list + mid_cap; k.mid_min = mid_min; k.mid_cap = mid_cap; rt.memset0(k.n_mid, 16); }
 		rt.launch_wide("chain", R, k);
@@ -768,7 +766,7 @@ public:
 			n_act = cnt[EXT_CLASSES];
 			int nt = 0;
 			for (int c = 0; c < EXT_CLASSES; ++c) nt += cnt[c];
-			if (trace) { fprintf(stderr, "[arx] ext round %d: %d chains active, %d DPs\n", round, n_act, nt); fflush(stderr); }
+			if (sw.trace) { fprintf(stderr, "[arx] ext round %d: %d chains active, %d DPs\n", round, n_act, nt); fflush(stderr); }
 			if (round > w.T + R + 8) { uint32_t e = ERR_INTERNAL; rt.h2d(w.err, &e, 4); break; } // cannot happen: every round retires a DP or a chain
 			if (nt == 0) continue;
 			out.n_ext_tasks += nt; ++out.ext_rounds;
@@ -777,9 +775,9 @@ public:
 		}
 		KExtGather kg{w.occ_off, w.n_chain, chain_off, w.cout, w.est, pool, w.regs, n_ext};
 		rt.launch_wide("ext_gather", R, kg);
-		if (trace) { fprintf(stderr, "[arx] dedup\n"); fflush(stderr); }
+		if (sw.trace) { fprintf(stderr, "[arx] dedup\n"); fflush(stderr); }
 		KDedup kd{ix, b.bases, b.base_off, b.lens, w.occ_off, n_ext, w.regs, w.rtmp, w.idx, w.eh, eh_words, w.n_core, w.core_clean, nullptr, nullptr,
-		          getenv("ARX_DEDUP_HEAVY_MIN") ? atoi(getenv("ARX_DEDUP_HEAVY_MIN")) : DEDUP_HEAVY_MIN};
+		          sw.dedup_heavy_min.value_or(DEDUP_HEAVY_MIN)};
 		if (rt.dedup_heavy_ok()) { kd.heavy_list = rt.template alloc<int32_t>(R + 4); kd.n_heavy = kd.heavy_list + R; rt.memset0(kd.n_heavy, 16); }
 		rt.launch_cold("dedup", R, kd);
 		if (kd.heavy_list) rt.run_dedup_heavy("dedup_heavy", R, kd);
@@ -803,20 +801,20 @@ public:
 		w.sw_scr = rt.template alloc<uint8_t>((size_t)slots * (q_cap + 2 * t_cap));
 		uint8_t *hv = nullptr; int32_t *hv_list = nullptr, *n_hv = nullptr;
 		if (rt.rescue_heavy_ok()) { hv = rt.template alloc<uint8_t>(NP + 8); hv_list = rt.template alloc<int32_t>(NP + 1); n_hv = rt.template alloc<int32_t>(2); rt.memset0(n_hv, 8); }
-		KPairInit ki{w.occ_off, w.n_core, w.preg_off, w.regs, w.pregs, w.n_regs, w.rst, w.core_clean, w.cap, hv, hv_list, n_hv, getenv("ARX_RESCUE_HEAVY_MIN") ? atoi(getenv("ARX_RESCUE_HEAVY_MIN")) : RESCUE_HEAVY_MIN};
+		KPairInit ki{w.occ_off, w.n_core, w.preg_off, w.regs, w.pregs, w.n_regs, w.rst, w.core_clean, w.cap, hv, hv_list, n_hv, sw.rescue_heavy_min.value_or(RESCUE_HEAVY_MIN)};
 		rt.launch_wide("pair_init", NP, ki);
 		int n_heavy = 0;
 		if (hv) rt.d2h(&n_heavy, n_hv, 4);
 		for (int round = 0;; ++round) {
 			rt.memset0(w.counter, 4);
-			KRescueStep ks{ix, b.lens, w.preg_off, w.pregs, w.ptmp, w.pidx, w.n_regs, w.rst, w.sres, w.stask, w.counter, n_slots, getenv("ARX_RESCUE_NO_AHEAD") ? 1 : 0, (int32_t)(2 * w.P), hv};
+			KRescueStep ks{ix, b.lens, w.preg_off, w.pregs, w.ptmp, w.pidx, w.n_regs, w.rst, w.sres, w.stask, w.counter, n_slots, sw.rescue_no_ahead ? 1 : 0, (int32_t)(2 * w.P), hv};
 			if (n_heavy > 0) rt.run_rescue_heavy("rescue_heavy", n_heavy, hv_list, ks); // on the side stream: a few wavefronts' worth of work
 			rt.launch_cold("rescue_step", NP, ks);
 			rt.aux_join();
 			int nt = read_counter(w);
-			if (trace) { fprintf(stderr, "[arx] rescue round %d: %d tasks\n", round, nt); fflush(stderr); }
+			if (sw.trace) { fprintf(stderr, "[arx] rescue round %d: %d tasks\n", round, nt); fflush(stderr); }
 			if (nt == 0) {
-				if (trace) { int32_t ns[2]; rt.d2h(ns, n_slots, 8); fprintf(stderr, "[arx] rescue: %d SWs queued ahead, %d single\n", ns[0], ns[1]); fflush(stderr); }
+				if (sw.trace) { int32_t ns[2]; rt.d2h(ns, n_slots, 8); fprintf(stderr, "[arx] rescue: %d SWs queued ahead, %d single\n", ns[0], ns[1]); fflush(stderr); }
 				break;
 			}
 			if (round > 2 * MAX_RESCUE + 4) { uint32_t e = ERR_INTERNAL; rt.h2d(w.err, &e, 4); break; }

@@ -12,6 +12,7 @@
 #include <map>
 #include <string>
 #include <vector>
+#include "../../arachne_amd/csrc/switches.h"
 #define ARX_DEV
 #define ARX_DEVI inline
 #define ARX_HDI inline
@@ -32,7 +33,7 @@ static void sim_stat_rescue(int n, bool ins, int clean)
 {
 	++sim_rescue_calls; sim_rescue_ins += ins; sim_rescue_skipped += (!ins && clean); sim_rescue_nsum += n; sim_rescue_n2sum += (long)n * n; if (n > sim_rescue_nmax) sim_rescue_nmax = n;
 }
-struct SimStatPrinter { ~SimStatPrinter() { if (getenv("ARX_RESCUE_STATS")) fprintf(stderr, "[sim] rescue applies %ld, inserted %ld, dedup skipped %ld, mean n %.1f, mean n^2 %.1f, max n %ld; fast inserts %ld, fallbacks %ld\n", sim_rescue_calls, sim_rescue_ins, sim_rescue_skipped, sim_rescue_calls ? (double)sim_rescue_nsum / sim_rescue_calls : 0.0, sim_rescue_calls ? (double)sim_rescue_n2sum / sim_rescue_calls : 0.0, sim_rescue_nmax, sim_rescue_fast_hits, sim_rescue_fast_fallbacks); } } sim_stat_printer;
+struct SimStatPrinter { ~SimStatPrinter() { if (arx::sw_present("ARX_RESCUE_STATS")) fprintf(stderr, "[sim] rescue applies %ld, inserted %ld, dedup skipped %ld, mean n %.1f, mean n^2 %.1f, max n %ld; fast inserts %ld, fallbacks %ld\n", sim_rescue_calls, sim_rescue_ins, sim_rescue_skipped, sim_rescue_calls ? (double)sim_rescue_nsum / sim_rescue_calls : 0.0, sim_rescue_calls ? (double)sim_rescue_n2sum / sim_rescue_calls : 0.0, sim_rescue_nmax, sim_rescue_fast_hits, sim_rescue_fast_fallbacks); } } sim_stat_printer;
 #define ARX_STAT_RESCUE(pair, n, inserts, clean) sim_stat_rescue((n), (inserts), (clean))
 // the rescue pre-filter against the DP it replaces: a filtered task must score below min_seed_len (always checked)
 static long sim_swf_tasks = 0, sim_swf_filtered = 0, sim_swf_low = 0;
@@ -41,7 +42,7 @@ static void sim_sw_filter_check(bool pass, int score)
 	++sim_swf_tasks; sim_swf_filtered += !pass; sim_swf_low += score < 19;
 	if (!pass && score >= 19) { fprintf(stderr, "[sim] rescue pre-filter dropped an alignment of score %d\n", score); abort(); }
 }
-struct SimSwfPrinter { ~SimSwfPrinter() { if (getenv("ARX_RESCUE_STATS")) fprintf(stderr, "[sim] rescue SWs %ld, below min_seed_len %ld, filtered %ld\n", sim_swf_tasks, sim_swf_low, sim_swf_filtered); } } sim_swf_printer;
+struct SimSwfPrinter { ~SimSwfPrinter() { if (arx::sw_present("ARX_RESCUE_STATS")) fprintf(stderr, "[sim] rescue SWs %ld, below min_seed_len %ld, filtered %ld\n", sim_swf_tasks, sim_swf_low, sim_swf_filtered); } } sim_swf_printer;
 #define ARX_SW_FILTER_CHECK(pass, score) sim_sw_filter_check((pass), (score))
 static long sim_bwd_hist_n[8], sim_bwd_hist_ext[8], sim_bwd_ext_by_n[8], sim_bwd_max_ext;
 static void sim_stat_bwd(int n, int ext)
@@ -50,13 +51,14 @@ static void sim_stat_bwd(int n, int ext)
 	int b = 0; while (b < 7 && (16 << b) <= ext) ++b;
 	++sim_bwd_hist_n[a]; ++sim_bwd_hist_ext[b]; sim_bwd_ext_by_n[a] += ext; if (ext > sim_bwd_max_ext) sim_bwd_max_ext = ext;
 }
-struct SimBwdPrinter { ~SimBwdPrinter() { if (!getenv("ARX_BWD_STATS")) return; fprintf(stderr, "[sim] backward tasks by list length (<=1,2,4,..,128):"); for (int a = 0; a < 8; ++a) fprintf(stderr, " %ld", sim_bwd_hist_n[a]);
+struct SimBwdPrinter { ~SimBwdPrinter() { if (!arx::sw_present("ARX_BWD_STATS")) return; fprintf(stderr, "[sim] backward tasks by list length (<=1,2,4,..,128):"); for (int a = 0; a < 8; ++a) fprintf(stderr, " %ld", sim_bwd_hist_n[a]);
 	fprintf(stderr, "\n[sim]   extensions spent there:"); for (int a = 0; a < 8; ++a) fprintf(stderr, " %ld", sim_bwd_ext_by_n[a]);
 	fprintf(stderr, "\n[sim]   tasks by extensions (<16,<32,..,>=1024):"); for (int a = 0; a < 8; ++a) fprintf(stderr, " %ld", sim_bwd_hist_ext[a]); fprintf(stderr, "; max %ld\n", sim_bwd_max_ext); } } sim_bwd_printer;
 #define ARX_STAT_BWD(n, ext) sim_stat_bwd((n), (ext))
-// ARX_RESCUE_FAST=0 switches dedup_insert() off; ARX_RESCUE_CHECK=1 runs the general path next to it on a copy and aborts on any difference
-static int sim_rescue_fast_f() { const char *e = getenv("ARX_RESCUE_FAST"); return e ? atoi(e) : 1; }
-static int sim_rescue_check_f() { const char *e = getenv("ARX_RESCUE_CHECK"); return e ? atoi(e) : 0; }
+// ARX_RESCUE_FAST=0 switches dedup_insert() off; ARX_RESCUE_CHECK=1 runs the general path next to it on a copy and aborts on any difference.
+// Both sit inside device functors, which see no runtime object: they are read where they are used, per insertion (the *_STATS above: at exit)
+static int sim_rescue_fast_f() { return arx::sw_int("ARX_RESCUE_FAST", 1); }
+static int sim_rescue_check_f() { return arx::sw_int("ARX_RESCUE_CHECK", 0); }
 #define ARX_RESCUE_FAST sim_rescue_fast_f()
 #define ARX_RESCUE_CROSSCHECK_BEGIN(ma, n, b) const int sim_rescue_check = sim_rescue_check_f(); std::vector<Reg> chk_(ma, ma + (n)); if (sim_rescue_check) { int at_ = 0; while (at_ < (n) && !(chk_[at_].score < (b).score)) ++at_; chk_.insert(chk_.begin() + at_, (b)); }
 #define ARX_RESCUE_CROSSCHECK_END(ix, ma, m) do { if ((m) >= 0) ++sim_rescue_fast_hits; else ++sim_rescue_fast_fallbacks; if (sim_rescue_check && (m) >= 0) { \
@@ -72,7 +74,7 @@ namespace arx {
 // (ARX_SIM_PFOR=1: descending, =2: a stride permutation -- a phase whose result depends on the lane order is a race on the GPU)
 constexpr int SMALL_LANES = 256, SMALL_SORT = 1024; // hip_block.h
 struct SimBlock {
-	int order = getenv("ARX_SIM_PFOR") ? atoi(getenv("ARX_SIM_PFOR")) : 0;
+	int order; // SimRT::sim_pfor
 	template <class F> void pfor(int n, F f)
 	{
 		if (order == 1) { for (int i = n - 1; i >= 0; --i) f(i); return; }
@@ -101,6 +103,9 @@ struct SimBlock {
 };
 struct KernelTimer { double ms = 0; int64_t calls = 0, items = 0; };
 struct SimRT {
+	// the double's own switches, read when the runtime is created like HipRT's (switches.h)
+	int sim_pfor = sw_int("ARX_SIM_PFOR", 0);
+	bool sim_rescue_heavy = sw_present("ARX_SIM_RESCUE_HEAVY"), sim_dedup_heavy = sw_present("ARX_SIM_DEDUP_HEAVY"), sim_chain_heavy = sw_present("ARX_SIM_CHAIN_HEAVY");
 	static const char *name() { return "hostsim"; }
 	static arx::BwtSaFn bwt_sa_fn() { return arx::build_bwt_sa_host; }
 	std::map<std::string, KernelTimer> tm;
@@ -111,11 +116,11 @@ struct SimRT {
 	template <class T> T *alloc(size_t n) { size_t b = (n ? n : 1) * sizeof(T); void *p = malloc(b); memset(p, 0xAB, b); return (T *)p; }
 	void free(void *p) { ::free(p); }
 	void seed_prepare(const uint8_t *, const int32_t *, const int32_t *, int) {}
-	bool rescue_heavy_ok() const { return getenv("ARX_SIM_RESCUE_HEAVY") != nullptr; } // the host double can run the split (same serial code on the flagged pairs)
+	bool rescue_heavy_ok() const { return sim_rescue_heavy; } // the host double can run the split (same serial code on the flagged pairs)
 	void aux_join() {}
-	bool dedup_heavy_ok() const { return getenv("ARX_SIM_DEDUP_HEAVY") != nullptr; }
+	bool dedup_heavy_ok() const { return sim_dedup_heavy; }
 	template <class F> void run_dedup_heavy(const char *nm, int, const F &f) { tm[nm].calls++; for (int i = 0; i < *f.n_heavy; ++i) f.one_thread(f.heavy_list[i], f.eh); }
-	bool chain_heavy_ok() const { return getenv("ARX_SIM_CHAIN_HEAVY") != nullptr; }
+	bool chain_heavy_ok() const { return sim_chain_heavy; }
 	template <class F> void run_chain_heavy(const char *nm, int, const F &f) { F g = f; g.heavy_list = nullptr; g.mid_list = nullptr; tm[nm].calls++; for (int i = 0; i < *f.n_heavy; ++i) g(f.heavy_list[i], 0); }
 	template <class F> void run_rescue_heavy(const char *nm, int n, const int32_t *list, const F &f) { F g = f; g.heavy = nullptr; tm[nm].calls++; for (int i = 0; i < n; ++i) g(list[i], 0); }
 	std::vector<uint8_t> stage_mem;
@@ -147,7 +152,7 @@ struct SimRT {
 	template <class F> void launch(const char *nm, int n, const F &f) { tm[nm].calls++; tm[nm].items += n; for (int i = 0; i < n; ++i) f(i, 0); }
 	template <class F> void launch_small(const char *nm, int n, const F &f) { launch(nm, n, f); }
 	template <class F> void launch_wide(const char *nm, int n, const F &f) { launch(nm, n, f); }
-	template <class F> void launch_block(const char *nm, int n, const F &f, const uint8_t * = nullptr) { tm[nm].calls++; tm[nm].items += n; SimBlock blk; for (int i = 0; i < n; ++i) f(i, blk); }
+	template <class F> void launch_block(const char *nm, int n, const F &f, const uint8_t * = nullptr) { tm[nm].calls++; tm[nm].items += n; SimBlock blk{sim_pfor}; for (int i = 0; i < n; ++i) f(i, blk); }
 	template <class F> void launch_cold(const char *nm, int n, const F &f) { launch(nm, n, f); }
 	void merge_sort_fail(uint32_t *err) { if (g_arx_sort_fail) *err |= ERR_INTERNAL; }
 	template <class F> void run_sw_u8(const char *nm, int n, const F &f, int max_len) { launch_rows(nm, n, f, 16 * ((max_len + 15) / 16)); }

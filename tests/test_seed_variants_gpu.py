@@ -12,7 +12,8 @@ the row-parallel kernel's four bins, the tasks flagged for k_seed_bwd_wave and f
 device memory after a launch anyway -- and each variant's counts are checked against the restatement's for the same input
 (seedcheck.Expected.census / handed_bounds).
 
-Knobs are read when a context (index knobs) or a batch (all others) is created, so the environment is set before that.  Values the code does
+Knobs are read when a context (index knobs) or a batch (all others) is created and at no other time (arachne_amd/csrc/switches.h; DESIGN.md
+section 13 is the table of every switch with its read time), so the environment is set before that.  Values the code does
 not support are left out: ARX_SEED_BWD_MID takes 16 .. 21 (the 21-lane body holds no longer row), ARX_SEED_BATCH is kept in 8 bits with 0 meaning
 the default, ARX_SEED_GRANT 0 means 64.
 """
