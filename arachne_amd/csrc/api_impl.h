@@ -201,6 +201,16 @@ template <class RT> struct Context {
 	~Context() { for (void *p : dev_index) rt.pfree(p); }
 };
 
+// what arx_batch_create and arx_batch_reset accept as reads: ARX_OK, or the error code with its text in *msg
+inline int check_reads(int32_t n_reads, const int32_t *lens, const char **msg)
+{
+	if (n_reads <= 0 || (n_reads & 1)) { *msg = "n_reads must be positive and even (read 2i/2i+1 are mates)"; return ARX_E_ARG; }
+	int64_t tot = 0;
+	for (int i = 0; i < n_reads; ++i) { if (lens[i] < 0 || lens[i] > MAX_READ_LEN) { *msg = "read length outside [0, 255]"; return ARX_E_ARG; } tot += lens[i]; }
+	if (tot >= ((int64_t)1 << 31) - 64) { *msg = "batch too large: more than 2^31 bases, split the batch"; return ARX_E_TOO_LARGE; }
+	return ARX_OK;
+}
+
 template <class RT> struct Batch {
 	Context<RT> *ctx;
 	RT rt;                      // this batch's stream
@@ -208,12 +218,52 @@ template <class RT> struct Batch {
 	typename Pipeline<RT>::DeviceBatch db;
 	typename Pipeline<RT>::Work work;
 	BatchResult res;
-	int done_stage = 0;
 	std::vector<int32_t> lens_host;
-	RfaResult rfa;
-	PostResult post; std::vector<size_t> post_mark;
-	TagsResult tags;            // arx_batch_tags: allocated behind arx_batch_post's memory, so a later arx_batch_post discards it
-	std::vector<size_t> rfa_mark; bool rfa_marked = false; // arena state after ARX_STAGE_ALN: a repeated arx_batch_rfa reuses the same memory
+	RfaResult rfa; PostResult post; TagsResult tags;
+	// The lifetime of the batch's work memory.  The stages (arx_batch_run) allocate from the start of the arena; the phases that follow them
+	// come in this order, each behind the memory of the one before, and a phase that was skipped (tags without post) is empty:
+	enum Phase { PH_PLACE, PH_POST, PH_TAGS, N_PHASES }; // arx_batch_rfa, arx_batch_post, arx_batch_tags
+	int done_stage = 0;                       // last stage run
+	std::vector<size_t> begin[N_PHASES]; int n_begun = 0; // arena marks: where the memory of phases [0, n_begun) begins
+	bool done[N_PHASES] = {false, false, false}; // the phase's results are there (done[p] only if p < n_begun)
+	bool aligned() const { return done_stage >= ARX_STAGE_ALN; }
+	// Entering a phase hands back its own memory of an earlier call and that of every later phase, and with it their results
+	void enter(Phase p)
+	{
+		if (p < n_begun) rt.arena_rewind(begin[p]); else while (n_begun <= p) begin[n_begun++] = rt.arena_mark();
+		n_begun = p + 1;
+		for (int q = p; q < N_PHASES; ++q) done[q] = false;
+	}
+	void drop_phases() { n_begun = 0; for (bool &d : done) d = false; }
+	// arx_batch_reset*, or a stage asked for again: all work memory back, nothing computed
+	void restart() { pipe.free_work(work); res = BatchResult(); done_stage = 0; drop_phases(); }
+	// arx_batch_run: ARX_OK or the error code, its text set in the context
+	int run_to(int32_t last_stage)
+	{
+		rt.set_timing(ctx->timing);
+		// stages already done are kept (run(SEED) then run(ALN) resumes); asking for a stage again restarts the batch
+		if (last_stage <= done_stage) restart(); else drop_phases();
+		if (done_stage < ARX_STAGE_SEED) {
+			if (pipe.stage_seed(db, work) == -2) { ctx->set_error("batch too large: seed occurrences exceed 2^30, split the batch"); return ARX_E_TOO_LARGE; }
+			res.n_occ = work.T;
+		}
+		if (done_stage < ARX_STAGE_CHAIN && last_stage >= ARX_STAGE_CHAIN) pipe.stage_chain(db, work);
+		if (done_stage < ARX_STAGE_EXTEND && last_stage >= ARX_STAGE_EXTEND) pipe.stage_extend(db, work, res);
+		if (done_stage < ARX_STAGE_RESCUE && last_stage >= ARX_STAGE_RESCUE) pipe.stage_rescue(db, work, res);
+		const uint32_t e = last_stage >= ARX_STAGE_ALN ? (uint32_t)pipe.stage_reg2aln(db, work) : pipe.read_err(work);
+		done_stage = last_stage;
+		rt.sync();
+		if (e) { ctx->set_error("device stage raised error bits " + std::to_string(e)); return ARX_E_DEVICE; }
+		return ARX_OK;
+	}
+	void place(int n_barcodes, const int64_t *bc_pair_off, const uint8_t *do_rfa, int32_t penalty, const int64_t *cen_start, const int64_t *cen_end)
+	{
+		rt.set_timing(ctx->timing); enter(PH_PLACE);
+		RfaStage<RT>::run(pipe, db, work, n_barcodes, bc_pair_off, do_rfa, penalty, cen_start, cen_end, lens_host.data(), rfa);
+		done[PH_PLACE] = true;
+	}
+	void run_post() { rt.set_timing(ctx->timing); enter(PH_POST); PostStage<RT>::run(pipe, db, work, rfa, post); rt.sync(); done[PH_POST] = true; }
+	void run_tags() { rt.set_timing(ctx->timing); enter(PH_TAGS); TagsStage<RT>::run(pipe, db, rfa, tags); rt.sync(); done[PH_TAGS] = true; }
 	// arx_batch_detach: the dense results copied aside (device memory of their own, outside the work arena) so that the handle can take its
 	// next reads while a second host thread takes them home through a stream of its own (arx_batch_fetch_detached)
 	struct Detached {
@@ -310,23 +360,18 @@ template <class RT> struct Batch {
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h;                                                                                                          \
 		*out = 0;                                                                                                                   \
-		if (n_reads <= 0 || (n_reads & 1)) { c->set_error("n_reads must be positive and even (read 2i/2i+1 are mates)"); return ARX_E_ARG; } \
-		{ int64_t tot = 0;                                                                                                          \
-		  for (int i = 0; i < n_reads; ++i) { if (lens[i] < 0 || lens[i] > arx::MAX_READ_LEN) { c->set_error("read length outside [0, 255]"); return ARX_E_ARG; } tot += lens[i]; } \
-		  if (tot >= ((int64_t)1 << 31) - 64) { c->set_error("batch too large: more than 2^31 bases, split the batch"); return ARX_E_TOO_LARGE; } } \
+		const char *bad = 0;                                                                                                        \
+		if (int rc = arx::check_reads(n_reads, lens, &bad)) { c->set_error(bad); return rc; }                                       \
 		ARX_TRY(c, Bat *b = new Bat(c); b->rt.bind(); b->db = b->pipe.upload(bases, lens, n_reads); b->lens_host.assign(lens, lens + n_reads); *out = (arx_batch *)b;) \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_reset(arx_ctx *h, arx_batch *bh, int32_t n_reads, const uint8_t *bases, const int32_t *lens)                      \
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
-		if (n_reads <= 0 || (n_reads & 1)) { c->set_error("n_reads must be positive and even (read 2i/2i+1 are mates)"); return ARX_E_ARG; } \
-		{ int64_t tot = 0;                                                                                                          \
-		  for (int i = 0; i < n_reads; ++i) { if (lens[i] < 0 || lens[i] > arx::MAX_READ_LEN) { c->set_error("read length outside [0, 255]"); return ARX_E_ARG; } tot += lens[i]; } \
-		  if (tot >= ((int64_t)1 << 31) - 64) { c->set_error("batch too large: more than 2^31 bases, split the batch"); return ARX_E_TOO_LARGE; } } \
+		const char *bad = 0;                                                                                                        \
+		if (int rc = arx::check_reads(n_reads, lens, &bad)) { c->set_error(bad); return rc; }                                       \
 		ARX_TRY(c, b->rt.bind();                                                                                                    \
-			b->pipe.free_work(b->work); b->res = arx::BatchResult(); b->done_stage = 0; b->rfa_marked = false;                      \
-			b->rfa = arx::RfaResult(); b->post = arx::PostResult(); b->tags = arx::TagsResult();                                                                 \
+			b->restart();                                                                                                           \
 			b->pipe.upload_into(b->db, bases, lens, n_reads); b->lens_host.assign(lens, lens + n_reads);)                           \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
@@ -337,8 +382,7 @@ template <class RT> struct Batch {
 		if (n_bases < 0 || n_bases >= ((int64_t)1 << 31) - 64) { c->set_error("batch too large: more than 2^31 bases, split the batch"); return ARX_E_TOO_LARGE; } \
 		bool ok = false;                                                                                                            \
 		ARX_TRY(c, b->rt.bind();                                                                                                    \
-			b->pipe.free_work(b->work); b->res = arx::BatchResult(); b->done_stage = 0; b->rfa_marked = false;                      \
-			b->rfa = arx::RfaResult(); b->post = arx::PostResult(); b->tags = arx::TagsResult();                                                                 \
+			b->restart();                                                                                                           \
 			ok = b->pipe.upload_from_device(b->db, d_bases, d_lens, n_reads, n_bases, 0, b->lens_host);)                            \
 		if (!ok) { c->set_error("device batch: the read lengths do not add up to n_bases, or a length is outside [0, 255]"); return ARX_E_ARG; } \
 		return ARX_OK;                                                                                                              \
@@ -346,21 +390,21 @@ template <class RT> struct Batch {
 	int arx_batch_device_view(arx_ctx *h, arx_batch *bh, arx_device_view *v)                                                        \
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
-		if (!b->work.alns) { c->set_error("arx_batch_device_view before arx_batch_run(ARX_STAGE_ALN)"); return ARX_E_ARG; }         \
+		if (!b->aligned()) { c->set_error("arx_batch_device_view before arx_batch_run(ARX_STAGE_ALN)"); return ARX_E_ARG; }         \
 		ARX_TRY(c, b->rt.bind(); b->rt.sync();)                                                                                     \
 		v->n_reads = b->db.n_reads; v->n_regs = b->work.c_n_regs; v->n_cigar = b->work.c_n_cig;                                     \
 		v->reg_off = b->work.c_reg_off; v->regs = (const arx_reg *)b->work.c_regs; v->alns = (const arx_aln *)b->work.c_alns; v->cigars = b->work.c_cig; \
-		const bool placed = b->rfa_marked && !b->rfa.cand_off.empty();                                                              \
+		const bool placed = b->done[Bat::PH_PLACE];                                                                                 \
 		v->n_cands = placed ? b->rfa.n_cands : 0; v->cand_off = placed ? b->rfa.d_cand_off : nullptr; v->cands = placed ? (const arx_cand *)b->rfa.d_cands : nullptr; \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_detach(arx_ctx *h, arx_batch *bh, int64_t *sizes)                                                                 \
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
-		if (!b->work.alns) { c->set_error("arx_batch_detach before arx_batch_run(ARX_STAGE_ALN)"); return ARX_E_ARG; }              \
+		if (!b->aligned()) { c->set_error("arx_batch_detach before arx_batch_run(ARX_STAGE_ALN)"); return ARX_E_ARG; }              \
 		ARX_TRY(c, b->rt.bind();                                                                                                    \
 			auto &d = b->det; d.valid = false;                                                                                      \
-			const bool placed = b->rfa_marked && !b->rfa.cand_off.empty();                                                          \
+			const bool placed = b->done[Bat::PH_PLACE];                                                                             \
 			d.n_reads = b->db.n_reads; d.n_regs = b->work.c_n_regs; d.n_cig = b->work.c_n_cig; d.n_cands = placed ? b->rfa.n_cands : 0; \
 			auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };                                                            \
 			size_t at = 0;                                                                                                          \
@@ -401,25 +445,7 @@ template <class RT> struct Batch {
 	int arx_batch_run(arx_ctx *h, arx_batch *bh, int32_t last_stage)                                                                \
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
-		ARX_TRY(c,                                                                                                                  \
-			b->rt.bind();                                                                                                           \
-			b->rt.set_timing(c->timing);                                                                                            \
-			/* stages already done are kept (run(SEED) then run(ALN) resumes); asking for a stage again restarts the batch */       \
-			if (last_stage <= b->done_stage) { b->pipe.free_work(b->work); b->res = arx::BatchResult(); b->done_stage = 0; }        \
-			b->rfa_marked = false; b->post = arx::PostResult(); b->tags = arx::TagsResult();                                                                          \
-			if (b->done_stage < ARX_STAGE_SEED) {                                                                                   \
-				int rc = b->pipe.stage_seed(b->db, b->work);                                                                        \
-				if (rc == -2) { c->set_error("batch too large: seed occurrences exceed 2^30, split the batch"); return ARX_E_TOO_LARGE; } \
-				b->res.n_occ = b->work.T;                                                                                           \
-			}                                                                                                                       \
-			if (b->done_stage < ARX_STAGE_CHAIN && last_stage >= ARX_STAGE_CHAIN) b->pipe.stage_chain(b->db, b->work);              \
-			if (b->done_stage < ARX_STAGE_EXTEND && last_stage >= ARX_STAGE_EXTEND) b->pipe.stage_extend(b->db, b->work, b->res);   \
-			if (b->done_stage < ARX_STAGE_RESCUE && last_stage >= ARX_STAGE_RESCUE) b->pipe.stage_rescue(b->db, b->work, b->res);   \
-			uint32_t e = last_stage >= ARX_STAGE_ALN ? (uint32_t)b->pipe.stage_reg2aln(b->db, b->work) : b->pipe.read_err(b->work); \
-			b->done_stage = last_stage;                                                                                             \
-			b->rt.sync();                                                                                                           \
-			if (e) { c->set_error("device stage raised error bits " + std::to_string(e)); return ARX_E_DEVICE; }                    \
-		)                                                                                                                           \
+		ARX_TRY(c, b->rt.bind(); if (int rc = b->run_to(last_stage)) return rc;)                                                    \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_counts(arx_ctx *h, arx_batch *bh, int64_t *c8)                                                                    \
@@ -435,7 +461,7 @@ template <class RT> struct Batch {
 	int arx_batch_fetch(arx_ctx *h, arx_batch *bh, int32_t *reg_off, arx_reg *regs, arx_aln *alns, uint32_t *cigars)                \
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
-		if (!b->work.alns) { c->set_error("arx_batch_fetch before arx_batch_run(ARX_STAGE_ALN)"); return ARX_E_ARG; }               \
+		if (!b->aligned()) { c->set_error("arx_batch_fetch before arx_batch_run(ARX_STAGE_ALN)"); return ARX_E_ARG; }               \
 		static_assert(sizeof(arx_reg) == sizeof(arx::Reg) && sizeof(arx_aln) == sizeof(arx::Aln), "C-ABI structs must mirror the device structs"); \
 		ARX_TRY(c, b->rt.bind(); b->pipe.fetch(b->db, b->work, reg_off, (arx::Reg *)regs, (arx::Aln *)alns, cigars);)                \
 		return ARX_OK;                                                                                                              \
@@ -450,59 +476,46 @@ template <class RT> struct Batch {
 			return ARX_E_ARG;                                                                                                       \
 		}                                                                                                                           \
 		const int32_t penalty = (int32_t)penalty_f;                                                                                 \
-		if (!b->work.alns) { c->set_error("arx_batch_rfa before arx_batch_run(ARX_STAGE_ALN)"); return ARX_E_ARG; }                 \
+		if (!b->aligned()) { c->set_error("arx_batch_rfa before arx_batch_run(ARX_STAGE_ALN)"); return ARX_E_ARG; }                 \
 		if (n_barcodes <= 0 || bc_pair_off[0] != 0 || 2 * bc_pair_off[n_barcodes] != b->db.n_reads) { c->set_error("barcode offsets must cover the batch"); return ARX_E_ARG; } \
 		for (int i = 0; i < n_barcodes; ++i) if (bc_pair_off[i + 1] < bc_pair_off[i]) { c->set_error("barcode offsets must not decrease"); return ARX_E_ARG; } \
-		ARX_TRY(c, b->rt.bind(); b->rt.set_timing(c->timing);                                                                       \
-			if (b->rfa_marked) b->rt.arena_rewind(b->rfa_mark); else { b->rfa_mark = b->rt.arena_mark(); b->rfa_marked = true; }    \
-			arx::RfaStage<RT>::run(b->pipe, b->db, b->work, n_barcodes, bc_pair_off, do_rfa, penalty, cen_start, cen_end, b->lens_host.data(), b->rfa); \
-			b->post = arx::PostResult(); b->tags = arx::TagsResult(); b->post_mark = b->rt.arena_mark();                                                         \
-			*n_cands = b->rfa.n_cands;)                                                                               \
+		ARX_TRY(c, b->rt.bind(); b->place(n_barcodes, bc_pair_off, do_rfa, penalty, cen_start, cen_end); *n_cands = b->rfa.n_cands;) \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_post(arx_ctx *h, arx_batch *bh, int64_t *n_mm)                                                                    \
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
-		if (b->rfa.cand_off.empty() || !b->rfa_marked) { c->set_error("arx_batch_post before arx_batch_rfa"); return ARX_E_ARG; }   \
+		if (!b->done[Bat::PH_PLACE]) { c->set_error("arx_batch_post before arx_batch_rfa"); return ARX_E_ARG; }                     \
 		static_assert(sizeof(arx_cand_post) == sizeof(arx::CandPost) && sizeof(arx_split) == sizeof(arx::SplitRec), "C-ABI structs must mirror the device structs"); \
-		ARX_TRY(c, b->rt.bind(); b->rt.set_timing(c->timing);                                                                       \
-			b->rt.arena_rewind(b->post_mark);                                                                                       \
-			b->tags = arx::TagsResult();                                                                                            \
-			arx::PostStage<RT>::run(b->pipe, b->db, b->work, b->rfa, b->post);                                                      \
-			b->rt.sync();                                                                                                           \
-			*n_mm = b->post.n_mm;)                                                                                                  \
+		ARX_TRY(c, b->rt.bind(); b->run_post(); *n_mm = b->post.n_mm;)                                                              \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_post_fetch(arx_ctx *h, arx_batch *bh, arx_cand_post *post, arx_split *split, int32_t *mm_ref, int32_t *mm_read)   \
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
-		if (!b->post.done || !b->rfa_marked) { c->set_error("arx_batch_post_fetch before arx_batch_post"); return ARX_E_ARG; }      \
+		if (!b->done[Bat::PH_POST]) { c->set_error("arx_batch_post_fetch before arx_batch_post"); return ARX_E_ARG; }               \
 		ARX_TRY(c, b->rt.bind(); arx::PostStage<RT>::fetch(b->pipe, b->db, b->rfa, b->post, (arx::CandPost *)post, (arx::SplitRec *)split, mm_ref, mm_read);) \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_tags(arx_ctx *h, arx_batch *bh)                                                                                   \
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
-		if (b->rfa.cand_off.empty() || !b->rfa_marked) { c->set_error("arx_batch_tags before arx_batch_rfa"); return ARX_E_ARG; }   \
+		if (!b->done[Bat::PH_PLACE]) { c->set_error("arx_batch_tags before arx_batch_rfa"); return ARX_E_ARG; }                     \
 		static_assert(sizeof(arx_read_tags) == sizeof(arx::ReadTags), "C-ABI structs must mirror the device structs");             \
-		ARX_TRY(c, b->rt.bind(); b->rt.set_timing(c->timing);                                                                       \
-			if (b->tags.marked) b->rt.arena_rewind(b->tags.mark); else { b->tags.mark = b->rt.arena_mark(); b->tags.marked = true; } \
-			b->tags.done = false;                                                                                                   \
-			arx::TagsStage<RT>::run(b->pipe, b->db, b->rfa, b->tags);                                                               \
-			b->rt.sync();)                                                                                                          \
+		ARX_TRY(c, b->rt.bind(); b->run_tags();)                                                                                    \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_tags_fetch(arx_ctx *h, arx_batch *bh, arx_read_tags *out)                                                         \
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
-		if (!b->tags.done || !b->rfa_marked) { c->set_error("arx_batch_tags_fetch before arx_batch_tags (or after a later arx_batch_rfa / arx_batch_post)"); return ARX_E_ARG; } \
+		if (!b->done[Bat::PH_TAGS]) { c->set_error("arx_batch_tags_fetch before arx_batch_tags (or after a later arx_batch_rfa / arx_batch_post)"); return ARX_E_ARG; } \
 		ARX_TRY(c, b->rt.bind(); arx::TagsStage<RT>::fetch(b->pipe, b->db, b->tags, (arx::ReadTags *)out);)                         \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_rfa_fetch(arx_ctx *h, arx_batch *bh, int32_t *cand_off, arx_cand *cands)                                          \
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
-		if (b->rfa.cand_off.empty() || !b->rfa_marked) { c->set_error("arx_batch_rfa_fetch before arx_batch_rfa"); return ARX_E_ARG; } \
+		if (!b->done[Bat::PH_PLACE]) { c->set_error("arx_batch_rfa_fetch before arx_batch_rfa"); return ARX_E_ARG; }                \
 		static_assert(sizeof(arx_cand) == sizeof(arx::Cand), "C-ABI structs must mirror the device structs");                       \
 		ARX_TRY(c, b->rt.bind(); arx::RfaStage<RT>::fetch(b->pipe, b->db, b->rfa, cand_off, (arx::Cand *)cands);)                    \
 		return ARX_OK;                                                                                                              \

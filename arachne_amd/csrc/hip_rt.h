@@ -89,8 +89,8 @@ struct HipRT {
 		if (hipGetDeviceProperties(&p, device) != hipSuccess) return "hipGetDeviceProperties failed";
 		n_cu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
 		if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return "hipStreamCreate failed";
-		(void)hipMalloc(&d_total, 8);
-		(void)hipHostMalloc(&pinned, 64, hipHostMallocDefault);
+		if (hipMalloc(&d_total, 8) != hipSuccess) return "hipMalloc failed";
+		if (hipHostMalloc(&pinned, 64, hipHostMallocDefault) != hipSuccess) return "hipHostMalloc failed";
 		return "";
 	}
 	~HipRT()
@@ -99,6 +99,7 @@ struct HipRT {
 		for (auto &sl : slabs) (void)hipFree(sl.p);
 		if (scan_tmp) hipFree(scan_tmp);
 		if (d_total) hipFree(d_total);
+		if (seed_dbg_buf) (void)hipFree(seed_dbg_buf);
 		if (pinned) (void)hipHostFree(pinned);
 		if (stage_buf) (void)hipHostFree(stage_buf);
 		for (auto &p : pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -106,9 +107,9 @@ struct HipRT {
 		if (aux) { hipStreamDestroy(aux); hipEventDestroy(ev_fork); hipEventDestroy(ev_join); }
 		if (stream) hipStreamDestroy(stream);
 	}
-	// Work memory of a batch comes from a per-runtime arena: slabs obtained once with hipMalloc, bump-allocated, reset as
-	// a whole when the batch is re-run.  Steady state therefore has no hipMalloc/hipFree at all -- both synchronise the
-	// device and would serialise the batches that run on other streams.
+	// Work memory of a batch comes from a per-runtime arena: slabs obtained once with hipMalloc, bump-allocated, handed back
+	// only by rewinding to a mark or resetting the whole (there is no free of a single block).  Steady state therefore has
+	// no hipMalloc/hipFree at all -- both synchronise the device and would serialise the batches that run on other streams.
 	struct Slab { char *p; size_t cap, used; };
 	std::vector<Slab> slabs;
 	template <class T> T *alloc(size_t n)
@@ -120,7 +121,6 @@ struct HipRT {
 		slabs.push_back(sl);
 		return (T *)sl.p;
 	}
-	void free(void *) {}                       // arena memory is released by arena_reset()
 	void arena_reset() { for (auto &sl : slabs) sl.used = 0; }
 	std::vector<size_t> arena_mark() const { std::vector<size_t> m; for (auto &sl : slabs) m.push_back(sl.used); return m; }
 	void arena_rewind(const std::vector<size_t> &m) { for (size_t i = 0; i < slabs.size(); ++i) slabs[i].used = i < m.size() ? m[i] : 0; }

@@ -596,24 +596,17 @@ public:
 
 	// everything that stays on the device between the stages of one batch
 	struct Work {
-		Biv *intv = 0, *smem_scr = 0; int32_t *n_intv = 0, *n_occ = 0, *occ_off = 0; Seed *occ_seed = 0; int32_t *occ_rid = 0, *core_clean = 0;
-		int32_t *next = 0, *iscr = 0, *n_chain = 0, *srt = 0, *idx = 0, *n_core = 0; Chain *ctmp = 0, *cout = 0; BtNode *nodes = 0; Seed *sout = 0;
-		Reg *regs = 0, *rtmp = 0; ExtState *est = 0; ExtTask *etask = 0; ExtRes *eres = 0; int32_t *counter = 0; uint32_t *err = 0;
-		int32_t *eh = 0; int32_t *cap = 0, *preg_off = 0, *n_regs = 0, *pidx = 0; Reg *pregs = 0, *ptmp = 0; ResState *rst = 0; SwTask *stask = 0; U8Res *sres = 0;
-		uint8_t *sw_scr = 0, *z = 0; Aln *alns = 0; uint32_t *cig = 0; int32_t *nw_list = 0;
+		Biv *intv = 0; int32_t *n_intv = 0, *n_occ = 0, *occ_off = 0; Seed *occ_seed = 0; int32_t *occ_rid = 0;  // seeding and locate
+		int32_t *n_chain = 0; Chain *cout = 0; Seed *sout = 0;                                                   // chaining
+		Reg *regs = 0; int32_t *n_core = 0, *core_clean = 0;                                                     // extension
+		int32_t *preg_off = 0, *n_regs = 0; Reg *pregs = 0;                                                      // rescue
+		Aln *alns = 0; uint32_t *cig = 0; int32_t *counter = 0; uint32_t *err = 0;                               // CIGARs; a counter and the error word for all
 		int32_t *c_reg_off = 0; Reg *c_regs = 0; Aln *c_alns = 0; uint32_t *c_cig = 0; int64_t c_n_regs = 0, c_n_cig = 0; // dense results
 		int64_t T = 0, P = 0; int cig_w = 0;
 	};
 
-	void free_work(Work &w)
-	{
-		void *ptrs[] = { w.intv, w.smem_scr, w.n_intv, w.n_occ, w.occ_off, w.occ_seed, w.occ_rid, w.next, w.iscr, w.n_chain, w.srt, w.idx, w.n_core, w.ctmp, w.cout,
-		                 w.nodes, w.sout, w.regs, w.rtmp, w.est, w.etask, w.eres, w.counter, w.err, w.eh, w.cap, w.preg_off, w.n_regs, w.pidx, w.pregs,
-		                 w.ptmp, w.rst, w.stask, w.sres, w.sw_scr, w.z, w.alns, w.cig, w.nw_list };
-		for (void *p : ptrs) if (p) rt.free(p);
-		rt.arena_reset();
-		w = Work();
-	}
+	// all of a batch's work memory goes back to the arena at once; a part of it only by arena_rewind() to a mark
+	void free_work(Work &w) { rt.arena_reset(); w = Work(); }
 
 	uint32_t read_err(Work &w) { uint32_t e = 0; rt.d2h(&e, w.err, 4); return e; }
 	int32_t read_counter(Work &w) { int32_t c = 0; rt.d2h(&c, w.counter, 4); return c; }
@@ -633,7 +626,7 @@ public:
 		// 1 M-pair batches in flight fit beside the index and the k-mer table (round 3).
 		const auto seed_mark = rt.arena_mark();
 		rt.seed_prepare(b.bases, b.base_off, b.lens, R);
-		w.smem_scr = rt.template alloc<Biv>((size_t)slots * list_cap);
+		Biv *smem_scr = rt.template alloc<Biv>((size_t)slots * list_cap);
 		Biv *strat = rt.template alloc<Biv>((size_t)R * CAP_STRAT);
 		int32_t *n_strat = rt.template alloc<int32_t>(R + 1);
 		// first two passes: forward chains -> backward tasks -> gather + re-seeding tasks -> their forward and backward halves -> gather,
@@ -655,7 +648,7 @@ public:
 			const int Rg = R - g0 < GR ? R - g0 : GR;
 			int32_t cur[2];
 			rt.memset0(P.cursors, 8);
-			KSeedFwd1 kf{ix, b.bases, b.base_off, b.lens, P, w.smem_scr, list_cap, first1, g0};
+			KSeedFwd1 kf{ix, b.bases, b.base_off, b.lens, P, smem_scr, list_cap, first1, g0};
 			rt.run_seed_fwd1("seed_fwd", Rg, kf, w.counter);
 			rt.d2h(cur, P.cursors, 8);
 			const int n1 = cur[1] < P.task_cap ? cur[1] : P.task_cap;
@@ -679,7 +672,7 @@ public:
 			rt.launch_wide("seed_gather", Rg, kg1);
 			rt.d2h(cur, P.cursors, 8);
 			const int n2 = cur[1] < P.task_cap ? cur[1] : P.task_cap;
-			KSeedFwd2 kf2{ix, b.bases, b.base_off, b.lens, P, w.smem_scr, list_cap, n1};
+			KSeedFwd2 kf2{ix, b.bases, b.base_off, b.lens, P, smem_scr, list_cap, n1};
 			rt.run_seed_fwd2("seed_fwd", n2 - n1, kf2, w.counter);
 			kb.t0 = n1;
 			rt.run_seed_bwd("seed_bwd", n2 - n1, kb, w.counter);
@@ -691,7 +684,7 @@ public:
 		KSeedMerge km{w.intv, w.n_intv, strat, n_strat, w.n_occ, w.err};
 		rt.launch_wide("seed_merge", R, km);
 		int64_t total = rt.exclusive_scan(w.n_occ, w.occ_off, R); // (waits for the stream: the seeding kernels are through)
-		rt.arena_rewind(seed_mark); // HipRT: the seeding passes' memory goes back to the arena (w.smem_scr dangles from here on: nothing reads it); the test double keeps it
+		rt.arena_rewind(seed_mark); // the seeding passes' memory goes back to the arena on both runtimes (the test double poisons and frees it: a later read shows under a sanitizer)
 		if (total >= (int64_t)1 << 30) return -2; // keep 32-bit pool indices; the caller splits the batch
 		w.T = total;
 		w.occ_seed = rt.template alloc<Seed>(w.T + 1); w.occ_rid = rt.template alloc<int32_t>(w.T + 1);
@@ -710,10 +703,10 @@ public:
 	void stage_chain(const DeviceBatch &b, Work &w)
 	{
 		const int R = b.n_reads; const size_t T = (size_t)w.T + 1;
-		w.next = rt.template alloc<int32_t>(T); w.ctmp = rt.template alloc<Chain>(T); w.cout = rt.template alloc<Chain>(T);
-		w.nodes = rt.template alloc<BtNode>(T / 3 + 4 * (size_t)R + 8); w.iscr = rt.template alloc<int32_t>(7 * T + 8); w.sout = rt.template alloc<Seed>(T);
+		int32_t *next = rt.template alloc<int32_t>(T); Chain *ctmp = rt.template alloc<Chain>(T); w.cout = rt.template alloc<Chain>(T);
+		BtNode *nodes = rt.template alloc<BtNode>(T / 3 + 4 * (size_t)R + 8); int32_t *iscr = rt.template alloc<int32_t>(7 * T + 8); w.sout = rt.template alloc<Seed>(T);
 		w.n_chain = rt.template alloc<int32_t>(R + 1);
-		KChain k{ix, b.lens, w.intv, w.n_intv, w.occ_off, w.occ_seed, w.occ_rid, w.next, w.ctmp, w.nodes, w.iscr, w.cout, w.sout, w.n_chain, w.err, nullptr, nullptr,
+		KChain k{ix, b.lens, w.intv, w.n_intv, w.occ_off, w.occ_seed, w.occ_rid, next, ctmp, nodes, iscr, w.cout, w.sout, w.n_chain, w.err, nullptr, nullptr,
 		         sw.chain_heavy_min.value_or(CHAIN_HEAVY_MIN)};
 		if (rt.chain_heavy_ok()) { k.heavy_list = rt.template alloc<int32_t>(R + 4); k.n_heavy = k.heavy_list + R; rt.memset0(k.n_heavy, 16); }
 		if constexpr (HasChainGroup<RT>::value) {
@@ -739,26 +732,26 @@ public:
 	void stage_extend(const DeviceBatch &b, Work &w, BatchResult &out)
 	{
 		const int R = b.n_reads; const size_t T = (size_t)w.T + 1; const int slots = rt.max_slots();
-		w.srt = rt.template alloc<int32_t>(T); w.regs = rt.template alloc<Reg>(T); w.rtmp = rt.template alloc<Reg>(T); w.idx = rt.template alloc<int32_t>(T);
+		int32_t *srt = rt.template alloc<int32_t>(T); w.regs = rt.template alloc<Reg>(T); Reg *rtmp = rt.template alloc<Reg>(T); int32_t *idx = rt.template alloc<int32_t>(T);
 		w.n_core = rt.template alloc<int32_t>(R + 1); w.core_clean = rt.template alloc<int32_t>(R + 1);
 		const int eh_words = 2 * (b.max_len + 2);
-		w.eh = rt.template alloc<int32_t>((size_t)slots * eh_words);
+		int32_t *eh = rt.template alloc<int32_t>((size_t)slots * eh_words);
 		// one state machine per chain (dev_regs.h): chain gids by a scan of the per-read chain counts
 		int32_t *chain_off = rt.template alloc<int32_t>(R + 2);
 		const int NCH = (int)rt.exclusive_scan(w.n_chain, chain_off, R);
-		w.est = rt.template alloc<ExtState>((size_t)NCH + 1); w.eres = rt.template alloc<ExtRes>((size_t)NCH + 1);
-		w.etask = rt.template alloc<ExtTask>((size_t)EXT_CLASSES * (NCH + 1));
+		ExtState *est = rt.template alloc<ExtState>((size_t)NCH + 1); ExtRes *eres = rt.template alloc<ExtRes>((size_t)NCH + 1);
+		ExtTask *etask = rt.template alloc<ExtTask>((size_t)EXT_CLASSES * (NCH + 1));
 		int32_t *chain_read = rt.template alloc<int32_t>((size_t)NCH + 1);
 		int32_t *act[2] = { rt.template alloc<int32_t>((size_t)NCH + 1), rt.template alloc<int32_t>((size_t)NCH + 1) };
 		int32_t *ecnt = rt.template alloc<int32_t>(EXT_CLASSES + 1);
 		int32_t *n_ext = rt.template alloc<int32_t>(R + 1);
-		Reg *pool = w.rtmp; // the chains' regions while they are extended; gathered into w.regs in chain order afterwards
-		KExtInit ki{ix, b.lens, w.occ_off, w.n_chain, chain_off, w.cout, w.sout, w.srt, w.est, chain_read};
+		Reg *pool = rtmp; // the chains' regions while they are extended; gathered into w.regs in chain order afterwards
+		KExtInit ki{ix, b.lens, w.occ_off, w.n_chain, chain_off, w.cout, w.sout, srt, est, chain_read};
 		rt.launch_wide("ext_init", R, ki);
 		int n_act = NCH;
 		for (int round = 2; n_act > 0; ++round) {
 			rt.memset0(ecnt, 4 * (EXT_CLASSES + 1));
-			KExtStep ks{ix, b.base_off, b.lens, w.occ_off, chain_off, chain_read, w.cout, w.sout, w.srt, pool, w.est, w.eres, w.etask, ecnt, round,
+			KExtStep ks{ix, b.base_off, b.lens, w.occ_off, chain_off, chain_read, w.cout, w.sout, srt, pool, est, eres, etask, ecnt, round,
 			            NCH + 1, round == 2 ? nullptr : act[round & 1], act[(round + 1) & 1]};
 			rt.launch_wide("ext_step", n_act, ks);
 			int32_t cnt[EXT_CLASSES + 1];
@@ -770,13 +763,13 @@ public:
 			if (round > w.T + R + 8) { uint32_t e = ERR_INTERNAL; rt.h2d(w.err, &e, 4); break; } // cannot happen: every round retires a DP or a chain
 			if (nt == 0) continue;
 			out.n_ext_tasks += nt; ++out.ext_rounds;
-			KExtend ke{ix, b.bases, w.etask, w.eres};
+			KExtend ke{ix, b.bases, etask, eres};
 			rt.run_extend("extend", cnt, NCH + 1, ke);
 		}
-		KExtGather kg{w.occ_off, w.n_chain, chain_off, w.cout, w.est, pool, w.regs, n_ext};
+		KExtGather kg{w.occ_off, w.n_chain, chain_off, w.cout, est, pool, w.regs, n_ext};
 		rt.launch_wide("ext_gather", R, kg);
 		if (sw.trace) { fprintf(stderr, "[arx] dedup\n"); fflush(stderr); }
-		KDedup kd{ix, b.bases, b.base_off, b.lens, w.occ_off, n_ext, w.regs, w.rtmp, w.idx, w.eh, eh_words, w.n_core, w.core_clean, nullptr, nullptr,
+		KDedup kd{ix, b.bases, b.base_off, b.lens, w.occ_off, n_ext, w.regs, rtmp, idx, eh, eh_words, w.n_core, w.core_clean, nullptr, nullptr,
 		          sw.dedup_heavy_min.value_or(DEDUP_HEAVY_MIN)};
 		if (rt.dedup_heavy_ok()) { kd.heavy_list = rt.template alloc<int32_t>(R + 4); kd.n_heavy = kd.heavy_list + R; rt.memset0(kd.n_heavy, 16); }
 		rt.launch_cold("dedup", R, kd);
@@ -787,27 +780,27 @@ public:
 	void stage_rescue(const DeviceBatch &b, Work &w, BatchResult &out)
 	{
 		const int R = b.n_reads, NP = R / 2, slots = rt.max_slots();
-		w.cap = rt.template alloc<int32_t>(R + 1); w.preg_off = rt.template alloc<int32_t>(R + 2); w.n_regs = rt.template alloc<int32_t>(R + 1);
-		KPairCap kc{w.n_core, w.cap};
+		int32_t *cap = rt.template alloc<int32_t>(R + 1); w.preg_off = rt.template alloc<int32_t>(R + 2); w.n_regs = rt.template alloc<int32_t>(R + 1);
+		KPairCap kc{w.n_core, cap};
 		rt.launch_wide("pair_cap", NP, kc);
-		w.P = rt.exclusive_scan(w.cap, w.preg_off, R);
+		w.P = rt.exclusive_scan(cap, w.preg_off, R);
 		const size_t P = (size_t)w.P + 1;
-		w.pregs = rt.template alloc<Reg>(P); w.ptmp = rt.template alloc<Reg>(P); w.pidx = rt.template alloc<int32_t>(P);
+		w.pregs = rt.template alloc<Reg>(P); Reg *ptmp = rt.template alloc<Reg>(P); int32_t *pidx = rt.template alloc<int32_t>(P);
 		// a loop queues at most min(n_regs, MAX_RESCUE) SWs per pair, so both loops stay below 2P result slots; plus one single SW per pair
-		w.rst = rt.template alloc<ResState>(NP + 1); w.stask = rt.template alloc<SwTask>(P + NP + 1); w.sres = rt.template alloc<U8Res>(2 * P + NP + 1);
+		ResState *rst = rt.template alloc<ResState>(NP + 1); SwTask *stask = rt.template alloc<SwTask>(P + NP + 1); U8Res *sres = rt.template alloc<U8Res>(2 * P + NP + 1);
 		int32_t *n_slots = rt.template alloc<int32_t>(2); // [0] result slots handed out, [1] single SWs
 		rt.memset0(n_slots, 8);
 		const int q_cap = (b.max_len + 15) & ~15, t_cap = (PES_HIGH - PES_LOW + 2 * b.max_len + 31) & ~15;
-		w.sw_scr = rt.template alloc<uint8_t>((size_t)slots * (q_cap + 2 * t_cap));
+		uint8_t *sw_scr = rt.template alloc<uint8_t>((size_t)slots * (q_cap + 2 * t_cap));
 		uint8_t *hv = nullptr; int32_t *hv_list = nullptr, *n_hv = nullptr;
 		if (rt.rescue_heavy_ok()) { hv = rt.template alloc<uint8_t>(NP + 8); hv_list = rt.template alloc<int32_t>(NP + 1); n_hv = rt.template alloc<int32_t>(2); rt.memset0(n_hv, 8); }
-		KPairInit ki{w.occ_off, w.n_core, w.preg_off, w.regs, w.pregs, w.n_regs, w.rst, w.core_clean, w.cap, hv, hv_list, n_hv, sw.rescue_heavy_min.value_or(RESCUE_HEAVY_MIN)};
+		KPairInit ki{w.occ_off, w.n_core, w.preg_off, w.regs, w.pregs, w.n_regs, rst, w.core_clean, cap, hv, hv_list, n_hv, sw.rescue_heavy_min.value_or(RESCUE_HEAVY_MIN)};
 		rt.launch_wide("pair_init", NP, ki);
 		int n_heavy = 0;
 		if (hv) rt.d2h(&n_heavy, n_hv, 4);
 		for (int round = 0;; ++round) {
 			rt.memset0(w.counter, 4);
-			KRescueStep ks{ix, b.lens, w.preg_off, w.pregs, w.ptmp, w.pidx, w.n_regs, w.rst, w.sres, w.stask, w.counter, n_slots, sw.rescue_no_ahead ? 1 : 0, (int32_t)(2 * w.P), hv};
+			KRescueStep ks{ix, b.lens, w.preg_off, w.pregs, ptmp, pidx, w.n_regs, rst, sres, stask, w.counter, n_slots, sw.rescue_no_ahead ? 1 : 0, (int32_t)(2 * w.P), hv};
 			if (n_heavy > 0) rt.run_rescue_heavy("rescue_heavy", n_heavy, hv_list, ks); // on the side stream: a few wavefronts' worth of work
 			rt.launch_cold("rescue_step", NP, ks);
 			rt.aux_join();
@@ -819,7 +812,7 @@ public:
 			}
 			if (round > 2 * MAX_RESCUE + 4) { uint32_t e = ERR_INTERNAL; rt.h2d(w.err, &e, 4); break; }
 			out.n_sw_tasks += nt; ++out.rescue_rounds;
-			KSwU8 kw{ix, b.bases, b.base_off, b.lens, w.stask, w.sres, w.sw_scr, q_cap, t_cap};
+			KSwU8 kw{ix, b.bases, b.base_off, b.lens, stask, sres, sw_scr, q_cap, t_cap};
 			rt.run_sw_u8("sw_u8", nt, kw, b.max_len);
 		}
 	}
@@ -831,18 +824,17 @@ public:
 		const int eh_words = 2 * (b.max_len + 2);
 		const int z_cap = b.max_len * (2 * b.max_len + 64);
 		const size_t P = (size_t)w.P + 1;
-		w.z = rt.template alloc<uint8_t>((size_t)slots * z_cap);
-		rt.free(w.eh); w.eh = rt.template alloc<int32_t>((size_t)slots * eh_words);
+		uint8_t *z = rt.template alloc<uint8_t>((size_t)slots * z_cap);
+		int32_t *eh = rt.template alloc<int32_t>((size_t)slots * eh_words);
 		w.alns = rt.template alloc<Aln>(P);
-		w.nw_list = rt.template alloc<int32_t>(P);
+		int32_t *nw_list = rt.template alloc<int32_t>(P);
 		int32_t *nw_need = rt.template alloc<int32_t>(P + 1), *nw_zoff = rt.template alloc<int32_t>(P + 2), *big_list = rt.template alloc<int32_t>(P);
 		int32_t *cnt2 = rt.template alloc<int32_t>(2 + NW_CLASSES), *class_list = rt.template alloc<int32_t>((size_t)NW_CLASSES * P + 1);
 		for (w.cig_w = 16;; w.cig_w *= 2) {
-			if (w.cig) rt.free(w.cig);
-			w.cig = rt.template alloc<uint32_t>(P * w.cig_w);
+			w.cig = rt.template alloc<uint32_t>(P * w.cig_w); // (a retry's wider slots: the narrower ones stay in the arena until the batch is restarted)
 			rt.memset0(cnt2, 4 * (2 + NW_CLASSES));
-			KReg2Aln k{ix, b.bases, b.base_off, b.lens, w.preg_off, w.n_regs, b.n_reads, w.pregs, w.alns, w.cig, w.cig_w, w.eh, eh_words, w.z, z_cap, w.err,
-			           w.nw_list, cnt2, 0, nw_need, big_list, class_list, (int)P};
+			KReg2Aln k{ix, b.bases, b.base_off, b.lens, w.preg_off, w.n_regs, b.n_reads, w.pregs, w.alns, w.cig, w.cig_w, eh, eh_words, z, z_cap, w.err,
+			           nw_list, cnt2, 0, nw_need, big_list, class_list, (int)P};
 			rt.launch("reg2aln", (int)w.P, k);
 			int32_t n2[2 + NW_CLASSES];
 			rt.d2h(n2, cnt2, 4 * (2 + NW_CLASSES));
@@ -860,19 +852,6 @@ public:
 			if (w.cig_w >= 1024) return (int)e;
 			e &= ~ERR_CIGAR_OVERFLOW; rt.h2d(w.err, &e, 4);
 		}
-	}
-
-	// ---- whole path for one batch (n_reads even: read 2i / 2i+1 are mates).  Returns 0 or an error bit set.
-	int run(const DeviceBatch &b, BatchResult &out, Work &w)
-	{
-		int rc = stage_seed(b, w);
-		if (rc) return rc;
-		stage_chain(b, w);
-		stage_extend(b, w, out);
-		stage_rescue(b, w, out);
-		rc = stage_reg2aln(b, w);
-		out.n_occ = w.T;
-		return rc;
 	}
 
 	// copy the final region lists and alignment records to the host, compacted

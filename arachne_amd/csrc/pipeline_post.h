@@ -61,7 +61,7 @@ struct KSplit {
 	}
 };
 
-struct PostResult { CandPost *d_post = nullptr; SplitRec *d_split = nullptr; int32_t *d_mm_ref = nullptr, *d_mm_read = nullptr; int64_t n_mm = 0; bool done = false; };
+struct PostResult { CandPost *d_post = nullptr; SplitRec *d_split = nullptr; int32_t *d_mm_ref = nullptr, *d_mm_read = nullptr; int64_t n_mm = 0; };
 
 template <class RT> struct PostStage {
 	static int run(Pipeline<RT> &pipe, const typename Pipeline<RT>::DeviceBatch &b, typename Pipeline<RT>::Work &w, const RfaResult &rfa, PostResult &res)
@@ -91,7 +91,7 @@ template <class RT> struct PostStage {
 		SplitRec *split = rt.template alloc<SplitRec>(R + 1);
 		KSplit ks{rfa.d_cands, post, rfa.d_cand_off, act, b.lens, rfa.penalty, rfa.d_cen_start, rfa.d_cen_end, split};
 		rt.launch_wide("split", R, ks);
-		res.d_post = post; res.d_split = split; res.d_mm_ref = mm_ref; res.d_mm_read = mm_read; res.n_mm = NM; res.done = true;
+		res.d_post = post; res.d_split = split; res.d_mm_ref = mm_ref; res.d_mm_read = mm_read; res.n_mm = NM;
 		return 0;
 	}
 	static void fetch(Pipeline<RT> &pipe, const typename Pipeline<RT>::DeviceBatch &b, const RfaResult &rfa, const PostResult &res, CandPost *post, SplitRec *split,

@@ -210,7 +210,7 @@ template <class RT> struct RfaStage {
 
 // arx_batch_tags: the per-read values of mapq_data that AppendBam writes (XS, AS, XM, XT, the second best for XC, DM), on the candidate
 // records and pair scores the RFA stage left in HBM.  Not part of arx_batch_rfa: callers that write no tags pay nothing for it.
-struct TagsResult { ReadTags *d_tags = nullptr; bool done = false; std::vector<size_t> mark; bool marked = false; };
+struct TagsResult { ReadTags *d_tags = nullptr; };
 template <class RT> struct TagsStage {
 	static void run(Pipeline<RT> &pipe, const typename Pipeline<RT>::DeviceBatch &b, const RfaResult &rfa, TagsResult &res)
 	{
@@ -227,7 +227,7 @@ template <class RT> struct TagsStage {
 		rt.launch_wide("tags_mol", R, km);
 		KTags kt{rfa.d_cands, rfa.d_cand_off, rfa.d_bc_read_off, NB, rfa.d_lmp, b.lens, rfa.d_pair_best, rfa.penalty, d_mol_off, mol_n, mol_sum, tags};
 		rt.launch_wide("tags", R, kt);
-		res.d_tags = tags; res.done = true;
+		res.d_tags = tags;
 	}
 	static void fetch(Pipeline<RT> &pipe, const typename Pipeline<RT>::DeviceBatch &b, const TagsResult &res, ReadTags *out)
 	{

@@ -112,9 +112,26 @@ struct SimRT {
 	std::string init(int) { return ""; }
 	void bind() {}
 	void set_timing(bool) {}
-	// poison fresh memory: hipMalloc does not zero either, so nothing may rely on it
-	template <class T> T *alloc(size_t n) { size_t b = (n ? n : 1) * sizeof(T); void *p = malloc(b); memset(p, 0xAB, b); return (T *)p; }
-	void free(void *p) { ::free(p); }
+	// The work arena of hip_rt.h, for real: alloc() records its blocks; arena_rewind() and arena_reset() fill every block handed out after the
+	// mark with 0xDD and free it, so whatever reads memory that a rewind gave away reads poison here and faults under AddressSanitizer.
+	// Fresh memory is poisoned with another byte: hipMalloc does not zero either, so nothing may rely on it
+	std::vector<std::pair<void *, size_t> > blocks; size_t live_bytes = 0; // (live_bytes: arx_test_arena_live_bytes)
+	SimRT() = default;
+	SimRT(const SimRT &) = delete;
+	SimRT &operator=(const SimRT &) = delete;
+	~SimRT() { arena_reset(); }
+	static void *fresh(size_t b) { void *p = malloc(b); memset(p, 0xAB, b); return p; }
+	template <class T> T *alloc(size_t n) { const size_t b = (n ? n : 1) * sizeof(T); blocks.push_back(std::make_pair(fresh(b), b)); live_bytes += b; return (T *)blocks.back().first; }
+	std::vector<size_t> arena_mark() const { return {blocks.size()}; }
+	void arena_rewind(const std::vector<size_t> &m)
+	{
+		for (const size_t keep = m.empty() ? 0 : m[0]; blocks.size() > keep; blocks.pop_back()) {
+			memset(blocks.back().first, 0xDD, blocks.back().second);
+			::free(blocks.back().first);
+			live_bytes -= blocks.back().second;
+		}
+	}
+	void arena_reset() { arena_rewind({}); }
 	void seed_prepare(const uint8_t *, const int32_t *, const int32_t *, int) {}
 	bool rescue_heavy_ok() const { return sim_rescue_heavy; } // the host double can run the split (same serial code on the flagged pairs)
 	void aux_join() {}
@@ -130,11 +147,8 @@ struct SimRT {
 	static int host_unregister(void *) { return 0; }
 	static bool host_pinned(const void *) { return false; }
 	void h2d_pinned(void *d, const void *s, size_t bytes) { memcpy(d, s, bytes); }
-	template <class T> T *palloc(size_t n) { return alloc<T>(n); }
+	template <class T> T *palloc(size_t n) { return (T *)fresh((n ? n : 1) * sizeof(T)); } // persistent: outside the arena
 	void pfree(void *p) { ::free(p); }
-	void arena_reset() {}
-	std::vector<size_t> arena_mark() const { return {}; }
-	void arena_rewind(const std::vector<size_t> &) {}
 	void h2d(void *d, const void *s, size_t b) { if (b) memcpy(d, s, b); }
 	void d2h(void *d, const void *s, size_t b) { if (b) memcpy(d, s, b); }
 	void d2h_async(void *d, const void *s, size_t b) { if (b) memcpy(d, s, b); }
@@ -184,6 +198,10 @@ struct SimRT {
 
 #include "../../arachne_amd/csrc/api_impl.h"
 ARX_DEFINE_C_API(arx::SimRT)
+
+// test entry: the bytes of a batch's work arena that are live now (tests/test_arena_lifecycle.py: no phase grows from one cycle to the next, and
+// each phase rewinds to its own mark)
+extern "C" int64_t arx_test_arena_live_bytes(arx_batch *bh) { return (int64_t)((arx::Batch<arx::SimRT> *)bh)->rt.live_bytes; }
 
 // test entry: ksw_align2's two passes with the row's F by the plain recurrence (dev_sw.h u8_pass, exact_f: what the rescue kernel's scan
 // computes) -- tests/test_sw_prefilter.py compares it with the restatement's striped pass + lazy-F loop
