@@ -96,6 +96,106 @@ ARX_DEV ExtRes ext2_task(const IndexView &ix, const uint8_t *bases, const ExtTas
 	return r;
 }
 
+// ---- The extensions their diagonal decides.  Most extension tasks carry a seed across the one substitution that ended it: behind it the
+// read follows the reference base for base to its end.  For a task with tlen >= qlen > 0, h0 >= 5, no ambiguous base and at most ONE
+// differing pair among the first qlen pairs (q[j], t[j]) all six outputs of ext2_task follow from the diagonal, without the DP.
+// With a = 1, b = 4, o_del = o_ins = 6, e_del = e_ins = 1 (the static_assert below holds the function to them):
+//   * Off the diagonal.  A path to cell (i, j), i != j, pays at least 6 + |i - j| for its gap and gains at most min(i, j) + 1 matches:
+//     H(i, j) <= h0 + min(i, j) + 1 - 6 - |i - j| <= h0 + i - 6 in row i, either side of the diagonal.  The first row and column are gap
+//     runs from h0 themselves (ext2_task's "first row" block and its h1 at beg == 0), and E and F are fed from M, not H (the tt = M - oe_*
+//     lines), which only lowers the bound.  A gapped path BACK to a diagonal cell needs an insertion and a deletion: <= h0 + i - 14.
+//   * On the diagonal.  With k(i) <= 1 differing pairs among pairs 0 .. i the prefix score is P(i) = h0 + (i + 1) - 5 k(i) >= h0 + i - 4, so
+//     H(i, i) = P(i) exactly, positive because h0 >= 5.  The running maximum after row i - 1 is at least P(i - 1) >= h0 + i - 5 > h0 + i - 6:
+//     no off-diagonal cell makes a row maximum that beats it, `m > max` can only fire on the diagonal cell, which is then the strict and only
+//     maximum of its row (mj == i), and max_off stays 0.  score = max(h0, max P) and qle = tle = the earliest index whose P strictly exceeds
+//     everything before it (0 when none exceeds h0): P rises by one per row up to the differing pair p, drops to h0 + p - 4 there and
+//     passes h0 + p again with the fifth pair behind p.
+//   * The `j == qlen` block.  Column qlen - 1 holds P(qlen - 1) >= h0 + qlen - 5 on the diagonal and at most h0 + qlen - 7 elsewhere, so
+//     gscore = P(qlen - 1) and gtle = qlen with no tie to break.  This needs the DP to reach row qlen - 1: tlen >= qlen.
+//   * Neither break fires before row qlen - 1: `m == 0` cannot (the row maximum is at least P(i) > 0) and z-drop cannot (max - m <= 4 on the
+//     diagonal, where mj - max_j == i - max_i); the diagonal cell lies inside the band (w >= 1) and is never trimmed from [beg, end), being
+//     non-zero.  The rows behind the query hold off-diagonal cells only and change nothing.
+// With two differing pairs the gscore bound no longer separates (h0 + qlen - 10 against h0 + qlen - 7): k <= 1 and nothing wider.
+// The target never holds an ambiguous base (two bits per base), so only the read's bases are looked at for that.
+static_assert(OPT_A == 1 && OPT_B == 4 && OPT_O_DEL == 6 && OPT_O_INS == 6 && OPT_E_DEL == 1 && OPT_E_INS == 1, "ext_closed_result's proof uses these scores");
+
+// the six outputs from the diagonal: n_mm (0 or 1) differing pairs among the qlen, the differing one at index p
+ARX_DEVI ExtRes ext_closed_result(const ExtTask &t, int n_mm, int p)
+{
+	ExtRes r;
+	const int full = t.h0 + t.qlen - 5 * n_mm;
+	const bool to_end = n_mm == 0 || t.qlen - 1 - p >= 5; // the last pair's P exceeds what stood before the differing pair
+	r.score = to_end ? full : t.h0 + p;
+	r.qle = r.tle = to_end ? t.qlen : p;
+	r.gtle = t.qlen; r.gscore = full; r.max_off = 0;
+	return r;
+}
+
+// pair by pair (the unit test holds the word-wise form to it)
+ARX_DEVI bool ext_closed_form_pairwise(const IndexView &ix, const uint8_t *bases, const ExtTask &t, ExtRes &r)
+{
+	if (t.qlen <= 0 || t.tlen < t.qlen || t.h0 < 5) return false;
+	int n_mm = 0, p = 0;
+	for (int j = 0; j < t.qlen; ++j) {
+		const int c = bases[t.qoff + j * t.qdir], tb = ref_base(ix, t.tpos + (int64_t)j * t.tdir);
+		if (c > 3) return false;
+		if (c != tb) { if (n_mm) return false; n_mm = 1; p = j; }
+	}
+	r = ext_closed_result(t, n_mm, p);
+	return true;
+}
+
+// Four pairs per step, as gapfree_counts walks them: the read's four bytes as one (unaligned) word squeezed to 2-bit codes, the packed
+// strand's byte sliding along.  Pair j sits at position p0 + j * sdir of the packed strand (sdir = tdir on the forward half of the doubled
+// coordinate, -tdir and complemented on the reverse half) and at byte qoff + j * qdir of the reads: four orientations.  The strand's byte
+// order decides the layout of the four codes (upwards: pair m in bits 7 - 2m, 6 - 2m; downwards: bits 2m + 1, 2m), and the read's word is
+// byte-swapped to match it where the two run the same way.  Leaves at the second differing pair or the first ambiguous base.
+ARX_DEVI bool ext_closed_form(const IndexView &ix, const uint8_t *bases, const ExtTask &t, ExtRes &r)
+{
+	const int qlen = t.qlen;
+	if (qlen <= 0 || t.tlen < qlen || t.h0 < 5) return false;
+	int n_mm = 0, p = 0, j = 0;
+	if (qlen >= 4) {
+		const bool rev = t.tpos >= ix.l_pac;
+		const int sdir = rev ? -t.tdir : t.tdir;
+		const int64_t p0 = rev ? (ix.l_pac << 1) - 1 - t.tpos : t.tpos;
+		const int o = (int)(p0 & 3);
+		const int64_t b_lim = (p0 + (int64_t)(qlen - 1) * sdir) >> 2; // last byte the walk touches
+		const bool swap = (t.qdir < 0) == (sdir < 0);
+		const uint32_t flip = rev ? 0xffu : 0u;
+		const uint8_t *q = bases + t.qoff + (t.qdir < 0 ? -3 : 0);
+		int64_t b = p0 >> 2;
+		uint32_t cur = ix.pac[b], nxt;
+		if (sdir > 0) b = b + 1 < b_lim ? b + 1 : b_lim; else b = b - 1 > b_lim ? b - 1 : b_lim;
+		nxt = ix.pac[b];
+		for (; j + 4 <= qlen; j += 4) {
+			uint32_t qw;
+			__builtin_memcpy(&qw, q + j * t.qdir, 4);
+			if (qw & 0xfcfcfcfcu) return false; // a read base above 3
+			if (swap) qw = __builtin_bswap32(qw);
+			const uint32_t q8 = (qw & 3u) | ((qw >> 6) & 0xcu) | ((qw >> 12) & 0x30u) | ((qw >> 18) & 0xc0u); // byte m in bits 2m + 1, 2m
+			const uint32_t t8 = (sdir > 0 ? (((cur << 8) | nxt) >> (8 - 2 * o)) : (((nxt << 8) | cur) >> (6 - 2 * o))) & 0xffu;
+			const uint32_t x = t8 ^ q8 ^ flip;
+			const uint32_t d = (x | (x >> 1)) & 0x55u;
+			if (d) {
+				if (n_mm || (d & (d - 1))) return false;
+				const int m = (31 - __builtin_clz(d)) >> 1; // the set bit's pair: m when the strand runs downwards, 3 - m upwards
+				n_mm = 1; p = j + (sdir > 0 ? 3 - m : m);
+			}
+			cur = nxt;
+			if (sdir > 0) b = b + 1 < b_lim ? b + 1 : b_lim; else b = b - 1 > b_lim ? b - 1 : b_lim;
+			nxt = ix.pac[b];
+		}
+	}
+	for (; j < qlen; ++j) {
+		const int c = bases[t.qoff + j * t.qdir], tb = ref_base(ix, t.tpos + (int64_t)j * t.tdir);
+		if (c > 3) return false;
+		if (c != tb) { if (n_mm) return false; n_mm = 1; p = j; }
+	}
+	r = ext_closed_result(t, n_mm, p);
+	return true;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Striped u8 local SW.  The 16-way striping of the SSE2 original is observable in the results (E is fed the
 // pre-lazy-F H, F restarts at every stripe boundary), so the cell order is kept: query position j + l*slen is

@@ -292,6 +292,7 @@ struct KExtStep {
 	ExtState *state; const ExtRes *res; ExtTask *tasks; int32_t *n_tasks; int round;
 	int task_stride;                              // tasks + c * task_stride: the list of length class c, n_tasks[c] its length
 	const int32_t *act_in; int32_t *act_out;      // chains still extending or waiting (null in the first round: all); n_tasks[EXT_CLASSES] counts act_out
+	const uint8_t *bases;                         // non-null: a task its diagonal decides (dev_sw.h ext_closed_form) is answered here, not queued
 	ARX_DEV void operator()(int item, int) const
 	{
 		const int gid = act_in ? act_in[item] : item;
@@ -299,8 +300,10 @@ struct KExtStep {
 		if (st.phase == PH_DONE) return;
 		const int r = chain_read[gid], c0 = chain_off[r], g0 = occ_off[r];
 		ExtTask t;
-		const ExtRes rs = res[gid]; // only read by a chain that queued a DP in the previous round
-		const int what = ext_step(ix, gid, base_off[r], lens[r], chains + g0, gid - c0, seeds, srt, regs, state + c0, round, st, rs, t);
+		ExtRes rs = res[gid]; // only read by a chain that queued a DP in the previous round
+		int what = ext_step(ix, gid, base_off[r], lens[r], chains + g0, gid - c0, seeds, srt, regs, state + c0, round, st, rs, t);
+		// the chain goes on within the round: to its neighbours it reads as running either way (done_round is 0 or this round)
+		if (bases) while (what == EXT_TASK && ext_closed_form(ix, bases, t, rs)) what = ext_step(ix, gid, base_off[r], lens[r], chains + g0, gid - c0, seeds, srt, regs, state + c0, round, st, rs, t);
 		state[gid] = st;
 #if defined(__HIP_DEVICE_COMPILE__)
 		// One atomic round trip per wavefront: the lanes count themselves per list with ballots, the first lane of every list reserves for
@@ -752,7 +755,7 @@ public:
 		for (int round = 2; n_act > 0; ++round) {
 			rt.memset0(ecnt, 4 * (EXT_CLASSES + 1));
 			KExtStep ks{ix, b.base_off, b.lens, w.occ_off, chain_off, chain_read, w.cout, w.sout, srt, pool, est, eres, etask, ecnt, round,
-			            NCH + 1, round == 2 ? nullptr : act[round & 1], act[(round + 1) & 1]};
+			            NCH + 1, round == 2 ? nullptr : act[round & 1], act[(round + 1) & 1], sw.ext_closed ? b.bases : nullptr};
 			rt.launch_wide("ext_step", n_act, ks);
 			int32_t cnt[EXT_CLASSES + 1];
 			rt.d2h(cnt, ecnt, 4 * (EXT_CLASSES + 1));

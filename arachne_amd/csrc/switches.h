@@ -129,6 +129,10 @@ struct PipelineSwitches {
 	std::optional<int> rescue_heavy_min = sw_int_if_set("ARX_RESCUE_HEAVY_MIN"); // regions of both reads together from which a pair is heavy (tests)
 	int chain_mid_min = sw_int("ARX_CHAIN_MID_MIN", 16);       // occurrences from which a read below the heavy threshold is listed for KChainMid; 0: no launch of their own for the reads in between
 	bool rescue_no_ahead = sw_present("ARX_RESCUE_NO_AHEAD");  // every rescue SW down the one-at-a-time path instead of queued ahead (tests)
+	// -- extension
+	// 0: every extension task goes to the DP.  Default: KExtStep answers the tasks their diagonal decides itself (dev_sw.h ext_closed_form: at
+	// most one differing pair, no ambiguous base, h0 >= 5, tlen >= qlen) and the chain goes on in the same round (profiles/ext_closed/)
+	bool ext_closed = sw_on_unless_zero("ARX_EXT_CLOSED");
 	// -- placement (pipeline_rfa.h)
 	// ARX_RFA_SMALL=1 (experiments): barcodes of TELLseq size in 256-lane workgroups (hip_block.h).  Measured at 4,333 barcodes x 77
 	// pairs per batch: 23.3 ms against 7.4 ms with 1,024 lanes for every barcode -- the per-barcode phases are latency chains whose
