@@ -127,6 +127,9 @@ _SELFTEST_ARGS = {
     "arx_selftest_rescue_sw": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
     "arx_selftest_gen_cigar": [C.c_int32, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
+    "arx_selftest_bgzf": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    # the device BAM sink: bound when first used, for the same reason
+    "arx_bam_open_device": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
 }
 
 
@@ -208,6 +211,21 @@ def selftest_gen_cigar(queries, targets, w, klass: int, cap=None, cig_w: int = 0
     if rc != 0:
         raise ArachneError("arx_selftest_gen_cigar: code %d" % rc)
     return out, cig
+
+
+def bgzf_selftest(data, device: int = 0, lib_path: str = LIB_PATH):
+    """The device BAM sink's kernels on arbitrary bytes (include/arachne_amd.h: arx_selftest_bgzf): data cut every 65280 bytes, every block
+    deflated and checksummed on the GPU -> (the framed BGZF blocks without the EOF block, dict(blocks, stored, fixed, dynamic))."""
+    lib = _load(lib_path)
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = len(src)
+    cap = n + 31 * ((n + 65279) // 65280) + 64
+    out = np.zeros(cap, dtype=np.uint8)
+    out_len, st = C.c_int64(-1), np.zeros(4, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_bgzf")(device, src.ctypes.data if n else None, n, out.ctypes.data, cap, C.byref(out_len), st.ctypes.data)
+    if rc != 0:
+        raise ArachneError("arx_selftest_bgzf: code %d" % rc)
+    return out[:out_len.value].tobytes(), dict(blocks=int(st[0]), stored=int(st[1]), fixed=int(st[2]), dynamic=int(st[3]))
 
 
 def index_build(fasta: str, prefix: str, lib_path: str = LIB_PATH) -> None:
@@ -533,15 +551,25 @@ class _BamBatch(C.Structure):
 
 class BamWriter:
     """The BAM sink behind the path (arx_bam_*): records in batches of flat arrays, encoded and BGZF-compressed on `threads` host threads.
-    Host code of the product library; needs no GPU."""
+    Host code of the product library; needs no GPU.
 
-    def __init__(self, path: str, contig_names, contig_lens, extra_header: str = "", threads: int = 8, level: int = -1, lib_path: str = LIB_PATH):
-        self.lib = _load(lib_path)
+    device=<Reference>: the device sink (arx_bam_open_device) -- records are still encoded on `threads` host threads, the BGZF blocks are
+    deflated and checksummed by HIP kernels on that reference's GPU; the file inflates to the same bytes, `level` does not apply."""
+
+    def __init__(self, path: str, contig_names, contig_lens, extra_header: str = "", threads: int = 8, level: int = -1, lib_path: str = LIB_PATH,
+                 device: "Reference | None" = None):
+        self.lib = device.lib if device is not None else _load(lib_path)
         self.h = C.c_void_p()
         n = len(contig_names)
         names = (C.c_char_p * n)(*[x.encode() for x in contig_names])
         lens = np.ascontiguousarray(contig_lens, dtype=np.int32)
         msg = C.create_string_buffer(512)
+        if device is not None:
+            rc = _selftest_fn(self.lib, "arx_bam_open_device")(device.h, path.encode(), n, names, lens.ctypes.data, extra_header.encode() if extra_header else None, threads,
+                                                               C.byref(self.h), msg, 512)
+            if rc != 0:
+                raise ArachneError("arx_bam_open_device: " + msg.value.decode())
+            return
         if self.lib.arx_bam_open(path.encode(), n, names, lens.ctypes.data, extra_header.encode() if extra_header else None, threads, level, C.byref(self.h), msg, 512) != 0:
             raise ArachneError("arx_bam_open: " + msg.value.decode())
 

@@ -348,6 +348,7 @@ template <class RT> struct Batch {
 		info[6] = info[7] = 0;                                                                                                      \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
+	int arx_ctx_device(arx_ctx *h) { return h ? ((Ctx *)h)->device : -1; }                                                       \
 	int arx_contigs(arx_ctx *h, int32_t *n, const char *const **names, const int64_t **offsets, const int32_t **lens,               \
 	                const int32_t **is_alt, int64_t *l_pac)                                                                         \
 	{                                                                                                                               \

@@ -1,0 +1,79 @@
+// arx_bgzf.hip -- the device BAM sink (include/arachne_amd.h: arx_bam_open_device, arx_selftest_bgzf): BamSink (bam_sink.h) with the compressor of
+// hip_bgzf.h behind its seam.  Its own unit: the kernels of dev_bgzf.h compile next to the pipeline's.
+#include <map>
+#include <memory>
+#include <mutex>
+#include "../../include/arachne_amd.h"
+#include "hip_bgzf.h"
+
+namespace arx {
+
+// One compressor per device, made by the first writer (or self-test) that asks for it and kept until the process ends: its streams, staging and
+// device buffers are sized once and reused by every later writer (the reference layout keeps one writer per position bucket open; e2e.run opens
+// writers run after run).  The map itself is never destroyed, so that no HIP call runs from a static destructor.
+static std::shared_ptr<DeviceBgzf> shared_device_bgzf(int device)
+{
+	static std::mutex mu;
+	static std::map<int, std::shared_ptr<DeviceBgzf> > *live = new std::map<int, std::shared_ptr<DeviceBgzf> >();
+	std::lock_guard<std::mutex> lock(mu);
+	std::shared_ptr<DeviceBgzf> &p = (*live)[device];
+	if (!p) {
+		std::shared_ptr<DeviceBgzf> z = std::make_shared<DeviceBgzf>();
+		z->init(device);
+		p = z;
+	}
+	return p;
+}
+
+} // namespace arx
+
+extern "C" int arx_bam_open_device(arx_ctx *ctx, const char *path, int32_t n_contigs, const char *const *names, const int32_t *lens, const char *extra_header,
+                                   int32_t threads, arx_bam **out, char *msg, int32_t msg_cap)
+{
+	auto say = [&](const char *m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m); };
+	if (out) *out = nullptr;
+	if (!ctx) { say("arx_bam_open_device: null context"); return ARX_E_ARG; }
+	if (!out || !path || n_contigs < 0 || (n_contigs > 0 && (!names || !lens))) { say("arx_bam_open_device: null argument"); return ARX_E_ARG; }
+	arx::BamSink *w = nullptr;
+	try {
+		w = new arx::BamSink();
+		w->comp = arx::shared_device_bgzf(arx_ctx_device(ctx));
+		if (!w->open(path, n_contigs, names, lens, extra_header, threads, 1)) {
+			const bool io = !w->f;
+			say(w->error.c_str());
+			delete w;
+			return io ? ARX_E_IO : ARX_E_DEVICE;
+		}
+	} catch (const std::exception &e) {
+		say(e.what());
+		delete w;
+		return ARX_E_DEVICE;
+	}
+	*out = (arx_bam *)w;
+	return ARX_OK;
+}
+
+extern "C" int arx_selftest_bgzf(int32_t device, const uint8_t *src, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, int64_t *stats)
+{
+	if (n < 0 || cap < 0 || !out_len || (n > 0 && (!src || !out))) return ARX_E_ARG;
+	*out_len = 0;
+	if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+	if (n == 0) return ARX_OK;
+	try {
+		std::shared_ptr<arx::DeviceBgzf> zp = arx::shared_device_bgzf(device);
+		arx::DeviceBgzf &z = *zp;
+		std::lock_guard<std::mutex> lock(z.mu); // a flush at a time; the counts of the forms below are this call's
+		const int64_t before[3] = {z.n_form[0], z.n_form[1], z.n_form[2]};
+		int64_t at = 0;
+		bool fits = true;
+		z.compress(src, (size_t)n, [&](const uint8_t *p, size_t bytes) {
+			if (fits && at + (int64_t)bytes <= cap) { memcpy(out + at, p, bytes); at += (int64_t)bytes; } else fits = false;
+		});
+		if (!fits) return ARX_E_ARG;
+		*out_len = at;
+		if (stats) { stats[0] = (n + arx::BGZF_IN - 1) / arx::BGZF_IN; stats[1] = z.n_form[0] - before[0]; stats[2] = z.n_form[1] - before[1]; stats[3] = z.n_form[2] - before[2]; }
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}

@@ -18,6 +18,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <zlib.h>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -25,8 +26,17 @@
 
 namespace arx {
 
+// The seam behind flush(): something else that turns `total` bytes, cut every BamSink::BLOCK_IN bytes, into framed BGZF blocks and writes them to f
+// in order, adding what it wrote to bytes_out.  BamSink's own path (zlib on `threads` host threads) is the default; hip_bgzf.h holds the one
+// that compresses on the GPU (arx_bam_open_device).
+struct BlockCompressor {
+	virtual ~BlockCompressor() {}
+	virtual bool run(const uint8_t *src, size_t total, FILE *f, int64_t &bytes_out, std::string &error) = 0;
+};
+
 struct BamSink {
 	FILE *f = nullptr;
+	std::shared_ptr<BlockCompressor> comp; // null: deflate_block below
 	int threads = 1, level = 6;
 	std::string error;
 	std::vector<uint8_t> pending;         // uncompressed bytes not yet cut into a block
@@ -155,6 +165,13 @@ struct BamSink {
 		const size_t total = pending.size();
 		const size_t nb = all ? (total + BLOCK_IN - 1) / BLOCK_IN : total / BLOCK_IN;
 		if (nb == 0) return true;
+		if (comp) {
+			const size_t used = all ? total : nb * BLOCK_IN;
+			if (!comp->run(pending.data(), used, f, bytes_out, error)) return false;
+			n_blocks += (int64_t)nb; bytes_in += (int64_t)used;
+			pending.erase(pending.begin(), pending.begin() + used);
+			return true;
+		}
 		std::vector<std::vector<uint8_t> > out(nb);
 		std::vector<int> ok(nb, 1);
 		parallel(nb, [&](size_t lo, size_t hi) {

@@ -1,0 +1,203 @@
+// hip_bgzf.h -- dev_bgzf.h on the GPU, and the device compressor behind BamSink's seam (bam_sink.h: BlockCompressor).
+//
+//   k_bgzf_deflate   one workgroup of BGZF_LANES lanes per BGZF block: input and tables in LDS (about 92 KB), the token array in a scratch row
+//                    of the workgroup's own; writes the raw DEFLATE stream into the block's 64 KiB slice and four words of meta
+//   k_bgzf_frame     one workgroup per block: the 18-byte BGZF header, the stream, CRC-32 and ISIZE, packed back to back in file order (the
+//                    bytes BamSink::deflate_block frames a block with); a block's offset is the sum of the framed sizes in front of it
+//
+// DeviceBgzf owns two streams, two page-locked staging pairs and the device buffers of two groups of at most GROUP blocks, allocated once
+// (about 64 MB of page-locked and 100 MB of device memory: one per device for the life of the process, see arx_bgzf.hip).
+// run() takes the blocks of one flush in groups: while group g is uploaded, compressed, framed and its sizes come back, the framed bytes of
+// group g - 1 are downloaded and written.  Blocks reach the sink in order.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <string.h>
+#include <mutex>
+#include <stdexcept>
+#include <string>
+#include "dev_bgzf.h"
+#include "hip_block.h"
+#include "bam_sink.h"
+
+namespace arx {
+
+#define ARX_BGZF_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw std::runtime_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+
+struct BgzfHipDrv { // dev_bgzf.h's driver on a workgroup
+	HipBlockT<BGZF_LANES, 1> blk;
+	template <class F> __device__ __forceinline__ void lanes(F f) { f(blk.tid); __syncthreads(); }
+	__device__ __forceinline__ void scan(const int32_t *in, int32_t *out, int n) { blk.exclusive_scan(in, out, n); }
+};
+
+constexpr int BGZF_TOK_ROW = BGZF_IN + 8; // uint16 entries of a workgroup's token row
+
+static __global__ void __launch_bounds__(BGZF_LANES) k_bgzf_deflate(const uint8_t *src, int64_t total, int n_blocks, uint16_t *tok, uint32_t *out, uint32_t *meta)
+{
+	extern __shared__ __attribute__((aligned(16))) uint8_t lds_bgzf[];
+	__shared__ int32_t l32[BGZF_LANES + 1];
+	BgzfWork w;
+	bgzf_carve(w, lds_bgzf, tok + (size_t)blockIdx.x * BGZF_TOK_ROW);
+	BgzfHipDrv drv{{(int)threadIdx.x, nullptr, l32, nullptr, nullptr}}; // only exclusive_scan is used: it needs l32 alone (no l64, no sort buffers)
+	drv.lanes([&](int lane) { bgzf_tables(w, lane); });
+	drv.lanes([&](int lane) { bgzf_shift_table(w, lane); });
+	// uniform over the workgroup.  With a grid of min(CUs, GROUP) workgroups and at most GROUP blocks per launch a workgroup takes a second
+	// block only on a device with fewer than GROUP CUs (the host simulator runs every block through one BgzfWork)
+	for (int b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+		const int64_t b0 = (int64_t)b * BGZF_IN;
+		const int n = total - b0 < BGZF_IN ? (int)(total - b0) : BGZF_IN;
+		bgzf_block(drv, w, src + b0, n, out + (size_t)b * (BGZF_OUT_SLICE / 4), meta + 4 * (size_t)b);
+	}
+}
+
+static __global__ void __launch_bounds__(256) k_bgzf_frame(const uint32_t *slices, const uint32_t *meta, int n_blocks, uint8_t *packed)
+{
+	__shared__ unsigned int lds_off;
+	const int b = blockIdx.x, tid = threadIdx.x;
+	if (tid == 0) lds_off = 0;
+	__syncthreads();
+	unsigned int part = 0;
+	for (int k = tid; k < b; k += 256) part += meta[4 * k] + 26;
+	if (part) atomicAdd(&lds_off, part);
+	__syncthreads();
+	const uint32_t clen = meta[4 * b], crc = meta[4 * b + 1], isize = meta[4 * b + 3], bsize = 18 + clen + 8 - 1;
+	uint8_t *o = packed + lds_off; // at most n_blocks * 65536 bytes: clen <= 5 + 65280
+	const uint8_t *s = (const uint8_t *)(slices + (size_t)b * (BGZF_OUT_SLICE / 4));
+	if (tid < 18) {
+		const uint8_t hdr[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)bsize, (uint8_t)(bsize >> 8)};
+		o[tid] = hdr[tid];
+	} else if (tid < 26) {
+		const int k = tid - 18;
+		o[18 + clen + k] = (uint8_t)((k < 4 ? crc : isize) >> (8 * (k & 3)));
+	}
+	for (uint32_t i = tid; i < clen; i += 256) o[18 + i] = s[i];
+}
+
+struct DeviceBgzf : BlockCompressor {
+	static constexpr int GROUP = 256; // blocks of a group: 16 MiB each way
+	int dev = -1, n_cu = 256, grid = 0;
+	bool ready = false;
+	hipStream_t st[2] = {nullptr, nullptr};
+	hipEvent_t ev_meta[2] = {nullptr, nullptr}, ev_pay[2] = {nullptr, nullptr};
+	uint8_t *h_in[2] = {nullptr, nullptr}, *h_out[2] = {nullptr, nullptr};
+	uint32_t *h_meta[2] = {nullptr, nullptr};
+	uint8_t *d_in[2] = {nullptr, nullptr}, *d_packed[2] = {nullptr, nullptr};
+	uint32_t *d_slices[2] = {nullptr, nullptr}, *d_meta[2] = {nullptr, nullptr};
+	uint16_t *d_tok[2] = {nullptr, nullptr};
+	int64_t n_form[3] = {0, 0, 0}; // blocks that went out stored, fixed, dynamic
+	std::mutex mu;                 // the writers of one device share one compressor (arx_bgzf.hip): a flush at a time
+
+	void init(int device)
+	{
+		int n = 0;
+		if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw std::runtime_error("no HIP device visible: the device BAM sink needs an MI355X (there is no CPU fallback)");
+		if (device < 0 || device >= n) throw std::runtime_error("device index out of range");
+		dev = device;
+		ARX_BGZF_CHECK(hipSetDevice(dev));
+		hipDeviceProp_t p;
+		ARX_BGZF_CHECK(hipGetDeviceProperties(&p, dev));
+		n_cu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+		grid = n_cu < GROUP ? n_cu : GROUP; // one workgroup per CU: its LDS does not leave room for two
+		ARX_BGZF_CHECK(hipFuncSetAttribute((const void *)k_bgzf_deflate, hipFuncAttributeMaxDynamicSharedMemorySize, BGZF_WORK_BYTES));
+		for (int s = 0; s < 2; ++s) {
+			ARX_BGZF_CHECK(hipStreamCreateWithFlags(&st[s], hipStreamNonBlocking));
+			ARX_BGZF_CHECK(hipEventCreateWithFlags(&ev_meta[s], hipEventDisableTiming));
+			ARX_BGZF_CHECK(hipEventCreateWithFlags(&ev_pay[s], hipEventDisableTiming));
+			ARX_BGZF_CHECK(hipHostMalloc((void **)&h_in[s], (size_t)GROUP * BGZF_IN, hipHostMallocDefault));
+			ARX_BGZF_CHECK(hipHostMalloc((void **)&h_out[s], (size_t)GROUP * BGZF_OUT_SLICE, hipHostMallocDefault));
+			ARX_BGZF_CHECK(hipHostMalloc((void **)&h_meta[s], (size_t)GROUP * 16, hipHostMallocDefault));
+			ARX_BGZF_CHECK(hipMalloc((void **)&d_in[s], (size_t)GROUP * BGZF_IN));
+			ARX_BGZF_CHECK(hipMalloc((void **)&d_slices[s], (size_t)GROUP * BGZF_OUT_SLICE));
+			ARX_BGZF_CHECK(hipMalloc((void **)&d_packed[s], (size_t)GROUP * BGZF_OUT_SLICE));
+			ARX_BGZF_CHECK(hipMalloc((void **)&d_meta[s], (size_t)GROUP * 16));
+			ARX_BGZF_CHECK(hipMalloc((void **)&d_tok[s], (size_t)grid * BGZF_TOK_ROW * 2));
+		}
+		ready = true;
+	}
+	~DeviceBgzf() override
+	{
+		if (dev >= 0) (void)hipSetDevice(dev);
+		for (int s = 0; s < 2; ++s) {
+			if (st[s]) (void)hipStreamSynchronize(st[s]);
+			if (h_in[s]) (void)hipHostFree(h_in[s]);
+			if (h_out[s]) (void)hipHostFree(h_out[s]);
+			if (h_meta[s]) (void)hipHostFree(h_meta[s]);
+			(void)hipFree(d_in[s]); (void)hipFree(d_slices[s]); (void)hipFree(d_packed[s]); (void)hipFree(d_meta[s]); (void)hipFree(d_tok[s]);
+			if (ev_meta[s]) (void)hipEventDestroy(ev_meta[s]);
+			if (ev_pay[s]) (void)hipEventDestroy(ev_pay[s]);
+			if (st[s]) (void)hipStreamDestroy(st[s]);
+		}
+	}
+
+	// group g of the flush: upload, the two kernels, the sizes on their way back
+	void submit(const uint8_t *src, size_t total, size_t g)
+	{
+		const int s = (int)(g & 1);
+		const size_t b0 = g * GROUP * (size_t)BGZF_IN, bytes = total - b0 < (size_t)GROUP * BGZF_IN ? total - b0 : (size_t)GROUP * BGZF_IN;
+		const int nb = (int)((bytes + BGZF_IN - 1) / BGZF_IN);
+		memcpy(h_in[s], src + b0, bytes);
+		ARX_BGZF_CHECK(hipMemcpyAsync(d_in[s], h_in[s], bytes, hipMemcpyHostToDevice, st[s]));
+		hipLaunchKernelGGL(k_bgzf_deflate, dim3(nb < grid ? nb : grid), dim3(BGZF_LANES), BGZF_WORK_BYTES, st[s], d_in[s], (int64_t)bytes, nb, d_tok[s], d_slices[s], d_meta[s]);
+		ARX_BGZF_CHECK(hipGetLastError());
+		hipLaunchKernelGGL(k_bgzf_frame, dim3(nb), dim3(256), 0, st[s], d_slices[s], d_meta[s], nb, d_packed[s]);
+		ARX_BGZF_CHECK(hipGetLastError());
+		ARX_BGZF_CHECK(hipMemcpyAsync(h_meta[s], d_meta[s], (size_t)nb * 16, hipMemcpyDeviceToHost, st[s]));
+		ARX_BGZF_CHECK(hipEventRecord(ev_meta[s], st[s]));
+	}
+	// the sizes of group g are known: its framed bytes on their way back -> their number
+	size_t fetch(size_t g, int nb)
+	{
+		const int s = (int)(g & 1);
+		ARX_BGZF_CHECK(hipEventSynchronize(ev_meta[s]));
+		size_t bytes = 0;
+		for (int b = 0; b < nb; ++b) {
+			const uint32_t *m = h_meta[s] + 4 * (size_t)b;
+			if (m[0] > 5u + BGZF_IN || m[2] > 2u) throw std::runtime_error("the BGZF kernel reported an impossible block");
+			bytes += m[0] + 26; ++n_form[m[2]];
+		}
+		ARX_BGZF_CHECK(hipMemcpyAsync(h_out[s], d_packed[s], bytes, hipMemcpyDeviceToHost, st[s]));
+		ARX_BGZF_CHECK(hipEventRecord(ev_pay[s], st[s]));
+		return bytes;
+	}
+
+	// sink(bytes, n): n framed bytes, in order
+	template <class Sink> void compress(const uint8_t *src, size_t total, Sink sink)
+	{
+		if (!ready) throw std::runtime_error("the device compressor is not initialised");
+		if (!total) return;
+		ARX_BGZF_CHECK(hipSetDevice(dev)); // the current device is per host thread and is left set: every entry of the library that touches the GPU binds its own first
+		const size_t per = (size_t)GROUP * BGZF_IN, ng = (total + per - 1) / per;
+		auto blocks_of = [&](size_t g) { const size_t bytes = total - g * per < per ? total - g * per : per; return (int)((bytes + BGZF_IN - 1) / BGZF_IN); };
+		auto drain = [&](size_t g) {
+			const size_t bytes = fetch(g, blocks_of(g));
+			ARX_BGZF_CHECK(hipEventSynchronize(ev_pay[g & 1]));
+			sink(h_out[g & 1], bytes);
+		};
+		try {
+			submit(src, total, 0);
+			for (size_t g = 1; g < ng; ++g) { submit(src, total, g); drain(g - 1); }
+			drain(ng - 1);
+		} catch (...) {
+			(void)hipStreamSynchronize(st[0]); (void)hipStreamSynchronize(st[1]); // nothing of this flush stays in flight
+			throw;
+		}
+	}
+
+	bool run(const uint8_t *src, size_t total, FILE *f, int64_t &bytes_out, std::string &error) override
+	{
+		try {
+			std::lock_guard<std::mutex> lock(mu);
+			bool ok = true;
+			compress(src, total, [&](const uint8_t *p, size_t n) {
+				if (ok && fwrite(p, 1, n, f) != n) { ok = false; error = "write failed"; }
+				if (ok) bytes_out += (int64_t)n;
+			});
+			return ok;
+		} catch (const std::exception &e) {
+			error = e.what();
+			return false;
+		}
+	}
+};
+
+} // namespace arx

@@ -36,24 +36,30 @@ _TRACE = bool(os.environ.get("ARX_E2E_TRACE"))
 
 def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int = 250_000, bam_threads: int = 8, rec_threads: int = 8, level: int = 1,
         penalty: float = -4, lib_path: str = api.LIB_PATH, warm_passes: int = 0, layout: str = "workers", chunk: int = 40_000_000,
-        read_groups: str = "", sample_id: str = "", feeder: str = "host", workers: int = 3, chunk_bytes: int = 0):
+        read_groups: str = "", sample_id: str = "", feeder: str = "host", workers: int = 3, chunk_bytes: int = 0,
+        sink: str = "host"):
     """fastq_pairs: [(r1, r2), ...] barcode-sorted files (plain or gzip), one worker each.  -> stats dict (pairs, seconds, pairs/s, per-stage
     seconds summed over workers).  warm_passes: untimed passes over the same files first, through the same batch handles -- a handle's first
     batch pays for its work memory (hipMalloc of several GiB: seconds once a 69 GB k-mer table sits beside it), which a run over a whole
     read set pays once; the stats are those of the last pass.  layout="reference": out_prefix is the output directory of the reference's
     layout (see the module docstring; chunk = -p/--partitions, read_groups / sample_id as the reference's flags); warm_passes must be 0.
     feeder="device": ONE file pair, parsed on the GPU by one feeder thread (arx_feeder_open_device) that hands super-batches to `workers`
-    worker threads (see _run_device); the default, feeder="host", is one host feeder and one worker per file pair."""
+    worker threads (see _run_device); the default, feeder="host", is one host feeder and one worker per file pair.
+    sink="device": every BAM writer, in both layouts, compresses its BGZF blocks on ref's GPU (arx_bam_open_device; `level` does not apply); the
+    files inflate to the same bytes as with the default, sink="host"."""
+    if sink not in ("host", "device"):
+        raise ValueError(f"unknown sink {sink!r}")
+    sink_dev = ref if sink == "device" else None
     if feeder == "device":
         if warm_passes:
             raise ValueError("feeder='device' reads its file pair once: warm_passes must be 0")
-        return _run_device(ref, fastq_pairs, out_prefix, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, layout, chunk, read_groups, workers, chunk_bytes)
+        return _run_device(ref, fastq_pairs, out_prefix, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, layout, chunk, read_groups, workers, chunk_bytes, sink_dev)
     if feeder != "host":
         raise ValueError(f"unknown feeder {feeder!r}")
     if layout == "reference":
         if warm_passes:
             raise ValueError("layout='reference' writes its files once: warm_passes must be 0")
-        return _run_reference(ref, fastq_pairs, out_prefix, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, chunk, read_groups, sample_id)
+        return _run_reference(ref, fastq_pairs, out_prefix, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, chunk, read_groups, sample_id, sink_dev)
     if layout != "workers":
         raise ValueError(f"unknown layout {layout!r}")
     names, offs, clens, alt, l_pac = ref.contigs()
@@ -83,7 +89,7 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
     def one_pass(k, r1, r2, batch, buf, rb, counted):
         if True:
             fd = api.Feeder(r1, r2, lib_path=lib_path)
-            bam = api.BamWriter(f"{out_prefix}.{k}.bam", names, clens, extra_header="@PG\tID:arachne_amd\n", threads=bam_threads, level=level, lib_path=lib_path)
+            bam = api.BamWriter(f"{out_prefix}.{k}.bam", names, clens, extra_header="@PG\tID:arachne_amd\n", threads=bam_threads, level=level, lib_path=lib_path, device=sink_dev)
             loc = dict(pairs=0, records=0, batches=0, feeder_s=0.0, device_s=0.0, fetch_s=0.0, records_s=0.0, bam_s=0.0)
             # the worker's BamThread (bamwriter.go:615-658): record views are compressed and written by a thread of their own while the worker
             # goes on with the next barcode sets; a view's record buffer is reused two batches later, when its write has returned
@@ -189,13 +195,13 @@ def reference_header(read_groups: str = "", date: str | None = None) -> str:
     return out + "@PG\tID:arachne\tPN:arachne\tCL:arachne_amd\n"
 
 
-def _run_reference(ref, fastq_pairs, out_dir, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, chunk, read_groups, sample_id):
+def _run_reference(ref, fastq_pairs, out_dir, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, chunk, read_groups, sample_id, sink_dev=None):
     names, offs, clens, alt, l_pac = ref.contigs()
     table = api.bucket_table(names, clens, chunk, lib_path=lib_path)
     os.makedirs(out_dir, exist_ok=True)
     hdr = reference_header(read_groups)
     files = ["bc_sorted_bam.bam"] + table.files
-    writers = [api.BamWriter(os.path.join(out_dir, f), names, clens, extra_header=hdr, threads=bam_threads, level=level, lib_path=lib_path) for f in files]
+    writers = [api.BamWriter(os.path.join(out_dir, f), names, clens, extra_header=hdr, threads=bam_threads, level=level, lib_path=lib_path, device=sink_dev) for f in files]
     locks = [threading.Lock() for _ in writers]
     stats = dict(pairs=0, records=0, batches=0, feeder_s=0.0, device_s=0.0, fetch_s=0.0, records_s=0.0, bam_s=0.0)
     slock = threading.Lock()
@@ -269,7 +275,7 @@ def _run_reference(ref, fastq_pairs, out_dir, pairs_per_batch, bam_threads, rec_
     return stats
 
 
-def _run_device(ref, fastq_pairs, out, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, layout, chunk, read_groups, workers, chunk_bytes):
+def _run_device(ref, fastq_pairs, out, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, layout, chunk, read_groups, workers, chunk_bytes, sink_dev=None):
     """One file pair, the reference's shape (aligner.go:335-358): ONE producer -- the device feeder, whose parse runs on the GPU -- puts
     super-batches into a queue, `workers` threads take them, each with its own batch handle (arx_batch_reset_device from the feeder's device
     arrays: the bases never come back to the host for the path's sake) and everything after that as in the host-feeder loops above.
@@ -290,10 +296,10 @@ def _run_device(ref, fastq_pairs, out, pairs_per_batch, bam_threads, rec_threads
         os.makedirs(out, exist_ok=True)
         files = ["bc_sorted_bam.bam"] + table.files
         hdr = reference_header(read_groups)
-        writers = [api.BamWriter(os.path.join(out, f), names, clens, extra_header=hdr, threads=bam_threads, level=level, lib_path=lib_path) for f in files]
+        writers = [api.BamWriter(os.path.join(out, f), names, clens, extra_header=hdr, threads=bam_threads, level=level, lib_path=lib_path, device=sink_dev) for f in files]
     else:
         files = [f"{out}.{k}.bam" for k in range(workers)]
-        writers = [api.BamWriter(f, names, clens, extra_header="@PG\tID:arachne_amd\n", threads=bam_threads, level=level, lib_path=lib_path) for f in files]
+        writers = [api.BamWriter(f, names, clens, extra_header="@PG\tID:arachne_amd\n", threads=bam_threads, level=level, lib_path=lib_path, device=sink_dev) for f in files]
     locks = [threading.Lock() for _ in writers]
     stats = dict(pairs=0, records=0, batches=0, feeder_s=0.0, device_s=0.0, fetch_s=0.0, records_s=0.0, bam_s=0.0)
     slock = threading.Lock()

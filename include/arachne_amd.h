@@ -70,6 +70,7 @@ const char *arx_backend(void);                 /* "hip:gfx950" for the product l
  * forward extensions (0: none); [3] rows per resident suffix-array entry (1: the whole array); [4] 1 if the inverse suffix array is resident
  * (text mode of the seeding passes); [5] bytes of device memory the index holds; [6], [7] reserved (0) */
 int arx_index_info(arx_ctx *ctx, int64_t *info /* 8 */);
+int arx_ctx_device(arx_ctx *ctx);               /* the device ordinal ctx was opened on (-1: ctx is NULL) */
 
 /* Page-locks host memory the caller hands to arx_batch_create / arx_batch_reset (bases) or receives results in (arx_batch_fetch,
  * arx_batch_rfa_fetch, arx_batch_post_fetch), for as long as it keeps reusing those arrays: copies then run at PCIe speed without a
@@ -253,6 +254,18 @@ int arx_bam_write_select(arx_bam *w, const arx_bam_batch *batch, const int64_t *
 /* stats[4] (may be NULL): records, BGZF blocks, uncompressed bytes, file bytes */
 int arx_bam_close(arx_bam *w, int64_t *stats);
 const char *arx_bam_error(arx_bam *w);
+/* arx_bam_open whose BGZF blocks are compressed and checksummed on ctx's GPU (csrc/dev_bgzf.h, hip_bgzf.h): records are still encoded on
+ * `threads` host threads; the stream is cut into blocks exactly where arx_bam_open's writer cuts it (every 65280 bytes; the header ends
+ * its own block, the last block is partial, then the 28-byte EOF block) and every block goes through HIP kernels that produce a raw
+ * DEFLATE stream -- greedy LZ77 parse, a length-limited dynamic Huffman code per block, or the fixed code or a stored block where that
+ * is smaller: the size is known before a byte is written -- and the CRC-32 of the input, framed on the device and written in order.
+ * After inflation the file is byte for byte arx_bam_open's; the compressed bytes are a function of the block's input only (not of batch
+ * sizes, `threads`, the other blocks of a launch or the run).  There is no level.  The writers of one device share one set of streams, page-locked staging and
+ * device buffers (about 64 MB and 100 MB), allocated by the first of them and kept until the process ends; their flushes take turns.  arx_bam_write, arx_bam_write_select, arx_bam_close (stats as above) and arx_bam_error take the handle as
+ * they take arx_bam_open's.  ARX_E_ARG: ctx is NULL; ARX_E_IO: the file cannot be written; ARX_E_DEVICE: no GPU, or a HIP error (msg
+ * says which; after open such errors surface as ARX_E_IO of the call with the text in arx_bam_error).  Never aborts. */
+int arx_bam_open_device(arx_ctx *ctx, const char *path, int32_t n_contigs, const char *const *names, const int32_t *lens, const char *extra_header,
+                        int32_t threads, arx_bam **out, char *msg, int32_t msg_cap);
 
 /* ---- between the path and the sink: the placed candidate of every read of a super-batch as BAM records -- the part of DumpToBams /
  * AppendBam (src/aligner/bamwriter.go:283-568, 635-658) that decides flags, position, MAPQ, mate fields, template length, CIGAR op codes,
@@ -329,6 +342,12 @@ int arx_batch_debug_core(arx_ctx *ctx, arx_batch *b, int32_t *n_core, arx_reg *r
  * against the one-thread ks_introsort, on n_cases random index arrays of 2..832 entries whose keys come from small ranges, so that ties
  * abound.  *n_bad = arrays on which the two differ. */
 int arx_selftest_wave_sort(int32_t device, int32_t n_cases, int64_t seed, int64_t *n_bad);
+
+/* self-test of the device sink's kernels on arbitrary bytes, no index needed (tests/test_bgzf_device_gpu.py): src[0..n) is cut every 65280
+ * bytes as the sink cuts its stream and goes through the kernels of arx_bam_open_device; out[0..*out_len) receives the framed BGZF blocks
+ * in order, without the EOF block (cap: bytes of out; n + 31 * blocks always suffice; ARX_E_ARG if it is too small).  stats[4] (may be
+ * NULL): blocks, and how many of them went out stored, with the fixed code, with a dynamic code.  n = 0: no block, *out_len = 0. */
+int arx_selftest_bgzf(int32_t device, const uint8_t *src, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, int64_t *stats);
 
 /* self-tests of the three DP kernel families on plain host arrays (csrc/arx_selftest.hip; tests/test_dp_kernels_gpu.py): each entry
  * uploads the tasks, launches the production code on them and returns one result row per task, in input order.  The reference text is
