@@ -96,7 +96,7 @@ template <> void HipRT::run_rescue_heavy<KRescueStep>(const char *nm, int n, con
 {
 	if (n <= 0) return;
 	const int wave = sw.rescue_wave, split = sw.rescue_lds_classes; // split: three launches by LDS footprint instead of one (measured slower: switches.h)
-	if (!rescue_heavy_attr_set) { ARX_HIP_CHECK(hipFuncSetAttribute((const void *)k_rescue_heavy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(RESCUE_LDS_REGS * sizeof(Reg)))); rescue_heavy_attr_set = true; }
+	allow_dynamic_lds(k_rescue_heavy, RESCUE_LDS_REGS * sizeof(Reg));
 	int32_t *cur = alloc<int32_t>(4);
 	memset0(cur, 16);
 	on_aux([&]() { // beside the thread-per-pair launch of the same round (the caller joins before it reads the round's task count)
@@ -106,9 +106,8 @@ template <> void HipRT::run_rescue_heavy<KRescueStep>(const char *nm, int n, con
 		for (int c = 2; c >= 0; --c) { // the longest first: their tail is what the launch ends on
 			if (caps[c + 1] <= caps[c]) continue;
 			const int per_cu = c == 0 ? 5 : c == 1 ? 3 : 2, blocks = n < n_cu * per_cu ? n : n_cu * per_cu;
-			hipLaunchKernelGGL(k_rescue_heavy, dim3(blocks), dim3(64), (size_t)caps[c + 1] * sizeof(Reg), stream, f, list, n, wave, caps[c], caps[c + 1], cur + c);
+			start({"k_rescue_heavy", nm, c}, k_rescue_heavy, dim3(blocks), dim3(64), (size_t)caps[c + 1] * sizeof(Reg), f, list, n, wave, caps[c], caps[c + 1], cur + c);
 		}
-		ARX_HIP_CHECK(hipGetLastError());
 	});
 	wsort_report(stream, nm);
 #ifdef ARX_WAVE_STATS
@@ -189,13 +188,11 @@ template <> void HipRT::run_chain_heavy<KChain>(const char *nm, int n_reads, con
 	Scope sc(*this, nm, n_reads);
 	const int wave = sw.chain_wave;
 	static const size_t lds_s = ChainLds::bytes(CHAIN_LDS_SMALL), lds_l = ChainLds::bytes(CHAIN_LDS_OCC);
-	// the opt-in applies to the device that is current when it is made: once per runtime (= per device context), not once per process
-	if (!chain_heavy_attr_set) { ARX_HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_heavy, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_l)); chain_heavy_attr_set = true; }
+	allow_dynamic_lds(k_chain_heavy, lds_l); // 128 KB
 	// f.n_heavy[0]: the list's length (stays on the device), [1] and [2]: the two launches' cursors into it
 	const int l_div = sw.chain_l_div; // the long ones' launch holds 128 KB of LDS per workgroup: on n_cu / l_div CUs
-	on_aux([&]() { hipLaunchKernelGGL(k_chain_heavy, dim3(n_cu / (l_div > 0 ? l_div : 1)), dim3(64), lds_l, stream, f, CHAIN_LDS_SMALL + 1, CHAIN_LDS_OCC, f.n_heavy + 2, wave); }); // the few long ones (beside the rest with ARX_AUX_STREAM=1)
-	hipLaunchKernelGGL(k_chain_heavy, dim3(n_cu * 4), dim3(64), lds_s, stream, f, 0, CHAIN_LDS_SMALL, f.n_heavy + 1, wave); // (a third launch for reads of up to 128 occurrences at half the LDS changed nothing: round 3)
-	ARX_HIP_CHECK(hipGetLastError());
+	on_aux([&]() { start("k_chain_heavy (long)", k_chain_heavy, dim3(n_cu / (l_div > 0 ? l_div : 1)), dim3(64), lds_l, f, CHAIN_LDS_SMALL + 1, CHAIN_LDS_OCC, f.n_heavy + 2, wave); }); // the few long ones (beside the rest with ARX_AUX_STREAM=1)
+	start("k_chain_heavy (short)", k_chain_heavy, dim3(n_cu * 4), dim3(64), lds_s, f, 0, CHAIN_LDS_SMALL, f.n_heavy + 1, wave); // (a third launch for reads of up to 128 occurrences at half the LDS changed nothing: round 3)
 	aux_join();
 #ifdef ARX_CHAIN_STATS
 	{ unsigned long long h[24], z[24] = {0}; hipStreamSynchronize(stream); hipMemcpyFromSymbol(h, HIP_SYMBOL(g_cstat), sizeof h); hipMemcpyToSymbol(HIP_SYMBOL(g_cstat), z, sizeof z);
@@ -247,7 +244,7 @@ template <> void HipRT::run_chain_group<KChain>(const char *nm, int n_reads, con
 	if (f.grp_max < 1 || n_reads <= 0) return;
 	Scope sc(*this, nm, n_reads);
 	static const size_t lds_cu = 160 << 10; // LDS of one CU: the workgroups a CU holds are what this latency-bound kernel scales with
-	if (!chain_group_attr_set) { ARX_HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_g16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * ChainLds::group_bytes(CHAIN_G16_MAX)))); chain_group_attr_set = true; }
+	allow_dynamic_lds(k_chain_g16, 4 * ChainLds::group_bytes(CHAIN_G16_MAX)); // above 64 KB when ARX_CHAIN_HEAVY_MIN is raised
 	// two classes by LDS footprint: 1-16 occurrences (11 KB per workgroup: 14 per CU) and 17 .. grp_max (36 KB at 63: 4 per CU)
 	const int tiles = (n_reads + 15) / 16;
 	for (int c = 0; c < 2; ++c) {
@@ -255,10 +252,8 @@ template <> void HipRT::run_chain_group<KChain>(const char *nm, int n_reads, con
 		if (c == 1 && cap < lo) continue;
 		const size_t lds = 4 * ChainLds::group_bytes(cap < lo ? lo : cap);
 		const int per_cu = lds_cu / lds < 16 ? (int)(lds_cu / lds) : 16, blocks = c == 1 || (tiles + 3) / 4 > n_cu * per_cu ? n_cu * per_cu : (tiles + 3) / 4;
-		hipLaunchKernelGGL(k_chain_g16, dim3(blocks), dim3(64), lds, stream, f, n_reads, lo, cap, c == 0 ? (const int32_t *)nullptr : (const int32_t *)f.mid_list,
-		                   (const int32_t *)f.n_mid);
+		start({"k_chain_g16", nm, c}, k_chain_g16, dim3(blocks), dim3(64), lds, f, n_reads, lo, cap, c == 0 ? nullptr : f.mid_list, f.n_mid);
 	}
-	ARX_HIP_CHECK(hipGetLastError());
 }
 
 // One read with a long region list per 64-lane workgroup: the list goes to LDS, the wavefront runs mem_sort_dedup_patch on it
@@ -298,15 +293,14 @@ template <> void HipRT::run_dedup_heavy<KDedup>(const char *nm, int n_reads, con
 	Scope sc(*this, nm, n_reads);
 	const int blocks = n_cu * 4;
 	int32_t *eh_pool = alloc<int32_t>((size_t)blocks * f.eh_words + 16);
-	hipLaunchKernelGGL(k_dedup_heavy, dim3(blocks), dim3(64), 0, stream, f, eh_pool);
-	ARX_HIP_CHECK(hipGetLastError());
+	start("k_dedup_heavy", k_dedup_heavy, dim3(blocks), dim3(64), 0, f, eh_pool);
 	wsort_report(stream, nm);
 }
 
 template <class F> struct ColdUsesSlots { static const bool value = true; };
 template <> struct ColdUsesSlots<KRescueStep> { static const bool value = false; }; // no per-slot scratch: may take one item per lane
 template <class F> void HipRT::launch_cold(const char *nm, int n, const F &f) { launch_cold_impl(nm, n, f, !ColdUsesSlots<F>::value); }
-void HipRT::merge_sort_fail_cold(uint32_t *err) { hipLaunchKernelGGL(k_merge_sort_fail, dim3(1), dim3(1), 0, stream, err); } // this unit's copy of the flag
+void HipRT::merge_sort_fail_cold(uint32_t *err) { start("k_merge_sort_fail (cold unit)", k_merge_sort_fail, dim3(1), dim3(1), 0, err); } // this unit's copy of the flag
 template void HipRT::launch_cold<KDedup>(const char *, int, const KDedup &);
 template void HipRT::launch_cold<KRescueStep>(const char *, int, const KRescueStep &);
 
@@ -353,8 +347,8 @@ extern "C" int arx_selftest_wave_sort(int32_t device, int32_t n_cases, int64_t s
 	int rc = ARX_OK;
 	if (hipMemset(d, 0, 8) != hipSuccess) rc = ARX_E_DEVICE;
 	if (rc == ARX_OK && n_cases > 0) {
-		hipLaunchKernelGGL(arx::k_selftest_wsort, dim3(n_cases < 4096 ? n_cases : 4096), dim3(64), 0, 0, n_cases, (uint64_t)seed, d);
-		if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = ARX_E_DEVICE;
+		try { arx::hip_launch("k_selftest_wsort", arx::k_selftest_wsort, dim3(n_cases < 4096 ? n_cases : 4096), dim3(64), 0, 0, n_cases, seed, d); } catch (const arx::HipError &) { rc = ARX_E_DEVICE; }
+		if (rc == ARX_OK && hipDeviceSynchronize() != hipSuccess) rc = ARX_E_DEVICE;
 	}
 	if (rc == ARX_OK && hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = ARX_E_DEVICE;
 	(void)hipFree(d);

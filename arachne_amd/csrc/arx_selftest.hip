@@ -172,18 +172,12 @@ extern "C" int arx_selftest_gen_cigar(int32_t device, int32_t n, const uint8_t *
 		rt.memset_bytes(dout, 0x80, (size_t)n * 16);
 		rt.memset0(dcig, (size_t)n * cig_w * 4);
 		const int blocks = (n + 3) / 4 < rt.n_cu * 4 ? (n + 3) / 4 : rt.n_cu * 4;
-#define ARX_NW_SELFTEST(LO_, HI_) hipLaunchKernelGGL((k_selftest_gen_cigar<LO_, HI_>), dim3(blocks), dim3(64), 0, rt.stream, dq, di, di + n, dt, di + 2 * (size_t)n, \
-                                                    di + 3 * (size_t)n, di + 4 * (size_t)n, di + 5 * (size_t)n, cig_w, dz, dzo, n, dout, dcig)
-		switch (klass) { // the instantiations of HipRT::run_reg2aln_nw
-		case 0: ARX_NW_SELFTEST(1, 2); break;
-		case 1: ARX_NW_SELFTEST(2, 4); break;
-		case 2: ARX_NW_SELFTEST(4, 8); break;
-		case 3: ARX_NW_SELFTEST(8, 16); break;
-		case 4: ARX_NW_SELFTEST(16, 16); break;
-		default: ARX_NW_SELFTEST(1, 16); break;
-		}
-#undef ARX_NW_SELFTEST
-		ARX_HIP_CHECK(hipGetLastError());
+		// the instantiations of HipRT::run_reg2aln_nw: its five class kernels and the one that holds every tiling
+		using Kernel = decltype(&k_selftest_gen_cigar<1, 2>);
+		static constexpr Kernel by_class[6] = {k_selftest_gen_cigar<1, 2>, k_selftest_gen_cigar<2, 4>, k_selftest_gen_cigar<4, 8>, k_selftest_gen_cigar<8, 16>,
+		                                       k_selftest_gen_cigar<16, 16>, k_selftest_gen_cigar<1, 16>};
+		rt.start("k_selftest_gen_cigar", by_class[klass], dim3(blocks), dim3(64), 0, dq, di, di + n, dt, di + 2 * (size_t)n, di + 3 * (size_t)n, di + 4 * (size_t)n,
+		         di + 5 * (size_t)n, cig_w, dz, dzo, n, dout, dcig);
 		ARX_HIP_CHECK(hipStreamSynchronize(rt.stream));
 		rt.d2h(out4, dout, (size_t)n * 16);
 		rt.d2h(cigar, dcig, (size_t)n * cig_w * 4);

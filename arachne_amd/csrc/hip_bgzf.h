@@ -16,13 +16,12 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include "hip_launch.h"
 #include "dev_bgzf.h"
 #include "hip_block.h"
 #include "bam_sink.h"
 
 namespace arx {
-
-#define ARX_BGZF_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw std::runtime_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 struct BgzfHipDrv { // dev_bgzf.h's driver on a workgroup
 	HipBlockT<BGZF_LANES, 1> blk;
@@ -93,24 +92,24 @@ struct DeviceBgzf : BlockCompressor {
 		if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw std::runtime_error("no HIP device visible: the device BAM sink needs an MI355X (there is no CPU fallback)");
 		if (device < 0 || device >= n) throw std::runtime_error("device index out of range");
 		dev = device;
-		ARX_BGZF_CHECK(hipSetDevice(dev));
+		ARX_HIP_CHECK(hipSetDevice(dev));
 		hipDeviceProp_t p;
-		ARX_BGZF_CHECK(hipGetDeviceProperties(&p, dev));
+		ARX_HIP_CHECK(hipGetDeviceProperties(&p, dev));
 		n_cu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
 		grid = n_cu < GROUP ? n_cu : GROUP; // one workgroup per CU: its LDS does not leave room for two
-		ARX_BGZF_CHECK(hipFuncSetAttribute((const void *)k_bgzf_deflate, hipFuncAttributeMaxDynamicSharedMemorySize, BGZF_WORK_BYTES));
+		ARX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bgzf_deflate, hipFuncAttributeMaxDynamicSharedMemorySize, BGZF_WORK_BYTES));
 		for (int s = 0; s < 2; ++s) {
-			ARX_BGZF_CHECK(hipStreamCreateWithFlags(&st[s], hipStreamNonBlocking));
-			ARX_BGZF_CHECK(hipEventCreateWithFlags(&ev_meta[s], hipEventDisableTiming));
-			ARX_BGZF_CHECK(hipEventCreateWithFlags(&ev_pay[s], hipEventDisableTiming));
-			ARX_BGZF_CHECK(hipHostMalloc((void **)&h_in[s], (size_t)GROUP * BGZF_IN, hipHostMallocDefault));
-			ARX_BGZF_CHECK(hipHostMalloc((void **)&h_out[s], (size_t)GROUP * BGZF_OUT_SLICE, hipHostMallocDefault));
-			ARX_BGZF_CHECK(hipHostMalloc((void **)&h_meta[s], (size_t)GROUP * 16, hipHostMallocDefault));
-			ARX_BGZF_CHECK(hipMalloc((void **)&d_in[s], (size_t)GROUP * BGZF_IN));
-			ARX_BGZF_CHECK(hipMalloc((void **)&d_slices[s], (size_t)GROUP * BGZF_OUT_SLICE));
-			ARX_BGZF_CHECK(hipMalloc((void **)&d_packed[s], (size_t)GROUP * BGZF_OUT_SLICE));
-			ARX_BGZF_CHECK(hipMalloc((void **)&d_meta[s], (size_t)GROUP * 16));
-			ARX_BGZF_CHECK(hipMalloc((void **)&d_tok[s], (size_t)grid * BGZF_TOK_ROW * 2));
+			ARX_HIP_CHECK(hipStreamCreateWithFlags(&st[s], hipStreamNonBlocking));
+			ARX_HIP_CHECK(hipEventCreateWithFlags(&ev_meta[s], hipEventDisableTiming));
+			ARX_HIP_CHECK(hipEventCreateWithFlags(&ev_pay[s], hipEventDisableTiming));
+			ARX_HIP_CHECK(hipHostMalloc((void **)&h_in[s], (size_t)GROUP * BGZF_IN, hipHostMallocDefault));
+			ARX_HIP_CHECK(hipHostMalloc((void **)&h_out[s], (size_t)GROUP * BGZF_OUT_SLICE, hipHostMallocDefault));
+			ARX_HIP_CHECK(hipHostMalloc((void **)&h_meta[s], (size_t)GROUP * 16, hipHostMallocDefault));
+			ARX_HIP_CHECK(hipMalloc((void **)&d_in[s], (size_t)GROUP * BGZF_IN));
+			ARX_HIP_CHECK(hipMalloc((void **)&d_slices[s], (size_t)GROUP * BGZF_OUT_SLICE));
+			ARX_HIP_CHECK(hipMalloc((void **)&d_packed[s], (size_t)GROUP * BGZF_OUT_SLICE));
+			ARX_HIP_CHECK(hipMalloc((void **)&d_meta[s], (size_t)GROUP * 16));
+			ARX_HIP_CHECK(hipMalloc((void **)&d_tok[s], (size_t)grid * BGZF_TOK_ROW * 2));
 		}
 		ready = true;
 	}
@@ -136,27 +135,25 @@ struct DeviceBgzf : BlockCompressor {
 		const size_t b0 = g * GROUP * (size_t)BGZF_IN, bytes = total - b0 < (size_t)GROUP * BGZF_IN ? total - b0 : (size_t)GROUP * BGZF_IN;
 		const int nb = (int)((bytes + BGZF_IN - 1) / BGZF_IN);
 		memcpy(h_in[s], src + b0, bytes);
-		ARX_BGZF_CHECK(hipMemcpyAsync(d_in[s], h_in[s], bytes, hipMemcpyHostToDevice, st[s]));
-		hipLaunchKernelGGL(k_bgzf_deflate, dim3(nb < grid ? nb : grid), dim3(BGZF_LANES), BGZF_WORK_BYTES, st[s], d_in[s], (int64_t)bytes, nb, d_tok[s], d_slices[s], d_meta[s]);
-		ARX_BGZF_CHECK(hipGetLastError());
-		hipLaunchKernelGGL(k_bgzf_frame, dim3(nb), dim3(256), 0, st[s], d_slices[s], d_meta[s], nb, d_packed[s]);
-		ARX_BGZF_CHECK(hipGetLastError());
-		ARX_BGZF_CHECK(hipMemcpyAsync(h_meta[s], d_meta[s], (size_t)nb * 16, hipMemcpyDeviceToHost, st[s]));
-		ARX_BGZF_CHECK(hipEventRecord(ev_meta[s], st[s]));
+		ARX_HIP_CHECK(hipMemcpyAsync(d_in[s], h_in[s], bytes, hipMemcpyHostToDevice, st[s]));
+		hip_launch("k_bgzf_deflate", k_bgzf_deflate, dim3(nb < grid ? nb : grid), dim3(BGZF_LANES), BGZF_WORK_BYTES, st[s], d_in[s], bytes, nb, d_tok[s], d_slices[s], d_meta[s]);
+		hip_launch("k_bgzf_frame", k_bgzf_frame, dim3(nb), dim3(256), 0, st[s], d_slices[s], d_meta[s], nb, d_packed[s]);
+		ARX_HIP_CHECK(hipMemcpyAsync(h_meta[s], d_meta[s], (size_t)nb * 16, hipMemcpyDeviceToHost, st[s]));
+		ARX_HIP_CHECK(hipEventRecord(ev_meta[s], st[s]));
 	}
 	// the sizes of group g are known: its framed bytes on their way back -> their number
 	size_t fetch(size_t g, int nb)
 	{
 		const int s = (int)(g & 1);
-		ARX_BGZF_CHECK(hipEventSynchronize(ev_meta[s]));
+		ARX_HIP_CHECK(hipEventSynchronize(ev_meta[s]));
 		size_t bytes = 0;
 		for (int b = 0; b < nb; ++b) {
 			const uint32_t *m = h_meta[s] + 4 * (size_t)b;
 			if (m[0] > 5u + BGZF_IN || m[2] > 2u) throw std::runtime_error("the BGZF kernel reported an impossible block");
 			bytes += m[0] + 26; ++n_form[m[2]];
 		}
-		ARX_BGZF_CHECK(hipMemcpyAsync(h_out[s], d_packed[s], bytes, hipMemcpyDeviceToHost, st[s]));
-		ARX_BGZF_CHECK(hipEventRecord(ev_pay[s], st[s]));
+		ARX_HIP_CHECK(hipMemcpyAsync(h_out[s], d_packed[s], bytes, hipMemcpyDeviceToHost, st[s]));
+		ARX_HIP_CHECK(hipEventRecord(ev_pay[s], st[s]));
 		return bytes;
 	}
 
@@ -165,12 +162,12 @@ struct DeviceBgzf : BlockCompressor {
 	{
 		if (!ready) throw std::runtime_error("the device compressor is not initialised");
 		if (!total) return;
-		ARX_BGZF_CHECK(hipSetDevice(dev)); // the current device is per host thread and is left set: every entry of the library that touches the GPU binds its own first
+		ARX_HIP_CHECK(hipSetDevice(dev)); // the current device is per host thread and is left set: every entry of the library that touches the GPU binds its own first
 		const size_t per = (size_t)GROUP * BGZF_IN, ng = (total + per - 1) / per;
 		auto blocks_of = [&](size_t g) { const size_t bytes = total - g * per < per ? total - g * per : per; return (int)((bytes + BGZF_IN - 1) / BGZF_IN); };
 		auto drain = [&](size_t g) {
 			const size_t bytes = fetch(g, blocks_of(g));
-			ARX_BGZF_CHECK(hipEventSynchronize(ev_pay[g & 1]));
+			ARX_HIP_CHECK(hipEventSynchronize(ev_pay[g & 1]));
 			sink(h_out[g & 1], bytes);
 		};
 		try {

@@ -36,12 +36,11 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include "hip_launch.h"
 #include "switches.h"
 
 namespace arx {
 namespace gpuidx {
-
-#define ARX_IDX_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw std::runtime_error(std::string("index build: ") + #x + ": " + hipGetErrorString(e_)); } while (0)
 
 struct DevBuf {
 	void *p = nullptr; size_t bytes = 0;
@@ -261,38 +260,38 @@ struct Scratch { // rocprim temporary storage, grown on demand
 inline void scan_max(Scratch &sc, u64 *data, u64 cnt, hipStream_t st)
 {
 	size_t tb = 0;
-	ARX_IDX_CHECK(rocprim::inclusive_scan(nullptr, tb, data, data, (size_t)cnt, MaxOp(), st));
+	ARX_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb, data, data, (size_t)cnt, MaxOp(), st));
 	void *tmp = sc.get(tb);
-	ARX_IDX_CHECK(rocprim::inclusive_scan(tmp, tb, data, data, (size_t)cnt, MaxOp(), st));
+	ARX_HIP_CHECK(rocprim::inclusive_scan(tmp, tb, data, data, (size_t)cnt, MaxOp(), st));
 }
 inline void scan_incl_sum(Scratch &sc, u64 *data, u64 cnt, hipStream_t st)
 {
 	size_t tb = 0;
-	ARX_IDX_CHECK(rocprim::inclusive_scan(nullptr, tb, data, data, (size_t)cnt, rocprim::plus<u64>(), st));
+	ARX_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb, data, data, (size_t)cnt, rocprim::plus<u64>(), st));
 	void *tmp = sc.get(tb);
-	ARX_IDX_CHECK(rocprim::inclusive_scan(tmp, tb, data, data, (size_t)cnt, rocprim::plus<u64>(), st));
+	ARX_HIP_CHECK(rocprim::inclusive_scan(tmp, tb, data, data, (size_t)cnt, rocprim::plus<u64>(), st));
 }
 inline void scan_excl_sum(Scratch &sc, const u64 *in, u64 *out, u64 cnt, hipStream_t st)
 {
 	size_t tb = 0;
-	ARX_IDX_CHECK(rocprim::exclusive_scan(nullptr, tb, in, out, (u64)0, (size_t)cnt, rocprim::plus<u64>(), st));
+	ARX_HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, in, out, (u64)0, (size_t)cnt, rocprim::plus<u64>(), st));
 	void *tmp = sc.get(tb);
-	ARX_IDX_CHECK(rocprim::exclusive_scan(tmp, tb, in, out, (u64)0, (size_t)cnt, rocprim::plus<u64>(), st));
+	ARX_HIP_CHECK(rocprim::exclusive_scan(tmp, tb, in, out, (u64)0, (size_t)cnt, rocprim::plus<u64>(), st));
 }
 inline void sort_pairs(Scratch &sc, const u64 *kin, u64 *kout, const u64 *vin, u64 *vout, u64 cnt, int bits, hipStream_t st)
 {
 	size_t tb = 0;
 	if (bits < 1) bits = 1;
 	if (bits > 64) bits = 64;
-	ARX_IDX_CHECK(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, (size_t)cnt, 0u, (unsigned)bits, st));
+	ARX_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, (size_t)cnt, 0u, (unsigned)bits, st));
 	void *tmp = sc.get(tb);
-	ARX_IDX_CHECK(rocprim::radix_sort_pairs(tmp, tb, kin, kout, vin, vout, (size_t)cnt, 0u, (unsigned)bits, st));
+	ARX_HIP_CHECK(rocprim::radix_sort_pairs(tmp, tb, kin, kout, vin, vout, (size_t)cnt, 0u, (unsigned)bits, st));
 }
 inline u64 read_u64(const u64 *d, hipStream_t st)
 {
 	u64 v = 0;
-	ARX_IDX_CHECK(hipMemcpyAsync(&v, d, 8, hipMemcpyDeviceToHost, st));
-	ARX_IDX_CHECK(hipStreamSynchronize(st));
+	ARX_HIP_CHECK(hipMemcpyAsync(&v, d, 8, hipMemcpyDeviceToHost, st));
+	ARX_HIP_CHECK(hipStreamSynchronize(st));
 	return v;
 }
 inline int bits_for(u64 x) { int b = 0; while (b < 64 && (x >> b)) ++b; return b; } // smallest b with x < 2^b
@@ -302,10 +301,10 @@ inline void stream_to_file(FILE *o, const void *dev, size_t bytes, hipStream_t s
 {
 	const size_t CH = (size_t)64 << 20;
 	void *pin[2] = {nullptr, nullptr};
-	ARX_IDX_CHECK(hipHostMalloc(&pin[0], CH, hipHostMallocDefault));
-	ARX_IDX_CHECK(hipHostMalloc(&pin[1], CH, hipHostMallocDefault));
+	ARX_HIP_CHECK(hipHostMalloc(&pin[0], CH, hipHostMallocDefault));
+	ARX_HIP_CHECK(hipHostMalloc(&pin[1], CH, hipHostMallocDefault));
 	hipEvent_t ev[2];
-	ARX_IDX_CHECK(hipEventCreate(&ev[0])); ARX_IDX_CHECK(hipEventCreate(&ev[1]));
+	ARX_HIP_CHECK(hipEventCreate(&ev[0])); ARX_HIP_CHECK(hipEventCreate(&ev[1]));
 	size_t done = 0, issued = 0; int k = 0;
 	size_t len[2] = {0, 0};
 	bool ok = true;
@@ -342,7 +341,7 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 	try {
 		int ndev = 0;
 		if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return "no HIP device visible";
-		if (sw.device >= 0) ARX_IDX_CHECK(hipSetDevice(sw.device));
+		if (sw.device >= 0) ARX_HIP_CHECK(hipSetDevice(sw.device));
 		hipStream_t st = 0; // the null stream: this is a stand-alone tool step, not part of a batch
 		Timer tm;
 		Scratch sc;
@@ -351,10 +350,9 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 		DevBuf dT(n_tw * 8);
 		{
 			DevBuf dpac(pac_bytes + 8);
-			ARX_IDX_CHECK(hipMemcpy(dpac.p, pac, pac_bytes, hipMemcpyHostToDevice));
-			hipLaunchKernelGGL(k_pack_text, grid_for(n_tw), dim3(256), 0, st, dpac.as<uint8_t>(), l_pac, dT.as<u64>(), n_tw);
-			ARX_IDX_CHECK(hipGetLastError());
-			ARX_IDX_CHECK(hipStreamSynchronize(st));
+			ARX_HIP_CHECK(hipMemcpy(dpac.p, pac, pac_bytes, hipMemcpyHostToDevice));
+			hip_launch("k_pack_text", k_pack_text, grid_for(n_tw), dim3(256), 0, st, dpac.as<uint8_t>(), l_pac, dT.as<u64>(), n_tw);
+			ARX_HIP_CHECK(hipStreamSynchronize(st));
 		}
 		const u64 *T = dT.as<u64>();
 		S.s_text = tm.lap();
@@ -364,16 +362,14 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 		std::vector<u64> bstart(N_BUCKETS + 1);
 		{
 			DevBuf dh(N_BUCKETS * 8), dc(N_BUCKETS * 8);
-			ARX_IDX_CHECK(hipMemsetAsync(dh.p, 0, N_BUCKETS * 8, st));
-			hipLaunchKernelGGL(k_hist, grid_for(n), dim3(256), 0, st, T, n, dh.as<u64>());
-			ARX_IDX_CHECK(hipGetLastError());
+			ARX_HIP_CHECK(hipMemsetAsync(dh.p, 0, N_BUCKETS * 8, st));
+			hip_launch("k_hist", k_hist, grid_for(n), dim3(256), 0, st, T, n, dh.as<u64>());
 			scan_excl_sum(sc, dh.as<u64>(), dc.as<u64>(), N_BUCKETS, st);
-			ARX_IDX_CHECK(hipMemcpyAsync(bstart.data(), dc.p, N_BUCKETS * 8, hipMemcpyDeviceToHost, st));
-			ARX_IDX_CHECK(hipStreamSynchronize(st));
+			ARX_HIP_CHECK(hipMemcpyAsync(bstart.data(), dc.p, N_BUCKETS * 8, hipMemcpyDeviceToHost, st));
+			ARX_HIP_CHECK(hipStreamSynchronize(st));
 			bstart[N_BUCKETS] = n;
-			hipLaunchKernelGGL(k_scatter, grid_for(n), dim3(256), 0, st, T, n, dc.as<u64>(), SA);
-			ARX_IDX_CHECK(hipGetLastError());
-			ARX_IDX_CHECK(hipStreamSynchronize(st));
+			hip_launch("k_scatter", k_scatter, grid_for(n), dim3(256), 0, st, T, n, dc.as<u64>(), SA);
+			ARX_HIP_CHECK(hipStreamSynchronize(st));
 		}
 		S.s_bucket = tm.lap();
 		// 3. chunks of whole buckets
@@ -395,23 +391,21 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 				if (cnt == 0) continue;
 				++S.n_chunks;
 				u64 *k1 = dk1.as<u64>(), *k2 = dk2.as<u64>(), *v2 = dv2.as<u64>();
-				hipLaunchKernelGGL(k_keys, grid_for(cnt), dim3(256), 0, st, T, SA + base, cnt, k1);
+				hip_launch("k_keys", k_keys, grid_for(cnt), dim3(256), 0, st, T, SA + base, cnt, k1);
 				sort_pairs(sc, k1, k2, SA + base, v2, cnt, 64, st);
-				hipLaunchKernelGGL(k_heads, grid_for(cnt), dim3(256), 0, st, k2, cnt, base, k1);
+				hip_launch("k_heads", k_heads, grid_for(cnt), dim3(256), 0, st, k2, cnt, base, k1);
 				scan_max(sc, k1, cnt, st);                          // k1 = rank
-				hipLaunchKernelGGL(k_chunk_apply, grid_for(cnt), dim3(256), 0, st, v2, k1, cnt, base, SA, ISA, k2); // k2 = flag
-				ARX_IDX_CHECK(hipGetLastError());
+				hip_launch("k_chunk_apply", k_chunk_apply, grid_for(cnt), dim3(256), 0, st, v2, k1, cnt, base, SA, ISA, k2); // k2 = flag
 				const u64 last_flag = read_u64(k2 + cnt - 1, st);
 				scan_excl_sum(sc, k2, k1, cnt, st);                 // k1 = offsets
 				const u64 m = read_u64(k1 + cnt - 1, st) + last_flag;
 				if (m) {
 					Seg *sg = new Seg(); segs.push_back(sg);
 					sg->m = m; sg->pos.alloc(m * 8); sg->sa.alloc(m * 8);
-					hipLaunchKernelGGL(k_compact, grid_for(cnt), dim3(256), 0, st, k2, k1, cnt, base, v2, sg->pos.as<u64>(), sg->sa.as<u64>());
-					ARX_IDX_CHECK(hipGetLastError());
+					hip_launch("k_compact", k_compact, grid_for(cnt), dim3(256), 0, st, k2, k1, cnt, base, v2, sg->pos.as<u64>(), sg->sa.as<u64>());
 					m_total += m;
 				}
-				ARX_IDX_CHECK(hipStreamSynchronize(st));
+				ARX_HIP_CHECK(hipStreamSynchronize(st));
 			}
 		}
 		S.s_chunks = tm.lap(); S.unresolved0 = m_total;
@@ -425,11 +419,11 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 				upos[0].alloc(m * 8); usa[0].alloc(m * 8);
 				u64 o = 0;
 				for (Seg *sg : segs) {
-					ARX_IDX_CHECK(hipMemcpyAsync(upos[0].as<u64>() + o, sg->pos.p, sg->m * 8, hipMemcpyDeviceToDevice, st));
-					ARX_IDX_CHECK(hipMemcpyAsync(usa[0].as<u64>() + o, sg->sa.p, sg->m * 8, hipMemcpyDeviceToDevice, st));
+					ARX_HIP_CHECK(hipMemcpyAsync(upos[0].as<u64>() + o, sg->pos.p, sg->m * 8, hipMemcpyDeviceToDevice, st));
+					ARX_HIP_CHECK(hipMemcpyAsync(usa[0].as<u64>() + o, sg->sa.p, sg->m * 8, hipMemcpyDeviceToDevice, st));
 					o += sg->m;
 				}
-				ARX_IDX_CHECK(hipStreamSynchronize(st));
+				ARX_HIP_CHECK(hipStreamSynchronize(st));
 			}
 			for (Seg *sg : segs) delete sg;
 			segs.clear();
@@ -439,7 +433,7 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 				const int kb = bits_for(n + h);
 				DevBuf dr(m * 8);
 				u64 *r = dr.as<u64>();
-				hipLaunchKernelGGL(k_rank_of, grid_for(m), dim3(256), 0, st, usa[cur].as<u64>(), m, ISA, r);
+				hip_launch("k_rank_of", k_rank_of, grid_for(m), dim3(256), 0, st, usa[cur].as<u64>(), m, ISA, r);
 				// slices of whole groups, about slice_cap elements each (a group longer than that is one slice); the key of a slice
 				// is (group number in the slice) << kb | rank: the group number must fit in 64 - kb bits
 				u64 Sl = slice_cap;
@@ -448,10 +442,10 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 				std::vector<u64> bound(n_sl + 1);
 				{
 					DevBuf db(n_sl * 8);
-					ARX_IDX_CHECK(hipMemsetAsync(db.p, 0xff, n_sl * 8, st));
-					hipLaunchKernelGGL(k_slice_bounds, grid_for(m), dim3(256), 0, st, r, m, Sl, db.as<u64>());
-					ARX_IDX_CHECK(hipMemcpyAsync(bound.data(), db.p, n_sl * 8, hipMemcpyDeviceToHost, st));
-					ARX_IDX_CHECK(hipStreamSynchronize(st));
+					ARX_HIP_CHECK(hipMemsetAsync(db.p, 0xff, n_sl * 8, st));
+					hip_launch("k_slice_bounds", k_slice_bounds, grid_for(m), dim3(256), 0, st, r, m, Sl, db.as<u64>());
+					ARX_HIP_CHECK(hipMemcpyAsync(bound.data(), db.p, n_sl * 8, hipMemcpyDeviceToHost, st));
+					ARX_HIP_CHECK(hipStreamSynchronize(st));
 				}
 				std::vector<u64> cuts;
 				for (u64 k = 0; k < n_sl; ++k) if (bound[k] != ~0ull) cuts.push_back(bound[k]);
@@ -467,23 +461,21 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 					const u64 a = cuts[k], cnt = cuts[k + 1] - a;
 					u64 *A = da.as<u64>(), *B = dbb.as<u64>(), *Cc = dc.as<u64>(), *D = dd.as<u64>();
 					const u64 *sa_in = usa[cur].as<u64>() + a, *pos_in = upos[cur].as<u64>() + a;
-					hipLaunchKernelGGL(k_head_flags, grid_for(cnt), dim3(256), 0, st, r + a, cnt, A);
+					hip_launch("k_head_flags", k_head_flags, grid_for(cnt), dim3(256), 0, st, r + a, cnt, A);
 					scan_incl_sum(sc, A, cnt, st);                                                     // A = group number (1-based)
-					hipLaunchKernelGGL(k_comp_keys, grid_for(cnt), dim3(256), 0, st, sa_in, A, cnt, ISA, n, h, kb, B); // B = keys
+					hip_launch("k_comp_keys", k_comp_keys, grid_for(cnt), dim3(256), 0, st, sa_in, A, cnt, ISA, n, h, kb, B); // B = keys
 					sort_pairs(sc, B, Cc, sa_in, D, cnt, kb + bits_for(cnt), st);                      // Cc = sorted keys, D = sorted suffixes
-					hipLaunchKernelGGL(k_heads2, grid_for(cnt), dim3(256), 0, st, Cc, pos_in, cnt, A);
+					hip_launch("k_heads2", k_heads2, grid_for(cnt), dim3(256), 0, st, Cc, pos_in, cnt, A);
 					scan_max(sc, A, cnt, st);                                                          // A = new rank
-					hipLaunchKernelGGL(k_round_apply, grid_for(cnt), dim3(256), 0, st, D, A, pos_in, cnt, SA, ISA, B); // B = flag
-					ARX_IDX_CHECK(hipGetLastError());
+					hip_launch("k_round_apply", k_round_apply, grid_for(cnt), dim3(256), 0, st, D, A, pos_in, cnt, SA, ISA, B); // B = flag
 					const u64 last_flag = read_u64(B + cnt - 1, st);
 					scan_excl_sum(sc, B, Cc, cnt, st);                                                 // Cc = offsets
 					const u64 keep = read_u64(Cc + cnt - 1, st) + last_flag;
 					if (keep) {
-						hipLaunchKernelGGL(k_compact2, grid_for(cnt), dim3(256), 0, st, B, Cc, cnt, pos_in, D, upos[nx].as<u64>() + m_next, usa[nx].as<u64>() + m_next);
-						ARX_IDX_CHECK(hipGetLastError());
+						hip_launch("k_compact2", k_compact2, grid_for(cnt), dim3(256), 0, st, B, Cc, cnt, pos_in, D, upos[nx].as<u64>() + m_next, usa[nx].as<u64>() + m_next);
 					}
 					m_next += keep;
-					ARX_IDX_CHECK(hipStreamSynchronize(st));
+					ARX_HIP_CHECK(hipStreamSynchronize(st));
 				}
 				if (verbose) fprintf(stderr, "[arx index] round h=%llu: %llu -> %llu unresolved, %zu slice(s)\n", h, m, m_next, cuts.size() - 1);
 				upos[cur].release(); usa[cur].release();
@@ -494,9 +486,8 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 		// 6. verification
 		if (verify) {
 			DevBuf dbad(8);
-			ARX_IDX_CHECK(hipMemsetAsync(dbad.p, 0, 8, st));
-			hipLaunchKernelGGL(k_verify, grid_for(n), dim3(256), 0, st, T, SA, ISA, n, dbad.as<u64>());
-			ARX_IDX_CHECK(hipGetLastError());
+			ARX_HIP_CHECK(hipMemsetAsync(dbad.p, 0, 8, st));
+			hip_launch("k_verify", k_verify, grid_for(n), dim3(256), 0, st, T, SA, ISA, n, dbad.as<u64>());
 			const u64 bad = read_u64(dbad.as<u64>(), st);
 			if (bad) return "index build: suffix array verification failed (" + std::to_string(bad) + " rows out of order)";
 			S.s_verify = tm.lap();
@@ -510,9 +501,8 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 			const u64 n_words = (n + 15) >> 4, n_blocks = (n + 127) / 128, out_words = n_words + (n_blocks + 1) * 8;
 			DevBuf dwords(n_words * 4), dwcnt(n_words * 4), dout(out_words * 4 + 64);
 			DevBuf c0(n_blocks * 8 + 8), c1(n_blocks * 8 + 8), c2(n_blocks * 8 + 8), c3(n_blocks * 8 + 8), dtot(32);
-			hipLaunchKernelGGL(k_bwt_words, grid_for(n_words), dim3(256), 0, st, T, SA, n, primary, n_words, dwords.as<uint32_t>(), dwcnt.as<uint32_t>());
-			hipLaunchKernelGGL(k_block_counts, grid_for(n_blocks), dim3(256), 0, st, dwcnt.as<uint32_t>(), n_words, n_blocks, c0.as<u64>(), c1.as<u64>(), c2.as<u64>(), c3.as<u64>());
-			ARX_IDX_CHECK(hipGetLastError());
+			hip_launch("k_bwt_words", k_bwt_words, grid_for(n_words), dim3(256), 0, st, T, SA, n, primary, n_words, dwords.as<uint32_t>(), dwcnt.as<uint32_t>());
+			hip_launch("k_block_counts", k_block_counts, grid_for(n_blocks), dim3(256), 0, st, dwcnt.as<uint32_t>(), n_words, n_blocks, c0.as<u64>(), c1.as<u64>(), c2.as<u64>(), c3.as<u64>());
 			u64 tot[4];
 			DevBuf *cs[4] = {&c0, &c1, &c2, &c3};
 			for (int c = 0; c < 4; ++c) {
@@ -522,11 +512,10 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 				tot[c] = read_u64(p + n_blocks - 1, st) + last;
 				if (tot[c] != cnt_fwd[c] + cnt_fwd[3 - c]) return "index build: BWT symbol counts do not match the text (internal error)";
 			}
-			ARX_IDX_CHECK(hipMemcpyAsync(dtot.p, tot, 32, hipMemcpyHostToDevice, st));
-			ARX_IDX_CHECK(hipMemsetAsync(dout.p, 0, out_words * 4, st));
-			hipLaunchKernelGGL(k_interleave, grid_for(n_blocks + 1), dim3(256), 0, st, dwords.as<uint32_t>(), n_words, n_blocks, c0.as<u64>(), c1.as<u64>(), c2.as<u64>(), c3.as<u64>(), dtot.as<u64>(), dout.as<uint32_t>());
-			ARX_IDX_CHECK(hipGetLastError());
-			ARX_IDX_CHECK(hipStreamSynchronize(st));
+			ARX_HIP_CHECK(hipMemcpyAsync(dtot.p, tot, 32, hipMemcpyHostToDevice, st));
+			ARX_HIP_CHECK(hipMemsetAsync(dout.p, 0, out_words * 4, st));
+			hip_launch("k_interleave", k_interleave, grid_for(n_blocks + 1), dim3(256), 0, st, dwords.as<uint32_t>(), n_words, n_blocks, c0.as<u64>(), c1.as<u64>(), c2.as<u64>(), c3.as<u64>(), dtot.as<u64>(), dout.as<uint32_t>());
+			ARX_HIP_CHECK(hipStreamSynchronize(st));
 			FILE *o = fopen((prefix + ".bwt").c_str(), "wb");
 			if (!o) return "cannot write " + prefix + ".bwt";
 			fwrite(&primary, 8, 1, o); fwrite(L2 + 1, 8, 4, o);
@@ -536,8 +525,7 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 		{
 			const u64 intv = 32, n_sa = (n + intv) / intv, seq_len = n;
 			DevBuf ds((n_sa ? n_sa : 1) * 8);
-			if (n_sa > 1) hipLaunchKernelGGL(k_sa_sample, grid_for(n_sa - 1), dim3(256), 0, st, SA, n_sa, intv, ds.as<u64>());
-			ARX_IDX_CHECK(hipGetLastError());
+			if (n_sa > 1) hip_launch("k_sa_sample", k_sa_sample, grid_for(n_sa - 1), dim3(256), 0, st, SA, n_sa, intv, ds.as<u64>());
 			FILE *o = fopen((prefix + ".sa").c_str(), "wb");
 			if (!o) return "cannot write " + prefix + ".sa";
 			fwrite(&primary, 8, 1, o); fwrite(L2 + 1, 8, 4, o); fwrite(&intv, 8, 1, o); fwrite(&seq_len, 8, 1, o);
@@ -546,6 +534,8 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 		}
 		S.s_emit = tm.lap();
 		if (verbose) fprintf(stderr, "[arx index] %d doubling rounds %.2fs, verify %.2fs, emit %.2fs\n", S.n_rounds, S.s_rounds, S.s_verify, S.s_emit);
+	} catch (const HipError &ex) { // a HIP call or a launch: hip_launch.h
+		return std::string("index build: ") + ex.what();
 	} catch (const std::exception &ex) {
 		return ex.what();
 	}

@@ -1,5 +1,5 @@
-// hip_rt.h -- the HIP runtime policy of Pipeline<RT>: device memory, kernel launches on one stream, device scan,
-// per-kernel timing with HIP events.  gfx950 only.
+// hip_rt.h -- the HIP runtime policy of Pipeline<RT>: device memory, kernel launches on one stream (every one through start(), i.e.
+// hip_launch.h's checked primitive), device scan, per-kernel timing with HIP events.  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -10,6 +10,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
+#include <climits>
+#include "hip_launch.h"
 #include "hip_sw_coop.h"
 #include "hip_block.h"
 #include "hip_nw_coop.h"
@@ -18,8 +20,6 @@
 #include "switches.h"
 
 namespace arx {
-
-#define ARX_HIP_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw std::runtime_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 // generic grid-stride launchers; slot = global thread index (always < max_slots) selects per-thread scratch
 #ifndef ARX_ITEMS_WPE
@@ -65,11 +65,25 @@ struct HipRT {
 		}
 		ARX_HIP_CHECK(hipEventRecord(ev_fork, stream)); ARX_HIP_CHECK(hipStreamWaitEvent(aux, ev_fork, 0));
 		hipStream_t main_stream = stream;
-		stream = aux; f(); stream = main_stream;
+		stream = aux;
+		try { f(); } catch (...) { stream = main_stream; throw; } // (a launch that fails in f must not leave the runtime on the side stream)
+		stream = main_stream;
 		ARX_HIP_CHECK(hipEventRecord(ev_join, aux));
 		aux_pending = true;
 	}
 	void aux_join() { if (aux_pending) { ARX_HIP_CHECK(hipStreamWaitEvent(stream, ev_join, 0)); aux_pending = false; } }
+	// every launch of the runtime: on the current stream (the side stream inside on_aux), checked at once under its name (hip_launch.h)
+	template <class... P> void start(const LaunchName &name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, typename as_declared<P>::type... args) { hip_launch(name, kernel, grid, block, lds_bytes, stream, args...); }
+	// a kernel's opt-in to `bytes` of dynamic LDS.  It applies to the device that is current when it is made, so it is made once per runtime (=
+	// per device context), not once per process.  Every caller asks for its kernel's largest footprint, a constant: a kernel is remembered by
+	// its address alone and a second call for it does nothing, whatever `bytes` it names
+	std::vector<const void *> lds_opted_in;
+	template <class K> void allow_dynamic_lds(K kernel, size_t bytes)
+	{
+		for (const void *k : lds_opted_in) if (k == (const void *)kernel) return;
+		ARX_HIP_CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+		lds_opted_in.push_back((const void *)kernel);
+	}
 	int n_cu = 256;
 	bool timing = false;
 	std::map<std::string, KernelTimer> tm;
@@ -196,8 +210,7 @@ struct HipRT {
 		uint32_t *q = alloc<uint32_t>((size_t)n_reads * rw + 8);
 		Scope sc(*this, "seed_pack", n_reads);
 		const long long total = (long long)n_reads * rw;
-		hipLaunchKernelGGL(k_pack_reads, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, bases, base_off, lens, n_reads, rw, q);
-		ARX_HIP_CHECK(hipGetLastError());
+		start("k_pack_reads", k_pack_reads, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, bases, base_off, lens, n_reads, rw, q);
 		seed_qn = q;
 	}
 
@@ -244,29 +257,29 @@ struct HipRT {
 	std::map<std::string, KernelTimer> &timers() { resolve_timers(); return tm; }
 	void timers_reset(bool enable) { resolve_timers(); tm.clear(); timing = enable; }
 
+	// The thread-per-item launches: functor f over n items with k_items<F>, on (n + 63) / 64 blocks of 64 lanes or on `cap` of them
+	// grid-striding, whichever is fewer.  items_kernel() is the launch alone, for a caller that has a Scope open.
+	template <class F> void items_kernel(const char *nm, int n, const F &f, int cap)
+	{
+		const int blocks = (n + 63) / 64;
+		start({"k_items", nm}, k_items<F>, dim3(blocks < cap ? blocks : cap), dim3(64), 0, f, n);
+	}
+	template <class F> void launch_items(const char *nm, int n, const F &f, int cap)
+	{
+		if (n <= 0) return;
+		Scope sc(*this, nm, n);
+		items_kernel(nm, n, f, cap);
+	}
+	template <class F> void launch(const char *nm, int n, const F &f) { launch_items(nm, n, f, max_blocks()); }
 	// for functors that use no per-slot scratch: one item per lane, as many blocks as that takes -- the hardware hands blocks to CUs
 	// as they free up, which balances kernels whose items differ a lot in cost better than a fixed grid-stride assignment
-	template <class F> void launch_wide(const char *nm, int n, const F &f)
-	{
-		if (n <= 0) return;
-		if (!sw.wide) { launch(nm, n, f); return; }
-		Scope sc(*this, nm, n);
-		hipLaunchKernelGGL(k_items<F>, dim3((n + 63) / 64), dim3(64), 0, stream, f, n);
-		ARX_HIP_CHECK(hipGetLastError());
-	}
-	template <class F> void launch(const char *nm, int n, const F &f)
-	{
-		if (n <= 0) return;
-		Scope sc(*this, nm, n);
-		int blocks = (n + 63) / 64; if (blocks > max_blocks()) blocks = max_blocks();
-		hipLaunchKernelGGL(k_items<F>, dim3(blocks), dim3(64), 0, stream, f, n);
-		ARX_HIP_CHECK(hipGetLastError());
-	}
+	template <class F> void launch_wide(const char *nm, int n, const F &f) { launch_items(nm, n, f, sw.wide ? INT_MAX : max_blocks()); }
+	template <class F> void launch_small(const char *nm, int n, const F &f) { launch_items(nm, n, f, n_cu); }
 	// "cold" kernels (list bookkeeping: dedup, rescue_step) are instantiated in arx_cold.hip, a translation unit of its own (-O3 like
 	// the rest since round 2; arx_dev.h ks_introsort has the story of the -O1 build they needed before)
 	template <class F> void launch_cold(const char *nm, int n, const F &f);
 	// ks_introsort's budget flag (arx_dev.h) of both device translation units into a batch's error word; no host round trip of its own
-	void merge_sort_fail(uint32_t *err) { hipLaunchKernelGGL(k_merge_sort_fail, dim3(1), dim3(1), 0, stream, err); merge_sort_fail_cold(err); }
+	void merge_sort_fail(uint32_t *err) { start("k_merge_sort_fail", k_merge_sort_fail, dim3(1), dim3(1), 0, err); merge_sort_fail_cold(err); }
 	void merge_sort_fail_cold(uint32_t *err); // arx_cold.hip
 	// rescue replay of the pairs with long lists, lists staged in LDS (arx_cold.hip)
 	bool rescue_heavy_ok() const { return sw.rescue_heavy; }
@@ -278,19 +291,9 @@ struct HipRT {
 	// (arx_cold.hip: k_chain_g16; f.grp_max, f.mid_list / f.n_mid)
 	bool chain_group_ok() const { return sw.chain_group; }
 	template <class F> void run_chain_group(const char *nm, int n_reads, const F &f);
-	bool rescue_heavy_attr_set = false;
-	bool chain_heavy_attr_set = false; // the 128 KB dynamic-LDS opt-in of k_chain_heavy was made on this runtime's device
-	bool chain_group_attr_set = false; // likewise the dynamic-LDS opt-in of k_chain_g16 (above 64 KB when ARX_CHAIN_HEAVY_MIN is raised)
 	bool dedup_heavy_ok() const { return sw.dedup_heavy; }
 	template <class F> void run_dedup_heavy(const char *nm, int n_reads, const F &f); // likewise the region lists of such reads (f.eh_words ints of scratch per workgroup)
-	template <class F> void launch_cold_impl(const char *nm, int n, const F &f, bool wide = false)
-	{
-		if (n <= 0) return;
-		Scope sc(*this, nm, n);
-		int blocks = (n + 63) / 64; if (!(wide && sw.wide) && blocks > max_blocks()) blocks = max_blocks();
-		hipLaunchKernelGGL(k_items<F>, dim3(blocks), dim3(64), 0, stream, f, n);
-		ARX_HIP_CHECK(hipGetLastError());
-	}
+	template <class F> void launch_cold_impl(const char *nm, int n, const F &f, bool wide = false) { launch_items(nm, n, f, wide && sw.wide ? INT_MAX : max_blocks()); }
 	// one work item per BLOCK_LANES-lane workgroup (hip_block.h); f(item, HipBlock&)
 	// small (host, may be null): small[i] = 1 sends item i to a SMALL_LANES-lane workgroup
 	template <class F> void launch_block(const char *nm, int n, const F &f, const uint8_t *small = nullptr)
@@ -301,26 +304,17 @@ struct HipRT {
 		if (small) for (int i = 0; i < n; ++i) n_small += small[i] ? 1 : 0;
 		if (n_small == 0) {
 			int blocks = n < n_cu * 8 ? n : n_cu * 8;
-			hipLaunchKernelGGL((k_block_items<F, BLOCK_LANES, SORT_LDS>), dim3(blocks), dim3(BLOCK_LANES), 0, stream, f, n, (const uint8_t *)nullptr, 0);
+			start({"k_block_items<BLOCK_LANES>", nm}, k_block_items<F, BLOCK_LANES, SORT_LDS>, dim3(blocks), dim3(BLOCK_LANES), 0, f, n, nullptr, 0);
 		} else {
 			uint8_t *d = alloc<uint8_t>((size_t)n + 8);
 			h2d(d, small, (size_t)n);
 			int blocks = n_small < n_cu * 32 ? n_small : n_cu * 32;
-			hipLaunchKernelGGL((k_block_items<F, SMALL_LANES, SMALL_SORT>), dim3(blocks), dim3(SMALL_LANES), 0, stream, f, n, (const uint8_t *)d, 1);
+			start({"k_block_items<SMALL_LANES>", nm}, k_block_items<F, SMALL_LANES, SMALL_SORT>, dim3(blocks), dim3(SMALL_LANES), 0, f, n, d, 1);
 			if (n_small < n) {
 				blocks = n - n_small < n_cu * 8 ? n - n_small : n_cu * 8;
-				hipLaunchKernelGGL((k_block_items<F, BLOCK_LANES, SORT_LDS>), dim3(blocks), dim3(BLOCK_LANES), 0, stream, f, n, (const uint8_t *)d, 0);
+				start({"k_block_items<BLOCK_LANES>", nm}, k_block_items<F, BLOCK_LANES, SORT_LDS>, dim3(blocks), dim3(BLOCK_LANES), 0, f, n, d, 0);
 			}
 		}
-		ARX_HIP_CHECK(hipGetLastError());
-	}
-	template <class F> void launch_small(const char *nm, int n, const F &f)
-	{
-		if (n <= 0) return;
-		Scope sc(*this, nm, n);
-		int blocks = (n + 63) / 64; if (blocks > n_cu) blocks = n_cu;
-		hipLaunchKernelGGL(k_items<F>, dim3(blocks), dim3(64), 0, stream, f, n);
-		ARX_HIP_CHECK(hipGetLastError());
 	}
 	// rescue SW: 16 lanes per alignment (hip_sw_coop.h); sw.sw_simple selects the one-thread-per-alignment kernel for A/B runs
 	template <class F> void run_sw_u8(const char *nm, int n, const F &f, int max_len)
@@ -333,15 +327,13 @@ struct HipRT {
 			order = alloc<int32_t>((size_t)n + 1); n_order = order + n;
 			memset0(n_order, 4);
 			Scope sc(*this, "sw_filter", n);
-			hipLaunchKernelGGL(k_sw_filter_g16, dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, f.base_off, f.lens, f.tasks, f.res, n, order, n_order);
-			ARX_HIP_CHECK(hipGetLastError());
+			start("k_sw_filter_g16", k_sw_filter_g16, dim3(blocks), dim3(64), 0, f.ix, f.bases, f.base_off, f.lens, f.tasks, f.res, n, order, n_order);
 		}
 		{
 			Scope sc(*this, nm, n);
-			if (max_len <= 160) hipLaunchKernelGGL(k_sw_u8_g16<10>, dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, f.base_off, f.lens, f.tasks, f.res, n, order, n_order);
-			else if (max_len * OPT_A < 250) hipLaunchKernelGGL(k_sw_u8_g16<16>, dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, f.base_off, f.lens, f.tasks, f.res, n, order, n_order);
-			else hipLaunchKernelGGL(k_sw_u8_g16<32>, dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, f.base_off, f.lens, f.tasks, f.res, n, order, n_order); // mates of 250+ bases: ksw_i16's eight stripes of up to 32 cells; shorter mates of the same batch take the byte form inside
-			ARX_HIP_CHECK(hipGetLastError());
+			// <32>: mates of 250+ bases: ksw_i16's eight stripes of up to 32 cells; shorter mates of the same batch take the byte form inside
+			const auto kern = max_len <= 160 ? k_sw_u8_g16<10> : max_len * OPT_A < 250 ? k_sw_u8_g16<16> : k_sw_u8_g16<32>;
+			start({"k_sw_u8_g16", nm, max_len <= 160 ? 10 : max_len * OPT_A < 250 ? 16 : 32}, kern, dim3(blocks), dim3(64), 0, f.ix, f.bases, f.base_off, f.lens, f.tasks, f.res, n, order, n_order);
 		}
 		if (sw.sw_filter_stats) { int32_t k = 0; d2h(&k, n_order, 4); sw_tasks_seen += n; sw_tasks_run += k; }
 	}
@@ -392,8 +384,7 @@ struct HipRT {
 		memset0(counter, 4);
 		Scope sc(*this, nm, n);
 		int blocks = (n + 63) / 64; if (blocks > n_cu * bpc_) blocks = n_cu * bpc_;
-		hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), 64 * (size_t)seed_row, stream, A, n, counter, (batch_ & 0xff) | grant_ << 8, chunk_);
-		ARX_HIP_CHECK(hipGetLastError());
+		start(nm, kern, dim3(blocks), dim3(64), 64 * (size_t)seed_row, A, n, counter, (batch_ & 0xff) | grant_ << 8, chunk_);
 	}
 	template <class F> void run_seed_fwd1(const char *nm, int n, const F &f, int32_t *counter)
 	{
@@ -411,101 +402,102 @@ struct HipRT {
 		launch_seed_kernel(nm, k_seed_fwd2, n, A, counter, seed_bpc());
 		seed_dbg_report(nm, n);
 	}
+	// backward sweeps: run_seed_bwd() dispatches on sw.seed_bwd2 to one function per kernel variant (switches.h has their story; all four are
+	// pinned by tests/test_seed_variants_gpu.py).  A: the variant's kernel arguments; A.heavy / A.n_heavy: the list of the sweeps that are
+	// finished by whole wavefronts (k_seed_bwd_wave) -- the ones longer than sw.seed_bwd_budget extensions, or too long for a row
 	template <class F> void run_seed_bwd(const char *nm, int n, const F &f, int32_t *counter)
 	{
 		if (n <= 0) return;
 		if (sw.sw_simple) { launch(nm, n, f); return; }
-		// sweeps longer than sw.seed_bwd_budget extensions are finished by whole wavefronts (k_seed_bwd_wave)
 		int32_t *heavy = alloc<int32_t>((size_t)n + 2);
 		memset0(heavy + n, 4);
 		SeedKArgs A{f.ix, f.bases, f.base_off, f.lens, f.P, nullptr, 0, nullptr, f.t0, heavy, heavy + n, sw.seed_bwd_budget, seed_row, seed_qn, 0, seed_dbg()};
 		if (!sw.text_bwd) A.ix.isa40 = nullptr; // ARX_TEXT_BWD=0: every sweep walked to its end (k_seed_bwd_g hands nothing to KSeedBwdTail)
-		if (sw.seed_bwd2 == 3) { // entry-parallel sweeps (k_seed_bwd_e): one lane per list entry
-			int32_t *ecnt = alloc<int32_t>((size_t)n + 2), *eoff = alloc<int32_t>((size_t)n + 2);
-			Scope sc(*this, nm, n);
-			hipLaunchKernelGGL(k_bwd_e_count, dim3((n + 255) / 256), dim3(256), 0, stream, f.P.tasks, f.t0, n, ecnt);
-			const int64_t total = exclusive_scan(ecnt, eoff, n); // (waits for the stream)
-			BwdItem *items = alloc<BwdItem>((size_t)total + 4);
-			hipLaunchKernelGGL(k_bwd_e_expand, dim3((n + 255) / 256), dim3(256), 0, stream, f.P.tasks, f.P.pool, f.t0, n, eoff, items);
-			if (total > 0) {
-				memset0(counter, 4);
-				int64_t blocks = (total + 63) / 64; if (blocks > (int64_t)n_cu * sw.seed_bwd_e_bpc) blocks = (int64_t)n_cu * sw.seed_bwd_e_bpc;
-				hipLaunchKernelGGL(k_seed_bwd_e, dim3((unsigned)blocks), dim3(64), 0, stream, A, items, (int)total, counter, sw.seed_bwd_e_chunk);
-				hipLaunchKernelGGL(k_bwd_e_final, dim3((n + 255) / 256), dim3(256), 0, stream, f.P.tasks, f.P.pool, f.t0, n);
-			}
-			ARX_HIP_CHECK(hipGetLastError());
-			seed_dbg_report(nm, (int)total);
-			seed_census_add(n, nullptr, nullptr, nullptr);
-			return;
+		if (sw.seed_bwd2 == 3) seed_bwd_entries(nm, n, f, A, counter);
+		else if (sw.seed_bwd2 == 2) seed_bwd_rows(nm, n, f, A);
+		else if (sw.seed_bwd2) seed_bwd_pipelined(nm, n, f, A, counter);
+		else seed_bwd_round1(nm, n, f, A, counter);
+	}
+	// The hand-off tail of a backward pass and its census.  wave: k_seed_bwd_wave finishes the listed sweeps; flag (may be null: the kernel
+	// listed them itself) marks the tasks k_collect_heavy puts on the list first; tail: KSeedBwdTail finishes the sweeps flagged 2
+	template <class F> void seed_bwd_handoff(int n, const F &f, const SeedKArgs &A, bool wave, const uint8_t *flag, bool tail, const int32_t *cnt)
+	{
+		if (wave) {
+			Scope sc(*this, "seed_bwd_wave", n);
+			if (flag) start("k_collect_heavy", k_collect_heavy, dim3((n + 255) / 256), dim3(256), 0, flag, n, f.t0, A.heavy, A.n_heavy);
+			start("k_seed_bwd_wave", k_seed_bwd_wave, dim3(n_cu * 16), dim3(64), 0, A);
+			if (tail) items_kernel("KSeedBwdTail", n, KSeedBwdTail{f.ix, f.bases, f.base_off, f.P.pool, f.P.tasks, f.t0, flag}, INT_MAX);
 		}
-		if (sw.seed_bwd2 == 2) { // row-parallel sweeps (k_seed_bwd_g<GL>): one task per 16/32/64-lane group, lists in registers
-			uint8_t *flag = alloc<uint8_t>((size_t)n + 8);
-			int32_t *bins = alloc<int32_t>(4 * (size_t)n + 8), *cnt = alloc<int32_t>(8); // cnt[0..3]: bin sizes, cnt[4..7]: the bins' item counters
-			memset0(flag, (size_t)n);
-			memset0(cnt, 32);
-			const int cap = n_cu * sw.seed_bwd_bpc;
-			auto blocks_for = [&](int per_wave) { int b = (n + per_wave - 1) / per_wave; return b > cap ? cap : (b < 1 ? 1 : b); };
-			const size_t xch = 64 * 32;
-			{
-				Scope sc(*this, nm, n);
-				hipLaunchKernelGGL(k_bin_tasks, dim3((n + 255) / 256), dim3(256), 0, stream, f.P.tasks, f.t0, n, bins, bins + n, bins + 2 * (size_t)n, bins + 3 * (size_t)n, cnt, sw.seed_bwd_mid);
-				const bool fit32 = sw.seed_fit32 && (((f.ix.L2[1] - f.ix.L2[0]) | (f.ix.L2[2] - f.ix.L2[1]) | (f.ix.L2[3] - f.ix.L2[2]) | (f.ix.L2[4] - f.ix.L2[3])) >> 32) == 0;
-				if (fit32) hipLaunchKernelGGL(k_seed_bwd_g<true>, dim3(blocks_for(4)), dim3(64), ((4 * (size_t)seed_row + 31) & ~(size_t)31) + xch, stream, A, bins, n, cnt, flag);
-				else hipLaunchKernelGGL(k_seed_bwd_g<false>, dim3(blocks_for(4)), dim3(64), ((4 * (size_t)seed_row + 31) & ~(size_t)31) + xch, stream, A, bins, n, cnt, flag);
-				ARX_HIP_CHECK(hipGetLastError());
-			}
-			if (sw.seed_hist) { // diagnostics: forward-list lengths of this launch's tasks
-				std::vector<SeedTask> ht((size_t)n);
-				d2h(ht.data(), f.P.tasks + f.t0, (size_t)n * sizeof(SeedTask));
-				long long hist[40] = {0};
-				for (auto &k : ht) ++hist[k.n < 39 ? k.n : 39];
-				fprintf(stderr, "[arx seed hist] %d tasks, list lengths 0..39+:", n);
-				for (int i = 0; i < 40; ++i) fprintf(stderr, " %lld", hist[i]);
-				fprintf(stderr, "\n");
-			}
-			if (sw.seed_stats) { int32_t h[4]; d2h(h, cnt, 16); fprintf(stderr, "[arx seed stats] backward tasks by list length: <= 16: %d, <= %d: %d, <= 32: %d, longer: %d\n", h[0], sw.seed_bwd_mid, h[1], h[2], h[3]); }
-			seed_dbg_report(nm, n);
-			{
-				Scope sc(*this, "seed_bwd_wave", n);
-				hipLaunchKernelGGL(k_collect_heavy, dim3((n + 255) / 256), dim3(256), 0, stream, flag, n, f.t0, heavy, heavy + n);
-				hipLaunchKernelGGL(k_seed_bwd_wave, dim3(n_cu * 16), dim3(64), 0, stream, A);
-				if (A.ix.isa40) { // the sweeps k_seed_bwd_g left at a row of one interval with one occurrence (text mode)
-					KSeedBwdTail kt{f.ix, f.bases, f.base_off, f.P.pool, f.P.tasks, f.t0, flag};
-					hipLaunchKernelGGL(k_items<KSeedBwdTail>, dim3((n + 63) / 64), dim3(64), 0, stream, kt, n);
-				}
-				ARX_HIP_CHECK(hipGetLastError());
-			}
-			seed_census_add(n, cnt, heavy + n, flag);
-			return;
-		}
-		if (sw.seed_bwd2) { // pipelined refills (k_seed_bwd2): one wait on memory per iteration
-			uint8_t *flag = alloc<uint8_t>((size_t)n + 8);
-			memset0(flag, (size_t)n);
+		seed_census_add(n, cnt, A.n_heavy, flag);
+	}
+	// ARX_SEED_BWD2=3, entry-parallel sweeps (k_seed_bwd_e): one lane per list entry
+	template <class F> void seed_bwd_entries(const char *nm, int n, const F &f, const SeedKArgs &A, int32_t *counter)
+	{
+		int32_t *ecnt = alloc<int32_t>((size_t)n + 2), *eoff = alloc<int32_t>((size_t)n + 2);
+		Scope sc(*this, nm, n);
+		const dim3 per_task((n + 255) / 256);
+		start("k_bwd_e_count", k_bwd_e_count, per_task, dim3(256), 0, f.P.tasks, f.t0, n, ecnt);
+		const int64_t total = exclusive_scan(ecnt, eoff, n); // (waits for the stream)
+		BwdItem *items = alloc<BwdItem>((size_t)total + 4);
+		start("k_bwd_e_expand", k_bwd_e_expand, per_task, dim3(256), 0, f.P.tasks, f.P.pool, f.t0, n, eoff, items);
+		if (total > 0) {
 			memset0(counter, 4);
-			{
-				Scope sc(*this, nm, n);
-				int blocks = (n + 63) / 64; if (blocks > n_cu * seed_bpc()) blocks = n_cu * seed_bpc();
-				hipLaunchKernelGGL(k_seed_bwd2, dim3(blocks), dim3(64), 64 * (size_t)seed_row, stream, A, n, counter, sw.seed_bwd_chunk, flag);
-				ARX_HIP_CHECK(hipGetLastError());
-			}
-			seed_dbg_report(nm, n);
-			if (sw.seed_bwd_budget > 0) {
-				Scope sc(*this, "seed_bwd_wave", n);
-				hipLaunchKernelGGL(k_collect_heavy, dim3((n + 255) / 256), dim3(256), 0, stream, flag, n, f.t0, heavy, heavy + n);
-				hipLaunchKernelGGL(k_seed_bwd_wave, dim3(n_cu * 16), dim3(64), 0, stream, A);
-				ARX_HIP_CHECK(hipGetLastError());
-			}
-			seed_census_add(n, nullptr, heavy + n, flag);
-			return;
+			int64_t blocks = (total + 63) / 64; if (blocks > (int64_t)n_cu * sw.seed_bwd_e_bpc) blocks = (int64_t)n_cu * sw.seed_bwd_e_bpc;
+			start("k_seed_bwd_e", k_seed_bwd_e, dim3((unsigned)blocks), dim3(64), 0, A, items, (int)total, counter, sw.seed_bwd_e_chunk);
+			start("k_bwd_e_final", k_bwd_e_final, per_task, dim3(256), 0, f.P.tasks, f.P.pool, f.t0, n);
 		}
+		seed_dbg_report(nm, (int)total);
+		seed_census_add(n, nullptr, nullptr, nullptr); // (nothing is handed on)
+	}
+	// ARX_SEED_BWD2=2 (the default), row-parallel sweeps (k_seed_bwd_g<FIT32>): one task per 16/32/64-lane group, lists in registers
+	template <class F> void seed_bwd_rows(const char *nm, int n, const F &f, const SeedKArgs &A)
+	{
+		uint8_t *flag = alloc<uint8_t>((size_t)n + 8);
+		int32_t *bins = alloc<int32_t>(4 * (size_t)n + 8), *cnt = alloc<int32_t>(8); // cnt[0..3]: bin sizes, cnt[4..7]: the bins' item counters
+		memset0(flag, (size_t)n);
+		memset0(cnt, 32);
+		{
+			Scope sc(*this, nm, n);
+			start("k_bin_tasks", k_bin_tasks, dim3((n + 255) / 256), dim3(256), 0, f.P.tasks, f.t0, n, bins, bins + n, bins + 2 * (size_t)n, bins + 3 * (size_t)n, cnt, sw.seed_bwd_mid);
+			const bool fit32 = sw.seed_fit32 && (((f.ix.L2[1] - f.ix.L2[0]) | (f.ix.L2[2] - f.ix.L2[1]) | (f.ix.L2[3] - f.ix.L2[2]) | (f.ix.L2[4] - f.ix.L2[3])) >> 32) == 0;
+			const int cap = n_cu * sw.seed_bwd_bpc, b = (n + 3) / 4, blocks = b > cap ? cap : (b < 1 ? 1 : b); // four tasks per wavefront
+			const size_t lds = ((4 * (size_t)seed_row + 31) & ~(size_t)31) + 64 * 32; // four reads and the lanes' exchange words
+			start({"k_seed_bwd_g", nm, fit32}, fit32 ? k_seed_bwd_g<true> : k_seed_bwd_g<false>, dim3(blocks), dim3(64), lds, A, bins, n, cnt, flag);
+		}
+		if (sw.seed_hist) { // diagnostics: forward-list lengths of this launch's tasks
+			std::vector<SeedTask> ht((size_t)n);
+			d2h(ht.data(), f.P.tasks + f.t0, (size_t)n * sizeof(SeedTask));
+			long long hist[40] = {0};
+			for (auto &k : ht) ++hist[k.n < 39 ? k.n : 39];
+			fprintf(stderr, "[arx seed hist] %d tasks, list lengths 0..39+:", n);
+			for (int i = 0; i < 40; ++i) fprintf(stderr, " %lld", hist[i]);
+			fprintf(stderr, "\n");
+		}
+		if (sw.seed_stats) { int32_t h[4]; d2h(h, cnt, 16); fprintf(stderr, "[arx seed stats] backward tasks by list length: <= 16: %d, <= %d: %d, <= 32: %d, longer: %d\n", h[0], sw.seed_bwd_mid, h[1], h[2], h[3]); }
+		seed_dbg_report(nm, n);
+		// the tail: the sweeps k_seed_bwd_g left at a row of one interval with one occurrence (text mode)
+		seed_bwd_handoff(n, f, A, /* wave */ true, flag, /* tail */ A.ix.isa40 != nullptr, cnt);
+	}
+	// ARX_SEED_BWD2=1, pipelined refills (k_seed_bwd2): one lane per task, one wait on memory per iteration
+	template <class F> void seed_bwd_pipelined(const char *nm, int n, const F &f, const SeedKArgs &A, int32_t *counter)
+	{
+		uint8_t *flag = alloc<uint8_t>((size_t)n + 8);
+		memset0(flag, (size_t)n);
+		memset0(counter, 4);
+		{
+			Scope sc(*this, nm, n);
+			int blocks = (n + 63) / 64; if (blocks > n_cu * seed_bpc()) blocks = n_cu * seed_bpc();
+			start("k_seed_bwd2", k_seed_bwd2, dim3(blocks), dim3(64), 64 * (size_t)seed_row, A, n, counter, sw.seed_bwd_chunk, flag);
+		}
+		seed_dbg_report(nm, n);
+		seed_bwd_handoff(n, f, A, /* wave */ sw.seed_bwd_budget > 0, flag, /* tail */ false, /* no bins */ nullptr);
+	}
+	// ARX_SEED_BWD2=0, round 1's kernel (k_seed_bwd): one lane per task, it lists the sweeps past their budget itself
+	template <class F> void seed_bwd_round1(const char *nm, int n, const F &f, const SeedKArgs &A, int32_t *counter)
+	{
 		launch_seed_kernel(nm, k_seed_bwd, n, A, counter, seed_bpc(), sw.seed_bwd_chunk, sw.seed_bwd_batch);
 		seed_dbg_report(nm, n);
-		if (sw.seed_bwd_budget > 0) {
-			Scope sc(*this, "seed_bwd_wave", n);
-			hipLaunchKernelGGL(k_seed_bwd_wave, dim3(n_cu * 16), dim3(64), 0, stream, A);
-			ARX_HIP_CHECK(hipGetLastError());
-		}
-		seed_census_add(n, nullptr, heavy + n, nullptr);
+		seed_bwd_handoff(n, f, A, /* wave */ sw.seed_bwd_budget > 0, /* listed by the kernel */ nullptr, /* tail */ false, /* no bins */ nullptr);
 	}
 	template <class F> void run_seed_strat(const char *nm, int n, const F &f, int32_t *counter)
 	{
@@ -515,8 +507,7 @@ struct HipRT {
 		Scope sc(*this, nm, n);
 		StratArgs A{f.ix, f.bases, f.base_off, f.lens, f.strat, f.n_strat, seed_row, seed_qn};
 		int blocks = (n + 63) / 64; if (blocks > n_cu * strat_bpc()) blocks = n_cu * strat_bpc();
-		hipLaunchKernelGGL(k_strat_dyn, dim3(blocks), dim3(64), 64 * (size_t)seed_row, stream, A, n, counter, sw.seed_chunk);
-		ARX_HIP_CHECK(hipGetLastError());
+		start("k_strat_dyn", k_strat_dyn, dim3(blocks), dim3(64), 64 * (size_t)seed_row, A, n, counter, sw.seed_chunk);
 	}
 	// locate: persistent lanes with wave-level work distribution (hip_fm_coop.h); 32 waves per CU to cover the miss latency
 	template <class F> void run_locate(const char *nm, int n, const F &f, int32_t *counter)
@@ -527,10 +518,10 @@ struct HipRT {
 		memset0(counter, 4);
 		Scope sc(*this, nm, n);
 		int blocks = (n + 255) / 256; if (blocks > n_cu * 8) blocks = n_cu * 8;
-		hipLaunchKernelGGL(k_locate_dyn, dim3(blocks), dim3(256), 0, stream, f.ix, f.occ_seed, n, counter);
-		ARX_HIP_CHECK(hipGetLastError());
+		start("k_locate_dyn", k_locate_dyn, dim3(blocks), dim3(256), 0, f.ix, f.occ_seed, n, counter);
 	}
 	// banded extension: 16 lanes per extension (hip_sw_coop.h); the query-length classes share one launch
+	using ExtKernel = void (*)(IndexView, const uint8_t *, const ExtTask *, ExtRes *, int);
 	template <class F> void run_extend(const char *nm, const int32_t *n_class, int stride, const F &f)
 	{
 		int total = 0;
@@ -546,20 +537,11 @@ struct HipRT {
 				if (nc <= 0) continue;
 				Scope sc(*this, nm, nc);
 				const ExtTask *tk = f.tasks + (size_t)c * stride;
-				const int blocks = coop_blocks(nc);
-#define ARX_EXT_LAUNCH(CN, CO) do { if (sw.ext_old) hipLaunchKernelGGL((k_extend_b16<CO, true>), dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, tk, f.res, nc); \
-                                    else hipLaunchKernelGGL((k_extend_b16<CN, false>), dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, tk, f.res, nc); } while (0)
-				switch (c) {
-				case 0: ARX_EXT_LAUNCH(2, 4); break;
-				case 1: ARX_EXT_LAUNCH(3, 4); break;
-				case 2: ARX_EXT_LAUNCH(4, 4); break;
-				case 3: ARX_EXT_LAUNCH(6, 7); break;
-				case 4: ARX_EXT_LAUNCH(8, 10); break;
-				case 5: ARX_EXT_LAUNCH(10, 10); break;
-				default: ARX_EXT_LAUNCH(16, 16); break;
-				}
-#undef ARX_EXT_LAUNCH
-				ARX_HIP_CHECK(hipGetLastError());
+				// per class: round 2's kernel on the same class lists (sw.ext_old), and this round's at the class's own register tiling
+				static constexpr ExtKernel by_class[EXT_CLASSES][2] = {{k_extend_b16<4, true>, k_extend_b16<2, false>}, {k_extend_b16<4, true>, k_extend_b16<3, false>},
+					{k_extend_b16<4, true>, k_extend_b16<4, false>}, {k_extend_b16<7, true>, k_extend_b16<6, false>}, {k_extend_b16<10, true>, k_extend_b16<8, false>},
+					{k_extend_b16<10, true>, k_extend_b16<10, false>}, {k_extend_b16<16, true>, k_extend_b16<16, false>}};
+				start({sw.ext_old ? "k_extend_b16<old>" : "k_extend_b16", nm, c}, by_class[c][sw.ext_old ? 0 : 1], dim3(coop_blocks(nc)), dim3(64), 0, f.ix, f.bases, tk, f.res, nc);
 			}
 			return;
 		}
@@ -573,11 +555,10 @@ struct HipRT {
 			if (nb > 0 && (total + 3) / 4 > cap) { nb = (int)((int64_t)nb * cap / ((total + 3) / 4)); if (nb < 1) nb = 1; } // share the grid cap by class size
 			sh.nb[c] = nb; blocks += nb;
 		}
-		if (sw.ext_old) hipLaunchKernelGGL(k_extend_classes_b<true>, dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, f.tasks, stride, f.res, sh);
-		else hipLaunchKernelGGL(k_extend_classes_b<false>, dim3(blocks), dim3(64), 0, stream, f.ix, f.bases, f.tasks, stride, f.res, sh);
-		ARX_HIP_CHECK(hipGetLastError());
+		start({"k_extend_classes_b", nm, sw.ext_old}, sw.ext_old ? k_extend_classes_b<true> : k_extend_classes_b<false>, dim3(blocks), dim3(64), 0, f.ix, f.bases, f.tasks, stride, f.res, sh);
 	}
 	// CIGARs of the gapped regions: 16 lanes per region (hip_nw_coop.h); f is pipeline.h's KReg2Aln
+	using NwKernel = void (*)(NwArgs, int, const int32_t *);
 	template <class F> void run_reg2aln_nw(const char *nm, int n, const int32_t *n_class, const F &f, uint8_t *zbuf, const int32_t *z_off)
 	{
 		if (n <= 0) return;
@@ -592,21 +573,13 @@ struct HipRT {
 			Scope sc(*this, nm, nc);
 			NwArgs A{f.ix, f.bases, f.base_off, f.lens, f.preg_off, f.n_regs, f.n_reads, f.pregs, f.alns, f.cig, f.cig_w, zbuf, z_off, f.nw_list, f.err,
 			         f.class_list + (size_t)c * f.class_stride, punt, n_punt};
-			const dim3 grid(coop_blocks(nc)), blk(64);
-			switch (c) {
-			case 0: hipLaunchKernelGGL((k_reg2aln_nw_g16<1, 2>), grid, blk, 0, stream, A, nc, (const int32_t *)nullptr); break;
-			case 1: hipLaunchKernelGGL((k_reg2aln_nw_g16<2, 4>), grid, blk, 0, stream, A, nc, (const int32_t *)nullptr); break;
-			case 2: hipLaunchKernelGGL((k_reg2aln_nw_g16<4, 8>), grid, blk, 0, stream, A, nc, (const int32_t *)nullptr); break;
-			case 3: hipLaunchKernelGGL((k_reg2aln_nw_g16<8, 16>), grid, blk, 0, stream, A, nc, (const int32_t *)nullptr); break;
-			default: hipLaunchKernelGGL((k_reg2aln_nw_g16<16, 16>), grid, blk, 0, stream, A, nc, (const int32_t *)nullptr); break;
-			}
-			ARX_HIP_CHECK(hipGetLastError());
+			static constexpr NwKernel by_class[NW_CLASSES] = {k_reg2aln_nw_g16<1, 2>, k_reg2aln_nw_g16<2, 4>, k_reg2aln_nw_g16<4, 8>, k_reg2aln_nw_g16<8, 16>, k_reg2aln_nw_g16<16, 16>};
+			start({"k_reg2aln_nw_g16", nm, c}, by_class[c], dim3(coop_blocks(nc)), dim3(64), 0, A, nc, nullptr);
 		}
 		{ // what the class kernels handed on (a third band, or a doubled band past the class's second tiling): all tilings, length read on the device
 			Scope sc(*this, nm, 0);
 			NwArgs A{f.ix, f.bases, f.base_off, f.lens, f.preg_off, f.n_regs, f.n_reads, f.pregs, f.alns, f.cig, f.cig_w, zbuf, z_off, f.nw_list, f.err, punt, punt, n_punt + 1};
-			hipLaunchKernelGGL((k_reg2aln_nw_g16<1, 16>), dim3(n_cu * 2), dim3(64), 0, stream, A, 0, (const int32_t *)n_punt);
-			ARX_HIP_CHECK(hipGetLastError());
+			start({"k_reg2aln_nw_g16<1, 16>", "punted"}, k_reg2aln_nw_g16<1, 16>, dim3(n_cu * 2), dim3(64), 0, A, 0, n_punt);
 		}
 	}
 	template <class F> void launch_rows(const char *nm, int n, const F &f, int words_per_thread)
@@ -615,8 +588,7 @@ struct HipRT {
 		Scope sc(*this, nm, n);
 		int blocks = (n + 63) / 64; if (blocks > max_blocks()) blocks = max_blocks();
 		size_t lds = (size_t)words_per_thread * 64 * 4;
-		hipLaunchKernelGGL(k_rows<F>, dim3(blocks), dim3(64), lds, stream, f, n);
-		ARX_HIP_CHECK(hipGetLastError());
+		start({"k_rows", nm}, k_rows<F>, dim3(blocks), dim3(64), lds, f, n);
 	}
 	// out[0..n] = exclusive prefix sums of in[0..n); returns the total as int64
 	int64_t exclusive_scan(const int32_t *in, int32_t *out, int n)
