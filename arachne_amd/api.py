@@ -91,6 +91,10 @@ def _load(path):
     lib.arx_batch_post_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.arx_batch_tags.argtypes = [vp, vp]
     lib.arx_batch_tags_fetch.argtypes = [vp, vp, vp]
+    lib.arx_batch_records.argtypes = [vp, vp, vp, i32, vp, vp]
+    lib.arx_batch_records_fetch.argtypes = [vp, vp, vp, vp]
+    lib.arx_batch_records_view.argtypes = [vp, vp, vp, vp, vp]
+    lib.arx_bam_write_encoded.argtypes = [vp, vp, i64, i64]
     lib.arx_bam_write_select.argtypes = [vp, vp, vp, i64]
     lib.arx_bucket_table.argtypes = [i32, vp, vp, i64, vp, vp, vp, i32, i32]
     lib.arx_recbuf_build_full.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
@@ -130,6 +134,7 @@ _SELFTEST_ARGS = {
     "arx_selftest_bgzf": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     # the device BAM sink: bound when first used, for the same reason
     "arx_bam_open_device": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
+    "arx_bam_write_encoded_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64],
 }
 
 
@@ -243,6 +248,8 @@ class _DeviceView(C.Structure):
 
 class Batch:
     """One batch of read pairs resident on the device (arx_batch)."""
+
+    _rec = (0, 0)   # (n_records, n_bytes) of the last records()
 
     def __init__(self, ref: "Reference", seqs, lens):
         self.ref = ref
@@ -431,6 +438,31 @@ class Batch:
         self.ref._check(self.ref.lib.arx_batch_tags_fetch(self.ref.h, self.h, out.ctypes.data))
         return out
 
+    def records(self, sb_raw, dup=True):
+        """arx_batch_records (needs rfa(); dup=True also post()): the BAM-encoded primary record of every read, written on the device -- the
+        bytes RecBuf.build -> BamWriter.write_view would append.  sb_raw: the _SuperBatch of Feeder.next_raw.  -> (n_records, n_bytes)"""
+        n, nb = C.c_int64(), C.c_int64()
+        self.ref._check(self.ref.lib.arx_batch_records(self.ref.h, self.h, C.byref(sb_raw), 1 if dup else 0, C.byref(n), C.byref(nb)))
+        self._rec = (int(n.value), int(nb.value))
+        return self._rec
+
+    def records_fetch(self, out=None, offsets=True):
+        """arx_batch_records_fetch -> (stream, rec_off): the record stream as a uint8 array (a view of `out`, a uint8 array the caller keeps,
+        when it is large enough) and the n_records + 1 byte offsets of the records (None with offsets=False)"""
+        n, nb = self._rec
+        if out is None or len(out) < nb:
+            out = np.zeros(max(nb, 1), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.int64) if offsets else None
+        self.ref._check(self.ref.lib.arx_batch_records_fetch(self.ref.h, self.h, out.ctypes.data, off.ctypes.data if offsets else None))
+        return out[:nb], off
+
+    def records_view(self):
+        """arx_batch_records_view -> (device pointer of the stream, n_bytes, n_records), valid until the phase is left; for
+        BamWriter.write_encoded_device"""
+        p, nb, n = C.c_void_p(), C.c_int64(), C.c_int64()
+        self.ref._check(self.ref.lib.arx_batch_records_view(self.ref.h, self.h, C.byref(p), C.byref(nb), C.byref(n)))
+        return p.value or 0, int(nb.value), int(n.value)
+
     def free(self):
         if self.h:
             self.ref.lib.arx_batch_free(self.ref.h, self.h)
@@ -603,6 +635,18 @@ class BamWriter:
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         if self.lib.arx_bam_write_select(self.h, C.byref(view), idx.ctypes.data if len(idx) else None, len(idx)) != 0:
             raise ArachneError("arx_bam_write_select: " + self.lib.arx_bam_error(self.h).decode())
+
+    def write_encoded(self, stream, n_records):
+        """arx_bam_write_encoded: n_records BAM-encoded records (Batch.records_fetch's stream: a uint8 array or bytes), any writer"""
+        a = np.frombuffer(stream, dtype=np.uint8) if isinstance(stream, (bytes, bytearray, memoryview)) else np.ascontiguousarray(stream, dtype=np.uint8)
+        if self.lib.arx_bam_write_encoded(self.h, a.ctypes.data if len(a) else None, len(a), int(n_records)) != 0:
+            raise ArachneError("arx_bam_write_encoded: " + self.lib.arx_bam_error(self.h).decode())
+
+    def write_encoded_device(self, ptr, n_bytes, n_records):
+        """arx_bam_write_encoded_device: the same from device memory (Batch.records_view), writers opened with device= only; returns when the
+        blocks are written -- the batch may then be reset"""
+        if _selftest_fn(self.lib, "arx_bam_write_encoded_device")(self.h, C.c_void_p(ptr), int(n_bytes), int(n_records)) != 0:
+            raise ArachneError("arx_bam_write_encoded_device: " + self.lib.arx_bam_error(self.h).decode())
 
     def close(self):
         st = np.zeros(4, dtype=np.int64)

@@ -17,6 +17,7 @@
 #include "pipeline.h"
 #include "pipeline_rfa.h"
 #include "pipeline_post.h"
+#include "pipeline_records.h"
 #include "device_feeder.h"
 
 namespace arx {
@@ -219,13 +220,13 @@ template <class RT> struct Batch {
 	typename Pipeline<RT>::Work work;
 	BatchResult res;
 	std::vector<int32_t> lens_host;
-	RfaResult rfa; PostResult post; TagsResult tags;
+	RfaResult rfa; PostResult post; TagsResult tags; RecordsResult recs;
 	// The lifetime of the batch's work memory.  The stages (arx_batch_run) allocate from the start of the arena; the phases that follow them
 	// come in this order, each behind the memory of the one before, and a phase that was skipped (tags without post) is empty:
-	enum Phase { PH_PLACE, PH_POST, PH_TAGS, N_PHASES }; // arx_batch_rfa, arx_batch_post, arx_batch_tags
+	enum Phase { PH_PLACE, PH_POST, PH_TAGS, PH_RECORDS, N_PHASES }; // arx_batch_rfa, arx_batch_post, arx_batch_tags, arx_batch_records
 	int done_stage = 0;                       // last stage run
 	std::vector<size_t> begin[N_PHASES]; int n_begun = 0; // arena marks: where the memory of phases [0, n_begun) begins
-	bool done[N_PHASES] = {false, false, false}; // the phase's results are there (done[p] only if p < n_begun)
+	bool done[N_PHASES] = {false, false, false, false}; // the phase's results are there (done[p] only if p < n_begun)
 	bool aligned() const { return done_stage >= ARX_STAGE_ALN; }
 	// Entering a phase hands back its own memory of an earlier call and that of every later phase, and with it their results
 	void enter(Phase p)
@@ -264,6 +265,16 @@ template <class RT> struct Batch {
 	}
 	void run_post() { rt.set_timing(ctx->timing); enter(PH_POST); PostStage<RT>::run(pipe, db, work, rfa, post); rt.sync(); done[PH_POST] = true; }
 	void run_tags() { rt.set_timing(ctx->timing); enter(PH_TAGS); TagsStage<RT>::run(pipe, db, rfa, tags); rt.sync(); done[PH_TAGS] = true; }
+	// arx_batch_records: ARX_OK or the error code, its text set in the context.  dup: the duplicate marks of the post phase (kept: it lies in front)
+	int run_records(const arx_super_batch &sb, bool dup)
+	{
+		rt.set_timing(ctx->timing); enter(PH_RECORDS);
+		std::string e;
+		const int rc = RecordsStage<RT>::run(pipe, db, work, rfa, dup ? &post : nullptr, sb, recs, e);
+		if (rc != ARX_OK) { rt.sync(); ctx->set_error(e); return rc; }
+		done[PH_RECORDS] = true;
+		return ARX_OK;
+	}
 	// arx_batch_detach: the dense results copied aside (device memory of their own, outside the work arena) so that the handle can take its
 	// next reads while a second host thread takes them home through a stream of its own (arx_batch_fetch_detached)
 	struct Detached {
@@ -511,6 +522,35 @@ template <class RT> struct Batch {
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
 		if (!b->done[Bat::PH_TAGS]) { c->set_error("arx_batch_tags_fetch before arx_batch_tags (or after a later arx_batch_rfa / arx_batch_post)"); return ARX_E_ARG; } \
 		ARX_TRY(c, b->rt.bind(); arx::TagsStage<RT>::fetch(b->pipe, b->db, b->tags, (arx::ReadTags *)out);)                         \
+		return ARX_OK;                                                                                                              \
+	}                                                                                                                               \
+	int arx_batch_records(arx_ctx *h, arx_batch *bh, const arx_super_batch *sb, int32_t flags, int64_t *n_records, int64_t *n_bytes)    \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
+		if (!b->done[Bat::PH_PLACE]) { c->set_error("arx_batch_records before arx_batch_rfa"); return ARX_E_ARG; }                  \
+		if ((flags & 1) && !b->done[Bat::PH_POST]) { c->set_error("arx_batch_records with the duplicate flags (flags bit 0) before arx_batch_post"); return ARX_E_ARG; } \
+		if (!sb || (flags & ~1)) { c->set_error("arx_batch_records: null super-batch or unknown flag bits"); return ARX_E_ARG; }    \
+		{ const std::string bad = arx::RecordsStage<RT>::check(*sb, b->db.n_reads, b->lens_host.data()); if (!bad.empty()) { c->set_error(bad); return ARX_E_ARG; } } \
+		ARX_TRY(c, b->rt.bind(); if (int rc = b->run_records(*sb, (flags & 1) != 0)) return rc;)                                    \
+		if (n_records) *n_records = b->recs.n_records;                                                                              \
+		if (n_bytes) *n_bytes = b->recs.n_bytes;                                                                                    \
+		return ARX_OK;                                                                                                              \
+	}                                                                                                                               \
+	int arx_batch_records_fetch(arx_ctx *h, arx_batch *bh, uint8_t *stream, int64_t *rec_off)                                       \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
+		if (!b->done[Bat::PH_RECORDS]) { c->set_error("arx_batch_records_fetch before arx_batch_records (or after a later arx_batch_run / _rfa / _post / _tags / _reset)"); return ARX_E_ARG; } \
+		ARX_TRY(c, b->rt.bind(); arx::RecordsStage<RT>::fetch(b->pipe, b->recs, stream, rec_off);)                                  \
+		return ARX_OK;                                                                                                              \
+	}                                                                                                                               \
+	int arx_batch_records_view(arx_ctx *h, arx_batch *bh, const uint8_t **d_stream, int64_t *n_bytes, int64_t *n_records)           \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
+		if (!b->done[Bat::PH_RECORDS]) { c->set_error("arx_batch_records_view before arx_batch_records (or after a later arx_batch_run / _rfa / _post / _tags / _reset)"); return ARX_E_ARG; } \
+		ARX_TRY(c, b->rt.bind(); b->rt.sync();)                                                                                     \
+		if (d_stream) *d_stream = b->recs.d_stream;                                                                                 \
+		if (n_bytes) *n_bytes = b->recs.n_bytes;                                                                                    \
+		if (n_records) *n_records = b->recs.n_records;                                                                              \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_rfa_fetch(arx_ctx *h, arx_batch *bh, int32_t *cand_off, arx_cand *cands)                                          \

@@ -50,6 +50,17 @@ int arx_bam_write_select(arx_bam *h, const arx_bam_batch *batch, const int64_t *
 	}
 }
 
+int arx_bam_write_encoded(arx_bam *h, const uint8_t *stream, int64_t n_bytes, int64_t n_records)
+{
+	arx::BamSink *w = (arx::BamSink *)h;
+	try {
+		return w->write_encoded(stream, n_bytes, n_records);
+	} catch (const std::exception &e) {
+		w->error = e.what();
+		return ARX_E_IO;
+	}
+}
+
 int arx_bam_close(arx_bam *h, int64_t *stats)
 {
 	arx::BamSink *w = (arx::BamSink *)h;

@@ -1,4 +1,4 @@
-// arx_bgzf.hip -- the device BAM sink (include/arachne_amd.h: arx_bam_open_device, arx_selftest_bgzf): BamSink (bam_sink.h) with the compressor of
+// arx_bgzf.hip -- the device BAM sink (include/arachne_amd.h: arx_bam_open_device, arx_bam_write_encoded_device, arx_selftest_bgzf): BamSink (bam_sink.h) with the compressor of
 // hip_bgzf.h behind its seam.  Its own unit: the kernels of dev_bgzf.h compile next to the pipeline's.
 #include <map>
 #include <memory>
@@ -50,6 +50,30 @@ extern "C" int arx_bam_open_device(arx_ctx *ctx, const char *path, int32_t n_con
 		return ARX_E_DEVICE;
 	}
 	*out = (arx_bam *)w;
+	return ARX_OK;
+}
+
+extern "C" int arx_bam_write_encoded_device(arx_bam *h, const uint8_t *d_stream, int64_t n_bytes, int64_t n_records)
+{
+	arx::BamSink *w = (arx::BamSink *)h;
+	if (!w) return ARX_E_ARG;
+	arx::DeviceBgzf *z = dynamic_cast<arx::DeviceBgzf *>(w->comp.get());
+	if (!z) { w->error = "arx_bam_write_encoded_device on a writer of arx_bam_open: only arx_bam_open_device's writers take a device stream"; return ARX_E_ARG; }
+	if (n_bytes < 0 || n_records < 0 || (n_bytes > 0 && !d_stream)) { w->error = "arx_bam_write_encoded_device: bad arguments"; return ARX_E_ARG; }
+	if (n_bytes == 0) { if (n_records) { w->error = "arx_bam_write_encoded_device: records without bytes"; return ARX_E_ARG; } return ARX_OK; }
+	try {
+		// a write on the host side may have left whole blocks pending only if its flush failed; the carry handed on is always short of a block
+		if (!w->flush(false)) return ARX_E_IO;
+		std::vector<uint8_t> tail;
+		size_t nb = 0;
+		if (!z->run_device(w->pending.data(), w->pending.size(), d_stream, (size_t)n_bytes, w->f, w->bytes_out, nb, tail, w->error)) return ARX_E_IO;
+		w->n_blocks += (int64_t)nb; w->bytes_in += (int64_t)(nb * arx::BamSink::BLOCK_IN);
+		w->pending.swap(tail);
+		w->n_records += n_records;
+	} catch (const std::exception &e) {
+		w->error = e.what();
+		return ARX_E_IO;
+	}
 	return ARX_OK;
 }
 

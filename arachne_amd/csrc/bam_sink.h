@@ -159,6 +159,25 @@ struct BamSink {
 		return flush(false);
 	}
 
+	// arx_bam_write_encoded: records that are BAM-encoded already (what encode() writes, e.g. by the device: dev_records.h).  Checked is only what is
+	// cheap: the block_size fields must tile n_bytes into exactly n records of at least the fixed part.  ARX_OK, ARX_E_ARG (nothing appended) or ARX_E_IO
+	static uint32_t r32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+	int write_encoded(const uint8_t *stream, int64_t n_bytes, int64_t n)
+	{
+		if (n_bytes < 0 || n < 0 || (n_bytes > 0 && !stream)) { error = "arx_bam_write_encoded: bad arguments"; return ARX_E_ARG; }
+		int64_t at = 0, seen = 0;
+		while (at < n_bytes) {
+			const int64_t left = n_bytes - at;
+			const int64_t bs = left >= 4 ? (int64_t)r32(stream + at) : -1;
+			if (bs < 32 || bs > left - 4) { error = "arx_bam_write_encoded: the block_size fields do not tile the stream (record " + std::to_string(seen) + " at byte " + std::to_string(at) + ")"; return ARX_E_ARG; }
+			at += 4 + bs; ++seen;
+		}
+		if (seen != n) { error = "arx_bam_write_encoded: the stream holds " + std::to_string(seen) + " records, not " + std::to_string(n); return ARX_E_ARG; }
+		pending.insert(pending.end(), stream, stream + n_bytes);
+		n_records += n;
+		return flush(false) ? ARX_OK : ARX_E_IO;
+	}
+
 	// compresses every whole block of `pending` (all of it when `all`), writes them in order
 	bool flush(bool all)
 	{

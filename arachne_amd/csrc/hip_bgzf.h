@@ -8,7 +8,8 @@
 // DeviceBgzf owns two streams, two page-locked staging pairs and the device buffers of two groups of at most GROUP blocks, allocated once
 // (about 64 MB of page-locked and 100 MB of device memory: one per device for the life of the process, see arx_bgzf.hip).
 // run() takes the blocks of one flush in groups: while group g is uploaded, compressed, framed and its sizes come back, the framed bytes of
-// group g - 1 are downloaded and written.  Blocks reach the sink in order.
+// group g - 1 are downloaded and written.  Blocks reach the sink in order.  run_device() is run() for a stream that is in device memory already
+// (arx_bam_write_encoded_device: the records phase's output, dev_records.h): only where a group's input comes from differs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -128,14 +129,13 @@ struct DeviceBgzf : BlockCompressor {
 		}
 	}
 
-	// group g of the flush: upload, the two kernels, the sizes on their way back
-	void submit(const uint8_t *src, size_t total, size_t g)
+	// group g of the flush: its input into d_in[s] (stage(s, b0, bytes) enqueues that on st[s]), the two kernels, the sizes on their way back
+	template <class Stage> void submit(size_t total, size_t g, Stage stage)
 	{
 		const int s = (int)(g & 1);
 		const size_t b0 = g * GROUP * (size_t)BGZF_IN, bytes = total - b0 < (size_t)GROUP * BGZF_IN ? total - b0 : (size_t)GROUP * BGZF_IN;
 		const int nb = (int)((bytes + BGZF_IN - 1) / BGZF_IN);
-		memcpy(h_in[s], src + b0, bytes);
-		ARX_HIP_CHECK(hipMemcpyAsync(d_in[s], h_in[s], bytes, hipMemcpyHostToDevice, st[s]));
+		stage(s, b0, bytes);
 		hip_launch("k_bgzf_deflate", k_bgzf_deflate, dim3(nb < grid ? nb : grid), dim3(BGZF_LANES), BGZF_WORK_BYTES, st[s], d_in[s], bytes, nb, d_tok[s], d_slices[s], d_meta[s]);
 		hip_launch("k_bgzf_frame", k_bgzf_frame, dim3(nb), dim3(256), 0, st[s], d_slices[s], d_meta[s], nb, d_packed[s]);
 		ARX_HIP_CHECK(hipMemcpyAsync(h_meta[s], d_meta[s], (size_t)nb * 16, hipMemcpyDeviceToHost, st[s]));
@@ -157,8 +157,8 @@ struct DeviceBgzf : BlockCompressor {
 		return bytes;
 	}
 
-	// sink(bytes, n): n framed bytes, in order
-	template <class Sink> void compress(const uint8_t *src, size_t total, Sink sink)
+	// sink(bytes, n): n framed bytes, in order; stage: where a group's input comes from (submit)
+	template <class Stage, class Sink> void compress_from(size_t total, Stage stage, Sink sink)
 	{
 		if (!ready) throw std::runtime_error("the device compressor is not initialised");
 		if (!total) return;
@@ -171,13 +171,21 @@ struct DeviceBgzf : BlockCompressor {
 			sink(h_out[g & 1], bytes);
 		};
 		try {
-			submit(src, total, 0);
-			for (size_t g = 1; g < ng; ++g) { submit(src, total, g); drain(g - 1); }
+			submit(total, 0, stage);
+			for (size_t g = 1; g < ng; ++g) { submit(total, g, stage); drain(g - 1); }
 			drain(ng - 1);
 		} catch (...) {
 			(void)hipStreamSynchronize(st[0]); (void)hipStreamSynchronize(st[1]); // nothing of this flush stays in flight
 			throw;
 		}
+	}
+	// from host memory: through the page-locked staging of the group's stream
+	template <class Sink> void compress(const uint8_t *src, size_t total, Sink sink)
+	{
+		compress_from(total, [&](int s, size_t b0, size_t bytes) {
+			memcpy(h_in[s], src + b0, bytes);
+			ARX_HIP_CHECK(hipMemcpyAsync(d_in[s], h_in[s], bytes, hipMemcpyHostToDevice, st[s]));
+		}, sink);
 	}
 
 	bool run(const uint8_t *src, size_t total, FILE *f, int64_t &bytes_out, std::string &error) override
@@ -190,6 +198,48 @@ struct DeviceBgzf : BlockCompressor {
 				if (ok) bytes_out += (int64_t)n;
 			});
 			return ok;
+		} catch (const std::exception &e) {
+			error = e.what();
+			return false;
+		}
+	}
+	// arx_bam_write_encoded_device: what is compressed is carry[0, n_carry) (host memory: the sink's pending bytes, fewer than a block) followed
+	// by d_stream[0, n_bytes) (device memory of this device, complete).  Every whole block of that concatenation goes through the same groups,
+	// kernels and framing as run(): the carry goes up to the front of group 0's input, the group's share of d_stream follows device to device.
+	// The tail short of a block is left in `tail` (the sink's next carry).  Returns when the blocks are written
+	bool run_device(const uint8_t *carry, size_t n_carry, const uint8_t *d_stream, size_t n_bytes, FILE *f, int64_t &bytes_out, size_t &n_blocks, std::vector<uint8_t> &tail,
+	                std::string &error)
+	{
+		try {
+			if (n_carry >= (size_t)BGZF_IN) throw std::runtime_error("the device sink's carry is a whole block");
+			std::lock_guard<std::mutex> lock(mu);
+			const size_t total = n_carry + n_bytes, nb = total / BGZF_IN, used = nb * (size_t)BGZF_IN;
+			bool ok = true;
+			compress_from(used, [&](int s, size_t b0, size_t bytes) {
+				size_t c = 0; // bytes of the group that come from the carry (group 0 only: the carry is shorter than a block)
+				if (b0 < n_carry) {
+					c = n_carry - b0 < bytes ? n_carry - b0 : bytes;
+					memcpy(h_in[s], carry + b0, c);
+					ARX_HIP_CHECK(hipMemcpyAsync(d_in[s], h_in[s], c, hipMemcpyHostToDevice, st[s]));
+				}
+				if (bytes > c) ARX_HIP_CHECK(hipMemcpyAsync(d_in[s] + c, d_stream + (b0 + c - n_carry), bytes - c, hipMemcpyDeviceToDevice, st[s]));
+			}, [&](const uint8_t *p, size_t n) {
+				if (ok && fwrite(p, 1, n, f) != n) { ok = false; error = "write failed"; }
+				if (ok) bytes_out += (int64_t)n;
+			});
+			if (!ok) return false;
+			n_blocks = nb;
+			// the tail: what is left of the carry (only when no block was cut), then the end of the device stream, copied home
+			const size_t keep_c = used < n_carry ? n_carry - used : 0, d0 = used > n_carry ? used - n_carry : 0, keep_d = n_bytes - d0;
+			tail.assign(carry + (n_carry - keep_c), carry + n_carry);
+			if (keep_d) {
+				if (keep_d >= (size_t)BGZF_IN) throw std::runtime_error("the device sink's tail is a whole block");
+				ARX_HIP_CHECK(hipSetDevice(dev));
+				ARX_HIP_CHECK(hipMemcpyAsync(h_in[0], d_stream + d0, keep_d, hipMemcpyDeviceToHost, st[0]));
+				ARX_HIP_CHECK(hipStreamSynchronize(st[0]));
+				tail.insert(tail.end(), h_in[0], h_in[0] + keep_d);
+			}
+			return true;
 		} catch (const std::exception &e) {
 			error = e.what();
 			return false;

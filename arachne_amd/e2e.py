@@ -37,7 +37,7 @@ _TRACE = bool(os.environ.get("ARX_E2E_TRACE"))
 def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int = 250_000, bam_threads: int = 8, rec_threads: int = 8, level: int = 1,
         penalty: float = -4, lib_path: str = api.LIB_PATH, warm_passes: int = 0, layout: str = "workers", chunk: int = 40_000_000,
         read_groups: str = "", sample_id: str = "", feeder: str = "host", workers: int = 3, chunk_bytes: int = 0,
-        sink: str = "host"):
+        sink: str = "host", records: str = "host"):
     """fastq_pairs: [(r1, r2), ...] barcode-sorted files (plain or gzip), one worker each.  -> stats dict (pairs, seconds, pairs/s, per-stage
     seconds summed over workers).  warm_passes: untimed passes over the same files first, through the same batch handles -- a handle's first
     batch pays for its work memory (hipMalloc of several GiB: seconds once a 69 GB k-mer table sits beside it), which a run over a whole
@@ -46,14 +46,24 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
     feeder="device": ONE file pair, parsed on the GPU by one feeder thread (arx_feeder_open_device) that hands super-batches to `workers`
     worker threads (see _run_device); the default, feeder="host", is one host feeder and one worker per file pair.
     sink="device": every BAM writer, in both layouts, compresses its BGZF blocks on ref's GPU (arx_bam_open_device; `level` does not apply); the
-    files inflate to the same bytes as with the default, sink="host"."""
+    files inflate to the same bytes as with the default, sink="host".
+    records="device" (layout="workers" only, both feeders): the BAM records are encoded on the GPU (arx_batch_records) instead of fetching the
+    result slabs and building them on host threads (arx_recbuf_build + arx_bam_write's encoder): a worker fetches ONE block, the record
+    stream, and queues it for its writer thread (arx_bam_write_encoded), or with sink="device" hands it to the device sink where it lies
+    (arx_bam_write_encoded_device) -- the records never visit the host uncompressed.  arx_batch_post still runs, for the duplicate marks.  The
+    files inflate to the same bytes; fetch_s / records_s then are the stream fetch and post + the records call."""
     if sink not in ("host", "device"):
         raise ValueError(f"unknown sink {sink!r}")
+    if records not in ("host", "device"):
+        raise ValueError(f"unknown records {records!r}")
+    if records == "device" and layout == "reference":
+        raise ValueError("records='device' writes the primary records only: layout='reference' needs records='host'")
+    dev_rec = records == "device"
     sink_dev = ref if sink == "device" else None
     if feeder == "device":
         if warm_passes:
             raise ValueError("feeder='device' reads its file pair once: warm_passes must be 0")
-        return _run_device(ref, fastq_pairs, out_prefix, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, layout, chunk, read_groups, workers, chunk_bytes, sink_dev)
+        return _run_device(ref, fastq_pairs, out_prefix, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, layout, chunk, read_groups, workers, chunk_bytes, sink_dev, dev_rec)
     if feeder != "host":
         raise ValueError(f"unknown feeder {feeder!r}")
     if layout == "reference":
@@ -99,16 +109,17 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
             for e_ in written:
                 e_.set()
             werr = []
+            streams = [None, None]                      # records="device": two host buffers for the record stream, one written out while the next is fetched
 
             def writer():
                 while True:
                     item = wq.get()
                     if item is None:
                         return
-                    slot, view = item
+                    slot, write = item
                     try:
                         t_ = time.time()
-                        bam.write_view(view)
+                        write()
                         loc["bam_s"] += time.time() - t_
                     except BaseException as e:  # noqa: BLE001
                         werr.append(e)
@@ -129,17 +140,22 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
                 t2 = time.time()
                 if _TRACE:
                     print(f"[e2e] worker {k} batch {loc['batches']}: {int(v['n_pairs'])} pairs, feeder {t1 - t0:.3f}s device {t2 - t1:.3f}s", flush=True)
+                slot = loc["batches"] & 1
+                if dev_rec:
+                    n_rec = _device_records(batch, sb, bam, sink_dev, slot, written, werr, wq, streams, loc)
+                    loc["pairs"] += int(v["n_pairs"]); loc["records"] += n_rec; loc["batches"] += 1
+                    loc["feeder_s"] += t1 - t0; loc["device_s"] += t2 - t1
+                    continue
                 batch.fetch_into(buf)
                 post = batch.post_into(buf)
                 t3 = time.time()
-                slot = loc["batches"] & 1
                 written[slot].wait()                    # the buffer's last view is on disk
                 if werr:
                     raise werr[0]
                 view = rb[slot].build(sb, buf["cand_off"], buf["cands"], buf["alns"], buf["cigars"], post, threads=rec_threads)
                 t4 = time.time()
                 written[slot].clear()
-                wq.put((slot, view))
+                wq.put((slot, lambda view=view: bam.write_view(view)))
                 loc["pairs"] += int(v["n_pairs"]); loc["records"] += int(view.n_records); loc["batches"] += 1
                 loc["feeder_s"] += t1 - t0; loc["device_s"] += t2 - t1; loc["fetch_s"] += t3 - t2; loc["records_s"] += t4 - t3
             wq.put(None)
@@ -179,6 +195,40 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
     stats["pairs_per_s"] = stats["pairs"] / stats["seconds"] if stats["seconds"] > 0 else 0.0
     stats["workers"] = len(fastq_pairs)
     return stats
+
+
+def _device_records(batch, sb, bam, sink_dev, slot, written, werr, wq, streams, loc, lock=None):
+    """records="device" for one super-batch of a worker: arx_batch_post (duplicate marks), arx_batch_records, then the stream either into the
+    device sink where it lies (the call returns when its blocks are written: the batch may be reset) or home as one block into streams[slot]
+    and onto the worker's writer thread.  -> records written"""
+    import contextlib
+    t2 = time.time()
+    batch.post(fetch=False)
+    n_rec, n_bytes = batch.records(sb)
+    t3 = time.time()
+    loc["records_s"] += t3 - t2
+    guard = lock if lock is not None else contextlib.nullcontext()
+    if sink_dev is not None:
+        ptr, n_bytes, n_rec = batch.records_view()
+        with guard:
+            bam.write_encoded_device(ptr, n_bytes, n_rec)
+        loc["bam_s"] += time.time() - t3
+        return n_rec
+    written[slot].wait()                                # the buffer's last stream is on disk
+    if werr:
+        raise werr[0]
+    if streams[slot] is None or len(streams[slot]) < n_bytes:
+        streams[slot] = None
+        streams[slot] = batch.pin(np.zeros(int(n_bytes * 1.2) + 4096, dtype=np.uint8))
+    stream, _ = batch.records_fetch(out=streams[slot], offsets=False)
+    loc["fetch_s"] += time.time() - t3
+    written[slot].clear()
+
+    def write():
+        with guard:
+            bam.write_encoded(stream, n_rec)
+    wq.put((slot, write))
+    return n_rec
 
 
 def reference_header(read_groups: str = "", date: str | None = None) -> str:
@@ -275,7 +325,7 @@ def _run_reference(ref, fastq_pairs, out_dir, pairs_per_batch, bam_threads, rec_
     return stats
 
 
-def _run_device(ref, fastq_pairs, out, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, layout, chunk, read_groups, workers, chunk_bytes, sink_dev=None):
+def _run_device(ref, fastq_pairs, out, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, layout, chunk, read_groups, workers, chunk_bytes, sink_dev=None, dev_rec=False):
     """One file pair, the reference's shape (aligner.go:335-358): ONE producer -- the device feeder, whose parse runs on the GPU -- puts
     super-batches into a queue, `workers` threads take them, each with its own batch handle (arx_batch_reset_device from the feeder's device
     arrays: the bases never come back to the host for the path's sake) and everything after that as in the host-feeder loops above.
@@ -361,6 +411,7 @@ def _run_device(ref, fastq_pairs, out, pairs_per_batch, bam_threads, rec_threads
         for e_ in written:
             e_.set()
         werr = []
+        streams = [None, None]
 
         def write(view, bucket):
             if not full:
@@ -381,10 +432,10 @@ def _run_device(ref, fastq_pairs, out, pairs_per_batch, bam_threads, rec_threads
                 item = wq.get()
                 if item is None:
                     return
-                slot, view, bucket = item
+                slot, wr = item
                 try:
                     t_ = time.time()
-                    write(view, bucket)
+                    wr()
                     loc["bam_s"] += time.time() - t_
                 except BaseException as e:  # noqa: BLE001
                     werr.append(e)
@@ -407,6 +458,13 @@ def _run_device(ref, fastq_pairs, out, pairs_per_batch, bam_threads, rec_threads
                 batch.run(api.STAGE_ALN)
                 batch.rfa(v["set_pair_off"], v["do_rfa"], penalty=penalty, fetch=False)
                 t2 = time.time()
+                if dev_rec:
+                    n_pairs = int(v["n_pairs"])
+                    n_rec = _device_records(batch, sb, writers[k], sink_dev, loc["batches"] & 1, written, werr, wq, streams, loc, lock=locks[k])
+                    released.set()                      # the stream is built (and fetched or compressed): the feeder's arrays are free
+                    loc["pairs"] += n_pairs; loc["records"] += n_rec; loc["batches"] += 1
+                    loc["device_s"] += t2 - t1
+                    continue
                 batch.fetch_into(buf)
                 if full:
                     post = batch.post()
@@ -428,7 +486,7 @@ def _run_device(ref, fastq_pairs, out, pairs_per_batch, bam_threads, rec_threads
                 released.set()                          # the feeder's arrays of this super-batch are no longer needed
                 t4 = time.time()
                 written[slot].clear()
-                wq.put((slot, view, bucket))
+                wq.put((slot, lambda view=view, bucket=bucket: write(view, bucket)))
                 loc["pairs"] += n_pairs; loc["records"] += int(view.n_records); loc["batches"] += 1
                 loc["device_s"] += t2 - t1; loc["fetch_s"] += t3 - t2; loc["records_s"] += t4 - t3
         except BaseException as e:  # noqa: BLE001 -- reported by the caller's thread

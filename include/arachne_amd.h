@@ -267,6 +267,22 @@ const char *arx_bam_error(arx_bam *w);
 int arx_bam_open_device(arx_ctx *ctx, const char *path, int32_t n_contigs, const char *const *names, const int32_t *lens, const char *extra_header,
                         int32_t threads, arx_bam **out, char *msg, int32_t msg_cap);
 
+/* Appends records that are BAM-encoded already -- block_size and all, as arx_batch_records writes them (csrc/dev_records.h; the bytes
+ * BamSink::encode, csrc/bam_sink.h, produces for arx_bam_write) -- to a writer of either kind: n_bytes bytes holding exactly n_records records.
+ * Only what is cheap is checked: the block_size fields must tile n_bytes into n_records records of at least 36 bytes; otherwise ARX_E_ARG and
+ * nothing is appended.  May be mixed freely with arx_bam_write / arx_bam_write_select on one writer (AppendBams' order of calls is the file's
+ * order of records, bamwriter.go:279-282). */
+int arx_bam_write_encoded(arx_bam *w, const uint8_t *stream, int64_t n_bytes, int64_t n_records);
+/* The same from DEVICE memory, for a writer of arx_bam_open_device only (ARX_E_ARG for arx_bam_open's): the stream never visits the host.  What
+ * is compressed is the writer's carry (the bytes its last call left short of a block, fewer than 65280) followed by d_stream, cut every 65280
+ * bytes as always; the carry goes up, the stream is copied device to device into the compressor's input, the kernels, framing and write order
+ * are arx_bam_open_device's.  The tail short of a block comes home into the carry, so host and device writes interleave freely and
+ * arx_bam_close is unchanged.  The block_size chain is not walked (it is in device memory): n_records is taken on trust for the statistics.
+ * Ordering rule: d_stream must be COMPLETE when this is called -- arx_batch_records ends with its stream synchronised, as every phase does, so
+ * a pointer from arx_batch_records_view qualifies -- and must stay valid until the call returns; it returns when its blocks are written, after
+ * which the batch may be reset. */
+int arx_bam_write_encoded_device(arx_bam *w, const uint8_t *d_stream, int64_t n_bytes, int64_t n_records);
+
 /* ---- between the path and the sink: the placed candidate of every read of a super-batch as BAM records -- the part of DumpToBams /
  * AppendBam (src/aligner/bamwriter.go:283-568, 635-658) that decides flags, position, MAPQ, mate fields, template length, CIGAR op codes,
  * strand of bases and qualities and the RG / AS / XM / AM / XT / BX / VX tags of the primary record (csrc/bam_records.h lists what is left
@@ -303,6 +319,23 @@ int arx_recbuf_build_full(arx_recbuf *rb, const arx_super_batch *sb, const int32
                           const arx_cand_post *post, const arx_recbuf_full *full, int32_t threads, arx_bam_batch *view, const int32_t **bucket);
 const char *arx_recbuf_error(arx_recbuf *rb);
 void arx_recbuf_free(arx_recbuf *rb);
+
+/* ---- arx_recbuf_build -> arx_bam_write's encoder on the device: the records phase of a batch.  Writes the BAM-encoded primary record of
+ * every read (the record set and rules of arx_recbuf_build above: csrc/bam_records.h:311-336, then BamSink::encode, csrc/bam_sink.h:101-129;
+ * bamwriter.go:283-568, 635-658) as one byte stream in device memory -- byte for byte what arx_recbuf_build -> arx_bam_write would append to a
+ * writer -- from what arx_batch_rfa left there; csrc/dev_records.h restates the rules.  sb: the super-batch the batch was created from; its
+ * qualities, names, read groups, barcodes and set table are uploaded by the call (2 * sb->n_pairs == n_reads, sb->lens the batch's lengths,
+ * names of 1..254 bytes: ARX_E_ARG before anything is launched otherwise).  flags bit 0: set 0x400 from arx_batch_post's duplicate marks
+ * (ARX_E_ARG if arx_batch_post has not run); 0 = arx_recbuf_build with post == NULL.  Needs arx_batch_rfa first (ARX_E_ARG).  A read without an
+ * active candidate: ARX_E_ARG; a stream of 2^31 - 1 bytes or more: ARX_E_TOO_LARGE, split the batch.  The phase comes last (after arx_batch_post
+ * and arx_batch_tags): calling it again rebuilds it in the same memory, and a later arx_batch_run / _rfa / _post / _tags / _reset* discards it.
+ * The call returns with the batch's stream synchronised: the stream of records is complete. */
+int arx_batch_records(arx_ctx *ctx, arx_batch *b, const arx_super_batch *sb, int32_t flags, int64_t *n_records, int64_t *n_bytes);
+/* stream[n_bytes]: the record stream as one block (hand it to arx_bam_write_encoded); rec_off[n_records + 1] (may be NULL): where each record starts */
+int arx_batch_records_fetch(arx_ctx *ctx, arx_batch *b, uint8_t *stream /* n_bytes */, int64_t *rec_off /* n_records + 1, may be NULL */);
+/* the stream in device memory (for arx_bam_write_encoded_device), valid until the phase is left -- the same contract and ordering rule as
+ * arx_batch_device_view: the call waits for the batch's stream */
+int arx_batch_records_view(arx_ctx *ctx, arx_batch *b, const uint8_t **d_stream, int64_t *n_bytes, int64_t *n_records);
 
 /* ---- several GPUs behind one handle (arx_open(prefix, n_devices, ...)): one index replica per device, a super-batch of whole
  * barcodes cut by pair count (greedy longest-processing-time), every device's share on a host thread of its own, the result slabs
