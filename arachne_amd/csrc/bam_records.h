@@ -4,28 +4,26 @@
 //
 // Two modes over the same size / scan / fill passes.
 //
-// arx_recbuf_build (kept as it was first written; tests/test_e2e.py pins it): one record per read, its ACTIVE candidate (what DoDumpToBam
-// writes as `primary`, bamwriter.go:635-658), with
-//   flags      paired 0x1, proper 0x2, unmapped 0x4, mate unmapped 0x8, reverse 0x10, mate reverse 0x20, first / second 0x40 / 0x80,
-//              duplicate 0x400; "unmapped" is the reference's rule: not proper and score - 17 < 19 (:287-290, aligner.go:140-145) or the
-//              placeholder of a read without hits (pos -1)
-//   pos / mapq / mate / template length  as :287-346 (the candidate's pos is 0-based already; reverse-strand candidates carry the
-//              swapped pos/aend of aligner.go:1577-1582, so TempLen reads the same fields the reference reads)
-//   CIGAR      BWA's op codes MIDSH -> BAM's M I D S H (fixCigar's table, :248-276); read and qualities reversed for reverse-strand
-//              records (:372-375; reverseComp / reverseQual)
-//   aux        RG:Z (the R1 header's last field, reader.go:144-153), AS:i (score), XM:Z:0, AM:Z:0|1, XT:C:0, and for a unique barcode set
-//              whose barcode holds a '-' BX:Z + VX:C:1 (:555-559).
+// The rules of a record's fields -- the score rule and "unmapped", the active candidate, the flag word, MAPQ, TempLen, the CIGAR op table,
+// which sets carry BX / VX -- are bam_rules.h's functions, shared by both modes here, the encoder (bam_sink.h) and the device (dev_records.h).
+//
+// arx_recbuf_build (kept as it was first written; tests/test_e2e.py pins it): one record per read, its ACTIVE candidate (bam_active), with
+//   flags / pos / mapq / mate / template length  from bam_unmapped of the candidate and of its mate, both positions as the candidates hold
+//              them (0-based already); an unmapped record has rid / pos -1 and mapq 0, an unmapped mate rid / pos -1
+//   CIGAR      bam_cigar_word; read and qualities reversed for reverse-strand records (:372-375; reverseComp / reverseQual)
+//   aux        RG:Z (the R1 header's last field, reader.go:144-153), AS:i (score), XM:Z:0, AM:Z:0|1, XT:C:0, and for a set with bam_set_bx
+//              BX:Z + VX:C:1 (:555-559).
 // That is NOT the reference's tag set: the reference never writes a read without mapq_data -- every Alignment is created with one
 // (aligner.go:1601) and estimateMapQualities fills it for every barcode, with or without RFA (aligner.go:471, 496).  Its AS also is the
 // BWA score rather than mapq_data.score, and its mate / TempLen rules read the mate's own is_proper.  Those stay as they are in this mode.
 //
 // arx_recbuf_build_full: the reference's record set.  Every read's primary record, then its split record (Alignment.secondary from
 // arx_split: flag 0x100, TempLen 0, HardClip of :660-689 after the reverse-complement), with
-//   flags / mate / TempLen  as :286-366 with AppendBam's in-place mutation: a record the score rule unmaps gets pos = -1, mapq = 0 before
+//   flags / mate / TempLen  the same functions on positions AS MUTATED by AppendBam (:286-366): a record the score rule unmaps gets pos = -1, mapq = 0 before
 //              anything is computed, and every record written later sees that -- read 2p is written before 2p+1, so 2p+1 sees its mate
 //              at pos -1 (mate unmapped, TempLen 0), a split record's SA is left out when its primary was unmapped, and a forward primary
 //              the rule unmaps while its mate stays mapped on the same contig gets TempLen mate.aend - (-1), the reference's form.  The
-//              mate-unmapped test is the reference's `mate.pos == -1 || (!primary.is_proper && mate.score - 17 < 19)`.
+//              mate-unmapped test is the reference's: mate.pos == -1, or the score rule on the mate's score under the PRIMARY's is_proper.
 //   aux        RG XS XC AC AS XM AM XT SA BX VX DM in the reference's order (:390-563), integers as `i` (auxify_int), strings NUL-ended.
 //              XS / AS / XM / XT / XC's second best / DM's inputs come from arx_batch_tags; XC / AC list "ref,read,1;" per mismatch location
 //              of the second best / the record's own alignment (arx_batch_post's lists); SA (:462-494) "contig,pos,strand,cigar,mapq,NM;"
@@ -44,6 +42,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/arachne_amd.h"
+#include "bam_rules.h"
 
 namespace arx {
 
@@ -90,10 +89,7 @@ struct RecBuf {
 	std::vector<int64_t> rbase; // full mode: record of every read's primary (its split record follows it)
 	std::vector<int32_t> bucket; // full mode: position bucket of every record
 
-	static inline bool unmapped(const arx_cand &a) { return a.pos == -1 || (!a.is_proper && a.score - 17 < 19); }
-
 	// What AppendBam sees when it writes read r's records (full mode): the mutation of the score rule applied in write order
-	static inline bool rule(const arx_cand &a) { return !a.is_proper && a.score - 17 < 19; } // IsUnmapped (aligner.go:140-145)
 	static inline bool pair_at(const arx_cand &a, int64_t apos, const arx_cand &b, int64_t bpos) // isPair (aligner.go:1032) on positions as mutated
 	{
 		if (a.reversed == b.reversed || a.rid != b.rid) return false;
@@ -107,7 +103,6 @@ struct RecBuf {
 		int64_t spos;          // the split record's pos as written
 		int hc0, hc1;          // HardClip: bases cut at the front / the back of the split record
 	};
-	static inline uint8_t mapq_byte(int32_t q) { return (uint8_t)(q < 0 ? 0 : (q > 255 ? 255 : q)); }
 
 	// sb: the super-batch the batch was created from; cand_off / cands: arx_batch_rfa_fetch; alns / cigars: arx_batch_fetch (cands[].reg indexes
 	// them); post: arx_batch_post_fetch's per-candidate records or NULL (then no duplicate flags); full: null for arx_recbuf_build's record set
@@ -127,30 +122,25 @@ struct RecBuf {
 		std::vector<int64_t> base_off((size_t)NR + 1, 0), pair_set((size_t)NP);
 		for (int64_t r = 0; r < NR; ++r) base_off[(size_t)r + 1] = base_off[(size_t)r] + sb.lens[r];
 		for (int s = 0; s < sb.n_sets; ++s) for (int64_t p = sb.set_pair_off[s]; p < sb.set_pair_off[s + 1]; ++p) pair_set[(size_t)p] = s;
-		// which sets get BX / VX: attach_bx = unique_barcode (aligner.go:474, 499) and a '-' in the barcode (bamwriter.go:389, 555)
 		std::vector<uint8_t> set_bx((size_t)sb.n_sets, 0);
-		for (int s = 0; s < sb.n_sets; ++s) {
-			const char *b = sb.barcodes + sb.barcode_off[s]; const int64_t bl = sb.barcode_off[s + 1] - sb.barcode_off[s];
-			set_bx[(size_t)s] = sb.unique[s] && memchr(b, '-', (size_t)bl) != nullptr;
-		}
+		for (int s = 0; s < sb.n_sets; ++s) set_bx[(size_t)s] = bam_set_bx(sb.unique[s], sb.barcodes + sb.barcode_off[s], sb.barcode_off[s + 1] - sb.barcode_off[s]);
 		bool bad = false;
 		auto par = [&](auto fn) {
 			std::vector<std::thread> th;
 			for (int t = 0; t < threads; ++t) th.emplace_back([&, t]() { const int64_t lo = NR * t / threads, hi = NR * (t + 1) / threads; for (int64_t r = lo; r < hi; ++r) fn(r); });
 			for (auto &x : th) x.join();
 		};
-		auto active_of = [&](int64_t r) { int a = -1; for (int i = cand_off[r]; i < cand_off[r + 1]; ++i) if (cands[i].active) a = i; return a; };
 		auto state = [&](int64_t r) { // full mode
 			ReadState st;
 			st.a = act[(size_t)r]; st.am = act[(size_t)(r ^ 1)]; st.s = full->split[r].split;
 			const arx_cand &c = cands[st.a], &m = cands[st.am];
-			st.cpos = rule(c) ? -1 : c.pos;
-			st.mpos = ((r & 1) && rule(m)) ? -1 : m.pos;
-			st.mate_un = st.mpos == -1 || (!c.is_proper && m.score - 17 < 19);
+			st.cpos = bam_score_rule(c) ? -1 : c.pos;
+			st.mpos = ((r & 1) && bam_score_rule(m)) ? -1 : m.pos;
+			st.mate_un = st.mpos == -1 || bam_score_rule(c.is_proper, m.score);
 			st.spos = -1; st.hc0 = st.hc1 = 0;
 			if (st.s >= 0) {
 				const arx_cand &x = cands[st.s];
-				st.spos = (!full->split[r].is_proper && x.score - 17 < 19) ? -1 : x.pos;
+				st.spos = bam_score_rule(full->split[r].is_proper, x.score) ? -1 : x.pos;
 				const arx_aln &al = alns[x.reg];
 				const uint32_t *w = cigs + al.cigar_off;
 				if (al.n_cigar >= 1 && (w[0] & 15u) == 3) st.hc0 = (int)(w[0] >> 4);                                  // BWA's S = 3 (BAM's 4)
@@ -212,7 +202,7 @@ struct RecBuf {
 		};
 		// pass 1: the active candidate and the sizes of every record
 		par([&](int64_t r) {
-			int a = active_of(r); // exactly one per read
+			int a = bam_active(cands, cand_off, r); // exactly one per read
 			if (a < 0) { bad = true; a = cand_off[r]; }
 			act[(size_t)r] = a;
 		});
@@ -229,10 +219,7 @@ struct RecBuf {
 			cigar_off[(size_t)q + 1] = c.reg >= 0 ? alns[c.reg].n_cigar : 0;
 			seq_off[(size_t)q + 1] = sb.lens[r];
 			if (!full) {
-				const int64_t rgl = sb.rg_off[p + 1] - sb.rg_off[p];
-				int64_t ax = (rgl > 0 ? 3 + rgl + 1 : 0) + 7 /* AS:i as int32 */ + 5 /* XM:Z:0 */ + 5 /* AM:Z:x */ + 4 /* XT:C:0 */;
-				if (set_bx[(size_t)s]) ax += 3 + (sb.barcode_off[s + 1] - sb.barcode_off[s]) + 1 + 4 /* VX:C:1 */;
-				aux_off[(size_t)q + 1] = ax;
+				aux_off[(size_t)q + 1] = bam_first_aux_len(sb.rg_off[p + 1] - sb.rg_off[p], set_bx[(size_t)s] != 0, sb.barcode_off[s + 1] - sb.barcode_off[s]);
 				return;
 			}
 			const ReadState st = state(r);
@@ -253,7 +240,6 @@ struct RecBuf {
 		names.resize((size_t)name_off[(size_t)NRec] + 1); cigars.resize((size_t)cigar_off[(size_t)NRec] + 1); seq.resize((size_t)seq_off[(size_t)NRec] + 1); qual.resize((size_t)seq_off[(size_t)NRec] + 1);
 		aux.resize((size_t)aux_off[(size_t)NRec] + 1);
 		// pass 2: fill
-		static const uint32_t op_table[5] = {0, 1, 2, 4, 5}; // fixCigar (bamwriter.go:248-254): BWA's MIDSH -> BAM's M I D S H
 		static const char comp[5] = {'T', 'G', 'C', 'A', 'N'}, fwd[5] = {'A', 'C', 'G', 'T', 'N'};
 		// name, CIGAR (BAM codes; S -> H at both ends for a split record), bases and qualities of record q from candidate x of read r
 		auto fill_body = [&](int64_t r, int64_t q, const arx_cand &x, int hc0, int hc1, bool hard) {
@@ -262,7 +248,7 @@ struct RecBuf {
 			if (x.reg >= 0) {
 				const arx_aln &al = alns[x.reg];
 				uint32_t *dst = cigars.data() + cigar_off[(size_t)q];
-				for (int k = 0; k < al.n_cigar; ++k) { const uint32_t w = cigs[al.cigar_off + k]; const uint32_t op = w & 15u; dst[k] = (w & ~15u) | (op < 5 ? op_table[op] : op); }
+				for (int k = 0; k < al.n_cigar; ++k) dst[k] = bam_cigar_word(cigs[al.cigar_off + k]);
 				if (hard && al.n_cigar >= 1 && (dst[0] & 15u) == 4) dst[0] = (dst[0] & ~15u) | 5u;                                   // HardClip (:660-689)
 				if (hard && al.n_cigar >= 2 && (dst[al.n_cigar - 1] & 15u) == 4) dst[al.n_cigar - 1] = (dst[al.n_cigar - 1] & ~15u) | 5u;
 			}
@@ -275,32 +261,28 @@ struct RecBuf {
 				else { const uint8_t y = b[k]; so[k - lo] = (uint8_t)fwd[y > 4 ? 4 : y]; qo[k - lo] = (uint8_t)qs[k]; }
 			}
 		};
+		// the fixed fields of record q: candidate x written at xpos (-1: unmapped) with MAPQ mq, its mate m at mpos
+		auto put_fields = [&](int64_t q, uint32_t fl, const arx_cand &x, int64_t xpos, int32_t mq, bool mate_un, const arx_cand &m, int64_t mpos, int32_t tl) {
+			flag[(size_t)q] = (int32_t)fl; rid[(size_t)q] = xpos == -1 ? -1 : x.rid; pos[(size_t)q] = (int32_t)xpos; mapq[(size_t)q] = xpos == -1 ? 0 : (uint8_t)bam_mapq(mq);
+			mate_rid[(size_t)q] = mate_un ? -1 : m.rid; mate_pos[(size_t)q] = mate_un ? -1 : (int32_t)mpos; tlen[(size_t)q] = tl;
+		};
 		par([&](int64_t r) {
 			const int64_t q = rbase[(size_t)r];
 			const arx_cand &c = cands[act[(size_t)r]], &m = cands[act[(size_t)(r ^ 1)]];
 			const int64_t p = r >> 1; const int s = (int)pair_set[(size_t)p];
 			if (full) {
 				const ReadState st = state(r);
-				const int32_t base_fl = 0x1 | ((r & 1) ? 0x80 : 0x40) | (st.mate_un ? 0x8 : (m.reversed ? 0x20 : 0));
-				const int32_t mrid = st.mate_un ? -1 : m.rid, mpos = st.mate_un ? -1 : (int32_t)st.mpos;
-				int32_t fl = base_fl | (c.is_proper ? 0x2 : 0) | (post[st.a].duplicate ? 0x400 : 0) | (st.cpos == -1 ? 0x4 : 0) | (c.reversed ? 0x10 : 0);
-				flag[(size_t)q] = fl;
-				rid[(size_t)q] = st.cpos == -1 ? -1 : c.rid; pos[(size_t)q] = (int32_t)st.cpos; mapq[(size_t)q] = st.cpos == -1 ? 0 : mapq_byte(c.mapq);
-				mate_rid[(size_t)q] = mrid; mate_pos[(size_t)q] = mpos;
-				int32_t tl = 0;
-				if (st.mpos != -1 && c.rid == m.rid && (c.is_proper || m.score - 17 >= 19)) tl = c.reversed ? -(int32_t)(c.aend - st.mpos) : (int32_t)(m.aend - st.cpos); // :329-343
-				tlen[(size_t)q] = tl;
-				bucket[(size_t)q] = rule(c) ? full->unmapped_file : full->contig_file[c.rid] + (int32_t)(c.pos / full->chunk);
+				put_fields(q, bam_flag(r & 1, c.is_proper, st.cpos == -1, st.mate_un, m.reversed, c.reversed, post[st.a].duplicate, false), c, st.cpos, c.mapq, st.mate_un, m, st.mpos,
+				           bam_tlen(c, m, st.cpos, st.mpos));
+				bucket[(size_t)q] = bam_score_rule(c) ? full->unmapped_file : full->contig_file[c.rid] + (int32_t)(c.pos / full->chunk);
 				fill_body(r, q, c, 0, 0, false);
 				AuxOut o{aux.data() + aux_off[(size_t)q]};
 				full_aux(r, st, false, o);
 				if (st.s >= 0) {
 					const arx_cand &x = cands[st.s];
 					const arx_split &S = full->split[r];
-					fl = base_fl | ((S.is_proper && pair_at(x, st.spos, m, st.mpos)) ? 0x2 : 0) | (post[st.s].duplicate ? 0x400 : 0) | 0x100 | (st.spos == -1 ? 0x4 : 0) | (x.reversed ? 0x10 : 0);
-					flag[(size_t)q + 1] = fl;
-					rid[(size_t)q + 1] = st.spos == -1 ? -1 : x.rid; pos[(size_t)q + 1] = (int32_t)st.spos; mapq[(size_t)q + 1] = st.spos == -1 ? 0 : mapq_byte(S.mapq);
-					mate_rid[(size_t)q + 1] = mrid; mate_pos[(size_t)q + 1] = mpos; tlen[(size_t)q + 1] = 0;
+					put_fields(q + 1, bam_flag(r & 1, S.is_proper && pair_at(x, st.spos, m, st.mpos), st.spos == -1, st.mate_un, m.reversed, x.reversed, post[st.s].duplicate, true), x, st.spos, S.mapq,
+					           st.mate_un, m, st.mpos, 0);
 					bucket[(size_t)q + 1] = st.spos == -1 ? full->unmapped_file : full->contig_file[x.rid] + (int32_t)(x.pos / full->chunk);
 					fill_body(r, q + 1, x, st.hc0, st.hc1, true);
 					AuxOut o2{aux.data() + aux_off[(size_t)q + 1]};
@@ -308,32 +290,15 @@ struct RecBuf {
 				}
 				return;
 			}
-			const bool un = unmapped(c), mun = unmapped(m);
-			int32_t fl = 0x1 | ((r & 1) ? 0x80 : 0x40);
-			if (c.is_proper) fl |= 0x2;
-			if (mun) fl |= 0x8; else if (m.reversed) fl |= 0x20;
-			if (post && post[act[(size_t)r]].duplicate) fl |= 0x400;
-			if (un) fl |= 0x4;
-			if (c.reversed) fl |= 0x10;
-			flag[(size_t)q] = fl;
-			rid[(size_t)q] = un ? -1 : c.rid; pos[(size_t)q] = un ? -1 : (int32_t)c.pos; mapq[(size_t)q] = un ? 0 : mapq_byte(c.mapq);
-			mate_rid[(size_t)q] = mun ? -1 : m.rid; mate_pos[(size_t)q] = mun ? -1 : (int32_t)m.pos;
-			int32_t tl = 0;
-			if (m.pos != -1 && c.rid == m.rid && (c.is_proper || m.score - 17 >= 19)) tl = c.reversed ? -(int32_t)(c.aend - m.pos) : (int32_t)(m.aend - c.pos); // bamwriter.go:329-343
-			tlen[(size_t)q] = tl;
+			const bool un = bam_unmapped(c), mun = bam_unmapped(m);
+			put_fields(q, bam_flag(r & 1, c.is_proper, un, mun, m.reversed, c.reversed, post && post[act[(size_t)r]].duplicate, false), c, un ? -1 : c.pos, c.mapq, mun, m, m.pos,
+			           bam_tlen(c, m, c.pos, m.pos));
 			fill_body(r, q, c, 0, 0, false);
-			uint8_t *a = aux.data() + aux_off[(size_t)q];
+			AuxOut o{aux.data() + aux_off[(size_t)q]};
 			const int64_t rgl = sb.rg_off[p + 1] - sb.rg_off[p];
-			if (rgl > 0) { *a++ = 'R'; *a++ = 'G'; *a++ = 'Z'; memcpy(a, sb.rgs + sb.rg_off[p], (size_t)rgl); a += rgl; *a++ = 0; }
-			*a++ = 'A'; *a++ = 'S'; *a++ = 'i'; { const int32_t v = c.score; memcpy(a, &v, 4); a += 4; }
-			*a++ = 'X'; *a++ = 'M'; *a++ = 'Z'; *a++ = '0'; *a++ = 0;
-			*a++ = 'A'; *a++ = 'M'; *a++ = 'Z'; *a++ = c.active_molecule ? '1' : '0'; *a++ = 0;
-			*a++ = 'X'; *a++ = 'T'; *a++ = 'C'; *a++ = 0;
-			if (set_bx[(size_t)s]) {
-				const int64_t bl = sb.barcode_off[s + 1] - sb.barcode_off[s];
-				*a++ = 'B'; *a++ = 'X'; *a++ = 'Z'; memcpy(a, sb.barcodes + sb.barcode_off[s], (size_t)bl); a += bl; *a++ = 0;
-				*a++ = 'V'; *a++ = 'X'; *a++ = 'C'; *a++ = 1;
-			}
+			if (rgl > 0) o.z("RG", sb.rgs + sb.rg_off[p], (size_t)rgl);
+			o.i32("AS", c.score); o.z("XM", "0", 1); o.z("AM", c.active_molecule ? "1" : "0", 1); o.tag("XT", 'C'); o.put("", 1);
+			if (set_bx[(size_t)s]) { o.z("BX", sb.barcodes + sb.barcode_off[s], (size_t)(sb.barcode_off[s + 1] - sb.barcode_off[s])); o.tag("VX", 'C'); o.put("\1", 1); }
 		});
 		view->n_records = NRec;
 		view->name_off = name_off.data(); view->names = names.data(); view->flag = flag.data(); view->rid = rid.data(); view->pos = pos.data(); view->mapq = mapq.data();

@@ -23,6 +23,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/arachne_amd.h"
+#include "bam_rules.h"
 
 namespace arx {
 
@@ -71,17 +72,6 @@ struct BamSink {
 		return flush(true); // the header ends its own block(s), as htslib and biogo write it
 	}
 
-	// reg2bin (SAM specification 5.3): the bin of [beg, end)
-	static int reg2bin(int64_t beg, int64_t end)
-	{
-		--end;
-		if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-		if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-		if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-		if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-		if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-		return 0;
-	}
 	static uint8_t base4(uint8_t c)
 	{
 		switch (c) { // "=ACMGRSVTWYHKDBN"
@@ -104,16 +94,10 @@ struct BamSink {
 		const size_t l_name = (size_t)(b.name_off[i + 1] - b.name_off[i]) + 1, n_cig = (size_t)(b.cigar_off[i + 1] - b.cigar_off[i]);
 		const size_t l_seq = (size_t)(b.seq_off[i + 1] - b.seq_off[i]), l_aux = (size_t)(b.aux_off[i + 1] - b.aux_off[i]);
 		const uint32_t *cg = b.cigars + b.cigar_off[i];
-		int64_t ref_len = 0;
-		for (size_t k = 0; k < n_cig; ++k) { const uint32_t op = cg[k] & 15; if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += cg[k] >> 4; }
-		const int64_t pos = b.pos[i];
-		const int bin = pos < 0 ? 4680 : reg2bin(pos, pos + (ref_len > 0 ? ref_len : 1)); // unmapped: reg2bin(-1, 0)
-		w32(p, (uint32_t)(sz - 4));
-		w32(p + 4, (uint32_t)b.rid[i]); w32(p + 8, (uint32_t)pos);
-		p[12] = (uint8_t)l_name; p[13] = b.mapq[i]; w16(p + 14, (uint32_t)bin);
-		w16(p + 16, (uint32_t)n_cig); w16(p + 18, (uint32_t)b.flag[i]);
-		w32(p + 20, (uint32_t)l_seq);
-		w32(p + 24, (uint32_t)b.mate_rid[i]); w32(p + 28, (uint32_t)b.mate_pos[i]); w32(p + 32, (uint32_t)b.tlen[i]);
+		uint32_t fixed[9];
+		bam_fixed(fixed, (int64_t)sz, b.rid[i], b.pos[i], (uint8_t)l_name, b.mapq[i], bam_bin(b.pos[i], bam_ref_len(cg, (int)n_cig, false)), (uint32_t)n_cig, (uint32_t)b.flag[i], (uint32_t)l_seq,
+		          b.mate_rid[i], b.mate_pos[i], b.tlen[i]);
+		for (int k = 0; k < 9; ++k) w32(p + 4 * k, fixed[k]);
 		uint8_t *q = p + 36;
 		memcpy(q, b.names + b.name_off[i], l_name - 1); q[l_name - 1] = 0; q += l_name;
 		for (size_t k = 0; k < n_cig; ++k) w32(q + 4 * k, cg[k]);
@@ -146,7 +130,7 @@ struct BamSink {
 			const int64_t i = rec(k);
 			if (i < 0 || i >= b.n_records) { error = "record index " + std::to_string(i) + " outside the batch"; return false; }
 			const int64_t ln = b.name_off[i + 1] - b.name_off[i], nc = b.cigar_off[i + 1] - b.cigar_off[i];
-			if (ln < 1 || ln > 254) { error = "read name of record " + std::to_string(i) + " must be 1..254 bytes"; return false; }
+			if (!bam_name_ok(ln)) { error = ARX_BAM_NAME_TEXT(i); return false; }
 			if (nc < 0 || nc > 65535) { error = "record " + std::to_string(i) + " has more than 65535 CIGAR operations"; return false; }
 		}
 		std::vector<size_t> off((size_t)n + 1, 0);

@@ -29,10 +29,7 @@
 #define ARX_BGZF_ADD(p, v) atomicAdd((unsigned int *)(p), (unsigned int)(v))
 #define ARX_BGZF_OR(p, v) atomicOr((unsigned int *)(p), (unsigned int)(v))
 #else
-#ifndef ARX_DEV
-#define ARX_DEV
-#define ARX_DEVI inline
-#endif
+#include "arx_hd.h"
 #define ARX_BGZF_MAX(p, v) (*(p) = *(p) > (uint32_t)(v) ? *(p) : (uint32_t)(v))
 #define ARX_BGZF_ADD(p, v) (*(p) += (uint32_t)(v))
 #define ARX_BGZF_OR(p, v) (*(p) |= (uint32_t)(v))

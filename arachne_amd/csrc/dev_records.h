@@ -1,20 +1,12 @@
-// dev_records.h -- the primary BAM record of every read, encoded on the device: RecBuf::build with full == nullptr (bam_records.h:311-336)
-// followed by BamSink::encode (bam_sink.h:101-129), restated as functors over the arrays a placed batch has in HBM -- the part of DumpToBams /
-// AppendBam (src/aligner/bamwriter.go:283-568, 635-658) that bam_records.h's first mode covers, rule for rule:
-//   active candidate   the LAST candidate of the read with `active` set (RecBuf's active_of); a read without one raises REC_ERR_NO_ACTIVE
-//   unmapped(c)        c.pos == -1 || (!c.is_proper && c.score - 17 < 19)                                            (:287-290, aligner.go:140-145)
-//   flags              0x1, 0x2 proper, 0x4 unmapped, 0x8 mate unmapped else 0x20 mate reversed, 0x10 reversed, 0x40 / 0x80, 0x400 duplicate (only
-//                      when the caller asks for arx_batch_post's marks)
-//   rid / pos / mapq   -1 / -1 / 0 when unmapped, mapq clamped to 0..255; mate rid / pos -1 when the mate is unmapped
-//   tlen               bam_records.h:322 (bamwriter.go:329-343)
-//   CIGAR              BWA's MIDSH -> BAM's {0, 1, 2, 4, 5} (fixCigar, :248-254); none for the placeholder (reg < 0)
-//   bin                4680 for pos < 0, else reg2bin(pos, pos + max(ref_len, 1)), ref_len over BAM ops 0, 2, 3, 7, 8
-//   name               l_read_name = length + 1, NUL-terminated
+// dev_records.h -- the primary BAM record of every read, encoded on the device: what RecBuf::build's first mode (bam_records.h) followed by
+// BamSink::encode (bam_sink.h) writes, as functors over the arrays a placed batch has in HBM.  Every rule of the record's fields -- active
+// candidate, unmapped, flags, mapq, TempLen, CIGAR ops, bin, aux length, the fixed part -- is bam_rules.h's, shared with those two; what is
+// stated here is where each byte of the stream comes from (rec_byte):
+//   name, CIGAR        the name NUL-terminated; bam_cigar_word of the alignment's words, none for the placeholder (reg < 0)
 //   bases              4-bit codes of ACGTN (1, 2, 4, 8, 15), high nibble first, complemented and reversed for a reverse-strand candidate; an odd
-//                      length leaves a zero low nibble.  Qualities minus 33, reversed likewise (:372-375)
-//   aux                RG:Z (only a non-empty read group), AS:i as int32, XM:Z:0, AM:Z:0|1, XT:C:0, BX:Z + VX:C:1 for a unique set whose barcode
-//                      holds a '-' (:555-559)
-// Compiled for the device and for the host test double.
+//                      length leaves a zero low nibble.  Qualities minus 33, reversed likewise (bamwriter.go:372-375)
+//   aux                RG:Z (only a non-empty read group), AS:i as int32, XM:Z:0, AM:Z:0|1, XT:C:0, BX:Z + VX:C:1 for a set with bam_set_bx
+// A read without an active candidate raises REC_ERR_NO_ACTIVE.  Compiled for the device and for the host test double.
 //
 // Launch order (pipeline_records.h), every functor through launch_wide:
 //   KBamRecSize    one read per lane: the active candidates of the read and its mate, the record's size and where its parts begin, its
@@ -23,6 +15,7 @@
 //   KBamRecFill    one aligned 16-byte word of the stream per lane, see there
 #pragma once
 #include "arx_dev.h"
+#include "bam_rules.h"
 #include "dev_rfa.h"
 #include "dev_post.h"
 
@@ -30,7 +23,6 @@ namespace arx {
 
 enum : uint32_t { REC_ERR_NO_ACTIVE = 1 };
 constexpr int REC_TILE = 256;       // bytes of the stream per entry of the tile table
-constexpr int REC_FIXED_AUX = 21;   // AS:i (7) XM:Z:0 (5) AM:Z:x (5) XT:C:0 (4)
 
 struct alignas(16) RecWord16 { uint32_t w[4]; };
 
@@ -44,9 +36,9 @@ struct RecInputs {
 	int32_t n_sets;
 };
 
-// per record: sizes and starts of its parts (byte offsets from the record's first byte) and its fixed part as BamSink::encode lays it out
+// per record: sizes and starts of its parts (byte offsets from the record's first byte) and its fixed part (bam_fixed)
 struct RecMeta {
-	uint32_t fixed[9];            // block_size, refID, pos, l_read_name | mapq << 8 | bin << 16, n_cigar_op | flag << 16, l_seq, next_refID, next_pos, tlen
+	uint32_t fixed[9];
 	int32_t size;                 // whole record, block_size included
 	int32_t o_cig, o_seq, o_qual, o_aux; // name starts at 36
 	int32_t cig_src;              // first CIGAR word of the candidate's alignment in the batch's CIGAR array
@@ -57,32 +49,13 @@ struct RecMeta {
 };
 static_assert(sizeof(RecMeta) == 96, "RecMeta is read as six 16-byte words");
 
-ARX_DEVI bool rec_unmapped(const Cand &a) { return a.pos == -1 || (!a.is_proper && a.score - 17 < 19); }
-ARX_DEVI uint32_t rec_bam_op(uint32_t w) { const uint32_t op = w & 15u; return (w & ~15u) | (op < 5 ? (0x54210u >> (4 * op)) & 15u : op); }
-ARX_DEVI int rec_reg2bin(int64_t beg, int64_t end) // reg2bin (SAM specification 5.3), as bam_sink.h:75-84
-{
-	--end;
-	if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-	if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-	if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-	if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-	if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-	return 0;
-}
-ARX_DEVI int rec_active(const Cand *cands, const int32_t *cand_off, int r)
-{
-	int a = -1;
-	for (int i = cand_off[r]; i < cand_off[r + 1]; ++i) if (cands[i].active) a = i;
-	return a;
-}
-
 struct KBamRecSize {
 	const Cand *cands; const int32_t *cand_off; const Aln *alns; const uint32_t *cig; const CandPost *post; // post: null = no duplicate flags
 	const int32_t *lens, *base_off; RecInputs in;
 	RecMeta *meta; int32_t *size; uint32_t *err;
 	ARX_DEV void operator()(int r, int) const
 	{
-		int a = rec_active(cands, cand_off, r), am = rec_active(cands, cand_off, r ^ 1);
+		int a = bam_active(cands, cand_off, r), am = bam_active(cands, cand_off, r ^ 1);
 		if (a < 0) { ARX_ATOMIC_OR(err, REC_ERR_NO_ACTIVE); a = cand_off[r]; }
 		if (am < 0) am = cand_off[r ^ 1]; // (the mate's own lane raises the bit)
 		const Cand &c = cands[a], &m = cands[am];
@@ -90,31 +63,19 @@ struct KBamRecSize {
 		int lo = 0, hi = in.n_sets; // the set of pair p: the last one that starts at or before it
 		while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (in.set_pair_off[mid] <= p) lo = mid; else hi = mid; }
 		const int s = lo;
-		const bool un = rec_unmapped(c), mun = rec_unmapped(m);
-		uint32_t fl = 0x1u | ((r & 1) ? 0x80u : 0x40u);
-		if (c.is_proper) fl |= 0x2;
-		if (mun) fl |= 0x8; else if (m.reversed) fl |= 0x20;
-		if (post && post[a].duplicate) fl |= 0x400;
-		if (un) fl |= 0x4;
-		if (c.reversed) fl |= 0x10;
+		const bool un = bam_unmapped(c), mun = bam_unmapped(m);
+		const uint32_t fl = bam_flag(r & 1, c.is_proper, un, mun, m.reversed, c.reversed, post && post[a].duplicate, false);
 		const int32_t rid = un ? -1 : c.rid, pos = un ? -1 : (int32_t)c.pos;
-		const uint32_t mapq = un ? 0u : (uint32_t)(c.mapq < 0 ? 0 : (c.mapq > 255 ? 255 : c.mapq));
-		int32_t tl = 0;
-		if (m.pos != -1 && c.rid == m.rid && (c.is_proper || m.score - 17 >= 19)) tl = c.reversed ? -(int32_t)(c.aend - m.pos) : (int32_t)(m.aend - c.pos); // bamwriter.go:329-343
+		const uint32_t mapq = un ? 0u : bam_mapq(c.mapq);
+		const int32_t tl = bam_tlen(c, m, c.pos, m.pos);
 		const int n_cig = c.reg >= 0 ? alns[c.reg].n_cigar : 0, cig_src = c.reg >= 0 ? alns[c.reg].cigar_off : 0;
-		int64_t ref_len = 0;
-		for (int k = 0; k < n_cig; ++k) { const uint32_t w = rec_bam_op(cig[cig_src + k]), op = w & 15u; if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += w >> 4; }
-		const int bin = pos < 0 ? 4680 : rec_reg2bin(pos, (int64_t)pos + (ref_len > 0 ? ref_len : 1));
+		const int bin = bam_bin(pos, bam_ref_len(cig + cig_src, n_cig, true));
 		const int l_name = (int)(in.name_off[p + 1] - in.name_off[p]) + 1, L = lens[r];
 		const int rgl = (int)(in.rg_off[p + 1] - in.rg_off[p]), bcl = (int)(in.barcode_off[s + 1] - in.barcode_off[s]);
 		const bool bx = in.set_bx[s] != 0;
-		const int l_aux = (rgl > 0 ? 3 + rgl + 1 : 0) + REC_FIXED_AUX + (bx ? 3 + bcl + 1 + 4 : 0);
 		RecMeta t;
-		t.o_cig = 36 + l_name; t.o_seq = t.o_cig + 4 * n_cig; t.o_qual = t.o_seq + (L + 1) / 2; t.o_aux = t.o_qual + L; t.size = t.o_aux + l_aux;
-		t.fixed[0] = (uint32_t)(t.size - 4); t.fixed[1] = (uint32_t)rid; t.fixed[2] = (uint32_t)pos;
-		t.fixed[3] = (uint32_t)l_name | mapq << 8 | (uint32_t)bin << 16;
-		t.fixed[4] = ((uint32_t)n_cig & 0xffffu) | fl << 16;
-		t.fixed[5] = (uint32_t)L; t.fixed[6] = (uint32_t)(mun ? -1 : m.rid); t.fixed[7] = (uint32_t)(mun ? -1 : (int32_t)m.pos); t.fixed[8] = (uint32_t)tl;
+		t.o_cig = 36 + l_name; t.o_seq = t.o_cig + 4 * n_cig; t.o_qual = t.o_seq + (L + 1) / 2; t.o_aux = t.o_qual + L; t.size = t.o_aux + bam_first_aux_len(rgl, bx, bcl);
+		bam_fixed(t.fixed, t.size, rid, pos, (uint32_t)l_name, mapq, bin, (uint32_t)n_cig, fl, (uint32_t)L, mun ? -1 : m.rid, mun ? -1 : (int32_t)m.pos, tl);
 		t.cig_src = cig_src; t.l_seq = L; t.base_off = base_off[r];
 		t.bits = (c.reversed ? 1 : 0) | (c.active_molecule ? 2 : 0) | (bx ? 4 : 0);
 		t.score = c.score; t.set = s; t.rgl = rgl; t.bcl = bcl; t.pad[0] = t.pad[1] = 0;
@@ -149,7 +110,7 @@ ARX_DEVI uint32_t rec_byte(const RecSources &S, const RecMeta &t, int r, int off
 	if (off < 36) return (t.fixed[off >> 2] >> (8 * (off & 3))) & 0xffu;
 	const int p = r >> 1;
 	if (off < t.o_cig) return off == t.o_cig - 1 ? 0u : S.in.names[S.in.name_off[p] + (off - 36)];
-	if (off < t.o_seq) { const int k = off - t.o_cig; return (rec_bam_op(S.cig[t.cig_src + (k >> 2)]) >> (8 * (k & 3))) & 0xffu; }
+	if (off < t.o_seq) { const int k = off - t.o_cig; return (bam_cigar_word(S.cig[t.cig_src + (k >> 2)]) >> (8 * (k & 3))) & 0xffu; }
 	if (off < t.o_qual) { const int i = 2 * (off - t.o_seq); return rec_base4(S, t, i) << 4 | (i + 1 < t.l_seq ? rec_base4(S, t, i + 1) : 0u); }
 	if (off < t.o_aux) { const int i = off - t.o_qual; return (uint32_t)(uint8_t)(S.in.quals[t.base_off + ((t.bits & 1) ? t.l_seq - 1 - i : i)] - 33); }
 	int k = off - t.o_aux;

@@ -14,7 +14,7 @@ struct RecordsResult { uint8_t *d_stream = nullptr; int32_t *d_rec_off = nullptr
 
 template <class RT> struct RecordsStage {
 	// What the host can check before anything is launched: the super-batch is the batch's (pair count, read lengths: the qualities are read at
-	// the batch's base offsets), names of 1..254 bytes (BamSink::write's text), offsets that do not decrease.  "" or the message of ARX_E_ARG
+	// the batch's base offsets), names bam_name_ok accepts (BamSink::write's text), offsets that do not decrease.  "" or the message of ARX_E_ARG
 	static std::string check(const arx_super_batch &sb, int n_reads, const int32_t *lens_host)
 	{
 		if (sb.n_pairs <= 0 || 2 * sb.n_pairs != (int64_t)n_reads) return "arx_batch_records: the super-batch holds " + std::to_string(sb.n_pairs) + " pairs, the batch " + std::to_string(n_reads) + " reads (2 * n_pairs must equal n_reads)";
@@ -22,7 +22,7 @@ template <class RT> struct RecordsStage {
 		if (memcmp(sb.lens, lens_host, sizeof(int32_t) * (size_t)n_reads)) return "arx_batch_records: the super-batch's read lengths are not those of the batch";
 		for (int64_t p = 0; p < sb.n_pairs; ++p) {
 			const int64_t ln = sb.name_off[p + 1] - sb.name_off[p];
-			if (ln < 1 || ln > 254) return "read name of record " + std::to_string(2 * p) + " must be 1..254 bytes";
+			if (!bam_name_ok(ln)) return ARX_BAM_NAME_TEXT(2 * p);
 			if (sb.rg_off[p + 1] < sb.rg_off[p] || sb.rg_off[p + 1] - sb.rg_off[p] > 65535) return "arx_batch_records: read-group offsets must not decrease (at most 65535 bytes each)";
 		}
 		if (sb.name_off[0] < 0 || sb.rg_off[0] < 0 || sb.barcode_off[0] < 0) return "arx_batch_records: negative offset in the super-batch";
@@ -60,8 +60,7 @@ template <class RT> struct RecordsStage {
 		memcpy(st + o_nm, sb.names + sb.name_off[0], n_nm);
 		if (n_rg) memcpy(st + o_rg, sb.rgs + sb.rg_off[0], n_rg);
 		if (n_bc) memcpy(st + o_bc, sb.barcodes + sb.barcode_off[0], n_bc);
-		// which sets get BX / VX: attach_bx = unique_barcode (aligner.go:474, 499) and a '-' in the barcode (bamwriter.go:389, 555)
-		for (int s = 0; s < NS; ++s) st[o_bx + s] = sb.unique[s] && memchr(sb.barcodes + sb.barcode_off[s], '-', (size_t)(sb.barcode_off[s + 1] - sb.barcode_off[s])) != nullptr;
+		for (int s = 0; s < NS; ++s) st[o_bx + s] = bam_set_bx(sb.unique[s], sb.barcodes + sb.barcode_off[s], sb.barcode_off[s + 1] - sb.barcode_off[s]);
 		int64_t *no = (int64_t *)(st + o_no), *ro = (int64_t *)(st + o_ro), *bo = (int64_t *)(st + o_bo);
 		for (int64_t p = 0; p <= P; ++p) { no[p] = sb.name_off[p] - sb.name_off[0]; ro[p] = sb.rg_off[p] - sb.rg_off[0]; }
 		for (int s = 0; s <= NS; ++s) bo[s] = sb.barcode_off[s] - sb.barcode_off[0];

@@ -321,9 +321,9 @@ const char *arx_recbuf_error(arx_recbuf *rb);
 void arx_recbuf_free(arx_recbuf *rb);
 
 /* ---- arx_recbuf_build -> arx_bam_write's encoder on the device: the records phase of a batch.  Writes the BAM-encoded primary record of
- * every read (the record set and rules of arx_recbuf_build above: csrc/bam_records.h:311-336, then BamSink::encode, csrc/bam_sink.h:101-129;
+ * every read (the record set and rules of arx_recbuf_build above: csrc/bam_records.h RecBuf::build, then BamSink::encode, csrc/bam_sink.h;
  * bamwriter.go:283-568, 635-658) as one byte stream in device memory -- byte for byte what arx_recbuf_build -> arx_bam_write would append to a
- * writer -- from what arx_batch_rfa left there; csrc/dev_records.h restates the rules.  sb: the super-batch the batch was created from; its
+ * writer -- from what arx_batch_rfa left there; the rules are csrc/bam_rules.h's on both sides.  sb: the super-batch the batch was created from; its
  * qualities, names, read groups, barcodes and set table are uploaded by the call (2 * sb->n_pairs == n_reads, sb->lens the batch's lengths,
  * names of 1..254 bytes: ARX_E_ARG before anything is launched otherwise).  flags bit 0: set 0x400 from arx_batch_post's duplicate marks
  * (ARX_E_ARG if arx_batch_post has not run); 0 = arx_recbuf_build with post == NULL.  Needs arx_batch_rfa first (ARX_E_ARG).  A read without an

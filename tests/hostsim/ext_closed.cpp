@@ -3,9 +3,6 @@
 #include <stdint.h>
 #include <string.h>
 #include <vector>
-#define ARX_DEV
-#define ARX_DEVI inline
-#define ARX_HDI inline
 #include "../../arachne_amd/csrc/arx_dev.h"
 #include "../../arachne_amd/csrc/dev_sw.h"
 

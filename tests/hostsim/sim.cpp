@@ -13,20 +13,6 @@
 #include <string>
 #include <vector>
 #include "../../arachne_amd/csrc/switches.h"
-#define ARX_DEV
-#define ARX_DEVI inline
-#define ARX_HDI inline
-#define ARX_ATOMIC_OR(p, v) (*(p) |= (v))
-#define ARX_ATOMIC_INC(p) ((*(p))++)
-#define ARX_ATOMIC_ADD(p, v) sim_fetch_add((p), (v))
-#define ARX_ATOMIC_MIN(p, v) (*(p) = *(p) < (v) ? *(p) : (v))
-#define ARX_ATOMIC_CAS(p, c, v) sim_cas((p), (c), (v))
-#define ARX_ATOMIC_ADD64(p, v) (*(p) += (v))
-#define ARX_ATOMIC_MIN64(p, v) (*(p) = *(p) < (v) ? *(p) : (v))
-#define ARX_ATOMIC_MAX64(p, v) (*(p) = *(p) > (v) ? *(p) : (v))
-#define ARX_LOAD_SHARED(p) (*(p))
-static inline int sim_fetch_add(int32_t *p, int v) { int o = *p; *p += v; return o; }
-static inline int sim_cas(int32_t *p, int c, int v) { int o = *p; if (o == c) *p = v; return o; }
 static long sim_rescue_fast_hits = 0, sim_rescue_fast_fallbacks = 0;
 static long sim_rescue_calls = 0, sim_rescue_ins = 0, sim_rescue_skipped = 0, sim_rescue_nsum = 0, sim_rescue_nmax = 0, sim_rescue_n2sum = 0;
 static void sim_stat_rescue(int n, bool ins, int clean)

@@ -3,26 +3,14 @@
 // The functors of arachne_amd/csrc/dev_records.h (what arx_batch_records launches) compiled for the host and run as plain loops over their
 // items on random cases, every array allocated at exactly the size the stage driver gives it, so that a read or write past an end shows under
 // -fsanitize=address,undefined.  The stream they write is compared byte for byte with the host path on the same case: RecBuf::build
-// (bam_records.h) followed by BamSink::encode (bam_sink.h).  Usage: rec_sim <seed> <cases> [rev]   (rev: items in descending order)
+// (bam_records.h) followed by BamSink::encode (bam_sink.h).  Both sides call bam_rules.h, so the program also prints a 64-bit digest of the
+// host path's stream for a test to pin.  Usage: rec_sim <seed> <cases> [rev]   (rev: items in descending order) -> "<cases> <digest>"
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <string>
 #include <vector>
-#define ARX_DEV
-#define ARX_DEVI inline
-#define ARX_HDI inline
-#define ARX_ATOMIC_OR(p, v) (*(p) |= (v))
-#define ARX_ATOMIC_INC(p) ((*(p))++)
-#define ARX_ATOMIC_ADD(p, v) (*(p) += (v))
-#define ARX_ATOMIC_MIN(p, v) (*(p) = *(p) < (v) ? *(p) : (v))
-#define ARX_ATOMIC_CAS(p, c, v) rs_cas((p), (c), (v))
-#define ARX_ATOMIC_ADD64(p, v) (*(p) += (v))
-#define ARX_ATOMIC_MIN64(p, v) (*(p) = *(p) < (v) ? *(p) : (v))
-#define ARX_ATOMIC_MAX64(p, v) (*(p) = *(p) > (v) ? *(p) : (v))
-#define ARX_LOAD_SHARED(p) (*(p))
-static inline int rs_cas(int32_t *p, int c, int v) { int o = *p; if (o == c) *p = v; return o; }
 #include "../../arachne_amd/csrc/dev_records.h"
 #include "../../arachne_amd/csrc/bam_records.h"
 #include "../../arachne_amd/csrc/bam_sink.h"
@@ -30,7 +18,7 @@ static inline int rs_cas(int32_t *p, int c, int v) { int o = *p; if (o == c) *p 
 using namespace arx;
 static_assert(sizeof(arx_cand) == sizeof(Cand) && sizeof(arx_aln) == sizeof(Aln) && sizeof(arx_cand_post) == sizeof(CandPost), "C-ABI structs mirror the device structs");
 
-static uint64_t g_x;
+static uint64_t g_x, g_digest = 0xcbf29ce484222325ull; // FNV-1a over the host path's stream of every case
 static int rnd(int m) { g_x ^= g_x << 13; g_x ^= g_x >> 7; g_x ^= g_x << 17; return (int)(g_x % (uint64_t)m); }
 template <class T> static T *exact(const std::vector<T> &v) { T *p = (T *)malloc(v.size() * sizeof(T) + (v.empty() ? 1 : 0)); if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T)); return p; }
 template <class F> static void items(int n, bool rev, const F &f) { if (rev) for (int i = n - 1; i >= 0; --i) f(i, 0); else for (int i = 0; i < n; ++i) f(i, 0); }
@@ -97,9 +85,10 @@ static bool one_case(int it, bool rev, bool dup)
 	for (int r = 0; r < R; ++r) woff[r + 1] = woff[r] + BamSink::record_size(view, r);
 	want.resize(woff[R]);
 	for (int r = 0; r < R; ++r) BamSink::encode(view, r, want.data() + woff[r]);
+	for (uint8_t b : want) g_digest = (g_digest ^ b) * 0x100000001b3ull;
 	// ---- the device functors on arrays of exactly the driver's sizes
 	std::vector<uint8_t> bx(NS);
-	for (int s = 0; s < NS; ++s) bx[s] = uniq[s] && memchr(bcs.data() + bc_off[s], '-', (size_t)(bc_off[s + 1] - bc_off[s])) != nullptr;
+	for (int s = 0; s < NS; ++s) bx[s] = bam_set_bx(uniq[s], bcs.data() + bc_off[s], bc_off[s + 1] - bc_off[s]);
 	std::vector<uint8_t> q8(quals.begin(), quals.end()), nm8(names.begin(), names.end() - 1), rg8(rgs.begin(), rgs.end() - 1), bc8(bcs.begin(), bcs.end() - 1);
 	RecInputs in;
 	uint8_t *d_q = exact(q8), *d_nm = exact(nm8), *d_rg = exact(rg8), *d_bc = exact(bc8), *d_bx = exact(bx), *d_bases = exact(bases);
@@ -142,6 +131,6 @@ int main(int argc, char **argv)
 	const int n = atoi(argv[2]);
 	const bool rev = argc > 3 && !strcmp(argv[3], "rev");
 	for (int it = 0; it < n; ++it) if (!one_case(it, rev, (it & 1) != 0)) return 1;
-	printf("%d\n", n);
+	printf("%d %016llx\n", n, (unsigned long long)g_digest);
 	return 0;
 }
