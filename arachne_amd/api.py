@@ -94,6 +94,9 @@ def _load(path):
     lib.arx_batch_records.argtypes = [vp, vp, vp, i32, vp, vp]
     lib.arx_batch_records_fetch.argtypes = [vp, vp, vp, vp]
     lib.arx_batch_records_view.argtypes = [vp, vp, vp, vp, vp]
+    lib.arx_batch_records_full.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.arx_batch_records_buckets_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.arx_batch_records_buckets_view.argtypes = [vp, vp, vp, vp, vp]
     lib.arx_bam_write_encoded.argtypes = [vp, vp, i64, i64]
     lib.arx_bam_write_select.argtypes = [vp, vp, vp, i64]
     lib.arx_bucket_table.argtypes = [i32, vp, vp, i64, vp, vp, vp, i32, i32]
@@ -132,6 +135,7 @@ _SELFTEST_ARGS = {
                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
     "arx_selftest_gen_cigar": [C.c_int32, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
     "arx_selftest_bgzf": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "arx_selftest_rec_text": [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
     # the device BAM sink: bound when first used, for the same reason
     "arx_bam_open_device": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
     "arx_bam_write_encoded_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64],
@@ -241,6 +245,24 @@ def index_build(fasta: str, prefix: str, lib_path: str = LIB_PATH) -> None:
         raise ArachneError("arx_index_build: " + msg.value.decode())
 
 
+def selftest_rec_text(a, b=None, device: int = 0, lib_path: str = LIB_PATH):
+    """The decimal text the records phase writes on the device (arx_selftest_rec_text): b"%d" % a[i] with b=None, else b"%.6f" % (a[i] / b[i])
+    (b[i] > 0) -> list of bytes"""
+    lib = _load(lib_path)
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    bb = None if b is None else np.ascontiguousarray(b, dtype=np.int32)
+    n = len(a)
+    out, ln = np.zeros((max(n, 1), 32), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.int32)
+    rc = _selftest_fn(lib, "arx_selftest_rec_text")(device, n, a.ctypes.data, None if bb is None else bb.ctypes.data, 0 if bb is None else 1, out.ctypes.data, ln.ctypes.data)
+    if rc != 0:
+        raise ArachneError("arx_selftest_rec_text: code %d" % rc)
+    return [out[i, :ln[i]].tobytes() for i in range(n)]
+
+
+class _RecordsLayout(C.Structure):
+    _fields_ = [("contig_file", C.c_void_p), ("n_contigs", C.c_int32), ("unmapped_file", C.c_int32), ("chunk", C.c_int64)]
+
+
 class _DeviceView(C.Structure):
     _fields_ = [("n_reads", C.c_int64), ("n_regs", C.c_int64), ("n_cigar", C.c_int64), ("n_cands", C.c_int64), ("reg_off", C.c_void_p), ("regs", C.c_void_p),
                 ("alns", C.c_void_p), ("cigars", C.c_void_p), ("cand_off", C.c_void_p), ("cands", C.c_void_p)]
@@ -249,7 +271,8 @@ class _DeviceView(C.Structure):
 class Batch:
     """One batch of read pairs resident on the device (arx_batch)."""
 
-    _rec = (0, 0)   # (n_records, n_bytes) of the last records()
+    _rec = (0, 0)   # (n_records, n_bytes) of the last records() / records_full()
+    _n_files = 0    # files of the table of the last records_full()
 
     def __init__(self, ref: "Reference", seqs, lens):
         self.ref = ref
@@ -462,6 +485,39 @@ class Batch:
         p, nb, n = C.c_void_p(), C.c_int64(), C.c_int64()
         self.ref._check(self.ref.lib.arx_batch_records_view(self.ref.h, self.h, C.byref(p), C.byref(nb), C.byref(n)))
         return p.value or 0, int(nb.value), int(n.value)
+
+    def records_full(self, sb_raw, table: "BucketTable"):
+        """arx_batch_records_full (needs rfa(), post() and tags(), fetch=False will do): the reference's record set -- primary and split
+        records, the full tag set -- BAM-encoded on the device, the bytes RecBuf.build_full -> BamWriter.write_view would append, and the same
+        records grouped by the position buckets of `table` (bucket_table(...)).  records_fetch / records_view serve the stream,
+        records_buckets_fetch / _view the grouped one.  -> (n_records, n_bytes)"""
+        lay = _RecordsLayout(table.contig_file.ctypes.data, len(table.contig_names), len(table.files) - 1, int(table.chunk))
+        n, nb = C.c_int64(), C.c_int64()
+        self.ref._check(self.ref.lib.arx_batch_records_full(self.ref.h, self.h, C.byref(sb_raw), C.byref(lay), C.byref(n), C.byref(nb)))
+        self._rec = (int(n.value), int(nb.value))
+        self._n_files = len(table.files)
+        return self._rec
+
+    def records_buckets_fetch(self, out=None, bucket=True, grouped=True):
+        """arx_batch_records_buckets_fetch (after records_full) -> dict(bucket: the bucket of every record (int32) or None, grouped: the records
+        ordered by bucket, stable (uint8; a view of `out`, an array the caller keeps, when it is large enough) or None, byte_off / rec_off:
+        n_files + 1 int64 each -- bucket f is grouped[byte_off[f]:byte_off[f + 1]], rec_off[f + 1] - rec_off[f] records)"""
+        n, nb = self._rec
+        bk = np.zeros(max(n, 1), dtype=np.int32) if bucket else None
+        if grouped and (out is None or len(out) < nb):
+            out = np.zeros(max(nb, 1), dtype=np.uint8)
+        bo, ro = np.zeros(self._n_files + 1, dtype=np.int64), np.zeros(self._n_files + 1, dtype=np.int64)
+        self.ref._check(self.ref.lib.arx_batch_records_buckets_fetch(self.ref.h, self.h, bk.ctypes.data if bucket else None, out.ctypes.data if grouped else None,
+                                                                     bo.ctypes.data, ro.ctypes.data))
+        return dict(bucket=bk[:n] if bucket else None, grouped=out[:nb] if grouped else None, byte_off=bo, rec_off=ro)
+
+    def records_buckets_view(self):
+        """arx_batch_records_buckets_view (after records_full) -> (device pointer of the grouped stream, byte_off, rec_off), the pointer valid
+        until the phase is left; bucket f goes to BamWriter.write_encoded_device(ptr + byte_off[f], byte_off[f + 1] - byte_off[f], records)"""
+        p = C.c_void_p()
+        bo, ro = np.zeros(self._n_files + 1, dtype=np.int64), np.zeros(self._n_files + 1, dtype=np.int64)
+        self.ref._check(self.ref.lib.arx_batch_records_buckets_view(self.ref.h, self.h, C.byref(p), bo.ctypes.data, ro.ctypes.data))
+        return p.value or 0, bo, ro
 
     def free(self):
         if self.h:

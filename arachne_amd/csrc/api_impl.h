@@ -97,6 +97,7 @@ template <class RT> struct Context {
 	std::map<std::string, KernelTimer> tm_done; // timers of batches already freed
 	bool timing = false;
 	uint64_t index_bytes = 0;   // device memory the index holds (arx_index_info)
+	uint8_t *d_contig_names = nullptr; int32_t *d_contig_name_off = nullptr; // the contig names for SA:Z (arx_batch_records_full), uploaded once here
 
 	void set_error(const std::string &e) { std::lock_guard<std::mutex> g(mu); last_error = e; }
 
@@ -196,6 +197,13 @@ template <class RT> struct Context {
 			}
 		}
 		for (auto &n : hix.names) name_ptrs.push_back(n.c_str());
+		{
+			std::vector<int32_t> off(1, 0); std::string all;
+			for (auto &n : hix.names) { all += n; off.push_back((int32_t)all.size()); }
+			d_contig_names = rt.template palloc<uint8_t>(all.size() + 1); d_contig_name_off = rt.template palloc<int32_t>(off.size());
+			rt.h2d(d_contig_names, all.data(), all.size()); rt.h2d(d_contig_name_off, off.data(), 4 * off.size());
+			dev_index.push_back(d_contig_names); dev_index.push_back(d_contig_name_off);
+		}
 		{ const uint64_t f = rt.free_bytes(); index_bytes = free_at_start > f ? free_at_start - f : 0; }
 		return "";
 	}
@@ -223,7 +231,7 @@ template <class RT> struct Batch {
 	RfaResult rfa; PostResult post; TagsResult tags; RecordsResult recs;
 	// The lifetime of the batch's work memory.  The stages (arx_batch_run) allocate from the start of the arena; the phases that follow them
 	// come in this order, each behind the memory of the one before, and a phase that was skipped (tags without post) is empty:
-	enum Phase { PH_PLACE, PH_POST, PH_TAGS, PH_RECORDS, N_PHASES }; // arx_batch_rfa, arx_batch_post, arx_batch_tags, arx_batch_records
+	enum Phase { PH_PLACE, PH_POST, PH_TAGS, PH_RECORDS, N_PHASES }; // arx_batch_rfa, arx_batch_post, arx_batch_tags, arx_batch_records / _records_full
 	int done_stage = 0;                       // last stage run
 	std::vector<size_t> begin[N_PHASES]; int n_begun = 0; // arena marks: where the memory of phases [0, n_begun) begins
 	bool done[N_PHASES] = {false, false, false, false}; // the phase's results are there (done[p] only if p < n_begun)
@@ -271,6 +279,16 @@ template <class RT> struct Batch {
 		rt.set_timing(ctx->timing); enter(PH_RECORDS);
 		std::string e;
 		const int rc = RecordsStage<RT>::run(pipe, db, work, rfa, dup ? &post : nullptr, sb, recs, e);
+		if (rc != ARX_OK) { rt.sync(); ctx->set_error(e); return rc; }
+		done[PH_RECORDS] = true;
+		return ARX_OK;
+	}
+	// arx_batch_records_full: the same phase, the reference's record set and its buckets; needs the post and the tags phase (both lie in front)
+	int run_records_full(const arx_super_batch &sb, const arx_records_layout &lay)
+	{
+		rt.set_timing(ctx->timing); enter(PH_RECORDS);
+		std::string e;
+		const int rc = RecordsFullStage<RT>::run(pipe, db, work, rfa, post, tags, sb, lay, ctx->d_contig_names, ctx->d_contig_name_off, recs, e);
 		if (rc != ARX_OK) { rt.sync(); ctx->set_error(e); return rc; }
 		done[PH_RECORDS] = true;
 		return ARX_OK;
@@ -551,6 +569,35 @@ template <class RT> struct Batch {
 		if (d_stream) *d_stream = b->recs.d_stream;                                                                                 \
 		if (n_bytes) *n_bytes = b->recs.n_bytes;                                                                                    \
 		if (n_records) *n_records = b->recs.n_records;                                                                              \
+		return ARX_OK;                                                                                                              \
+	}                                                                                                                               \
+	int arx_batch_records_full(arx_ctx *h, arx_batch *bh, const arx_super_batch *sb, const arx_records_layout *lay, int64_t *n_records, int64_t *n_bytes) \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
+		if (!b->done[Bat::PH_PLACE]) { c->set_error("arx_batch_records_full before arx_batch_rfa"); return ARX_E_ARG; }             \
+		if (!b->done[Bat::PH_POST]) { c->set_error("arx_batch_records_full before arx_batch_post"); return ARX_E_ARG; }             \
+		if (!b->done[Bat::PH_TAGS]) { c->set_error("arx_batch_records_full before arx_batch_tags (call it after arx_batch_post, which discards it)"); return ARX_E_ARG; } \
+		if (!sb) { c->set_error("arx_batch_records_full: null super-batch"); return ARX_E_ARG; }                                    \
+		{ const std::string bad = arx::RecordsFullStage<RT>::check_layout(lay, (int)c->hix.names.size()); if (!bad.empty()) { c->set_error(bad); return ARX_E_ARG; } } \
+		{ const std::string bad = arx::RecordsStage<RT>::check(*sb, b->db.n_reads, b->lens_host.data()); if (!bad.empty()) { c->set_error(bad); return ARX_E_ARG; } } \
+		ARX_TRY(c, b->rt.bind(); if (int rc = b->run_records_full(*sb, *lay)) return rc;)                                           \
+		if (n_records) *n_records = b->recs.n_records;                                                                              \
+		if (n_bytes) *n_bytes = b->recs.n_bytes;                                                                                    \
+		return ARX_OK;                                                                                                              \
+	}                                                                                                                               \
+	int arx_batch_records_buckets_fetch(arx_ctx *h, arx_batch *bh, int32_t *bucket, uint8_t *grouped, int64_t *bucket_byte_off, int64_t *bucket_rec_off) \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
+		if (!b->done[Bat::PH_RECORDS] || !b->recs.full) { c->set_error("arx_batch_records_buckets_fetch needs arx_batch_records_full as the last records call (not arx_batch_records, and no later arx_batch_run / _rfa / _post / _tags / _reset)"); return ARX_E_ARG; } \
+		ARX_TRY(c, b->rt.bind(); arx::RecordsFullStage<RT>::fetch_buckets(b->pipe, b->recs, bucket, grouped, bucket_byte_off, bucket_rec_off);) \
+		return ARX_OK;                                                                                                              \
+	}                                                                                                                               \
+	int arx_batch_records_buckets_view(arx_ctx *h, arx_batch *bh, const uint8_t **d_grouped, int64_t *bucket_byte_off, int64_t *bucket_rec_off) \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
+		if (!b->done[Bat::PH_RECORDS] || !b->recs.full) { c->set_error("arx_batch_records_buckets_view needs arx_batch_records_full as the last records call (not arx_batch_records, and no later arx_batch_run / _rfa / _post / _tags / _reset)"); return ARX_E_ARG; } \
+		ARX_TRY(c, b->rt.bind(); b->rt.sync(); arx::RecordsFullStage<RT>::fetch_buckets(b->pipe, b->recs, nullptr, nullptr, bucket_byte_off, bucket_rec_off);) \
+		if (d_grouped) *d_grouped = b->recs.d_grouped;                                                                              \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_rfa_fetch(arx_ctx *h, arx_batch *bh, int32_t *cand_off, arx_cand *cands)                                          \

@@ -1,5 +1,5 @@
 // arx_selftest.hip -- the self-test entries of the three DP kernel families (include/arachne_amd.h: arx_selftest_extend,
-// arx_selftest_rescue_sw, arx_selftest_gen_cigar).  They take plain host arrays, build what the pipeline would hand the kernels (an IndexView
+// arx_selftest_rescue_sw, arx_selftest_gen_cigar) and of the records phase's decimal text (arx_selftest_rec_text).  They take plain host arrays, build what the pipeline would hand the kernels (an IndexView
 // with only the packed text set, class-binned extension tasks, rescue tasks with their mates, staged CIGAR regions) and launch the production
 // code through HipRT, so that tests/test_dp_kernels_gpu.py can compare every output field with ksw_extend2 / ksw_align2 / ksw_global2.
 // Its own unit so that the unit of the list-bookkeeping kernels does not grow.
@@ -8,6 +8,7 @@
 #include "../../include/arachne_amd.h"
 #include "hip_rt.h"
 #include "pipeline.h"
+#include "dev_records_full.h"
 
 namespace arx {
 
@@ -34,6 +35,20 @@ static __global__ void __launch_bounds__(64) k_selftest_gen_cigar(const uint8_t 
 		__builtin_amdgcn_wave_barrier(); // the LDS rows are reused by the group's next region
 	}
 }
+
+// the records phase's decimal text (dev_records_full.h), one input per lane, written character by character as the fill asks for it
+struct KSelftestRecText {
+	const int32_t *a, *b; int kind; uint8_t *out; int32_t *len;
+	ARX_DEV void operator()(int i, int) const
+	{
+		uint8_t *o = out + 32 * (size_t)i;
+		int l;
+		if (kind == 0) { l = int_len(a[i]); for (int k = 0; k < l; ++k) o[k] = (uint8_t)int_char(a[i], k); }
+		else { const uint64_t t = dm_scaled_signed(a[i], b[i]); l = dm_len(a[i], t); for (int k = 0; k < l; ++k) o[k] = (uint8_t)dm_char(a[i] < 0, t, k); }
+		for (int k = l; k < 32; ++k) o[k] = 0;
+		len[i] = l;
+	}
+};
 
 static bool one_strand(int64_t a, int64_t b, int64_t l_pac) // both ends inside the same strand of [0, 2 * l_pac)
 {
@@ -181,6 +196,31 @@ extern "C" int arx_selftest_gen_cigar(int32_t device, int32_t n, const uint8_t *
 		ARX_HIP_CHECK(hipStreamSynchronize(rt.stream));
 		rt.d2h(out4, dout, (size_t)n * 16);
 		rt.d2h(cigar, dcig, (size_t)n * cig_w * 4);
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}
+
+extern "C" int arx_selftest_rec_text(int32_t device, int32_t n, const int32_t *a, const int32_t *b, int32_t kind, uint8_t *out, int32_t *len)
+{
+	using namespace arx;
+	if (n < 0 || kind < 0 || kind > 1 || (n > 0 && (!a || !out || !len || (kind == 1 && !b)))) return ARX_E_ARG;
+	if (kind == 1) for (int i = 0; i < n; ++i) if (b[i] <= 0) return ARX_E_ARG;
+	if (n == 0) return ARX_OK;
+	try {
+		HipRT rt;
+		if (!rt.init(device).empty()) return ARX_E_DEVICE;
+		rt.timing = false;
+		int32_t *da = rt.alloc<int32_t>((size_t)n), *db = rt.alloc<int32_t>((size_t)n), *dl = rt.alloc<int32_t>((size_t)n);
+		uint8_t *dout = rt.alloc<uint8_t>(32 * (size_t)n);
+		rt.h2d(da, a, 4 * (size_t)n);
+		if (kind == 1) rt.h2d(db, b, 4 * (size_t)n);
+		KSelftestRecText f{da, db, kind, dout, dl};
+		rt.launch_wide("selftest_rec_text", n, f);
+		ARX_HIP_CHECK(hipStreamSynchronize(rt.stream));
+		rt.d2h(out, dout, 32 * (size_t)n);
+		rt.d2h(len, dl, 4 * (size_t)n);
 	} catch (const std::exception &) {
 		return ARX_E_DEVICE;
 	}

@@ -34,6 +34,11 @@
 //              snapshot taken inside the RFA kernel on the timed path.  Split records carry no DM here.
 //   bucket     per record the position bucket of arx_bucket_table, chosen by IsUnmapped() (the score rule alone) as AppendBams does (:280).
 // Left out in both modes: the -debug tags (:495-553), which no command-line path reaches.
+//
+// The device builds both record sets too, already BAM-encoded: arx_batch_records (dev_records.h) the first mode's, arx_batch_records_full
+// (dev_records_full.h) the full mode's -- primary and split records, the whole tag set, the bucket of every record and a second stream grouped
+// by bucket -- from what arx_batch_post and arx_batch_tags left in HBM.  What the full mode decides per read and per record (ReadState, the
+// split record's flag and fields, order and length of the aux fields, SA's pieces, the bucket) is stated in bam_rules.h for both.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -89,20 +94,9 @@ struct RecBuf {
 	std::vector<int64_t> rbase; // full mode: record of every read's primary (its split record follows it)
 	std::vector<int32_t> bucket; // full mode: position bucket of every record
 
-	// What AppendBam sees when it writes read r's records (full mode): the mutation of the score rule applied in write order
-	static inline bool pair_at(const arx_cand &a, int64_t apos, const arx_cand &b, int64_t bpos) // isPair (aligner.go:1032) on positions as mutated
-	{
-		if (a.reversed == b.reversed || a.rid != b.rid) return false;
-		const int64_t dist = a.reversed ? apos - bpos : bpos - apos;
-		return dist >= -35 && dist < 750;
-	}
-	struct ReadState {
-		int a, am, s;          // active candidate, the mate's, the split candidate (-1: none)
-		int64_t cpos, mpos;    // the primary's pos as written; the mate's pos when r's records are written (2p+1 sees 2p's mutation)
-		bool mate_un;          // flag 0x8 of both records
-		int64_t spos;          // the split record's pos as written
-		int hc0, hc1;          // HardClip: bases cut at the front / the back of the split record
-	};
+	// What AppendBam sees when it writes read r's records (full mode): bam_rules.h's, shared with the device (dev_records_full.h)
+	template <class C> static inline bool pair_at(const C &a, int64_t apos, const C &b, int64_t bpos) { return bam_pair_at(a, apos, b, bpos); }
+	typedef BamReadState ReadState;
 
 	// sb: the super-batch the batch was created from; cand_off / cands: arx_batch_rfa_fetch; alns / cigars: arx_batch_fetch (cands[].reg indexes
 	// them); post: arx_batch_post_fetch's per-candidate records or NULL (then no duplicate flags); full: null for arx_recbuf_build's record set
@@ -130,24 +124,7 @@ struct RecBuf {
 			for (int t = 0; t < threads; ++t) th.emplace_back([&, t]() { const int64_t lo = NR * t / threads, hi = NR * (t + 1) / threads; for (int64_t r = lo; r < hi; ++r) fn(r); });
 			for (auto &x : th) x.join();
 		};
-		auto state = [&](int64_t r) { // full mode
-			ReadState st;
-			st.a = act[(size_t)r]; st.am = act[(size_t)(r ^ 1)]; st.s = full->split[r].split;
-			const arx_cand &c = cands[st.a], &m = cands[st.am];
-			st.cpos = bam_score_rule(c) ? -1 : c.pos;
-			st.mpos = ((r & 1) && bam_score_rule(m)) ? -1 : m.pos;
-			st.mate_un = st.mpos == -1 || bam_score_rule(c.is_proper, m.score);
-			st.spos = -1; st.hc0 = st.hc1 = 0;
-			if (st.s >= 0) {
-				const arx_cand &x = cands[st.s];
-				st.spos = bam_score_rule(full->split[r].is_proper, x.score) ? -1 : x.pos;
-				const arx_aln &al = alns[x.reg];
-				const uint32_t *w = cigs + al.cigar_off;
-				if (al.n_cigar >= 1 && (w[0] & 15u) == 3) st.hc0 = (int)(w[0] >> 4);                                  // BWA's S = 3 (BAM's 4)
-				if (al.n_cigar >= 2 && (w[al.n_cigar - 1] & 15u) == 3) st.hc1 = (int)(w[al.n_cigar - 1] >> 4);
-			}
-			return st;
-		};
+		auto state = [&](int64_t r) { return bam_read_state(cands, alns, cigs, act[(size_t)r], act[(size_t)(r ^ 1)], full->split[r], r); }; // full mode
 		// "ref,read,1;" per mismatch location of candidate i (XC / AC)
 		auto mm_string = [&](int i) {
 			std::string out;
@@ -163,41 +140,50 @@ struct RecBuf {
 			std::string out = (x.rid >= 0 && x.rid < full->n_contigs) ? full->contig_names[x.rid] : "";
 			char b[48];
 			snprintf(b, sizeof b, ",%lld,%c,", (long long)p, x.reversed ? '-' : '+'); out += b;
-			int indel = 0;
 			for (int k = 0; k < al.n_cigar; ++k) {
-				const uint32_t w = cigs[al.cigar_off + (x.reversed ? al.n_cigar - 1 - k : k)];
-				const int op = (int)(w & 15u);
-				if (op == 1 || op == 2) indel += (int)(w >> 4);
-				snprintf(b, sizeof b, "%u%c", w >> 4, op == 3 ? (hard ? 'H' : 'S') : "MIDSH"[op < 5 ? op : 4]); out += b;
+				const uint32_t w = bam_sa_word(cigs + al.cigar_off, al.n_cigar, k, x.reversed != 0);
+				snprintf(b, sizeof b, "%u%c", w >> 4, bam_sa_op(w, hard)); out += b;
 			}
-			snprintf(b, sizeof b, ",%d,%d;", q, post[i].n_mm + indel); out += b;
+			snprintf(b, sizeof b, ",%d,%d;", q, bam_sa_nm(post[i].n_mm, cigs + al.cigar_off, al.n_cigar)); out += b;
 			return out;
 		};
-		// the aux fields of read r's primary (split = false) or split record (full mode), counted or written
+		// the aux fields of read r's primary (split = false) or split record (full mode), counted (bam_full_aux_len) or written in that order
 		auto full_aux = [&](int64_t r, const ReadState &st, bool split, AuxOut &o) {
 			const int64_t p = r >> 1; const int s = (int)pair_set[(size_t)p];
 			const arx_read_tags &T = full->tags[r];
 			const arx_split &S = full->split[r];
 			const arx_cand &x = cands[split ? st.s : st.a];
 			const int64_t rgl = sb.rg_off[p + 1] - sb.rg_off[p];
-			if (rgl > 0) o.z("RG", sb.rgs + sb.rg_off[p], (size_t)rgl);
-			o.i32("XS", split ? S.second_best2 / 2 : T.xs);
-			o.zs("XC", split ? std::string() : mm_string(T.second_best));
-			o.zs("AC", mm_string(split ? st.s : st.a));
-			o.i32("AS", split ? S.score2 / 2 : T.as);
-			o.z("XM", (!split && T.xm) ? "1" : "0", 1);
-			o.z("AM", x.active_molecule ? "1" : "0", 1);
-			o.i32("XT", split ? 0 : T.xt);
-			if (!split && st.s >= 0) o.zs("SA", sa_string(st.s, cands[st.s].pos, S.mapq, true));        // the split is written after: not mutated yet
-			if (split && st.cpos > -1) o.zs("SA", sa_string(st.a, st.cpos, cands[st.a].mapq, false));
-			if (set_bx[(size_t)s]) {
-				o.z("BX", sb.barcodes + sb.barcode_off[s], (size_t)(sb.barcode_off[s + 1] - sb.barcode_off[s]));
-				o.i32("VX", 1);
-				if (!split && x.active_molecule && T.dm_n > 0) {
-					char b[64];
-					const int l = snprintf(b, sizeof b, "%.6f", (double)T.dm_sum / (double)T.dm_n); // strconv.FormatFloat(x, 'f', 6, 64)
-					o.z("DM", b, (size_t)l);
-				}
+			const bool bx = set_bx[(size_t)s] != 0;
+			int32_t xs, as, xt; bool xm;
+			bam_full_ints(split, T, S, &xs, &as, &xt, &xm);
+			const std::string xc = split ? std::string() : mm_string(T.second_best), ac = mm_string(split ? st.s : st.a);
+			std::string sa, dm;
+			const bool has_sa = bam_has_sa(split, st), has_dm = bam_has_dm(split, bx, x.active_molecule != 0, T.dm_n);
+			if (has_sa) { int i; int64_t sp; int32_t q; bool hard; bam_sa_source(split, st, cands, S, &i, &sp, &q, &hard); sa = sa_string(i, sp, q, hard); }
+			if (has_dm) {
+				char b[64];
+				const int l = snprintf(b, sizeof b, "%.6f", (double)T.dm_sum / (double)T.dm_n); // strconv.FormatFloat(x, 'f', 6, 64)
+				dm.assign(b, (size_t)l);
+			}
+			const int64_t bcl = sb.barcode_off[s + 1] - sb.barcode_off[s];
+			if (!o.p) {
+				o.n = bam_full_aux_len(BamFullAux{(int32_t)rgl, (int32_t)xc.size(), (int32_t)ac.size(), has_sa ? (int32_t)sa.size() : -1, (int32_t)bcl, has_dm ? (int32_t)dm.size() : -1, bx});
+				return;
+			}
+			for (int f = 0; f < FA_N; ++f) switch (f) {
+			case FA_RG: if (rgl > 0) o.z("RG", sb.rgs + sb.rg_off[p], (size_t)rgl); break;
+			case FA_XS: o.i32("XS", xs); break;
+			case FA_XC: o.zs("XC", xc); break;
+			case FA_AC: o.zs("AC", ac); break;
+			case FA_AS: o.i32("AS", as); break;
+			case FA_XM: o.z("XM", xm ? "1" : "0", 1); break;
+			case FA_AM: o.z("AM", x.active_molecule ? "1" : "0", 1); break;
+			case FA_XT: o.i32("XT", xt); break;
+			case FA_SA: if (has_sa) o.zs("SA", sa); break;
+			case FA_BX: if (bx) o.z("BX", sb.barcodes + sb.barcode_off[s], (size_t)bcl); break;
+			case FA_VX: if (bx) o.i32("VX", 1); break;
+			case FA_DM: if (has_dm) o.zs("DM", dm); break;
 			}
 		};
 		// pass 1: the active candidate and the sizes of every record
@@ -209,7 +195,7 @@ struct RecBuf {
 		if (bad) { err = "a read without an active candidate: arx_batch_rfa must have run on this batch"; return false; }
 		if (full) for (int64_t r = 0; r < NR; ++r) {
 			const int sp = full->split[r].split;
-			if (sp >= 0 && (sp < cand_off[r] || sp >= cand_off[r + 1] || cands[sp].reg < 0)) { err = "arx_split names a candidate of another read"; return false; }
+			if (!bam_split_ok(cands, cand_off, r, sp)) { err = ARX_BAM_SPLIT_TEXT; return false; }
 		}
 		par([&](int64_t r) {
 			const int64_t q = rbase[(size_t)r];
@@ -249,8 +235,7 @@ struct RecBuf {
 				const arx_aln &al = alns[x.reg];
 				uint32_t *dst = cigars.data() + cigar_off[(size_t)q];
 				for (int k = 0; k < al.n_cigar; ++k) dst[k] = bam_cigar_word(cigs[al.cigar_off + k]);
-				if (hard && al.n_cigar >= 1 && (dst[0] & 15u) == 4) dst[0] = (dst[0] & ~15u) | 5u;                                   // HardClip (:660-689)
-				if (hard && al.n_cigar >= 2 && (dst[al.n_cigar - 1] & 15u) == 4) dst[al.n_cigar - 1] = (dst[al.n_cigar - 1] & ~15u) | 5u;
+				if (hard) for (int k = 0; k < al.n_cigar; ++k) dst[k] = bam_hard_word(dst[k], k, al.n_cigar);                        // HardClip (:660-689)
 			}
 			const int L = sb.lens[r];
 			const uint8_t *b = sb.bases + base_off[(size_t)r]; const char *qs = sb.quals + base_off[(size_t)r];
@@ -263,8 +248,9 @@ struct RecBuf {
 		};
 		// the fixed fields of record q: candidate x written at xpos (-1: unmapped) with MAPQ mq, its mate m at mpos
 		auto put_fields = [&](int64_t q, uint32_t fl, const arx_cand &x, int64_t xpos, int32_t mq, bool mate_un, const arx_cand &m, int64_t mpos, int32_t tl) {
-			flag[(size_t)q] = (int32_t)fl; rid[(size_t)q] = xpos == -1 ? -1 : x.rid; pos[(size_t)q] = (int32_t)xpos; mapq[(size_t)q] = xpos == -1 ? 0 : (uint8_t)bam_mapq(mq);
-			mate_rid[(size_t)q] = mate_un ? -1 : m.rid; mate_pos[(size_t)q] = mate_un ? -1 : (int32_t)mpos; tlen[(size_t)q] = tl;
+			const BamFields f = bam_fields(x, xpos, mq, mate_un, m, mpos);
+			flag[(size_t)q] = (int32_t)fl; rid[(size_t)q] = f.rid; pos[(size_t)q] = f.pos; mapq[(size_t)q] = (uint8_t)f.mapq;
+			mate_rid[(size_t)q] = f.mate_rid; mate_pos[(size_t)q] = f.mate_pos; tlen[(size_t)q] = tl;
 		};
 		par([&](int64_t r) {
 			const int64_t q = rbase[(size_t)r];
@@ -274,16 +260,15 @@ struct RecBuf {
 				const ReadState st = state(r);
 				put_fields(q, bam_flag(r & 1, c.is_proper, st.cpos == -1, st.mate_un, m.reversed, c.reversed, post[st.a].duplicate, false), c, st.cpos, c.mapq, st.mate_un, m, st.mpos,
 				           bam_tlen(c, m, st.cpos, st.mpos));
-				bucket[(size_t)q] = bam_score_rule(c) ? full->unmapped_file : full->contig_file[c.rid] + (int32_t)(c.pos / full->chunk);
+				bucket[(size_t)q] = bam_bucket(bam_score_rule(c), c.rid, c.pos, full->contig_file, full->n_contigs, full->chunk, full->unmapped_file);
 				fill_body(r, q, c, 0, 0, false);
 				AuxOut o{aux.data() + aux_off[(size_t)q]};
 				full_aux(r, st, false, o);
 				if (st.s >= 0) {
 					const arx_cand &x = cands[st.s];
 					const arx_split &S = full->split[r];
-					put_fields(q + 1, bam_flag(r & 1, S.is_proper && pair_at(x, st.spos, m, st.mpos), st.spos == -1, st.mate_un, m.reversed, x.reversed, post[st.s].duplicate, true), x, st.spos, S.mapq,
-					           st.mate_un, m, st.mpos, 0);
-					bucket[(size_t)q + 1] = st.spos == -1 ? full->unmapped_file : full->contig_file[x.rid] + (int32_t)(x.pos / full->chunk);
+					put_fields(q + 1, bam_split_flag(r & 1, S.is_proper != 0, x, st, m, post[st.s].duplicate != 0), x, st.spos, S.mapq, st.mate_un, m, st.mpos, 0);
+					bucket[(size_t)q + 1] = bam_bucket(st.spos == -1, x.rid, x.pos, full->contig_file, full->n_contigs, full->chunk, full->unmapped_file);
 					fill_body(r, q + 1, x, st.hc0, st.hc1, true);
 					AuxOut o2{aux.data() + aux_off[(size_t)q + 1]};
 					full_aux(r, st, true, o2);

@@ -51,14 +51,20 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
     result slabs and building them on host threads (arx_recbuf_build + arx_bam_write's encoder): a worker fetches ONE block, the record
     stream, and queues it for its writer thread (arx_bam_write_encoded), or with sink="device" hands it to the device sink where it lies
     (arx_bam_write_encoded_device) -- the records never visit the host uncompressed.  arx_batch_post still runs, for the duplicate marks.  The
-    files inflate to the same bytes; fetch_s / records_s then are the stream fetch and post + the records call."""
+    files inflate to the same bytes; fetch_s / records_s then are the stream fetch and post + the records call.
+    records="device_full" (layout="reference" only, both feeders): the reference's record set and its buckets from the GPU
+    (arx_batch_post, arx_batch_tags, arx_batch_records_full): the record stream goes to bc_sorted_bam.bam, every non-empty bucket's slice of
+    the grouped stream to its writer -- fetched as two blocks (arx_bam_write_encoded), or with sink="device" handed over where they lie
+    (arx_bam_write_encoded_device); no result slab comes home and nothing is built or encoded on host threads."""
     if sink not in ("host", "device"):
         raise ValueError(f"unknown sink {sink!r}")
-    if records not in ("host", "device"):
+    if records not in ("host", "device", "device_full"):
         raise ValueError(f"unknown records {records!r}")
     if records == "device" and layout == "reference":
         raise ValueError("records='device' writes the primary records only: layout='reference' needs records='host'")
-    dev_rec = records == "device"
+    if records == "device_full" and layout != "reference":
+        raise ValueError("records='device_full' builds the reference's record set and its buckets: it needs layout='reference'")
+    dev_rec = "full" if records == "device_full" else records == "device"
     sink_dev = ref if sink == "device" else None
     if feeder == "device":
         if warm_passes:
@@ -69,7 +75,7 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
     if layout == "reference":
         if warm_passes:
             raise ValueError("layout='reference' writes its files once: warm_passes must be 0")
-        return _run_reference(ref, fastq_pairs, out_prefix, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, chunk, read_groups, sample_id, sink_dev)
+        return _run_reference(ref, fastq_pairs, out_prefix, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, chunk, read_groups, sample_id, sink_dev, dev_rec == "full")
     if layout != "workers":
         raise ValueError(f"unknown layout {layout!r}")
     names, offs, clens, alt, l_pac = ref.contigs()
@@ -231,6 +237,47 @@ def _device_records(batch, sb, bam, sink_dev, slot, written, werr, wq, streams, 
     return n_rec
 
 
+def _device_records_full(batch, sb, table, writers, locks, sink_dev, streams, loc):
+    """records="device_full" for one super-batch: arx_batch_post, arx_batch_tags, arx_batch_records_full, then the record stream into writers[0]
+    (bc_sorted_bam.bam) and bucket f's slice of the grouped stream into writers[f + 1] (AppendBams, bamwriter.go:279-281) -- from device memory
+    with the device sink, else fetched as two blocks into streams[0] / streams[1] (page-locked, grown when needed).  Returns when the
+    writers have taken the bytes: the batch may be reset.  -> records"""
+    t2 = time.time()
+    batch.post(fetch=False)                             # arx_batch_post, then the tags on top of it (a later post would discard them)
+    batch.tags(fetch=False)
+    n_rec, n_bytes = batch.records_full(sb, table)
+    t3 = time.time()
+    loc["records_s"] += t3 - t2
+    if sink_dev is not None:
+        ptr, n_bytes, n_rec = batch.records_view()
+        gptr, bo, ro = batch.records_buckets_view()
+        with locks[0]:
+            writers[0].write_encoded_device(ptr, n_bytes, n_rec)
+        for f in range(len(table.files)):
+            if ro[f + 1] > ro[f]:
+                with locks[f + 1]:
+                    writers[f + 1].write_encoded_device(gptr + int(bo[f]), int(bo[f + 1] - bo[f]), int(ro[f + 1] - ro[f]))
+        loc["bam_s"] += time.time() - t3
+        return n_rec
+    for k in (0, 1):
+        if streams[k] is None or len(streams[k]) < n_bytes:
+            streams[k] = None
+            streams[k] = batch.pin(np.zeros(int(n_bytes * 1.2) + 4096, dtype=np.uint8))
+    stream, _ = batch.records_fetch(out=streams[0], offsets=False)
+    g = batch.records_buckets_fetch(out=streams[1], bucket=False)
+    t4 = time.time()
+    loc["fetch_s"] += t4 - t3
+    bo, ro = g["byte_off"], g["rec_off"]
+    with locks[0]:
+        writers[0].write_encoded(stream, n_rec)
+    for f in range(len(table.files)):
+        if ro[f + 1] > ro[f]:
+            with locks[f + 1]:
+                writers[f + 1].write_encoded(g["grouped"][bo[f]:bo[f + 1]], int(ro[f + 1] - ro[f]))
+    loc["bam_s"] += time.time() - t4
+    return n_rec
+
+
 def reference_header(read_groups: str = "", date: str | None = None) -> str:
     """The header lines CreateBAM adds to every file (bamwriter.go:74-109): one @RG per comma-separated read group of at least five ':' fields
     (sample:library:gem_group:flowcell:lane -> ID, LB = library.gem_group, PL ILLUMINA, PU = ID, SM = sample, DT = the run time), then @PG."""
@@ -245,7 +292,7 @@ def reference_header(read_groups: str = "", date: str | None = None) -> str:
     return out + "@PG\tID:arachne\tPN:arachne\tCL:arachne_amd\n"
 
 
-def _run_reference(ref, fastq_pairs, out_dir, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, chunk, read_groups, sample_id, sink_dev=None):
+def _run_reference(ref, fastq_pairs, out_dir, pairs_per_batch, bam_threads, rec_threads, level, penalty, lib_path, chunk, read_groups, sample_id, sink_dev=None, full_dev=False):
     names, offs, clens, alt, l_pac = ref.contigs()
     table = api.bucket_table(names, clens, chunk, lib_path=lib_path)
     os.makedirs(out_dir, exist_ok=True)
@@ -263,6 +310,7 @@ def _run_reference(ref, fastq_pairs, out_dir, pairs_per_batch, bam_threads, rec_
         rb = api.RecBuf(lib_path=lib_path)
         loc = dict(pairs=0, records=0, batches=0, feeder_s=0.0, device_s=0.0, fetch_s=0.0, records_s=0.0, bam_s=0.0)
         buf = {}
+        streams = [None, None]
         try:
             while True:
                 t0 = time.time()
@@ -275,6 +323,11 @@ def _run_reference(ref, fastq_pairs, out_dir, pairs_per_batch, bam_threads, rec_
                 batch.run(api.STAGE_ALN)
                 batch.rfa(v["set_pair_off"], v["do_rfa"], penalty=penalty, fetch=False)
                 t2 = time.time()
+                if full_dev:
+                    n_rec = _device_records_full(batch, sb, table, writers, locks, sink_dev, streams, loc)
+                    loc["pairs"] += int(v["n_pairs"]); loc["records"] += n_rec; loc["batches"] += 1
+                    loc["feeder_s"] += t1 - t0; loc["device_s"] += t2 - t1
+                    continue
                 batch.fetch_into(buf)
                 post = batch.post()                      # arx_batch_post, then the tags on top of it (a later post would discard them)
                 tags = batch.tags()
@@ -458,6 +511,13 @@ def _run_device(ref, fastq_pairs, out, pairs_per_batch, bam_threads, rec_threads
                 batch.run(api.STAGE_ALN)
                 batch.rfa(v["set_pair_off"], v["do_rfa"], penalty=penalty, fetch=False)
                 t2 = time.time()
+                if dev_rec == "full":
+                    n_pairs = int(v["n_pairs"])
+                    n_rec = _device_records_full(batch, sb, table, writers, locks, sink_dev, streams, loc)
+                    released.set()                      # both streams are with their writers: the feeder's arrays are free
+                    loc["pairs"] += n_pairs; loc["records"] += n_rec; loc["batches"] += 1
+                    loc["device_s"] += t2 - t1
+                    continue
                 if dev_rec:
                     n_pairs = int(v["n_pairs"])
                     n_rec = _device_records(batch, sb, writers[k], sink_dev, loc["batches"] & 1, written, werr, wq, streams, loc, lock=locks[k])

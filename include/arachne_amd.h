@@ -337,6 +337,32 @@ int arx_batch_records_fetch(arx_ctx *ctx, arx_batch *b, uint8_t *stream /* n_byt
  * arx_batch_device_view: the call waits for the batch's stream */
 int arx_batch_records_view(arx_ctx *ctx, arx_batch *b, const uint8_t **d_stream, int64_t *n_bytes, int64_t *n_records);
 
+/* ---- the reference's record set on the device: what arx_recbuf_build_full -> arx_bam_write would append (DoDumpToBam, bamwriter.go:278-566,
+ * 635-689: primary and split records, the tags RG XS XC AC AS XM AM XT SA BX VX DM), byte for byte, and the same records a second time grouped
+ * by position bucket (AppendBams writes every record to bc_sorted_bam.bam and to its bucket, :279-281; the files of CreateBAMs, :134-188),
+ * built from what arx_batch_post and arx_batch_tags left in device memory.  The layout is arx_bucket_table's: n_files = unmapped_file + 1. */
+typedef struct {
+	const int32_t *contig_file;     /* arx_bucket_table: n_contigs */
+	int32_t n_contigs;              /* must equal the context's (arx_contigs) */
+	int32_t unmapped_file;          /* *n_files - 1 */
+	int64_t chunk;
+} arx_records_layout;
+/* Needs arx_batch_rfa, arx_batch_post AND arx_batch_tags on the batch (ARX_E_ARG names the missing one).  The same phase as arx_batch_records
+ * -- either call rebuilds it, a later arx_batch_run / _rfa / _post / _tags / _reset* discards it -- with the same checks of the super-batch.
+ * n_records = n_reads + splits.  ARX_E_ARG also: a layout that is not the index's (n_contigs, a file outside [0, unmapped_file), a record whose
+ * bucket lies outside the table), more than 4096 files (the grouping's table holds n_files entries per 256 records), an arx_split that names
+ * a candidate of another read or one without an alignment (arx_recbuf_build_full's text).  ARX_E_TOO_LARGE: a stream of 2^31 - 1 bytes or
+ * more, or a grouping table (n_files * ceil(n_records / 256) entries) above 2^26: split the batch or use a larger chunk.  Returns with both streams complete. */
+int arx_batch_records_full(arx_ctx *ctx, arx_batch *b, const arx_super_batch *sb, const arx_records_layout *lay, int64_t *n_records, int64_t *n_bytes);
+/* After arx_batch_records_full only (ARX_E_ARG when arx_batch_records ran last); any argument may be NULL.  bucket[n_records]: the bucket of
+ * every record; grouped[n_bytes]: the records ordered by bucket, within a bucket in stream order (the stable order by bucket);
+ * bucket_byte_off / bucket_rec_off[n_files + 1]: where bucket f's bytes / records start in it.  arx_batch_records_fetch / _view serve the
+ * ungrouped stream of whichever of the two calls ran last. */
+int arx_batch_records_buckets_fetch(arx_ctx *ctx, arx_batch *b, int32_t *bucket, uint8_t *grouped, int64_t *bucket_byte_off, int64_t *bucket_rec_off);
+/* the grouped stream where it lies (bucket f: arx_bam_write_encoded_device(w, *d_grouped + bucket_byte_off[f], bytes, records)), the offsets
+ * on the host; the contract of arx_batch_records_view */
+int arx_batch_records_buckets_view(arx_ctx *ctx, arx_batch *b, const uint8_t **d_grouped, int64_t *bucket_byte_off, int64_t *bucket_rec_off);
+
 /* ---- several GPUs behind one handle (arx_open(prefix, n_devices, ...)): one index replica per device, a super-batch of whole
  * barcodes cut by pair count (greedy longest-processing-time), every device's share on a host thread of its own, the result slabs
  * renumbered into the order of the read set -- byte for byte what ONE batch over everything returns.  devices: HIP device indices or NULL
@@ -381,6 +407,11 @@ int arx_selftest_wave_sort(int32_t device, int32_t n_cases, int64_t seed, int64_
  * in order, without the EOF block (cap: bytes of out; n + 31 * blocks always suffice; ARX_E_ARG if it is too small).  stats[4] (may be
  * NULL): blocks, and how many of them went out stored, with the fixed code, with a dynamic code.  n = 0: no block, *out_len = 0. */
 int arx_selftest_bgzf(int32_t device, const uint8_t *src, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, int64_t *stats);
+
+/* self-test of the decimal text the records phase writes on the device (csrc/dev_records_full.h), one input per lane: kind 0: "%d" of a[i]
+ * (b is not read); kind 1: "%.6f" of (double)a[i] / (double)b[i], b[i] > 0 (else ARX_E_ARG).  out: n rows of 32 bytes, len[n]: the bytes
+ * of each text.  There so that the GPU suite can hold the formatters to the host's on inputs the path does not produce at test size. */
+int arx_selftest_rec_text(int32_t device, int32_t n, const int32_t *a, const int32_t *b, int32_t kind, uint8_t *out /* 32 * n */, int32_t *len /* n */);
 
 /* self-tests of the three DP kernel families on plain host arrays (csrc/arx_selftest.hip; tests/test_dp_kernels_gpu.py): each entry
  * uploads the tasks, launches the production code on them and returns one result row per task, in input order.  The reference text is

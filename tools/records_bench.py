@@ -9,8 +9,17 @@ of the headline command at the default step size, genome and index from bench.py
               stream up again) against records="device" (the super-batch's qualities / names / tables up; the stream home, or nothing)
   e2e         e2e.run on that pair, four arms records x sink, alternating, --repeats passes each after one untimed pass per arm
 
+--layout reference adds the full records phase (arx_batch_records_full) and measures the reference's layout instead of the workers':
+  kernels     arx_batch_tags once, then arx_batch_records_full --repeats times -> ms per call of its launches (rec_mm_len, rec_full_count,
+              rec_full_meta, rec_tile and rec_full_fill -- two calls each per phase: the stream and the grouped stream --, the rec_group_* launches,
+              scan), its stream bytes
+  pcie        records="host" brings the slabs, the post phase's records, the mismatch lists and the tags home and, with the device sink, sends
+              every record up twice; records="device_full" sends the super-batch's arrays up and brings both streams home, or nothing
+  e2e         e2e.run(layout="reference") with records="host" (the baseline: the parent's path) against records="device_full", both sinks,
+              alternating
+
 One JSON line per measurement on stdout, a table on stderr.  Usage: records_bench.py [--workload grch38] [--repeats 5] [--feeder device]
-[--workers 3] [--pairs-per-batch 250000] [--no-e2e] [--out-dir DIR]"""
+[--workers 3] [--pairs-per-batch 250000] [--layout workers|reference] [--chunk 40000000] [--no-e2e] [--out-dir DIR]"""
 import argparse
 import json
 import os
@@ -35,6 +44,8 @@ def main():
     ap.add_argument("--pairs-per-batch", type=int, default=250_000)
     ap.add_argument("--hbm-peak", type=float, default=8e12, help="bytes/s the fill's traffic is set against")
     ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--layout", default="workers", choices=["workers", "reference"], help="reference: also the full records phase, and the e2e arms of the reference's layout")
+    ap.add_argument("--chunk", type=int, default=40_000_000, help="bases per position bucket (--layout reference)")
     ap.add_argument("--cache", default="/tmp/arx_bench_cache")
     ap.add_argument("--lib", default=api.LIB_PATH, help="(dry runs of this script only) alternative library exporting the C ABI")
     ap.add_argument("--out-dir", default=None, help="where the FASTQ and BAM files go (default: <cache>/records_bench_<pid>; removed afterwards)")
@@ -91,6 +102,34 @@ def main():
             x["d2h"], x["h2d"] = round(x["d2h"] * scale), round(x["h2d"] * scale)
             rows.append((f"PCIe per 1 M pairs, {k}", f"D2H {x['d2h'] / 1e6:8.1f} MB  H2D {x['h2d'] / 1e6:8.1f} MB  {x.get('note', '')}"))
         print(json.dumps(dict(what="pcie_per_1M_pairs", n_regs=c["n_regs"], n_cands=n_cands, arms=pcie)), flush=True)
+        if args.layout == "reference":
+            # ---- the full phase on the same batch: tags once, then arx_batch_records_full
+            names, _, clens, _, _ = ref.contigs()
+            table = api.bucket_table(names, clens, args.chunk, lib_path=lib)
+            n_mm = b.post(fetch=False)               # (again, for the size of the mismatch lists; the tags go on top of it)
+            b.tags(fetch=False)
+            nf, nbf = b.records_full(sb, table)      # untimed
+            ref.kernel_times_reset(True)
+            for _ in range(args.repeats):
+                b.records_full(sb, table)
+            kt = ref.kernel_times()
+            ref.kernel_times_reset(False)
+            full_names = ("rec_mm_len", "rec_full_count", "rec_full_meta", "rec_tile", "rec_full_fill", "rec_group_count", "rec_group_rank", "rec_group_size", "rec_group_off", "scan")
+            per_phase = {k: kt[k]["ms"] / args.repeats for k in full_names if k in kt}      # per records_full call (rec_tile / rec_full_fill run twice in it)
+            print(json.dumps(dict(what="kernels_full", pairs=P, records=nf, stream_bytes=nbf, files=len(table.files), ms_per_phase={k: round(x, 4) for k, x in per_phase.items()},
+                                  ms_total=round(sum(per_phase.values()), 4))), flush=True)
+            for k, x in per_phase.items():
+                rows.append((f"full phase {k}", f"{x:9.4f} ms per {P} pairs"))
+            rows.append(("full phase stream", f"{nbf * scale / 1e6:.1f} MB per 1 M pairs, {nf} records, each written twice"))
+            home = slabs + api.SPLIT_DTYPE.itemsize * 2 * P + 8 * n_mm + api.TAGS_DTYPE.itemsize * 2 * P
+            upf = up + 4 * len(names)
+            pcie = {"records=host sink=host": dict(d2h=home, h2d=0), "records=host sink=device": dict(d2h=home, h2d=2 * nbf, note="plus the compressed blocks home"),
+                    "records=device_full sink=host": dict(d2h=2 * nbf + 16 * (len(table.files) + 1), h2d=upf),
+                    "records=device_full sink=device": dict(d2h=16 * (len(table.files) + 1), h2d=upf, note="plus the compressed blocks home")}
+            for k, x in pcie.items():
+                x["d2h"], x["h2d"] = round(x["d2h"] * scale), round(x["h2d"] * scale)
+                rows.append((f"PCIe per 1 M pairs (reference), {k}", f"D2H {x['d2h'] / 1e6:8.1f} MB  H2D {x['h2d'] / 1e6:8.1f} MB  {x.get('note', '')}"))
+            print(json.dumps(dict(what="pcie_per_1M_pairs_reference", n_mm=n_mm, arms=pcie)), flush=True)
         b.free()
         fd.close()
         # ---- end to end, four arms
@@ -99,12 +138,15 @@ def main():
             if args.feeder == "device":
                 kw.update(feeder="device", workers=args.workers)
             arms = [("host", "host"), ("device", "host"), ("host", "device"), ("device", "device")]
+            if args.layout == "reference":
+                arms = [("host", "host"), ("device_full", "host"), ("host", "device"), ("device_full", "device")]
+                kw.update(layout="reference", chunk=args.chunk)
             res = {a: [] for a in arms}
             for rep in range(args.repeats + 1):          # pass 0 of every arm is not counted: it pays for the handles' work memory and the sink's buffers
                 for records, sink in arms:
                     st = e2e.run(ref, [plain], os.path.join(d, f"out_{records}_{sink}"), records=records, sink=sink, **kw)
                     assert st["pairs"] == rs.n_pairs
-                    print(json.dumps(dict(what="e2e", counted=rep > 0, records=records, sink=sink, feeder=args.feeder, workers=st["workers"], pairs=st["pairs"], seconds=round(st["seconds"], 4),
+                    print(json.dumps(dict(what="e2e", layout=args.layout, counted=rep > 0, records=records, sink=sink, feeder=args.feeder, workers=st["workers"], pairs=st["pairs"], seconds=round(st["seconds"], 4),
                                           pairs_per_s=round(st["pairs_per_s"]), worker_seconds={k: round(st[k], 3) for k in ("feeder_s", "device_s", "fetch_s", "records_s", "bam_s")})), flush=True)
                     if rep > 0:
                         res[records, sink].append(st["pairs_per_s"])
