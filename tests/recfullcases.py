@@ -175,6 +175,13 @@ def check_identity(c):
     return n, nb
 
 
+def e2e_paths(st, layout, out):
+    """the files of a finished e2e.run(..., out, layout=layout) with stats st: name ("k.bam" for worker k's file) -> path"""
+    if layout == "reference":
+        return {f: os.path.join(out, f) for f in st["files"]}
+    return {f"{k}.bam": f"{out}.{k}.bam" for k in range(st["workers"])}
+
+
 def records_of(path):
     """the records of a BAM file as a list of their bytes"""
     data = rc.inflate(path)
