@@ -105,6 +105,8 @@ def _load(path):
     lib.arx_feeder_next.argtypes = [vp, i64, vp]
     lib.arx_feeder_close.argtypes = [vp]
     lib.arx_feeder_open_device.argtypes = [vp, C.c_char_p, C.c_char_p, i64, i32, C.POINTER(vp), C.c_char_p, i32]
+    if hasattr(lib, "arx_feeder_open_device_ex"):      # (a library built before the entry existed: Feeder(inflate="device") says so)
+        lib.arx_feeder_open_device_ex.argtypes = [vp, C.c_char_p, C.c_char_p, i64, i32, i32, C.POINTER(vp), C.c_char_p, i32]
     lib.arx_feeder_device_reads.argtypes = [vp, vp, vp, vp]
     lib.arx_feeder_stats.argtypes = [vp, vp]
     lib.arx_bam_open.argtypes = [C.c_char_p, i32, vp, vp, C.c_char_p, i32, i32, C.POINTER(vp), C.c_char_p, i32]
@@ -135,6 +137,7 @@ _SELFTEST_ARGS = {
                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
     "arx_selftest_gen_cigar": [C.c_int32, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
     "arx_selftest_bgzf": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "arx_selftest_inflate": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
     "arx_selftest_rec_text": [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
     # the device BAM sink: bound when first used, for the same reason
     "arx_bam_open_device": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
@@ -235,6 +238,44 @@ def bgzf_selftest(data, device: int = 0, lib_path: str = LIB_PATH):
     if rc != 0:
         raise ArachneError("arx_selftest_bgzf: code %d" % rc)
     return out[:out_len.value].tobytes(), dict(blocks=int(st[0]), stored=int(st[1]), fixed=int(st[2]), dynamic=int(st[3]))
+
+
+INFLATE_STATUS = ("OK", "BAD_HEADER", "BAD_BTYPE", "BAD_STORED_LEN", "BAD_CODE_LENGTHS", "BAD_SYMBOL", "BAD_DISTANCE", "TRUNCATED", "SIZE_MISMATCH", "CRC_MISMATCH")
+
+
+def selftest_inflate(chain, device: int = 0, fill: int = 0, lib_path: str = LIB_PATH):
+    """The device inflate's kernel on a chain of whole BGZF blocks (include/arachne_amd.h: arx_selftest_inflate) -> dict(rc: the entry's
+    return value (0, ARX_E_IO = -5 with a bad block, ARX_E_ARG = -2 for a chain that is no chain), out: the bytes of all blocks in order,
+    a bad block's left at `fill`, out_len: the bytes in front of the first bad block, status: one ARX_INFLATE_* per block,
+    blocks / compressed_bytes / inflated_bytes / deflate_blocks: the entry's stats)."""
+    lib = _load(lib_path)
+    src = np.frombuffer(bytes(chain), dtype=np.uint8)
+    n = len(src)
+    # room for what the chain says it holds: a walk over BSIZE and ISIZE (a chain that cannot be walked is refused by the entry before it writes)
+    cap, blocks, at = 0, 0, 0
+    raw = bytes(chain)
+    while at + 18 <= n:
+        xlen = raw[at + 10] | raw[at + 11] << 8
+        o, bsize = at + 12, 0
+        while o + 6 <= min(at + 12 + xlen, n) and not bsize:
+            if raw[o:o + 2] == b"BC" and raw[o + 2] | raw[o + 3] << 8 == 2:
+                bsize = (raw[o + 4] | raw[o + 5] << 8) + 1
+            o += 4 + (raw[o + 2] | raw[o + 3] << 8)
+        if not bsize or at + bsize > n or bsize < 12 + xlen + 8:
+            break
+        cap += min(int.from_bytes(raw[at + bsize - 4:at + bsize], "little"), 65536)
+        blocks += 1
+        at += bsize
+    out = np.full(cap + 8, fill, dtype=np.uint8)
+    cap = len(out)
+    status = np.full(blocks + 1, -1, dtype=np.int32)
+    out_len, st = C.c_int64(-1), np.zeros(4, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_inflate")(device, src.ctypes.data if n else None, n, out.ctypes.data, cap, C.byref(out_len), status.ctypes.data, len(status),
+                                                   st.ctypes.data)
+    if rc not in (0, -2, -5):
+        raise ArachneError("arx_selftest_inflate: code %d" % rc)
+    return dict(rc=rc, out=out[:int(st[2])].tobytes(), out_len=int(out_len.value), status=[int(x) for x in status[:int(st[0])]], blocks=int(st[0]),
+                compressed_bytes=int(st[1]), inflated_bytes=int(st[2]), deflate_blocks=int(st[3]))
 
 
 def index_build(fasta: str, prefix: str, lib_path: str = LIB_PATH) -> None:
@@ -545,12 +586,28 @@ class Feeder:
 
     device=<Reference>: the device feeder (arx_feeder_open_device) -- two reader threads, the parse on that reference's GPU; the
     super-batches are byte for byte the host feeder's.  chunk_bytes: bytes of each file's inflated stream per chunk (0: the default);
-    depth: the arrays of call k stay valid until call k + depth returns (next_raw's views and device_reads)."""
+    depth: the arrays of call k stay valid until call k + depth returns (next_raw's views and device_reads).
+    inflate="device" (device feeder only; arx_feeder_open_device_ex with ARX_FEEDER_INFLATE_DEVICE): a file that is BGZF is inflated by a
+    HIP kernel instead of zlib on its reader thread; "host" (the default): zlib for every file."""
 
-    def __init__(self, r1: str, r2: str, lib_path: str = LIB_PATH, device: "Reference | None" = None, chunk_bytes: int = 0, depth: int = 1):
+    INFLATE_DEVICE = 1           # ARX_FEEDER_INFLATE_DEVICE
+
+    def __init__(self, r1: str, r2: str, lib_path: str = LIB_PATH, device: "Reference | None" = None, chunk_bytes: int = 0, depth: int = 1, inflate: str = "host"):
         self.h = C.c_void_p()
         msg = C.create_string_buffer(512)
         self.device = device
+        if inflate not in ("host", "device"):
+            raise ValueError("inflate is 'host' or 'device'")
+        if inflate == "device" and device is None:
+            raise ValueError("inflate='device' needs the device feeder (device=<Reference>): the host feeder inflates with zlib")
+        if device is not None and inflate == "device":
+            self.lib = device.lib
+            if not hasattr(self.lib, "arx_feeder_open_device_ex"):
+                raise ArachneError("inflate='device': this library has no arx_feeder_open_device_ex (rebuild it)")
+            rc = self.lib.arx_feeder_open_device_ex(device.h, r1.encode(), r2.encode(), int(chunk_bytes), int(depth), self.INFLATE_DEVICE, C.byref(self.h), msg, 512)
+            if rc != 0:
+                raise ArachneError("arx_feeder_open_device_ex: " + msg.value.decode())
+            return
         if device is not None:
             self.lib = device.lib
             if self.lib.arx_feeder_open_device(device.h, r1.encode(), r2.encode(), int(chunk_bytes), int(depth), C.byref(self.h), msg, 512) != 0:
@@ -572,7 +629,7 @@ class Feeder:
         st = (C.c_int64 * 8)()
         if self.lib.arx_feeder_stats(self.h, st) != 0:
             raise ArachneError("arx_feeder_stats: not a device feeder")
-        return dict(chunks=st[0], bytes=st[1], records=st[2], bad_lines=st[3], runs=st[4], fallback_chunks=st[5])
+        return dict(chunks=st[0], bytes=st[1], records=st[2], bad_lines=st[3], runs=st[4], fallback_chunks=st[5], device_blocks=st[6], compressed_bytes=st[7])
 
     def next(self, target_pairs: int):
         """-> dict (numpy copies) or None at the end of the input"""

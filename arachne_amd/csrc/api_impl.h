@@ -647,25 +647,32 @@ template <class RT> struct Batch {
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	void arx_batch_free(arx_ctx *, arx_batch *bh) { try { delete (Bat *)bh; } catch (...) {} }                                      \
+	int arx_feeder_open_device_ex(arx_ctx *h, const char *r1, const char *r2, int64_t chunk_bytes, int32_t depth, int32_t flags,    \
+	                              arx_feeder **out, char *msg, int32_t msg_cap)                                                     \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h;                                                                                                             \
+		*out = 0;                                                                                                                      \
+		std::string e;                                                                                                                 \
+		arx::DeviceFeeder<RT> *f = 0;                                                                                                  \
+		int rc = ARX_OK;                                                                                                               \
+		if (!c || !r1 || !r2 || depth < 1 || depth > 64 || chunk_bytes < 0 || chunk_bytes > (int64_t)arx::DeviceFeeder<RT>::MAX_CHUNK) {\
+			e = "arx_feeder_open_device: 1 <= depth <= 64 and 0 <= chunk_bytes <= 2^28"; rc = ARX_E_ARG;                                  \
+		} else if (flags & ~ARX_FEEDER_INFLATE_DEVICE) {                                                                               \
+			e = "arx_feeder_open_device_ex: unknown flag bits"; rc = ARX_E_ARG;                                                           \
+		} else try {                                                                                                                   \
+			f = new arx::DeviceFeeder<RT>(c->device, (size_t)chunk_bytes, depth, flags);                                                  \
+			rc = f->open(r1, r2);                                                                                                         \
+			if (rc != ARX_OK) { e = f->error; delete f; f = 0; }                                                                          \
+		} catch (const std::exception &ex) { e = ex.what(); rc = ARX_E_DEVICE; delete f; f = 0; }                                      \
+		if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", e.c_str());                                                       \
+		if (rc != ARX_OK) return rc;                                                                                                   \
+		*out = (arx_feeder *)(arx::FeederBase *)f;                                                                                     \
+		return ARX_OK;                                                                                                                 \
+	}                                                                                                                               \
 	int arx_feeder_open_device(arx_ctx *h, const char *r1, const char *r2, int64_t chunk_bytes, int32_t depth, arx_feeder **out,    \
 	                           char *msg, int32_t msg_cap)                                                                          \
 	{                                                                                                                               \
-		Ctx *c = (Ctx *)h;                                                                                                          \
-		*out = 0;                                                                                                                   \
-		std::string e;                                                                                                              \
-		arx::DeviceFeeder<RT> *f = 0;                                                                                               \
-		int rc = ARX_OK;                                                                                                            \
-		if (!c || !r1 || !r2 || depth < 1 || depth > 64 || chunk_bytes < 0 || chunk_bytes > (int64_t)arx::DeviceFeeder<RT>::MAX_CHUNK) { \
-			e = "arx_feeder_open_device: 1 <= depth <= 64 and 0 <= chunk_bytes <= 2^28"; rc = ARX_E_ARG;                            \
-		} else try {                                                                                                                \
-			f = new arx::DeviceFeeder<RT>(c->device, (size_t)chunk_bytes, depth);                                                   \
-			rc = f->open(r1, r2);                                                                                                   \
-			if (rc != ARX_OK) { e = f->error; delete f; f = 0; }                                                                    \
-		} catch (const std::exception &ex) { e = ex.what(); rc = ARX_E_DEVICE; delete f; f = 0; }                                   \
-		if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", e.c_str());                                                    \
-		if (rc != ARX_OK) return rc;                                                                                                \
-		*out = (arx_feeder *)(arx::FeederBase *)f;                                                                                  \
-		return ARX_OK;                                                                                                              \
+		return arx_feeder_open_device_ex(h, r1, r2, chunk_bytes, depth, 0, out, msg, msg_cap);                                         \
 	}                                                                                                                               \
 	int arx_kernel_times(arx_ctx *h, int32_t cap, char *names, int32_t name_w, double *ms, int64_t *calls, int64_t *items)          \
 	{                                                                                                                               \

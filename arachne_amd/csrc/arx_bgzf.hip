@@ -1,10 +1,12 @@
 // arx_bgzf.hip -- the device BAM sink (include/arachne_amd.h: arx_bam_open_device, arx_bam_write_encoded_device, arx_selftest_bgzf): BamSink (bam_sink.h) with the compressor of
-// hip_bgzf.h behind its seam.  Its own unit: the kernels of dev_bgzf.h compile next to the pipeline's.
+// hip_bgzf.h behind its seam.  Its own unit: the kernels of dev_bgzf.h compile next to the pipeline's.  The mirror image lives here too: the
+// inflate kernel of hip_inflate.h (arx_selftest_inflate; the device feeder starts it through inflate_launch).
 #include <map>
 #include <memory>
 #include <mutex>
 #include "../../include/arachne_amd.h"
 #include "hip_bgzf.h"
+#include "hip_inflate.h"
 
 namespace arx {
 
@@ -23,6 +25,15 @@ static std::shared_ptr<DeviceBgzf> shared_device_bgzf(int device)
 		p = z;
 	}
 	return p;
+}
+
+void inflate_launch(hipStream_t stream, const uint8_t *d_src, int64_t src_bytes, const InfRow *d_rows, int n_blocks, uint8_t *d_out, int64_t out_bytes, int32_t *d_status,
+                    int32_t *d_counts)
+{
+	if (n_blocks <= 0) return;
+	// per device and cheap; set on every launch rather than remembered per device
+	ARX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bgzf_inflate, hipFuncAttributeMaxDynamicSharedMemorySize, INF_LDS_BYTES));
+	hip_launch("k_bgzf_inflate", k_bgzf_inflate, dim3(n_blocks), dim3(INF_LANES), INF_LDS_BYTES, stream, d_src, src_bytes, d_rows, n_blocks, d_out, out_bytes, d_status, d_counts);
 }
 
 } // namespace arx
@@ -100,4 +111,56 @@ extern "C" int arx_selftest_bgzf(int32_t device, const uint8_t *src, int64_t n, 
 		return ARX_E_DEVICE;
 	}
 	return ARX_OK;
+}
+
+extern "C" int arx_selftest_inflate(int32_t device, const uint8_t *src, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, int32_t *status, int32_t status_cap,
+                                    int64_t *stats)
+{
+	static_assert(ARX_INFLATE_CRC_MISMATCH == arx::INF_CRC_MISMATCH && ARX_INFLATE_BAD_HEADER == arx::INF_BAD_HEADER, "the public statuses are dev_inflate.h's");
+	if (n < 0 || cap < 0 || status_cap < 0 || !out_len || (n > 0 && (!src || !status)) || (cap > 0 && !out)) return ARX_E_ARG;
+	*out_len = 0;
+	if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+	if (n == 0) return ARX_OK;
+	int64_t total = 0;
+	const int64_t nb = arx::bgzf_walk(src, n, nullptr, 0, &total);
+	if (nb < 0 || nb > status_cap || nb > INT32_MAX || total > cap) return ARX_E_ARG;
+	std::vector<arx::InfRow> rows((size_t)nb);
+	arx::bgzf_walk(src, n, rows.data(), nb, &total);
+	uint8_t *d_src = nullptr, *d_out = nullptr;
+	arx::InfRow *d_rows = nullptr;
+	int32_t *d_status = nullptr; // nb statuses, then the two counts
+	int rc = ARX_OK;
+	try {
+		int n_dev = 0;
+		if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return ARX_E_DEVICE;
+		ARX_HIP_CHECK(hipSetDevice(device));
+		ARX_HIP_CHECK(hipMalloc((void **)&d_src, (size_t)n));
+		ARX_HIP_CHECK(hipMalloc((void **)&d_out, (size_t)(total ? total : 1)));
+		ARX_HIP_CHECK(hipMalloc((void **)&d_rows, sizeof(arx::InfRow) * (size_t)nb));
+		ARX_HIP_CHECK(hipMalloc((void **)&d_status, 4 * ((size_t)nb + 2)));
+		ARX_HIP_CHECK(hipMemcpy(d_src, src, (size_t)n, hipMemcpyHostToDevice));
+		ARX_HIP_CHECK(hipMemcpy(d_rows, rows.data(), sizeof(arx::InfRow) * (size_t)nb, hipMemcpyHostToDevice));
+		if (total) ARX_HIP_CHECK(hipMemcpy(d_out, out, (size_t)total, hipMemcpyHostToDevice)); // what a bad block leaves alone comes back as it was
+		ARX_HIP_CHECK(hipMemset(d_status, 0, 4 * ((size_t)nb + 2)));
+		arx::inflate_launch(nullptr, d_src, n, d_rows, (int)nb, d_out, total, d_status, d_status + nb);
+		ARX_HIP_CHECK(hipDeviceSynchronize());
+		int32_t counts[2];
+		ARX_HIP_CHECK(hipMemcpy(status, d_status, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+		ARX_HIP_CHECK(hipMemcpy(counts, d_status + nb, 8, hipMemcpyDeviceToHost));
+		if (total) ARX_HIP_CHECK(hipMemcpy(out, d_out, (size_t)total, hipMemcpyDeviceToHost));
+		int64_t good = 0, n_bad = 0;
+		bool all = true;
+		for (int64_t b = 0; b < nb; ++b) {
+			if (status[b] != arx::INF_OK) { all = false; ++n_bad; }
+			if (all) good += rows[(size_t)b].isize;
+		}
+		if (n_bad != counts[0]) rc = ARX_E_DEVICE; // the count the feeder relies on is the statuses'
+		else rc = all ? ARX_OK : ARX_E_IO;
+		*out_len = good;
+		if (stats) { stats[0] = nb; stats[1] = n; stats[2] = total; stats[3] = counts[1]; }
+	} catch (const std::exception &) {
+		rc = ARX_E_DEVICE;
+	}
+	(void)hipFree(d_src); (void)hipFree(d_out); (void)hipFree(d_rows); (void)hipFree(d_status);
+	return rc;
 }

@@ -1,7 +1,11 @@
 // device_feeder.h -- the FASTQ feeder whose per-byte work runs on the device (arx_feeder_open_device): what feeder.h's Feeder does on
 // one host thread per file pair, re-shaped so that ONE file pair can feed several workers.
 //
-//   two ChunkReader threads (feeder.h)   inflate R1 and R2 side by side into page-locked buffers, chunk by chunk
+//   two reader threads (feeder.h)        ChunkReader: inflate R1 and R2 side by side into page-locked buffers, chunk by chunk; or, for a
+//                                         BGZF file of a feeder opened with ARX_FEEDER_INFLATE_DEVICE, BgzfChunkReader: whole blocks as
+//                                         they are in the file, with one table row per block
+//   step()                                uploads what both readers have; a BGZF slab's blocks are inflated on the device (dev_inflate.h),
+//                                         straight into the window behind the carry, so that the parse sees text either way
 //   parse_window()                        uploads what both readers have, runs dev_fastq.h's functors on the raw text (line index, record
 //                                         recognition, header fields, base codes, barcode runs) and copies one output blob home
 //   next()                                ReadBarcodeSet's rules (feeder.h:141-169) applied to the run list on the host; whole sets are
@@ -16,6 +20,7 @@
 #pragma once
 #include <chrono>
 #include <deque>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -23,13 +28,50 @@
 #include "dev_fastq.h"
 #include "switches.h"
 
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#else
+#include "dev_inflate.h"
+#endif
+
 namespace arx {
+
+// The inflate of a slab's BGZF blocks, enqueued on the runtime's stream: the HIP kernel (hip_inflate.h, compiled in arx_bgzf.hip) with the HIP
+// runtime, the same dev_inflate.h functions with the lanes in a loop with the sequential runtime of the host test double.  Everything is
+// device memory; counts[0] is raised per block that is not INF_OK, counts[1] by the DEFLATE blocks read
+#if defined(__HIPCC__)
+void inflate_launch(hipStream_t stream, const uint8_t *d_src, int64_t src_bytes, const InfRow *d_rows, int n_blocks, uint8_t *d_out, int64_t out_bytes, int32_t *d_status,
+                    int32_t *d_counts);
+template <class RT> inline void inflate_rows(RT &rt, const uint8_t *src, int64_t src_bytes, const InfRow *rows, int n, uint8_t *out, int64_t out_bytes, int32_t *status, int32_t *counts)
+{
+	typename RT::Scope sc(rt, "bgzf_inflate", n);
+	inflate_launch(rt.stream, src, src_bytes, rows, n, out, out_bytes, status, counts);
+}
+#else
+struct InfLoopDrv { template <class F> void lanes(F f) { for (int l = 0; l < INF_LANES; ++l) f(l); } };
+template <class RT> inline void inflate_rows(RT &, const uint8_t *src, int64_t src_bytes, const InfRow *rows, int n, uint8_t *out, int64_t out_bytes, int32_t *status, int32_t *counts)
+{
+	std::vector<uint8_t> mem(INF_WORK_BYTES + 4), lds_out(INF_MAX_OUT);
+	InfWork w;
+	inf_carve(w, mem.data() + ((4 - ((uintptr_t)mem.data() & 3)) & 3), lds_out.data());
+	InfLoopDrv drv;
+	for (int b = 0; b < n; ++b) {
+		const InfRow &r = rows[b];
+		int st = INF_BAD_HEADER, nd = 0;
+		if (inf_row_in_range(r, src_bytes, out_bytes)) st = inf_block(drv, w, src + r.coff, r.clen, r.isize, r.crc, out + r.ooff, &nd);
+		status[b] = st;
+		if (st != INF_OK) ++counts[0];
+		counts[1] += nd;
+	}
+}
+#endif
 
 template <class RT> class DeviceFeeder : public FeederBase {
 public:
 	static constexpr size_t DEFAULT_CHUNK = (size_t)8 << 20, MAX_CHUNK = (size_t)256 << 20, SLAB_TARGET = (size_t)8 << 20;
 
-	DeviceFeeder(int device, size_t chunk_bytes, int depth) : device_(device), chunk_(chunk_bytes ? chunk_bytes : DEFAULT_CHUNK), slots_((size_t)depth + 2) {}
+	// flags: ARX_FEEDER_INFLATE_DEVICE -- a file that is BGZF is read as it is and inflated on the device
+	DeviceFeeder(int device, size_t chunk_bytes, int depth, int flags = 0) : device_(device), flags_(flags), chunk_(chunk_bytes ? chunk_bytes : DEFAULT_CHUNK), slots_((size_t)depth + 2) {}
 
 	// ARX_OK, ARX_E_IO (a file cannot be opened) or ARX_E_DEVICE (no GPU); `error` says which
 	int open(const char *r1, const char *r2)
@@ -40,16 +82,27 @@ public:
 		per = per < 1 ? 1 : per > 64 ? 64 : per;
 		if (sw_.parse_chunks) { const long v = *sw_.parse_chunks; if (v >= 1 && (size_t)v * chunk_ <= MAX_CHUNK) per = (size_t)v; }
 		const char *path[2] = {r1, r2};
-		for (int f = 0; f < 2; ++f)
-			if (!rd_[f].open(path[f], chunk_, per)) { error = std::string("cannot open ") + path[f]; return ARX_E_IO; }
+		for (int f = 0; f < 2; ++f) { // each file by its own first bytes: R1 may be BGZF where R2 is ordinary gzip or plain text
+			bool ok;
+			bgzf_[f] = (flags_ & ARX_FEEDER_INFLATE_DEVICE) && file_is_bgzf(path[f]);
+			if (bgzf_[f]) { std::unique_ptr<BgzfChunkReader> r(new BgzfChunkReader()); ok = r->open(path[f], chunk_, per); rd_[f] = std::move(r); }
+			else { std::unique_ptr<ChunkReader> r(new ChunkReader()); ok = r->open(path[f], chunk_, per); rd_[f] = std::move(r); }
+			if (!ok) { error = std::string("cannot open ") + path[f]; return ARX_E_IO; }
+		}
 		const std::string e = rt.init(device_);
 		if (!e.empty()) { error = e; return ARX_E_DEVICE; }
 		ready_ = true;
 		if (sw_.times) rt.set_timing(true);
 		for (int f = 0; f < 2; ++f)
-			for (int i = 0; i < 2; ++i) registered_[f][i] = RT::host_register(rd_[f].slab(i), rd_[f].slab_cap()) == 0;
+			for (int i = 0; i < 2; ++i) registered_[f][i] = RT::host_register(rd_[f]->slab(i), rd_[f]->slab_cap()) == 0;
 		meta_ = rt.template palloc<int32_t>(16);
-		for (int f = 0; f < 2; ++f) rd_[f].start();
+		if (bgzf_[0] || bgzf_[1]) {
+			icnt_ = rt.template palloc<int32_t>(4);
+			if (posix_memalign((void **)&hcnt_, 4096, 4096)) { hcnt_ = nullptr; throw std::bad_alloc(); }
+			memset(hcnt_, 0, 4096);
+			hcnt_reg_ = RT::host_register(hcnt_, 4096) == 0;
+		}
+		for (int f = 0; f < 2; ++f) rd_[f]->start();
 		return ARX_OK;
 	}
 
@@ -66,9 +119,12 @@ public:
 		try { rt.sync(); } catch (...) {}
 		for (int f = 0; f < 2; ++f)
 			for (int i = 0; i < 2; ++i) {
-				if (registered_[f][i]) RT::host_unregister(rd_[f].slab(i));
+				if (registered_[f][i]) RT::host_unregister(rd_[f]->slab(i));
 				rt.pfree(win_[f][i].p);
 			}
+		for (int f = 0; f < 2; ++f) { rt.pfree(cin_[f].p); rt.pfree(rows_[f].p); rt.pfree(ist_[f].p); }
+		rt.pfree(icnt_);
+		if (hcnt_) { if (hcnt_reg_) RT::host_unregister(hcnt_); free(hcnt_); }
 		if (hblob_) { if (hblob_reg_) RT::host_unregister(hblob_); free(hblob_); }
 		rt.pfree(cnt_.p); rt.pfree(off_.p); rt.pfree(nl_.p); rt.pfree(bmap_.p); rt.pfree(bstate_.p); rt.pfree(hdr_.p); rt.pfree(rcnt_.p); rt.pfree(roff_.p);
 		rt.pfree(recl_.p); rt.pfree(tmp_.p); rt.pfree(sc_.p); rt.pfree(so_.p); rt.pfree(dvalid_.p); rt.pfree(blob_.p); rt.pfree(meta_);
@@ -142,7 +198,7 @@ public:
 
 	int stats(int64_t *st) override
 	{
-		st[0] = n_chunks_; st[1] = n_bytes_; st[2] = n_records_; st[3] = bad_base_; st[4] = n_runs_; st[5] = 0; st[6] = st[7] = 0;
+		st[0] = n_chunks_; st[1] = n_bytes_; st[2] = n_records_; st[3] = bad_base_; st[4] = n_runs_; st[5] = 0; st[6] = n_dev_blocks_; st[7] = n_cbytes_;
 		return ARX_OK;
 	}
 
@@ -230,24 +286,52 @@ private:
 	{
 		bool want[2];
 		for (int f = 0; f < 2; ++f) want[f] = !eof_[f] && (lim_[f] || wlen_[f] < chunk_);
-		const ChunkReader::Slab *sl[2] = {nullptr, nullptr};
+		const SlabReader::Slab *sl[2] = {nullptr, nullptr};
 		double t0 = now();
-		for (int f = 0; f < 2; ++f) if (want[f]) { sl[f] = rd_[f].acquire(); if (!sl[f]) eof_[f] = true; }
+		for (int f = 0; f < 2; ++f) if (want[f]) { sl[f] = rd_[f]->acquire(); if (!sl[f]) eof_[f] = true; }
 		t_[0] += now() - t0; t0 = now();
+		// the tables of both files' BGZF slabs go up through the runtime's page-locked staging (the stream is idle here: stage() does not wait)
+		size_t row_at[2] = {0, 0}, row_bytes = 0;
+		for (int f = 0; f < 2; ++f) if (sl[f] && bgzf_[f]) { row_at[f] = row_bytes; row_bytes += sl[f]->n_rows * sizeof(InfRow); }
+		uint8_t *staged_rows = row_bytes ? (uint8_t *)rt.stage(row_bytes) : nullptr;
 		for (int f = 0; f < 2; ++f) {
 			if (!sl[f]) continue;
+			const SlabReader::Slab &s = *sl[f];
 			DBuf<uint8_t> &w = win_[f][wcur_[f]];
-			ensure_keep(w, wlen_[f] + sl[f]->len + 64, wlen_[f]);
-			rt.h2d_staged(w.p + wlen_[f], sl[f]->buf, sl[f]->len);
+			ensure_keep(w, wlen_[f] + s.text + 64, wlen_[f]);
+			if (!bgzf_[f]) { rt.h2d_staged(w.p + wlen_[f], s.buf, s.len); continue; }
+			if (!s.n_rows) continue;
+			// the compressed blocks and their table go up; the text appears behind the carry; the count of bad blocks comes home with the wait below
+			ensure(cin_[f], s.len + 64); ensure(rows_[f], s.n_rows); ensure(ist_[f], s.n_rows);
+			rt.h2d_staged(cin_[f].p, s.buf, s.len);
+			memcpy(staged_rows + row_at[f], s.rows, s.n_rows * sizeof(InfRow));
+			rt.h2d_staged(rows_[f].p, staged_rows + row_at[f], s.n_rows * sizeof(InfRow));
+			rt.memset0(icnt_ + 2 * f, 8);
+			inflate_rows(rt, cin_[f].p, (int64_t)s.len, rows_[f].p, (int)s.n_rows, w.p + wlen_[f], (int64_t)s.text, ist_[f].p, icnt_ + 2 * f);
+			rt.d2h_async(hcnt_ + 2 * f, icnt_ + 2 * f, 8);
 		}
 		rt.sync(); // the readers may refill the buffers
 		t_[1] += now() - t0;
 		for (int f = 0; f < 2; ++f) {
 			if (!sl[f]) continue;
-			wlen_[f] += sl[f]->len; n_bytes_ += (int64_t)sl[f]->len; n_chunks_ += sl[f]->chunks;
-			if (sl[f]->eof || sl[f]->err) eof_[f] = true;
-			if (sl[f]->err) err_ = true;
-			rd_[f].release();
+			const SlabReader::Slab &s = *sl[f];
+			size_t text = s.text;
+			bool bad = false;
+			if (bgzf_[f] && s.n_rows) {
+				n_dev_blocks_ += (int64_t)s.n_rows; n_cbytes_ += (int64_t)s.len;
+				if (hcnt_[2 * f] != 0) { // a block that did not inflate: the input ends in front of the first one, as at a read error of the host's inflate
+					std::vector<int32_t> st(s.n_rows);
+					rt.d2h(st.data(), ist_[f].p, 4 * s.n_rows);
+					size_t b = 0;
+					while (b < s.n_rows && st[b] == 0) ++b;
+					text = b < s.n_rows ? (size_t)s.rows[b].ooff : s.text;
+					bad = true;
+				}
+			}
+			wlen_[f] += text; n_bytes_ += (int64_t)text; n_chunks_ += s.chunks;
+			if (s.eof || s.err || bad) eof_[f] = true;
+			if (s.err || bad) err_ = true;
+			rd_[f]->release();
 		}
 		if (wlen_[0] >= ((size_t)1 << 30) || wlen_[1] >= ((size_t)1 << 30)) throw std::runtime_error("FASTQ input: a record of more than 2^30 bytes");
 		parse_window(S);
@@ -361,9 +445,13 @@ private:
 
 	RT rt;
 	const FeederSwitches sw_; // read when the feeder is created (switches.h)
-	int device_;
+	int device_, flags_;
 	size_t chunk_;
-	ChunkReader rd_[2];
+	std::unique_ptr<SlabReader> rd_[2];
+	bool bgzf_[2] = {false, false};                 // the file's blocks are inflated on the device
+	DBuf<uint8_t> cin_[2]; DBuf<InfRow> rows_[2]; DBuf<int32_t> ist_[2]; // a BGZF slab on the device: its bytes, its table, the blocks' statuses
+	int32_t *icnt_ = nullptr, *hcnt_ = nullptr; bool hcnt_reg_ = false;  // per file: bad blocks, DEFLATE blocks read; device and page-locked host
+	int64_t n_dev_blocks_ = 0, n_cbytes_ = 0;
 	bool registered_[2][2] = {{false, false}, {false, false}};
 	DBuf<uint8_t> win_[2][2]; int wcur_[2] = {0, 0}; size_t wlen_[2] = {0, 0};
 	bool ready_ = false, eof_[2] = {false, false}, lim_[2] = {true, true}, end_ = false, err_ = false;

@@ -12,6 +12,7 @@
 // Plain C++ (no device code); compiled into libarachne_amd.so and, for the CPU tests, into the host test double.
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <condition_variable>
@@ -21,6 +22,7 @@
 #include <vector>
 #include <zlib.h>
 #include "../../include/arachne_amd.h"
+#include "bgzf_walk.h"
 
 namespace arx {
 
@@ -121,32 +123,21 @@ public:
 	virtual int stats(int64_t *) { return ARX_E_ARG; }
 };
 
-// One file of the device feeder: a thread of its own inflates it (gzread: plain files too) chunk by chunk into one of two buffers
-// while the other one is uploaded and parsed.  Chunk k is bytes [k * chunk_bytes, (k + 1) * chunk_bytes) of the inflated stream;
-// a buffer ("slab") holds a whole number of chunks.  The buffers are the caller's to page-lock (slab(i), slab_cap()).
-class ChunkReader {
+// One file of the device feeder: a thread of its own reads it slab by slab into one of two buffers while the other one is uploaded and
+// parsed.  SlabReader is the protocol -- two slabs, the thread, acquire() / release() --; what a slab holds is the derived class's fill():
+//   ChunkReader      inflates the file through zlib (gzread: plain files too).  Chunk k is bytes [k * chunk_bytes, (k + 1) * chunk_bytes) of
+//                    the inflated stream; a slab holds a whole number of chunks
+//   BgzfChunkReader  reads a BGZF file as it is: whole blocks, still compressed, and one InfRow (dev_inflate.h) per block.  The device
+//                    inflates them (arx_feeder_open_device_ex with ARX_FEEDER_INFLATE_DEVICE)
+// The buffers are the caller's to page-lock (slab(i), slab_cap()).
+class SlabReader {
 public:
-	struct Slab { char *buf = nullptr; size_t len = 0; int64_t chunks = 0; bool eof = false, err = false, full = false; };
-	bool open(const char *path, size_t chunk_bytes, size_t chunks_per_slab)
-	{
-		f_ = gzopen(path, "rb");
-		if (!f_) return false;
-		gzbuffer(f_, 1 << 20);
-		chunk_ = chunk_bytes; cap_ = chunk_bytes * chunks_per_slab;
-		for (Slab &s : slab_) { if (posix_memalign((void **)&s.buf, 4096, cap_ + 64)) { s.buf = nullptr; return false; } }
-		return true;
-	}
+	// len bytes of buf: text, or for a BGZF slab (n_rows > 0, or text == 0) whole compressed blocks that inflate to `text` bytes
+	struct Slab { char *buf = nullptr; size_t len = 0, text = 0; int64_t chunks = 0; const InfRow *rows = nullptr; size_t n_rows = 0; bool eof = false, err = false, full = false; };
+	virtual ~SlabReader() {}
 	void start() { th_ = std::thread([this] { run(); }); }
-	~ChunkReader()
-	{
-		{ std::lock_guard<std::mutex> g(mu_); stop_ = true; }
-		cv_.notify_all();
-		if (th_.joinable()) th_.join();
-		if (f_) gzclose(f_);
-		for (Slab &s : slab_) free(s.buf);
-	}
 	char *slab(int i) const { return slab_[i].buf; }
-	size_t slab_cap() const { return cap_ + 64; }
+	size_t slab_cap() const { return bytes_; }
 	// the next slab in file order (waits for it); nullptr once the slab that carried eof or an error has been taken
 	const Slab *acquire()
 	{
@@ -163,6 +154,22 @@ public:
 		cv_.notify_all();
 	}
 	bool done() const { return done_; }
+protected:
+	bool alloc_slabs(size_t bytes)
+	{
+		bytes_ = bytes;
+		for (Slab &s : slab_) { if (posix_memalign((void **)&s.buf, 4096, bytes_)) { s.buf = nullptr; return false; } }
+		return true;
+	}
+	void stop() // every derived destructor calls it first: the thread runs the derived fill()
+	{
+		{ std::lock_guard<std::mutex> g(mu_); stop_ = true; }
+		cv_.notify_all();
+		if (th_.joinable()) th_.join();
+	}
+	void free_slabs() { for (Slab &s : slab_) { free(s.buf); s.buf = nullptr; } }
+	// slab k & 1 from the file: everything but `full` of the Slab it is given
+	virtual void fill(int k, Slab &s) = 0;
 private:
 	void run()
 	{
@@ -173,26 +180,133 @@ private:
 				cv_.wait(g, [&] { return stop_ || !s.full; });
 				if (stop_) return;
 			}
-			size_t len = 0; int64_t chunks = 0; bool eof = false, err = false;
-			while (len < cap_) {
-				const int got = gzread(f_, s.buf + len, (unsigned)chunk_);
-				if (got < 0) { err = true; break; }
-				if (got > 0) { len += (size_t)got; ++chunks; }
-				if ((size_t)got < chunk_) { eof = true; break; }
-			}
-			{ std::lock_guard<std::mutex> g(mu_); s.len = len; s.chunks = chunks; s.eof = eof; s.err = err; s.full = true; }
+			Slab t;
+			t.buf = s.buf;
+			fill(k, t);
+			{ std::lock_guard<std::mutex> g(mu_); s = t; s.full = true; }
 			cv_.notify_all();
-			if (eof || err) return;
+			if (t.eof || t.err) return;
 		}
 	}
-	gzFile f_ = nullptr;
-	size_t chunk_ = 0, cap_ = 0;
+	size_t bytes_ = 0;
 	Slab slab_[2];
 	std::thread th_;
 	std::mutex mu_;
 	std::condition_variable cv_;
 	int take_ = 0;
 	bool stop_ = false, done_ = false;
+};
+
+class ChunkReader : public SlabReader {
+public:
+	bool open(const char *path, size_t chunk_bytes, size_t chunks_per_slab)
+	{
+		f_ = gzopen(path, "rb");
+		if (!f_) return false;
+		gzbuffer(f_, 1 << 20);
+		chunk_ = chunk_bytes; cap_ = chunk_bytes * chunks_per_slab;
+		return alloc_slabs(cap_ + 64);
+	}
+	~ChunkReader() override
+	{
+		stop();
+		if (f_) gzclose(f_);
+		free_slabs();
+	}
+protected:
+	void fill(int, Slab &s) override
+	{
+		while (s.len < cap_) {
+			const int got = gzread(f_, s.buf + s.len, (unsigned)chunk_);
+			if (got < 0) { s.err = true; break; }
+			if (got > 0) { s.len += (size_t)got; ++s.chunks; }
+			if ((size_t)got < chunk_) { s.eof = true; break; }
+		}
+		s.text = s.len;
+	}
+private:
+	gzFile f_ = nullptr;
+	size_t chunk_ = 0, cap_ = 0;
+};
+
+// true where the file's first member is a BGZF block (bgzf_read_header: the test htslib makes); anything else -- plain text, ordinary gzip, a
+// file that cannot be read -- is not
+inline bool file_is_bgzf(const char *path)
+{
+	FILE *f = fopen(path, "rb");
+	if (!f) return false;
+	uint8_t h[12 + 65535];
+	size_t n = fread(h, 1, 12, f);
+	BgzfHeader bh;
+	int r = bgzf_read_header(h, n, &bh);
+	if (r == 0 && n == 12) { n += fread(h + 12, 1, (size_t)h[10] | (size_t)h[11] << 8, f); r = bgzf_read_header(h, n, &bh); }
+	fclose(f);
+	return r == 1;
+}
+
+class BgzfChunkReader : public SlabReader {
+public:
+	// A chunk is the longest run of whole blocks that inflate to at most chunk_bytes, and always at least one block; a slab holds
+	// chunks_per_slab chunks.  A slab's buffer takes the compressed form of that much text with an eighth to spare, and a block of 64 KiB per
+	// chunk at least; a chunk also ends where the buffer is full (a file of blocks that hold next to nothing)
+	bool open(const char *path, size_t chunk_bytes, size_t chunks_per_slab)
+	{
+		f_ = fopen(path, "rb");
+		if (!f_) return false;
+		setvbuf(f_, nullptr, _IOFBF, 1 << 20);
+		chunk_ = chunk_bytes; per_ = chunks_per_slab;
+		const size_t text = chunk_bytes * chunks_per_slab, blocks = chunks_per_slab * 65536;
+		return alloc_slabs((text + text / 8 > blocks ? text + text / 8 : blocks) + 65536 + 64);
+	}
+	~BgzfChunkReader() override
+	{
+		stop();
+		if (f_) fclose(f_);
+		free_slabs();
+	}
+protected:
+	void fill(int k, Slab &s) override
+	{
+		std::vector<InfRow> &rows = rows_[k & 1];
+		rows.clear();
+		const size_t room = slab_cap() - 64;
+		size_t in_chunk = 0; // text of the chunk that is being filled
+		bool open_chunk = false;
+		for (;;) {
+			if (!have_) { // the next block's header: 12 bytes, then the extra field
+				const size_t got = fread(head_, 1, 12, f_);
+				if (got == 0 && feof(f_) && !ferror(f_)) { s.eof = true; break; } // the end of the file between two blocks (no EOF block needed)
+				BgzfHeader h;
+				size_t n = got;
+				int r = bgzf_read_header(head_, n, &h);
+				if (r == 0 && got == 12) { n += fread(head_ + 12, 1, (size_t)head_[10] | (size_t)head_[11] << 8, f_); r = bgzf_read_header(head_, n, &h); }
+				if (r != 1 || (size_t)h.block < n) { s.err = true; break; } // no BGZF header, or the file ends inside one
+				hdr_ = h; head_n_ = n; have_ = true;
+				const size_t rest = (size_t)h.block - n; // the trailer's ISIZE decides where the block goes: it is read now, into its place behind the header
+				if (fread(head_ + n, 1, rest, f_) != rest) { s.err = true; break; } // BSIZE runs past the end of the file
+				row_ = bgzf_row(head_, h, 0, 0);
+			}
+			const size_t isize = (size_t)row_.isize;
+			if (s.len + (size_t)hdr_.block > room || (open_chunk && in_chunk + isize > chunk_)) { // the chunk ends in front of this block
+				if (open_chunk) { ++s.chunks; open_chunk = false; in_chunk = 0; }
+				if ((size_t)s.chunks >= per_ || s.len + (size_t)hdr_.block > room) break;
+			}
+			memcpy(s.buf + s.len, head_, (size_t)hdr_.block);
+			InfRow r = row_;
+			r.coff = (int64_t)s.len + hdr_.payload; r.ooff = (int64_t)s.text;
+			rows.push_back(r);
+			s.len += (size_t)hdr_.block; s.text += isize; in_chunk += isize; open_chunk = true;
+			have_ = false;
+		}
+		if (open_chunk) ++s.chunks;
+		s.rows = rows.data(); s.n_rows = rows.size();
+	}
+private:
+	FILE *f_ = nullptr;
+	size_t chunk_ = 0, per_ = 1;
+	std::vector<InfRow> rows_[2];
+	uint8_t head_[65536 + 12]; // the block that is read ahead
+	BgzfHeader hdr_; InfRow row_; size_t head_n_ = 0; bool have_ = false;
 };
 
 class Feeder : public FeederBase {

@@ -40,11 +40,12 @@ _COUNTERS = dict(pairs=0, records=0, batches=0, feeder_s=0.0, device_s=0.0, fetc
 def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int = 250_000, bam_threads: int = 8, rec_threads: int = 8, level: int = 1,
         penalty: float = -4, lib_path: str = api.LIB_PATH, warm_passes: int = 0, layout: str = "workers", chunk: int = 40_000_000,
         read_groups: str = "", sample_id: str = "", feeder: str = "host", workers: int = 3, chunk_bytes: int = 0,
-        sink: str = "host", records: str = "host"):
+        sink: str = "host", records: str = "host", inflate: str = "host"):
     """fastq_pairs: [(r1, r2), ...] barcode-sorted files (plain or gzip).  -> stats dict (pairs, records, batches, seconds, pairs/s, bam_bytes,
     workers, files, per-stage seconds summed over workers; bam_s: the writes and the closing of the writers).  One loop with four axes (the module docstring has them):
     feeder="host" (default): one host feeder and one worker per file pair.  feeder="device": ONE file pair, parsed on the GPU by one feeder
     thread (arx_feeder_open_device) that hands super-batches to `workers` worker threads; stats["feeder"] are the feeder's own counts.
+    inflate="device" (feeder="device" only): BGZF files are inflated by a HIP kernel instead of zlib on the reader threads (api.Feeder).
     layout="workers" (default): out_prefix.k.bam per worker.  layout="reference": out_prefix is the output directory of the reference's layout
     (chunk = -p/--partitions, read_groups / sample_id as the reference's flags).
     records="host" (default): the records are built on host threads from the fetched result slabs.  records="device" (layout="workers" only):
@@ -70,6 +71,10 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
         raise ValueError("records='device_full' builds the reference's record set and its buckets: it needs layout='reference'")
     if feeder not in ("host", "device"):
         raise ValueError(f"unknown feeder {feeder!r}")
+    if inflate not in ("host", "device"):
+        raise ValueError(f"unknown inflate {inflate!r}")
+    if inflate == "device" and feeder != "device":
+        raise ValueError("inflate='device' is the device feeder's: it needs feeder='device' (the host feeder inflates with zlib)")
     if layout not in ("workers", "reference"):
         raise ValueError(f"unknown layout {layout!r}")
     if warm_passes and feeder == "device":
@@ -106,7 +111,7 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
         take = producer = fd = None
         try:
             if feeder == "device":
-                fd = api.Feeder(*fastq_pairs[0], device=ref, chunk_bytes=chunk_bytes, depth=n_workers + 2)
+                fd = api.Feeder(*fastq_pairs[0], device=ref, chunk_bytes=chunk_bytes, depth=n_workers + 2, inflate=inflate)
                 take, producer = _device_source(ref, fd, pairs_per_batch, n_workers, errors, stats, lock)
 
             def work(k):

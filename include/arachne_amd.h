@@ -220,11 +220,24 @@ void arx_feeder_close(arx_feeder *f);
  * thread's seconds per stage and its kernels' times (HIP events) on stderr. */
 int arx_feeder_open_device(arx_ctx *ctx, const char *r1_path, const char *r2_path, int64_t chunk_bytes, int32_t depth, arx_feeder **out, char *msg,
                            int32_t msg_cap);
+/* arx_feeder_open_device with flags.  ARX_FEEDER_INFLATE_DEVICE: a file that is BGZF -- its first gzip member has an extra subfield BC of
+ * length 2, the test htslib makes; what `samtools fastq -c` and bgzip write -- is read as it is and its blocks are inflated by a HIP kernel
+ * (csrc/dev_inflate.h), one wavefront per block, straight into the text the parse kernels read: its reader thread only walks block headers,
+ * and the upload is the compressed bytes.  R1 and R2 are looked at separately; a file that is anything else (plain text, ordinary gzip)
+ * goes through zlib on its reader thread as without the flag.  chunk_bytes then counts inflated bytes of whole blocks: a chunk is the longest
+ * run of blocks that inflate to at most chunk_bytes, at least one block.  A block that does not inflate (damaged stream, wrong CRC-32 or
+ * ISIZE, a header that is not BGZF, a BSIZE that runs past the end of the file) ends the input in front of it like a read error of zlib
+ * does: the sets that are complete are delivered, then arx_feeder_next returns < 0.  A missing EOF block is no error.  The super-batches
+ * are byte for byte those of the plain text.  flags = 0 is arx_feeder_open_device exactly; unknown bits: ARX_E_ARG. */
+#define ARX_FEEDER_INFLATE_DEVICE 1
+int arx_feeder_open_device_ex(arx_ctx *ctx, const char *r1_path, const char *r2_path, int64_t chunk_bytes, int32_t depth, int32_t flags, arx_feeder **out,
+                              char *msg, int32_t msg_cap);
 /* the reads of the super-batch the last arx_feeder_next delivered, in device memory, for arx_batch_reset_device (same validity as its host
  * arrays; the feeder's stream is done with them).  ARX_E_ARG for a host feeder or before the first super-batch. */
 int arx_feeder_device_reads(arx_feeder *f, const uint8_t **d_bases, const int32_t **d_lens, int64_t *n_bases);
-/* stats[8] of a device feeder since open: chunks read (both files), bytes uploaded, records parsed, lines skipped, barcode runs, chunks that
- * took a host fallback (always 0: there is none), reserved x2.  ARX_E_ARG for a host feeder. */
+/* stats[8] of a device feeder since open: chunks read (both files), bytes of text that entered the parse (the same for the plain, gzip and
+ * BGZF form of a text), records parsed, lines skipped, barcode runs, chunks that took a host fallback (always 0: there is none), BGZF blocks
+ * inflated on the device, compressed bytes uploaded for them (both 0 without ARX_FEEDER_INFLATE_DEVICE).  ARX_E_ARG for a host feeder. */
 int arx_feeder_stats(arx_feeder *f, int64_t *stats);
 
 /* ---- behind the path: the BAM sink.  The reference builds one biogo sam.Record per alignment on a single goroutine and
@@ -407,6 +420,19 @@ int arx_selftest_wave_sort(int32_t device, int32_t n_cases, int64_t seed, int64_
  * in order, without the EOF block (cap: bytes of out; n + 31 * blocks always suffice; ARX_E_ARG if it is too small).  stats[4] (may be
  * NULL): blocks, and how many of them went out stored, with the fixed code, with a dynamic code.  n = 0: no block, *out_len = 0. */
 int arx_selftest_bgzf(int32_t device, const uint8_t *src, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, int64_t *stats);
+
+/* self-test of the device inflate's kernel on arbitrary BGZF blocks, no index needed (tests/test_inflate_gpu.py): src[0..n) is a chain of
+ * whole BGZF blocks; its headers are walked on the host with the function the device feeder's reader thread uses, every block goes through
+ * the kernel of arx_feeder_open_device_ex (csrc/dev_inflate.h, hip_inflate.h).  out receives the inflated bytes of all blocks in order, a
+ * block's at the sum of ISIZE in front of it (cap: bytes of out; that sum must fit, else ARX_E_ARG); a block that is not ARX_INFLATE_OK
+ * leaves its bytes of out as they were.  status[b] (status_cap entries; more blocks: ARX_E_ARG) is block b's status, one of ARX_INFLATE_*;
+ * *out_len counts the bytes up to the first bad block.  Returns ARX_OK when every block is ARX_INFLATE_OK, ARX_E_IO when one is not, and
+ * ARX_E_ARG for a chain whose headers do not tile src (no gzip magic, no BC subfield, a BSIZE that runs past n).  stats[4] (may be NULL):
+ * blocks, compressed bytes (n), inflated bytes (the sum of ISIZE), DEFLATE blocks read.  n = 0: no block, *out_len = 0. */
+enum { ARX_INFLATE_OK = 0, ARX_INFLATE_BAD_HEADER, ARX_INFLATE_BAD_BTYPE, ARX_INFLATE_BAD_STORED_LEN, ARX_INFLATE_BAD_CODE_LENGTHS, ARX_INFLATE_BAD_SYMBOL,
+       ARX_INFLATE_BAD_DISTANCE, ARX_INFLATE_TRUNCATED, ARX_INFLATE_SIZE_MISMATCH, ARX_INFLATE_CRC_MISMATCH };
+int arx_selftest_inflate(int32_t device, const uint8_t *src, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, int32_t *status, int32_t status_cap,
+                         int64_t *stats);
 
 /* self-test of the decimal text the records phase writes on the device (csrc/dev_records_full.h), one input per lane: kind 0: "%d" of a[i]
  * (b is not read); kind 1: "%.6f" of (double)a[i] / (double)b[i], b[i] > 0 (else ARX_E_ARG).  out: n rows of 32 bytes, len[n]: the bytes
