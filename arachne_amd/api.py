@@ -83,6 +83,7 @@ def _load(path):
     lib.arx_batch_free.argtypes = [vp, vp]
     lib.arx_batch_debug_intv.argtypes = [vp, vp, vp, vp]
     lib.arx_batch_debug_seed_census.argtypes = [vp, vp, i32, vp]
+    lib.arx_batch_debug_heavy_census.argtypes = [vp, vp, i32, vp]
     lib.arx_batch_debug_chains.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.arx_batch_debug_core.argtypes = [vp, vp, vp, vp]
     lib.arx_batch_rfa.argtypes = [vp, vp, i32, vp, vp, C.c_double, vp, vp, vp]
@@ -441,6 +442,14 @@ class Batch:
         c = np.zeros(8, dtype=np.int64)
         self.ref._check(self.ref.lib.arx_batch_debug_seed_census(self.ref.h, self.h, -1 if enable is None else int(bool(enable)), c.ctypes.data))
         return dict(zip(self.SEED_CENSUS_FIELDS, c.tolist()))
+
+    HEAVY_CENSUS_FIELDS = ["chain_stages", "chain_short", "chain_long", "dedup", "rescue", "rescue_170", "rescue_340", "rescue_680"]
+
+    def heavy_census(self, enable=None):
+        """arx_batch_debug_heavy_census: the sums so far as a dict; enable = True / False then switches the census on / off and clears them."""
+        c = np.zeros(8, dtype=np.int64)
+        self.ref._check(self.ref.lib.arx_batch_debug_heavy_census(self.ref.h, self.h, -1 if enable is None else int(bool(enable)), c.ctypes.data))
+        return dict(zip(self.HEAVY_CENSUS_FIELDS, c.tolist()))
 
     def debug_chains(self):
         T = self.counts()["n_occ"]

@@ -35,6 +35,16 @@ template <class RT> struct SeedCensus<RT, std::void_t<decltype(std::declval<RT &
 	static void set(RT &rt, bool on) { rt.seed_census_on = on; for (int i = 0; i < 8; ++i) rt.seed_census[i] = 0; }
 };
 
+// arx_batch_debug_heavy_census: likewise (HipRT: heavy_census_on, heavy_census[8]; the double runs the serial code for every listed item)
+template <class RT, class = void> struct HeavyCensus {
+	static void read(const RT &, int64_t *c8) { for (int i = 0; i < 8; ++i) c8[i] = 0; }
+	static void set(RT &, bool) {}
+};
+template <class RT> struct HeavyCensus<RT, std::void_t<decltype(std::declval<RT &>().heavy_census_on)>> {
+	static void read(const RT &rt, int64_t *c8) { for (int i = 0; i < 8; ++i) c8[i] = rt.heavy_census[i]; }
+	static void set(RT &rt, bool on) { rt.heavy_census_on = on; for (int i = 0; i < 8; ++i) rt.heavy_census[i] = 0; }
+};
+
 // SA[i * d] for every i: the suffix-array sample the locate kernel walks to.  The files sample every 32nd row (bwt.c:62,
 // bwtindex.c:309); bwt_sa's LF walk from a row to the next sampled one (bwt.c:86-96) is what locating a seed costs, 15.5 steps on
 // average.  A sample every `d`-th row, computed once per arx_open on the device with that same walk, gives the same values in
@@ -623,6 +633,14 @@ template <class RT> struct Batch {
 		if (!b) { c->set_error("arx_batch_debug_seed_census without a batch"); return ARX_E_ARG; }                                  \
 		if (census8) arx::SeedCensus<RT>::read(b->rt, census8);                                                                     \
 		if (enable >= 0) arx::SeedCensus<RT>::set(b->rt, enable != 0);                                                              \
+		return ARX_OK;                                                                                                              \
+	}                                                                                                                               \
+	int arx_batch_debug_heavy_census(arx_ctx *h, arx_batch *bh, int32_t enable, int64_t *census8)                                   \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
+		if (!b) { c->set_error("arx_batch_debug_heavy_census without a batch"); return ARX_E_ARG; }                                 \
+		if (census8) arx::HeavyCensus<RT>::read(b->rt, census8);                                                                    \
+		if (enable >= 0) arx::HeavyCensus<RT>::set(b->rt, enable != 0);                                                             \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_batch_debug_chains(arx_ctx *h, arx_batch *bh, int32_t *occ_off, int32_t *n_chain, arx_chain *chains, arx_seed *seeds)   \

@@ -140,7 +140,7 @@ struct ChainLds { // carved out of the dynamic LDS block for a read with n occur
 		iscr = (int32_t *)p;
 	}
 };
-constexpr int CHAIN_LDS_SMALL = 256; // two launches: reads with up to 256 occurrences (40 KB of LDS, four workgroups per CU), and the rest (one per CU)
+// (pipeline.h: CHAIN_LDS_SMALL = 256) two launches: reads with up to 256 occurrences (40 KB of LDS, four workgroups per CU), and the rest (one per CU)
 static __global__ void __launch_bounds__(64) k_chain_heavy(KChain f, int n_lo, int n_hi, int32_t *cursor, int wave)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_chain[];

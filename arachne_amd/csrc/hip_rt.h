@@ -377,6 +377,45 @@ struct HipRT {
 			for (uint8_t f : fl) { seed_census[5] += f == 1; seed_census[6] += f == 2; }
 		}
 	}
+	// opt-in census of the heavy-item lists (arx_batch_debug_heavy_census; tests assert from it which items the wavefront-per-item kernels of
+	// arx_cold.hip took).  The lists and their lengths are in device memory after the launches that fill them anyway, so switched on it copies
+	// them home and counts; switched off (the default) it is one untaken branch on the host per stage: no round trip, no kernel argument, no
+	// counter inside a kernel.
+	// [0] chaining stages, [1] reads listed for k_chain_heavy with up to CHAIN_LDS_SMALL occurrences (its short launch), [2] with more (its long
+	// launch), [3] reads listed for k_dedup_heavy, [4] pairs listed for k_rescue_heavy, [5..7] those pairs by the LDS class of their two
+	// capacities together (up to 170 / 340 / RESCUE_LDS_REGS records) when the replay is launched per class, otherwise all in [7]
+	bool heavy_census_on = false;
+	int64_t heavy_census[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	void heavy_census_chain(int n_reads, const int32_t *list, const int32_t *n_heavy, const int32_t *occ_off, int split)
+	{
+		if (!heavy_census_on) return;
+		++heavy_census[0];
+		int32_t nh = 0;
+		if (!list) return;
+		d2h(&nh, n_heavy, 4);
+		if (nh <= 0) return;
+		std::vector<int32_t> l((size_t)nh), off((size_t)n_reads + 1);
+		d2h(l.data(), list, 4 * (size_t)nh);
+		d2h(off.data(), occ_off, 4 * ((size_t)n_reads + 1));
+		for (int32_t r : l) ++heavy_census[off[(size_t)r + 1] - off[(size_t)r] <= split ? 1 : 2];
+	}
+	void heavy_census_dedup(const int32_t *n_heavy)
+	{
+		if (!heavy_census_on || !n_heavy) return;
+		int32_t nh = 0;
+		d2h(&nh, n_heavy, 4);
+		heavy_census[3] += nh;
+	}
+	void heavy_census_rescue(int n_reads, int n_heavy, const int32_t *list, const int32_t *preg_off)
+	{
+		if (!heavy_census_on || n_heavy <= 0) return;
+		heavy_census[4] += n_heavy;
+		if (!sw.rescue_lds_classes) { heavy_census[7] += n_heavy; return; }
+		std::vector<int32_t> l((size_t)n_heavy), off((size_t)n_reads + 1);
+		d2h(l.data(), list, 4 * (size_t)n_heavy);
+		d2h(off.data(), preg_off, 4 * ((size_t)n_reads + 1));
+		for (int32_t p : l) { const int c = off[2 * (size_t)p + 2] - off[2 * (size_t)p]; ++heavy_census[c <= 170 ? 5 : c <= 340 ? 6 : 7]; }
+	}
 	template <class K> void launch_seed_kernel(const char *nm, K kern, int n, const SeedKArgs &A, int32_t *counter, int bpc_, int chunk_ = 0, int batch_ = 0, int grant_ = 64)
 	{
 		if (chunk_ <= 0) chunk_ = sw.seed_chunk;

@@ -224,6 +224,7 @@ struct KOccRid {
 // round trips -- while the other 99.9 % finish in a quarter of it.  KChain hands such a read to k_chain_heavy (arx_cold.hip): one
 // wavefront per read, the read's working set in LDS.
 constexpr int CHAIN_HEAVY_MIN = 64, CHAIN_LDS_OCC = 832; // 832 occurrences x 154 B of working set = 128 KB of a CU's 160 KB LDS
+constexpr int CHAIN_LDS_SMALL = 256; // k_chain_heavy's two launches: reads with up to 256 occurrences, and the rest (arx_cold.hip)
 // Opt-in (ARX_CHAIN_GROUP=1, where the runtime has it): the reads below that threshold go to k_chain_g16 (arx_cold.hip, dev_chain_group.h),
 // one read per 16-lane group with its working set in LDS, in two classes -- 1-16 occurrences and 17 up to the threshold, at most
 // CHAIN_G16_MAX (18 KB of LDS per read).  Not the default: measured, it is no faster (profiles/chain_group/).
@@ -266,6 +267,10 @@ struct KChain {
 // HipRT has the group kernel (chain_group_ok / run_chain_group); the host test double chains every read on the serial path
 template <class R, class = void> struct HasChainGroup { static constexpr bool value = false; };
 template <class R> struct HasChainGroup<R, decltype((void)std::declval<const R &>().chain_group_ok())> { static constexpr bool value = true; };
+
+// HipRT keeps the opt-in census of the heavy lists (heavy_census_*; arx_batch_debug_heavy_census); the host test double has none
+template <class R, class = void> struct HasHeavyCensus { static constexpr bool value = false; };
+template <class R> struct HasHeavyCensus<R, decltype((void)std::declval<R &>().heavy_census_on)> { static constexpr bool value = true; };
 
 struct KChainMid { // the listed reads of KChain, one thread each; the list's length stays on the device
 	KChain f;
@@ -729,6 +734,7 @@ public:
 		if (k.mid_list && !k.grp_max) { KChainMid km{k}; rt.launch_wide("chain", mid_cap, km); } // (the list's length is not on the host: threads beyond it return at once)
 		if constexpr (HasChainGroup<RT>::value) { if (k.grp_max) rt.run_chain_group("chain", R, k); }
 		if (k.heavy_list) rt.run_chain_heavy("chain_heavy", R, k); // the list's length stays on the device: no host round trip
+		if constexpr (HasHeavyCensus<RT>::value) rt.heavy_census_chain(R, k.heavy_list, k.n_heavy, w.occ_off, CHAIN_LDS_SMALL);
 	}
 
 	// ---- stage 4: extension rounds, then de-duplication -> core regions of every read
@@ -777,6 +783,7 @@ public:
 		if (rt.dedup_heavy_ok()) { kd.heavy_list = rt.template alloc<int32_t>(R + 4); kd.n_heavy = kd.heavy_list + R; rt.memset0(kd.n_heavy, 16); }
 		rt.launch_cold("dedup", R, kd);
 		if (kd.heavy_list) rt.run_dedup_heavy("dedup_heavy", R, kd);
+		if constexpr (HasHeavyCensus<RT>::value) rt.heavy_census_dedup(kd.heavy_list ? kd.n_heavy : nullptr);
 	}
 
 	// ---- stage 5: mate rescue rounds
@@ -801,6 +808,7 @@ public:
 		rt.launch_wide("pair_init", NP, ki);
 		int n_heavy = 0;
 		if (hv) rt.d2h(&n_heavy, n_hv, 4);
+		if constexpr (HasHeavyCensus<RT>::value) rt.heavy_census_rescue(R, n_heavy, hv_list, w.preg_off);
 		for (int round = 0;; ++round) {
 			rt.memset0(w.counter, 4);
 			KRescueStep ks{ix, b.lens, w.preg_off, w.pregs, ptmp, pidx, w.n_regs, rst, sres, stask, w.counter, n_slots, sw.rescue_no_ahead ? 1 : 0, (int32_t)(2 * w.P), hv};

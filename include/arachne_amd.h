@@ -406,6 +406,13 @@ int arx_batch_debug_intv(arx_ctx *ctx, arx_batch *b, int32_t *n_intv, uint64_t *
  * whole-wavefront kernel was given.  Off (the default) nothing is counted and nothing is copied; on, each backward launch costs one more
  * device-to-host copy of its bookkeeping.  The host test double keeps no census and reports zeros. */
 int arx_batch_debug_seed_census(arx_ctx *ctx, arx_batch *b, int32_t enable, int64_t *census8);
+/* Census of the heavy-item lists (tests: which reads and pairs the wavefront-per-item kernels took); enable and census8 as above.
+ * [0] chaining stages run, [1] reads listed for the chaining kernel's launch of up to 256 seed occurrences, [2] for its launch above that,
+ * [3] reads listed for the de-duplication kernel, [4] pairs listed for the rescue replay, [5..7] those pairs by the LDS class of their two
+ * list capacities together (up to 170 / 340 / 680 records) when the replay is launched per class (ARX_RESCUE_LDS_CLASSES=1), otherwise all
+ * in [7].  Off (the default) nothing is counted and nothing is copied; on, each of the three stages costs device-to-host copies of its
+ * list.  The host test double keeps no census and reports zeros. */
+int arx_batch_debug_heavy_census(arx_ctx *ctx, arx_batch *b, int32_t enable, int64_t *census8);
 int arx_batch_debug_chains(arx_ctx *ctx, arx_batch *b, int32_t *occ_off /* n_reads+1 */, int32_t *n_chain, arx_chain *chains, arx_seed *seeds /* counts[3] each */);
 int arx_batch_debug_core(arx_ctx *ctx, arx_batch *b, int32_t *n_core, arx_reg *regs /* counts[3] */);
 

@@ -801,6 +801,12 @@ static int chain_weight(const chain_t *c)
 
 typedef struct { int n; chain_t *a; } chainvec_t;
 
+/* ora_list_shapes: counts taken inside the functions below while one pair runs (null otherwise; nothing they compute depends on it).
+ * rd: the row of the read whose mem_align1_core is running, ins: one row per insertion of mem_matesw. */
+typedef struct { int64_t *rd0, *rd, *ins; int n_ins, cap_ins, list, anchor; } lshape_t;
+static __thread lshape_t *g_ls;
+#define LS_RD (g_ls && g_ls->rd)
+
 /* ref: bwamem.c:251-315 (mem_chain) */
 static chainvec_t do_chain(const index_t *ix, int len, const uint8_t *seq, ora_counters_t *cnt)
 {
@@ -808,7 +814,7 @@ static chainvec_t do_chain(const index_t *ix, int len, const uint8_t *seq, ora_c
 	bivec_t mem = {0,0,0};
 	btree_t bt;
 	chain_t *ch = 0;
-	int n_ch = 0, m_ch = 0, i, b, e, l_rep;
+	int n_ch = 0, m_ch = 0, i, b, e, l_rep, n_occ = 0;
 	if (len < OPT_MIN_SEED_LEN) return out;
 	memset(&bt, 0, sizeof bt);
 	bt.root = bt_new(&bt);
@@ -828,6 +834,7 @@ static chainvec_t do_chain(const index_t *ix, int len, const uint8_t *seq, ora_c
 		for (k = count = 0; k < (int64_t)p->s && count < OPT_MAX_OCC; k += step, ++count) {
 			seed_t s;
 			int rid, to_add = 0;
+			++n_occ;
 			s.rbeg = (int64_t)sa_lookup(ix, p->k + k, cnt);
 			s.qbeg = (int32_t)(p->info >> 32);
 			s.score = s.len = slen;
@@ -863,6 +870,7 @@ static chainvec_t do_chain(const index_t *ix, int len, const uint8_t *seq, ora_c
 		out.n = n;
 		free(order);
 	}
+	if (LS_RD) { g_ls->rd[0] = n_occ; g_ls->rd[1] = n_ch; }
 	free(ch); free(bt.nodes); free(mem.a);
 	return out;
 }
@@ -890,6 +898,11 @@ static int chain_flt(int n_chn, chain_t *a)
 	for (i = 0; i < n_chn; ++i) tmp[i] = a[idx[i]];
 	memcpy(a, tmp, n_chn * sizeof(chain_t));
 	free(idx); free(tmp);
+	if (LS_RD) { /* chains the filter sorts; the longest run of equal weights among them */
+		int run = 1, best = 1;
+		for (i = 1; i < n_chn; ++i) { run = a[i].w == a[i - 1].w? run + 1 : 1; if (run > best) best = run; }
+		g_ls->rd[2] = n_chn; g_ls->rd[8] = best; g_ls->rd[4] = -1;
+	}
 	kept_idx = (int*)malloc(n_chn * sizeof(int));
 	a[0].kept = 3;
 	kept_idx[n_kept++] = 0;
@@ -906,7 +919,16 @@ static int chain_flt(int n_chn, chain_t *a)
 				if (e_min - b_max >= min_l * OPT_MASK_LEVEL && min_l < OPT_MAX_CHAIN_GAP) {
 					large_ovlp = 1;
 					if (a[j].first < 0) a[j].first = i;
-					if (a[i].w < a[j].w * OPT_DROP_RATIO && a[j].w - a[i].w >= OPT_MIN_SEED_LEN << 1) break;
+					if (a[i].w < a[j].w * OPT_DROP_RATIO && a[j].w - a[i].w >= OPT_MIN_SEED_LEN << 1) {
+						if (LS_RD) { /* chain i is dropped by the kept chain of rank k, with n_kept chains kept so far */
+							int64_t *rd = g_ls->rd;
+							if (k > rd[4]) rd[4] = k;
+							if (k >= 62 && k <= 64) ++rd[5 + k - 62];
+							if (n_kept > rd[16]) rd[16] = n_kept;
+							++rd[17];
+						}
+						break;
+					}
 				}
 			}
 		}
@@ -929,6 +951,7 @@ static int chain_flt(int n_chn, chain_t *a)
 		if (a[i].kept == 0) free(a[i].seeds);
 		else a[k++] = a[i];
 	}
+	if (LS_RD) g_ls->rd[3] = k;
 	return k;
 }
 
@@ -1620,11 +1643,13 @@ static int patch_reg(const index_t *ix, uint8_t *query, const reg_t *a, const re
 	} else if (w > OPT_W << 2 || r >= 0.05f * 2) return 0;
 	w += a->w + b->w;
 	w = w < OPT_W << 2? w : OPT_W << 2;
+	if (LS_RD) ++g_ls->rd[14];
 	score = 0; /* NB: the reference leaves `score` uninitialised when bwa_gen_cigar2 rejects the region */
 	gen_cigar2(ix, w, b->qe - a->qb, query + a->qb, a->rb, b->re, &score, 0, 0, cnt);
 	q_s = (int)((double)(b->qe - a->qb) / ((b->qe - b->qb) + (a->qe - a->qb)) * (b->score + a->score) + .499);
 	r_s = (int)((double)(b->re - a->rb) / ((b->re - b->rb) + (a->re - a->rb)) * (b->score + a->score) + .499);
 	if ((double)score / (q_s > r_s? q_s : r_s) < 0.90f) return 0;
+	if (LS_RD && score > 0) ++g_ls->rd[15];
 	*w_ = w;
 	return score;
 }
@@ -1650,6 +1675,8 @@ static void permute_regs(int n, reg_t *a, lt_fn lt)
 static int sort_dedup_patch(const index_t *ix, uint8_t *query, int n, reg_t *a, ora_counters_t *cnt)
 {
 	int m, i, j;
+	int64_t *rd = LS_RD && ix? g_ls->rd : 0; /* the read's own pass (mem_align1_core), not the ones mem_matesw repeats */
+	if (rd) rd[9] = rd[10] = n;
 	if (n <= 1) return n;
 	permute_regs(n, a, reg_lt_re);
 	for (i = 0; i < n; ++i) a[i].n_comp = 1;
@@ -1666,6 +1693,12 @@ static int sort_dedup_patch(const index_t *ix, uint8_t *query, int n, reg_t *a, 
 			mr = q->re - q->rb < p->re - p->rb? q->re - q->rb : p->re - p->rb;
 			mq = q->qe - q->qb < p->qe - p->qb? q->qe - q->qb : p->qe - p->qb;
 			if (orr > OPT_MASK_LEVEL_REDUN * mr && oq > OPT_MASK_LEVEL_REDUN * mq) {
+				if (rd) { /* the entry that goes (index x) and the one it is redundant with (the stopper) */
+					const int x = p->score < q->score? i : j;
+					++rd[11];
+					if (x >= 64 && i >> 6 != j >> 6) ++rd[12];
+					if (x == i) { ++rd[20]; if (i >> 6 != j >> 6) ++rd[21]; }
+				}
 				if (p->score < q->score) { p->qe = p->qb; break; }
 				else q->qe = q->qb;
 			} else if (q->rb < p->rb && (score = patch_reg(ix, query, q, p, &w, cnt)) > 0) {
@@ -1685,9 +1718,13 @@ static int sort_dedup_patch(const index_t *ix, uint8_t *query, int n, reg_t *a, 
 	n = m;
 	permute_regs(n, a, reg_lt_score);
 	for (i = 1; i < n; ++i)
-		if (a[i].score == a[i - 1].score && a[i].rb == a[i - 1].rb && a[i].qb == a[i - 1].qb) a[i].qe = a[i].qb;
+		if (a[i].score == a[i - 1].score && a[i].rb == a[i - 1].rb && a[i].qb == a[i - 1].qb) {
+			a[i].qe = a[i].qb;
+			if (rd) { ++rd[18]; if (!(i & 63)) ++rd[13]; }
+		}
 	for (i = 1, m = 1; i < n; ++i)
 		if (a[i].qe > a[i].qb) { if (m != i) a[m++] = a[i]; else ++m; }
+	if (rd) rd[10] = m;
 	return m;
 }
 
@@ -1754,7 +1791,7 @@ static inline int infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist
 static int matesw(const index_t *ix, const reg_t *a, int l_ms, const uint8_t *ms, regvec_t *ma, ora_counters_t *cnt)
 {
 	int64_t l_pac = ix->l_pac;
-	int i, r, skip[4], n = 0, rid = -1;
+	int i, r, skip[4], n = 0, rid = -1, ins_row = -1;
 	for (r = 0; r < 4; ++r) skip[r] = PES_FAILED[r]? 1 : 0;
 	for (i = 0; i < ma->n; ++i) {
 		int64_t dist;
@@ -1803,12 +1840,39 @@ static int matesw(const index_t *ix, const reg_t *a, int l_ms, const uint8_t *ms
 				rv_pushp(ma);
 				for (i = 0; i < ma->n - 1; ++i) if (ma->a[i].score < b.score) break;
 				tmp = i;
+				if (g_ls) {
+					int tie = 0, top_j = -1, top_far = 0;
+					int64_t top_re = 0;
+					for (i = 0; i < ma->n - 1; ++i) {
+						const reg_t *x = &ma->a[i];
+						if (x->re == b.re || (x->score == b.score && x->rb == b.rb && x->qb == b.qb)) tie = 1;
+						/* entries that end before the region, are redundant with it and score higher (they stop its scan): do two with the
+						 * same, greatest end lie in different 64-entry steps of the list? */
+						if (x->rid == b.rid && x->re < b.re && b.rb < x->re + OPT_MAX_CHAIN_GAP && b.score < x->score) {
+							int64_t orr = x->re - b.rb, oq = x->qb < b.qb? x->qe - b.qb : b.qe - x->qb;
+							int64_t mr = x->re - x->rb < b.re - b.rb? x->re - x->rb : b.re - b.rb, mq = x->qe - x->qb < b.qe - b.qb? x->qe - x->qb : b.qe - b.qb;
+							if (orr > OPT_MASK_LEVEL_REDUN * mr && oq > OPT_MASK_LEVEL_REDUN * mq) {
+								if (top_j < 0 || x->re > top_re) { top_j = i; top_re = x->re; top_far = 0; }
+								else if (x->re == top_re && i >> 6 != top_j >> 6) top_far = 1;
+							}
+						}
+					}
+					if (g_ls->n_ins < g_ls->cap_ins) {
+						int64_t *w = g_ls->ins + (size_t)g_ls->n_ins * ORA_LINS_W;
+						w[0] = g_ls->list; w[1] = ma->n - 1; w[2] = tmp; w[3] = tie; w[4] = -1; w[5] = g_ls->anchor; w[6] = top_far; w[7] = 0;
+					}
+					++g_ls->n_ins; ins_row = g_ls->n_ins - 1;
+				}
 				for (i = ma->n - 1; i > tmp; --i) ma->a[i] = ma->a[i - 1];
 				ma->a[i] = b;
 			}
 			++n;
 		}
-		if (n) ma->n = sort_dedup_patch(0, 0, ma->n, ma->a, cnt);
+		if (n) {
+			const int before = ma->n;
+			ma->n = sort_dedup_patch(0, 0, ma->n, ma->a, cnt);
+			if (g_ls && ins_row >= 0 && ins_row < g_ls->cap_ins) g_ls->ins[(size_t)ins_row * ORA_LINS_W + 4] = before - ma->n;
+		}
 		free(seq); free(ref);
 	}
 	return n;
@@ -1917,7 +1981,9 @@ static void do_pair(const index_t *ix, int l1, const uint8_t *s1, int l2, const 
 	memcpy(q[0], s1, l1); memcpy(q[1], s2, l2);
 	memset(res, 0, sizeof(*res));
 	for (e = 0; e < 2; ++e) {
+		if (g_ls) g_ls->rd = g_ls->rd0 + e * ORA_LSHAPE_W;
 		if (l[e] > 0) res->r[e] = align1_core(ix, l[e], q[e], cnt);
+		if (g_ls) g_ls->rd = 0;
 		for (i = 0; i < res->r[e].n; ++i) if (res->r[e].a[i].score > best[e]) best[e] = res->r[e].a[i].score;
 	}
 	/* read1 is rescued from read2's hits; then read2 from the POST-rescue read1 list, still against the PRE-rescue best1 */
@@ -1925,13 +1991,33 @@ static void do_pair(const index_t *ix, int l1, const uint8_t *s1, int l2, const 
 		int o = 1 - e, n_snap = res->r[e].n;
 		const reg_t *snap = res->r[e].a;
 		for (i = 0, num = 0; i < n_snap && num < 50 && l[o] > 0; ++i)
-			if (snap[i].score >= best[e] - score_delta) { ++num; matesw(ix, &snap[i], l[o], q[o], &res->r[o], cnt); }
+			if (snap[i].score >= best[e] - score_delta) { ++num; if (g_ls) { g_ls->list = o; g_ls->anchor = i; } matesw(ix, &snap[i], l[o], q[o], &res->r[o], cnt); }
 	}
 	for (e = 0; e < 2; ++e) {
 		res->aln[e] = (aln_t*)calloc(res->r[e].n + 1, sizeof(aln_t));
 		for (i = 0; i < res->r[e].n; ++i) res->aln[e][i] = reg2aln(ix, l[e], q[e], &res->r[e].a[i], cnt);
 	}
 	free(q[0]); free(q[1]);
+}
+
+int ora_list_shapes(ora_ctx_t *c, int l1, const uint8_t *s1, int l2, const uint8_t *s2, int score_delta, int64_t *reads, int64_t *ins, int cap_ins)
+{
+	pair_res_t res;
+	lshape_t ls;
+	int e, i;
+	memset(&ls, 0, sizeof ls);
+	memset(reads, 0, 2 * ORA_LSHAPE_W * sizeof(int64_t));
+	reads[4] = reads[ORA_LSHAPE_W + 4] = -1;
+	ls.rd0 = reads; ls.ins = ins; ls.cap_ins = cap_ins;
+	g_ls = &ls;
+	do_pair(&c->ix, l1, s1, l2, s2, score_delta, &res, 0);
+	g_ls = 0;
+	for (e = 0; e < 2; ++e) {
+		reads[e * ORA_LSHAPE_W + 19] = res.r[e].n;
+		for (i = 0; i < res.r[e].n; ++i) free(res.aln[e][i].cigar);
+		free(res.r[e].a); free(res.aln[e]);
+	}
+	return ls.n_ins;
 }
 
 static void add_counters(ora_counters_t *d, const ora_counters_t *s)

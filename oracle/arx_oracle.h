@@ -70,6 +70,25 @@ int ora_collect_intv(ora_ctx_t *c, int len, const uint8_t *seq, uint64_t *out, i
  * kf and k3 only enter column 9.  Returns the number of rows (rows beyond cap_s are counted, not stored). */
 #define ORA_SHAPE_W 12
 int ora_seed_shapes(ora_ctx_t *c, int len, const uint8_t *seq, int kf, int k3, int64_t *shapes, int cap_s, uint64_t *intv, int cap_i, int *n_intv);
+/* The shape of a pair's list work, from one run of the pair path (counts only; nothing the path computes depends on them).  Tests assert from
+ * these that their inputs reach the lane, word and LDS-class edges of the product's wavefront-per-item list kernels.
+ * reads: two rows of ORA_LSHAPE_W numbers, read 1 then read 2:
+ *  0 seed occurrences mem_chain takes (its loop's iterations, at most max_occ per interval)   1 chains built   2 chains mem_chain_flt sorts
+ *  3 chains it keeps (after the max_chain_extend cut)   4 the highest kept rank (index into kept_idx) of a chain that dropped another, -1: no
+ *  drop   5, 6, 7 drops decided at kept rank 62, 63, 64   8 the longest run of equal weights among the sorted chains
+ *  9 regions before mem_sort_dedup_patch   10 regions after it   11 entries its redundancy loop removes   12 those of them whose index is >= 64
+ *  and whose stopper lies in another 64-entry word   13 identical (score, rb, qb) neighbours its final sort drops at an index that is a multiple
+ *  of 64   14 mem_patch_reg calls that reach their alignment   15 those that merge   16 the most chains kept at the time of a drop
+ *  17 drops   18 identical neighbours dropped   19 regions after rescue   20 of the entries in 11, those dropped as the LATER of a pair (the
+ *  earlier one scores higher and stops the scan)   21 those of them whose stopper lies in another 64-entry word.
+ * ins: one row of ORA_LINS_W numbers per region mem_matesw inserts, in call order:
+ *  0 the list (0: read 1's)   1 its length before the insertion   2 the position the region is inserted at   3 an entry of the list ties with
+ *  it (equal re, or equal score, rb and qb)   4 entries the pass that follows removes   5 index of the anchor in the mate's list   6 two
+ *  entries that end before the region, are redundant with it and score higher share the greatest end and lie in different 64-entry steps.
+ * Returns the number of insertions (rows beyond cap_ins are counted, not stored). */
+#define ORA_LSHAPE_W 24
+#define ORA_LINS_W 8
+int ora_list_shapes(ora_ctx_t *c, int l1, const uint8_t *s1, int l2, const uint8_t *s2, int score_delta, int64_t *reads, int64_t *ins, int cap_ins);
 int ora_chains(ora_ctx_t *c, int len, const uint8_t *seq, int do_flt, int64_t *chains, int cap_c, int64_t *seeds, int cap_s, int *n_seeds_out, uint32_t *frac_rep_bits);
 void ora_ksw_extend2(ora_ctx_t *c, int qlen, const uint8_t *q, int tlen, const uint8_t *t, int w, int end_bonus, int zdrop, int h0, int *out);
 void ora_ksw_align2(ora_ctx_t *c, int qlen, const uint8_t *q, int tlen, const uint8_t *t, int xtra, int *out);

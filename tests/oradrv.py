@@ -118,6 +118,21 @@ class Oracle:
         assert n <= cap and ni.value <= cap
         return sh[:n], iv[:ni.value]
 
+    LSHAPE_FIELDS = ["occ", "built", "sorted", "kept", "max_drop_rank", "drop62", "drop63", "drop64", "w_run", "regs_in", "regs_out", "redun", "redun_far",
+                     "ident_far", "patch_aln", "patch_merged", "kept_at_drop", "drops", "ident", "regs_final", "stopped", "stopped_far", "pad0", "pad1"]
+    LINS_FIELDS = ["list", "len", "pos", "tie", "removed", "anchor", "stoppers_far", "pad"]
+
+    def list_shapes(self, s1, s2, score_delta=25, cap=128):
+        """ora_list_shapes of one pair: (2 x LSHAPE_FIELDS, one row per read; rows of LINS_FIELDS, one per insertion of mem_matesw)."""
+        s1 = np.ascontiguousarray(s1, dtype=np.uint8)
+        s2 = np.ascontiguousarray(s2, dtype=np.uint8)
+        rd = np.zeros((2, len(self.LSHAPE_FIELDS)), dtype=np.int64)
+        ins = np.zeros((cap, len(self.LINS_FIELDS)), dtype=np.int64)
+        self.lib.ora_list_shapes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        n = self.lib.ora_list_shapes(self.h, len(s1), s1.ctypes.data, len(s2), s2.ctypes.data, int(score_delta), rd.ctypes.data, ins.ctypes.data, cap)
+        assert n <= cap
+        return rd, ins[:n]
+
     def chains(self, seq, do_flt, cap_c=8192, cap_s=65536):
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         ch = np.zeros((cap_c, 8), dtype=np.int64)
