@@ -53,7 +53,10 @@ def sequence_convert(seq) -> np.ndarray:
 
 
 class ArachneError(RuntimeError):
-    pass
+    code = None             # the ARX_E_* code of the entry that failed, where the caller may want to tell them apart
+
+
+ARX_OK, ARX_E_OPEN, ARX_E_ARG, ARX_E_DEVICE, ARX_E_TOO_LARGE, ARX_E_IO = 0, -1, -2, -3, -4, -5
 
 
 def _load(path):
@@ -143,6 +146,10 @@ _SELFTEST_ARGS = {
     # the device BAM sink: bound when first used, for the same reason
     "arx_bam_open_device": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
     "arx_bam_write_encoded_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64],
+    # the coordinate sort into an open writer
+    "arx_bam_open_ex": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
+    "arx_bam_sort_append": [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.c_int64, C.c_void_p, C.c_char_p, C.c_int32],
+    "arx_selftest_bam_sort": [C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 
 
@@ -239,6 +246,36 @@ def bgzf_selftest(data, device: int = 0, lib_path: str = LIB_PATH):
     if rc != 0:
         raise ArachneError("arx_selftest_bgzf: code %d" % rc)
     return out[:out_len.value].tobytes(), dict(blocks=int(st[0]), stored=int(st[1]), fixed=int(st[2]), dynamic=int(st[3]))
+
+
+SORT_MODES = {"coordinate": 0, "copy": 1}
+SORT_TIMED = 0x100
+_SORT_STATS = ("records", "inflated_bytes", "blocks", "segments", "guess_right", "repaired", "rounds", "slabs", "read_us", "inflate_us", "probe_us", "walk_us",
+               "repair_us", "keys_us", "sort_us", "gather_us", "write_us", "total_us")
+
+
+def _sort_stats(st):
+    return {k: int(st[i]) for i, k in enumerate(_SORT_STATS)}
+
+
+def selftest_bam_sort(stream, n_ref: int, seg_bytes: int = 1 << 18, mode: str = "coordinate", timed: bool = False, device: int = 0, fill: int = 0xA5,
+                      lib_path: str = LIB_PATH):
+    """The record discovery, key, sort and gather kernels on plain BAM record bytes (include/arachne_amd.h: arx_selftest_bam_sort) -> dict(rc:
+    the entry's return value (0, or ARX_E_IO = -5 for a broken chain), out: the records in coordinate order (mode="copy": as they are; left at
+    `fill` when rc is not 0), rec_off: where they start in out (n_records + 1), n_records, stats)."""
+    lib = _load(lib_path)
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    n = len(src)
+    out = np.full(n + 8, fill, dtype=np.uint8)
+    rec_off = np.full(n // 36 + 2, -1, dtype=np.int64)
+    n_rec, st = C.c_int64(-1), np.zeros(20, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_bam_sort")(device, src.ctypes.data if n else None, n, n_ref, seg_bytes, SORT_MODES[mode] | (SORT_TIMED if timed else 0),
+                                                    out.ctypes.data, rec_off.ctypes.data, C.byref(n_rec), st.ctypes.data)
+    if rc not in (ARX_OK, ARX_E_IO):
+        e = ArachneError("arx_selftest_bam_sort: code %d" % rc)
+        e.code = rc
+        raise e
+    return dict(rc=rc, out=out[:n].tobytes(), guard=out[n:].tobytes(), rec_off=rec_off, n_records=int(n_rec.value), stats=_sort_stats(st))
 
 
 INFLATE_STATUS = ("OK", "BAD_HEADER", "BAD_BTYPE", "BAD_STORED_LEN", "BAD_CODE_LENGTHS", "BAD_SYMBOL", "BAD_DISTANCE", "TRUNCATED", "SIZE_MISMATCH", "CRC_MISMATCH")
@@ -708,16 +745,28 @@ class BamWriter:
     Host code of the product library; needs no GPU.
 
     device=<Reference>: the device sink (arx_bam_open_device) -- records are still encoded on `threads` host threads, the BGZF blocks are
-    deflated and checksummed by HIP kernels on that reference's GPU; the file inflates to the same bytes, `level` does not apply."""
+    deflated and checksummed by HIP kernels on that reference's GPU; the file inflates to the same bytes, `level` does not apply.
+
+    coordinate=True: the header says SO:coordinate (arx_bam_open_ex, ARX_BAM_COORDINATE) -- for a file filled by sort_append; flags: the
+    entry's flag word as it is (0: byte for byte the file of the plain open)."""
 
     def __init__(self, path: str, contig_names, contig_lens, extra_header: str = "", threads: int = 8, level: int = -1, lib_path: str = LIB_PATH,
-                 device: "Reference | None" = None):
+                 device: "Reference | None" = None, coordinate: bool = False, flags: "int | None" = None):
         self.lib = device.lib if device is not None else _load(lib_path)
         self.h = C.c_void_p()
         n = len(contig_names)
         names = (C.c_char_p * n)(*[x.encode() for x in contig_names])
         lens = np.ascontiguousarray(contig_lens, dtype=np.int32)
         msg = C.create_string_buffer(512)
+        if coordinate or flags is not None:
+            rc = _selftest_fn(self.lib, "arx_bam_open_ex")(device.h if device is not None else None, path.encode(), n, names, lens.ctypes.data,
+                                                           extra_header.encode() if extra_header else None, threads, level, int(flags or 0) | (1 if coordinate else 0),
+                                                           C.byref(self.h), msg, 512)
+            if rc != 0:
+                e = ArachneError("arx_bam_open_ex: " + msg.value.decode())
+                e.code = rc
+                raise e
+            return
         if device is not None:
             rc = _selftest_fn(self.lib, "arx_bam_open_device")(device.h, path.encode(), n, names, lens.ctypes.data, extra_header.encode() if extra_header else None, threads,
                                                                C.byref(self.h), msg, 512)
@@ -769,6 +818,19 @@ class BamWriter:
         blocks are written -- the batch may then be reset"""
         if _selftest_fn(self.lib, "arx_bam_write_encoded_device")(self.h, C.c_void_p(ptr), int(n_bytes), int(n_records)) != 0:
             raise ArachneError("arx_bam_write_encoded_device: " + self.lib.arx_bam_error(self.h).decode())
+
+    def sort_append(self, ref: "Reference", path: str, mode: str = "coordinate", max_bytes: int = 0, timed: bool = False):
+        """arx_bam_sort_append: the records of the BAM file `path` appended on ref's GPU, ordered stably by ((uint32_t)refID, pos)
+        (mode="coordinate": the whole file in device memory at once) or as they are (mode="copy": in slabs of at most max_bytes inflated
+        bytes) -> the entry's stats as a dict.  ArachneError.code tells ARX_E_TOO_LARGE, ARX_E_ARG and ARX_E_IO apart."""
+        st, msg = np.zeros(20, dtype=np.int64), C.create_string_buffer(512)
+        rc = _selftest_fn(self.lib, "arx_bam_sort_append")(ref.h, self.h, path.encode(), SORT_MODES[mode] | (SORT_TIMED if timed else 0), int(max_bytes), st.ctypes.data,
+                                                           msg, 512)
+        if rc != 0:
+            e = ArachneError("arx_bam_sort_append: " + msg.value.decode())
+            e.code = rc
+            raise e
+        return _sort_stats(st)
 
     def close(self):
         st = np.zeros(4, dtype=np.int64)

@@ -1,12 +1,14 @@
 // arx_bgzf.hip -- the device BAM sink (include/arachne_amd.h: arx_bam_open_device, arx_bam_write_encoded_device, arx_selftest_bgzf): BamSink (bam_sink.h) with the compressor of
 // hip_bgzf.h behind its seam.  Its own unit: the kernels of dev_bgzf.h compile next to the pipeline's.  The mirror image lives here too: the
-// inflate kernel of hip_inflate.h (arx_selftest_inflate; the device feeder starts it through inflate_launch).
+// inflate kernel of hip_inflate.h (arx_selftest_inflate; the device feeder starts it through inflate_launch).  And what needs both: the coordinate
+// sort of a BAM file into an open writer (arx_bam_open_ex, arx_bam_sort_append, arx_selftest_bam_sort: dev_bamsort.h, hip_bamsort.h).
 #include <map>
 #include <memory>
 #include <mutex>
 #include "../../include/arachne_amd.h"
 #include "hip_bgzf.h"
 #include "hip_inflate.h"
+#include "hip_bamsort.h"
 
 namespace arx {
 
@@ -163,4 +165,96 @@ extern "C" int arx_selftest_inflate(int32_t device, const uint8_t *src, int64_t 
 	}
 	(void)hipFree(d_src); (void)hipFree(d_out); (void)hipFree(d_rows); (void)hipFree(d_status);
 	return rc;
+}
+
+// ---- the coordinate sort of a BAM file into an open writer (dev_bamsort.h, hip_bamsort.h)
+extern "C" int arx_bam_open_ex(arx_ctx *ctx, const char *path, int32_t n_contigs, const char *const *names, const int32_t *lens, const char *extra_header, int32_t threads,
+                               int32_t level, int32_t flags, arx_bam **out, char *msg, int32_t msg_cap)
+{
+	auto say = [&](const char *m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m); };
+	if (out) *out = nullptr;
+	if (!out || !path || n_contigs < 0 || (n_contigs > 0 && (!names || !lens))) { say("arx_bam_open_ex: null argument"); return ARX_E_ARG; }
+	if (flags & ~ARX_BAM_COORDINATE) { say("arx_bam_open_ex: unknown flag bits"); return ARX_E_ARG; }
+	arx::BamSink *w = nullptr;
+	try {
+		w = new arx::BamSink();
+		w->coordinate = (flags & ARX_BAM_COORDINATE) != 0;
+		if (ctx) w->comp = arx::shared_device_bgzf(arx_ctx_device(ctx));
+		if (!w->open(path, n_contigs, names, lens, extra_header, threads, ctx ? 1 : level)) {
+			const bool io = !ctx || !w->f;
+			say(w->error.c_str());
+			delete w;
+			return io ? ARX_E_IO : ARX_E_DEVICE;
+		}
+	} catch (const std::exception &e) {
+		say(e.what());
+		delete w;
+		return ctx ? ARX_E_DEVICE : ARX_E_IO;
+	}
+	*out = (arx_bam *)w;
+	return ARX_OK;
+}
+
+extern "C" int arx_bam_sort_append(arx_ctx *ctx, arx_bam *h, const char *in_path, int32_t mode, int64_t max_bytes, int64_t *stats, char *msg, int32_t msg_cap)
+{
+	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
+	if (stats) for (int k = 0; k < arx::BS_N_STATS; ++k) stats[k] = 0;
+	arx::BamSink *w = (arx::BamSink *)h;
+	const int32_t what = mode & ~ARX_SORT_TIMED;
+	if (!ctx || !w || !in_path || max_bytes < 0 || (what != ARX_SORT_COORDINATE && what != ARX_SORT_COPY)) { say("arx_bam_sort_append: bad arguments"); return ARX_E_ARG; }
+	std::string err;
+	try {
+		int32_t n = 0;
+		const char *const *names = nullptr;
+		const int64_t *offs = nullptr;
+		const int32_t *lens = nullptr, *alt = nullptr;
+		int64_t l_pac = 0;
+		if (arx_contigs(ctx, &n, &names, &offs, &lens, &alt, &l_pac) != ARX_OK) { say("arx_bam_sort_append: the context has no contigs"); return ARX_E_ARG; }
+		const bool device_writer = dynamic_cast<arx::DeviceBgzf *>(w->comp.get()) != nullptr;
+		const int rc = arx::bs_sort_append(arx_ctx_device(ctx), w, device_writer, [&](const uint8_t *d, int64_t bytes, int64_t recs) { return arx_bam_write_encoded_device(h, d, bytes, recs); },
+		                                   in_path, mode, max_bytes, n, names, lens, stats, err);
+		if (rc != ARX_OK) say(err);
+		return rc;
+	} catch (const arx::BsTooLarge &e) {
+		say(e.what());
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &e) {
+		say(e.what());
+		return ARX_E_DEVICE;
+	}
+}
+
+extern "C" int arx_selftest_bam_sort(int32_t device, const uint8_t *stream, int64_t n_bytes, int32_t n_ref, int64_t seg_bytes, int32_t mode, uint8_t *out, int64_t *rec_off,
+                                     int64_t *n_records, int64_t *stats)
+{
+	const int32_t what = mode & ~ARX_SORT_TIMED;
+	if (n_bytes < 0 || n_ref < 0 || seg_bytes < arx::BS_MIN_SEG || (seg_bytes & (seg_bytes - 1)) || !n_records || !rec_off || (n_bytes > 0 && (!stream || !out)) ||
+	    (what != ARX_SORT_COORDINATE && what != ARX_SORT_COPY))
+		return ARX_E_ARG;
+	*n_records = 0;
+	if (stats) for (int k = 0; k < arx::BS_N_STATS; ++k) stats[k] = 0;
+	try {
+		arx::BsStreamScope scope(device);
+		arx::BsHipDrv drv; drv.st = scope.st; drv.timed = (mode & ARX_SORT_TIMED) != 0;
+		arx::BsBuf d_s;
+		d_s.alloc((size_t)n_bytes);
+		if (n_bytes) ARX_HIP_CHECK(hipMemcpyAsync(d_s.p, stream, (size_t)n_bytes, hipMemcpyHostToDevice, drv.st));
+		const bool sort = what == ARX_SORT_COORDINATE;
+		const double t0 = arx::bs_now_us();
+		arx::BsSorted s;
+		if (s.run(drv, d_s.as<uint8_t>(), n_bytes, 0, seg_bytes, n_ref, sort) != arx::BS_OK) return ARX_E_IO;
+		ARX_HIP_CHECK(hipStreamSynchronize(drv.st));
+		drv.us[arx::BS_T_TOTAL] = arx::bs_now_us() - t0;
+		const int64_t N = s.found.n_records;
+		if (n_bytes) ARX_HIP_CHECK(hipMemcpyAsync(out, sort ? s.out.p : d_s.p, (size_t)n_bytes, hipMemcpyDeviceToHost, drv.st));
+		ARX_HIP_CHECK(hipMemcpyAsync(rec_off, sort ? (const void *)s.m.out_off : s.rec_off.p, (size_t)(N + 1) * 8, hipMemcpyDeviceToHost, drv.st));
+		ARX_HIP_CHECK(hipStreamSynchronize(drv.st));
+		*n_records = N;
+		arx::bs_stats(stats, drv, N, n_bytes, 0, s.found.n_seg, s.found.right, s.found.repaired, s.found.rounds, 1);
+	} catch (const arx::BsTooLarge &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
 }

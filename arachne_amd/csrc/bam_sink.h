@@ -39,6 +39,7 @@ struct BamSink {
 	FILE *f = nullptr;
 	std::shared_ptr<BlockCompressor> comp; // null: deflate_block below
 	int threads = 1, level = 6;
+	bool coordinate = false;               // set before open(): @HD says SO:coordinate (arx_bam_open_ex; what is appended is the caller's to order)
 	std::string error;
 	std::vector<uint8_t> pending;         // uncompressed bytes not yet cut into a block
 	int64_t n_records = 0, n_blocks = 0, bytes_in = 0, bytes_out = 0;
@@ -54,7 +55,7 @@ struct BamSink {
 		if (!f) { error = std::string("cannot write ") + path; return false; }
 		threads = threads_ > 0 ? threads_ : 1;
 		level = level_ >= 0 && level_ <= 9 ? level_ : 6;
-		std::string text = "@HD\tVN:1.6\tSO:unknown\n";
+		std::string text = coordinate ? "@HD\tVN:1.6\tSO:coordinate\n" : "@HD\tVN:1.6\tSO:unknown\n";
 		for (int i = 0; i < n_contigs; ++i) text += std::string("@SQ\tSN:") + names[i] + "\tLN:" + std::to_string(lens[i]) + "\n";
 		if (extra_header) text += extra_header;
 		std::vector<uint8_t> h;

@@ -40,7 +40,7 @@ _COUNTERS = dict(pairs=0, records=0, batches=0, feeder_s=0.0, device_s=0.0, fetc
 def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int = 250_000, bam_threads: int = 8, rec_threads: int = 8, level: int = 1,
         penalty: float = -4, lib_path: str = api.LIB_PATH, warm_passes: int = 0, layout: str = "workers", chunk: int = 40_000_000,
         read_groups: str = "", sample_id: str = "", feeder: str = "host", workers: int = 3, chunk_bytes: int = 0,
-        sink: str = "host", records: str = "host", inflate: str = "host"):
+        sink: str = "host", records: str = "host", inflate: str = "host", final_bam: str | None = None):
     """fastq_pairs: [(r1, r2), ...] barcode-sorted files (plain or gzip).  -> stats dict (pairs, records, batches, seconds, pairs/s, bam_bytes,
     workers, files, per-stage seconds summed over workers; bam_s: the writes and the closing of the writers).  One loop with four axes (the module docstring has them):
     feeder="host" (default): one host feeder and one worker per file pair.  feeder="device": ONE file pair, parsed on the GPU by one feeder
@@ -60,7 +60,11 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
     to the same bytes as with the default, sink="host".
     warm_passes (host feeder, layout="workers" only): untimed passes over the same files first, through the same batch handles -- a handle's
     first batch pays for its work memory (hipMalloc of several GiB: seconds once a 69 GB k-mer table sits beside it), which a run over a
-    whole read set pays once; the stats are those of the last pass."""
+    whole read set pays once; the stats are those of the last pass.
+    final_bam (layout="reference" only; default: off): after the pass, finalize() sorts the position buckets on ref's GPU into that one
+    coordinate-sorted BAM, through a writer of the same `sink`; stats["final"] are its stats."""
+    if final_bam is not None and layout != "reference":
+        raise ValueError("final_bam is made from the position buckets: it needs layout='reference'")
     if sink not in ("host", "device"):
         raise ValueError(f"unknown sink {sink!r}")
     if records not in ("host", "device", "device_full"):
@@ -203,7 +207,36 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
                 w.batch.free()
             for x in w.rb:
                 x.free()
+    if final_bam is not None:
+        stats["final"] = finalize(ref, out_prefix, final_bam, sink=sink, chunk=chunk, read_groups=read_groups, bam_threads=bam_threads, level=level, lib_path=lib_path)
     return stats
+
+
+def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "host", chunk: int = 40_000_000, read_groups: str = "", bam_threads: int = 8,
+             level: int = 1, max_bytes: int = 0, lib_path: str = api.LIB_PATH):
+    """The step the position buckets exist for: out_dir is a reference-layout directory (run(layout="reference") with the same chunk); every
+    bucket of api.bucket_table that was written is sorted by coordinate on ref's GPU (BamWriter.sort_append) and appended, in table order, to ONE
+    writer with reference_header(read_groups) and SO:coordinate; the unmapped file, which is its own sorted form (refID = pos = -1 throughout),
+    is appended in copy mode.  Buckets hold disjoint, ascending ranges of (contig, position), so the concatenation is sorted.  sink as in run.
+    -> dict(records, buckets, bytes, seconds, sort: the per-file stats)."""
+    if sink not in ("host", "device"):
+        raise ValueError(f"unknown sink {sink!r}")
+    names, offs, clens, alt, l_pac = ref.contigs()
+    table = api.bucket_table(names, clens, chunk, lib_path=lib_path)
+    t = time.time()
+    w = api.BamWriter(final_path, names, clens, extra_header=reference_header(read_groups), threads=bam_threads, level=level, lib_path=lib_path,
+                      device=ref if sink == "device" else None, coordinate=True)
+    per = []
+    try:
+        for k, f in enumerate(table.files):
+            p = os.path.join(out_dir, f)
+            if not os.path.exists(p):       # a bucket that was never written
+                continue
+            unmapped = k == len(table.files) - 1
+            per.append(dict(file=f, **w.sort_append(ref, p, mode="copy" if unmapped else "coordinate", max_bytes=max_bytes)))
+    finally:
+        st = w.close()
+    return dict(records=st["records"], buckets=len(per), bytes=st["bytes_out"], seconds=time.time() - t, sort=per)
 
 
 def _nothing():

@@ -296,6 +296,46 @@ int arx_bam_write_encoded(arx_bam *w, const uint8_t *stream, int64_t n_bytes, in
  * which the batch may be reset. */
 int arx_bam_write_encoded_device(arx_bam *w, const uint8_t *d_stream, int64_t n_bytes, int64_t n_records);
 
+/* ---- behind the sink: one coordinate-sorted BAM from the position buckets.  The reference writes the buckets so that each can be sorted in
+ * memory and the results concatenated in file order (its -p flag, "to speed up final BAM concatenation"); it contains no sort itself.
+ *
+ * arx_bam_open_ex: ctx == NULL: arx_bam_open; otherwise arx_bam_open_device on ctx's GPU, and `level` is ignored.  flags bit 0,
+ * ARX_BAM_COORDINATE: @HD says SO:coordinate instead of SO:unknown -- the order of what is appended stays the caller's business.  flags = 0
+ * gives byte for byte the file of the call it stands for; any other bit: ARX_E_ARG. */
+enum { ARX_BAM_COORDINATE = 1 };
+int arx_bam_open_ex(arx_ctx *ctx, const char *path, int32_t n_contigs, const char *const *names, const int32_t *lens, const char *extra_header, int32_t threads,
+                    int32_t level, int32_t flags, arx_bam **out, char *msg, int32_t msg_cap);
+/* Appends the records of the BAM file in_path to the open writer w, on ctx's GPU (csrc/dev_bamsort.h, hip_bamsort.h): the file's BGZF blocks are
+ * inflated there, the record starts found by segments walked side by side and verified against one another (exact whatever the data looks
+ * like), and
+ *   ARX_SORT_COORDINATE  the records are ordered stably by ((uint32_t)refID, pos) -- the SAM specification's SO:coordinate: refID = -1 last,
+ *                        equal keys in file order, the strand no part of the key -- by a radix sort of (key, index) and a gather.  The whole
+ *                        file is held at once, about 2.3 times its inflated size; a file that inflates to more than max_bytes (0: no limit
+ *                        of its own) or whose working set exceeds the free device memory is ARX_E_TOO_LARGE, and msg names the remedy: a
+ *                        smaller position bucket.  A refID outside [0, n_ref) sorts with -1
+ *   ARX_SORT_COPY        the records are appended in file order, in slabs of whole BGZF blocks that inflate to at most max_bytes (0: 256 MiB;
+ *                        at least one block) -- for a file that is its own sorted form, such as the unmapped bucket (refID = pos = -1
+ *                        throughout).  Only a slab is in device memory; the compressed file is read into host memory whole.  The records
+ *                        are counted by the same discovery, the chain carried from slab to slab
+ * and the stream is handed to the writer: in device memory to a writer of ctx's device (arx_bam_write_encoded_device's path), fetched to a host
+ * writer.  mode | ARX_SORT_TIMED waits for every launch and fills the phase times of stats.  ARX_E_ARG: the input's header does not list
+ * exactly the context's contigs (count, names, lengths), or bad arguments; ARX_E_IO, nothing appended: the file cannot be read, is not BGZF, a
+ * block does not inflate, it has no BAM header, or the chain of block_size fields breaks or does not end with the stream -- or the writer
+ * failed (then its arx_bam_error has the text too); ARX_E_DEVICE: a HIP error.  msg (may be NULL) receives the text.
+ * stats[20] (may be NULL): [0] records appended, [1] inflated bytes, [2] BGZF blocks, [3] segments, [4] segments whose guess was right,
+ * [5] segments repaired, [6] repair rounds, [7] slabs; microseconds: [8] read and header, [9] upload and inflate, [16] compress and write,
+ * [17] the call; with ARX_SORT_TIMED also [10] probe, [11] walk and fill, [12] verify and repair, [13] keys, [14] key sort, [15] sizes, scan
+ * and gather. */
+enum { ARX_SORT_COORDINATE = 0, ARX_SORT_COPY = 1, ARX_SORT_TIMED = 0x100 };
+int arx_bam_sort_append(arx_ctx *ctx, arx_bam *w, const char *in_path, int32_t mode, int64_t max_bytes, int64_t *stats, char *msg, int32_t msg_cap);
+/* self-test of the discovery, key, sort and gather kernels on plain record bytes, no index and no file needed (tests/test_bam_sort_gpu.py):
+ * stream[0..n_bytes) is a chain of BAM records from its first byte, n_ref what the probe holds refID against, seg_bytes the segment size (a
+ * power of two, at least 64; arx_bam_sort_append uses 256 KiB).  out[n_bytes] receives the records in coordinate order (mode ARX_SORT_COPY: as
+ * they are), rec_off[*n_records + 1] where they start in out (room for n_bytes / 36 + 2 entries always suffices).  ARX_E_IO: the chain is
+ * broken; out and rec_off are untouched.  stats[20] (may be NULL) as above, without blocks and file times. */
+int arx_selftest_bam_sort(int32_t device, const uint8_t *stream, int64_t n_bytes, int32_t n_ref, int64_t seg_bytes, int32_t mode, uint8_t *out, int64_t *rec_off,
+                          int64_t *n_records, int64_t *stats);
+
 /* ---- between the path and the sink: the placed candidate of every read of a super-batch as BAM records -- the part of DumpToBams /
  * AppendBam (src/aligner/bamwriter.go:283-568, 635-658) that decides flags, position, MAPQ, mate fields, template length, CIGAR op codes,
  * strand of bases and qualities and the RG / AS / XM / AM / XT / BX / VX tags of the primary record (csrc/bam_records.h lists what is left
