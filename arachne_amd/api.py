@@ -143,6 +143,10 @@ _SELFTEST_ARGS = {
     "arx_selftest_bgzf": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "arx_selftest_inflate": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
     "arx_selftest_rec_text": [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+    "arx_selftest_block_shape": [C.c_int32, C.c_void_p, C.c_void_p],
+    "arx_selftest_block": [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64],
+    "arx_selftest_rfa": [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                         C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     # the device BAM sink: bound when first used, for the same reason
     "arx_bam_open_device": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
     "arx_bam_write_encoded_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64],
@@ -336,6 +340,90 @@ def selftest_rec_text(a, b=None, device: int = 0, lib_path: str = LIB_PATH):
     if rc != 0:
         raise ArachneError("arx_selftest_rec_text: code %d" % rc)
     return [out[i, :ln[i]].tobytes() for i in range(n)]
+
+
+BLOCK_OPS = {"scan": 0, "sort_kv": 1, "argmax": 2}
+def block_class(klass: int, lib_path: str = LIB_PATH):
+    """(lanes, sort entries in LDS) of workgroup class `klass` as the library was built (hip_block.h: BLOCK_LANES / SORT_LDS, SMALL_LANES / SMALL_SORT;
+    arx_selftest_block_shape)."""
+    lib = _load(lib_path)
+    lanes, srt = C.c_int32(0), C.c_int32(0)
+    rc = _selftest_fn(lib, "arx_selftest_block_shape")(klass, C.byref(lanes), C.byref(srt))
+    if rc != 0:
+        raise ArachneError("arx_selftest_block_shape: code %d" % rc)
+    return int(lanes.value), int(srt.value)
+BARCODE_OUT_DTYPE = np.dtype([("dna_len", "<f8"), ("n_mol", "<i4"), ("pad", "<i4")])
+
+
+def selftest_block(klass: int, cases, device: int = 0, lib_path: str = LIB_PATH):
+    """hip_block.h's workgroup primitives, one case per workgroup (include/arachne_amd.h: arx_selftest_block).  cases: list of (op, keys, vals) with
+    op in BLOCK_OPS; scan reads vals, argmax keys, sort_kv both.  Returns one entry per case: scan -> (out[0..n] int32, the return value as lanes
+    0, 63, 64 and the last got it), sort_kv -> (keys uint64, vals int32), argmax -> (keys uint64[4], idx int32[4]) of the same four lanes."""
+    lib = _load(lib_path)
+    nc = len(cases)
+    ops = np.array([BLOCK_OPS[c[0]] for c in cases], dtype=np.int32)
+    ks = [np.ascontiguousarray(c[1] if c[1] is not None else [], dtype=np.uint64) for c in cases]
+    vs = [np.ascontiguousarray(c[2] if c[2] is not None else [], dtype=np.int32) for c in cases]
+    ns = np.array([max(len(k), len(v)) for k, v in zip(ks, vs)], dtype=np.int32)
+    need = [int(n) + 5 if o == 0 else int(n) if o == 1 else 4 for o, n in zip(ops, ns)]
+    in_off = np.concatenate([[0], np.cumsum(ns, dtype=np.int64)]).astype(np.int64)
+    out_off = np.concatenate([[0], np.cumsum(need, dtype=np.int64)]).astype(np.int64)
+    keys, vals = np.zeros(int(in_off[-1]) + 1, dtype=np.uint64), np.zeros(int(in_off[-1]) + 1, dtype=np.int32)
+    for i in range(nc):
+        keys[in_off[i]:in_off[i] + len(ks[i])] = ks[i]
+        vals[in_off[i]:in_off[i] + len(vs[i])] = vs[i]
+    n_out = int(out_off[-1])
+    ok, ov = np.full(n_out + 1, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64), np.full(n_out + 1, -0x5A5A5A5B, dtype=np.int32)  # a value no lane wrote stays recognisable
+    rc = _selftest_fn(lib, "arx_selftest_block")(device, klass, nc, ops.ctypes.data, ns.ctypes.data, in_off.ctypes.data, out_off.ctypes.data, keys.ctypes.data,
+                                                 vals.ctypes.data, int(in_off[-1]), ok.ctypes.data, ov.ctypes.data, n_out)
+    if rc != 0:
+        raise ArachneError("arx_selftest_block: code %d" % rc)
+    res = []
+    for i in range(nc):
+        o, n = int(out_off[i]), int(ns[i])
+        if ops[i] == 0:
+            res.append((ov[o:o + n + 1].copy(), ov[o + n + 1:o + n + 5].copy()))
+        elif ops[i] == 1:
+            res.append((ok[o:o + n].copy(), ov[o:o + n].copy()))
+        else:
+            res.append((ok[o:o + 4].copy(), ov[o:o + 4].copy()))
+    return res
+
+
+def selftest_rfa(batch, lens, bc_pair_off, do_rfa, l_pac: int, ann_off, penalty: int = -4, centromeres=None, rfa_small: bool = False, mapq_guard=None,
+                 device: int = 0, lib_path: str = LIB_PATH):
+    """The placement stage on given alignments (include/arachne_amd.h: arx_selftest_rfa).  batch: dict with reg_off / regs / alns / cigars in the
+    restatement's int64 row layout (what tests/rfadrv.py oracle_rfa takes) -> dict(cand_off, cands (CAND_DTYPE), barcodes (BARCODE_OUT_DTYPE),
+    cls (uint8 per barcode: 1 = small workgroup class), n_host_mapq)."""
+    lib = _load(lib_path)
+    reg_off = np.ascontiguousarray(batch["reg_off"], dtype=np.int64)
+    regs = np.ascontiguousarray(batch["regs"], dtype=np.int64).reshape(-1, 20)
+    alns = np.ascontiguousarray(batch["alns"], dtype=np.int64).reshape(-1, 12)
+    cig = np.ascontiguousarray(batch["cigars"], dtype=np.uint32)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    bco = np.ascontiguousarray(bc_pair_off, dtype=np.int64)
+    flags = np.ascontiguousarray(do_rfa, dtype=np.uint8)
+    ann = np.ascontiguousarray(ann_off, dtype=np.int64)
+    n_reads, nb = len(lens), len(bco) - 1
+    if len(reg_off) != n_reads + 1 or len(flags) != nb:
+        raise ValueError("reg_off / do_rfa do not match the reads / barcodes")
+    cs = ce = None
+    if centromeres is not None:
+        cs, ce = (np.ascontiguousarray(x, dtype=np.int64) for x in centromeres)
+        if len(cs) != len(ann) or len(ce) != len(ann):
+            raise ValueError("one centromere per contig")
+    n_regs = np.diff(reg_off)
+    n_cands = int(np.where(n_regs > 0, n_regs, 1).sum())
+    off, cands = np.zeros(n_reads + 1, dtype=np.int32), np.zeros(n_cands, dtype=CAND_DTYPE)
+    bc, cls, nh = np.zeros(nb, dtype=BARCODE_OUT_DTYPE), np.full(nb, 255, dtype=np.uint8), C.c_int64(-1)
+    rc = _selftest_fn(lib, "arx_selftest_rfa")(device, n_reads, reg_off.ctypes.data, regs.ctypes.data, alns.ctypes.data, cig.ctypes.data, len(cig), lens.ctypes.data, nb,
+                                               bco.ctypes.data, flags.ctypes.data, int(penalty), int(l_pac), ann.ctypes.data, len(ann),
+                                               None if cs is None else cs.ctypes.data, None if ce is None else ce.ctypes.data, int(bool(rfa_small)),
+                                               -1.0 if mapq_guard is None else float(mapq_guard), off.ctypes.data, cands.ctypes.data, n_cands, bc.ctypes.data,
+                                               cls.ctypes.data, C.byref(nh))
+    if rc != 0:
+        raise ArachneError("arx_selftest_rfa: code %d" % rc)
+    return dict(cand_off=off, cands=cands, barcodes=bc, cls=cls, n_host_mapq=int(nh.value))
 
 
 class _RecordsLayout(C.Structure):

@@ -2,6 +2,8 @@
 // arx_selftest_rescue_sw, arx_selftest_gen_cigar) and of the records phase's decimal text (arx_selftest_rec_text).  They take plain host arrays, build what the pipeline would hand the kernels (an IndexView
 // with only the packed text set, class-binned extension tasks, rescue tasks with their mates, staged CIGAR regions) and launch the production
 // code through HipRT, so that tests/test_dp_kernels_gpu.py can compare every output field with ksw_extend2 / ksw_align2 / ksw_global2.
+// arx_selftest_block runs the workgroup primitives of hip_block.h (scan, bitonic sort, arg-max) through k_block_items itself, one case per workgroup, and
+// arx_selftest_rfa (selftest_rfa.h) the whole placement stage on alignments the caller made up (tests/test_block_primitives_gpu.py, tests/test_rfa_cases_gpu.py).
 // Its own unit so that the unit of the list-bookkeeping kernels does not grow.
 #include <climits>
 #include <vector>
@@ -9,6 +11,7 @@
 #include "hip_rt.h"
 #include "pipeline.h"
 #include "dev_records_full.h"
+#include "selftest_rfa.h"
 
 namespace arx {
 
@@ -47,6 +50,30 @@ struct KSelftestRecText {
 		else { const uint64_t t = dm_scaled_signed(a[i], b[i]); l = dm_len(a[i], t); for (int k = 0; k < l; ++k) o[k] = (uint8_t)dm_char(a[i] < 0, t, k); }
 		for (int k = l; k < 32; ++k) o[k] = 0;
 		len[i] = l;
+	}
+};
+
+// one case per workgroup of hip_block.h's primitives, started by HipRT::launch_block like the placement kernel (k_block_items<F, LANES, SORT>: the
+// production LDS layout and launch bounds).  A value every lane receives is read back from lanes 0, 63, 64 and LANES - 1 (slots 0..3).
+struct KSelftestBlock {
+	const int32_t *op, *n; const int64_t *in_off, *out_off; const uint64_t *keys; const int32_t *vals; uint64_t *ok; int32_t *ov;
+	template <int L> static __device__ int slot_of(int tid) { return tid == 0 ? 0 : tid == 63 ? 1 : tid == 64 ? 2 : tid == L - 1 ? 3 : -1; }
+	template <int L, int S> __device__ void operator()(int c, HipBlockT<L, S> &blk) const
+	{
+		const int m = n[c], slot = slot_of<L>(blk.tid);
+		const uint64_t *k = keys + in_off[c]; const int32_t *v = vals + in_off[c];
+		uint64_t *o64 = ok + out_off[c]; int32_t *o32 = ov + out_off[c];
+		if (op[c] == ARX_BLOCK_OP_SCAN) { // o32[0..m] = the scan, o32[m + 1 + slot] = the return value in four lanes
+			const int total = blk.exclusive_scan(v, o32, m);
+			if (slot >= 0) o32[m + 1 + slot] = total;
+		} else if (op[c] == ARX_BLOCK_OP_SORT) { // in place on the output arrays, as rfa_barcode sorts its scratch
+			blk.pfor(m, [&](int i) { o64[i] = k[i]; o32[i] = v[i]; });
+			blk.sort_kv(o64, o32, m);
+		} else {
+			uint64_t bk; int bi;
+			blk.argmax(m, [&](int i) -> uint64_t { return k[i]; }, &bk, &bi);
+			if (slot >= 0) { o64[slot] = bk; o32[slot] = bi; }
+		}
 	}
 };
 
@@ -225,4 +252,68 @@ extern "C" int arx_selftest_rec_text(int32_t device, int32_t n, const int32_t *a
 		return ARX_E_DEVICE;
 	}
 	return ARX_OK;
+}
+
+extern "C" int arx_selftest_block_shape(int32_t klass, int32_t *lanes, int32_t *sort_entries)
+{
+	if (klass < 0 || klass > 1 || !lanes || !sort_entries) return ARX_E_ARG;
+	*lanes = klass == 0 ? arx::BLOCK_LANES : arx::SMALL_LANES;
+	*sort_entries = klass == 0 ? arx::SORT_LDS : arx::SMALL_SORT;
+	return ARX_OK;
+}
+
+extern "C" int arx_selftest_block(int32_t device, int32_t klass, int32_t n_cases, const int32_t *op, const int32_t *n, const int64_t *in_off, const int64_t *out_off,
+                                  const uint64_t *keys, const int32_t *vals, int64_t n_in, uint64_t *out_keys, int32_t *out_vals, int64_t n_out)
+{
+	using namespace arx;
+	if (n_cases < 0 || klass < 0 || klass > 1 || n_in < 0 || n_out < 0) return ARX_E_ARG;
+	if (n_cases > 0 && (!op || !n || !in_off || !out_off || !out_keys || !out_vals || (n_in > 0 && (!keys || !vals)))) return ARX_E_ARG;
+	for (int c = 0; c < n_cases; ++c) { // every index a workgroup forms lies inside the arrays
+		if (n[c] < 0 || n[c] > (1 << 24) || in_off[c] < 0 || out_off[c] < 0 || in_off[c] + n[c] > n_in) return ARX_E_ARG;
+		int64_t need;
+		if (op[c] == ARX_BLOCK_OP_SCAN) need = (int64_t)n[c] + 5;
+		else if (op[c] == ARX_BLOCK_OP_SORT) { need = n[c]; if (n[c] < 1 || (n[c] & (n[c] - 1))) return ARX_E_ARG; }
+		else if (op[c] == ARX_BLOCK_OP_ARGMAX) need = 4;
+		else return ARX_E_ARG;
+		if (out_off[c] + need > n_out) return ARX_E_ARG;
+	}
+	if (n_cases == 0) return ARX_OK;
+	try {
+		HipRT rt;
+		if (!rt.init(device).empty()) return ARX_E_DEVICE;
+		rt.timing = false;
+		int32_t *d_i = rt.alloc<int32_t>(2 * (size_t)n_cases), *d_v = rt.alloc<int32_t>((size_t)n_in + 1), *d_ov = rt.alloc<int32_t>((size_t)n_out + 1);
+		int64_t *d_o = rt.alloc<int64_t>(2 * (size_t)n_cases);
+		uint64_t *d_k = rt.alloc<uint64_t>((size_t)n_in + 1), *d_ok = rt.alloc<uint64_t>((size_t)n_out + 1);
+		rt.h2d(d_i, op, 4 * (size_t)n_cases); rt.h2d(d_i + n_cases, n, 4 * (size_t)n_cases);
+		rt.h2d(d_o, in_off, 8 * (size_t)n_cases); rt.h2d(d_o + n_cases, out_off, 8 * (size_t)n_cases);
+		rt.h2d(d_k, keys, 8 * (size_t)n_in); rt.h2d(d_v, vals, 4 * (size_t)n_in);
+		rt.h2d(d_ok, out_keys, 8 * (size_t)n_out); rt.h2d(d_ov, out_vals, 4 * (size_t)n_out); // what no case writes comes back as the caller filled it
+		KSelftestBlock f{d_i, d_i + n_cases, d_o, d_o + n_cases, d_k, d_v, d_ok, d_ov};
+		const std::vector<uint8_t> small((size_t)n_cases, 1);
+		rt.launch_block("selftest_block", n_cases, f, klass == 1 ? small.data() : nullptr);
+		ARX_HIP_CHECK(hipStreamSynchronize(rt.stream));
+		rt.d2h(out_keys, d_ok, 8 * (size_t)n_out);
+		rt.d2h(out_vals, d_ov, 4 * (size_t)n_out);
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}
+
+extern "C" int arx_selftest_rfa(int32_t device, int32_t n_reads, const int64_t *reg_off, const int64_t *regs, const int64_t *alns, const uint32_t *cigars, int64_t n_cig,
+                                const int32_t *lens, int32_t n_barcodes, const int64_t *bc_pair_off, const uint8_t *do_rfa, int32_t penalty, int64_t l_pac,
+                                const int64_t *ann_off, int32_t n_seqs, const int64_t *cen_start, const int64_t *cen_end, int32_t rfa_small, double mapq_guard,
+                                int32_t *cand_off, void *cands, int64_t cand_cap, void *bc_out, uint8_t *cls, int64_t *n_host_mapq)
+{
+	using namespace arx;
+	try {
+		HipRT rt;
+		if (!rt.init(device).empty()) return ARX_E_DEVICE;
+		rt.timing = false;
+		return selftest_rfa_run(rt, n_reads, reg_off, regs, alns, cigars, n_cig, lens, n_barcodes, bc_pair_off, do_rfa, penalty, l_pac, ann_off, n_seqs, cen_start, cen_end,
+		                        rfa_small, mapq_guard, cand_off, cands, cand_cap, bc_out, cls, n_host_mapq);
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
 }

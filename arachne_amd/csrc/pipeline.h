@@ -541,6 +541,7 @@ public:
 	IndexView ix;
 	const PipelineSwitches sw; // the stages' environment switches as they were when this pipeline (= its batch handle) was created (switches.h)
 	explicit Pipeline(RT &rt_, const IndexView &ix_) : rt(rt_), ix(ix_) {}
+	Pipeline(RT &rt_, const IndexView &ix_, const PipelineSwitches &sw_) : rt(rt_), ix(ix_), sw(sw_) {} // the self-tests: switches from arguments, not the environment
 
 	// device-resident input of one batch; the buffers are kept by the handle and reused by arx_batch_reset (cap_*: what they hold)
 	struct DeviceBatch { uint8_t *bases = 0; int32_t *base_off = 0, *lens = 0; int n_reads = 0; int64_t n_bases = 0; int max_len = 0; int64_t cap_bases = 0; int cap_reads = 0; };

@@ -42,6 +42,7 @@ struct KMapqPair { // one candidate per lane: its best pair score over the mate'
 struct KMapq { // one read per lane: MAPQ of its active candidate; values a few ulp could change are queued for the host
 	Cand *cands; const int32_t *cand_off; const int32_t *lens; const int32_t *bc_read_off; int n_barcodes; const double *log_mol_pen;
 	int penalty; const int64_t *cen_start, *cen_end; double guard; int32_t *flagged, *n_flagged; const int32_t *pair_best;
+	int all_host; // every read is queued for the host, whatever its value (RfaStage::run decides)
 	ARX_DEV void operator()(int r, int) const
 	{
 		int lo = 0, hi = n_barcodes;
@@ -50,7 +51,7 @@ struct KMapq { // one read per lane: MAPQ of its active candidate; values a few 
 		int a; double largest;
 		const double v = rfa_mapq_value(cands, cand_off[r], cand_off[r + 1], cand_off[mr], cand_off[mr + 1], lens[r], log_mol_pen[lo], penalty, &a, &largest, pair_best);
 		cands[a].mapq = rfa_mapq_final(v, cands[a], cen_start, cen_end); // the mate's lane reads other fields of this record, never mapq
-		if (rfa_mapq_needs_host(v, largest, guard)) flagged[ARX_ATOMIC_INC(n_flagged)] = r;
+		if (all_host || rfa_mapq_needs_host(v, largest, guard)) flagged[ARX_ATOMIC_INC(n_flagged)] = r;
 	}
 };
 struct KMapqPatch { Cand *cands; const int32_t *idx, *val; ARX_DEV void operator()(int k, int) const { cands[idx[k]].mapq = val[k]; } };
@@ -93,6 +94,7 @@ struct KTags {
 
 struct RfaResult {
 	std::vector<int32_t> cand_off; std::vector<RfaBarcodeOut> bc;
+	std::vector<uint8_t> cls; // per barcode: 1 = launched in the SMALL_LANES workgroup class (all 0 unless pipe.sw.rfa_small)
 	Cand *d_cands = nullptr; int64_t n_cands = 0; int64_t n_host_mapq = 0;
 	// kept in HBM for the passes that follow (pipeline_post.h, TagsStage)
 	int32_t *d_cand_off = nullptr, *d_bc_read_off = nullptr; int64_t *d_cen_start = nullptr, *d_cen_end = nullptr; int n_barcodes = 0, penalty = 0;
@@ -138,7 +140,8 @@ template <class RT> struct RfaStage {
 		rt.h2d(d_flags, do_rfa, n_barcodes); rt.h2d(d_p10, p10.data(), 8 * p10.size());
 		KRfa kr{cand_off, d_bro, d_flags, d_so, penalty, pipe.ix.n_seqs, d_p10, cands, d_scr, d_out};
 		// pipe.sw.rfa_small (experiments, off by default: switches.h has the measurement): barcodes of TELLseq size in 256-lane workgroups (hip_block.h)
-		std::vector<uint8_t> small(n_barcodes, 0);
+		std::vector<uint8_t> &small = res.cls;
+		small.assign(n_barcodes, 0);
 		const bool rfa_small = pipe.sw.rfa_small;
 		if (rfa_small)
 			for (int i = 0; i < n_barcodes; ++i) small[i] = (bro[i + 1] - bro[i] <= 2 * SMALL_LANES && res.cand_off[bro[i + 1]] - res.cand_off[bro[i]] <= SMALL_SORT / 2) ? 1 : 0;
@@ -166,7 +169,10 @@ template <class RT> struct RfaStage {
 		int32_t *pair_best = rt.template alloc<int32_t>((size_t)NC + 1);
 		KMapqPair kp{cands, cand_off, penalty, pair_best};
 		rt.launch_wide("mapq_pair", (int)NC, kp);
-		KMapq km{cands, cand_off, b.lens, d_bro, n_barcodes, d_lmp, penalty, d_cs, d_ce, guard, d_flag, w.counter, pair_best};
+		// No value lies further than 0.5 from an integer, so a guard that wide asks for every read, capped values (which rfa_mapq_needs_host leaves
+		// out: they are 60 on either side) included: the whole batch goes through the host evaluation and the patch
+		const int all_host = guard >= 0.5 ? 1 : 0;
+		KMapq km{cands, cand_off, b.lens, d_bro, n_barcodes, d_lmp, penalty, d_cs, d_ce, guard, d_flag, w.counter, pair_best, all_host};
 		rt.launch_wide("mapq", R, km);
 		const int nf = pipe.read_counter(w);
 		res.n_host_mapq = nf;

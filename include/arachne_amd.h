@@ -486,6 +486,31 @@ int arx_selftest_inflate(int32_t device, const uint8_t *src, int64_t n, uint8_t 
  * of each text.  There so that the GPU suite can hold the formatters to the host's on inputs the path does not produce at test size. */
 int arx_selftest_rec_text(int32_t device, int32_t n, const int32_t *a, const int32_t *b, int32_t kind, uint8_t *out /* 32 * n */, int32_t *len /* n */);
 
+/* self-test of the workgroup primitives the placement kernel is written in (csrc/hip_block.h: exclusive_scan, sort_kv, argmax), one case per
+ * workgroup, started through k_block_items like the kernel itself.  klass 0: BLOCK_LANES lanes and SORT_LDS sort entries of LDS, 1: SMALL_LANES
+ * and SMALL_SORT.  Case c reads keys / vals at [in_off[c], in_off[c] + n[c]) and writes out_keys / out_vals from out_off[c] on:
+ *   ARX_BLOCK_OP_SCAN    out_vals[0 .. n] = sums of vals in front of each index (n + 1 values), out_vals[n + 1 .. n + 4] = the value the call
+ *                        returned in lanes 0, 63, 64 and the last one;
+ *   ARX_BLOCK_OP_SORT    the n pairs (n a power of two) ascending by (key, (uint32)val); above the class's sort entries the sort runs in HBM;
+ *   ARX_BLOCK_OP_ARGMAX  out_keys / out_vals[0 .. 3] = the largest key (0: none) and its smallest index (0x7fffffff: none) as those four lanes got them.
+ * Everything else of out_keys / out_vals (n_out entries each) comes back as the caller filled it.  Offsets outside the arrays: ARX_E_ARG. */
+enum { ARX_BLOCK_OP_SCAN = 0, ARX_BLOCK_OP_SORT = 1, ARX_BLOCK_OP_ARGMAX = 2 };
+int arx_selftest_block_shape(int32_t klass, int32_t *lanes, int32_t *sort_entries); /* the two numbers of a class as this library was built (no device needed) */
+int arx_selftest_block(int32_t device, int32_t klass, int32_t n_cases, const int32_t *op, const int32_t *n, const int64_t *in_off, const int64_t *out_off,
+                       const uint64_t *keys, const int32_t *vals, int64_t n_in, uint64_t *out_keys, int32_t *out_vals, int64_t n_out);
+
+/* self-test of the placement stage (what arx_batch_rfa runs: candidates per read, per-barcode joint placement, MAPQ with its host patch) on
+ * alignments the caller made up, in the int64 row layout of the CPU restatement (oracle/arx_oracle.h: 20 columns per region, 12 per
+ * alignment, CIGAR words at column 8's offset; n_cig words in all).  ann_off[n_seqs], l_pac: the only things read of an index.  rfa_small and
+ * mapq_guard (< 0: the default) stand for ARX_RFA_SMALL and ARX_MAPQ_GUARD, which this entry does not read.  cands: cand_cap records of 96
+ * bytes (api.py CAND_DTYPE), cand_cap = one per region plus one per read without any (else ARX_E_ARG); cand_off[n_reads + 1]; bc_out:
+ * n_barcodes x (double dna_len, int32 n_mol, int32 pad); cls[n_barcodes]: 1 where the barcode was given to the small workgroup class;
+ * *n_host_mapq: reads whose MAPQ the host re-evaluated.  Row values that a kernel would index with are checked first (ARX_E_ARG). */
+int arx_selftest_rfa(int32_t device, int32_t n_reads, const int64_t *reg_off, const int64_t *regs, const int64_t *alns, const uint32_t *cigars, int64_t n_cig,
+                     const int32_t *lens, int32_t n_barcodes, const int64_t *bc_pair_off, const uint8_t *do_rfa, int32_t penalty, int64_t l_pac,
+                     const int64_t *ann_off, int32_t n_seqs, const int64_t *cen_start, const int64_t *cen_end, int32_t rfa_small, double mapq_guard,
+                     int32_t *cand_off, void *cands, int64_t cand_cap, void *bc_out, uint8_t *cls, int64_t *n_host_mapq);
+
 /* self-tests of the three DP kernel families on plain host arrays (csrc/arx_selftest.hip; tests/test_dp_kernels_gpu.py): each entry
  * uploads the tasks, launches the production code on them and returns one result row per task, in input order.  The reference text is
  * passed in bwa's .pac layout (pac: (l_pac + 3) / 4 bytes, 2 bits per base, first base in the top bits); coordinates are doubled, so a

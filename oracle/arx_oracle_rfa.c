@@ -37,6 +37,7 @@ typedef struct {
 	int mismatches, indels, soft_clipped, soft_clipped_length;
 	int lap2;           /* log_alignment_probability in half-units */
 	int active, is_proper, mol, best_in_mol, active_molecule;
+	int bim_out;        /* best_in_mol as scrapMolecules left it, kept for the output row beside the filtered marker */
 	double sum_move;
 	int mapq;
 } cand_t;
@@ -128,7 +129,7 @@ static int fast_score2(const bc_t *b, int S, int T, int *num_out, int *mv_read, 
 static int cmp_pos(const void *x, const void *y) { const int64_t *a = (const int64_t*)x, *b = (const int64_t*)y; return (a[0] > b[0]) - (a[0] < b[0]) ? (a[0] > b[0]) - (a[0] < b[0]) : (a[1] > b[1]) - (a[1] < b[1]); }
 
 /* output row per candidate (ORA_CAND_W int64): reg read pos aend reversed rid score mismatches indels soft_clipped
- * soft_clipped_length lap2 active is_proper mapq molecule_id active_molecule in_filtered */
+ * soft_clipped_length lap2 active is_proper mapq molecule_id active_molecule in_filtered sum_move(bits) best_in_mol */
 
 
 /* One barcode.  Region/aln rows are the batch-global ones; r0 = first read of the barcode (even), n_reads reads. */
@@ -366,7 +367,7 @@ static void rfa_one_barcode(const int64_t *reg_off, const int64_t *regs, const i
 	}
 	/* emit: one row per candidate of `full`, flags taken from its filtered copy */
 	for (int i = 0; i < n_full; ++i) full[i].mol = -1;
-	for (int i = 0; i < b.n_c; ++i) { cand_t t = b.c[i]; full[src_idx[i]] = t; full[src_idx[i]].best_in_mol = 2; }
+	for (int i = 0; i < b.n_c; ++i) { cand_t t = b.c[i]; full[src_idx[i]] = t; full[src_idx[i]].bim_out = t.best_in_mol; full[src_idx[i]].best_in_mol = 2; }
 	for (int r = 0; r < n_reads; ++r) cand_off_out[r] = *n_cand_total + foff[r];
 	for (int i = 0; i < n_full; ++i) {
 		int64_t *o = cand_rows + (*n_cand_total + i) * ORA_CAND_W;
@@ -374,6 +375,7 @@ static void rfa_one_barcode(const int64_t *reg_off, const int64_t *regs, const i
 		o[0] = c->reg; o[1] = r0 + c->read; o[2] = c->pos; o[3] = c->aend; o[4] = c->reversed; o[5] = c->rid; o[6] = c->score;
 		o[7] = c->mismatches; o[8] = c->indels; o[9] = c->soft_clipped; o[10] = c->soft_clipped_length; o[11] = c->lap2;
 		o[12] = c->active; o[13] = c->is_proper; o[14] = c->mapq; o[15] = c->mol; o[16] = c->active_molecule; o[17] = c->best_in_mol == 2;
+		memcpy(&o[18], &c->sum_move, sizeof(double)); o[19] = c->bim_out;
 	}
 	*n_cand_total += n_full;
 	free(full); free(foff); free(b.c); free(b.roff); free(src_idx); free(b.mol); free(b.pot_off); free(b.pot_read);

@@ -183,6 +183,7 @@ struct SimRT {
 } // namespace arx
 
 #include "../../arachne_amd/csrc/api_impl.h"
+#include "../../arachne_amd/csrc/selftest_rfa.h"
 ARX_DEFINE_C_API(arx::SimRT)
 
 // test entry: the bytes of a batch's work arena that are live now (tests/test_arena_lifecycle.py: no phase grows from one cycle to the next, and
@@ -414,6 +415,20 @@ extern "C" int arx_selftest_rescue_sw(int32_t, const uint8_t *, int64_t, const u
                                       int32_t, int32_t, int32_t *) { return ARX_E_DEVICE; }
 extern "C" int arx_selftest_gen_cigar(int32_t, int32_t, const uint8_t *, const int32_t *, const int32_t *, const uint8_t *, const int32_t *, const int32_t *, const int32_t *,
                                       const int32_t *, int32_t, int32_t, int32_t *, uint32_t *) { return ARX_E_DEVICE; }
+
+// the workgroup primitives themselves exist on the GPU only (SimBlock above stands in for them); the placement stage on given alignments runs here too
+extern "C" int arx_selftest_block_shape(int32_t, int32_t *, int32_t *) { return ARX_E_DEVICE; }
+extern "C" int arx_selftest_block(int32_t, int32_t, int32_t, const int32_t *, const int32_t *, const int64_t *, const int64_t *, const uint64_t *, const int32_t *, int64_t,
+                                  uint64_t *, int32_t *, int64_t) { return ARX_E_DEVICE; }
+extern "C" int arx_selftest_rfa(int32_t, int32_t n_reads, const int64_t *reg_off, const int64_t *regs, const int64_t *alns, const uint32_t *cigars, int64_t n_cig,
+                                const int32_t *lens, int32_t n_barcodes, const int64_t *bc_pair_off, const uint8_t *do_rfa, int32_t penalty, int64_t l_pac,
+                                const int64_t *ann_off, int32_t n_seqs, const int64_t *cen_start, const int64_t *cen_end, int32_t rfa_small, double mapq_guard,
+                                int32_t *cand_off, void *cands, int64_t cand_cap, void *bc_out, uint8_t *cls, int64_t *n_host_mapq)
+{
+	arx::SimRT rt;
+	return arx::selftest_rfa_run(rt, n_reads, reg_off, regs, alns, cigars, n_cig, lens, n_barcodes, bc_pair_off, do_rfa, penalty, l_pac, ann_off, n_seqs, cen_start, cen_end,
+	                             rfa_small, mapq_guard, cand_off, cands, cand_cap, bc_out, cls, n_host_mapq);
+}
 
 // test entry: the one-thread extension (dev_sw.h ext2_task, what ARX_SW_SIMPLE runs) on tasks laid out as arx_selftest_extend takes them --
 // text in .pac layout, doubled coordinates, both directions (tests/test_dp_cases_hostsim.py compares it with the oracle's ksw_extend2)

@@ -75,7 +75,7 @@ def check_core(batch, ora, seqs, lens, reads=None):
 
 RFA_FIELDS = [("reg", 0), ("read", 1), ("pos", 2), ("aend", 3), ("reversed", 4), ("rid", 5), ("score", 6), ("mismatches", 7), ("indels", 8),
               ("soft_clipped", 9), ("soft_clipped_length", 10), ("lap2", 11), ("active", 12), ("is_proper", 13), ("mapq", 14),
-              ("molecule_id", 15), ("active_molecule", 16), ("in_filtered", 17)]
+              ("molecule_id", 15), ("active_molecule", 16), ("in_filtered", 17), ("sum_move", 18), ("best_in_mol", 19)]
 
 
 def check_rfa(dev, ora):
@@ -84,7 +84,8 @@ def check_rfa(dev, ora):
     d, o = dev["cands"], ora["cands"]
     assert len(d) == len(o)
     for name, col in RFA_FIELDS:
-        a, b = d[name].astype(np.int64), o[:, col]
+        a = d[name].view(np.int64) if name == "sum_move" else d[name].astype(np.int64)   # the double's bits: no tolerance
+        b = o[:, col]
         if name == "mapq":
             m = o[:, 12] == 1
             a, b = a[m], b[m]

@@ -6,9 +6,9 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORA_SO = os.path.join(HERE, "..", "oracle", "liboracle.so")
-CAND_W = 18
+CAND_W = 20
 CAND_FIELDS = ["reg", "read", "pos", "aend", "reversed", "rid", "score", "mismatches", "indels", "soft_clipped", "soft_clipped_length",
-               "lap2", "active", "is_proper", "mapq", "molecule_id", "active_molecule", "in_filtered"]
+               "lap2", "active", "is_proper", "mapq", "molecule_id", "active_molecule", "in_filtered", "sum_move", "best_in_mol"]
 
 
 from arachne_amd.api import worth_running_rfa  # noqa: E402,F401  (host logic of the product, re-exported for the tests)

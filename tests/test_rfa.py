@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import parity
+import rfacases
 import rfadrv
 import workloads
 from arachne_amd import api, synth
@@ -21,26 +22,8 @@ L_PAC = 1_000_000
 
 
 def _rows(cands):
-    """cands: list per read of dicts(pos, rev, score, nm, cigar=[(op,len)...]) on one contig at offset 0 -> oracle input rows.
-    A reverse-strand candidate with leftmost position P covers [P, P+150): aligner.go:1577-1582 with gobwa.go:351-363."""
-    reg_off, regs, alns, cig = [0], [], [], []
-    for read in cands:
-        for c in read:
-            if c["rev"]:
-                cend = c["pos"] - 1          # pos = Alignment_end + 1
-                re_ = 2 * L_PAC - 1 - cend
-                rb = re_ - 150
-            else:
-                rb, re_ = c["pos"], c["pos"] + 150
-            r = [0] * 20
-            r[0], r[1], r[2], r[3], r[4], r[5], r[6] = rb, re_, 0, 150, 0, c["score"], c["score"]
-            regs.append(r)
-            cg = c.get("cigar", [(0, 150)])
-            alns.append([0, 0, 0, int(c["rev"]), 0, 0, c.get("nm", 0), len(cg), len(cig), c["score"], 0, 0])
-            cig += [(ln << 4) | op for op, ln in cg]
-        reg_off.append(len(regs))
-    return dict(reg_off=np.array(reg_off), regs=np.array(regs, dtype=np.int64).reshape(-1, 20), alns=np.array(alns, dtype=np.int64).reshape(-1, 12),
-                cigars=np.array(cig + [0], dtype=np.uint32))
+    """cands: list per read of dicts(pos, rev, score, nm, cigar=[(op,len)...]) on one contig at offset 0 -> oracle input rows (rfacases.rows has the layout)."""
+    return rfacases.rows(cands, L_PAC)
 
 
 def _run(cands, do_rfa=True, penalty=-4):
