@@ -128,18 +128,13 @@ extern "C" int arx_selftest_inflate(int32_t device, const uint8_t *src, int64_t 
 	if (nb < 0 || nb > status_cap || nb > INT32_MAX || total > cap) return ARX_E_ARG;
 	std::vector<arx::InfRow> rows((size_t)nb);
 	arx::bgzf_walk(src, n, rows.data(), nb, &total);
-	uint8_t *d_src = nullptr, *d_out = nullptr;
-	arx::InfRow *d_rows = nullptr;
-	int32_t *d_status = nullptr; // nb statuses, then the two counts
 	int rc = ARX_OK;
 	try {
-		int n_dev = 0;
-		if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return ARX_E_DEVICE;
-		ARX_HIP_CHECK(hipSetDevice(device));
-		ARX_HIP_CHECK(hipMalloc((void **)&d_src, (size_t)n));
-		ARX_HIP_CHECK(hipMalloc((void **)&d_out, (size_t)(total ? total : 1)));
-		ARX_HIP_CHECK(hipMalloc((void **)&d_rows, sizeof(arx::InfRow) * (size_t)nb));
-		ARX_HIP_CHECK(hipMalloc((void **)&d_status, 4 * ((size_t)nb + 2)));
+		arx::select_device(device, "no such HIP device");
+		arx::DevBuf src_buf((size_t)n), out_buf((size_t)total), rows_buf(sizeof(arx::InfRow) * (size_t)nb), status_buf(4 * ((size_t)nb + 2));
+		uint8_t *d_src = src_buf.as<uint8_t>(), *d_out = out_buf.as<uint8_t>();
+		arx::InfRow *d_rows = rows_buf.as<arx::InfRow>();
+		int32_t *d_status = status_buf.as<int32_t>(); // nb statuses, then the two counts
 		ARX_HIP_CHECK(hipMemcpy(d_src, src, (size_t)n, hipMemcpyHostToDevice));
 		ARX_HIP_CHECK(hipMemcpy(d_rows, rows.data(), sizeof(arx::InfRow) * (size_t)nb, hipMemcpyHostToDevice));
 		if (total) ARX_HIP_CHECK(hipMemcpy(d_out, out, (size_t)total, hipMemcpyHostToDevice)); // what a bad block leaves alone comes back as it was
@@ -163,7 +158,6 @@ extern "C" int arx_selftest_inflate(int32_t device, const uint8_t *src, int64_t 
 	} catch (const std::exception &) {
 		rc = ARX_E_DEVICE;
 	}
-	(void)hipFree(d_src); (void)hipFree(d_out); (void)hipFree(d_rows); (void)hipFree(d_status);
 	return rc;
 }
 
@@ -218,6 +212,9 @@ extern "C" int arx_bam_sort_append(arx_ctx *ctx, arx_bam *h, const char *in_path
 	} catch (const arx::BsTooLarge &e) {
 		say(e.what());
 		return ARX_E_TOO_LARGE;
+	} catch (const arx::HipOutOfMemory &e) { // any buffer of the sort (hip_res.h)
+		say("the device memory does not hold the sort of this file (" + std::to_string(e.wanted >> 20) + " MiB more were asked for): use a smaller position bucket");
+		return ARX_E_TOO_LARGE;
 	} catch (const std::exception &e) {
 		say(e.what());
 		return ARX_E_DEVICE;
@@ -234,10 +231,11 @@ extern "C" int arx_selftest_bam_sort(int32_t device, const uint8_t *stream, int6
 	*n_records = 0;
 	if (stats) for (int k = 0; k < arx::BS_N_STATS; ++k) stats[k] = 0;
 	try {
-		arx::BsStreamScope scope(device);
-		arx::BsHipDrv drv; drv.st = scope.st; drv.timed = (mode & ARX_SORT_TIMED) != 0;
-		arx::BsBuf d_s;
-		d_s.alloc((size_t)n_bytes);
+		arx::select_device(device, arx::BS_NO_DEVICE);
+		arx::Stream st;
+		st.create();
+		arx::BsHipDrv drv; drv.st = st; drv.timed = (mode & ARX_SORT_TIMED) != 0;
+		arx::DevBuf d_s((size_t)n_bytes);
 		if (n_bytes) ARX_HIP_CHECK(hipMemcpyAsync(d_s.p, stream, (size_t)n_bytes, hipMemcpyHostToDevice, drv.st));
 		const bool sort = what == ARX_SORT_COORDINATE;
 		const double t0 = arx::bs_now_us();
@@ -252,6 +250,8 @@ extern "C" int arx_selftest_bam_sort(int32_t device, const uint8_t *stream, int6
 		*n_records = N;
 		arx::bs_stats(stats, drv, N, n_bytes, 0, s.found.n_seg, s.found.right, s.found.repaired, s.found.rounds, 1);
 	} catch (const arx::BsTooLarge &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::HipOutOfMemory &) {
 		return ARX_E_TOO_LARGE;
 	} catch (const std::exception &) {
 		return ARX_E_DEVICE;

@@ -342,16 +342,20 @@ static __global__ void __launch_bounds__(64) k_selftest_wsort(int n_cases, uint6
 extern "C" int arx_selftest_wave_sort(int32_t device, int32_t n_cases, int64_t seed, int64_t *n_bad)
 {
 	if (n_cases < 0 || !n_bad) return ARX_E_ARG;
-	unsigned long long *d = nullptr, h = 0;
-	if (hipSetDevice(device) != hipSuccess || hipMalloc(&d, 8) != hipSuccess) return ARX_E_DEVICE;
+	unsigned long long h = 0;
 	int rc = ARX_OK;
-	if (hipMemset(d, 0, 8) != hipSuccess) rc = ARX_E_DEVICE;
-	if (rc == ARX_OK && n_cases > 0) {
-		try { arx::hip_launch("k_selftest_wsort", arx::k_selftest_wsort, dim3(n_cases < 4096 ? n_cases : 4096), dim3(64), 0, 0, n_cases, seed, d); } catch (const arx::HipError &) { rc = ARX_E_DEVICE; }
-		if (rc == ARX_OK && hipDeviceSynchronize() != hipSuccess) rc = ARX_E_DEVICE;
+	try {
+		ARX_HIP_CHECK(hipSetDevice(device));
+		arx::DevBuf d(8);
+		ARX_HIP_CHECK(hipMemset(d.p, 0, 8));
+		if (n_cases > 0) {
+			arx::hip_launch("k_selftest_wsort", arx::k_selftest_wsort, dim3(n_cases < 4096 ? n_cases : 4096), dim3(64), 0, 0, n_cases, seed, d.as<unsigned long long>());
+			ARX_HIP_CHECK(hipDeviceSynchronize());
+		}
+		ARX_HIP_CHECK(hipMemcpy(&h, d.p, 8, hipMemcpyDeviceToHost));
+	} catch (const arx::HipError &) {
+		rc = ARX_E_DEVICE;
 	}
-	if (rc == ARX_OK && hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = ARX_E_DEVICE;
-	(void)hipFree(d);
 	*n_bad = (int64_t)h;
 	return rc;
 }

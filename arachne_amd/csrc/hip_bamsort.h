@@ -5,14 +5,14 @@
 //   k_bs_items<F>    one item of a functor of dev_bamsort.h per thread (probe, walk, verify, tally, fill: an item is a segment; keys, sizes: a
 //                    record; gather: one of the BS_GATHER_LANES lanes of a record), started through hip_launch under the functor's name
 // The key sort is rocprim::radix_sort_pairs over the key bits that can differ (bs_key_bits), the prefix sums are rocprim's scan.
+// The stream, every buffer and rocprim's scratch are owners of hip_res.h (Stream, DevBuf, DevScratch; dev_sort_pairs, dev_two_pass, dev_get); a
+// hipMalloc that finds no room (HipOutOfMemory) becomes ARX_E_TOO_LARGE where arx_bgzf.hip catches.
 //
 // Memory of a sort (all of the file at once): the compressed file (freed once inflated), the inflated stream, the sorted stream, and per record
 // 48 bytes of offsets, sizes, keys and values -- about 2.3 times the inflated size at the 300 to 400 bytes of a short-read record.  What does
 // not fit is ARX_E_TOO_LARGE: the remedy is a smaller position bucket.  Copy mode holds one slab of whole BGZF blocks at a time.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <stdio.h>
 #include <string.h>
 #include <zlib.h>
@@ -21,7 +21,7 @@
 #include <string>
 #include <vector>
 #include "../../include/arachne_amd.h"
-#include "hip_launch.h"
+#include "hip_res.h"
 #include "bgzf_walk.h"
 #include "dev_bamsort.h"
 #include "bam_sink.h"
@@ -44,24 +44,6 @@ template <class F> static __global__ void __launch_bounds__(256) k_bs_items(F f,
 
 struct BsTooLarge : std::runtime_error { using std::runtime_error::runtime_error; };
 
-struct BsBuf { // device memory with a scope
-	void *p = nullptr; size_t bytes = 0;
-	BsBuf() {}
-	BsBuf(const BsBuf &) = delete;
-	BsBuf &operator=(const BsBuf &) = delete;
-	void alloc(size_t n)
-	{
-		release();
-		const hipError_t e = hipMalloc(&p, n ? n : 1);
-		if (e == hipErrorOutOfMemory) { p = nullptr; (void)hipGetLastError(); throw BsTooLarge("the device memory does not hold the sort of this file (" + std::to_string(n >> 20) + " MiB more were asked for): use a smaller position bucket"); }
-		ARX_HIP_CHECK(e);
-		bytes = n;
-	}
-	void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-	~BsBuf() { release(); }
-	template <class T> T *as() const { return (T *)p; }
-};
-
 inline double bs_now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // dev_bamsort.h's driver on a stream
@@ -69,7 +51,7 @@ struct BsHipDrv {
 	hipStream_t st = nullptr;
 	bool timed = false;          // wait for every launch and book its time under its phase
 	double us[BS_N_STATS] = {0};
-	BsBuf tmp;
+	DevScratch tmp;
 
 	static int phase_of(const char *nm)
 	{
@@ -96,56 +78,26 @@ struct BsHipDrv {
 		if (grid > 0x7fffffff) throw BsTooLarge("too many items for one launch: use a smaller position bucket");
 		booked(nm, [&]() { hip_launch({"k_bs_items", nm}, k_bs_items<F>, dim3((unsigned)grid), dim3(256), 0, st, f, n); });
 	}
-	void *scratch(size_t bytes) { if (bytes > tmp.bytes) tmp.alloc(bytes + (bytes >> 2)); return tmp.p; }
 	void scan(const int64_t *in, int64_t *out, int64_t n)
 	{
 		put(&out[0], 0);
 		if (n <= 0) return;
-		booked("bs_scan", [&]() {
-			size_t tb = 0;
-			ARX_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb, in, out + 1, (size_t)n, rocprim::plus<int64_t>(), st));
-			void *t = scratch(tb);
-			ARX_HIP_CHECK(rocprim::inclusive_scan(t, tb, in, out + 1, (size_t)n, rocprim::plus<int64_t>(), st));
-		});
+		booked("bs_scan", [&]() { dev_two_pass(tmp, "rocprim::inclusive_scan", [&](void *t, size_t &tb) { return rocprim::inclusive_scan(t, tb, in, out + 1, (size_t)n, rocprim::plus<int64_t>(), st); }); });
 	}
-	int64_t get(const int64_t *p)
-	{
-		int64_t v = 0;
-		ARX_HIP_CHECK(hipMemcpyAsync(&v, p, 8, hipMemcpyDeviceToHost, st));
-		ARX_HIP_CHECK(hipStreamSynchronize(st));
-		return v;
-	}
+	int64_t get(const int64_t *p) { return dev_get(p, st); }
 	void put(int64_t *p, int64_t v)
 	{
 		ARX_HIP_CHECK(hipMemcpyAsync(p, &v, 8, hipMemcpyHostToDevice, st));
-		ARX_HIP_CHECK(hipStreamSynchronize(st)); // v leaves scope
+		ARX_HIP_CHECK(hipStreamSynchronize(st)); // v leaves scope when this returns: the copy has read it by then
 	}
-	void sort_pairs(const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout, int64_t n, int bits)
-	{
-		booked("bs_sort", [&]() {
-			size_t tb = 0;
-			ARX_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, (size_t)n, 0u, (unsigned)bits, st));
-			void *t = scratch(tb);
-			ARX_HIP_CHECK(rocprim::radix_sort_pairs(t, tb, kin, kout, vin, vout, (size_t)n, 0u, (unsigned)bits, st));
-		});
-	}
+	void sort_pairs(const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout, int64_t n, int bits) { booked("bs_sort", [&]() { dev_sort_pairs(tmp, kin, kout, vin, vout, (size_t)n, bits, st); }); }
 };
 
-struct BsStreamScope { // a stream of the call's own
-	hipStream_t st = nullptr;
-	explicit BsStreamScope(int device)
-	{
-		int n = 0;
-		if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) throw HipError("no such HIP device: the BAM sort runs on the GPU (there is no CPU fallback)");
-		ARX_HIP_CHECK(hipSetDevice(device));
-		ARX_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-	}
-	~BsStreamScope() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
-};
+constexpr const char *BS_NO_DEVICE = "no such HIP device: the BAM sort runs on the GPU (there is no CPU fallback)"; // select_device's text for the sort's two entries
 
 // the device side of one closed stream: discovery, then (sort) keys, sort and gather.  d_s[0, n): the bytes, records from hdr on
 struct BsSorted {
-	BsBuf segs, rec_off, mem, out; // out: the sorted records (n - hdr bytes); rec_off: where the records start in d_s
+	DevBuf segs, rec_off, mem, out; // out: the sorted records (n - hdr bytes); rec_off: where the records start in d_s
 	BsFound found{};
 	BsSortMem m{};
 	// BS_OK or BS_E_CHAIN; with sort the sorted stream is complete on the stream when this returns
@@ -289,8 +241,10 @@ template <class WriteDev> int bs_sort_append(int device, BamSink *w, bool device
 	cut.push_back(nb);
 	const int64_t n_slabs = (int64_t)cut.size() - 1;
 
-	BsStreamScope scope(device);
-	BsHipDrv drv; drv.st = scope.st; drv.timed = (mode & ARX_SORT_TIMED) != 0;
+	select_device(device, BS_NO_DEVICE);
+	Stream st; // the call's own; declared before the buffers, so that it has ended when they are freed
+	st.create();
+	BsHipDrv drv; drv.st = st; drv.timed = (mode & ARX_SORT_TIMED) != 0;
 	drv.us[BS_T_READ] = bs_now_us() - t_begin;
 	if (sort) {
 		size_t free_b = 0, total_b = 0;
@@ -301,7 +255,7 @@ template <class WriteDev> int bs_sort_append(int device, BamSink *w, bool device
 			return ARX_E_TOO_LARGE;
 		}
 	}
-	BsBuf d_comp, d_rows, d_status, d_out, segs;
+	DevBuf d_comp, d_rows, d_status, d_out, segs;
 	BsCarry carry = {hdr, 0, 0, 0, 0, 0};
 	uint8_t keep_bytes[BS_SLAB_KEEP] = {0, 0, 0};
 	// one slab inflated into d_out behind the `keep` bytes of the one before -> false: a block does not inflate

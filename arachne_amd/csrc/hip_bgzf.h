@@ -5,7 +5,7 @@
 //   k_bgzf_frame     one workgroup per block: the 18-byte BGZF header, the stream, CRC-32 and ISIZE, packed back to back in file order (the
 //                    bytes BamSink::deflate_block frames a block with); a block's offset is the sum of the framed sizes in front of it
 //
-// DeviceBgzf owns two streams, two page-locked staging pairs and the device buffers of two groups of at most GROUP blocks, allocated once
+// DeviceBgzf owns (through the types of hip_res.h) two streams, two page-locked staging pairs and the device buffers of two groups of at most GROUP blocks, allocated once
 // (about 64 MB of page-locked and 100 MB of device memory: one per device for the life of the process, see arx_bgzf.hip).
 // run() takes the blocks of one flush in groups: while group g is uploaded, compressed, framed and its sizes come back, the framed bytes of
 // group g - 1 are downloaded and written.  Blocks reach the sink in order.  run_device() is run() for a stream that is in device memory already
@@ -17,7 +17,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
-#include "hip_launch.h"
+#include "hip_res.h"
 #include "dev_bgzf.h"
 #include "hip_block.h"
 #include "bam_sink.h"
@@ -77,57 +77,34 @@ struct DeviceBgzf : BlockCompressor {
 	static constexpr int GROUP = 256; // blocks of a group: 16 MiB each way
 	int dev = -1, n_cu = 256, grid = 0;
 	bool ready = false;
-	hipStream_t st[2] = {nullptr, nullptr};
-	hipEvent_t ev_meta[2] = {nullptr, nullptr}, ev_pay[2] = {nullptr, nullptr};
-	uint8_t *h_in[2] = {nullptr, nullptr}, *h_out[2] = {nullptr, nullptr};
-	uint32_t *h_meta[2] = {nullptr, nullptr};
-	uint8_t *d_in[2] = {nullptr, nullptr}, *d_packed[2] = {nullptr, nullptr};
-	uint32_t *d_slices[2] = {nullptr, nullptr}, *d_meta[2] = {nullptr, nullptr};
-	uint16_t *d_tok[2] = {nullptr, nullptr};
+	// what it holds (hip_res.h).  The streams first: members die in reverse order, so a stream has ended (its destructor waits) after nothing but
+	// its own events and buffers were freed, and those are only freed once the flush that used them has returned
+	Stream st[2];
+	Event ev_meta[2], ev_pay[2];
+	PinnedBuf h_in[2], h_out[2], h_meta[2];
+	DevBuf d_in[2], d_slices[2], d_packed[2], d_meta[2], d_tok[2];
 	int64_t n_form[3] = {0, 0, 0}; // blocks that went out stored, fixed, dynamic
 	std::mutex mu;                 // the writers of one device share one compressor (arx_bgzf.hip): a flush at a time
 
 	void init(int device)
 	{
-		int n = 0;
-		if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw std::runtime_error("no HIP device visible: the device BAM sink needs an MI355X (there is no CPU fallback)");
-		if (device < 0 || device >= n) throw std::runtime_error("device index out of range");
+		select_device(device, "no HIP device visible: the device BAM sink needs an MI355X (there is no CPU fallback)", "device index out of range");
 		dev = device;
-		ARX_HIP_CHECK(hipSetDevice(dev));
 		hipDeviceProp_t p;
 		ARX_HIP_CHECK(hipGetDeviceProperties(&p, dev));
 		n_cu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
 		grid = n_cu < GROUP ? n_cu : GROUP; // one workgroup per CU: its LDS does not leave room for two
 		ARX_HIP_CHECK(hipFuncSetAttribute((const void *)k_bgzf_deflate, hipFuncAttributeMaxDynamicSharedMemorySize, BGZF_WORK_BYTES));
 		for (int s = 0; s < 2; ++s) {
-			ARX_HIP_CHECK(hipStreamCreateWithFlags(&st[s], hipStreamNonBlocking));
-			ARX_HIP_CHECK(hipEventCreateWithFlags(&ev_meta[s], hipEventDisableTiming));
-			ARX_HIP_CHECK(hipEventCreateWithFlags(&ev_pay[s], hipEventDisableTiming));
-			ARX_HIP_CHECK(hipHostMalloc((void **)&h_in[s], (size_t)GROUP * BGZF_IN, hipHostMallocDefault));
-			ARX_HIP_CHECK(hipHostMalloc((void **)&h_out[s], (size_t)GROUP * BGZF_OUT_SLICE, hipHostMallocDefault));
-			ARX_HIP_CHECK(hipHostMalloc((void **)&h_meta[s], (size_t)GROUP * 16, hipHostMallocDefault));
-			ARX_HIP_CHECK(hipMalloc((void **)&d_in[s], (size_t)GROUP * BGZF_IN));
-			ARX_HIP_CHECK(hipMalloc((void **)&d_slices[s], (size_t)GROUP * BGZF_OUT_SLICE));
-			ARX_HIP_CHECK(hipMalloc((void **)&d_packed[s], (size_t)GROUP * BGZF_OUT_SLICE));
-			ARX_HIP_CHECK(hipMalloc((void **)&d_meta[s], (size_t)GROUP * 16));
-			ARX_HIP_CHECK(hipMalloc((void **)&d_tok[s], (size_t)grid * BGZF_TOK_ROW * 2));
+			st[s].create();
+			ev_meta[s].create(hipEventDisableTiming); ev_pay[s].create(hipEventDisableTiming);
+			h_in[s].alloc((size_t)GROUP * BGZF_IN); h_out[s].alloc((size_t)GROUP * BGZF_OUT_SLICE); h_meta[s].alloc((size_t)GROUP * 16);
+			d_in[s].alloc((size_t)GROUP * BGZF_IN); d_slices[s].alloc((size_t)GROUP * BGZF_OUT_SLICE); d_packed[s].alloc((size_t)GROUP * BGZF_OUT_SLICE);
+			d_meta[s].alloc((size_t)GROUP * 16); d_tok[s].alloc((size_t)grid * BGZF_TOK_ROW * 2);
 		}
 		ready = true;
 	}
-	~DeviceBgzf() override
-	{
-		if (dev >= 0) (void)hipSetDevice(dev);
-		for (int s = 0; s < 2; ++s) {
-			if (st[s]) (void)hipStreamSynchronize(st[s]);
-			if (h_in[s]) (void)hipHostFree(h_in[s]);
-			if (h_out[s]) (void)hipHostFree(h_out[s]);
-			if (h_meta[s]) (void)hipHostFree(h_meta[s]);
-			(void)hipFree(d_in[s]); (void)hipFree(d_slices[s]); (void)hipFree(d_packed[s]); (void)hipFree(d_meta[s]); (void)hipFree(d_tok[s]);
-			if (ev_meta[s]) (void)hipEventDestroy(ev_meta[s]);
-			if (ev_pay[s]) (void)hipEventDestroy(ev_pay[s]);
-			if (st[s]) (void)hipStreamDestroy(st[s]);
-		}
-	}
+	~DeviceBgzf() override { if (dev >= 0) (void)hipSetDevice(dev); } // (the members are this device's)
 
 	// group g of the flush: its input into d_in[s] (stage(s, b0, bytes) enqueues that on st[s]), the two kernels, the sizes on their way back
 	template <class Stage> void submit(size_t total, size_t g, Stage stage)
@@ -136,9 +113,9 @@ struct DeviceBgzf : BlockCompressor {
 		const size_t b0 = g * GROUP * (size_t)BGZF_IN, bytes = total - b0 < (size_t)GROUP * BGZF_IN ? total - b0 : (size_t)GROUP * BGZF_IN;
 		const int nb = (int)((bytes + BGZF_IN - 1) / BGZF_IN);
 		stage(s, b0, bytes);
-		hip_launch("k_bgzf_deflate", k_bgzf_deflate, dim3(nb < grid ? nb : grid), dim3(BGZF_LANES), BGZF_WORK_BYTES, st[s], d_in[s], bytes, nb, d_tok[s], d_slices[s], d_meta[s]);
-		hip_launch("k_bgzf_frame", k_bgzf_frame, dim3(nb), dim3(256), 0, st[s], d_slices[s], d_meta[s], nb, d_packed[s]);
-		ARX_HIP_CHECK(hipMemcpyAsync(h_meta[s], d_meta[s], (size_t)nb * 16, hipMemcpyDeviceToHost, st[s]));
+		hip_launch("k_bgzf_deflate", k_bgzf_deflate, dim3(nb < grid ? nb : grid), dim3(BGZF_LANES), BGZF_WORK_BYTES, st[s], d_in[s].as<uint8_t>(), bytes, nb, d_tok[s].as<uint16_t>(), d_slices[s].as<uint32_t>(), d_meta[s].as<uint32_t>());
+		hip_launch("k_bgzf_frame", k_bgzf_frame, dim3(nb), dim3(256), 0, st[s], d_slices[s].as<uint32_t>(), d_meta[s].as<uint32_t>(), nb, d_packed[s].as<uint8_t>());
+		ARX_HIP_CHECK(hipMemcpyAsync(h_meta[s].p, d_meta[s].p, (size_t)nb * 16, hipMemcpyDeviceToHost, st[s]));
 		ARX_HIP_CHECK(hipEventRecord(ev_meta[s], st[s]));
 	}
 	// the sizes of group g are known: its framed bytes on their way back -> their number
@@ -148,11 +125,11 @@ struct DeviceBgzf : BlockCompressor {
 		ARX_HIP_CHECK(hipEventSynchronize(ev_meta[s]));
 		size_t bytes = 0;
 		for (int b = 0; b < nb; ++b) {
-			const uint32_t *m = h_meta[s] + 4 * (size_t)b;
+			const uint32_t *m = h_meta[s].as<uint32_t>() + 4 * (size_t)b;
 			if (m[0] > 5u + BGZF_IN || m[2] > 2u) throw std::runtime_error("the BGZF kernel reported an impossible block");
 			bytes += m[0] + 26; ++n_form[m[2]];
 		}
-		ARX_HIP_CHECK(hipMemcpyAsync(h_out[s], d_packed[s], bytes, hipMemcpyDeviceToHost, st[s]));
+		ARX_HIP_CHECK(hipMemcpyAsync(h_out[s].p, d_packed[s].p, bytes, hipMemcpyDeviceToHost, st[s]));
 		ARX_HIP_CHECK(hipEventRecord(ev_pay[s], st[s]));
 		return bytes;
 	}
@@ -168,7 +145,7 @@ struct DeviceBgzf : BlockCompressor {
 		auto drain = [&](size_t g) {
 			const size_t bytes = fetch(g, blocks_of(g));
 			ARX_HIP_CHECK(hipEventSynchronize(ev_pay[g & 1]));
-			sink(h_out[g & 1], bytes);
+			sink(h_out[g & 1].as<uint8_t>(), bytes);
 		};
 		try {
 			submit(total, 0, stage);
@@ -183,8 +160,8 @@ struct DeviceBgzf : BlockCompressor {
 	template <class Sink> void compress(const uint8_t *src, size_t total, Sink sink)
 	{
 		compress_from(total, [&](int s, size_t b0, size_t bytes) {
-			memcpy(h_in[s], src + b0, bytes);
-			ARX_HIP_CHECK(hipMemcpyAsync(d_in[s], h_in[s], bytes, hipMemcpyHostToDevice, st[s]));
+			memcpy(h_in[s].p, src + b0, bytes);
+			ARX_HIP_CHECK(hipMemcpyAsync(d_in[s].p, h_in[s].p, bytes, hipMemcpyHostToDevice, st[s]));
 		}, sink);
 	}
 
@@ -219,10 +196,10 @@ struct DeviceBgzf : BlockCompressor {
 				size_t c = 0; // bytes of the group that come from the carry (group 0 only: the carry is shorter than a block)
 				if (b0 < n_carry) {
 					c = n_carry - b0 < bytes ? n_carry - b0 : bytes;
-					memcpy(h_in[s], carry + b0, c);
-					ARX_HIP_CHECK(hipMemcpyAsync(d_in[s], h_in[s], c, hipMemcpyHostToDevice, st[s]));
+					memcpy(h_in[s].p, carry + b0, c);
+					ARX_HIP_CHECK(hipMemcpyAsync(d_in[s].p, h_in[s].p, c, hipMemcpyHostToDevice, st[s]));
 				}
-				if (bytes > c) ARX_HIP_CHECK(hipMemcpyAsync(d_in[s] + c, d_stream + (b0 + c - n_carry), bytes - c, hipMemcpyDeviceToDevice, st[s]));
+				if (bytes > c) ARX_HIP_CHECK(hipMemcpyAsync(d_in[s].as<uint8_t>() + c, d_stream + (b0 + c - n_carry), bytes - c, hipMemcpyDeviceToDevice, st[s]));
 			}, [&](const uint8_t *p, size_t n) {
 				if (ok && fwrite(p, 1, n, f) != n) { ok = false; error = "write failed"; }
 				if (ok) bytes_out += (int64_t)n;
@@ -235,9 +212,9 @@ struct DeviceBgzf : BlockCompressor {
 			if (keep_d) {
 				if (keep_d >= (size_t)BGZF_IN) throw std::runtime_error("the device sink's tail is a whole block");
 				ARX_HIP_CHECK(hipSetDevice(dev));
-				ARX_HIP_CHECK(hipMemcpyAsync(h_in[0], d_stream + d0, keep_d, hipMemcpyDeviceToHost, st[0]));
+				ARX_HIP_CHECK(hipMemcpyAsync(h_in[0].p, d_stream + d0, keep_d, hipMemcpyDeviceToHost, st[0]));
 				ARX_HIP_CHECK(hipStreamSynchronize(st[0]));
-				tail.insert(tail.end(), h_in[0], h_in[0] + keep_d);
+				tail.insert(tail.end(), h_in[0].as<uint8_t>(), h_in[0].as<uint8_t>() + keep_d);
 			}
 			return true;
 		} catch (const std::exception &e) {

@@ -24,42 +24,22 @@
 //      checked to be its inverse: a wrong order cannot reach the files.
 //
 // Memory: 16 bytes per suffix (SA + rank) + 24 bytes per chunk element + 40 per slice element; GRCh38 (6.2 G suffixes): ~125 GB.
+// Every buffer, the rocprim scratch and the emit's page-locked staging are owners of hip_res.h: whatever leaves the build early frees them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 #include <chrono>
 #include <stdexcept>
 #include <string>
 #include <vector>
-#include "hip_launch.h"
+#include "hip_res.h"
 #include "switches.h"
 
 namespace arx {
 namespace gpuidx {
-
-struct DevBuf {
-	void *p = nullptr; size_t bytes = 0;
-	DevBuf() {}
-	explicit DevBuf(size_t b) { alloc(b); }
-	DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
-	void alloc(size_t b)
-	{
-		release(); bytes = b ? b : 8;
-		if (hipMalloc(&p, bytes) != hipSuccess) {
-			size_t fr = 0, to = 0; (void)hipMemGetInfo(&fr, &to);
-			p = nullptr;
-			throw std::runtime_error("index build: out of device memory (wanted " + std::to_string(bytes >> 20) + " MiB, " + std::to_string(fr >> 20) + " of " + std::to_string(to >> 20) + " MiB free)");
-		}
-	}
-	void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-	~DevBuf() { release(); }
-	template <class T> T *as() const { return (T *)p; }
-};
 
 typedef unsigned long long u64;
 constexpr int BUCKET_BASES = 12;
@@ -252,77 +232,40 @@ struct Timer {
 	double lap() { auto t = std::chrono::steady_clock::now(); double s = std::chrono::duration<double>(t - t0).count(); t0 = t; return s; }
 };
 
-struct Scratch { // rocprim temporary storage, grown on demand
-	DevBuf buf;
-	void *get(size_t bytes) { if (bytes > buf.bytes) buf.alloc(bytes + (bytes >> 2)); return buf.p; }
-};
-
-inline void scan_max(Scratch &sc, u64 *data, u64 cnt, hipStream_t st)
-{
-	size_t tb = 0;
-	ARX_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb, data, data, (size_t)cnt, MaxOp(), st));
-	void *tmp = sc.get(tb);
-	ARX_HIP_CHECK(rocprim::inclusive_scan(tmp, tb, data, data, (size_t)cnt, MaxOp(), st));
-}
-inline void scan_incl_sum(Scratch &sc, u64 *data, u64 cnt, hipStream_t st)
-{
-	size_t tb = 0;
-	ARX_HIP_CHECK(rocprim::inclusive_scan(nullptr, tb, data, data, (size_t)cnt, rocprim::plus<u64>(), st));
-	void *tmp = sc.get(tb);
-	ARX_HIP_CHECK(rocprim::inclusive_scan(tmp, tb, data, data, (size_t)cnt, rocprim::plus<u64>(), st));
-}
-inline void scan_excl_sum(Scratch &sc, const u64 *in, u64 *out, u64 cnt, hipStream_t st)
-{
-	size_t tb = 0;
-	ARX_HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, in, out, (u64)0, (size_t)cnt, rocprim::plus<u64>(), st));
-	void *tmp = sc.get(tb);
-	ARX_HIP_CHECK(rocprim::exclusive_scan(tmp, tb, in, out, (u64)0, (size_t)cnt, rocprim::plus<u64>(), st));
-}
-inline void sort_pairs(Scratch &sc, const u64 *kin, u64 *kout, const u64 *vin, u64 *vout, u64 cnt, int bits, hipStream_t st)
-{
-	size_t tb = 0;
-	if (bits < 1) bits = 1;
-	if (bits > 64) bits = 64;
-	ARX_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, (size_t)cnt, 0u, (unsigned)bits, st));
-	void *tmp = sc.get(tb);
-	ARX_HIP_CHECK(rocprim::radix_sort_pairs(tmp, tb, kin, kout, vin, vout, (size_t)cnt, 0u, (unsigned)bits, st));
-}
-inline u64 read_u64(const u64 *d, hipStream_t st)
-{
-	u64 v = 0;
-	ARX_HIP_CHECK(hipMemcpyAsync(&v, d, 8, hipMemcpyDeviceToHost, st));
-	ARX_HIP_CHECK(hipStreamSynchronize(st));
-	return v;
-}
+inline void scan_max(DevScratch &sc, u64 *data, u64 cnt, hipStream_t st) { dev_two_pass(sc, "rocprim::inclusive_scan", [&](void *t, size_t &tb) { return rocprim::inclusive_scan(t, tb, data, data, (size_t)cnt, MaxOp(), st); }); }
+inline void scan_incl_sum(DevScratch &sc, u64 *data, u64 cnt, hipStream_t st) { dev_two_pass(sc, "rocprim::inclusive_scan", [&](void *t, size_t &tb) { return rocprim::inclusive_scan(t, tb, data, data, (size_t)cnt, rocprim::plus<u64>(), st); }); }
+inline void scan_excl_sum(DevScratch &sc, const u64 *in, u64 *out, u64 cnt, hipStream_t st) { dev_two_pass(sc, "rocprim::exclusive_scan", [&](void *t, size_t &tb) { return rocprim::exclusive_scan(t, tb, in, out, (u64)0, (size_t)cnt, rocprim::plus<u64>(), st); }); }
 inline int bits_for(u64 x) { int b = 0; while (b < 64 && (x >> b)) ++b; return b; } // smallest b with x < 2^b
 
 // device -> file through two pinned buffers
 inline void stream_to_file(FILE *o, const void *dev, size_t bytes, hipStream_t st)
 {
 	const size_t CH = (size_t)64 << 20;
-	void *pin[2] = {nullptr, nullptr};
-	ARX_HIP_CHECK(hipHostMalloc(&pin[0], CH, hipHostMallocDefault));
-	ARX_HIP_CHECK(hipHostMalloc(&pin[1], CH, hipHostMallocDefault));
-	hipEvent_t ev[2];
-	ARX_HIP_CHECK(hipEventCreate(&ev[0])); ARX_HIP_CHECK(hipEventCreate(&ev[1]));
+	PinnedBuf pin[2] = {PinnedBuf(CH), PinnedBuf(CH)};
+	Event ev[2] = {Event(hipEventDefault), Event(hipEventDefault)};
 	size_t done = 0, issued = 0; int k = 0;
 	size_t len[2] = {0, 0};
+	auto fetch = [&](int b) { // the next chunk on its way into pin[b]
+		len[b] = bytes - issued < CH ? bytes - issued : CH;
+		ARX_HIP_CHECK(hipMemcpyAsync(pin[b].p, (const char *)dev + issued, len[b], hipMemcpyDeviceToHost, st));
+		ARX_HIP_CHECK(hipEventRecord(ev[b], st));
+		issued += len[b];
+	};
 	bool ok = true;
-	if (bytes) { len[0] = bytes < CH ? bytes : CH; (void)hipMemcpyAsync(pin[0], dev, len[0], hipMemcpyDeviceToHost, st); (void)hipEventRecord(ev[0], st); issued = len[0]; }
-	while (done < bytes) {
-		const int nx = k ^ 1;
-		if (issued < bytes) { // next chunk flies while this one is written
-			len[nx] = bytes - issued < CH ? bytes - issued : CH;
-			(void)hipMemcpyAsync(pin[nx], (const char *)dev + issued, len[nx], hipMemcpyDeviceToHost, st); (void)hipEventRecord(ev[nx], st);
-			issued += len[nx];
+	try {
+		if (bytes) fetch(0);
+		while (done < bytes) {
+			const int nx = k ^ 1;
+			if (issued < bytes) fetch(nx); // flies while this one is written
+			if (hipEventSynchronize(ev[k]) != hipSuccess) { ok = false; break; }
+			if (fwrite(pin[k].p, 1, len[k], o) != len[k]) { ok = false; break; }
+			done += len[k]; k = nx;
 		}
-		if (hipEventSynchronize(ev[k]) != hipSuccess) { ok = false; break; }
-		if (fwrite(pin[k], 1, len[k], o) != len[k]) { ok = false; break; }
-		done += len[k]; k = nx;
+	} catch (...) {
+		(void)hipStreamSynchronize(st); // no copy into the buffers is in flight when they are freed
+		throw;
 	}
 	(void)hipStreamSynchronize(st);
-	(void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
-	(void)hipHostFree(pin[0]); (void)hipHostFree(pin[1]);
 	if (!ok) throw std::runtime_error("index build: writing the index files failed");
 }
 
@@ -344,7 +287,7 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 		if (sw.device >= 0) ARX_HIP_CHECK(hipSetDevice(sw.device));
 		hipStream_t st = 0; // the null stream: this is a stand-alone tool step, not part of a batch
 		Timer tm;
-		Scratch sc;
+		DevScratch sc;
 		// 1. text
 		const u64 n_tw = (n + 31) / 32 + 2;
 		DevBuf dT(n_tw * 8);
@@ -374,8 +317,7 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 		S.s_bucket = tm.lap();
 		// 3. chunks of whole buckets
 		struct Seg { DevBuf pos, sa; u64 m = 0; };
-		std::vector<Seg *> segs;
-		struct SegGuard { std::vector<Seg *> &v; ~SegGuard() { for (Seg *s : v) delete s; } } seg_guard{segs};
+		std::vector<Seg> segs;
 		u64 m_total = 0;
 		{
 			u64 biggest = 0;
@@ -392,17 +334,16 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 				++S.n_chunks;
 				u64 *k1 = dk1.as<u64>(), *k2 = dk2.as<u64>(), *v2 = dv2.as<u64>();
 				hip_launch("k_keys", k_keys, grid_for(cnt), dim3(256), 0, st, T, SA + base, cnt, k1);
-				sort_pairs(sc, k1, k2, SA + base, v2, cnt, 64, st);
+				dev_sort_pairs(sc, k1, k2, SA + base, v2, (size_t)cnt, 64, st);
 				hip_launch("k_heads", k_heads, grid_for(cnt), dim3(256), 0, st, k2, cnt, base, k1);
 				scan_max(sc, k1, cnt, st);                          // k1 = rank
 				hip_launch("k_chunk_apply", k_chunk_apply, grid_for(cnt), dim3(256), 0, st, v2, k1, cnt, base, SA, ISA, k2); // k2 = flag
-				const u64 last_flag = read_u64(k2 + cnt - 1, st);
+				const u64 last_flag = dev_get(k2 + cnt - 1, st);
 				scan_excl_sum(sc, k2, k1, cnt, st);                 // k1 = offsets
-				const u64 m = read_u64(k1 + cnt - 1, st) + last_flag;
+				const u64 m = dev_get(k1 + cnt - 1, st) + last_flag;
 				if (m) {
-					Seg *sg = new Seg(); segs.push_back(sg);
-					sg->m = m; sg->pos.alloc(m * 8); sg->sa.alloc(m * 8);
-					hip_launch("k_compact", k_compact, grid_for(cnt), dim3(256), 0, st, k2, k1, cnt, base, v2, sg->pos.as<u64>(), sg->sa.as<u64>());
+					segs.push_back(Seg{DevBuf(m * 8), DevBuf(m * 8), m});
+					hip_launch("k_compact", k_compact, grid_for(cnt), dim3(256), 0, st, k2, k1, cnt, base, v2, segs.back().pos.as<u64>(), segs.back().sa.as<u64>());
 					m_total += m;
 				}
 				ARX_HIP_CHECK(hipStreamSynchronize(st));
@@ -418,14 +359,13 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 			if (m) {
 				upos[0].alloc(m * 8); usa[0].alloc(m * 8);
 				u64 o = 0;
-				for (Seg *sg : segs) {
-					ARX_HIP_CHECK(hipMemcpyAsync(upos[0].as<u64>() + o, sg->pos.p, sg->m * 8, hipMemcpyDeviceToDevice, st));
-					ARX_HIP_CHECK(hipMemcpyAsync(usa[0].as<u64>() + o, sg->sa.p, sg->m * 8, hipMemcpyDeviceToDevice, st));
-					o += sg->m;
+				for (const Seg &sg : segs) {
+					ARX_HIP_CHECK(hipMemcpyAsync(upos[0].as<u64>() + o, sg.pos.p, sg.m * 8, hipMemcpyDeviceToDevice, st));
+					ARX_HIP_CHECK(hipMemcpyAsync(usa[0].as<u64>() + o, sg.sa.p, sg.m * 8, hipMemcpyDeviceToDevice, st));
+					o += sg.m;
 				}
 				ARX_HIP_CHECK(hipStreamSynchronize(st));
 			}
-			for (Seg *sg : segs) delete sg;
 			segs.clear();
 			for (u64 h = 32; m > 0; h <<= 1) {
 				if (h > 2 * n + 64) return "index build: prefix doubling did not converge (internal error)";
@@ -464,13 +404,14 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 					hip_launch("k_head_flags", k_head_flags, grid_for(cnt), dim3(256), 0, st, r + a, cnt, A);
 					scan_incl_sum(sc, A, cnt, st);                                                     // A = group number (1-based)
 					hip_launch("k_comp_keys", k_comp_keys, grid_for(cnt), dim3(256), 0, st, sa_in, A, cnt, ISA, n, h, kb, B); // B = keys
-					sort_pairs(sc, B, Cc, sa_in, D, cnt, kb + bits_for(cnt), st);                      // Cc = sorted keys, D = sorted suffixes
+					const int sort_bits = kb + bits_for(cnt); // (at least 1: kb is)
+					dev_sort_pairs(sc, B, Cc, sa_in, D, (size_t)cnt, sort_bits < 64 ? sort_bits : 64, st); // Cc = sorted keys, D = sorted suffixes
 					hip_launch("k_heads2", k_heads2, grid_for(cnt), dim3(256), 0, st, Cc, pos_in, cnt, A);
 					scan_max(sc, A, cnt, st);                                                          // A = new rank
 					hip_launch("k_round_apply", k_round_apply, grid_for(cnt), dim3(256), 0, st, D, A, pos_in, cnt, SA, ISA, B); // B = flag
-					const u64 last_flag = read_u64(B + cnt - 1, st);
+					const u64 last_flag = dev_get(B + cnt - 1, st);
 					scan_excl_sum(sc, B, Cc, cnt, st);                                                 // Cc = offsets
-					const u64 keep = read_u64(Cc + cnt - 1, st) + last_flag;
+					const u64 keep = dev_get(Cc + cnt - 1, st) + last_flag;
 					if (keep) {
 						hip_launch("k_compact2", k_compact2, grid_for(cnt), dim3(256), 0, st, B, Cc, cnt, pos_in, D, upos[nx].as<u64>() + m_next, usa[nx].as<u64>() + m_next);
 					}
@@ -488,12 +429,12 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 			DevBuf dbad(8);
 			ARX_HIP_CHECK(hipMemsetAsync(dbad.p, 0, 8, st));
 			hip_launch("k_verify", k_verify, grid_for(n), dim3(256), 0, st, T, SA, ISA, n, dbad.as<u64>());
-			const u64 bad = read_u64(dbad.as<u64>(), st);
+			const u64 bad = dev_get(dbad.as<u64>(), st);
 			if (bad) return "index build: suffix array verification failed (" + std::to_string(bad) + " rows out of order)";
 			S.s_verify = tm.lap();
 		}
 		// 5. emit
-		const u64 primary = read_u64(ISA, st);
+		const u64 primary = dev_get(ISA, st);
 		dISA.release();
 		u64 L2[5] = {0, 0, 0, 0, 0};
 		for (int c = 0; c < 4; ++c) L2[c + 1] = L2[c] + cnt_fwd[c] + cnt_fwd[3 - c];
@@ -507,9 +448,9 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 			DevBuf *cs[4] = {&c0, &c1, &c2, &c3};
 			for (int c = 0; c < 4; ++c) {
 				u64 *p = cs[c]->as<u64>();
-				const u64 last = read_u64(p + n_blocks - 1, st);
+				const u64 last = dev_get(p + n_blocks - 1, st);
 				scan_excl_sum(sc, p, p, n_blocks, st);
-				tot[c] = read_u64(p + n_blocks - 1, st) + last;
+				tot[c] = dev_get(p + n_blocks - 1, st) + last;
 				if (tot[c] != cnt_fwd[c] + cnt_fwd[3 - c]) return "index build: BWT symbol counts do not match the text (internal error)";
 			}
 			ARX_HIP_CHECK(hipMemcpyAsync(dtot.p, tot, 32, hipMemcpyHostToDevice, st));
@@ -534,6 +475,8 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 		}
 		S.s_emit = tm.lap();
 		if (verbose) fprintf(stderr, "[arx index] %d doubling rounds %.2fs, verify %.2fs, emit %.2fs\n", S.n_rounds, S.s_rounds, S.s_verify, S.s_emit);
+	} catch (const HipOutOfMemory &ex) { // hip_res.h: the free memory is what the failed request met
+		return "index build: out of device memory (wanted " + std::to_string(ex.wanted >> 20) + " MiB, " + std::to_string(ex.free_bytes >> 20) + " of " + std::to_string(ex.total_bytes >> 20) + " MiB free)";
 	} catch (const HipError &ex) { // a HIP call or a launch: hip_launch.h
 		return std::string("index build: ") + ex.what();
 	} catch (const std::exception &ex) {

@@ -1,5 +1,6 @@
 // hip_rt.h -- the HIP runtime policy of Pipeline<RT>: device memory, kernel launches on one stream (every one through start(), i.e.
-// hip_launch.h's checked primitive), device scan, per-kernel timing with HIP events.  gfx950 only.
+// hip_launch.h's checked primitive), device scan, per-kernel timing with HIP events.  gfx950 only.  What the runtime holds for itself -- its
+// streams, events, arena slabs, staging and scratch -- are owners of hip_res.h; palloc / pfree stay raw: they are the interface the host double mirrors.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -11,7 +12,7 @@
 #include <cstring>
 #include <cstdio>
 #include <climits>
-#include "hip_launch.h"
+#include "hip_res.h"
 #include "hip_sw_coop.h"
 #include "hip_block.h"
 #include "hip_nw_coop.h"
@@ -52,17 +53,15 @@ struct HipRT {
 	BatchSwitches sw; // the ARX_* environment as it was when this runtime (= its batch handle, context or device feeder) was created (switches.h)
 	static const char *name() { return "hip:gfx950"; }
 	static BwtSaFn bwt_sa_fn() { return product_bwt_sa; } // arx_index_build: the suffix sort runs in HBM
-	hipStream_t stream = 0;
+	Stream own_stream;      // declared before everything that is used on it: it is the last to go, and waits for what is on it
+	hipStream_t stream = 0; // the stream of the next launch: own_stream, or the side stream inside on_aux
 	// side stream for launches that are one wavefront's tail (the heavy-item kernels): they run beside the launches that follow on the main
 	// stream until aux_join().  Off unless sw.aux_stream
-	hipStream_t aux = 0; hipEvent_t ev_fork = 0, ev_join = 0; bool aux_pending = false;
+	Stream aux; Event ev_fork, ev_join; bool aux_pending = false;
 	template <class L> void on_aux(L f)
 	{
 		if (!sw.aux_stream) { f(); return; }
-		if (!aux) {
-			ARX_HIP_CHECK(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
-			ARX_HIP_CHECK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming)); ARX_HIP_CHECK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-		}
+		if (!aux) { aux.create(); ev_fork.create(hipEventDisableTiming); ev_join.create(hipEventDisableTiming); }
 		ARX_HIP_CHECK(hipEventRecord(ev_fork, stream)); ARX_HIP_CHECK(hipStreamWaitEvent(aux, ev_fork, 0));
 		hipStream_t main_stream = stream;
 		stream = aux;
@@ -87,7 +86,7 @@ struct HipRT {
 	int n_cu = 256;
 	bool timing = false;
 	std::map<std::string, KernelTimer> tm;
-	void *scan_tmp = 0; size_t scan_tmp_bytes = 0; int64_t *d_total = 0; void *pinned = 0;
+	DevScratch scan_tmp; DevBuf d_total; PinnedBuf pinned;
 
 	int dev = 0;
 	void bind() { (void)hipSetDevice(dev); }           // the current device is per host thread
@@ -102,52 +101,41 @@ struct HipRT {
 		hipDeviceProp_t p;
 		if (hipGetDeviceProperties(&p, device) != hipSuccess) return "hipGetDeviceProperties failed";
 		n_cu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-		if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return "hipStreamCreate failed";
-		if (hipMalloc(&d_total, 8) != hipSuccess) return "hipMalloc failed";
-		if (hipHostMalloc(&pinned, 64, hipHostMallocDefault) != hipSuccess) return "hipHostMalloc failed";
+		try { own_stream.create(); stream = own_stream; } catch (const HipError &) { return "hipStreamCreate failed"; }
+		try { d_total.alloc(8); } catch (const HipError &) { return "hipMalloc failed"; }
+		try { pinned.alloc(64); } catch (const HipError &) { return "hipHostMalloc failed"; }
 		return "";
 	}
 	~HipRT()
 	{
 		if (sw.sw_filter_stats && sw_tasks_seen) fprintf(stderr, "[arx] rescue alignments queued %lld, run after the pre-filter %lld\n", (long long)sw_tasks_seen, (long long)sw_tasks_run);
-		for (auto &sl : slabs) (void)hipFree(sl.p);
-		if (scan_tmp) hipFree(scan_tmp);
-		if (d_total) hipFree(d_total);
-		if (seed_dbg_buf) (void)hipFree(seed_dbg_buf);
-		if (pinned) (void)hipHostFree(pinned);
-		if (stage_buf) (void)hipHostFree(stage_buf);
-		for (auto &p : pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-		for (auto e : free_events) (void)hipEventDestroy(e);
-		if (aux) { hipStreamDestroy(aux); hipEventDestroy(ev_fork); hipEventDestroy(ev_join); }
-		if (stream) hipStreamDestroy(stream);
 	}
 	// Work memory of a batch comes from a per-runtime arena: slabs obtained once with hipMalloc, bump-allocated, handed back
 	// only by rewinding to a mark or resetting the whole (there is no free of a single block).  Steady state therefore has
 	// no hipMalloc/hipFree at all -- both synchronise the device and would serialise the batches that run on other streams.
-	struct Slab { char *p; size_t cap, used; };
+	struct Slab { DevBuf mem; size_t used; };
 	std::vector<Slab> slabs;
 	template <class T> T *alloc(size_t n)
 	{
 		size_t bytes = ((n ? n : 1) * sizeof(T) + 255) & ~(size_t)255;
-		for (auto &sl : slabs) if (sl.cap - sl.used >= bytes) { char *r = sl.p + sl.used; sl.used += bytes; return (T *)r; }
-		Slab sl; sl.cap = bytes > ((size_t)1 << 30) ? bytes : ((size_t)1 << 30); sl.used = bytes;
-		ARX_HIP_CHECK(hipMalloc((void **)&sl.p, sl.cap));
-		slabs.push_back(sl);
-		return (T *)sl.p;
+		for (auto &sl : slabs) if (sl.mem.bytes - sl.used >= bytes) { char *r = sl.mem.as<char>() + sl.used; sl.used += bytes; return (T *)r; }
+		slabs.push_back(Slab{DevBuf(bytes > ((size_t)1 << 30) ? bytes : ((size_t)1 << 30)), bytes});
+		return slabs.back().mem.as<T>();
 	}
 	void arena_reset() { for (auto &sl : slabs) sl.used = 0; }
 	std::vector<size_t> arena_mark() const { std::vector<size_t> m; for (auto &sl : slabs) m.push_back(sl.used); return m; }
 	void arena_rewind(const std::vector<size_t> &m) { for (size_t i = 0; i < slabs.size(); ++i) slabs[i].used = i < m.size() ? m[i] : 0; }
-	template <class T> T *palloc(size_t n) { void *p = 0; ARX_HIP_CHECK(hipMalloc(&p, (n ? n : 1) * sizeof(T))); return (T *)p; } // persistent
+	// persistent memory.  Raw hipMalloc / hipFree on purpose: the pair is the runtime interface (SimRT has the same), what it returns is its caller's to free
+	template <class T> T *palloc(size_t n) { void *p = 0; ARX_HIP_CHECK(hipMalloc(&p, (n ? n : 1) * sizeof(T))); return (T *)p; }
 	void pfree(void *p) { if (p) (void)hipFree(p); }
 	void h2d(void *d, const void *s, size_t bytes) { if (bytes) { ARX_HIP_CHECK(hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, stream)); ARX_HIP_CHECK(hipStreamSynchronize(stream)); } }
 	void d2h(void *d, const void *s, size_t bytes)
 	{
 		if (!bytes) return;
-		if (bytes <= 64 && pinned) { // small read-backs (round counters, error word, scan totals) go through pinned memory
-			ARX_HIP_CHECK(hipMemcpyAsync(pinned, s, bytes, hipMemcpyDeviceToHost, stream));
+		if (bytes <= 64 && pinned.p) { // small read-backs (round counters, error word, scan totals) go through pinned memory
+			ARX_HIP_CHECK(hipMemcpyAsync(pinned.p, s, bytes, hipMemcpyDeviceToHost, stream));
 			ARX_HIP_CHECK(hipStreamSynchronize(stream));
-			memcpy(d, pinned, bytes);
+			memcpy(d, pinned.p, bytes);
 			return;
 		}
 		ARX_HIP_CHECK(hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, stream));
@@ -156,16 +144,12 @@ struct HipRT {
 	void d2h_async(void *d, const void *s, size_t bytes) { if (bytes) ARX_HIP_CHECK(hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, stream)); } // sync() before the data is read
 	// staging for uploads: pinned host memory owned by the runtime, grown on demand.  stage() waits for the copies of the previous
 	// use (the stream has long passed them when a batch is reset after its results were fetched); h2d_staged() only enqueues.
-	void *stage_buf = 0; size_t stage_cap = 0;
+	PinnedBuf stage_buf;
 	void *stage(size_t bytes)
 	{
 		ARX_HIP_CHECK(hipStreamSynchronize(stream));
-		if (bytes > stage_cap) {
-			if (stage_buf) (void)hipHostFree(stage_buf);
-			stage_buf = 0; stage_cap = bytes + bytes / 8 + 4096;
-			ARX_HIP_CHECK(hipHostMalloc(&stage_buf, stage_cap, hipHostMallocDefault));
-		}
-		return stage_buf;
+		if (bytes > stage_buf.bytes) stage_buf.alloc(bytes + bytes / 8 + 4096);
+		return stage_buf.p;
 	}
 	void h2d_staged(void *d, const void *staged, size_t bytes) { if (bytes) ARX_HIP_CHECK(hipMemcpyAsync(d, staged, bytes, hipMemcpyHostToDevice, stream)); }
 	// Host memory the caller has page-locked (arx_host_register): copies to and from it are DMA at PCIe speed without a staging copy --
@@ -216,13 +200,13 @@ struct HipRT {
 
 	// Kernel timing: a pair of HIP events around each launch on the launch stream, recorded without blocking and
 	// resolved (hipEventElapsedTime) the next time the stream is known to be idle.
-	struct Pending { hipEvent_t a, b; const char *nm; int64_t items; };
+	struct Pending { Event a, b; const char *nm; int64_t items; };
 	std::vector<Pending> pending;
-	std::vector<hipEvent_t> free_events;
-	hipEvent_t get_event()
+	std::vector<Event> free_events;
+	Event get_event()
 	{
-		if (!free_events.empty()) { hipEvent_t e = free_events.back(); free_events.pop_back(); return e; }
-		hipEvent_t e; ARX_HIP_CHECK(hipEventCreate(&e)); return e;
+		if (free_events.empty()) return Event(hipEventDefault);
+		Event e = std::move(free_events.back()); free_events.pop_back(); return e;
 	}
 	struct Scope {
 		HipRT &rt; Pending p; bool on; const char *tn;
@@ -235,7 +219,7 @@ struct HipRT {
 		}
 		~Scope()
 		{
-			if (on) { (void)hipEventRecord(p.b, rt.stream); rt.pending.push_back(p); }
+			if (on) { (void)hipEventRecord(p.b, rt.stream); rt.pending.push_back(std::move(p)); }
 			if (tn) { (void)hipStreamSynchronize(rt.stream); fprintf(stderr, "[arx launch] %s done\n", tn); fflush(stderr); }
 		}
 	};
@@ -249,7 +233,7 @@ struct HipRT {
 			(void)hipEventElapsedTime(&ms, p.a, p.b);
 			if (launch_log) fprintf(launch_log, "%s\t%lld\t%.4f\n", p.nm, (long long)p.items, ms);
 			KernelTimer &t = tm[p.nm]; t.ms += ms; ++t.calls; t.items += p.items;
-			free_events.push_back(p.a); free_events.push_back(p.b);
+			free_events.push_back(std::move(p.a)); free_events.push_back(std::move(p.b));
 		}
 		pending.clear();
 		if (launch_log) fflush(launch_log);
@@ -341,19 +325,19 @@ struct HipRT {
 	// seeding: persistent lanes, items handed out in chunks (hip_fm_coop.h); f is one of pipeline.h's KSeedFwd1 / KSeedFwd2 / KSeedBwd,
 	// f.scratch holds max_slots() forward lists
 	// diagnostics (ARX_SEED_STATS=1): lane utilisation of the persistent-lane seeding kernels, printed per launch
-	unsigned long long *seed_dbg_buf = nullptr;
+	DevBuf seed_dbg_buf;
 	unsigned long long *seed_dbg()
 	{
 		if (!sw.seed_stats) return nullptr;
-		if (!seed_dbg_buf) ARX_HIP_CHECK(hipMalloc((void **)&seed_dbg_buf, 32));
-		memset0(seed_dbg_buf, 32);
-		return seed_dbg_buf;
+		if (!seed_dbg_buf.p) seed_dbg_buf.alloc(32);
+		memset0(seed_dbg_buf.p, 32);
+		return seed_dbg_buf.as<unsigned long long>();
 	}
 	void seed_dbg_report(const char *nm, int n)
 	{
-		if (!seed_dbg_buf) return; // (only seed_dbg() allocates it: sw.seed_stats is on)
+		if (!seed_dbg_buf.p) return; // (only seed_dbg() allocates it: sw.seed_stats is on)
 		unsigned long long h[4];
-		d2h(h, seed_dbg_buf, 32);
+		d2h(h, seed_dbg_buf.p, 32);
 		fprintf(stderr, "[arx seed stats] %s: %d items, %llu waves, %.0f iterations/wave, %.1f lanes extending per iteration, %.0f slow-path entries/wave\n", nm, n, h[3],
 		        h[3] ? (double)h[0] / h[3] : 0.0, h[0] ? (double)h[1] / h[0] : 0.0, h[3] ? (double)h[2] / h[3] : 0.0);
 	}
@@ -637,15 +621,14 @@ struct HipRT {
 		hipcub::DeviceScan::ExclusiveSum(nullptr, need, in, out, n, stream);
 		size_t need2 = 0;
 		hipcub::TransformInputIterator<int64_t, CastI64, const int32_t *> it(in, CastI64());
-		hipcub::DeviceReduce::Sum(nullptr, need2, it, d_total, n, stream);
-		if (need2 > need) need = need2;
-		if (need > scan_tmp_bytes) { if (scan_tmp) hipFree(scan_tmp); ARX_HIP_CHECK(hipMalloc(&scan_tmp, need)); scan_tmp_bytes = need; }
-		size_t nb = scan_tmp_bytes;
-		ARX_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(scan_tmp, nb, in, out, n, stream));
-		nb = scan_tmp_bytes;
-		ARX_HIP_CHECK(hipcub::DeviceReduce::Sum(scan_tmp, nb, it, d_total, n, stream));
+		hipcub::DeviceReduce::Sum(nullptr, need2, it, d_total.as<int64_t>(), n, stream);
+		void *tmp = scan_tmp.get(need2 > need ? need2 : need); // one scratch for both
+		size_t nb = scan_tmp.buf.bytes;
+		ARX_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, nb, in, out, n, stream));
+		nb = scan_tmp.buf.bytes;
+		ARX_HIP_CHECK(hipcub::DeviceReduce::Sum(tmp, nb, it, d_total.as<int64_t>(), n, stream));
 		int64_t total = 0;
-		d2h(&total, d_total, 8);
+		d2h(&total, d_total.p, 8);
 		int32_t t32 = (int32_t)(total < ((int64_t)1 << 31) ? total : 0x7fffffff);
 		ARX_HIP_CHECK(hipMemcpyAsync(out + n, &t32, 4, hipMemcpyHostToDevice, stream));
 		ARX_HIP_CHECK(hipStreamSynchronize(stream));
