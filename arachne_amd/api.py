@@ -154,6 +154,9 @@ _SELFTEST_ARGS = {
     "arx_bam_open_ex": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
     "arx_bam_sort_append": [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.c_int64, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_bam_sort": [C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    # the sort of a FASTQ file pair by barcode
+    "arx_fastq_sort": [C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_void_p, C.c_char_p, C.c_int32],
+    "arx_selftest_fastq_sort": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7,
 }
 
 
@@ -280,6 +283,55 @@ def selftest_bam_sort(stream, n_ref: int, seg_bytes: int = 1 << 18, mode: str = 
         e.code = rc
         raise e
     return dict(rc=rc, out=out[:n].tobytes(), guard=out[n:].tobytes(), rec_off=rec_off, n_records=int(n_rec.value), stats=_sort_stats(st))
+
+
+FQSORT_BGZF, FQSORT_CHECK, FQSORT_TIMED = 1, 2, 0x100
+_FQSORT_STATS = ("records", "bytes_in_r1", "bytes_in_r2", "bytes_out_r1", "bytes_out_r2", "skipped_lines", "runs", "distinct", "longest_barcode", "sort_passes", "windows",
+                 "slabs", "read_us", "inflate_us", "parse_us", "keys_us", "sort_us", "gather_us", "compress_us", "write_us")
+
+
+def _fqsort_stats(st):
+    return {k: int(st[i]) for i, k in enumerate(_FQSORT_STATS)}
+
+
+def fastq_sort(r1: str, r2: str, r1_out: "str | None" = None, r2_out: "str | None" = None, bgzf: bool = False, check: bool = False, timed: bool = False,
+               max_bytes: int = 0, device: int = 0, lib_path: str = LIB_PATH):
+    """A FASTQ file pair sorted by barcode on the GPU (include/arachne_amd.h: arx_fastq_sort, the reference's `preprocess`): the records the
+    feeder recognises, verbatim, ordered by the barcode's bytes, equal barcodes in input order.  Inputs plain, gzip or BGZF; outputs plain, or
+    BGZF with bgzf=True.  check=True writes nothing and only counts: stats["runs"] == stats["distinct"] says the input is sorted already.
+    -> the stats as a dict; ArachneError with .code on failure (nothing is left behind then)."""
+    lib = _load(lib_path)
+    st, msg = np.zeros(20, dtype=np.int64), C.create_string_buffer(1024)
+    flags = (FQSORT_BGZF if bgzf else 0) | (FQSORT_CHECK if check else 0) | (FQSORT_TIMED if timed else 0)
+    enc = lambda p: None if p is None else os.fsencode(p)
+    rc = _selftest_fn(lib, "arx_fastq_sort")(device, enc(r1), enc(r2), enc(r1_out), enc(r2_out), flags, int(max_bytes), st.ctypes.data, msg, 1024)
+    if rc != 0:
+        e = ArachneError("arx_fastq_sort: " + msg.value.decode(errors="replace"))
+        e.code = rc
+        raise e
+    return _fqsort_stats(st)
+
+
+def selftest_fastq_sort(t1, t2, window_bytes: int = 0, slab_bytes: int = 0, device: int = 0, fill: int = 0xA5, lib_path: str = LIB_PATH):
+    """arx_fastq_sort's orchestration on two texts in memory (include/arachne_amd.h: arx_selftest_fastq_sort) -> dict(rc: the entry's return
+    value (0, or ARX_E_TOO_LARGE = -4 for a line or record longer than a window), out1, out2: the sorted texts, guard1, guard2: the 8 bytes
+    behind the room the entry was given, rec_off1, rec_off2: where the sorted records start (-1 behind n_records + 1 entries), n_records,
+    stats).  On an error everything is as it was filled: `fill`, -1."""
+    lib = _load(lib_path)
+    s1, s2 = np.frombuffer(bytes(t1), dtype=np.uint8), np.frombuffer(bytes(t2), dtype=np.uint8)
+    n1, n2 = len(s1), len(s2)
+    out1, out2 = np.full(n1 + 8, fill, dtype=np.uint8), np.full(n2 + 8, fill, dtype=np.uint8)
+    off1, off2 = np.full(n1 // 5 + 2, -1, dtype=np.int64), np.full(n1 // 5 + 2, -1, dtype=np.int64)
+    n_rec, out_len, st = C.c_int64(-1), np.full(2, -1, dtype=np.int64), np.zeros(20, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_fastq_sort")(device, s1.ctypes.data if n1 else None, n1, s2.ctypes.data if n2 else None, n2, int(window_bytes), int(slab_bytes),
+                                                      out1.ctypes.data, out2.ctypes.data, out_len.ctypes.data, off1.ctypes.data, off2.ctypes.data, C.byref(n_rec), st.ctypes.data)
+    if rc not in (ARX_OK, ARX_E_TOO_LARGE):
+        e = ArachneError("arx_selftest_fastq_sort: code %d" % rc)
+        e.code = rc
+        raise e
+    l1, l2 = (int(out_len[0]), int(out_len[1])) if rc == ARX_OK else (n1, n2)
+    return dict(rc=rc, out1=out1[:l1].tobytes(), out2=out2[:l2].tobytes(), rest1=out1[l1:n1].tobytes(), rest2=out2[l2:n2].tobytes(), guard1=out1[n1:].tobytes(),
+                guard2=out2[n2:].tobytes(), rec_off1=off1, rec_off2=off2, n_records=int(n_rec.value), stats=_fqsort_stats(st))
 
 
 INFLATE_STATUS = ("OK", "BAD_HEADER", "BAD_BTYPE", "BAD_STORED_LEN", "BAD_CODE_LENGTHS", "BAD_SYMBOL", "BAD_DISTANCE", "TRUNCATED", "SIZE_MISMATCH", "CRC_MISMATCH")

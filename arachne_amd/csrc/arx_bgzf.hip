@@ -1,7 +1,8 @@
 // arx_bgzf.hip -- the device BAM sink (include/arachne_amd.h: arx_bam_open_device, arx_bam_write_encoded_device, arx_selftest_bgzf): BamSink (bam_sink.h) with the compressor of
 // hip_bgzf.h behind its seam.  Its own unit: the kernels of dev_bgzf.h compile next to the pipeline's.  The mirror image lives here too: the
 // inflate kernel of hip_inflate.h (arx_selftest_inflate; the device feeder starts it through inflate_launch).  And what needs both: the coordinate
-// sort of a BAM file into an open writer (arx_bam_open_ex, arx_bam_sort_append, arx_selftest_bam_sort: dev_bamsort.h, hip_bamsort.h).
+// sort of a BAM file into an open writer (arx_bam_open_ex, arx_bam_sort_append, arx_selftest_bam_sort: dev_bamsort.h, hip_bamsort.h), and the sort
+// of a FASTQ file pair by barcode (arx_fastq_sort, arx_selftest_fastq_sort: dev_fqsort.h, hip_fqsort.h).
 #include <map>
 #include <memory>
 #include <mutex>
@@ -9,6 +10,7 @@
 #include "hip_bgzf.h"
 #include "hip_inflate.h"
 #include "hip_bamsort.h"
+#include "hip_fqsort.h"
 
 namespace arx {
 
@@ -250,6 +252,92 @@ extern "C" int arx_selftest_bam_sort(int32_t device, const uint8_t *stream, int6
 		*n_records = N;
 		arx::bs_stats(stats, drv, N, n_bytes, 0, s.found.n_seg, s.found.right, s.found.repaired, s.found.rounds, 1);
 	} catch (const arx::BsTooLarge &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::HipOutOfMemory &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}
+
+// ---- the sort of a FASTQ file pair by barcode (dev_fqsort.h, hip_fqsort.h)
+static bool fs_same_file(const char *a, const char *b)
+{
+	if (!strcmp(a, b)) return true;
+	struct stat sa, sb;
+	return stat(a, &sa) == 0 && stat(b, &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
+}
+
+extern "C" int arx_fastq_sort(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t flags, int64_t max_bytes, int64_t *stats,
+                              char *msg, int32_t msg_cap)
+{
+	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
+	if (stats) for (int k = 0; k < arx::FS_N_STATS; ++k) stats[k] = 0;
+	if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) { say("arx_fastq_sort: unknown flag bits"); return ARX_E_ARG; }
+	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
+	if (!r1_in || !r2_in || max_bytes < 0 || (!check && (!r1_out || !r2_out))) { say("arx_fastq_sort: null argument"); return ARX_E_ARG; }
+	const char *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
+	if (!check) {
+		if (fs_same_file(r1_out, r2_out)) { say("arx_fastq_sort: the two output paths are the same file"); return ARX_E_ARG; }
+		for (int i = 0; i < 2; ++i)
+			for (int o = 0; o < 2; ++o)
+				if (fs_same_file(in[i], out[o])) { say(std::string("arx_fastq_sort: ") + out[o] + " is an input and an output"); return ARX_E_ARG; }
+	}
+	std::string err;
+	try {
+		const int rc = arx::fs_sort_files(device, in, out, flags, max_bytes, stats, err, arx::shared_device_bgzf);
+		if (rc != ARX_OK) say(err);
+		return rc;
+	} catch (const arx::FsTooLarge &e) {
+		say(e.what());
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::FsIoError &e) {
+		say(e.what());
+		return ARX_E_IO;
+	} catch (const arx::HipOutOfMemory &e) { // any buffer of the sort (hip_res.h)
+		say("the device memory does not hold the sort of these files (" + std::to_string(e.wanted >> 20) + " MiB more were asked for, " + std::to_string(e.free_bytes >> 20) + " MiB are free)" +
+		    arx::FS_REMEDY);
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &e) {
+		say(e.what());
+		return ARX_E_DEVICE;
+	}
+}
+
+extern "C" int arx_selftest_fastq_sort(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int64_t window_bytes, int64_t slab_bytes, uint8_t *out1,
+                                       uint8_t *out2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2, int64_t *n_records, int64_t *stats)
+{
+	if (n1 < 0 || n2 < 0 || !out_len || !rec_off1 || !rec_off2 || !n_records || (n1 > 0 && (!t1 || !out1)) || (n2 > 0 && (!t2 || !out2)) || slab_bytes < 0 ||
+	    (window_bytes != 0 && (window_bytes < arx::FS_MIN_WINDOW || window_bytes > arx::FS_MAX_WINDOW)))
+		return ARX_E_ARG;
+	if (stats) for (int k = 0; k < arx::FS_N_STATS; ++k) stats[k] = 0;
+	try {
+		arx::select_device(device, arx::FS_NO_DEVICE);
+		arx::Stream st;
+		st.create();
+		arx::FsHipDrv drv; drv.st = st;
+		arx::DevBuf d1((size_t)n1), d2((size_t)n2);
+		if (n1) ARX_HIP_CHECK(hipMemcpyAsync(d1.p, t1, (size_t)n1, hipMemcpyHostToDevice, drv.st));
+		if (n2) ARX_HIP_CHECK(hipMemcpyAsync(d2.p, t2, (size_t)n2, hipMemcpyHostToDevice, drv.st));
+		const arx::FsText T = {d1.as<uint8_t>(), d2.as<uint8_t>(), n1, n2};
+		arx::FsMemSink sink;
+		sink.init(drv.st);
+		arx::FsCounts c{};
+		arx::FsSortMem m{};
+		arx::fs_run(drv, T, window_bytes ? window_bytes : arx::FS_WINDOW_DEFAULT, slab_bytes ? slab_bytes : arx::FS_SLAB_DEFAULT, &sink, c, m);
+		const int64_t N = c.n_records;
+		std::vector<int64_t> off1((size_t)N + 1, 0), off2((size_t)N + 1, 0);
+		if (N) { drv.fetch(off1.data(), m.out1, (size_t)(N + 1) * 8); drv.fetch(off2.data(), m.out2, (size_t)(N + 1) * 8); }
+		if ((int64_t)sink.text[0].size() != c.bytes1 || (int64_t)sink.text[1].size() != c.bytes2 || c.bytes1 > n1 || c.bytes2 > n2) return ARX_E_DEVICE;
+		// everything is here: only now is anything of the caller's written
+		if (c.bytes1) memcpy(out1, sink.text[0].data(), (size_t)c.bytes1);
+		if (c.bytes2) memcpy(out2, sink.text[1].data(), (size_t)c.bytes2);
+		memcpy(rec_off1, off1.data(), (size_t)(N + 1) * 8); memcpy(rec_off2, off2.data(), (size_t)(N + 1) * 8);
+		out_len[0] = c.bytes1; out_len[1] = c.bytes2;
+		*n_records = N;
+		arx::fs_stats(stats, drv, c, n1, n2, true);
+	} catch (const arx::FsTooLarge &) {
 		return ARX_E_TOO_LARGE;
 	} catch (const arx::HipOutOfMemory &) {
 		return ARX_E_TOO_LARGE;

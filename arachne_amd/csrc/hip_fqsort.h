@@ -1,0 +1,410 @@
+// hip_fqsort.h -- dev_fqsort.h on the GPU, and the driver behind arx_fastq_sort and arx_selftest_fastq_sort (arx_bgzf.hip): a FASTQ file pair
+// sorted by barcode, the reference's `preprocess` (src/preprocess/preprocess.go:42-114: samtools import | sort -t BX | fastq) without samtools.
+//
+//   k_fs_items<F>    one item of a functor of dev_fqsort.h (or, wrapped, of dev_fastq.h) per thread, started through hip_launch under the
+//                    functor's name.  An item is a 16-byte word (window, newlines), a block of line pairs (state scan), a record (fields, table,
+//                    keys, runs, sizes) or one of the FS_GATHER_LANES lanes of a record of one file (gather)
+// The key sorts are rocprim::radix_sort_pairs over the bits that differ, the prefix sums rocprim's scan, the maximum and the OR rocprim's reduce.
+// The streams, events, every buffer and rocprim's scratch are owners of hip_res.h.
+//
+// The files.  Each input is judged by its own first bytes: a BGZF file is read as it is, slab by slab (BgzfChunkReader), and inflated on the device
+// (inflate_launch: only compressed bytes go up); anything else -- plain text, ordinary gzip -- goes through zlib on a reader thread (ChunkReader).
+// Host memory holds two slabs per file, never a file.  The inflated texts of both files stay in device memory until the call ends.
+// The output leaves in slabs of FS_SLAB_DEFAULT bytes per file from two pairs of buffers: while slab k is fetched and written (plain text), or
+// compressed and written (ARX_FQSORT_BGZF: DeviceBgzf::run_device, blocks cut every 65280 bytes, the 28-byte EOF block last), slab k + 1 is
+// gathered.  It goes to <out>.tmp, renamed when everything is written and removed otherwise.
+//
+// Device memory of a call: the two texts (a text that outgrows its buffer moves to one half as large again), four output slab buffers (256 MiB at
+// the default), per record 80 bytes (dev_fqsort.h: table, keys, values, output offsets), the parse's window buffers (FS_WINDOW_DEFAULT per file,
+// and about as much again for the line index), rocprim's scratch.  What does not fit is ARX_E_TOO_LARGE: sort per lane, or split the input.
+// Not built: an out-of-core merge of sorted runs.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_reduce.hpp>
+#include <stdio.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <vector>
+#include "../../include/arachne_amd.h"
+#include "hip_res.h"
+#include "bgzf_walk.h"
+#include "feeder.h"
+#include "dev_fqsort.h"
+#include "hip_bgzf.h"
+#include "hip_bamsort.h"
+
+namespace arx {
+
+constexpr int64_t FS_WINDOW_DEFAULT = (int64_t)32 << 20; // window_bytes of arx_fastq_sort
+constexpr int64_t FS_SLAB_DEFAULT = (int64_t)64 << 20;   // slab_bytes of arx_fastq_sort
+constexpr size_t FS_READ_CHUNK = (size_t)8 << 20;        // the readers' chunk; FS_READ_CHUNKS of them a slab
+constexpr size_t FS_READ_CHUNKS = 4;
+constexpr int FS_N_STATS = 20;
+enum { FS_T_READ = 12, FS_T_INFLATE, FS_T_PARSE, FS_T_KEYS, FS_T_SORT, FS_T_GATHER, FS_T_COMPRESS, FS_T_WRITE };
+
+template <class F> static __global__ void __launch_bounds__(256) k_fs_items(F f, int64_t n)
+{
+	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i < n) f(i);
+}
+
+struct FsTooLarge : std::runtime_error { using std::runtime_error::runtime_error; };
+struct FsIoError : std::runtime_error { using std::runtime_error::runtime_error; };
+struct FsOr { __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a | b; } };
+
+constexpr const char *FS_NO_DEVICE = "no such HIP device: the FASTQ sort runs on the GPU (there is no CPU fallback)";
+constexpr const char *FS_REMEDY = ": sort per lane, or split the input";
+
+// dev_fqsort.h's driver on a stream
+struct FsHipDrv {
+	hipStream_t st = nullptr;
+	bool timed = false;          // wait for every launch and book its time under its phase
+	double us[FS_N_STATS] = {0};
+	DevScratch tmp;
+	DevBuf work_[FS_N_WORK], tab_, red_;
+	int64_t tab_n_ = 0;
+
+	static int phase_of(const char *nm)
+	{
+		if (!strncmp(nm, "fq_", 3) || !strcmp(nm, "fs_window") || !strcmp(nm, "fs_store") || !strcmp(nm, "fs_scan32")) return FS_T_PARSE;
+		if (!strcmp(nm, "fs_sort")) return FS_T_SORT;
+		if (!strcmp(nm, "fs_gather") || !strcmp(nm, "fs_sizes")) return FS_T_GATHER;
+		return FS_T_KEYS; // length and chunk keys, runs, their scans and reductions
+	}
+	template <class Fn> void booked(const char *nm, Fn fn)
+	{
+		if (!timed) { fn(); return; }
+		ARX_HIP_CHECK(hipStreamSynchronize(st));
+		const double t0 = bs_now_us();
+		fn();
+		ARX_HIP_CHECK(hipStreamSynchronize(st));
+		us[phase_of(nm)] += bs_now_us() - t0;
+	}
+	template <class F> void items(const char *nm, int64_t n, const F &f)
+	{
+		if (n <= 0) return;
+		const int64_t grid = (n + 255) / 256;
+		if (grid > 0x7fffffff) throw FsTooLarge(std::string("too many items for one launch") + FS_REMEDY);
+		booked(nm, [&]() { hip_launch({"k_fs_items", nm}, k_fs_items<F>, dim3((unsigned)grid), dim3(256), 0, st, f, n); });
+	}
+	void scan(const int64_t *in, int64_t *out, int64_t n)
+	{
+		ARX_HIP_CHECK(hipMemsetAsync(out, 0, 8, st));
+		if (n <= 0) return;
+		booked("fs_scan", [&]() { dev_two_pass(tmp, "rocprim::inclusive_scan", [&](void *t, size_t &tb) { return rocprim::inclusive_scan(t, tb, in, out + 1, (size_t)n, rocprim::plus<int64_t>(), st); }); });
+	}
+	int64_t scan32(const int32_t *in, int32_t *out, int64_t n)
+	{
+		ARX_HIP_CHECK(hipMemsetAsync(out, 0, 4, st));
+		if (n <= 0) return 0;
+		booked("fs_scan32", [&]() { dev_two_pass(tmp, "rocprim::inclusive_scan", [&](void *t, size_t &tb) { return rocprim::inclusive_scan(t, tb, in, out + 1, (size_t)n, rocprim::plus<int32_t>(), st); }); });
+		return get32(out + n);
+	}
+	template <class Op> uint64_t reduce(const char *nm, const uint64_t *in, int64_t n, Op op)
+	{
+		if (n <= 0) return 0;
+		if (!red_.p) red_.alloc(8);
+		booked(nm, [&]() { dev_two_pass(tmp, "rocprim::reduce", [&](void *t, size_t &tb) { return rocprim::reduce(t, tb, in, red_.as<uint64_t>(), (uint64_t)0, (size_t)n, op, st); }); });
+		return dev_get(red_.as<uint64_t>(), st);
+	}
+	uint64_t max64(const uint64_t *in, int64_t n) { return reduce("fs_max", in, n, rocprim::maximum<uint64_t>()); }
+	uint64_t or64(const uint64_t *in, int64_t n) { return reduce("fs_or", in, n, FsOr()); }
+	int64_t get(const int64_t *p) { return dev_get(p, st); }
+	int32_t get32(const int32_t *p) { return dev_get(p, st); }
+	void fetch(void *host, const void *dev, size_t bytes)
+	{
+		ARX_HIP_CHECK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+		ARX_HIP_CHECK(hipStreamSynchronize(st));
+	}
+	void sort_pairs(const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout, int64_t n, int bits) { booked("fs_sort", [&]() { dev_sort_pairs(tmp, kin, kout, vin, vout, (size_t)n, bits, st); }); }
+	void *work(int slot, int64_t bytes)
+	{
+		DevBuf &b = work_[slot];
+		if (!b.p || (size_t)bytes > b.bytes) {
+			ARX_HIP_CHECK(hipStreamSynchronize(st)); // what still reads the old buffer has ended
+			b.alloc((size_t)bytes + (size_t)bytes / 4);
+		}
+		return b.p;
+	}
+	FsRec *table(int64_t n)
+	{
+		if (n > tab_n_) {
+			const int64_t room = fs_table_room(n);
+			DevBuf t((size_t)room * sizeof(FsRec));
+			if (tab_n_) ARX_HIP_CHECK(hipMemcpyAsync(t.p, tab_.p, (size_t)tab_n_ * sizeof(FsRec), hipMemcpyDeviceToDevice, st));
+			ARX_HIP_CHECK(hipStreamSynchronize(st));
+			tab_ = std::move(t); tab_n_ = room;
+		}
+		return tab_.as<FsRec>();
+	}
+};
+
+// ---- where the slabs go.  Two pairs of device buffers: the gather of slab k runs while slab k - 1 is consumed (its gather is awaited through an event)
+struct FsSink {
+	hipStream_t st = nullptr; // the gather's stream
+	Stream out;               // the fetches' stream
+	Event done[2];
+	DevBuf buf[2][2];
+	bool have = false;
+	int64_t pk = 0, pb[2] = {0, 0};
+	double us_consume = 0;
+	virtual ~FsSink() {}
+	void init(hipStream_t gather_stream)
+	{
+		st = gather_stream;
+		out.create();
+		for (Event &e : done) e.create(hipEventDisableTiming);
+	}
+	void take(int64_t k, int64_t cap, int64_t, int64_t, uint8_t **d1, uint8_t **d2)
+	{
+		for (int f = 0; f < 2; ++f)
+			if (!buf[k & 1][f].p || (size_t)cap > buf[k & 1][f].bytes) buf[k & 1][f].alloc((size_t)cap);
+		*d1 = buf[k & 1][0].as<uint8_t>(); *d2 = buf[k & 1][1].as<uint8_t>();
+	}
+	void give(int64_t k, int64_t, int64_t, int64_t b1, int64_t b2)
+	{
+		ARX_HIP_CHECK(hipEventRecord(done[k & 1], st));
+		flush();
+		have = true; pk = k; pb[0] = b1; pb[1] = b2;
+	}
+	void flush()
+	{
+		if (!have) return;
+		have = false;
+		ARX_HIP_CHECK(hipEventSynchronize(done[pk & 1]));
+		const double t0 = bs_now_us();
+		for (int f = 0; f < 2; ++f) consume(f, buf[pk & 1][f].as<uint8_t>(), pb[f]);
+		us_consume += bs_now_us() - t0;
+	}
+	// n bytes of file f's output, complete in device memory; returns when they may be overwritten
+	virtual void consume(int f, const uint8_t *d, int64_t n) = 0;
+	void fetch(void *host, const uint8_t *d, int64_t n)
+	{
+		ARX_HIP_CHECK(hipMemcpyAsync(host, d, (size_t)n, hipMemcpyDeviceToHost, out));
+		ARX_HIP_CHECK(hipStreamSynchronize(out));
+	}
+};
+struct FsMemSink : FsSink { // the self-test's: into host memory
+	std::vector<uint8_t> text[2];
+	void consume(int f, const uint8_t *d, int64_t n) override
+	{
+		const size_t at = text[f].size();
+		text[f].resize(at + (size_t)n);
+		if (n) fetch(text[f].data() + at, d, n);
+	}
+};
+
+// an output file: written as <path>.tmp, renamed by commit(), removed where that was not reached
+struct FsOutFile {
+	FILE *f = nullptr;
+	std::string path, tmp;
+	int64_t bytes_out = 0;
+	bool open(const char *p)
+	{
+		path = p; tmp = path + ".tmp";
+		f = fopen(tmp.c_str(), "wb");
+		if (f) setvbuf(f, nullptr, _IOFBF, 1 << 20);
+		return f != nullptr;
+	}
+	bool commit()
+	{
+		bool ok = f && fflush(f) == 0 && !ferror(f);
+		if (f) { ok = fclose(f) == 0 && ok; f = nullptr; }
+		ok = ok && rename(tmp.c_str(), path.c_str()) == 0;
+		if (ok) tmp.clear();
+		return ok;
+	}
+	~FsOutFile()
+	{
+		if (f) fclose(f);
+		if (!tmp.empty()) remove(tmp.c_str());
+	}
+};
+struct FsFileSink : FsSink {
+	FsOutFile file[2];
+	bool bgzf = false;
+	std::shared_ptr<DeviceBgzf> z;
+	std::vector<uint8_t> carry[2]; // BGZF: the bytes short of a block
+	PinnedBuf h;
+	double us_compress = 0, us_write = 0;
+	void consume(int f, const uint8_t *d, int64_t n) override
+	{
+		if (n <= 0) return;
+		const double t0 = bs_now_us();
+		if (bgzf) {
+			std::vector<uint8_t> tail;
+			size_t nb = 0;
+			std::string err;
+			if (!z->run_device(carry[f].data(), carry[f].size(), d, (size_t)n, file[f].f, file[f].bytes_out, nb, tail, err)) throw FsIoError(file[f].path + ": " + err);
+			carry[f].swap(tail);
+			us_compress += bs_now_us() - t0;
+			return;
+		}
+		if (!h.p || (size_t)n > h.bytes) h.alloc((size_t)n);
+		fetch(h.p, d, n);
+		if (fwrite(h.p, 1, (size_t)n, file[f].f) != (size_t)n) throw FsIoError(file[f].path + ": write failed");
+		file[f].bytes_out += n;
+		us_write += bs_now_us() - t0;
+	}
+	// the last block and the EOF block of a BGZF output; both files to their names
+	void finish()
+	{
+		flush();
+		const double t0 = bs_now_us();
+		for (int f = 0; f < 2; ++f) {
+			if (bgzf) {
+				static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+				std::string err;
+				if (!carry[f].empty() && !z->run(carry[f].data(), carry[f].size(), file[f].f, file[f].bytes_out, err)) throw FsIoError(file[f].path + ": " + err);
+				carry[f].clear();
+				if (fwrite(eof, 1, 28, file[f].f) != 28) throw FsIoError(file[f].path + ": write failed");
+				file[f].bytes_out += 28;
+			}
+		}
+		for (int f = 0; f < 2; ++f)
+			if (!file[f].commit()) throw FsIoError(file[f].path + ": write failed");
+		us_write += bs_now_us() - t0;
+	}
+};
+
+inline void fs_stats(int64_t *stats, const FsHipDrv &drv, const FsCounts &c, int64_t n1, int64_t n2, bool written)
+{
+	if (!stats) return;
+	stats[0] = c.n_records; stats[1] = n1; stats[2] = n2; stats[3] = written ? c.bytes1 : 0; stats[4] = written ? c.bytes2 : 0; stats[5] = c.skipped; stats[6] = c.runs_in; stats[7] = c.distinct;
+	stats[8] = c.max_bc; stats[9] = c.passes; stats[10] = c.windows; stats[11] = written ? c.slabs : 0;
+	for (int k = FS_T_READ; k < FS_N_STATS; ++k) stats[k] = (int64_t)drv.us[k];
+}
+
+// table, order and (sink != null) gather of two texts in device memory.  Without `timed` the phases are wall-clock times between their ends: keys
+// and sort passes together under FS_T_SORT; with it every launch group is awaited and booked on its own
+inline void fs_run(FsHipDrv &drv, const FsText &T, int64_t window, int64_t slab, FsSink *sink, FsCounts &c, FsSortMem &m)
+{
+	double t0 = bs_now_us();
+	const int rc = fs_parse(drv, T, window, c);
+	if (rc == FS_E_RECORDS) throw FsTooLarge(std::string("more than 2^32 - 1 records") + FS_REMEDY);
+	if (rc != FS_OK) throw FsTooLarge("a line or a record is longer than the " + std::to_string(window) + " bytes of a parse window");
+	ARX_HIP_CHECK(hipStreamSynchronize(drv.st));
+	if (!drv.timed) drv.us[FS_T_PARSE] = bs_now_us() - t0;
+	t0 = bs_now_us();
+	for (int s = FS_W_WIN1; s < FS_W_KEYS0; ++s) drv.work_[s].release(); // the parse's buffers make room for the sort's
+	const int64_t N = c.n_records;
+	fs_sort_mem(drv, N, m);
+	const int64_t longest = fs_order(drv, T, drv.tab_.as<FsRec>(), N, m, c);
+	ARX_HIP_CHECK(hipStreamSynchronize(drv.st));
+	if (!drv.timed) drv.us[FS_T_SORT] = bs_now_us() - t0;
+	c.slabs = 0;
+	if (!sink) return;
+	t0 = bs_now_us();
+	fs_gather(drv, T, drv.tab_.as<FsRec>(), N, m, slab, longest, *sink, c);
+	sink->flush();
+	if (!drv.timed) drv.us[FS_T_GATHER] = bs_now_us() - t0 - sink->us_consume;
+}
+
+// one input file into device memory
+struct FsInput {
+	std::unique_ptr<SlabReader> rd;
+	bool bgzf = false, done = false;
+	DevBuf text;
+	int64_t len = 0;
+	bool open(const char *path)
+	{
+		bgzf = file_is_bgzf(path);
+		if (bgzf) { std::unique_ptr<BgzfChunkReader> r(new BgzfChunkReader()); const bool ok = r->open(path, FS_READ_CHUNK, FS_READ_CHUNKS); rd = std::move(r); return ok; }
+		std::unique_ptr<ChunkReader> r(new ChunkReader());
+		const bool ok = r->open(path, FS_READ_CHUNK, FS_READ_CHUNKS);
+		rd = std::move(r);
+		return ok;
+	}
+	void room(int64_t need, hipStream_t st) // the text so far stays
+	{
+		if (text.p && (size_t)need <= text.bytes) return;
+		DevBuf t((size_t)(need + need / 2) + 64);
+		if (len) ARX_HIP_CHECK(hipMemcpyAsync(t.p, text.p, (size_t)len, hipMemcpyDeviceToDevice, st));
+		ARX_HIP_CHECK(hipStreamSynchronize(st));
+		text = std::move(t);
+	}
+};
+
+// -> ARX_*; err: the text
+// get_z: the device's compressor (arx_bgzf.hip keeps one per device)
+inline int fs_sort_files(int device, const char *const in_path[2], const char *const out_path[2], int flags, int64_t max_bytes, int64_t *stats, std::string &err,
+                         std::shared_ptr<DeviceBgzf> (*get_z)(int))
+{
+	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
+	FsInput in[2];
+	for (int f = 0; f < 2; ++f)
+		if (!in[f].open(in_path[f])) { err = std::string("cannot read ") + in_path[f]; return ARX_E_IO; }
+	FsFileSink sink;
+	sink.bgzf = (flags & ARX_FQSORT_BGZF) != 0;
+	if (!check)
+		for (int f = 0; f < 2; ++f)
+			if (!sink.file[f].open(out_path[f])) { err = std::string("cannot write ") + sink.file[f].tmp; return ARX_E_IO; }
+	select_device(device, FS_NO_DEVICE);
+	Stream st; // the call's own; declared before the buffers, so that it has ended when they are freed
+	st.create();
+	FsHipDrv drv; drv.st = st; drv.timed = (flags & ARX_FQSORT_TIMED) != 0;
+	// ---- the two texts into device memory, slab by slab as the readers have them
+	{
+		DevBuf d_comp, d_rows, d_status;
+		for (int f = 0; f < 2; ++f) in[f].rd->start();
+		while (!in[0].done || !in[1].done) {
+			for (int f = 0; f < 2; ++f) {
+				FsInput &I = in[f];
+				if (I.done) continue;
+				double t0 = bs_now_us();
+				const SlabReader::Slab *s = I.rd->acquire();
+				drv.us[FS_T_READ] += bs_now_us() - t0;
+				if (!s) { I.done = true; continue; }
+				t0 = bs_now_us();
+				if (s->err) { err = std::string(in_path[f]) + (I.bgzf ? ": not a chain of whole BGZF blocks" : ": read error"); return ARX_E_IO; }
+				if (max_bytes > 0 && in[0].len + in[1].len + (int64_t)s->text > max_bytes) {
+					err = std::string(in_path[0]) + " and " + in_path[1] + " inflate to more than the " + std::to_string(max_bytes) + " bytes allowed" + FS_REMEDY;
+					return ARX_E_TOO_LARGE;
+				}
+				I.room(I.len + (int64_t)s->text, st);
+				uint8_t *dst = I.text.as<uint8_t>() + I.len;
+				if (!I.bgzf) {
+					if (s->len) ARX_HIP_CHECK(hipMemcpyAsync(dst, s->buf, s->len, hipMemcpyHostToDevice, st));
+				} else if (s->n_rows) {
+					const size_t nr = s->n_rows;
+					if (!d_comp.p || s->len > d_comp.bytes) d_comp.alloc(s->len + s->len / 4);
+					if (!d_rows.p || nr * sizeof(InfRow) > d_rows.bytes) { d_rows.alloc(2 * nr * sizeof(InfRow)); d_status.alloc(4 * (2 * nr + 2)); }
+					ARX_HIP_CHECK(hipMemcpyAsync(d_comp.p, s->buf, s->len, hipMemcpyHostToDevice, st));
+					ARX_HIP_CHECK(hipMemcpyAsync(d_rows.p, s->rows, nr * sizeof(InfRow), hipMemcpyHostToDevice, st));
+					ARX_HIP_CHECK(hipMemsetAsync(d_status.p, 0, 4 * (nr + 2), st));
+					int32_t *counts = d_status.as<int32_t>() + nr;
+					inflate_launch(st, d_comp.as<uint8_t>(), (int64_t)s->len, d_rows.as<InfRow>(), (int)nr, dst, (int64_t)s->text, d_status.as<int32_t>(), counts);
+					int32_t bad[2] = {0, 0};
+					ARX_HIP_CHECK(hipMemcpyAsync(bad, counts, 8, hipMemcpyDeviceToHost, st));
+					ARX_HIP_CHECK(hipStreamSynchronize(st));
+					if (bad[0] != 0) { err = std::string(in_path[f]) + ": a BGZF block does not inflate"; return ARX_E_IO; }
+				}
+				ARX_HIP_CHECK(hipStreamSynchronize(st)); // the reader may refill the slab
+				I.len += (int64_t)s->text;
+				if (s->eof) I.done = true;
+				I.rd->release();
+				drv.us[FS_T_INFLATE] += bs_now_us() - t0;
+			}
+		}
+		for (int f = 0; f < 2; ++f) in[f].rd.reset();
+	}
+	const FsText T = {in[0].text.as<uint8_t>(), in[1].text.as<uint8_t>(), in[0].len, in[1].len};
+	FsCounts c{};
+	FsSortMem m{};
+	if (!check) {
+		sink.init(st);
+		if (sink.bgzf) sink.z = get_z(device);
+	}
+	fs_run(drv, T, FS_WINDOW_DEFAULT, FS_SLAB_DEFAULT, check ? nullptr : &sink, c, m);
+	if (!check) {
+		sink.finish();
+		drv.us[FS_T_COMPRESS] = sink.us_compress; drv.us[FS_T_WRITE] = sink.us_write;
+	}
+	fs_stats(stats, drv, c, T.n1, T.n2, !check);
+	return ARX_OK;
+}
+
+} // namespace arx

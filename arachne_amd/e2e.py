@@ -239,6 +239,30 @@ def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "hos
     return dict(records=st["records"], buckets=len(per), bytes=st["bytes_out"], seconds=time.time() - t, sort=per)
 
 
+def presort(r1: str, r2: str, out_dir: str, device: int = 0, bgzf: bool = False, if_needed: bool = True, lib_path: str = api.LIB_PATH):
+    """The step in front of run(): the file pair sorted by barcode on the GPU (api.fastq_sort; the reference's `arachne preprocess`), which
+    the feeder's barcode sets rely on.  With if_needed the input is counted first (check=True) and returned as it is when every barcode
+    is one run already.  The sorted files go to out_dir under the inputs' base names (+ ".sorted.fastq", ".gz" with bgzf: a BGZF file is a
+    gzip file).  -> (r1_sorted, r2_sorted, stats); stats["sorted"] says whether files were written."""
+    if if_needed:
+        st = api.fastq_sort(r1, r2, check=True, device=device, lib_path=lib_path)
+        if st["runs"] == st["distinct"]:
+            return r1, r2, dict(st, sorted=False)
+    os.makedirs(out_dir, exist_ok=True)
+
+    def name(p):
+        b = os.path.basename(p)
+        for ext in (".gz", ".bgz", ".fastq", ".fq"):
+            if b.endswith(ext):
+                b = b[:-len(ext)]
+        return os.path.join(out_dir, b + ".sorted.fastq" + (".gz" if bgzf else ""))
+    o1, o2 = name(r1), name(r2)
+    if o1 == o2:
+        o2 = o2.replace(".sorted.", ".sorted.2.")
+    st = api.fastq_sort(r1, r2, o1, o2, bgzf=bgzf, device=device, lib_path=lib_path)
+    return o1, o2, dict(st, sorted=True)
+
+
 def _nothing():
     pass
 

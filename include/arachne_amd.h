@@ -336,6 +336,46 @@ int arx_bam_sort_append(arx_ctx *ctx, arx_bam *w, const char *in_path, int32_t m
 int arx_selftest_bam_sort(int32_t device, const uint8_t *stream, int64_t n_bytes, int32_t n_ref, int64_t seg_bytes, int32_t mode, uint8_t *out, int64_t *rec_off,
                           int64_t *n_records, int64_t *stats);
 
+/* ---- in front of the feeder: a FASTQ file pair sorted by barcode on the GPU -- the reference's `arachne preprocess`
+ * (src/preprocess/preprocess.go:42-114: samtools import -T '*' | samtools sort -t BX | samtools fastq -T '*'), which the aligner needs: the
+ * feeder opens a new barcode set wherever the barcode changes, so a barcode that returns later in the file would be placed as several
+ * molecules.  The contract:
+ *   record    what the feeder recognises.  Lines exist only where they end in '\n'; the lines of R1 and R2 are walked in lockstep up to the
+ *             shorter file's line count; while searching, a pair whose R1 line is non-empty and starts with '@' opens a record of four line
+ *             pairs, any other pair is skipped; a record that the end of either file cuts off does not exist
+ *   barcode   the feeder's: the value of the leftmost BX:Z:(\S+)\s of the R1 header, the header's own newline closing a value, white space
+ *             being ' ', \t, \n, \r, \v, \f; no match: the empty barcode.  R2's header plays no part
+ *   output    every record's eight lines verbatim, four to each output file, ordered by barcode as unsigned bytes (byte-wise, a proper prefix
+ *             first: strcmp's order extended to any byte, so the empty barcode comes first, as `samtools sort -t` puts records without the
+ *             tag), equal barcodes in input order (stable, as samtools' merge sort).  Skipped lines and the cut-off record are dropped
+ * So the feeder sees every barcode of the output as exactly one run, and the records it delivers are the input's.  The output is not the
+ * bytes of the samtools pipeline, which rewrites the headers (tab-separated tags, /1 and /2).
+ * device: a HIP device index -- no context is needed, and none should be open beside a large sort: its index competes for the memory.
+ * Inputs may be plain text, gzip or BGZF, each file judged by itself; a BGZF file is inflated on the device.  Outputs are plain text, or
+ * with ARX_FQSORT_BGZF BGZF files (blocks cut every 65280 bytes, the 28-byte EOF block last) that inflate to the same bytes; they are
+ * written as <path>.tmp and renamed at the end: a failing call leaves nothing behind.  ARX_FQSORT_CHECK: nothing is written, the output
+ * paths may be NULL, only stats is filled -- stats[6] == stats[7] says that the input needs no sort.  ARX_FQSORT_TIMED waits for every
+ * launch and books the phases per launch group.  Both texts and 80 bytes per record stay in device memory (csrc/hip_fqsort.h); max_bytes
+ * (0: no limit of its own) bounds the inflated bytes of both files together.  ARX_E_TOO_LARGE: more than max_bytes, or than the device
+ * holds -- msg names the remedy: sort per lane, or split the input (there is no out-of-core merge); ARX_E_IO: a file cannot be read or
+ * written, or a block does not inflate (nothing is produced then, where the feeder delivers the sets in front of the damage); ARX_E_ARG:
+ * null paths without CHECK, unknown flag bits, an output path that is an input; ARX_E_DEVICE: no GPU, or a HIP error.
+ * stats[20] (may be NULL): [0] records written, [1] [2] inflated bytes read from R1, R2, [3] [4] bytes written to R1, R2 as inflated text,
+ * [5] lines skipped, [6] barcode runs in the input, [7] distinct barcodes, [8] longest barcode, [9] sort passes, [10] parse windows,
+ * [11] output slabs, then microseconds: [12] waiting for the readers, [13] upload and inflate, [14] parse, [15] keys (TIMED only: otherwise
+ * under [16]), [16] sort passes, [17] gather, [18] compress and write of BGZF blocks, [19] fetch and write of plain text, last blocks, rename */
+enum { ARX_FQSORT_BGZF = 1, ARX_FQSORT_CHECK = 2, ARX_FQSORT_TIMED = 0x100 };
+int arx_fastq_sort(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t flags, int64_t max_bytes, int64_t *stats,
+                   char *msg, int32_t msg_cap);
+/* self-test of the same orchestration (preprocess.go:42-114 as above) on two texts in host memory, no file and no index needed
+ * (tests/test_fastq_sort_gpu.py).  window_bytes: the text a parse looks at per file (0: the 32 MiB of arx_fastq_sort; otherwise at least 128
+ * and at most 2^29 -- ARX_E_ARG outside; a line or record that a window does not hold is ARX_E_TOO_LARGE); slab_bytes: the output bytes per
+ * file that are gathered at a time (0: 64 MiB; a slab holds one record at least).  out1[n1], out2[n2] receive the sorted texts, out_len[2] their
+ * lengths, rec_off1 / rec_off2[*n_records + 1] where the sorted records start (room for n1 / 5 + 2 entries always suffices), stats[20] (may
+ * be NULL) as above.  On any error out1, out2, rec_off1 and rec_off2 are untouched. */
+int arx_selftest_fastq_sort(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int64_t window_bytes, int64_t slab_bytes, uint8_t *out1,
+                            uint8_t *out2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2, int64_t *n_records, int64_t *stats);
+
 /* ---- between the path and the sink: the placed candidate of every read of a super-batch as BAM records -- the part of DumpToBams /
  * AppendBam (src/aligner/bamwriter.go:283-568, 635-658) that decides flags, position, MAPQ, mate fields, template length, CIGAR op codes,
  * strand of bases and qualities and the RG / AS / XM / AM / XT / BX / VX tags of the primary record (csrc/bam_records.h lists what is left
