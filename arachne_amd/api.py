@@ -143,6 +143,7 @@ _SELFTEST_ARGS = {
     "arx_selftest_bgzf": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "arx_selftest_inflate": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
     "arx_selftest_rec_text": [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+    "arx_selftest_seed_bins": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64],
     "arx_selftest_block_shape": [C.c_int32, C.c_void_p, C.c_void_p],
     "arx_selftest_block": [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64],
     "arx_selftest_rfa": [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
@@ -392,6 +393,34 @@ def selftest_rec_text(a, b=None, device: int = 0, lib_path: str = LIB_PATH):
     if rc != 0:
         raise ArachneError("arx_selftest_rec_text: code %d" % rc)
     return [out[i, :ln[i]].tobytes() for i in range(n)]
+
+
+def selftest_seed_bins(ref, seqs, lens, tasks_per_read: int = 64):
+    """The bins of the backward sweeps as the forward seeding kernels fill them (include/arachne_amd.h: arx_selftest_seed_bins): the seeding stage
+    of the reads on a runtime of its own, with ref's index and the ARX_* switches as they are now -> one dict per forward launch (first pass and
+    re-seeding pass of every group of reads): t0, n (the launch's tasks), cnt (the four counters), err (the batch's error word so far), task_n
+    (the list length of each task) and bins (four arrays of task ids)."""
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    flat = np.ascontiguousarray(seqs, dtype=np.uint8).reshape(-1)
+    if int(lens.sum()) != len(flat):
+        raise ValueError("seqs must hold the reads back to back")
+    rec_cap, cap = 2 * len(lens) + 2, tasks_per_read * len(lens) + 64
+    n_l = C.c_int32(0)
+    rec, task_n, ids = np.zeros((rec_cap, 8), dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+    rc = _selftest_fn(ref.lib, "arx_selftest_seed_bins")(ref.h, flat.ctypes.data, lens.ctypes.data, len(lens), C.byref(n_l), rec.ctypes.data, rec_cap,
+                                                         task_n.ctypes.data, cap, ids.ctypes.data, cap)
+    if rc != 0:
+        raise ArachneError("arx_selftest_seed_bins: code %d" % rc)
+    out, nt, nb = [], 0, 0
+    for r in rec[:n_l.value]:
+        cnt = [int(x) for x in r[2:6]]
+        bins = []
+        for c in cnt:
+            bins.append(ids[nb:nb + c].copy())
+            nb += c
+        out.append(dict(t0=int(r[0]), n=int(r[1]), cnt=cnt, err=int(r[6]) & 0xffffffff, task_n=task_n[nt:nt + int(r[1])].copy(), bins=bins))
+        nt += int(r[1])
+    return out
 
 
 BLOCK_OPS = {"scan": 0, "sort_kv": 1, "argmax": 2}

@@ -25,3 +25,5 @@ template <> struct ItemsWpe<KReg2Aln> { static constexpr int v = ARX_WPE_REG2ALN
 }
 
 ARX_DEFINE_C_API(arx::HipRT)
+
+namespace arx { const IndexView *ctx_index_view(::arx_ctx *ctx) { return ctx ? &((Context<HipRT> *)ctx)->ix : nullptr; } }

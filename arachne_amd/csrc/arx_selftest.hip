@@ -317,3 +317,42 @@ extern "C" int arx_selftest_rfa(int32_t device, int32_t n_reads, const int64_t *
 		return ARX_E_DEVICE;
 	}
 }
+
+// The bins of the backward sweeps as the forward kernels fill them: Pipeline::stage_seed itself on the caller's reads, with the runtime's
+// record of the bins switched on (hip_rt.h seed_bins_record)
+extern "C" int arx_selftest_seed_bins(arx_ctx *ctx, const uint8_t *bases, const int32_t *lens, int32_t n_reads, int32_t *n_launches, int32_t *rec, int32_t rec_cap,
+                                      int32_t *task_n, int64_t task_cap, int32_t *bin_ids, int64_t bin_cap)
+{
+	using namespace arx;
+	const IndexView *ix = ctx_index_view(ctx);
+	if (!ix || !bases || !lens || n_reads < 1 || !n_launches || !rec || !task_n || !bin_ids || rec_cap < 0 || task_cap < 0 || bin_cap < 0) return ARX_E_ARG;
+	int64_t tot = 0;
+	for (int i = 0; i < n_reads; ++i) { if (lens[i] < 0 || lens[i] > MAX_READ_LEN) return ARX_E_ARG; tot += lens[i]; }
+	if (tot >= ((int64_t)1 << 31) - 64) return ARX_E_TOO_LARGE;
+	*n_launches = 0;
+	try {
+		HipRT rt;
+		if (!rt.init(arx_ctx_device(ctx)).empty()) return ARX_E_DEVICE;
+		rt.timing = false;
+		rt.seed_bins_log_on = true;
+		Pipeline<HipRT> pipe(rt, *ix);
+		Pipeline<HipRT>::DeviceBatch db = pipe.upload(bases, lens, n_reads);
+		Pipeline<HipRT>::Work w;
+		int rc = ARX_OK;
+		try { if (pipe.stage_seed(db, w) == -2) rc = ARX_E_TOO_LARGE; rt.sync(); } catch (...) { pipe.release(db); throw; }
+		pipe.release(db);
+		if (rc != ARX_OK) return rc;
+		int64_t nt = 0, nb = 0;
+		for (const HipRT::SeedBinsRecord &r : rt.seed_bins_log) {
+			if (*n_launches >= rec_cap || nt + r.n > task_cap || nb + r.cnt[0] + r.cnt[1] + r.cnt[2] + r.cnt[3] > bin_cap) return ARX_E_TOO_LARGE;
+			int32_t *o = rec + 8 * (size_t)*n_launches;
+			o[0] = r.t0; o[1] = r.n; for (int c = 0; c < 4; ++c) o[2 + c] = r.cnt[c]; o[6] = (int32_t)r.err; o[7] = 0;
+			for (int32_t v : r.task_n) task_n[nt++] = v;
+			for (int c = 0; c < 4; ++c) for (int32_t v : r.bin[c]) bin_ids[nb++] = v;
+			++*n_launches;
+		}
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}

@@ -294,6 +294,11 @@ struct SeedTask { // off/n: pool slice; nm: SMEMs found; next: the read's next t
 	int32_t row, n_prev, mls, pad; // the row to go on with, the entries of its list, the start of the last SMEM found
 };
 
+// The bin of a task's backward sweep by the entries of its forward list (hip_fm_coop.h k_seed_bwd_g: the smallest group of lanes that holds
+// a row): 0 up to 16 entries, 1 up to mid (21; 16: the bin stays empty), 2 up to 32, 3 the rest; -1: nothing to sweep (an empty list, or a
+// task whose pool slice overflowed).  Stated once, for the grant step that fills the bins and for the host.
+ARX_HDI int seed_bwd_class(int n, int mid) { return n <= 0 ? -1 : n <= 16 ? 0 : n <= mid ? 1 : n <= 32 ? 2 : 3; }
+
 struct SeedPools { // batch-wide, filled through atomic cursors; an overflow raises ERR_POOL_OVERFLOW and the read yields no more tasks
 	Biv *pool; int64_t pool_cap; SeedTask *tasks; int32_t task_cap; int32_t *cursors; // cursors[0]: pool entries handed out, [1]: tasks
 	uint32_t *err;

@@ -140,7 +140,15 @@ struct SeedKArgs { // shared by the three kernels
 	const uint32_t *qn;                            // the batch's reads as nibble rows (k_pack_reads), row / 4 words each
 	int read0;                                     // first pass: item i is read read0 + i
 	unsigned long long *dbg;                       // (diagnostics, ARX_SEED_STATS) [0] wave-iterations, [1] lane-extensions, [2] slow-path entries, [3] waves
+	// forward kernels: the backward sweeps' bins (dev_fm.h seed_bwd_class), filled by the grant step as the lists get their slices.  One block
+	// of memory (one pointer: the forward kernels have no scalar registers to spare): bins[c], c < 4, counts the tasks of class c, and their ids
+	// are the list seed_bin_list(bins, c, P.task_cap); mid: the longest list of class 1.  bins == nullptr: no binning (the backward variants
+	// that take the tasks in id order)
+	int32_t *bins; int mid;
 };
+constexpr int SEED_BIN_HEAD = 64; // words in front of the four lists: the counters (hip_rt.h SeedBins)
+__host__ __device__ inline int32_t *seed_bin_list(int32_t *bins, int c, int32_t task_cap) { return bins + SEED_BIN_HEAD + (size_t)c * (size_t)task_cap; }
+inline size_t seed_bin_words(int32_t task_cap) { return SEED_BIN_HEAD + 4 * (size_t)task_cap; }
 
 // Lane programs: begin(item) after the read is staged (false: nothing to do), advance(req, rb, rc, slow_ok) -> has a request /
 // parked or done, consume(req, ok), done(), finish().  A program that needs pool entries (and a task id) parks with want() > 0;
@@ -191,6 +199,7 @@ struct FwdProg1 { // first pass: the forward extensions of one read, start after
 	__device__ int export_def() const { return pend_def; }
 	__device__ uint32_t export_code() const { return pend_code; }
 	__device__ int export_x() const { return pend_x; }
+	__device__ int task_id() const { return -1; } // (NEW_TASK: the grant step hands the id out)
 	__device__ void granted(int off, int t, int n_act) // n_act: entries the wavefront wrote (the lane's own plus the owed prefix)
 	{
 		const int n = n_act, n_res = pend_n + pend_def;
@@ -251,6 +260,7 @@ struct FwdProg2 { // re-seeding: the forward extension of one task
 	__device__ int export_def() const { return ln.n_def; }
 	__device__ uint32_t export_code() const { return ln.code; }
 	__device__ int export_x() const { return x; }
+	__device__ int task_id() const { return t; }
 	__device__ void granted(int off, int, int n_act)
 	{
 		awaiting = false; over = true;
@@ -292,6 +302,7 @@ struct BwdProg { // the backward sweep of one task
 	__device__ int export_def() const { return 0; }
 	__device__ uint32_t export_code() const { return 0; }
 	__device__ int export_x() const { return 0; }
+	__device__ int task_id() const { return t; }
 	__device__ void granted(int, int, int) {}
 	__device__ void consume(const Biv &req, const Biv &ok) { ln.consume(req, ok); }
 	__device__ void consume_aux(uint32_t, uint32_t, uint32_t, uint32_t) {}
@@ -451,7 +462,34 @@ __device__ __forceinline__ void persistent_lanes(const SeedKArgs &A, int n, int3
 				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 				__builtin_amdgcn_wave_barrier(); // (g_act is read below; the LDS words are rewritten by the next grant step)
 				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-				if (amt > 0) prog.granted(base + incl - amt, tbase + rank, g_n[rank] >= 0 ? g_act[rank] : 0);
+				const int n_act = amt > 0 && g_n[rank] >= 0 ? g_act[rank] : 0;
+				if (amt > 0) prog.granted(base + incl - amt, tbase + rank, n_act);
+				if (A.bins) { // (wave-uniform) the backward sweeps' bins: every task that just got its list goes to the bin of its length -- what granted()
+					// stored as the task's n, so a task whose slice or id overflowed (n = 0) goes to none.  One ballot per class; lane 0 adds each class that
+					// occurs to its counter, the (up to) four atomics in flight together; a lane's slot is its class's base plus its rank in the class.
+					// The grant step is where these kernels' register count is set, so masks, bases and list offsets stay scalar (readlane, mbcnt): 120 / 96
+					// vector registers against 120 / 95 without the bins; a shuffle for the base and a 64-bit lane mask for the rank made it 124 / 99.
+					const int tid = Prog::NEW_TASK ? tbase + rank : prog.task_id();
+					const int cls = amt > 0 && (!Prog::NEW_TASK || tid < A.P.task_cap) ? seed_bwd_class(n_act, A.mid) : -1;
+					const unsigned long long m0 = __ballot(cls == 0), m1 = __ballot(cls == 1), m2 = __ballot(cls == 2), m3 = __ballot(cls == 3);
+					if (m0 | m1 | m2 | m3) {
+						int r0 = 0, r1 = 0, r2 = 0, r3 = 0;
+						if (lane == 0) { // (no atomic depends on another: they are in flight together)
+							if (m0) r0 = atomicAdd(A.bins, __builtin_popcountll(m0));
+							if (m1) r1 = atomicAdd(A.bins + 1, __builtin_popcountll(m1));
+							if (m2) r2 = atomicAdd(A.bins + 2, __builtin_popcountll(m2));
+							if (m3) r3 = atomicAdd(A.bins + 3, __builtin_popcountll(m3));
+						}
+						const int b0 = __builtin_amdgcn_readlane(r0, 0), b1 = __builtin_amdgcn_readlane(r1, 0), b2 = __builtin_amdgcn_readlane(r2, 0), b3 = __builtin_amdgcn_readlane(r3, 0);
+						size_t pos = 0; // from the first list's start (seed_bin_list)
+						const size_t cap = (size_t)A.P.task_cap;
+						if (cls == 0) pos = (size_t)b0 + __builtin_amdgcn_mbcnt_hi((unsigned)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m0, 0));
+						if (cls == 1) pos = cap + b1 + __builtin_amdgcn_mbcnt_hi((unsigned)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m1, 0));
+						if (cls == 2) pos = 2 * cap + b2 + __builtin_amdgcn_mbcnt_hi((unsigned)(m2 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m2, 0));
+						if (cls == 3) pos = 3 * cap + b3 + __builtin_amdgcn_mbcnt_hi((unsigned)(m3 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m3, 0));
+						if (cls >= 0) A.bins[SEED_BIN_HEAD + pos] = tid;
+					}
+				}
 				__builtin_amdgcn_wave_barrier();
 			}
 			if (item >= 0 && !have_req) have_req = prog.advance(&req, &rb, &rc, true); // a lane whose parked list just got its slice goes on
@@ -587,7 +625,7 @@ static __global__ void __launch_bounds__(64, ARX_SEED_WPE) k_seed_bwd2(SeedKArgs
 // group's low lanes through LDS.  Refills are pipelined as in k_seed_bwd2: a group that takes a task loads it in one iteration, its read
 // row and list in the next, riding along with the Occ loads of the groups that extend; one wait on memory per iteration.
 // Tasks whose forward list is longer than 16 go to k_seed_bwd_wave (64 lanes) from their first row.
-// GL = lanes per group (16, 21, 32 or 64): tasks are binned by the length of their forward list (k_bin_tasks) and each bin runs with the
+// GL = lanes per group (16, 21, 32 or 64): tasks are binned by the length of their forward list (by the forward kernels' grant step, persistent_lanes) and each bin runs with the
 // smallest group that holds its rows; `list` / `n_list` = the bin's task ids and their number (device memory).  GL = 21 (three groups and an
 // idle lane): at GRCh38 size a forward list has an entry for nearly every one of the ~16 depths it takes to get to one occurrence, so more
 // than half of the first pass's lists are 17-20 entries long -- just too long for a quarter of a wavefront, and half a wavefront leaves most
@@ -728,15 +766,15 @@ __device__ __forceinline__ void seed_bwd_g_body(const SeedKArgs &A, const int32_
 // FIT32: every symbol occurs fewer than 2^32 times in the text (dev_fm.h occ_counts_fit32; the host checks the index header): the sizes of an
 // extension's children in 32 bits, the 40-bit count for one symbol only
 template <bool FIT32>
-static __global__ void __launch_bounds__(64, ARX_SEED_WPE) k_seed_bwd_g(SeedKArgs A, const int32_t *bins, int n, int32_t *cnt, uint8_t *heavy_flag)
+static __global__ void __launch_bounds__(64, ARX_SEED_WPE) k_seed_bwd_g(SeedKArgs A, const int32_t *bin0, const int32_t *bin1, const int32_t *bin2, const int32_t *bin3, int32_t *cnt, uint8_t *heavy_flag)
 {
-	seed_bwd_g_body<16, FIT32>(A, bins, cnt, cnt + 4, 32, heavy_flag);
+	seed_bwd_g_body<16, FIT32>(A, bin0, cnt, cnt + 4, 32, heavy_flag);
 	__builtin_amdgcn_wave_barrier();
-	seed_bwd_g_body<21, FIT32>(A, bins + n, cnt + 1, cnt + 5, 24, heavy_flag);
+	seed_bwd_g_body<21, FIT32>(A, bin1, cnt + 1, cnt + 5, 24, heavy_flag);
 	__builtin_amdgcn_wave_barrier();
-	seed_bwd_g_body<32, FIT32>(A, bins + 2 * (size_t)n, cnt + 2, cnt + 6, 16, heavy_flag);
+	seed_bwd_g_body<32, FIT32>(A, bin2, cnt + 2, cnt + 6, 16, heavy_flag);
 	__builtin_amdgcn_wave_barrier();
-	seed_bwd_g_body<64, FIT32>(A, bins + 3 * (size_t)n, cnt + 3, cnt + 7, 2, heavy_flag);
+	seed_bwd_g_body<64, FIT32>(A, bin3, cnt + 3, cnt + 7, 2, heavy_flag);
 }
 // ---- the backward sweeps, entry-parallel (end of round 3; ARX_SEED_BWD2=3).  What bwt_smem1a's backward loop computes (bwt.c:322-348) is,
 // for every interval of the forward list on its own, how far to the left it can be extended before it holds fewer than min_intv occurrences:
@@ -860,23 +898,6 @@ static __global__ void __launch_bounds__(64, ARX_SEED_WPE) k_seed_bwd_e(SeedKArg
 	if (A.dbg && lane == 0) { atomicAdd(A.dbg, n_it); atomicAdd(A.dbg + 1, n_ext); atomicAdd(A.dbg + 3, 1ull); }
 }
 
-// task ids of [t0, t0 + n) by the group size their forward list needs: bins[0] <= 16 entries, [1] <= 21, [2] <= 32, [3] the rest; cnt[4]
-static __global__ void __launch_bounds__(256) k_bin_tasks(const SeedTask *tasks, int t0, int n, int32_t *bin0, int32_t *bin1, int32_t *bin2, int32_t *bin3, int32_t *cnt, int mid)
-{
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	const int len = i < n ? tasks[t0 + i].n : 0; // 0: nothing to sweep (nm stays 0)
-	const int cls = len == 0 ? -1 : len <= 16 ? 0 : len <= mid ? 1 : len <= 32 ? 2 : 3; // mid = 21 (16: the 21-lane bin stays empty)
-	int32_t *const bins[4] = {bin0, bin1, bin2, bin3};
-#pragma unroll
-	for (int c = 0; c < 4; ++c) { // one atomic per wavefront and bin
-		const unsigned long long m = __ballot(cls == c);
-		if (!m) continue;
-		int base = 0;
-		if ((int)(threadIdx.x & 63) == __builtin_ctzll(m)) base = atomicAdd(cnt + c, __builtin_popcountll(m));
-		base = __shfl(base, __builtin_ctzll(m));
-		if (cls == c) bins[c][base + __builtin_popcountll(m & ((1ull << (threadIdx.x & 63)) - 1))] = t0 + i;
-	}
-}
 static __global__ void __launch_bounds__(256) k_collect_heavy(const uint8_t *flag, int n, int t0, int32_t *heavy, int32_t *n_heavy)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -20,6 +20,8 @@
 #include "index_build.h"
 #include "switches.h"
 
+struct arx_ctx; // include/arachne_amd.h
+
 namespace arx {
 
 // generic grid-stride launchers; slot = global thread index (always < max_slots) selects per-thread scratch
@@ -48,6 +50,7 @@ struct CastI64 { __host__ __device__ int64_t operator()(const int32_t &x) const 
 struct KernelTimer { double ms = 0; int64_t calls = 0, items = 0; };
 
 std::string product_bwt_sa(const uint8_t *pac, size_t pac_bytes, int64_t l_pac, const uint64_t cnt_fwd[4], const std::string &prefix); // arx_index.hip
+const IndexView *ctx_index_view(::arx_ctx *ctx); // arx_api.hip: the device-resident index of an open context (null: no context); for the self-test entries that need one
 
 struct HipRT {
 	BatchSwitches sw; // the ARX_* environment as it was when this runtime (= its batch handle, context or device feeder) was created (switches.h)
@@ -189,6 +192,7 @@ struct HipRT {
 	const uint32_t *seed_qn = nullptr;
 	void seed_prepare(const uint8_t *bases, const int32_t *base_off, const int32_t *lens, int n_reads)
 	{
+		seed_bins = SeedBins(); // (arena memory of the batch before)
 		if (sw.sw_simple || n_reads <= 0) return;
 		const int rw = seed_row >> 2;
 		uint32_t *q = alloc<uint32_t>((size_t)n_reads * rw + 8);
@@ -400,6 +404,47 @@ struct HipRT {
 		d2h(off.data(), preg_off, 4 * ((size_t)n_reads + 1));
 		for (int32_t p : l) { const int c = off[2 * (size_t)p + 2] - off[2 * (size_t)p]; ++heavy_census[c <= 170 ? 5 : c <= 340 ? 6 : 7]; }
 	}
+	// The bins of the row-parallel backward sweeps (k_seed_bwd_g): four lists of task ids by the length of the tasks' forward lists, filled by
+	// the forward kernel that makes the lists (hip_fm_coop.h persistent_lanes, grant step), so that the backward launch starts with nothing in
+	// front of it.  They have to exist before the forward launch, when the number of tasks is not known: each holds task_cap ids (a task is in
+	// one bin at most, and ids from task_cap on are refused).  One block (hip_fm_coop.h seed_bin_list), taken from the arena by the first forward
+	// launch after seed_prepare(), used by every pass and group of the batch, handed back with the seeding stage's memory.  Its first words are
+	// the counters: [0..3] the bins' sizes, [4..7] k_seed_bwd_g's item counters; cleared in front of every forward launch.
+	struct SeedBins { int32_t *mem = nullptr; int32_t cap = 0; };
+	SeedBins seed_bins;
+	bool seed_bins_on() const { return sw.seed_bwd2 == 2 && !sw.sw_simple; }
+	void seed_bins_attach(SeedKArgs &A)
+	{
+		if (!seed_bins_on()) return;
+		if (!seed_bins.mem || seed_bins.cap != A.P.task_cap) { seed_bins.mem = alloc<int32_t>(seed_bin_words(A.P.task_cap)); seed_bins.cap = A.P.task_cap; }
+		memset0(seed_bins.mem, 32);
+		A.bins = seed_bins.mem; A.mid = sw.seed_bwd_mid;
+	}
+	// opt-in record of the bins (arx_selftest_seed_bins; tests assert from it that every task is in the bin its list length names).  Everything
+	// it reports is in device memory after a forward launch anyway; switched on, it is copied home after the launch: the launch's tasks
+	// [t0, t0 + n) with their list lengths, the four counters, the four lists and the error word.  Switched off (everywhere else) it is one
+	// untaken branch on the host per forward launch.
+	struct SeedBinsRecord { int32_t t0 = 0, n = 0, cnt[4] = {0, 0, 0, 0}; uint32_t err = 0; std::vector<int32_t> task_n, bin[4]; };
+	bool seed_bins_log_on = false;
+	std::vector<SeedBinsRecord> seed_bins_log;
+	void seed_bins_record(const SeedPools &P, int t0, int n) // n < 0: the launch made the tasks itself (first pass): as many as the task cursor says
+	{
+		if (!seed_bins_log_on || !seed_bins.mem) return;
+		SeedBinsRecord r;
+		if (n < 0) { int32_t cur[2]; d2h(cur, P.cursors, 8); n = cur[1] < P.task_cap ? cur[1] : P.task_cap; }
+		r.t0 = t0; r.n = n;
+		std::vector<SeedTask> tk((size_t)n);
+		d2h(tk.data(), P.tasks + t0, sizeof(SeedTask) * (size_t)n);
+		for (const SeedTask &k : tk) r.task_n.push_back(k.n);
+		d2h(r.cnt, seed_bins.mem, 16);
+		d2h(&r.err, P.err, 4);
+		for (int c = 0; c < 4; ++c) {
+			if (r.cnt[c] < 0 || r.cnt[c] > seed_bins.cap) throw std::runtime_error("seed_bins_record: a bin's counter is outside its list");
+			r.bin[c].resize((size_t)r.cnt[c]);
+			d2h(r.bin[c].data(), seed_bin_list(seed_bins.mem, c, seed_bins.cap), 4 * (size_t)r.cnt[c]);
+		}
+		seed_bins_log.push_back(std::move(r));
+	}
 	template <class K> void launch_seed_kernel(const char *nm, K kern, int n, const SeedKArgs &A, int32_t *counter, int bpc_, int chunk_ = 0, int batch_ = 0, int grant_ = 64)
 	{
 		if (chunk_ <= 0) chunk_ = sw.seed_chunk;
@@ -414,16 +459,20 @@ struct HipRT {
 		if (n <= 0) return;
 		if (sw.sw_simple) { launch(nm, n, f); return; }
 		SeedKArgs A{f.ix, f.bases, f.base_off, f.lens, f.P, f.scratch, f.list_cap, f.first1, 0, nullptr, nullptr, 0, seed_row, seed_qn, f.read0, seed_dbg()};
+		seed_bins_attach(A);
 		launch_seed_kernel(nm, k_seed_fwd1, n, A, counter, seed_bpc(), 0, 0, sw.seed_grant); // (the re-seeding pass has one extension per item: no grant step of its own)
 		seed_dbg_report(nm, n);
+		seed_bins_record(f.P, 0, -1);
 	}
 	template <class F> void run_seed_fwd2(const char *nm, int n, const F &f, int32_t *counter)
 	{
 		if (n <= 0) return;
 		if (sw.sw_simple) { launch(nm, n, f); return; }
 		SeedKArgs A{f.ix, f.bases, f.base_off, f.lens, f.P, f.scratch, f.list_cap, nullptr, f.t0, nullptr, nullptr, 0, seed_row, seed_qn, 0, seed_dbg()};
+		seed_bins_attach(A);
 		launch_seed_kernel(nm, k_seed_fwd2, n, A, counter, seed_bpc());
 		seed_dbg_report(nm, n);
+		seed_bins_record(f.P, f.t0, n);
 	}
 	// backward sweeps: run_seed_bwd() dispatches on sw.seed_bwd2 to one function per kernel variant (switches.h has their story; all four are
 	// pinned by tests/test_seed_variants_gpu.py).  A: the variant's kernel arguments; A.heavy / A.n_heavy: the list of the sweeps that are
@@ -472,20 +521,20 @@ struct HipRT {
 		seed_dbg_report(nm, (int)total);
 		seed_census_add(n, nullptr, nullptr, nullptr); // (nothing is handed on)
 	}
-	// ARX_SEED_BWD2=2 (the default), row-parallel sweeps (k_seed_bwd_g<FIT32>): one task per 16/32/64-lane group, lists in registers
+	// ARX_SEED_BWD2=2 (the default), row-parallel sweeps (k_seed_bwd_g<FIT32>): one task per 16/32/64-lane group, lists in registers.  The tasks
+	// [f.t0, f.t0 + n) are the ones the forward launch before this one gave their lists, and it has binned them (seed_bins)
 	template <class F> void seed_bwd_rows(const char *nm, int n, const F &f, const SeedKArgs &A)
 	{
+		if (!seed_bins.mem || seed_bins.cap != f.P.task_cap) throw std::runtime_error("seed_bwd_rows: no forward launch has filled the bins");
 		uint8_t *flag = alloc<uint8_t>((size_t)n + 8);
-		int32_t *bins = alloc<int32_t>(4 * (size_t)n + 8), *cnt = alloc<int32_t>(8); // cnt[0..3]: bin sizes, cnt[4..7]: the bins' item counters
+		int32_t *const cnt = seed_bins.mem;
 		memset0(flag, (size_t)n);
-		memset0(cnt, 32);
 		{
 			Scope sc(*this, nm, n);
-			start("k_bin_tasks", k_bin_tasks, dim3((n + 255) / 256), dim3(256), 0, f.P.tasks, f.t0, n, bins, bins + n, bins + 2 * (size_t)n, bins + 3 * (size_t)n, cnt, sw.seed_bwd_mid);
 			const bool fit32 = sw.seed_fit32 && (((f.ix.L2[1] - f.ix.L2[0]) | (f.ix.L2[2] - f.ix.L2[1]) | (f.ix.L2[3] - f.ix.L2[2]) | (f.ix.L2[4] - f.ix.L2[3])) >> 32) == 0;
 			const int cap = n_cu * sw.seed_bwd_bpc, b = (n + 3) / 4, blocks = b > cap ? cap : (b < 1 ? 1 : b); // four tasks per wavefront
 			const size_t lds = ((4 * (size_t)seed_row + 31) & ~(size_t)31) + 64 * 32; // four reads and the lanes' exchange words
-			start({"k_seed_bwd_g", nm, fit32}, fit32 ? k_seed_bwd_g<true> : k_seed_bwd_g<false>, dim3(blocks), dim3(64), lds, A, bins, n, cnt, flag);
+			start({"k_seed_bwd_g", nm, fit32}, fit32 ? k_seed_bwd_g<true> : k_seed_bwd_g<false>, dim3(blocks), dim3(64), lds, A, seed_bin_list(cnt, 0, seed_bins.cap), seed_bin_list(cnt, 1, seed_bins.cap), seed_bin_list(cnt, 2, seed_bins.cap), seed_bin_list(cnt, 3, seed_bins.cap), cnt, flag);
 		}
 		if (sw.seed_hist) { // diagnostics: forward-list lengths of this launch's tasks
 			std::vector<SeedTask> ht((size_t)n);

@@ -551,6 +551,16 @@ int arx_selftest_rfa(int32_t device, int32_t n_reads, const int64_t *reg_off, co
                      const int64_t *ann_off, int32_t n_seqs, const int64_t *cen_start, const int64_t *cen_end, int32_t rfa_small, double mapq_guard,
                      int32_t *cand_off, void *cands, int64_t cand_cap, void *bc_out, uint8_t *cls, int64_t *n_host_mapq);
 
+/* self-test of the bins of the row-parallel backward sweeps, which the forward seeding kernels fill as they hand out pool slices
+ * (csrc/hip_fm_coop.h grant step, csrc/dev_fm.h seed_bwd_class): the seeding stage of the given reads (bases: codes 0..4 back to back, any
+ * n_reads >= 1) runs on a runtime of its own with ctx's index and the ARX_* switches as they are at the call, and what device memory holds
+ * after every forward launch comes home.  Launch i (first pass and re-seeding pass of each group of reads, in that order): rec[8 i ..] =
+ * first task, tasks, the four bins' counters, the batch's error word so far, 0; task_n: the list length of each of the launch's tasks;
+ * bin_ids: the four bins' task ids, bin after bin.  task_n and bin_ids are appended launch after launch.  *n_launches: launches recorded.
+ * ARX_E_TOO_LARGE: a cap is too small; an error word that is not 0 is no failure of this entry. */
+int arx_selftest_seed_bins(arx_ctx *ctx, const uint8_t *bases, const int32_t *lens, int32_t n_reads, int32_t *n_launches, int32_t *rec, int32_t rec_cap,
+                           int32_t *task_n, int64_t task_cap, int32_t *bin_ids, int64_t bin_cap);
+
 /* self-tests of the three DP kernel families on plain host arrays (csrc/arx_selftest.hip; tests/test_dp_kernels_gpu.py): each entry
  * uploads the tasks, launches the production code on them and returns one result row per task, in input order.  The reference text is
  * passed in bwa's .pac layout (pac: (l_pac + 3) / 4 bytes, 2 bits per base, first base in the top bits); coordinates are doubled, so a
