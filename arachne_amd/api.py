@@ -148,6 +148,8 @@ _SELFTEST_ARGS = {
     "arx_selftest_block": [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64],
     "arx_selftest_rfa": [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
                          C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "arx_selftest_reg2aln": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_int64, C.c_int32],
     # the device BAM sink: bound when first used, for the same reason
     "arx_bam_open_device": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
     "arx_bam_write_encoded_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64],
@@ -505,6 +507,41 @@ def selftest_rfa(batch, lens, bc_pair_off, do_rfa, l_pac: int, ann_off, penalty:
     if rc != 0:
         raise ArachneError("arx_selftest_rfa: code %d" % rc)
     return dict(cand_off=off, cands=cands, barcodes=bc, cls=cls, n_host_mapq=int(nh.value))
+
+
+R2A_CENSUS_HEAD = 12
+
+
+def selftest_reg2aln(ref, seqs, lens, cap, n_regs, regs, census: bool = False, grid_cap: int = 0):
+    """The CIGAR stage on given regions (include/arachne_amd.h: arx_selftest_reg2aln), on a runtime of its own with ref's index and the ARX_*
+    switches as they are now.  seqs: the reads back to back (codes 0..4); cap / n_regs: region slots and used regions per read; regs: one row
+    per SLOT in the restatement's 20-column int64 layout -> dict(reg_off, alns (ALN_DTYPE), cigars, err (the error word), census (None, or
+    dict(cig_w, passes, queued, big, per_class[5], punts (-1: not kept), known (bit mask over the entry's first values), rows (n x 3: region
+    index among the used ones, band class, nw_need)))).  grid_cap > 0: at most that many workgroups per class launch."""
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    flat = np.ascontiguousarray(seqs, dtype=np.uint8).reshape(-1)
+    cap, n_regs = np.ascontiguousarray(cap, dtype=np.int32), np.ascontiguousarray(n_regs, dtype=np.int32)
+    regs = np.ascontiguousarray(regs, dtype=np.int64).reshape(-1, 20)
+    if int(lens.sum()) != len(flat) or len(cap) != len(lens) or len(n_regs) != len(lens) or len(regs) != int(cap.sum()):
+        raise ValueError("reads, slots and region rows do not match")
+    n = int(n_regs.sum())
+    reg_off, alns = np.zeros(len(lens) + 1, dtype=np.int32), np.zeros(n + 1, dtype=ALN_DTYPE)
+    cig_cap = 1024 * n + 1
+    cig, n_cig, err = np.zeros(min(cig_cap, 64 * n + 4096), dtype=np.uint32), C.c_int64(-1), C.c_uint32(0)
+    cen = np.zeros(R2A_CENSUS_HEAD + 3 * n, dtype=np.int64) if census else None
+    rc = _selftest_fn(ref.lib, "arx_selftest_reg2aln")(ref.h, flat.ctypes.data, lens.ctypes.data, len(lens), cap.ctypes.data, n_regs.ctypes.data, regs.ctypes.data,
+                                                       reg_off.ctypes.data, alns.ctypes.data, n, cig.ctypes.data, len(cig), C.byref(n_cig), C.byref(err),
+                                                       None if cen is None else cen.ctypes.data, 0 if cen is None else len(cen), int(grid_cap))
+    if rc != 0:
+        e = ArachneError("arx_selftest_reg2aln: code %d" % rc)
+        e.code = rc
+        raise e
+    out = dict(reg_off=reg_off, alns=alns[:int(reg_off[-1])], cigars=cig[:n_cig.value].copy(), err=int(err.value), census=None)
+    if cen is not None:
+        k = int(cen[10])
+        out["census"] = dict(cig_w=int(cen[0]), passes=int(cen[1]), queued=int(cen[2]), big=int(cen[3]), per_class=[int(x) for x in cen[4:9]], punts=int(cen[9]),
+                             known=int(cen[11]), rows=cen[R2A_CENSUS_HEAD:R2A_CENSUS_HEAD + 3 * k].reshape(k, 3).copy())
+    return out
 
 
 class _RecordsLayout(C.Structure):

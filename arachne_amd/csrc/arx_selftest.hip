@@ -4,6 +4,8 @@
 // code through HipRT, so that tests/test_dp_kernels_gpu.py can compare every output field with ksw_extend2 / ksw_align2 / ksw_global2.
 // arx_selftest_block runs the workgroup primitives of hip_block.h (scan, bitonic sort, arg-max) through k_block_items itself, one case per workgroup, and
 // arx_selftest_rfa (selftest_rfa.h) the whole placement stage on alignments the caller made up (tests/test_block_primitives_gpu.py, tests/test_rfa_cases_gpu.py).
+// arx_selftest_reg2aln (selftest_reg2aln.h) runs stage 6 itself -- Pipeline::stage_reg2aln with its slot loop, k_reg2aln_nw_g16 per band class, the launch
+// that takes what they hand on, the one-thread path and compact() -- on regions the caller made up (tests/test_cigar_stage_gpu.py).
 // Its own unit so that the unit of the list-bookkeeping kernels does not grow.
 #include <climits>
 #include <vector>
@@ -12,6 +14,7 @@
 #include "pipeline.h"
 #include "dev_records_full.h"
 #include "selftest_rfa.h"
+#include "selftest_reg2aln.h"
 
 namespace arx {
 
@@ -355,4 +358,23 @@ extern "C" int arx_selftest_seed_bins(arx_ctx *ctx, const uint8_t *bases, const 
 		return ARX_E_DEVICE;
 	}
 	return ARX_OK;
+}
+
+// Stage 6 on the caller's regions: Pipeline::stage_reg2aln on a runtime of its own, with ctx's index and the ARX_* switches as they are at the call
+extern "C" int arx_selftest_reg2aln(arx_ctx *ctx, const uint8_t *bases, const int32_t *lens, int32_t n_reads, const int32_t *cap, const int32_t *n_regs, const int64_t *regs,
+                                    int32_t *reg_off, void *alns, int64_t aln_cap, uint32_t *cigars, int64_t cig_cap, int64_t *n_cig, uint32_t *err, int64_t *census,
+                                    int64_t census_cap, int32_t grid_cap)
+{
+	using namespace arx;
+	const IndexView *ix = ctx_index_view(ctx);
+	if (!ix) return ARX_E_ARG;
+	try {
+		HipRT rt;
+		if (!rt.init(arx_ctx_device(ctx)).empty()) return ARX_E_DEVICE;
+		rt.timing = false;
+		if (grid_cap > 0) { rt.n_cu = 1; rt.sw.coop_bpc = grid_cap; } // class launches of at most grid_cap workgroups, two for what they hand on: every group takes many regions
+		return selftest_reg2aln_run(rt, *ix, bases, lens, n_reads, cap, n_regs, regs, reg_off, alns, aln_cap, cigars, cig_cap, n_cig, err, census, census_cap);
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
 }

@@ -391,6 +391,7 @@ struct SegView { // query segment [qb,qe) / reference segment [rb,re), both read
 
 ARX_DEVI int push_cigar(uint32_t *cg, int n, int cap, int op, int len) // ksw.c:487-497; returns the new length (> cap on overflow)
 {
+	if (n > cap) return n; // overflowed: cg[n - 1] lies behind the slot (the next region's, or the end of the array) and the caller only asks whether n > cap
 	if (n == 0 || op != (int)(cg[n - 1] & 0xf)) { if (n < cap) cg[n] = (uint32_t)len << 4 | op; return n + 1; }
 	cg[n - 1] += (uint32_t)len << 4;
 	return n;

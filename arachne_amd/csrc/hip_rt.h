@@ -631,14 +631,18 @@ struct HipRT {
 	}
 	// CIGARs of the gapped regions: 16 lanes per region (hip_nw_coop.h); f is pipeline.h's KReg2Aln
 	using NwKernel = void (*)(NwArgs, int, const int32_t *);
+	const int32_t *nw_n_punt = nullptr; // the last run_reg2aln_nw's punt counter on the device (null: it kept none)
+	int nw_punts() { if (!nw_n_punt) return -1; int32_t v = 0; d2h(&v, nw_n_punt, 4); return v; } // Pipeline::reg2aln_census
 	template <class F> void run_reg2aln_nw(const char *nm, int n, const int32_t *n_class, const F &f, uint8_t *zbuf, const int32_t *z_off)
 	{
+		nw_n_punt = nullptr;
 		if (n <= 0) return;
 		if (sw.sw_simple) { launch_small(nm, n, f); return; }
 		// one launch per band class: the four groups of a wavefront then run the same tiling, and the class kernel holds only the tilings the
 		// class can need (its own and the doubled band's): 5 / 4 / 3 / 2 / 2 wavefronts per SIMD instead of 2 for all
 		int32_t *punt = alloc<int32_t>((size_t)n + 4), *n_punt = punt + n;
 		memset0(n_punt, 16);
+		nw_n_punt = n_punt;
 		for (int c = 0; c < NW_CLASSES; ++c) {
 			const int nc = n_class[c];
 			if (nc <= 0) continue;

@@ -272,6 +272,18 @@ template <class R> struct HasChainGroup<R, decltype((void)std::declval<const R &
 template <class R, class = void> struct HasHeavyCensus { static constexpr bool value = false; };
 template <class R> struct HasHeavyCensus<R, decltype((void)std::declval<R &>().heavy_census_on)> { static constexpr bool value = true; };
 
+// opt-in census of stage 6 (arx_selftest_reg2aln; Pipeline::reg2aln_census): what the stage's launches leave in device memory anyway, copied
+// home after every pass of the slot loop; the last pass stays.  Off (the default) nothing is counted and nothing is copied
+struct Reg2AlnCensus {
+	int cig_w = 0, passes = 0;
+	int punts = -1;                         // regions the class kernels handed on; -1: this runtime keeps no such list (one-thread form, host double)
+	int32_t count[2 + NW_CLASSES] = {};     // queued for the 16-lane kernel, too long for it, queued per band class
+	std::vector<int32_t> list, need, klass; // per queued region: slot index, 64-byte units of traceback matrix, band class
+};
+// HipRT knows how many regions its class launches handed on (nw_punts()); the host test double runs every queued region on the serial path
+template <class R, class = void> struct HasNwPunts { static constexpr bool value = false; };
+template <class R> struct HasNwPunts<R, decltype((void)std::declval<R &>().nw_punts())> { static constexpr bool value = true; };
+
 struct KChainMid { // the listed reads of KChain, one thread each; the list's length stays on the device
 	KChain f;
 	ARX_DEV void operator()(int i, int) const { const int n = *f.n_mid < f.mid_cap ? *f.n_mid : f.mid_cap; if (i < n) f.one(f.mid_list[i]); }
@@ -542,6 +554,7 @@ public:
 	const PipelineSwitches sw; // the stages' environment switches as they were when this pipeline (= its batch handle) was created (switches.h)
 	explicit Pipeline(RT &rt_, const IndexView &ix_) : rt(rt_), ix(ix_) {}
 	Pipeline(RT &rt_, const IndexView &ix_, const PipelineSwitches &sw_) : rt(rt_), ix(ix_), sw(sw_) {} // the self-tests: switches from arguments, not the environment
+	Reg2AlnCensus *reg2aln_census = nullptr; // where stage_reg2aln reports (null: no census)
 
 	// device-resident input of one batch; the buffers are kept by the handle and reused by arx_batch_reset (cap_*: what they hold)
 	struct DeviceBatch { uint8_t *bases = 0; int32_t *base_off = 0, *lens = 0; int n_reads = 0; int64_t n_bases = 0; int max_len = 0; int64_t cap_bases = 0; int cap_reads = 0; };
@@ -860,6 +873,20 @@ public:
 			rt.launch_small("reg2aln_nw_big", n2[1], k);
 			rt.merge_sort_fail(w.err);
 			uint32_t e = read_err(w);
+			if (reg2aln_census) { // (read_err has waited for the launches)
+				Reg2AlnCensus &c = *reg2aln_census;
+				c.cig_w = w.cig_w; ++c.passes; c.punts = n2[0] > 0 ? -1 : 0;
+				for (int q = 0; q < 2 + NW_CLASSES; ++q) c.count[q] = n2[q];
+				c.list.assign((size_t)n2[0], 0); c.need.assign((size_t)n2[0], 0); c.klass.assign((size_t)n2[0], -1);
+				rt.d2h(c.list.data(), nw_list, 4 * (size_t)n2[0]); rt.d2h(c.need.data(), nw_need, 4 * (size_t)n2[0]);
+				std::vector<int32_t> pos;
+				for (int q = 0; q < NW_CLASSES; ++q) {
+					pos.assign((size_t)n2[2 + q], 0);
+					rt.d2h(pos.data(), class_list + (size_t)q * P, 4 * pos.size());
+					for (int32_t at : pos) if (at >= 0 && at < n2[0]) c.klass[(size_t)at] = q;
+				}
+				if constexpr (HasNwPunts<RT>::value) { if (n2[0] > 0) c.punts = rt.nw_punts(); }
+			}
 			if (!(e & ERR_CIGAR_OVERFLOW)) { compact(b, w); return (int)e; }
 			if (w.cig_w >= 1024) return (int)e;
 			e &= ~ERR_CIGAR_OVERFLOW; rt.h2d(w.err, &e, 4);

@@ -561,6 +561,27 @@ int arx_selftest_rfa(int32_t device, int32_t n_reads, const int64_t *reg_off, co
 int arx_selftest_seed_bins(arx_ctx *ctx, const uint8_t *bases, const int32_t *lens, int32_t n_reads, int32_t *n_launches, int32_t *rec, int32_t rec_cap,
                            int32_t *task_n, int64_t task_cap, int32_t *bin_ids, int64_t bin_cap);
 
+/* self-test of the CIGAR stage (stage 6: what arx_batch_run does last -- classification by the first band, the 16-lane kernel per band class with
+ * its band retries, the launch that takes what the class kernels hand on, the one-thread path for long regions, the retry of the whole stage with
+ * wider CIGAR slots, and the compaction behind it) on regions the caller made up.  The stage runs on a runtime of its own with ctx's index and the
+ * ARX_* switches as they are at the call.  Read r has cap[r] region slots of which the first n_regs[r] are used (0 <= n_regs[r] <= cap[r]; cap 0
+ * is allowed); regs holds one row per SLOT (sum of cap rows, slot after slot; rows of unused slots are not read) in the int64 layout of the CPU
+ * restatement (oracle/arx_oracle.h: 20 columns).  Checked before anything is uploaded (ARX_E_ARG): 0 <= lens <= 255; per used row 0 <= qb < qe
+ * <= len, 0 <= rb < re <= 2 l_pac with both ends on one strand, re - rb <= 4096, w >= 0, |truesc| and the copied fields below 2^24, at most 2^20
+ * slots -- a region bwa_gen_cigar2 rejects (bwa.c:126-134) is refused, the reference reads a score it never set there.
+ * Out: reg_off[n_reads + 1], alns (aln_cap records of arx_aln, one per used region in read order) and cigars (cig_cap words, *n_cig used) as
+ * arx_batch_fetch hands them out; *err: the batch's error word (ERR_POOL_OVERFLOW = 4: a long region's matrix did not fit, its record has rid -1
+ * and no CIGAR; ERR_CIGAR_OVERFLOW = 8: 1024 words per region did not suffice, nothing is handed out).  ARX_E_TOO_LARGE: a cap is too small.
+ * census (may be NULL: nothing is copied; else census_cap values): [0] the final CIGAR slot width  [1] passes of the slot loop; of the last pass
+ * [2] regions queued for the 16-lane kernel  [3] regions too long for it  [4..8] the queued ones per band class  [9] regions the class kernels
+ * handed on (-1: this runtime keeps no such list -- ARX_SW_SIMPLE, the host test double)  [10] n = rows that follow  [11] bit i: value [i] is
+ * known to this runtime; then n rows (index of the region among the used ones, band class, 64-byte units of traceback matrix it was given).
+ * grid_cap > 0: at most that many workgroups per class launch and two for the launch behind them (the grid-stride loops then take many regions
+ * per group, one after the other through the same LDS rows); 0: the launch shapes of arx_batch_run. */
+int arx_selftest_reg2aln(arx_ctx *ctx, const uint8_t *bases, const int32_t *lens, int32_t n_reads, const int32_t *cap, const int32_t *n_regs, const int64_t *regs,
+                         int32_t *reg_off, void *alns, int64_t aln_cap, uint32_t *cigars, int64_t cig_cap, int64_t *n_cig, uint32_t *err, int64_t *census,
+                         int64_t census_cap, int32_t grid_cap);
+
 /* self-tests of the three DP kernel families on plain host arrays (csrc/arx_selftest.hip; tests/test_dp_kernels_gpu.py): each entry
  * uploads the tasks, launches the production code on them and returns one result row per task, in input order.  The reference text is
  * passed in bwa's .pac layout (pac: (l_pac + 3) / 4 bytes, 2 bits per base, first base in the top bits); coordinates are doubled, so a

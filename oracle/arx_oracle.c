@@ -1443,6 +1443,7 @@ int ora_ksw_global2(ora_ctx_t *c, int qlen, const uint8_t *q, int tlen, const ui
 
 /* ref: bwa.c:121-207 (bwa_gen_cigar2).  Returns 0 and leaves *score untouched when the region is rejected.
  * `query` is reversed in place and restored, like the reference does. */
+static __thread int g_gc_w, g_gc_ncol; /* the band and the columns of the last call's ksw_global2 (-1, 0: the gap-free shortcut or a reject): ora_reg2aln's shape row */
 static int gen_cigar2(const index_t *ix, int w_, int l_query, uint8_t *query, int64_t rb, int64_t re, int *score, cigar_t *cig, int *NM, ora_counters_t *cnt)
 {
 	uint8_t *rseq;
@@ -1450,6 +1451,7 @@ static int gen_cigar2(const index_t *ix, int w_, int l_query, uint8_t *query, in
 	int i, ok = 0;
 	if (cig) cig->n = 0;
 	if (NM) *NM = -1;
+	g_gc_w = -1; g_gc_ncol = 0;
 	if (l_query <= 0 || rb >= re || (rb < L && re > L)) return 0;
 	rseq = get_seq(ix, rb, re, &rlen);
 	if (re - rb != rlen) goto done;
@@ -1467,6 +1469,7 @@ static int gen_cigar2(const index_t *ix, int w_, int l_query, uint8_t *query, in
 		w = w < w_? w : w_;
 		min_w = abs((int)rlen - l_query) + 3;
 		w = w > min_w? w : min_w;
+		g_gc_w = w; g_gc_ncol = l_query < 2 * w + 1? l_query : 2 * w + 1; /* ksw.c:515 */
 		*score = ksw_global2(l_query, query, (int)rlen, rseq, w, cig, cnt);
 	}
 	if (NM && cig) { /* NM = mismatches + gap bases (a leading/trailing D does not count); MD is not kept */
@@ -1915,6 +1918,7 @@ static int approx_mapq_se(const reg_t *a)
 	return mapq;
 }
 
+static __thread int64_t *g_r2a_shape; /* ora_reg2aln: where reg2aln writes its shape row (null: nowhere) */
 static aln_t reg2aln(const index_t *ix, int l_query, const uint8_t *query_, const reg_t *ar, ora_counters_t *cnt)
 {
 	aln_t a;
@@ -1937,25 +1941,29 @@ static aln_t reg2aln(const index_t *ix, int l_query, const uint8_t *query_, cons
 	do {
 		w2 = w2 < OPT_W << 2? w2 : OPT_W << 2;
 		gen_cigar2(ix, w2, qe - qb, &query[qb], rb, re, &score, &cg, &NM, cnt);
-		if (score == last_sc || w2 == OPT_W << 2) break;
+		if (g_r2a_shape) { int64_t *sh = g_r2a_shape; sh[0] = i + 1; sh[1 + i] = w2; sh[4 + i] = g_gc_w; sh[7 + i] = g_gc_ncol; sh[10 + i] = score; if (cg.n > sh[18]) sh[18] = cg.n; }
+		if (score == last_sc || w2 == OPT_W << 2) { if (g_r2a_shape) g_r2a_shape[17] = (score == last_sc? 1 : 0) | (w2 == OPT_W << 2? 2 : 0); break; }
 		last_sc = score;
 		w2 <<= 1;
 	} while (++i < 3 && score < ar->truesc - OPT_A);
+	if (g_r2a_shape) g_r2a_shape[13] = cg.n;
 	a.NM = NM;
 	pos = depos(ix, rb < ix->l_pac? rb : re - 1, &is_rev);
 	a.is_rev = is_rev;
 	if (cg.n > 0) { /* squeeze out a leading or trailing deletion */
 		if ((cg.a[0] & 0xf) == 2) {
+			if (g_r2a_shape) g_r2a_shape[14] = 1;
 			pos += cg.a[0] >> 4;
 			--cg.n;
 			memmove(cg.a, cg.a + 1, cg.n * 4);
-		} else if ((cg.a[cg.n - 1] & 0xf) == 2) --cg.n;
+		} else if ((cg.a[cg.n - 1] & 0xf) == 2) { if (g_r2a_shape) g_r2a_shape[14] = 2; --cg.n; }
 	}
 	if (qb != 0 || qe != l_query) { /* soft clips (op 3) */
 		int clip5 = is_rev? l_query - qe : qb, clip3 = is_rev? qb : l_query - qe;
 		cg.a = (uint32_t*)realloc(cg.a, 4 * (cg.n + 2));
 		if (clip5) { memmove(cg.a + 1, cg.a, cg.n * 4); cg.a[0] = (uint32_t)clip5 << 4 | 3; ++cg.n; }
 		if (clip3) cg.a[cg.n++] = (uint32_t)clip3 << 4 | 3;
+		if (g_r2a_shape) { g_r2a_shape[15] = clip5; g_r2a_shape[16] = clip3; }
 	}
 	a.n_cigar = cg.n; a.cigar = cg.a;
 	a.rid = pos2rid(ix, pos);
@@ -1964,6 +1972,34 @@ static aln_t reg2aln(const index_t *ix, int l_query, const uint8_t *query_, cons
 	a.is_alt = ar->is_alt; a.alt_sc = ar->alt_sc;
 	free(query);
 	return a;
+}
+
+/* mem_reg2aln on one region row (ORA_REG_W columns, as put_reg writes them) and its read; see arx_oracle.h */
+static void get_reg(reg_t *p, const int64_t *r)
+{
+	uint32_t fb = (uint32_t)r[18];
+	memset(p, 0, sizeof *p);
+	p->rb = r[0]; p->re = r[1]; p->qb = (int)r[2]; p->qe = (int)r[3]; p->rid = (int)r[4]; p->score = (int)r[5]; p->truesc = (int)r[6];
+	p->sub = (int)r[7]; p->alt_sc = (int)r[8]; p->csub = (int)r[9]; p->sub_n = (int)r[10]; p->w = (int)r[11]; p->seedcov = (int)r[12];
+	p->secondary = (int)r[13]; p->secondary_all = (int)r[14]; p->seedlen0 = (int)r[15]; p->n_comp = (int)r[16]; p->is_alt = (int)r[17];
+	memcpy(&p->frac_rep, &fb, 4);
+}
+
+int ora_reg2aln(ora_ctx_t *c, int l_query, const uint8_t *query, const int64_t *reg_row, int64_t *aln_row, uint32_t *cigar, int cap, int64_t *shape)
+{
+	reg_t ar;
+	aln_t a;
+	int i;
+	get_reg(&ar, reg_row);
+	for (i = 0; i < ORA_R2A_W; ++i) shape[i] = i >= 1 && i <= 12? -1 : 0;
+	g_r2a_shape = shape;
+	a = reg2aln(&c->ix, l_query, query, &ar, 0);
+	g_r2a_shape = 0;
+	aln_row[0] = a.pos; aln_row[1] = a.rid; aln_row[2] = a.flag; aln_row[3] = a.is_rev; aln_row[4] = a.is_alt; aln_row[5] = a.mapq; aln_row[6] = a.NM;
+	aln_row[7] = a.n_cigar; aln_row[8] = 0; aln_row[9] = a.score; aln_row[10] = a.sub; aln_row[11] = a.alt_sc;
+	for (i = 0; i < a.n_cigar && i < cap; ++i) cigar[i] = a.cigar[i];
+	free(a.cigar);
+	return a.n_cigar;
 }
 
 /* ------------------------------------------------------------------------------------------

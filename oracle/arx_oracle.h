@@ -96,6 +96,17 @@ int ora_ksw_global2(ora_ctx_t *c, int qlen, const uint8_t *q, int tlen, const ui
 int ora_align1(ora_ctx_t *c, int len, const uint8_t *seq, int64_t *regs, int cap);
 int64_t ora_fetch_seq(ora_ctx_t *c, int64_t *beg, int64_t mid, int64_t *end, int *rid, uint8_t *out, int64_t cap);
 
+/* mem_reg2aln (bwamem.c:1086-1156) on one region row and its read: the aln row (cigar_off 0), the CIGAR (returns n_cigar; words beyond cap are not
+ * stored) and the shape of the work, from the same run.  The row must be one bwa_gen_cigar2 accepts (bwa.c:126-134); mem_reg2aln is a pure function
+ * of (row, read, index), so any such row is legal input.  shape, ORA_R2A_W numbers:
+ *  0 bwa_gen_cigar2 calls (1..3)   1-3 the band w_ each call was given, -1: no such call   4-6 the band ksw_global2 ran with (-1: the gap-free
+ *  shortcut)   7-9 its n_col = min(l_query, 2w + 1) (0: the shortcut)   10-12 the call's score   13 n_cigar as bwa_gen_cigar2 left it (before the
+ *  squeeze and the clips)   14 a deletion was squeezed: 1 the leading one, 2 the trailing one   15, 16 clip5, clip3   17 why the loop stopped,
+ *  as bits: 1 score == last_sc, 2 the band had reached opt->w << 2 (both can hold); 0: its own condition (three calls, or a score within opt->a of truesc).
+ *  18 the largest n_cigar any of the calls left (a narrow band's detour can take more operations than the final CIGAR). */
+#define ORA_R2A_W 19
+int ora_reg2aln(ora_ctx_t *c, int l_query, const uint8_t *query, const int64_t *reg_row, int64_t *aln_row, uint32_t *cigar, int cap, int64_t *shape);
+
 /* the per-pair path */
 double ora_batch_run(ora_ctx_t *c, int64_t n_pairs, const uint8_t *seqs, const int32_t *lens, int score_delta, int n_threads);
 void ora_batch_get(ora_ctx_t *c, int64_t *n_reads, int64_t *n_regs, int64_t *n_cig, int64_t **reg_off, int64_t **regs, int64_t **alns, uint32_t **cigars);

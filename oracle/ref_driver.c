@@ -226,6 +226,28 @@ int64_t ref_fetch_seq(ref_ctx_t *c, int64_t *beg, int64_t mid, int64_t *end, int
 	return n;
 }
 
+/* mem_reg2aln (bwamem.c:1086) on one region row (the columns put_reg writes) and its 2-bit read; aln row with cigar_off 0; returns n_cigar */
+int ref_reg2aln(ref_ctx_t *c, int l_query, const uint8_t *query, const int64_t *r, int64_t *aln_row, uint32_t *cigar, int cap)
+{
+	mem_alnreg_t p;
+	mem_aln_t a;
+	uint32_t fb = (uint32_t)r[18];
+	char *q = (char*)malloc(l_query + 1);
+	int i;
+	memset(&p, 0, sizeof p);
+	p.rb = r[0]; p.re = r[1]; p.qb = (int)r[2]; p.qe = (int)r[3]; p.rid = (int)r[4]; p.score = (int)r[5]; p.truesc = (int)r[6];
+	p.sub = (int)r[7]; p.alt_sc = (int)r[8]; p.csub = (int)r[9]; p.sub_n = (int)r[10]; p.w = (int)r[11]; p.seedcov = (int)r[12];
+	p.secondary = (int)r[13]; p.secondary_all = (int)r[14]; p.seedlen0 = (int)r[15]; p.n_comp = (int)r[16]; p.is_alt = (int)r[17];
+	memcpy(&p.frac_rep, &fb, 4);
+	memcpy(q, query, l_query);
+	a = mem_reg2aln(c->opt, c->idx->bns, c->idx->pac, l_query, q, &p);
+	aln_row[0] = a.pos; aln_row[1] = a.rid; aln_row[2] = a.flag; aln_row[3] = a.is_rev; aln_row[4] = a.is_alt; aln_row[5] = a.mapq; aln_row[6] = a.NM;
+	aln_row[7] = a.n_cigar; aln_row[8] = 0; aln_row[9] = a.score; aln_row[10] = a.sub; aln_row[11] = a.alt_sc;
+	for (i = 0; i < a.n_cigar && i < cap; ++i) cigar[i] = a.cigar[i];
+	free(a.cigar); free(q);
+	return a.n_cigar;
+}
+
 /* ---------------- the per-pair path, as the Go bridge drives it ---------------- */
 
 typedef struct {

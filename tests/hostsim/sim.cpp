@@ -184,6 +184,7 @@ struct SimRT {
 
 #include "../../arachne_amd/csrc/api_impl.h"
 #include "../../arachne_amd/csrc/selftest_rfa.h"
+#include "../../arachne_amd/csrc/selftest_reg2aln.h"
 ARX_DEFINE_C_API(arx::SimRT)
 
 // test entry: the bytes of a batch's work arena that are live now (tests/test_arena_lifecycle.py: no phase grows from one cycle to the next, and
@@ -428,6 +429,18 @@ extern "C" int arx_selftest_rfa(int32_t, int32_t n_reads, const int64_t *reg_off
 	arx::SimRT rt;
 	return arx::selftest_rfa_run(rt, n_reads, reg_off, regs, alns, cigars, n_cig, lens, n_barcodes, bc_pair_off, do_rfa, penalty, l_pac, ann_off, n_seqs, cen_start, cen_end,
 	                             rfa_small, mapq_guard, cand_off, cands, cand_cap, bc_out, cls, n_host_mapq);
+}
+
+// stage 6 on given regions runs here too: the same Pipeline::stage_reg2aln, every queued region on the serial reg2aln of dev_regs.h.  Of the census
+// the double knows the slot loop (cig_w, passes), the lists the first launch fills (queued, too long, per class, nw_need); it keeps no punt list
+extern "C" int arx_selftest_reg2aln(arx_ctx *h, const uint8_t *bases, const int32_t *lens, int32_t n_reads, const int32_t *cap, const int32_t *n_regs, const int64_t *regs,
+                                    int32_t *reg_off, void *alns, int64_t aln_cap, uint32_t *cigars, int64_t cig_cap, int64_t *n_cig, uint32_t *err, int64_t *census,
+                                    int64_t census_cap, int32_t) // (grid_cap: the double has no grid)
+{
+	if (!h) return ARX_E_ARG;
+	arx::SimRT rt;
+	return arx::selftest_reg2aln_run(rt, ((arx::Context<arx::SimRT> *)h)->ix, bases, lens, n_reads, cap, n_regs, regs, reg_off, alns, aln_cap, cigars, cig_cap, n_cig, err,
+	                                 census, census_cap);
 }
 
 // test entry: the one-thread extension (dev_sw.h ext2_task, what ARX_SW_SIMPLE runs) on tasks laid out as arx_selftest_extend takes them --

@@ -174,6 +174,21 @@ class Oracle:
         n = self.lib.ora_ksw_global2(self.h, len(q), q.ctypes.data, len(t), t.ctypes.data, w, C.byref(sc), cg.ctypes.data, cap)
         return sc.value, cg[:n]
 
+    R2A_FIELDS = ["calls", "w_0", "w_1", "w_2", "w0", "w1", "w2", "n_col0", "n_col1", "n_col2", "score0", "score1", "score2", "core_n", "squeezed", "clip5", "clip3", "stop", "max_n"]
+    SQUEEZED_LEADING, SQUEEZED_TRAILING = 1, 2
+    STOP_SAME_SCORE, STOP_BAND_CAP = 1, 2   # bits of the stop column
+
+    def reg2aln(self, seq, reg_row, cap=2048):
+        """ora_reg2aln: mem_reg2aln on one region row (REG_W int64) and its read -> (aln row of ALN_W, CIGAR words, shape row of R2A_FIELDS)."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        row = np.ascontiguousarray(reg_row, dtype=np.int64)
+        assert row.shape == (REG_W,)
+        aln, cg, sh = np.zeros(ALN_W, dtype=np.int64), np.zeros(cap, dtype=np.uint32), np.zeros(len(self.R2A_FIELDS), dtype=np.int64)
+        self.lib.ora_reg2aln.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        n = self.lib.ora_reg2aln(self.h, len(seq), seq.ctypes.data, row.ctypes.data, aln.ctypes.data, cg.ctypes.data, cap, sh.ctypes.data)
+        assert 0 <= n <= cap
+        return aln, cg[:n].copy(), sh
+
     def align1(self, seq, cap=4096):
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         out = np.zeros((cap, REG_W), dtype=np.int64)

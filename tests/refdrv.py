@@ -18,6 +18,29 @@ def available() -> bool:
     return os.path.exists(REF_SO)
 
 
+def has(entry: str) -> bool:
+    """The library is there and exports `entry` (one that was built from an earlier oracle/ref_driver.c, where the reference sources are not at
+    hand to rebuild it, lacks the newer entries)."""
+    if not available():
+        return False
+    try:
+        getattr(C.CDLL(REF_SO), entry)
+    except AttributeError:
+        return False
+    return True
+
+
+def need(entry: str):
+    """For a test that calls `entry`: skip where there is no library, or one from an earlier driver that cannot be rebuilt here (no reference
+    sources); fail where the sources are present and the library still lacks the entry (the `built` fixture should have rebuilt it)."""
+    import pytest
+    if has(entry):
+        return
+    if available() and os.path.isdir("/root/reference/src/gobwa/bwa"):
+        pytest.fail(f"oracle/_ref/libbwaref.so lacks {entry} although the reference sources are present: `make -C oracle ref` did not rebuild it")
+    pytest.skip("oracle/_ref not built, or built from an earlier ref_driver.c (needs the reference sources)")
+
+
 def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
@@ -139,6 +162,17 @@ class Ref:
         cg = np.zeros(cap, dtype=np.uint32)
         n = self.lib.ref_ksw_global2(self.h, len(q), q.ctypes.data, len(t), t.ctypes.data, w, C.byref(sc), cg.ctypes.data, cap)
         return sc.value, cg[:n]
+
+    def reg2aln(self, seq, reg_row, cap=2048):
+        """ref_reg2aln: the reference's mem_reg2aln on one region row (REG_W int64) and its read -> (aln row of ALN_W, CIGAR words)."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        row = np.ascontiguousarray(reg_row, dtype=np.int64)
+        assert row.shape == (REG_W,)
+        aln, cg = np.zeros(ALN_W, dtype=np.int64), np.zeros(cap, dtype=np.uint32)
+        self.lib.ref_reg2aln.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        n = self.lib.ref_reg2aln(self.h, len(seq), seq.ctypes.data, row.ctypes.data, aln.ctypes.data, cg.ctypes.data, cap)
+        assert 0 <= n <= cap
+        return aln, cg[:n].copy()
 
     def align1(self, seq, cap=4096):
         seq = np.ascontiguousarray(seq, dtype=np.uint8)

@@ -23,6 +23,7 @@ def test_every_declared_symbol_is_exported(lib):
     names = set(re.findall(r"\b(arx_[a-z_0-9]+)\s*\(", hdr))
     assert len(names) >= 14
     assert {"arx_selftest_block", "arx_selftest_block_shape", "arx_selftest_rfa"} <= names   # the placement stage's self-test entries
+    assert "arx_selftest_reg2aln" in names   # the CIGAR stage's self-test entry
     for n in sorted(names):
         assert hasattr(lib, n), n
 
