@@ -160,6 +160,10 @@ _SELFTEST_ARGS = {
     # the sort of a FASTQ file pair by barcode
     "arx_fastq_sort": [C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_fastq_sort": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7,
+    # the .bai of a coordinate-sorted BAM file
+    "arx_bam_index": [C.c_int32, C.c_char_p, C.c_char_p, C.c_int64, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32],
+    "arx_selftest_bam_index": [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                               C.c_void_p, C.c_void_p],
 }
 
 
@@ -335,6 +339,52 @@ def selftest_fastq_sort(t1, t2, window_bytes: int = 0, slab_bytes: int = 0, devi
     l1, l2 = (int(out_len[0]), int(out_len[1])) if rc == ARX_OK else (n1, n2)
     return dict(rc=rc, out1=out1[:l1].tobytes(), out2=out2[:l2].tobytes(), rest1=out1[l1:n1].tobytes(), rest2=out2[l2:n2].tobytes(), guard1=out1[n1:].tobytes(),
                 guard2=out2[n2:].tobytes(), rec_off1=off1, rec_off2=off2, n_records=int(n_rec.value), stats=_fqsort_stats(st))
+
+
+BAI_TIMED = 0x100
+BAI_RULES = ("", "fields", "refid", "pos", "end", "order")        # the rule numbers of arx_selftest_bam_index's stats[9]
+BAI_PSEUDO_BIN, BAI_WINDOW, BAI_MAX_CONTIG = 37450, 16384, 1 << 29
+_BAI_STATS = ("records", "inflated_bytes", "blocks", "slabs", "runs", "chunks", "bins", "linear", "n_no_coor", "refused", "read_us", "inflate_us", "discover_us", "records_us",
+              "runs_us", "write_us", "total_us")
+
+
+def _bai_stats(st):
+    return {k: int(st[i]) for i, k in enumerate(_BAI_STATS)}
+
+
+def bam_index(path: str, bai_path: "str | None" = None, max_bytes: int = 0, timed: bool = False, device: int = 0, lib_path: str = LIB_PATH):
+    """The .bai of a coordinate-sorted BAM file, built on the GPU (include/arachne_amd.h: arx_bam_index, which states the index's rules):
+    bai_path defaults to path + ".bai"; max_bytes bounds the inflated bytes of a slab (0: 256 MiB).  htslib's folding of small bins into
+    their parents is not done, so the bytes are not those of `samtools index`.  -> the stats as a dict; ArachneError with .code on failure
+    (no file is left behind then)."""
+    lib = _load(lib_path)
+    st, msg = np.zeros(20, dtype=np.int64), C.create_string_buffer(1024)
+    rc = _selftest_fn(lib, "arx_bam_index")(device, os.fsencode(path), None if bai_path is None else os.fsencode(bai_path), int(max_bytes), BAI_TIMED if timed else 0,
+                                            st.ctypes.data, msg, 1024)
+    if rc != 0:
+        e = ArachneError("arx_bam_index: " + msg.value.decode(errors="replace"))
+        e.code = rc
+        raise e
+    return _bai_stats(st)
+
+
+def selftest_bam_index(stream, hdr: int, ref_len, blk_at, blk_isize, seg_bytes: int = 1 << 18, slab_bytes: int = 0, out_cap: "int | None" = None, device: int = 0,
+                       lib_path: str = LIB_PATH):
+    """The same indexing on an inflated BAM stream in memory with a block table given (include/arachne_amd.h: arx_selftest_bam_index)
+    -> (rc: the entry's return value, the .bai's bytes (empty unless rc is 0), stats; stats["refused"]: record << 8 | rule where a record
+    rule refused the stream)."""
+    lib = _load(lib_path)
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    n = len(src)
+    lens, at, isize = _arr(ref_len, np.int32), _arr(blk_at, np.int64), _arr(blk_isize, np.int32)
+    assert len(at) == len(isize) + 1
+    cap = 64 + 64 * len(lens) + 24 * (n // 36 + 1) + 8 * int(sum((int(l) + 16383) >> 14 for l in lens if 0 < l <= BAI_MAX_CONTIG)) if out_cap is None else out_cap
+    out = np.full(cap + 8, 0xA5, dtype=np.uint8)
+    out_len, st = C.c_int64(-1), np.zeros(20, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_bam_index")(device, src.ctypes.data if n else None, n, int(hdr), len(lens), lens.ctypes.data if len(lens) else None, len(isize), at.ctypes.data,
+                                                     isize.ctypes.data if len(isize) else None, int(seg_bytes), int(slab_bytes), out.ctypes.data, cap, C.byref(out_len), st.ctypes.data)
+    assert out[cap:].tobytes() == b"\xa5" * 8
+    return rc, (out[:out_len.value].tobytes() if rc == 0 else b""), _bai_stats(st)
 
 
 INFLATE_STATUS = ("OK", "BAD_HEADER", "BAD_BTYPE", "BAD_STORED_LEN", "BAD_CODE_LENGTHS", "BAD_SYMBOL", "BAD_DISTANCE", "TRUNCATED", "SIZE_MISMATCH", "CRC_MISMATCH")
@@ -1176,6 +1226,7 @@ class Reference:
     def __init__(self, prefix: str, device: int = 0, lib_path: str = LIB_PATH):
         self.lib = _load(lib_path)
         self.h = C.c_void_p()
+        self.device = device                # for the entries that take a device, not a context (bam_index)
         rc = self.lib.arx_open(prefix.encode(), device, C.byref(self.h))
         if rc != 0:
             msg = self.lib.arx_last_error(None).decode()

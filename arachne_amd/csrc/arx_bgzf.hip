@@ -2,7 +2,8 @@
 // hip_bgzf.h behind its seam.  Its own unit: the kernels of dev_bgzf.h compile next to the pipeline's.  The mirror image lives here too: the
 // inflate kernel of hip_inflate.h (arx_selftest_inflate; the device feeder starts it through inflate_launch).  And what needs both: the coordinate
 // sort of a BAM file into an open writer (arx_bam_open_ex, arx_bam_sort_append, arx_selftest_bam_sort: dev_bamsort.h, hip_bamsort.h), and the sort
-// of a FASTQ file pair by barcode (arx_fastq_sort, arx_selftest_fastq_sort: dev_fqsort.h, hip_fqsort.h).
+// of a FASTQ file pair by barcode (arx_fastq_sort, arx_selftest_fastq_sort: dev_fqsort.h, hip_fqsort.h), and the .bai of a coordinate-sorted
+// BAM file (arx_bam_index, arx_selftest_bam_index: dev_bamindex.h, hip_bamindex.h).
 #include <map>
 #include <memory>
 #include <mutex>
@@ -11,6 +12,7 @@
 #include "hip_inflate.h"
 #include "hip_bamsort.h"
 #include "hip_fqsort.h"
+#include "hip_bamindex.h"
 
 namespace arx {
 
@@ -338,6 +340,81 @@ extern "C" int arx_selftest_fastq_sort(int32_t device, const uint8_t *t1, int64_
 		*n_records = N;
 		arx::fs_stats(stats, drv, c, n1, n2, true);
 	} catch (const arx::FsTooLarge &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::HipOutOfMemory &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}
+
+// ---- the .bai of a coordinate-sorted BAM file (dev_bamindex.h, hip_bamindex.h)
+extern "C" int arx_bam_index(int32_t device, const char *bam_path, const char *bai_path, int64_t max_bytes, int32_t flags, int64_t *stats, char *msg, int32_t msg_cap)
+{
+	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
+	if (stats) for (int k = 0; k < arx::BI_N_STATS; ++k) stats[k] = 0;
+	if (flags & ~ARX_BAI_TIMED) { say("arx_bam_index: unknown flag bits"); return ARX_E_ARG; }
+	if (!bam_path || max_bytes < 0) { say("arx_bam_index: bad arguments"); return ARX_E_ARG; }
+	std::string err;
+	try {
+		const int rc = arx::bi_index_file(device, bam_path, bai_path, max_bytes, (flags & ARX_BAI_TIMED) != 0, stats, err);
+		if (rc != ARX_OK) say(err);
+		return rc;
+	} catch (const arx::BsTooLarge &e) {
+		say(e.what());
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::HipOutOfMemory &e) { // any buffer of a slab (hip_res.h)
+		say("the device memory does not hold a slab of this file (" + std::to_string(e.wanted >> 20) + " MiB more were asked for): use a smaller max_bytes");
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &e) {
+		say(e.what());
+		return ARX_E_DEVICE;
+	}
+}
+
+extern "C" int arx_selftest_bam_index(int32_t device, const uint8_t *stream, int64_t n_bytes, int64_t hdr, int32_t n_ref, const int32_t *ref_len, int64_t n_blocks,
+                                      const int64_t *blk_at, const int32_t *blk_isize, int64_t seg_bytes, int64_t slab_bytes, uint8_t *out, int64_t out_cap, int64_t *out_len,
+                                      int64_t *stats)
+{
+	if (n_bytes < 0 || hdr < 0 || hdr > n_bytes || n_ref < 0 || (n_ref > 0 && !ref_len) || n_blocks < 0 || !blk_at || (n_blocks > 0 && !blk_isize) || seg_bytes < arx::BS_MIN_SEG ||
+	    (seg_bytes & (seg_bytes - 1)) || slab_bytes < 0 || out_cap < 0 || (out_cap > 0 && !out) || !out_len || (n_bytes > 0 && !stream))
+		return ARX_E_ARG;
+	*out_len = 0;
+	if (stats) for (int k = 0; k < arx::BI_N_STATS; ++k) stats[k] = 0;
+	int64_t sum = 0;
+	for (int64_t b = 0; b < n_blocks; ++b) {
+		if (blk_isize[b] < 0 || blk_isize[b] > arx::INF_MAX_OUT || blk_at[b] > blk_at[b + 1]) return ARX_E_ARG;
+		sum += blk_isize[b];
+	}
+	if (sum != n_bytes || arx::bi_long_contig(n_ref, ref_len) >= 0) return ARX_E_ARG;
+	for (int32_t i = 0; i < n_ref; ++i)
+		if (ref_len[i] < 0) return ARX_E_ARG;
+	arx::BiBlocks B;
+	if (!B.build(n_blocks, blk_at, blk_isize, slab_bytes)) return ARX_E_ARG;
+	try {
+		arx::select_device(device, arx::BI_NO_DEVICE);
+		arx::Stream st;
+		st.create();
+		arx::BiHipDrv drv; drv.st = st;
+		const double t0 = arx::bs_now_us();
+		arx::DevBuf d_s((size_t)n_bytes);
+		drv.upload(d_s.p, stream, (size_t)n_bytes);
+		arx::BiIndex ix;
+		arx::BiMemSrc src{drv, d_s.as<uint8_t>(), B};
+		std::string err;
+		const int rc = arx::bi_result(arx::bi_run(drv, src, B, hdr, n_ref, ref_len, seg_bytes, ix), ix, "the stream", err);
+		if (rc != ARX_OK) {
+			if (stats) stats[9] = (int64_t)ix.err; // the first offending record's number << 8 | the rule, or -1
+			return rc;
+		}
+		const std::vector<uint8_t> bai = arx::bi_serialise(ix);
+		if ((int64_t)bai.size() > out_cap) return ARX_E_TOO_LARGE;
+		memcpy(out, bai.data(), bai.size());
+		*out_len = (int64_t)bai.size();
+		drv.us[arx::BI_T_TOTAL] = arx::bs_now_us() - t0;
+		arx::bi_stats(stats, drv, ix, n_bytes, n_blocks);
+	} catch (const arx::BsTooLarge &) {
 		return ARX_E_TOO_LARGE;
 	} catch (const arx::HipOutOfMemory &) {
 		return ARX_E_TOO_LARGE;

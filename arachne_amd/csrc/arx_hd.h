@@ -15,6 +15,7 @@
 #define ARX_ATOMIC_ADD64(p, v) atomicAdd((unsigned long long *)(p), (unsigned long long)(v))
 #define ARX_ATOMIC_MIN64(p, v) atomicMin((long long *)(p), (long long)(v))
 #define ARX_ATOMIC_MAX64(p, v) atomicMax((long long *)(p), (long long)(v))
+#define ARX_ATOMIC_MINU64(p, v) atomicMin((unsigned long long *)(p), (unsigned long long)(v))
 // plain read of a word other lanes of the workgroup update with atomics (which execute in L2): bypass the per-CU L1
 #define ARX_LOAD_SHARED(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #else
@@ -29,6 +30,7 @@
 #define ARX_ATOMIC_ADD64(p, v) (*(p) += (v))
 #define ARX_ATOMIC_MIN64(p, v) (*(p) = *(p) < (v) ? *(p) : (v))
 #define ARX_ATOMIC_MAX64(p, v) (*(p) = *(p) > (v) ? *(p) : (v))
+#define ARX_ATOMIC_MINU64(p, v) (*(p) = *(p) < (v) ? *(p) : (v))
 #define ARX_LOAD_SHARED(p) (*(p))
 static inline int arx_host_fetch_add(int32_t *p, int v) { int o = *p; *p += v; return o; }
 static inline int arx_host_cas(int32_t *p, int c, int v) { int o = *p; if (o == c) *p = v; return o; }

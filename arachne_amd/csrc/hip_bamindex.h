@@ -1,0 +1,198 @@
+// hip_bamindex.h -- dev_bamindex.h on the GPU, and the drivers behind arx_bam_index and arx_selftest_bam_index (arx_bgzf.hip): one coordinate-
+// sorted BAM file, its blocks inflated on the device slab by slab (inflate_launch over the rows of bgzf_walk, as the sort's copy mode), indexed
+// there by bi_run, and the .bai written as <path>.tmp and renamed.
+//
+//   k_bs_items<F>    hip_bamsort.h's kernel: one item of a functor per thread (bi_tail: the one last record; bi_rec, bi_flag, bi_runs: a record;
+//                    bi_head, bi_chunks: a run), started through hip_launch under the functor's name
+// The run sort is rocprim::radix_sort_pairs over the key bits that can differ (bi_key_bits), the prefix sums are rocprim's scan.  The stream,
+// every buffer and rocprim's scratch are owners of hip_res.h.
+//
+// Memory: the compressed file in host memory whole (BsFile); on the device the linear table (8 bytes per 16384 bases of the contigs) for the
+// whole call, and one slab at a time: its compressed and inflated bytes, the carry in front, 16 bytes per block, 56 per record, about 100 per run.
+#pragma once
+#include <stdio.h>
+#include "hip_bamsort.h"
+#include "dev_bamindex.h"
+
+namespace arx {
+
+constexpr int BI_N_STATS = 20;
+enum { BI_T_READ = 10, BI_T_INFLATE, BI_T_DISCOVER, BI_T_RECORDS, BI_T_RUNS, BI_T_WRITE, BI_T_TOTAL };
+constexpr const char *BI_NO_DEVICE = "no such HIP device: the BAM index is built on the GPU (there is no CPU fallback)";
+
+// dev_bamindex.h's driver on a stream
+struct BiHipDrv {
+	typedef DevBuf Buf;
+	hipStream_t st = nullptr;
+	bool timed = false; // wait for every launch and book its time under its phase
+	double us[BI_N_STATS] = {0};
+	DevScratch tmp;
+
+	static int phase_of(const char *nm)
+	{
+		if (!strncmp(nm, "bs_", 3)) return BI_T_DISCOVER;
+		if (!strcmp(nm, "bi_tail") || !strcmp(nm, "bi_rec") || !strcmp(nm, "bi_flag")) return BI_T_RECORDS;
+		return BI_T_RUNS;
+	}
+	template <class Fn> void booked(const char *nm, Fn fn)
+	{
+		if (!timed) { fn(); return; }
+		ARX_HIP_CHECK(hipStreamSynchronize(st));
+		const double t0 = bs_now_us();
+		fn();
+		ARX_HIP_CHECK(hipStreamSynchronize(st));
+		us[phase_of(nm)] += bs_now_us() - t0;
+	}
+	template <class F> void items(const char *nm, int64_t n, const F &f)
+	{
+		if (n <= 0) return;
+		const int64_t grid = (n + 255) / 256;
+		if (grid > 0x7fffffff) throw BsTooLarge("too many items for one launch: use a smaller max_bytes");
+		booked(nm, [&]() { hip_launch({"k_bs_items", nm}, k_bs_items<F>, dim3((unsigned)grid), dim3(256), 0, st, f, n); });
+	}
+	void scan(const int64_t *in, int64_t *out, int64_t n, const char *nm = "bs_scan")
+	{
+		put(&out[0], 0);
+		if (n <= 0) return;
+		booked(nm, [&]() { dev_two_pass(tmp, "rocprim::inclusive_scan", [&](void *t, size_t &tb) { return rocprim::inclusive_scan(t, tb, in, out + 1, (size_t)n, rocprim::plus<int64_t>(), st); }); });
+	}
+	int64_t get(const int64_t *p) { return dev_get(p, st); }
+	void put(int64_t *p, int64_t v) { upload(p, &v, 8); }
+	void sort_pairs(const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout, int64_t n, int bits) { booked("bi_sort", [&]() { dev_sort_pairs(tmp, kin, kout, vin, vout, (size_t)n, bits, st); }); }
+	void upload(void *d, const void *h, size_t n) // h may leave scope when this returns: the copy has read it by then
+	{
+		if (!n) return;
+		ARX_HIP_CHECK(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, st));
+		ARX_HIP_CHECK(hipStreamSynchronize(st));
+	}
+	void fetch(void *h, const void *d, size_t n)
+	{
+		if (!n) return;
+		ARX_HIP_CHECK(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, st));
+		ARX_HIP_CHECK(hipStreamSynchronize(st));
+	}
+	void copy(void *d, const void *s, size_t n) { if (n) ARX_HIP_CHECK(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, st)); }
+	void fill(void *d, int byte, size_t n) { if (n) ARX_HIP_CHECK(hipMemsetAsync(d, byte, n, st)); }
+};
+
+inline void bi_stats(int64_t *stats, const BiHipDrv &drv, const BiIndex &ix, int64_t bytes, int64_t blocks)
+{
+	if (!stats) return;
+	stats[0] = ix.n_records; stats[1] = bytes; stats[2] = blocks; stats[3] = ix.n_slabs; stats[4] = ix.n_runs; stats[5] = ix.n_chunks; stats[6] = ix.n_bins;
+	stats[7] = ix.n_lin; stats[8] = ix.n_no_coor;
+	for (int k = BI_T_READ; k <= BI_T_TOTAL; ++k) stats[k] = (int64_t)drv.us[k];
+}
+
+inline std::string bi_long_text(int32_t i, int64_t len)
+{
+	return "contig " + std::to_string(i) + " has " + std::to_string(len) + " bases, more than the 2^29 a BAI index can hold (the CSI format is not built)";
+}
+
+// a slab of the selftest: the stream lies in device memory already
+struct BiMemSrc {
+	BiHipDrv &drv; const uint8_t *d_stream; const BiBlocks &B;
+	bool load(int64_t k, uint8_t *dst, int64_t n) { drv.copy(dst, d_stream + B.cut_o[(size_t)k], (size_t)n); return true; }
+};
+// a slab of a file: its blocks uploaded and inflated where the buffer wants them
+struct BiFileSrc {
+	BiHipDrv &drv; const BsFile &file; const BiBlocks &B;
+	DevBuf d_comp, d_rows, d_status;
+	bool load(int64_t k, uint8_t *dst, int64_t n)
+	{
+		const double t0 = bs_now_us();
+		const int64_t b0 = B.cut_b[(size_t)k], b1 = B.cut_b[(size_t)k + 1], c0 = file.at[(size_t)b0], c1 = file.at[(size_t)b1], a = B.cut_o[(size_t)k];
+		std::vector<InfRow> rows(file.rows.begin() + b0, file.rows.begin() + b1);
+		for (InfRow &r : rows) { r.coff -= c0; r.ooff -= a; }
+		d_comp.alloc((size_t)(c1 - c0));
+		d_rows.alloc(rows.size() * sizeof(InfRow));
+		d_status.alloc(4 * (rows.size() + 2));
+		ARX_HIP_CHECK(hipMemcpyAsync(d_comp.p, file.raw.data() + c0, (size_t)(c1 - c0), hipMemcpyHostToDevice, drv.st));
+		ARX_HIP_CHECK(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * sizeof(InfRow), hipMemcpyHostToDevice, drv.st));
+		ARX_HIP_CHECK(hipMemsetAsync(d_status.p, 0, 4 * (rows.size() + 2), drv.st));
+		int32_t *counts = d_status.as<int32_t>() + rows.size();
+		for (size_t r0 = 0; r0 < rows.size(); r0 += (size_t)1 << 20) { // many blocks a launch
+			const size_t nr = rows.size() - r0 < ((size_t)1 << 20) ? rows.size() - r0 : (size_t)1 << 20;
+			inflate_launch(drv.st, d_comp.as<uint8_t>(), c1 - c0, d_rows.as<InfRow>() + r0, (int)nr, dst, n, d_status.as<int32_t>() + r0, counts);
+		}
+		int32_t bad[2] = {0, 0};
+		ARX_HIP_CHECK(hipMemcpyAsync(bad, counts, 8, hipMemcpyDeviceToHost, drv.st));
+		ARX_HIP_CHECK(hipStreamSynchronize(drv.st)); // rows and bad are the host's
+		d_comp.release();
+		drv.us[BI_T_INFLATE] += bs_now_us() - t0;
+		return bad[0] == 0;
+	}
+};
+
+// bi_run's result as one of ARX_*, with the text
+inline int bi_result(int rc, const BiIndex &ix, const std::string &what, std::string &err)
+{
+	if (rc == BI_OK) return ARX_OK;
+	if (rc == BI_E_RULE) {
+		err = what + ": " + bi_rule_text(ix.err);
+		return (ix.err & 0xff) == BI_R_FIELDS ? ARX_E_IO : ARX_E_ARG;
+	}
+	err = what + (rc == BI_E_INFLATE ? ": a BGZF block does not inflate" : ": the chain of BAM records is broken");
+	return ARX_E_IO;
+}
+
+// -> ARX_*; err: the text
+inline int bi_index_file(int device, const char *path, const char *bai_path, int64_t max_bytes, bool timed, int64_t *stats, std::string &err)
+{
+	const double t_begin = bs_now_us();
+	BsFile file;
+	if (!file.load(path, err)) return ARX_E_IO;
+	const int64_t nb = (int64_t)file.rows.size();
+	// the header, by zlib from the first blocks
+	std::vector<uint8_t> head;
+	std::vector<int32_t> ref_len;
+	int64_t hdr = 0;
+	int32_t n_ref = 0;
+	for (size_t b = 0;; ++b) {
+		int64_t need = 0;
+		ref_len.clear();
+		const int rc = bs_parse_header(head.data(), (int64_t)head.size(), &need, &n_ref, [&](int32_t, const char *, int64_t, int32_t len) { ref_len.push_back(len); });
+		if (rc == 1) { hdr = need; break; }
+		if (rc < 0) { err = std::string(path) + " does not start with a BAM header"; return ARX_E_IO; }
+		if ((int64_t)b >= nb) { err = std::string(path) + ": the BAM header is cut short"; return ARX_E_IO; }
+		if (!file.host_inflate(b, head)) { err = std::string(path) + ": BGZF block " + std::to_string(b) + " does not inflate"; return ARX_E_IO; }
+	}
+	if (hdr > file.total) { err = std::string(path) + ": the BAM header is cut short"; return ARX_E_IO; }
+	const int32_t too_long = bi_long_contig(n_ref, ref_len.data());
+	if (too_long >= 0) { err = std::string(path) + ": " + bi_long_text(too_long, ref_len[(size_t)too_long]); return ARX_E_ARG; }
+	std::vector<int32_t> isize((size_t)nb);
+	for (int64_t b = 0; b < nb; ++b) isize[(size_t)b] = file.rows[(size_t)b].isize;
+	BiBlocks B;
+	if (!B.build(nb, file.at.data(), isize.data(), max_bytes > 0 ? max_bytes : BS_SLAB_DEFAULT)) {
+		err = std::string(path) + " is 2^48 bytes or longer: a virtual offset cannot address it"; return ARX_E_ARG;
+	}
+
+	select_device(device, BI_NO_DEVICE);
+	Stream st; // the call's own; declared before the buffers, so that it has ended when they are freed
+	st.create();
+	BiHipDrv drv; drv.st = st; drv.timed = timed;
+	drv.us[BI_T_READ] = bs_now_us() - t_begin;
+	BiIndex ix;
+	{
+		BiFileSrc src{drv, file, B};
+		const int rc = bi_result(bi_run(drv, src, B, hdr, n_ref, ref_len.data(), BS_SEG_DEFAULT, ix), ix, path, err);
+		if (rc != ARX_OK) return rc;
+	}
+	const double t_w = bs_now_us();
+	const std::vector<uint8_t> out = bi_serialise(ix);
+	const std::string final_path = bai_path ? std::string(bai_path) : std::string(path) + ".bai", tmp_path = final_path + ".tmp";
+	FILE *f = fopen(tmp_path.c_str(), "wb");
+	if (!f) { err = "cannot write " + tmp_path; return ARX_E_IO; }
+	const bool wrote = fwrite(out.data(), 1, out.size(), f) == out.size();
+	const bool closed = fclose(f) == 0;
+	if (!wrote || !closed || rename(tmp_path.c_str(), final_path.c_str()) != 0) {
+		remove(tmp_path.c_str());
+		err = "cannot write " + final_path;
+		return ARX_E_IO;
+	}
+	drv.us[BI_T_WRITE] = bs_now_us() - t_w;
+	drv.us[BI_T_TOTAL] = bs_now_us() - t_begin;
+	bi_stats(stats, drv, ix, file.total, nb);
+	return ARX_OK;
+}
+
+} // namespace arx

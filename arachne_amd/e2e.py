@@ -213,12 +213,13 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
 
 
 def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "host", chunk: int = 40_000_000, read_groups: str = "", bam_threads: int = 8,
-             level: int = 1, max_bytes: int = 0, lib_path: str = api.LIB_PATH):
+             level: int = 1, max_bytes: int = 0, lib_path: str = api.LIB_PATH, index: bool = False):
     """The step the position buckets exist for: out_dir is a reference-layout directory (run(layout="reference") with the same chunk); every
     bucket of api.bucket_table that was written is sorted by coordinate on ref's GPU (BamWriter.sort_append) and appended, in table order, to ONE
     writer with reference_header(read_groups) and SO:coordinate; the unmapped file, which is its own sorted form (refID = pos = -1 throughout),
     is appended in copy mode.  Buckets hold disjoint, ascending ranges of (contig, position), so the concatenation is sorted.  sink as in run.
-    -> dict(records, buckets, bytes, seconds, sort: the per-file stats)."""
+    -> dict(records, buckets, bytes, seconds, sort: the per-file stats).  index=True: the closed file's .bai is written beside it
+    (final_path + ".bai", api.bam_index on ref's device -- one more read of the file); the dict gains index (its stats) and index_seconds."""
     if sink not in ("host", "device"):
         raise ValueError(f"unknown sink {sink!r}")
     names, offs, clens, alt, l_pac = ref.contigs()
@@ -236,7 +237,12 @@ def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "hos
             per.append(dict(file=f, **w.sort_append(ref, p, mode="copy" if unmapped else "coordinate", max_bytes=max_bytes)))
     finally:
         st = w.close()
-    return dict(records=st["records"], buckets=len(per), bytes=st["bytes_out"], seconds=time.time() - t, sort=per)
+    out = dict(records=st["records"], buckets=len(per), bytes=st["bytes_out"], seconds=time.time() - t, sort=per)
+    if index:
+        t = time.time()
+        out["index"] = api.bam_index(final_path, device=ref.device, lib_path=lib_path)
+        out["index_seconds"] = time.time() - t
+    return out
 
 
 def presort(r1: str, r2: str, out_dir: str, device: int = 0, bgzf: bool = False, if_needed: bool = True, lib_path: str = api.LIB_PATH):

@@ -336,6 +336,55 @@ int arx_bam_sort_append(arx_ctx *ctx, arx_bam *w, const char *in_path, int32_t m
 int arx_selftest_bam_sort(int32_t device, const uint8_t *stream, int64_t n_bytes, int32_t n_ref, int64_t seg_bytes, int32_t mode, uint8_t *out, int64_t *rec_off,
                           int64_t *n_records, int64_t *stats);
 
+/* ---- beside the final BAM: its .bai (the SAM specification, 5.2), built on the GPU (csrc/dev_bamindex.h, hip_bamindex.h).  device: a HIP
+ * device index -- no context is needed, the contigs are the BAM header's own.  The file must be sorted by coordinate, as arx_bam_sort_append
+ * leaves it.  Its BGZF blocks are inflated on the device in slabs of whole blocks that inflate to at most max_bytes (0: 256 MiB; at least one
+ * block), the record starts found by the sort's discovery, and every record indexed by one lane.  The contract:
+ *   virtual offsets  the file's blocks are b = 0 .. nb-1; at[b] is a block's file offset, ooff[b] where its bytes start in the inflated stream,
+ *             isize[b] its inflated size.  For an inflated offset o < total, b is the one block with ooff[b] <= o < ooff[b] + isize[b] (empty
+ *             blocks hold nothing) and V(o) = at[b] << 16 | (o - ooff[b]).  V(total) = at[b'] << 16 with b' the first block behind the last
+ *             non-empty one (normally the EOF block), or the file size where there is none.  A record that starts at o and is followed by one
+ *             at o' occupies [V(o), V(o')); the last record ends at V(total).  at must stay below 2^48
+ *   interval  beg = pos; end = pos + 1 where flag bit 4 is set, n_cigar_op is 0 or the operations consume no reference, otherwise pos + the
+ *             summed lengths of the operations M, D, N, = and X (0, 2, 3, 7, 8); bin = reg2bin(beg, end) as the specification's 5.3 states it.
+ *             The record's own bin field is not read, and the CG-tag form of CIGARs above 65,535 operations is not interpreted
+ *   chunks    in file order a run is a maximal sequence of consecutive records with the same (refID, bin), from its first record's begin to
+ *             its last record's end; the runs of one bin, in file order, are its chunks; two neighbouring chunks are joined when
+ *             (earlier.end >> 16) >= (later.beg >> 16) -- a reader that has reached the block where the earlier ends gains nothing from a
+ *             seek.  Bins are written in ascending order of their number.  htslib's folding of small bins into their parents is NOT done
+ *             (the index is valid without it): byte equality with `samtools index` is not claimed and was never checked
+ *   pseudo-bin 37450  last in every contig that holds a record: (V(first record), end of the last record) and (records without flag bit 4,
+ *             records with it)
+ *   linear    windows of 16,384 bases; a record sets the windows beg >> 14 .. (end - 1) >> 14; a window's value is the smallest V(start) among
+ *             the records that set it; n_intv = 1 + the highest window set in the contig; an unset window below that takes the value of the
+ *             next set window above it.  A contig without records has n_bin = 0 and n_intv = 0
+ *   trailer   n_no_coor, the number of records with refID = -1, is always written
+ * Refused, with nothing written and no partial file left (the index is written as <bai>.tmp and renamed at the end):
+ *   ARX_E_ARG  msg names the record (numbered from 0 in file order) and the rule: the keys ((uint32_t)refID, pos) are not non-decreasing, also
+ *             across a slab border; a refID outside [-1, n_ref); refID >= 0 with pos < 0; an end beyond the record's contig length.  Also: a
+ *             contig longer than 2^29, the BAI format's limit (the CSI format is not built); a file of 2^48 bytes or more; unknown flag bits
+ *   ARX_E_IO  the file is unreadable or not BGZF, a block does not inflate, there is no BAM header, the chain of block_size fields breaks or
+ *             does not end with the stream, a record's name and CIGAR do not fit into its block_size, or the index cannot be written
+ *   ARX_E_DEVICE  there is no such device, or a HIP error: there is no CPU fallback.  ARX_E_TOO_LARGE: a slab does not fit the device memory
+ * stats[20] (may be NULL): [0] records, [1] inflated bytes, [2] BGZF blocks, [3] slabs, [4] runs of records with a refID, [5] chunks written,
+ * [6] bins written without the pseudo-bins, [7] linear entries written, [8] n_no_coor; microseconds: [10] read and header, [11] upload and
+ * inflate, [15] serialise and write, [16] the call; with ARX_BAI_TIMED, which waits for every launch, also [12] discovery, [13] the record
+ * kernels, [14] run scans, sort and merge (with the fetch of the chunks). */
+enum { ARX_BAI_TIMED = 0x100 };
+int arx_bam_index(int32_t device, const char *bam_path, const char *bai_path /* NULL: bam_path + ".bai" */,
+                  int64_t max_bytes /* inflated bytes of a slab; 0: 256 MiB */, int32_t flags /* ARX_BAI_TIMED or 0 */,
+                  int64_t *stats /* [20], may be NULL */, char *msg, int32_t msg_cap);
+/* self-test of the same indexing on an inflated stream in host memory, no file needed (tests/test_bam_index_gpu.py): stream[0..n_bytes) is the
+ * BAM's inflated bytes, records from hdr on; the contigs; the block table the virtual offsets are made of (blk_at: n_blocks + 1 file offsets,
+ * the last the file's size; blk_isize sums to n_bytes); seg_bytes: the discovery's segment (a power of two, at least 64); slab_bytes: the
+ * inflated bytes of a slab (0: one slab; otherwise whole blocks, at least one).  out[0..*out_len) receives the .bai's bytes (ARX_E_TOO_LARGE:
+ * out_cap is too small).  Codes as above, without a text; on a refusal by a record rule stats[9] is the record's number << 8 | the rule
+ * (1 fields, 2 refID, 3 pos, 4 end, 5 order). */
+int arx_selftest_bam_index(int32_t device, const uint8_t *stream, int64_t n_bytes, int64_t hdr,
+                  int32_t n_ref, const int32_t *ref_len,
+                  int64_t n_blocks, const int64_t *blk_at /* n_blocks + 1 file offsets */, const int32_t *blk_isize /* sum = n_bytes */,
+                  int64_t seg_bytes, int64_t slab_bytes, uint8_t *out, int64_t out_cap, int64_t *out_len, int64_t *stats);
+
 /* ---- in front of the feeder: a FASTQ file pair sorted by barcode on the GPU -- the reference's `arachne preprocess`
  * (src/preprocess/preprocess.go:42-114: samtools import -T '*' | samtools sort -t BX | samtools fastq -T '*'), which the aligner needs: the
  * feeder opens a new barcode set wherever the barcode changes, so a barcode that returns later in the file would be placed as several

@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""The .bai of a coordinate-sorted BAM file on the GPU (arx_bam_index), phase by phase, next to the sort that made the file.
+
+The bucket of tools/bam_sort_bench.py (--records typical 2x150 bp records on random positions of one contig, written by the host sink) is
+sorted into one file by arx_bam_sort_append (host writer), and that file is indexed.  One JSON line per measurement:
+  append   arx_bam_sort_append of the bucket into the host writer: the seconds of the call and of the close that follows
+  index    arx_bam_index of the sorted file, plain and with ARX_BAI_TIMED (which waits for every launch): the phases in ms, the counts
+           of runs, chunks, bins and linear entries, and max_bytes (0: the 256 MiB default; --slab sets a second size)
+Usage: bam_index_bench.py [--records 2000000] [--repeats 3] [--slab 33554432]"""
+import argparse
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from arachne_amd import api, synth
+from bam_sort_bench import make_bucket
+
+PHASES = ("read", "inflate", "discover", "records", "runs", "write", "total")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--records", type=int, default=2_000_000)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--slab", type=int, default=32 << 20)
+    args = ap.parse_args()
+    tmp = "/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir()
+    d = tempfile.mkdtemp(prefix="arx_index_bench_", dir=tmp)
+    try:
+        g = synth.make_genome(15, [400000, 150000])
+        fa = os.path.join(d, "g.fa")
+        g.write_fasta(fa)
+        api.index_build(fa, fa)
+        ref = api.Reference(fa)
+        names, offs, clens, alt, l_pac = ref.contigs()
+        bucket, final = os.path.join(d, "bucket.bam"), os.path.join(d, "sorted.bam")
+        made = make_bucket(bucket, ref, args.records)
+        print(json.dumps(dict(what="input", records=made["records"], file_bytes=made["bytes_out"])), flush=True)
+        for rep in range(args.repeats + 1):                     # pass 0 is not counted: code objects, rocprim's first calls
+            w = api.BamWriter(final, names, clens, extra_header="@PG\tID:bench\n", threads=16, level=1, coordinate=True)
+            t = time.time()
+            st = w.sort_append(ref, bucket)
+            dt = time.time() - t
+            t = time.time()
+            closed = w.close()
+            print(json.dumps(dict(what="append", counted=rep > 0, seconds=round(dt, 4), close_seconds=round(time.time() - t, 4), file_bytes=closed["bytes_out"],
+                                  inflated_bytes=st["inflated_bytes"])), flush=True)
+        for rep in range(args.repeats + 1):
+            for max_bytes in (0, args.slab):
+                for timed in (False, True):
+                    t = time.time()
+                    st = api.bam_index(final, max_bytes=max_bytes, timed=timed, device=ref.device)
+                    dt = time.time() - t
+                    assert st["records"] == args.records
+                    print(json.dumps(dict(what="index", counted=rep > 0, max_bytes=max_bytes, timed=timed, seconds=round(dt, 4), slabs=st["slabs"], blocks=st["blocks"],
+                                          runs=st["runs"], chunks=st["chunks"], bins=st["bins"], linear=st["linear"], bai_bytes=os.path.getsize(final + ".bai"),
+                                          ms={p: round(st[p + "_us"] / 1e3, 3) for p in PHASES})), flush=True)
+        ref.close()
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
