@@ -160,6 +160,8 @@ _SELFTEST_ARGS = {
     # the sort of a FASTQ file pair by barcode
     "arx_fastq_sort": [C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_fastq_sort": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7,
+    "arx_fastq_sort_ex": [C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int64, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int32],
+    "arx_selftest_fastq_sort_ext": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7,
     # the .bai of a coordinate-sorted BAM file
     "arx_bam_index": [C.c_int32, C.c_char_p, C.c_char_p, C.c_int64, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_bam_index": [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
@@ -339,6 +341,49 @@ def selftest_fastq_sort(t1, t2, window_bytes: int = 0, slab_bytes: int = 0, devi
     l1, l2 = (int(out_len[0]), int(out_len[1])) if rc == ARX_OK else (n1, n2)
     return dict(rc=rc, out1=out1[:l1].tobytes(), out2=out2[:l2].tobytes(), rest1=out1[l1:n1].tobytes(), rest2=out2[l2:n2].tobytes(), guard1=out1[n1:].tobytes(),
                 guard2=out2[n2:].tobytes(), rec_off1=off1, rec_off2=off2, n_records=int(n_rec.value), stats=_fqsort_stats(st))
+
+
+_FQSORT_EX_STATS = _FQSORT_STATS + ("sorted_runs", "tmp_bytes", "run_write_us", "run_read_us")
+
+
+def fastq_sort_ex(r1: str, r2: str, r1_out: "str | None" = None, r2_out: "str | None" = None, bgzf: bool = False, check: bool = False, timed: bool = False,
+                  max_bytes: int = 0, run_bytes: int = 0, tmp_dir: "str | None" = None, device: int = 0, lib_path: str = LIB_PATH):
+    """fastq_sort for a file pair that device memory does not hold (include/arachne_amd.h: arx_fastq_sort_ex): sorted runs of run_bytes of
+    inflated text per file go to temporary files under tmp_dir (None: r1_out's directory) and are merged on the GPU; the same output
+    bytes.  run_bytes 0: fastq_sort itself; -1: chosen from the free device memory.  -> the stats as a dict, with "sorted_runs",
+    "tmp_bytes", "run_write_us", "run_read_us"; ArachneError with .code on failure (nothing is left behind then)."""
+    lib = _load(lib_path)
+    st, msg = np.zeros(24, dtype=np.int64), C.create_string_buffer(1024)
+    flags = (FQSORT_BGZF if bgzf else 0) | (FQSORT_CHECK if check else 0) | (FQSORT_TIMED if timed else 0)
+    enc = lambda p: None if p is None else os.fsencode(p)
+    rc = _selftest_fn(lib, "arx_fastq_sort_ex")(device, enc(r1), enc(r2), enc(r1_out), enc(r2_out), flags, int(max_bytes), int(run_bytes), enc(tmp_dir), st.ctypes.data, msg, 1024)
+    if rc != 0:
+        e = ArachneError("arx_fastq_sort_ex: " + msg.value.decode(errors="replace"))
+        e.code = rc
+        raise e
+    return {k: int(st[i]) for i, k in enumerate(_FQSORT_EX_STATS)}
+
+
+def selftest_fastq_sort_ext(t1, t2, run_bytes: int, window_bytes: int = 0, slab_bytes: int = 0, device: int = 0, fill: int = 0xA5, lib_path: str = LIB_PATH):
+    """selftest_fastq_sort through sorted runs of run_bytes per text (include/arachne_amd.h: arx_selftest_fastq_sort_ext) -> the same dict,
+    stats with the four names of fastq_sort_ex.  rc is 0 or ARX_E_TOO_LARGE = -4 (a line or record that a window or a run does not hold,
+    too many runs); on an error everything is as it was filled."""
+    lib = _load(lib_path)
+    s1, s2 = np.frombuffer(bytes(t1), dtype=np.uint8), np.frombuffer(bytes(t2), dtype=np.uint8)
+    n1, n2 = len(s1), len(s2)
+    out1, out2 = np.full(n1 + 8, fill, dtype=np.uint8), np.full(n2 + 8, fill, dtype=np.uint8)
+    off1, off2 = np.full(n1 // 5 + 2, -1, dtype=np.int64), np.full(n1 // 5 + 2, -1, dtype=np.int64)
+    n_rec, out_len, st = C.c_int64(-1), np.full(2, -1, dtype=np.int64), np.zeros(24, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_fastq_sort_ext")(device, s1.ctypes.data if n1 else None, n1, s2.ctypes.data if n2 else None, n2, int(window_bytes), int(slab_bytes),
+                                                          int(run_bytes), out1.ctypes.data, out2.ctypes.data, out_len.ctypes.data, off1.ctypes.data, off2.ctypes.data,
+                                                          C.byref(n_rec), st.ctypes.data)
+    if rc not in (ARX_OK, ARX_E_TOO_LARGE):
+        e = ArachneError("arx_selftest_fastq_sort_ext: code %d" % rc)
+        e.code = rc
+        raise e
+    l1, l2 = (int(out_len[0]), int(out_len[1])) if rc == ARX_OK else (n1, n2)
+    return dict(rc=rc, out1=out1[:l1].tobytes(), out2=out2[:l2].tobytes(), rest1=out1[l1:n1].tobytes(), rest2=out2[l2:n2].tobytes(), guard1=out1[n1:].tobytes(),
+                guard2=out2[n2:].tobytes(), rec_off1=off1, rec_off2=off2, n_records=int(n_rec.value), stats={k: int(st[i]) for i, k in enumerate(_FQSORT_EX_STATS)})
 
 
 BAI_TIMED = 0x100

@@ -349,6 +349,92 @@ extern "C" int arx_selftest_fastq_sort(int32_t device, const uint8_t *t1, int64_
 	return ARX_OK;
 }
 
+// ---- the same sort of a file pair that device memory does not hold: sorted runs in temporary files, merged on the device (dev_fqmerge.h)
+extern "C" int arx_fastq_sort_ex(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t flags, int64_t max_bytes, int64_t run_bytes,
+                                 const char *tmp_dir, int64_t *stats, char *msg, int32_t msg_cap)
+{
+	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
+	if (stats) for (int k = 0; k < arx::FX_N_STATS; ++k) stats[k] = 0;
+	if (run_bytes == 0) return arx_fastq_sort(device, r1_in, r2_in, r1_out, r2_out, flags, max_bytes, stats, msg, msg_cap);
+	if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) { say("arx_fastq_sort_ex: unknown flag bits"); return ARX_E_ARG; }
+	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
+	if (!r1_in || !r2_in || max_bytes < 0 || (!check && (!r1_out || !r2_out))) { say("arx_fastq_sort_ex: null argument"); return ARX_E_ARG; }
+	if (run_bytes < -1 || (run_bytes > 0 && run_bytes < arx::FS_MIN_WINDOW)) {
+		say("arx_fastq_sort_ex: run_bytes is -1, 0 or at least the " + std::to_string(arx::FS_MIN_WINDOW) + " bytes of the smallest parse window");
+		return ARX_E_ARG;
+	}
+	const char *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
+	if (!check) {
+		if (fs_same_file(r1_out, r2_out)) { say("arx_fastq_sort_ex: the two output paths are the same file"); return ARX_E_ARG; }
+		for (int i = 0; i < 2; ++i)
+			for (int o = 0; o < 2; ++o)
+				if (fs_same_file(in[i], out[o])) { say(std::string("arx_fastq_sort_ex: ") + out[o] + " is an input and an output"); return ARX_E_ARG; }
+	}
+	std::string err;
+	try {
+		const int rc = arx::fx_sort_files(device, in, out, flags, max_bytes, run_bytes, tmp_dir, stats, err, arx::shared_device_bgzf);
+		if (rc != ARX_OK) say(err);
+		return rc;
+	} catch (const arx::FsTooLarge &e) {
+		say(e.what());
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::FsIoError &e) {
+		say(e.what());
+		return ARX_E_IO;
+	} catch (const arx::HipOutOfMemory &e) { // a run's buffers, or the table of all records (hip_res.h)
+		say("the device memory does not hold a run of these files or the table of their records (" + std::to_string(e.wanted >> 20) + " MiB more were asked for, " +
+		    std::to_string(e.free_bytes >> 20) + " MiB are free): use a smaller run_bytes; where the table of all records is what does not fit, sort per lane");
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &e) {
+		say(e.what());
+		return ARX_E_DEVICE;
+	}
+}
+
+extern "C" int arx_selftest_fastq_sort_ext(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int64_t window_bytes, int64_t slab_bytes, int64_t run_bytes,
+                                           uint8_t *out1, uint8_t *out2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2, int64_t *n_records, int64_t *stats)
+{
+	const int64_t window = window_bytes ? window_bytes : run_bytes < arx::FS_WINDOW_DEFAULT ? run_bytes : arx::FS_WINDOW_DEFAULT; // 0: arx_fastq_sort_ex's
+	if (n1 < 0 || n2 < 0 || !out_len || !rec_off1 || !rec_off2 || !n_records || (n1 > 0 && (!t1 || !out1)) || (n2 > 0 && (!t2 || !out2)) || slab_bytes < 0 ||
+	    window < arx::FS_MIN_WINDOW || window > arx::FS_MAX_WINDOW || run_bytes < window)
+		return ARX_E_ARG;
+	if (stats) for (int k = 0; k < arx::FX_N_STATS; ++k) stats[k] = 0;
+	try {
+		arx::select_device(device, arx::FS_NO_DEVICE);
+		arx::Stream st;
+		st.create();
+		arx::FxHipDrv drv; drv.st = st;
+		arx::FxMemSrc src;
+		src.st = st; src.t[0] = t1; src.t[1] = t2; src.n[0] = n1; src.n[1] = n2;
+		arx::FxMemStore store;
+		arx::FsMemSink sink;
+		sink.init(drv.st);
+		arx::FxIo io;
+		arx::FsCounts c{};
+		arx::FsSortMem m{};
+		arx::FxRuns S;
+		arx::fx_run(drv, src, &store, &sink, run_bytes, window, slab_bytes ? slab_bytes : arx::FS_SLAB_DEFAULT, c, m, S, io);
+		const int64_t N = c.n_records;
+		std::vector<int64_t> off1((size_t)N + 1, 0), off2((size_t)N + 1, 0);
+		if (N) { drv.fetch(off1.data(), m.out1, (size_t)(N + 1) * 8); drv.fetch(off2.data(), m.out2, (size_t)(N + 1) * 8); }
+		if ((int64_t)sink.text[0].size() != c.bytes1 || (int64_t)sink.text[1].size() != c.bytes2 || c.bytes1 > n1 || c.bytes2 > n2) return ARX_E_DEVICE;
+		// everything is here: only now is anything of the caller's written
+		if (c.bytes1) memcpy(out1, sink.text[0].data(), (size_t)c.bytes1);
+		if (c.bytes2) memcpy(out2, sink.text[1].data(), (size_t)c.bytes2);
+		memcpy(rec_off1, off1.data(), (size_t)(N + 1) * 8); memcpy(rec_off2, off2.data(), (size_t)(N + 1) * 8);
+		out_len[0] = c.bytes1; out_len[1] = c.bytes2;
+		*n_records = N;
+		arx::fx_stats(stats, drv, c, n1, n2, true, S, io);
+	} catch (const arx::FsTooLarge &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::HipOutOfMemory &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}
+
 // ---- the .bai of a coordinate-sorted BAM file (dev_bamindex.h, hip_bamindex.h)
 extern "C" int arx_bam_index(int32_t device, const char *bam_path, const char *bai_path, int64_t max_bytes, int32_t flags, int64_t *stats, char *msg, int32_t msg_cap)
 {

@@ -45,7 +45,9 @@ constexpr int64_t FS_MAX_WINDOW = (int64_t)1 << 29;  // dev_fastq.h counts in in
 constexpr int FS_GATHER_LANES = 16;                  // lanes that copy one record of one file
 enum { FS_OK = 0, FS_E_TOO_LARGE = 1, FS_E_RECORDS = 2 };
 enum { FS_W_WIN1 = 0, FS_W_WIN2, FS_W_CNT, FS_W_OFF, FS_W_NL, FS_W_BMAP, FS_W_BSTATE, FS_W_HDR, FS_W_RCNT, FS_W_ROFF, FS_W_RECL, FS_W_TMP, FS_W_SC, FS_W_VALID, FS_W_META,
-       FS_W_KEYS0, FS_W_KEYS1, FS_W_VALS0, FS_W_VALS1, FS_W_OUT1, FS_W_OUT2, FS_N_WORK };
+       FS_W_KEYS0, FS_W_KEYS1, FS_W_VALS0, FS_W_VALS1, FS_W_OUT1, FS_W_OUT2,
+       FS_W_KOFF, FS_W_FIRST, FS_W_RANGE, FS_W_DELTA, FS_W_STAGE1, FS_W_STAGE2, // dev_fqmerge.h
+       FS_N_WORK };
 
 struct FsRec { int64_t off1, off2, bc_off; int32_t len1, len2, bc_len, pad; }; // the record's lines in R1 and R2, its barcode in R1's text
 // the table grows by half: what a driver allocates when n records are asked for and the table holds fewer
@@ -147,14 +149,20 @@ struct FsGatherF { // item: one lane of one file of one sorted record of the sla
 };
 
 // ---- the table: every record of the two texts, in input order.  FS_OK: c.n_records, c.skipped, c.windows are set and drv.table() holds the
-// records; FS_E_TOO_LARGE: a line or a record does not fit a window of `window` bytes; FS_E_RECORDS: more than 2^32 - 1 records
-template <class Drv> int fs_parse(Drv &drv, const FsText &T, int64_t window, FsCounts &c)
+// records; FS_E_TOO_LARGE: a line or a record does not fit a window of `window` bytes; FS_E_RECORDS: more than 2^32 - 1 records.
+// fs_parse_part is the parse of a text that may be a part of its file (dev_fqmerge.h: a run).  open1 / open2: the file goes on behind T.n1 /
+// T.n2, so the text's end is no end of input: the parse stops behind the first window that touches such an end, ended = false, and
+// [a1, T.n1), [a2, T.n2) are the line pairs it did not consume -- they start in the search state, as every window does -- for the caller to
+// put in front of what follows; lines: the line pairs consumed.  The end-of-input rule is applied only where a closed end is reached
+struct FsPart { bool open1 = false, open2 = false; int64_t n_before = 0; /* records of earlier parts */ int64_t a1 = 0, a2 = 0, lines = 0; bool ended = true; };
+template <class Drv> int fs_parse_part(Drv &drv, const FsText &T, int64_t window, FsCounts &c, FsPart &p)
 {
 	int64_t a1 = 0, a2 = 0, N = 0;
+	p.a1 = p.a2 = p.lines = 0; p.ended = true;
 	c.n_records = c.skipped = c.windows = 0;
 	for (;;) {
 		const int64_t w1 = T.n1 - a1 < window ? T.n1 - a1 : window, w2 = T.n2 - a2 < window ? T.n2 - a2 : window;
-		const bool end1 = a1 + w1 == T.n1, end2 = a2 + w2 == T.n2;
+		const bool at1 = a1 + w1 == T.n1, at2 = a2 + w2 == T.n2, end1 = at1 && !p.open1, end2 = at2 && !p.open2;
 		const int32_t nw1 = (int32_t)((w1 + 15) / 16), nw2 = (int32_t)((w2 + 15) / 16), nw = nw1 + nw2;
 		++c.windows;
 		int32_t L1 = 0, L2 = 0;
@@ -187,7 +195,7 @@ template <class Drv> int fs_parse(Drv &drv, const FsText &T, int64_t window, FsC
 			drv.items("fq_line_states", 1, fs_wide(KLineStates{ln, bmap, bstate, nblk, 0, dmeta}));
 			drv.items("fq_rec_count", nblk, fs_wide(KRecCount{ln, bstate, hdr, rcnt, dmeta}));
 			n = drv.scan32(rcnt, roff, nblk);
-			if (N + n > (int64_t)UINT32_MAX) return FS_E_RECORDS;
+			if (p.n_before + N + n > (int64_t)UINT32_MAX) return FS_E_RECORDS;
 			if (n > 0) {
 				const int32_t ni = (int32_t)n;
 				int32_t *recl = (int32_t *)drv.work(FS_W_RECL, 4 * n), *sc = (int32_t *)drv.work(FS_W_SC, 16 * n);
@@ -205,11 +213,18 @@ template <class Drv> int fs_parse(Drv &drv, const FsText &T, int64_t window, FsC
 		// a file that is at its end and has no line left ends the input: an unterminated last line does not count, nor what the other
 		// file still has, and the record the end cut off does not exist
 		if ((end1 && L1 == L) || (end2 && L2 == L)) break;
-		if (meta[2] == 0) return FS_E_TOO_LARGE; // a full window, and not one line pair of it could be consumed
 		a1 += meta[0]; a2 += meta[1];
+		p.lines += meta[2];
+		if ((at1 && p.open1) || (at2 && p.open2)) { p.a1 = a1; p.a2 = a2; p.ended = false; break; }
+		if (meta[2] == 0) return FS_E_TOO_LARGE; // a full window, and not one line pair of it could be consumed
 	}
 	c.n_records = N;
 	return FS_OK;
+}
+template <class Drv> int fs_parse(Drv &drv, const FsText &T, int64_t window, FsCounts &c)
+{
+	FsPart whole;
+	return fs_parse_part(drv, T, window, c, whole);
 }
 
 struct FsSortMem { uint64_t *keys[2]; uint32_t *vals[2]; int64_t *out1, *out2; int cur; }; // vals[cur]: the order

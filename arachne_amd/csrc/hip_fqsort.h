@@ -17,13 +17,25 @@
 // Device memory of a call: the two texts (a text that outgrows its buffer moves to one half as large again), four output slab buffers (256 MiB at
 // the default), per record 80 bytes (dev_fqsort.h: table, keys, values, output offsets), the parse's window buffers (FS_WINDOW_DEFAULT per file,
 // and about as much again for the line index), rocprim's scratch.  What does not fit is ARX_E_TOO_LARGE: sort per lane, or split the input.
-// Not built: an out-of-core merge of sorted runs.
+//
+// A pair that device memory does not hold goes through arx_fastq_sort_ex (run_bytes != 0; below: FxHipDrv ... fx_sort_files), dev_fqmerge.h on
+// the GPU: the readers' slabs go up into a buffer per file and from there, split where a run ends, into the two run buffers; a run is parsed,
+// ordered and gathered as above and its slabs are appended to two temporary files (FxFileStore; FxMemStore in the self-test), FxKeepF keeps a
+// table row and the barcode per record; fs_order over those rows is the merge, and FxGatherF makes every output slab from the ranges of the
+// runs, read back through page-locked memory.  The next slab is not staged while one is consumed: the read-back is in the open.
+// Device memory of such a call.  During the runs: the two run buffers (2 run_bytes), one slab text per file as the readers cut it (32 MiB
+// each), the windows and line index of a parse (min(run_bytes, FS_WINDOW_DEFAULT) per file and as much again), the run's 80 bytes per record,
+// four slab buffers.  Throughout: 40 bytes and the barcode per record of the whole input (grown by half when full).  During the merge the
+// runs' memory is gone: 40 bytes per record for the order, two stage buffers and four slab buffers of FS_SLAB_DEFAULT.  Not built: compressed
+// run files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_reduce.hpp>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
+#include <unistd.h>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -33,6 +45,7 @@
 #include "bgzf_walk.h"
 #include "feeder.h"
 #include "dev_fqsort.h"
+#include "dev_fqmerge.h"
 #include "hip_bgzf.h"
 #include "hip_bamsort.h"
 
@@ -71,7 +84,7 @@ struct FsHipDrv {
 	{
 		if (!strncmp(nm, "fq_", 3) || !strcmp(nm, "fs_window") || !strcmp(nm, "fs_store") || !strcmp(nm, "fs_scan32")) return FS_T_PARSE;
 		if (!strcmp(nm, "fs_sort")) return FS_T_SORT;
-		if (!strcmp(nm, "fs_gather") || !strcmp(nm, "fs_sizes")) return FS_T_GATHER;
+		if (!strcmp(nm, "fs_gather") || !strcmp(nm, "fs_sizes") || !strcmp(nm, "fx_gather")) return FS_T_GATHER;
 		return FS_T_KEYS; // length and chunk keys, runs, their scans and reductions
 	}
 	template <class Fn> void booked(const char *nm, Fn fn)
@@ -404,6 +417,304 @@ inline int fs_sort_files(int device, const char *const in_path[2], const char *c
 		drv.us[FS_T_COMPRESS] = sink.us_compress; drv.us[FS_T_WRITE] = sink.us_write;
 	}
 	fs_stats(stats, drv, c, T.n1, T.n2, !check);
+	return ARX_OK;
+}
+
+// ---- the external sort (dev_fqmerge.h): arx_fastq_sort_ex with run_bytes != 0, arx_selftest_fastq_sort_ext
+struct FxHipDrv : FsHipDrv {
+	DevBuf run_[2], keep_[2];
+	void *run_buf(int f, int64_t bytes) { run_[f].alloc((size_t)bytes); return run_[f].p; }
+	void copy(void *dst, const void *src, int64_t n) { if (n > 0) ARX_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)n, hipMemcpyDeviceToDevice, st)); }
+	void upload(void *dev, const void *host, size_t bytes)
+	{
+		if (!bytes) return;
+		ARX_HIP_CHECK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, st));
+		ARX_HIP_CHECK(hipStreamSynchronize(st));
+	}
+	void *keep(int which, int64_t bytes, int64_t kept) // grows by half, as the table
+	{
+		DevBuf &b = keep_[which];
+		if (!b.p || (size_t)bytes > b.bytes) {
+			DevBuf t((size_t)(bytes + bytes / 2));
+			if (kept) ARX_HIP_CHECK(hipMemcpyAsync(t.p, b.p, (size_t)kept, hipMemcpyDeviceToDevice, st));
+			ARX_HIP_CHECK(hipStreamSynchronize(st));
+			b = std::move(t);
+		}
+		return b.p;
+	}
+	void runs_done() // what only the runs needed makes room for the merge's order
+	{
+		ARX_HIP_CHECK(hipStreamSynchronize(st));
+		for (DevBuf &b : run_) b.release();
+		for (DevBuf &b : work_) b.release();
+		tab_.release(); tab_n_ = 0;
+	}
+};
+
+// where the sorted runs wait for the merge: one store per sort, the runs of file f appended one after another to its one file
+struct FxRunStore {
+	int64_t bytes[2] = {0, 0};
+	virtual ~FxRunStore() {}
+	virtual void append(int f, const void *p, int64_t n) = 0;
+	virtual void read(int f, int64_t at, int64_t n, void *dst) = 0;
+};
+struct FxMemStore : FxRunStore { // the self-test's
+	std::vector<uint8_t> text[2];
+	void append(int f, const void *p, int64_t n) override { text[f].insert(text[f].end(), (const uint8_t *)p, (const uint8_t *)p + n); bytes[f] += n; }
+	void read(int f, int64_t at, int64_t n, void *dst) override
+	{
+		if (at < 0 || n < 0 || at + n > bytes[f]) throw FsIoError("a range outside the sorted runs");
+		memcpy(dst, text[f].data() + at, (size_t)n);
+	}
+};
+// a temporary file under a name of its own (mkstemps), removed when its owner goes
+struct FxTmpFile {
+	int fd = -1;
+	std::string path;
+	bool create(const std::string &dir, const char *suffix)
+	{
+		std::string t = dir + "/arx_fqsort_XXXXXX" + suffix;
+		fd = mkstemps(&t[0], (int)strlen(suffix));
+		if (fd >= 0) path = t;
+		return fd >= 0;
+	}
+	~FxTmpFile()
+	{
+		if (fd >= 0) close(fd);
+		if (!path.empty()) unlink(path.c_str());
+	}
+};
+struct FxFileStore : FxRunStore {
+	FxTmpFile file[2];
+	void append(int f, const void *p, int64_t n) override
+	{
+		for (int64_t done = 0; done < n;) {
+			const ssize_t k = pwrite(file[f].fd, (const char *)p + done, (size_t)(n - done), (off_t)(bytes[f] + done));
+			if (k <= 0) throw FsIoError(file[f].path + ": write failed");
+			done += k;
+		}
+		bytes[f] += n;
+	}
+	void read(int f, int64_t at, int64_t n, void *dst) override
+	{
+		for (int64_t done = 0; done < n;) {
+			const ssize_t k = pread(file[f].fd, (char *)dst + done, (size_t)(n - done), (off_t)(at + done));
+			if (k <= 0) throw FsIoError(file[f].path + ": read failed");
+			done += k;
+		}
+	}
+};
+
+// dev_fqmerge.h's io: a run's slabs to the store (a sink of fs_gather), and the store's ranges to the merge's stage buffers through page-locked memory
+struct FxIo : FsSink {
+	FxRunStore *store = nullptr;
+	PinnedBuf h, hs;
+	struct Up { void *dst; size_t at, n; };
+	std::vector<Up> ups;
+	size_t used = 0;
+	double us_write = 0, us_read = 0;
+	void consume(int f, const uint8_t *d, int64_t n) override
+	{
+		if (n <= 0) return;
+		const double t0 = bs_now_us();
+		if (!h.p || (size_t)n > h.bytes) h.alloc((size_t)n);
+		fetch(h.p, d, n);
+		store->append(f, h.p, n);
+		us_write += bs_now_us() - t0;
+	}
+	void end_run() { flush(); }
+	void runs_done() // the merge's sink has slab buffers of its own
+	{
+		for (auto &pair : buf) for (DevBuf &b : pair) b.release();
+		h.release();
+	}
+	void begin(int64_t bytes)
+	{
+		if (!hs.p || (size_t)bytes > hs.bytes) hs.alloc((size_t)bytes);
+		used = 0; ups.clear();
+	}
+	void read(int f, int64_t at, int64_t n, uint8_t *dst)
+	{
+		const double t0 = bs_now_us();
+		store->read(f, at, n, hs.as<uint8_t>() + used);
+		ups.push_back(Up{dst, used, (size_t)n});
+		used += (size_t)n;
+		us_read += bs_now_us() - t0;
+	}
+	void staged()
+	{
+		const double t0 = bs_now_us();
+		for (const Up &u : ups) ARX_HIP_CHECK(hipMemcpyAsync(u.dst, hs.as<uint8_t>() + u.at, u.n, hipMemcpyHostToDevice, st));
+		ARX_HIP_CHECK(hipStreamSynchronize(st)); // hs may be refilled
+		us_read += bs_now_us() - t0;
+	}
+};
+
+constexpr int FX_N_STATS = 24;
+enum { FX_RUNS = 20, FX_TMP_BYTES, FX_T_RUN_WRITE, FX_T_RUN_READ };
+constexpr int64_t FX_AUTO_RESERVE = (int64_t)1 << 30, FX_AUTO_SHARE = 8, FX_AUTO_MOST = (int64_t)16 << 30;
+
+// run_bytes == -1: an eighth of the free device memory less 1 GiB, in whole MiB, 16 GiB at most (include/arachne_amd.h has the accounting)
+inline int64_t fx_auto_run_bytes(int64_t least)
+{
+	size_t fr = 0, total = 0;
+	ARX_HIP_CHECK(hipMemGetInfo(&fr, &total));
+	int64_t rb = ((int64_t)fr - FX_AUTO_RESERVE) / FX_AUTO_SHARE;
+	rb &= ~(((int64_t)1 << 20) - 1);
+	if (rb > FX_AUTO_MOST) rb = FX_AUTO_MOST;
+	return rb < least ? least : rb;
+}
+
+// runs, merge and (sink != null) output of what src delivers; store == null: CHECK, only the keys are kept
+template <class Src> void fx_run(FxHipDrv &drv, Src &src, FxRunStore *store, FsSink *sink, int64_t run_bytes, int64_t window, int64_t slab, FsCounts &c, FsSortMem &m, FxRuns &S, FxIo &io)
+{
+	double t0 = bs_now_us();
+	io.store = store;
+	if (store) io.init(drv.st);
+	const double fed0 = drv.us[FS_T_READ] + drv.us[FS_T_INFLATE];
+	const int rc = fx_runs(drv, src, store ? &io : nullptr, run_bytes, window, slab, S);
+	if (rc == FS_E_RECORDS) throw FsTooLarge(std::string("more than 2^32 - 1 records") + FS_REMEDY);
+	if (rc == FS_E_TOO_LARGE) throw FsTooLarge("a line or a record is longer than the " + std::to_string(window) + " bytes of a parse window");
+	if (rc == FS_E_RUN) throw FsTooLarge("a line or a record does not fit a run of " + std::to_string(run_bytes) + " bytes per file: use a larger run_bytes");
+	if (rc == FS_E_RUNS) throw FsTooLarge("more than " + std::to_string(FS_MAX_RUNS) + " sorted runs of " + std::to_string(run_bytes) + " bytes per file: use a larger run_bytes");
+	if (rc != FS_OK) throw std::runtime_error("the external sort failed in its runs");
+	drv.runs_done();
+	io.runs_done();
+	if (!drv.timed) drv.us[FS_T_SORT] = bs_now_us() - t0 - io.us_write - (drv.us[FS_T_READ] + drv.us[FS_T_INFLATE] - fed0);
+	t0 = bs_now_us();
+	if (fx_merge(drv, &io, sink, S, slab, m, c) != FS_OK) throw std::runtime_error("the external sort's merge: the staged ranges are not the slab's bytes");
+	if (sink) sink->flush();
+	ARX_HIP_CHECK(hipStreamSynchronize(drv.st));
+	if (!drv.timed) drv.us[FS_T_GATHER] = bs_now_us() - t0 - io.us_read - (sink ? sink->us_consume : 0);
+}
+inline void fx_stats(int64_t *stats, const FxHipDrv &drv, const FsCounts &c, int64_t n1, int64_t n2, bool written, const FxRuns &S, const FxIo &io)
+{
+	if (!stats) return;
+	fs_stats(stats, drv, c, n1, n2, written);
+	stats[FX_RUNS] = S.n_runs; stats[FX_TMP_BYTES] = written ? S.file1 + S.file2 : 0;
+	stats[FX_T_RUN_WRITE] = (int64_t)io.us_write; stats[FX_T_RUN_READ] = (int64_t)io.us_read;
+}
+
+// two texts in host memory (the self-test's source)
+struct FxMemSrc {
+	hipStream_t st = nullptr;
+	const uint8_t *t[2] = {nullptr, nullptr};
+	int64_t n[2] = {0, 0}, at[2] = {0, 0};
+	bool ended(int f) const { return at[f] == n[f]; }
+	int64_t fill(int f, uint8_t *dst, int64_t want)
+	{
+		const int64_t k = want < n[f] - at[f] ? want : n[f] - at[f];
+		if (k > 0) {
+			ARX_HIP_CHECK(hipMemcpyAsync(dst, t[f] + at[f], (size_t)k, hipMemcpyHostToDevice, st));
+			ARX_HIP_CHECK(hipStreamSynchronize(st));
+		}
+		at[f] += k;
+		return k;
+	}
+};
+// the two files through their readers.  A reader's slab goes up (and, BGZF, is inflated) into a buffer of its own; the runs take their bytes from
+// there, so a slab that straddles a run's end is split and its rest opens the next run
+struct FxFileSrc {
+	FsInput *in = nullptr;        // [2]
+	const char *const *path = nullptr;
+	FsHipDrv *drv = nullptr;
+	int64_t max_bytes = 0;
+	DevBuf text[2], d_comp, d_rows, d_status;
+	int64_t have[2] = {0, 0}, at[2] = {0, 0}, total[2] = {0, 0};
+	bool ended(int f) const { return in[f].done && at[f] == have[f]; }
+	void next(int f) // the next slab of file f into text[f]
+	{
+		FsInput &I = in[f];
+		hipStream_t st = drv->st;
+		double t0 = bs_now_us();
+		const SlabReader::Slab *s = I.rd->acquire();
+		drv->us[FS_T_READ] += bs_now_us() - t0;
+		have[f] = at[f] = 0;
+		if (!s) { I.done = true; return; }
+		t0 = bs_now_us();
+		if (s->err) throw FsIoError(std::string(path[f]) + (I.bgzf ? ": not a chain of whole BGZF blocks" : ": read error"));
+		if (max_bytes > 0 && total[0] + total[1] + (int64_t)s->text > max_bytes)
+			throw FsTooLarge(std::string(path[0]) + " and " + path[1] + " inflate to more than the " + std::to_string(max_bytes) + " bytes allowed");
+		if (!text[f].p || s->text > text[f].bytes) { ARX_HIP_CHECK(hipStreamSynchronize(st)); text[f].alloc(s->text + 64); }
+		uint8_t *dst = text[f].as<uint8_t>();
+		if (!I.bgzf) {
+			if (s->len) ARX_HIP_CHECK(hipMemcpyAsync(dst, s->buf, s->len, hipMemcpyHostToDevice, st));
+		} else if (s->n_rows) {
+			const size_t nr = s->n_rows;
+			if (!d_comp.p || s->len > d_comp.bytes) d_comp.alloc(s->len + s->len / 4);
+			if (!d_rows.p || nr * sizeof(InfRow) > d_rows.bytes) { d_rows.alloc(2 * nr * sizeof(InfRow)); d_status.alloc(4 * (2 * nr + 2)); }
+			ARX_HIP_CHECK(hipMemcpyAsync(d_comp.p, s->buf, s->len, hipMemcpyHostToDevice, st));
+			ARX_HIP_CHECK(hipMemcpyAsync(d_rows.p, s->rows, nr * sizeof(InfRow), hipMemcpyHostToDevice, st));
+			ARX_HIP_CHECK(hipMemsetAsync(d_status.p, 0, 4 * (nr + 2), st));
+			int32_t *counts = d_status.as<int32_t>() + nr;
+			inflate_launch(st, d_comp.as<uint8_t>(), (int64_t)s->len, d_rows.as<InfRow>(), (int)nr, dst, (int64_t)s->text, d_status.as<int32_t>(), counts);
+			int32_t bad[2] = {0, 0};
+			ARX_HIP_CHECK(hipMemcpyAsync(bad, counts, 8, hipMemcpyDeviceToHost, st));
+			ARX_HIP_CHECK(hipStreamSynchronize(st));
+			if (bad[0] != 0) throw FsIoError(std::string(path[f]) + ": a BGZF block does not inflate");
+		}
+		ARX_HIP_CHECK(hipStreamSynchronize(st)); // the reader may refill the slab
+		have[f] = (int64_t)s->text; total[f] += have[f];
+		if (s->eof) I.done = true;
+		I.rd->release();
+		drv->us[FS_T_INFLATE] += bs_now_us() - t0;
+	}
+	int64_t fill(int f, uint8_t *dst, int64_t want)
+	{
+		int64_t got = 0;
+		while (got < want && !ended(f)) {
+			if (at[f] == have[f]) { next(f); continue; }
+			const int64_t k = want - got < have[f] - at[f] ? want - got : have[f] - at[f];
+			ARX_HIP_CHECK(hipMemcpyAsync(dst + got, text[f].as<uint8_t>() + at[f], (size_t)k, hipMemcpyDeviceToDevice, drv->st));
+			at[f] += k; got += k;
+		}
+		while (at[f] == have[f] && !in[f].done) next(f); // so that ended() knows of an end that lies right here
+		return got;
+	}
+};
+
+// arx_fastq_sort_ex with run_bytes != 0 -> ARX_*; err: the text
+inline int fx_sort_files(int device, const char *const in_path[2], const char *const out_path[2], int flags, int64_t max_bytes, int64_t run_bytes, const char *tmp_dir, int64_t *stats,
+                         std::string &err, std::shared_ptr<DeviceBgzf> (*get_z)(int))
+{
+	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
+	FsInput in[2];
+	for (int f = 0; f < 2; ++f)
+		if (!in[f].open(in_path[f])) { err = std::string("cannot read ") + in_path[f]; return ARX_E_IO; }
+	FsFileSink sink;
+	sink.bgzf = (flags & ARX_FQSORT_BGZF) != 0;
+	FxFileStore store;
+	if (!check) {
+		for (int f = 0; f < 2; ++f)
+			if (!sink.file[f].open(out_path[f])) { err = std::string("cannot write ") + sink.file[f].tmp; return ARX_E_IO; }
+		std::string dir = tmp_dir ? tmp_dir : out_path[0];
+		if (!tmp_dir) { const size_t cut = dir.rfind('/'); dir = cut == std::string::npos ? "." : cut == 0 ? "/" : dir.substr(0, cut); }
+		for (int f = 0; f < 2; ++f)
+			if (!store.file[f].create(dir, f ? ".r2" : ".r1")) { err = "cannot write a temporary file under " + dir; return ARX_E_IO; }
+	}
+	select_device(device, FS_NO_DEVICE);
+	Stream st; // the call's own; declared before the buffers, so that it has ended when they are freed
+	st.create();
+	FxHipDrv drv; drv.st = st; drv.timed = (flags & ARX_FQSORT_TIMED) != 0;
+	const int64_t rb = run_bytes == -1 ? fx_auto_run_bytes(FS_WINDOW_DEFAULT) : run_bytes;
+	FsCounts c{};
+	FsSortMem m{};
+	FxRuns S;
+	FxIo io;
+	FxFileSrc src;
+	src.in = in; src.path = in_path; src.drv = &drv; src.max_bytes = max_bytes;
+	for (int f = 0; f < 2; ++f) in[f].rd->start();
+	if (!check) {
+		sink.init(st);
+		if (sink.bgzf) sink.z = get_z(device);
+	}
+	fx_run(drv, src, check ? nullptr : &store, check ? nullptr : &sink, rb, rb < FS_WINDOW_DEFAULT ? rb : FS_WINDOW_DEFAULT, FS_SLAB_DEFAULT, c, m, S, io);
+	for (int f = 0; f < 2; ++f) in[f].rd.reset();
+	if (!check) {
+		sink.finish();
+		drv.us[FS_T_COMPRESS] = sink.us_compress; drv.us[FS_T_WRITE] = sink.us_write;
+	}
+	fx_stats(stats, drv, c, src.total[0], src.total[1], !check, S, io);
 	return ARX_OK;
 }
 

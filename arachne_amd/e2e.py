@@ -23,6 +23,7 @@ the source that the feeder's arrays of it are free, and counts.  Four axes, each
   sink     how BGZF blocks are made: on the writers' host threads, or by HIP kernels (arx_bam_open_device)."""
 from __future__ import annotations
 
+import functools
 import os
 import queue
 import threading
@@ -245,13 +246,17 @@ def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "hos
     return out
 
 
-def presort(r1: str, r2: str, out_dir: str, device: int = 0, bgzf: bool = False, if_needed: bool = True, lib_path: str = api.LIB_PATH):
+def presort(r1: str, r2: str, out_dir: str, device: int = 0, bgzf: bool = False, if_needed: bool = True, lib_path: str = api.LIB_PATH, run_bytes: int = 0,
+            tmp_dir: "str | None" = None):
     """The step in front of run(): the file pair sorted by barcode on the GPU (api.fastq_sort; the reference's `arachne preprocess`), which
     the feeder's barcode sets rely on.  With if_needed the input is counted first (check=True) and returned as it is when every barcode
     is one run already.  The sorted files go to out_dir under the inputs' base names (+ ".sorted.fastq", ".gz" with bgzf: a BGZF file is a
-    gzip file).  -> (r1_sorted, r2_sorted, stats); stats["sorted"] says whether files were written."""
+    gzip file).  run_bytes != 0 sorts in runs of that many bytes per file through temporary files under tmp_dir (api.fastq_sort_ex: a pair that
+    device memory does not hold; -1: the library chooses), the count before it included.
+    -> (r1_sorted, r2_sorted, stats); stats["sorted"] says whether files were written."""
+    sort = api.fastq_sort if run_bytes == 0 else functools.partial(api.fastq_sort_ex, run_bytes=run_bytes, tmp_dir=tmp_dir)
     if if_needed:
-        st = api.fastq_sort(r1, r2, check=True, device=device, lib_path=lib_path)
+        st = sort(r1, r2, check=True, device=device, lib_path=lib_path)
         if st["runs"] == st["distinct"]:
             return r1, r2, dict(st, sorted=False)
     os.makedirs(out_dir, exist_ok=True)
@@ -265,7 +270,7 @@ def presort(r1: str, r2: str, out_dir: str, device: int = 0, bgzf: bool = False,
     o1, o2 = name(r1), name(r2)
     if o1 == o2:
         o2 = o2.replace(".sorted.", ".sorted.2.")
-    st = api.fastq_sort(r1, r2, o1, o2, bgzf=bgzf, device=device, lib_path=lib_path)
+    st = sort(r1, r2, o1, o2, bgzf=bgzf, device=device, lib_path=lib_path)
     return o1, o2, dict(st, sorted=True)
 
 

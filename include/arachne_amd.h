@@ -406,7 +406,7 @@ int arx_selftest_bam_index(int32_t device, const uint8_t *stream, int64_t n_byte
  * paths may be NULL, only stats is filled -- stats[6] == stats[7] says that the input needs no sort.  ARX_FQSORT_TIMED waits for every
  * launch and books the phases per launch group.  Both texts and 80 bytes per record stay in device memory (csrc/hip_fqsort.h); max_bytes
  * (0: no limit of its own) bounds the inflated bytes of both files together.  ARX_E_TOO_LARGE: more than max_bytes, or than the device
- * holds -- msg names the remedy: sort per lane, or split the input (there is no out-of-core merge); ARX_E_IO: a file cannot be read or
+ * holds -- msg names the remedy: sort per lane, or split the input (arx_fastq_sort_ex below sorts such a pair in runs); ARX_E_IO: a file cannot be read or
  * written, or a block does not inflate (nothing is produced then, where the feeder delivers the sets in front of the damage); ARX_E_ARG:
  * null paths without CHECK, unknown flag bits, an output path that is an input; ARX_E_DEVICE: no GPU, or a HIP error.
  * stats[20] (may be NULL): [0] records written, [1] [2] inflated bytes read from R1, R2, [3] [4] bytes written to R1, R2 as inflated text,
@@ -424,6 +424,38 @@ int arx_fastq_sort(int32_t device, const char *r1_in, const char *r2_in, const c
  * be NULL) as above.  On any error out1, out2, rec_off1 and rec_off2 are untouched. */
 int arx_selftest_fastq_sort(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int64_t window_bytes, int64_t slab_bytes, uint8_t *out1,
                             uint8_t *out2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2, int64_t *n_records, int64_t *stats);
+/* ---- the same sort of a file pair that device memory does not hold: sorted runs in temporary files, merged on the GPU.  The record, barcode
+ * and output rules are arx_fastq_sort's, word for word; the output bytes do not depend on run_bytes, nor on how the readers cut their slabs,
+ * and are arx_fastq_sort's for every input that call accepts.  flags, max_bytes (which here is what keeps a call from filling the disk),
+ * msg and stats[0..19] as there; stats[6] is the input's own count of barcode runs.
+ *   run_bytes == 0   exactly arx_fastq_sort: tmp_dir is ignored, stats[20..23] are 0
+ *   run_bytes > 0    the inflated text of EACH file that one run holds in device memory, what the run before left over included; at least 128,
+ *                    the smallest parse window (ARX_E_ARG below).  A run is parsed in windows of min(run_bytes, 32 MiB)
+ *   run_bytes == -1  the library chooses: an eighth of the device memory that is free at the call less 1 GiB, in whole MiB, at least 32 MiB
+ *                    and at most 16 GiB.  The accounting behind it: a run needs its two buffers (2 run_bytes), the readers' two slab texts
+ *                    (64 MiB), the parse's windows and line index (about 128 MiB), four slab buffers (256 MiB) and a run's own 80 bytes per
+ *                    record -- 1.6 run_bytes at 100 bytes of text per record and file --, which leaves about half of the free memory to what
+ *                    grows with the whole input: 40 bytes and the barcode per record throughout, 40 bytes more per record while the merge
+ *                    orders.  Nobody has measured which run size is fastest; fewer, larger runs mean fewer ranges per output slab.
+ * Every record of a run is read, ordered and appended to the temporary files; the GPU keeps a table row and the barcode per record, orders
+ * all rows at the end (stable: equal barcodes in run order, which is input order) and gathers the output slab by slab from the ranges of
+ * the runs that the host reads back -- every temporary byte is written once and read once.
+ * Temporary files: plain text, one per input file (arx_fqsort_XXXXXX.r1 / .r2, the name unique per call), under tmp_dir (NULL: the directory
+ * of r1_out); the disk needed is the inflated size of both files; they are removed on every way out.  With ARX_FQSORT_CHECK no temporary
+ * file is written and tmp_dir is not looked at: only the keys are kept, so an input of any size can be judged.
+ * ARX_E_TOO_LARGE: more than max_bytes; a line or record that a run does not hold with both buffers full, or more than 1024 runs (msg:
+ * use a larger run_bytes); more than 2^32 - 1 records; buffers or a record table that the device does not hold.  ARX_E_IO as above, and a
+ * tmp_dir in which no file can be made.  After any error neither outputs, .tmp files nor temporary files are left.
+ * stats[24] (may be NULL): [0..19] as above ([10] counts the windows of all runs; without ARX_FQSORT_TIMED [16] is the device work of the
+ * runs and [17] that of the merge, [14] and [15] are 0), [20] sorted runs written, [21] bytes of the temporary files, [22] microseconds
+ * fetching and writing runs, [23] microseconds reading them back and uploading them. */
+int arx_fastq_sort_ex(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t flags, int64_t max_bytes, int64_t run_bytes,
+                      const char *tmp_dir, int64_t *stats, char *msg, int32_t msg_cap);
+/* arx_selftest_fastq_sort's arguments and run_bytes (at least 128 and at least window_bytes, ARX_E_ARG below; window_bytes 0: min(run_bytes, 32 MiB)): the
+ * orchestration of arx_fastq_sort_ex on two texts in host memory, the sorted runs held in host memory too (tests/test_fastq_sort_ext_gpu.py).
+ * stats[24] as above.  On any error out1, out2, rec_off1 and rec_off2 are untouched. */
+int arx_selftest_fastq_sort_ext(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int64_t window_bytes, int64_t slab_bytes, int64_t run_bytes,
+                                uint8_t *out1, uint8_t *out2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2, int64_t *n_records, int64_t *stats);
 
 /* ---- between the path and the sink: the placed candidate of every read of a super-batch as BAM records -- the part of DumpToBams /
  * AppendBam (src/aligner/bamwriter.go:283-568, 635-658) that decides flags, position, MAPQ, mate fields, template length, CIGAR op codes,

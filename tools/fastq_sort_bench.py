@@ -8,7 +8,11 @@ BGZF (blocks of 65,280 bytes, level 1), files in the page cache.  One JSON line 
   plain        plain -> plain          bgzf   BGZF -> BGZF          check   ARX_FQSORT_CHECK on the plain and on the BGZF pair
 each --repeats times untimed (the call's seconds and pairs/s; phases by wall clock) and once with ARX_FQSORT_TIMED (every launch group awaited:
 read, inflate, parse, keys, sort, gather, compress, write in ms).  The first sorted output is compared with Python's stable sort of the records.
-Usage: fastq_sort_bench.py [--pairs 1000000] [--per-barcode 200] [--repeats 3] [--out-dir DIR]"""
+--run-bytes takes a comma-separated list: 0 is the in-core call above, any other value repeats the plain and the bgzf arm through
+arx_fastq_sort_ex with that run size (-1: the library's choice), temporary files in the output directory; those lines carry run_bytes, the
+sorted runs, the temporary bytes and the milliseconds spent writing the runs and reading them back.  --also-lib PATH adds the in-core plain arm
+of another build of the library (the parent commit's, say), its passes alternated with this tree's (what: plain_this, plain_other).
+Usage: fastq_sort_bench.py [--pairs 1000000] [--per-barcode 200] [--repeats 3] [--out-dir DIR] [--run-bytes 0,RB,...] [--also-lib PATH]"""
 import argparse
 import json
 import os
@@ -48,7 +52,10 @@ def main():
     ap.add_argument("--per-barcode", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out-dir", default=None)
+    ap.add_argument("--run-bytes", default="0")
+    ap.add_argument("--also-lib", default=None)
     args = ap.parse_args()
+    run_sizes = [int(x) for x in args.run_bytes.split(",") if x.strip()]
     d = args.out_dir or tempfile.mkdtemp(prefix="arx_fqsort_bench_")
     os.makedirs(d, exist_ok=True)
     g = synth.make_genome(21, [2_000_000], fast=True)
@@ -86,22 +93,39 @@ def main():
     print(json.dumps(dict(what="input", pairs=n, barcodes=len(ids), plain_bytes=sum(os.path.getsize(p) for p in plain), bgzf_bytes=sum(os.path.getsize(p) for p in bz))), flush=True)
     out = (os.path.join(d, "out1.fq"), os.path.join(d, "out2.fq"))
     arms = (("plain", plain, dict(bgzf=False)), ("bgzf", bz, dict(bgzf=True)), ("check_plain", plain, dict(check=True)), ("check_bgzf", bz, dict(check=True)))
-    for what, src_files, kw in arms:
-        outs = (None, None) if kw.get("check") else out
+    first = True
+    for rb in run_sizes:
+        for what, src_files, kw in arms:
+            if rb != 0 and kw.get("check"):
+                continue
+            outs = (None, None) if kw.get("check") else out
+            for rep in range(args.repeats + 1):
+                timed = rep == args.repeats
+                t = time.time()
+                st = api.fastq_sort(*src_files, *outs, timed=timed, **kw) if rb == 0 else api.fastq_sort_ex(*src_files, *outs, timed=timed, run_bytes=rb, tmp_dir=d, **kw)
+                s = time.time() - t
+                row = dict(what=what, run_bytes=rb, timed=timed, seconds=round(s, 4), pairs_per_s=round(n / s), records=st["records"], runs=st["runs"], distinct=st["distinct"],
+                           sort_passes=st["sort_passes"], windows=st["windows"], slabs=st["slabs"], **{p + "_ms": round(st[p + "_us"] / 1e3, 2) for p in PHASES})
+                if rb != 0:
+                    row.update(sorted_runs=st["sorted_runs"], tmp_bytes=st["tmp_bytes"], run_write_ms=round(st["run_write_us"] / 1e3, 2), run_read_ms=round(st["run_read_us"] / 1e3, 2))
+                if rep == 0 and not kw.get("check"):
+                    got = [open(p, "rb").read() for p in out]
+                    if kw["bgzf"]:
+                        row["out_bytes"] = sum(len(x) for x in got)
+                        got = [bgzfio.inflate(x) for x in got]
+                    row["output_is_the_stable_sort"] = got[0] == want[0] and got[1] == want[1]
+                    if not first:
+                        del got
+                    first = False
+                print(json.dumps(row), flush=True)
+    if args.also_lib:
         for rep in range(args.repeats + 1):
-            timed = rep == args.repeats
-            t = time.time()
-            st = api.fastq_sort(*src_files, *outs, timed=timed, **kw)
-            s = time.time() - t
-            row = dict(what=what, timed=timed, seconds=round(s, 4), pairs_per_s=round(n / s), records=st["records"], runs=st["runs"], distinct=st["distinct"],
-                       sort_passes=st["sort_passes"], windows=st["windows"], slabs=st["slabs"], **{p + "_ms": round(st[p + "_us"] / 1e3, 2) for p in PHASES})
-            if rep == 0 and not kw.get("check"):
-                got = [open(p, "rb").read() for p in out]
-                if kw["bgzf"]:
-                    row["out_bytes"] = sum(len(x) for x in got)
-                    got = [bgzfio.inflate(x) for x in got]
-                row["output_is_the_stable_sort"] = got[0] == want[0] and got[1] == want[1]
-            print(json.dumps(row), flush=True)
+            for what, lib in (("plain_this", api.LIB_PATH), ("plain_other", args.also_lib)):
+                t = time.time()
+                st = api.fastq_sort(*plain, *out, lib_path=lib)
+                s = time.time() - t
+                print(json.dumps(dict(what=what, run_bytes=0, timed=False, seconds=round(s, 4), pairs_per_s=round(n / s), records=st["records"],
+                                      **{p + "_ms": round(st[p + "_us"] / 1e3, 2) for p in PHASES})), flush=True)
     if not args.out_dir:
         shutil.rmtree(d, ignore_errors=True)
 
