@@ -150,6 +150,8 @@ _SELFTEST_ARGS = {
                          C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "arx_selftest_reg2aln": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_int64, C.c_int32],
+    "arx_selftest_post": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                          C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32],
     # the device BAM sink: bound when first used, for the same reason
     "arx_bam_open_device": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
     "arx_bam_write_encoded_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64],
@@ -637,6 +639,50 @@ def selftest_reg2aln(ref, seqs, lens, cap, n_regs, regs, census: bool = False, g
         out["census"] = dict(cig_w=int(cen[0]), passes=int(cen[1]), queued=int(cen[2]), big=int(cen[3]), per_class=[int(x) for x in cen[4:9]], punts=int(cen[9]),
                              known=int(cen[11]), rows=cen[R2A_CENSUS_HEAD:R2A_CENSUS_HEAD + 3 * k].reshape(k, 3).copy())
     return out
+
+
+def selftest_post(ref, batch, cand_off, cands, seqs, lens, bc_pair_off, penalty: int = -4, centromeres=None, census: bool = False, grid_cap: int = 0, order: int = 0):
+    """The passes between placement and the BAM records on given candidates (include/arachne_amd.h: arx_selftest_post), on a runtime of its own with
+    ref's index and the ARX_* switches as they are now.  batch: dict with regs / alns / cigars in the restatement's int64 row layout; cand_off, cands:
+    its 20-column candidate rows (what tests/rfadrv.py oracle_post takes) -> dict(post (POST_DTYPE), split (SPLIT_DTYPE), mm_ref, mm_read, table, home);
+    table / home (census=True, else None): the duplicate table as the launches left it and every read's home slot.  grid_cap > 0: every launch on at
+    most that many workgroups; order: the host double's item order (0, 1, 2), which the library ignores."""
+    regs = np.ascontiguousarray(batch["regs"], dtype=np.int64).reshape(-1, 20)
+    alns = np.ascontiguousarray(batch["alns"], dtype=np.int64).reshape(-1, 12)
+    cig = np.ascontiguousarray(batch["cigars"], dtype=np.uint32)
+    off = np.ascontiguousarray(cand_off, dtype=np.int64)
+    rows = np.ascontiguousarray(cands, dtype=np.int64).reshape(-1, 20)
+    flat = np.ascontiguousarray(seqs, dtype=np.uint8).reshape(-1)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    bco = np.ascontiguousarray(bc_pair_off, dtype=np.int64)
+    n_reads = len(lens)
+    if len(off) != n_reads + 1 or int(off[-1]) != len(rows) or len(regs) != len(alns) or int(lens.sum()) != len(flat) or len(bco) < 2:
+        raise ValueError("reads, candidate rows and alignment rows do not match")
+    cs = ce = None
+    if centromeres is not None:
+        cs, ce = (np.ascontiguousarray(x, dtype=np.int64) for x in centromeres)
+        if len(cs) != len(ref.contigs()[0]) or len(ce) != len(cs):
+            raise ValueError("one centromere per contig")
+    post, split = np.zeros(len(rows), dtype=POST_DTYPE), np.zeros(n_reads, dtype=SPLIT_DTYPE)
+    lens_of = lens[rows[:, 1].clip(0, n_reads - 1)] if len(rows) else lens[:0]
+    mm_cap = int(lens_of.sum()) + 1                                 # a candidate lists at most one location per base of its read
+    mm_ref, mm_read, n_mm = np.zeros(mm_cap, dtype=np.int32), np.zeros(mm_cap, dtype=np.int32), C.c_int64(-1)
+    t_cap = 64
+    while t_cap < 2 * n_reads:
+        t_cap <<= 1
+    table = np.full(t_cap, -2, dtype=np.int32) if census else None
+    home, n_table = np.full(n_reads, -2, dtype=np.int32), C.c_int32(0)
+    rc = _selftest_fn(ref.lib, "arx_selftest_post")(ref.h, n_reads, off.ctypes.data, rows.ctypes.data, len(regs), regs.ctypes.data, alns.ctypes.data, cig.ctypes.data, len(cig),
+                                                    flat.ctypes.data, lens.ctypes.data, len(bco) - 1, bco.ctypes.data, int(penalty),
+                                                    None if cs is None else cs.ctypes.data, None if ce is None else ce.ctypes.data, post.ctypes.data, split.ctypes.data,
+                                                    mm_ref.ctypes.data, mm_read.ctypes.data, mm_cap, C.byref(n_mm), None if table is None else table.ctypes.data, t_cap,
+                                                    C.byref(n_table), home.ctypes.data, int(grid_cap), int(order))
+    if rc != 0:
+        e = ArachneError("arx_selftest_post: code %d" % rc)
+        e.code = rc
+        raise e
+    return dict(post=post, split=split, mm_ref=mm_ref[:n_mm.value].copy(), mm_read=mm_read[:n_mm.value].copy(),
+                table=None if table is None else table[:n_table.value].copy(), home=home if census else None)
 
 
 class _RecordsLayout(C.Structure):

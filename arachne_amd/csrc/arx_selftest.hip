@@ -6,6 +6,8 @@
 // arx_selftest_rfa (selftest_rfa.h) the whole placement stage on alignments the caller made up (tests/test_block_primitives_gpu.py, tests/test_rfa_cases_gpu.py).
 // arx_selftest_reg2aln (selftest_reg2aln.h) runs stage 6 itself -- Pipeline::stage_reg2aln with its slot loop, k_reg2aln_nw_g16 per band class, the launch
 // that takes what they hand on, the one-thread path and compact() -- on regions the caller made up (tests/test_cigar_stage_gpu.py).
+// arx_selftest_post (selftest_post.h) runs PostStage::run -- the CIGAR walk, the duplicate table, the split pass -- on candidates the caller made up
+// (tests/test_post_stage_gpu.py).
 // Its own unit so that the unit of the list-bookkeeping kernels does not grow.
 #include <climits>
 #include <vector>
@@ -15,6 +17,7 @@
 #include "dev_records_full.h"
 #include "selftest_rfa.h"
 #include "selftest_reg2aln.h"
+#include "selftest_post.h"
 
 namespace arx {
 
@@ -374,6 +377,28 @@ extern "C" int arx_selftest_reg2aln(arx_ctx *ctx, const uint8_t *bases, const in
 		rt.timing = false;
 		if (grid_cap > 0) { rt.n_cu = 1; rt.sw.coop_bpc = grid_cap; } // class launches of at most grid_cap workgroups, two for what they hand on: every group takes many regions
 		return selftest_reg2aln_run(rt, *ix, bases, lens, n_reads, cap, n_regs, regs, reg_off, alns, aln_cap, cigars, cig_cap, n_cig, err, census, census_cap);
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+}
+
+// The passes between placement and the BAM records on the caller's candidates: PostStage::run on a runtime of its own, with ctx's index and the ARX_*
+// switches as they are at the call.  (order: the host double's item order; a GPU's arrival order is not ours to choose)
+extern "C" int arx_selftest_post(arx_ctx *ctx, int32_t n_reads, const int64_t *cand_off, const int64_t *cands, int64_t n_regs, const int64_t *regs, const int64_t *alns,
+                                 const uint32_t *cigars, int64_t n_cig, const uint8_t *bases, const int32_t *lens, int32_t n_barcodes, const int64_t *bc_pair_off,
+                                 int32_t penalty, const int64_t *cen_start, const int64_t *cen_end, void *post, void *split, int32_t *mm_ref, int32_t *mm_read,
+                                 int64_t mm_cap, int64_t *n_mm, int32_t *table, int64_t table_cap, int32_t *n_table, int32_t *home, int32_t grid_cap, int32_t)
+{
+	using namespace arx;
+	const IndexView *ix = ctx_index_view(ctx);
+	if (!ix) return ARX_E_ARG;
+	try {
+		HipRT rt;
+		if (!rt.init(arx_ctx_device(ctx)).empty()) return ARX_E_DEVICE;
+		rt.timing = false;
+		if (grid_cap > 0) { rt.n_cu = 1; rt.sw.bpc = grid_cap; rt.sw.wide = false; } // launch_wide's capped form on grid_cap workgroups: every lane strides through many items
+		return selftest_post_run(rt, *ix, n_reads, cand_off, cands, n_regs, regs, alns, cigars, n_cig, bases, lens, n_barcodes, bc_pair_off, penalty, cen_start, cen_end,
+		                         post, split, mm_ref, mm_read, mm_cap, n_mm, table, table_cap, n_table, home);
 	} catch (const std::exception &) {
 		return ARX_E_DEVICE;
 	}

@@ -61,7 +61,10 @@ struct KSplit {
 	}
 };
 
-struct PostResult { CandPost *d_post = nullptr; SplitRec *d_split = nullptr; int32_t *d_mm_ref = nullptr, *d_mm_read = nullptr; int64_t n_mm = 0; };
+struct PostResult {
+	CandPost *d_post = nullptr; SplitRec *d_split = nullptr; int32_t *d_mm_ref = nullptr, *d_mm_read = nullptr; int64_t n_mm = 0;
+	int32_t *d_table = nullptr, *d_act = nullptr, *d_bc_of = nullptr; uint32_t cap = 0; // the duplicate table (cap slots) and what its keys are made of, for arx_selftest_post
+};
 
 template <class RT> struct PostStage {
 	static int run(Pipeline<RT> &pipe, const typename Pipeline<RT>::DeviceBatch &b, typename Pipeline<RT>::Work &w, const RfaResult &rfa, PostResult &res)
@@ -92,6 +95,7 @@ template <class RT> struct PostStage {
 		KSplit ks{rfa.d_cands, post, rfa.d_cand_off, act, b.lens, rfa.penalty, rfa.d_cen_start, rfa.d_cen_end, split};
 		rt.launch_wide("split", R, ks);
 		res.d_post = post; res.d_split = split; res.d_mm_ref = mm_ref; res.d_mm_read = mm_read; res.n_mm = NM;
+		res.d_table = table; res.d_act = act; res.d_bc_of = bc_of; res.cap = cap;
 		return 0;
 	}
 	static void fetch(Pipeline<RT> &pipe, const typename Pipeline<RT>::DeviceBatch &b, const RfaResult &rfa, const PostResult &res, CandPost *post, SplitRec *split,

@@ -663,6 +663,28 @@ int arx_selftest_reg2aln(arx_ctx *ctx, const uint8_t *bases, const int32_t *lens
                          int32_t *reg_off, void *alns, int64_t aln_cap, uint32_t *cigars, int64_t cig_cap, int64_t *n_cig, uint32_t *err, int64_t *census,
                          int64_t census_cap, int32_t grid_cap);
 
+/* self-test of the passes between placement and the BAM records (what arx_batch_post runs: GetAlignments' CIGAR walk with the mismatch lists and
+ * `matches`, markDuplicates, CheckSplitReads) on candidates the caller made up, in the int64 row layouts of the CPU restatement (oracle/arx_oracle.h;
+ * ora_post takes the same arrays): cands holds cand_off[n_reads] rows of 20 columns (reg read pos aend reversed rid score ... lap2 active ...), read
+ * after read; regs (20 columns, only qb / qe are read) and alns (12 columns, only NM / n_cigar / cigar_off are read) hold n_regs rows, a candidate's
+ * column `reg` names its row (-1: the placeholder of a read without hits); cigars: n_cig words; bases: the reads back to back (codes 0..4).  The
+ * stage runs on a runtime of its own with ctx's index (pac, contig offsets and lengths) and the ARX_* switches as they are at the call.
+ * Checked before anything is uploaded (ARX_E_ARG): n_reads even, 0 <= lens <= 255, every read has a candidate and its rows carry its id, reg inside
+ * [-1, n_regs), rid inside [0, n_seqs) (-1 allowed for a placeholder), -1 <= pos, 0 <= aend, both below 2^31, pos <= aend <= pos + 2^18, reversed
+ * and active 0 or 1, |score|, |lap2|, |qb|, |qe|, |NM| at most 2^24, at most 64 CIGAR words per alignment inside [0, n_cig), each of length <= 4096,
+ * barcodes that tile the pairs, both centromere arrays (n_seqs values each) or neither.
+ * Out: post (cand_off[n_reads] records of 24 bytes: qb qe matches n_mm mm_off duplicate), split (n_reads records of 32 bytes: split mapq is_proper
+ * n_split_cand order_pinned second_best2 score2 pad), mm_ref / mm_read (*n_mm locations; ARX_E_TOO_LARGE with *n_mm set when mm_cap is smaller).
+ * table (may be NULL: nothing of it is copied): the duplicate table as the launches leave it in device memory (*n_table slots of read ids, -1: free;
+ * ARX_E_TOO_LARGE when table_cap is smaller), and home[n_reads]: the slot each read's key hashes to, written by the table's own hash function.
+ * grid_cap > 0: every thread-per-item launch on at most that many workgroups of 64 lanes, which stride through the items; 0: the launch shapes of
+ * arx_batch_post.  order: the item order of the host test double's launches (0 ascending, 1 descending, 2 a stride permutation); the library
+ * ignores it -- the order in which a GPU's lanes arrive is nobody's to choose. */
+int arx_selftest_post(arx_ctx *ctx, int32_t n_reads, const int64_t *cand_off, const int64_t *cands, int64_t n_regs, const int64_t *regs, const int64_t *alns,
+                      const uint32_t *cigars, int64_t n_cig, const uint8_t *bases, const int32_t *lens, int32_t n_barcodes, const int64_t *bc_pair_off,
+                      int32_t penalty, const int64_t *cen_start, const int64_t *cen_end, void *post, void *split, int32_t *mm_ref, int32_t *mm_read,
+                      int64_t mm_cap, int64_t *n_mm, int32_t *table, int64_t table_cap, int32_t *n_table, int32_t *home, int32_t grid_cap, int32_t order);
+
 /* self-tests of the three DP kernel families on plain host arrays (csrc/arx_selftest.hip; tests/test_dp_kernels_gpu.py): each entry
  * uploads the tasks, launches the production code on them and returns one result row per task, in input order.  The reference text is
  * passed in bwa's .pac layout (pac: (l_pac + 3) / 4 bytes, 2 bits per base, first base in the top bits); coordinates are doubled, so a

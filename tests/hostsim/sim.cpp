@@ -149,7 +149,16 @@ struct SimRT {
 	void set_seed_read_len(int) {}
 	std::map<std::string, KernelTimer> &timers() { return tm; }
 	void timers_reset(bool) { tm.clear(); }
-	template <class F> void launch(const char *nm, int n, const F &f) { tm[nm].calls++; tm[nm].items += n; for (int i = 0; i < n; ++i) f(i, 0); }
+	// the order in which a thread-per-item launch takes its items: 0 ascending, 1 descending, 2 SimBlock::pfor's stride permutation.  A GPU has every
+	// order by nature; only arx_selftest_post below sets it (a launch whose result depends on it is a race there)
+	int item_order = 0;
+	template <class F> void launch(const char *nm, int n, const F &f)
+	{
+		tm[nm].calls++; tm[nm].items += n;
+		if (item_order == 0) { for (int i = 0; i < n; ++i) f(i, 0); return; }
+		SimBlock blk{item_order};
+		blk.pfor(n, [&](int i) { f(i, 0); });
+	}
 	template <class F> void launch_small(const char *nm, int n, const F &f) { launch(nm, n, f); }
 	template <class F> void launch_wide(const char *nm, int n, const F &f) { launch(nm, n, f); }
 	template <class F> void launch_block(const char *nm, int n, const F &f, const uint8_t * = nullptr) { tm[nm].calls++; tm[nm].items += n; SimBlock blk{sim_pfor}; for (int i = 0; i < n; ++i) f(i, blk); }
@@ -185,6 +194,7 @@ struct SimRT {
 #include "../../arachne_amd/csrc/api_impl.h"
 #include "../../arachne_amd/csrc/selftest_rfa.h"
 #include "../../arachne_amd/csrc/selftest_reg2aln.h"
+#include "../../arachne_amd/csrc/selftest_post.h"
 ARX_DEFINE_C_API(arx::SimRT)
 
 // test entry: the bytes of a batch's work arena that are live now (tests/test_arena_lifecycle.py: no phase grows from one cycle to the next, and
@@ -441,6 +451,21 @@ extern "C" int arx_selftest_reg2aln(arx_ctx *h, const uint8_t *bases, const int3
 	arx::SimRT rt;
 	return arx::selftest_reg2aln_run(rt, ((arx::Context<arx::SimRT> *)h)->ix, bases, lens, n_reads, cap, n_regs, regs, reg_off, alns, aln_cap, cigars, cig_cap, n_cig, err,
 	                                 census, census_cap);
+}
+
+// the post passes on given candidates run here too: the same PostStage::run.  order: SimRT::item_order for every launch of the stage -- the duplicate
+// table is the one structure its items share, and dup_insert's atomic minimum decides only when a group's later read arrives first (order 1 and 2).
+// (grid_cap: the double has no grid)
+extern "C" int arx_selftest_post(arx_ctx *h, int32_t n_reads, const int64_t *cand_off, const int64_t *cands, int64_t n_regs, const int64_t *regs, const int64_t *alns,
+                                 const uint32_t *cigars, int64_t n_cig, const uint8_t *bases, const int32_t *lens, int32_t n_barcodes, const int64_t *bc_pair_off,
+                                 int32_t penalty, const int64_t *cen_start, const int64_t *cen_end, void *post, void *split, int32_t *mm_ref, int32_t *mm_read,
+                                 int64_t mm_cap, int64_t *n_mm, int32_t *table, int64_t table_cap, int32_t *n_table, int32_t *home, int32_t, int32_t order)
+{
+	if (!h || order < 0 || order > 2) return ARX_E_ARG;
+	arx::SimRT rt;
+	rt.item_order = order;
+	return arx::selftest_post_run(rt, ((arx::Context<arx::SimRT> *)h)->ix, n_reads, cand_off, cands, n_regs, regs, alns, cigars, n_cig, bases, lens, n_barcodes, bc_pair_off,
+	                              penalty, cen_start, cen_end, post, split, mm_ref, mm_read, mm_cap, n_mm, table, table_cap, n_table, home);
 }
 
 // test entry: the one-thread extension (dev_sw.h ext2_task, what ARX_SW_SIMPLE runs) on tasks laid out as arx_selftest_extend takes them --
