@@ -164,6 +164,10 @@ _SELFTEST_ARGS = {
     "arx_selftest_fastq_sort": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7,
     "arx_fastq_sort_ex": [C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int64, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_fastq_sort_ext": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7,
+    # the header standardization in front of it
+    "arx_fastq_standardize": [C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32],
+    "arx_selftest_fastq_standardize": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] +
+                                      [C.c_void_p] * 5,
     # the .bai of a coordinate-sorted BAM file
     "arx_bam_index": [C.c_int32, C.c_char_p, C.c_char_p, C.c_int64, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_bam_index": [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
@@ -343,6 +347,75 @@ def selftest_fastq_sort(t1, t2, window_bytes: int = 0, slab_bytes: int = 0, devi
     l1, l2 = (int(out_len[0]), int(out_len[1])) if rc == ARX_OK else (n1, n2)
     return dict(rc=rc, out1=out1[:l1].tobytes(), out2=out2[:l2].tobytes(), rest1=out1[l1:n1].tobytes(), rest2=out2[l2:n2].tobytes(), guard1=out1[n1:].tobytes(),
                 guard2=out2[n2:].tobytes(), rec_off1=off1, rec_off2=off2, n_records=int(n_rec.value), stats=_fqsort_stats(st))
+
+
+FQSTD_BGZF, FQSTD_DETECT, FQSTD_TIMED = 1, 2, 0x100
+FQSTD_FORMATS = ("auto", "haplotagging", "stlfr", "tellseq", "standard", "unknown")      # ARX_FQSTD_*: the last two are results only
+_FQSTD_STATS = ("records", "bytes_in_r1", "bytes_in_r2", "bytes_out_r1", "bytes_out_r2", "skipped_lines", "format", "decided_by", "with_barcode", "valid", "longest_barcode",
+                "windows", "slabs", "read_us", "inflate_us", "parse_us", "fields_us", "compose_us", "compress_us", "write_us")
+
+
+def _fqstd_stats(st):
+    d = {k: int(st[i]) for i, k in enumerate(_FQSTD_STATS)}
+    d["format"] = FQSTD_FORMATS[d["format"]]
+    return d
+
+
+def _fqstd_format(format):
+    if isinstance(format, str):
+        if format not in FQSTD_FORMATS:
+            raise ValueError("format is one of " + ", ".join(FQSTD_FORMATS[:4]))
+        return FQSTD_FORMATS.index(format)
+    return int(format)
+
+
+def fastq_standardize(r1: str, r2: str, r1_out: "str | None" = None, r2_out: "str | None" = None, format="auto", bgzf: bool = False, detect: bool = False,
+                      timed: bool = False, device: int = 0, lib_path: str = LIB_PATH):
+    """The headers of a haplotagging, stLFR or TELLseq FASTQ pair rewritten on the GPU to `@<id>/1\tBX:Z:<barcode>\tVX:i:<0|1>`, the form the
+    feeder and fastq_sort read (include/arachne_amd.h: arx_fastq_standardize has the contract).  format: "auto" detects from the first 200
+    records, "haplotagging", "stlfr" or "tellseq" force one (a number is passed on as it is).  Inputs plain, gzip or BGZF; outputs plain, or
+    BGZF with bgzf=True.  detect=True only detects: nothing is written, the outputs may be None.  -> the stats as a dict, "format" as a name:
+    "standard" under "auto" says that nothing was written and the inputs serve as they are.  ArachneError with .code on failure -- an
+    unknown format under "auto" among them -- and nothing is left behind then."""
+    lib = _load(lib_path)
+    st, msg = np.zeros(20, dtype=np.int64), C.create_string_buffer(1024)
+    flags = (FQSTD_BGZF if bgzf else 0) | (FQSTD_DETECT if detect else 0) | (FQSTD_TIMED if timed else 0)
+    enc = lambda p: None if p is None else os.fsencode(p)
+    rc = _selftest_fn(lib, "arx_fastq_standardize")(device, enc(r1), enc(r2), enc(r1_out), enc(r2_out), _fqstd_format(format), flags, st.ctypes.data, msg, 1024)
+    if rc != 0:
+        e = ArachneError("arx_fastq_standardize: " + msg.value.decode(errors="replace"))
+        e.code = rc
+        raise e
+    return _fqstd_stats(st)
+
+
+def selftest_fastq_standardize(t1, t2, format="auto", window_bytes: int = 0, slab_bytes: int = 0, cap1: "int | None" = None, cap2: "int | None" = None, device: int = 0,
+                               fill: int = 0xA5, lib_path: str = LIB_PATH):
+    """arx_fastq_standardize's orchestration, detection included, on two texts in memory (include/arachne_amd.h: arx_selftest_fastq_standardize)
+    -> dict(rc: the entry's return value (0; ARX_E_TOO_LARGE = -4 for a line or record longer than a window or an output longer than its room;
+    ARX_E_ARG = -2 where "auto" finds no format), out1, out2: the rewritten texts, guard1, guard2: the 8 bytes behind the room the entry was
+    given (cap1, cap2: by default what always suffices), rec_off1, rec_off2: where the records start (-1 behind n_records + 1 entries),
+    n_records, out_len, stats).  On an error, and where "auto" finds standard, everything is as it was filled: `fill`, -1."""
+    lib = _load(lib_path)
+    s1, s2 = np.frombuffer(bytes(t1), dtype=np.uint8), np.frombuffer(bytes(t2), dtype=np.uint8)
+    n1, n2 = len(s1), len(s2)
+    cap1 = 2 * n1 + 17 * (n1 // 5 + 2) if cap1 is None else int(cap1)
+    cap2 = 2 * n1 + n2 + 17 * (n1 // 5 + 2) if cap2 is None else int(cap2)
+    out1, out2 = np.full(cap1 + 8, fill, dtype=np.uint8), np.full(cap2 + 8, fill, dtype=np.uint8)
+    off1, off2 = np.full(n1 // 5 + 2, -1, dtype=np.int64), np.full(n1 // 5 + 2, -1, dtype=np.int64)
+    n_rec, out_len, st = C.c_int64(-1), np.full(2, -1, dtype=np.int64), np.zeros(20, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_fastq_standardize")(device, s1.ctypes.data if n1 else None, n1, s2.ctypes.data if n2 else None, n2, _fqstd_format(format),
+                                                             int(window_bytes), int(slab_bytes), out1.ctypes.data, cap1, out2.ctypes.data, cap2, out_len.ctypes.data,
+                                                             off1.ctypes.data, off2.ctypes.data, C.byref(n_rec), st.ctypes.data)
+    stats = _fqstd_stats(st)
+    if rc not in (ARX_OK, ARX_E_TOO_LARGE) and not (rc == ARX_E_ARG and stats["format"] == "unknown"):
+        e = ArachneError("arx_selftest_fastq_standardize: code %d" % rc)
+        e.code = rc
+        raise e
+    written = rc == ARX_OK and int(n_rec.value) >= 0
+    l1, l2 = (int(out_len[0]), int(out_len[1])) if written else (0, 0)
+    return dict(rc=rc, out1=out1[:l1].tobytes(), out2=out2[:l2].tobytes(), rest1=out1[l1:cap1].tobytes(), rest2=out2[l2:cap2].tobytes(), guard1=out1[cap1:].tobytes(),
+                guard2=out2[cap2:].tobytes(), rec_off1=off1, rec_off2=off2, n_records=int(n_rec.value), out_len=out_len, stats=stats)
 
 
 _FQSORT_EX_STATS = _FQSORT_STATS + ("sorted_runs", "tmp_bytes", "run_write_us", "run_read_us")

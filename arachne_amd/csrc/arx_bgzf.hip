@@ -2,7 +2,8 @@
 // hip_bgzf.h behind its seam.  Its own unit: the kernels of dev_bgzf.h compile next to the pipeline's.  The mirror image lives here too: the
 // inflate kernel of hip_inflate.h (arx_selftest_inflate; the device feeder starts it through inflate_launch).  And what needs both: the coordinate
 // sort of a BAM file into an open writer (arx_bam_open_ex, arx_bam_sort_append, arx_selftest_bam_sort: dev_bamsort.h, hip_bamsort.h), and the sort
-// of a FASTQ file pair by barcode (arx_fastq_sort, arx_selftest_fastq_sort: dev_fqsort.h, hip_fqsort.h), and the .bai of a coordinate-sorted
+// of a FASTQ file pair by barcode (arx_fastq_sort, arx_selftest_fastq_sort: dev_fqsort.h, hip_fqsort.h) with the header standardization in front of it (arx_fastq_standardize,
+// arx_selftest_fastq_standardize: dev_fqstd.h, hip_fqstd.h), and the .bai of a coordinate-sorted
 // BAM file (arx_bam_index, arx_selftest_bam_index: dev_bamindex.h, hip_bamindex.h).
 #include <map>
 #include <memory>
@@ -12,6 +13,7 @@
 #include "hip_inflate.h"
 #include "hip_bamsort.h"
 #include "hip_fqsort.h"
+#include "hip_fqstd.h"
 #include "hip_bamindex.h"
 
 namespace arx {
@@ -425,6 +427,105 @@ extern "C" int arx_selftest_fastq_sort_ext(int32_t device, const uint8_t *t1, in
 		out_len[0] = c.bytes1; out_len[1] = c.bytes2;
 		*n_records = N;
 		arx::fx_stats(stats, drv, c, n1, n2, true, S, io);
+	} catch (const arx::FsTooLarge &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::HipOutOfMemory &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}
+
+// ---- in front of the sort: haplotagging, stLFR and TELLseq headers rewritten to the feeder's form (dev_fqstd.h, hip_fqstd.h)
+extern "C" int arx_fastq_standardize(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t format, int32_t flags, int64_t *stats,
+                                     char *msg, int32_t msg_cap)
+{
+	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
+	if (stats) for (int k = 0; k < arx::FQS_N_STATS; ++k) stats[k] = 0;
+	if (flags & ~(ARX_FQSTD_BGZF | ARX_FQSTD_DETECT | ARX_FQSTD_TIMED)) { say("arx_fastq_standardize: unknown flag bits"); return ARX_E_ARG; }
+	if (format < ARX_FQSTD_AUTO || format > ARX_FQSTD_TELLSEQ) { say("arx_fastq_standardize: format is ARX_FQSTD_AUTO, _HAPLOTAGGING, _STLFR or _TELLSEQ"); return ARX_E_ARG; }
+	const bool detect = (flags & ARX_FQSTD_DETECT) != 0;
+	if (!r1_in || !r2_in || (!detect && (!r1_out || !r2_out))) { say("arx_fastq_standardize: null argument"); return ARX_E_ARG; }
+	const char *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
+	if (!detect) {
+		if (fs_same_file(r1_out, r2_out)) { say("arx_fastq_standardize: the two output paths are the same file"); return ARX_E_ARG; }
+		for (int i = 0; i < 2; ++i)
+			for (int o = 0; o < 2; ++o)
+				if (fs_same_file(in[i], out[o])) { say(std::string("arx_fastq_standardize: ") + out[o] + " is an input and an output"); return ARX_E_ARG; }
+	}
+	std::string err;
+	try {
+		const int rc = arx::fqs_files(device, in, out, format, flags, stats, err, arx::shared_device_bgzf);
+		if (rc != ARX_OK) say(err);
+		return rc;
+	} catch (const arx::FsTooLarge &e) {
+		say(e.what());
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::FsIoError &e) {
+		say(e.what());
+		return ARX_E_IO;
+	} catch (const arx::HipOutOfMemory &e) { // the windows or the slab buffers (hip_res.h)
+		say("the device memory does not hold the windows and slabs of the call (" + std::to_string(e.wanted >> 20) + " MiB more were asked for, " + std::to_string(e.free_bytes >> 20) +
+		    " MiB are free)");
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &e) {
+		say(e.what());
+		return ARX_E_DEVICE;
+	}
+}
+
+extern "C" int arx_selftest_fastq_standardize(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int32_t format, int64_t window_bytes, int64_t slab_bytes,
+                                              uint8_t *out1, int64_t cap1, uint8_t *out2, int64_t cap2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2, int64_t *n_records,
+                                              int64_t *stats)
+{
+	if (n1 < 0 || n2 < 0 || cap1 < 0 || cap2 < 0 || !out_len || !rec_off1 || !rec_off2 || !n_records || (n1 > 0 && !t1) || (n2 > 0 && !t2) || (cap1 > 0 && !out1) || (cap2 > 0 && !out2) ||
+	    slab_bytes < 0 || format < ARX_FQSTD_AUTO || format > ARX_FQSTD_TELLSEQ || (window_bytes != 0 && (window_bytes < arx::FS_MIN_WINDOW || window_bytes > arx::FS_MAX_WINDOW)))
+		return ARX_E_ARG;
+	if (stats) for (int k = 0; k < arx::FQS_N_STATS; ++k) stats[k] = 0;
+	const int64_t window = window_bytes ? window_bytes : arx::FS_WINDOW_DEFAULT, slab = slab_bytes ? slab_bytes : arx::FS_SLAB_DEFAULT;
+	try {
+		arx::select_device(device, arx::FQS_NO_DEVICE);
+		arx::Stream st;
+		st.create();
+		arx::FqsHipDrv drv; drv.st = st;
+		int fmt = format;
+		int64_t decided = -1;
+		if (format == ARX_FQSTD_AUTO) {
+			arx::FxMemSrc src;
+			src.st = st; src.t[0] = t1; src.t[1] = t2; src.n[0] = n1; src.n[1] = n2;
+			arx::FqsCounts d;
+			const int rc = arx::fqs_detect(drv, src, window, d);
+			drv.pass_done();
+			if (rc != arx::FS_OK) return rc == arx::FS_E_TOO_LARGE ? ARX_E_TOO_LARGE : ARX_E_DEVICE;
+			fmt = d.format; decided = d.decided;
+			if (fmt == ARX_FQSTD_STANDARD || fmt == ARX_FQSTD_UNKNOWN) {
+				d.n_records = 0; // nothing was written
+				arx::fqs_stats(stats, drv, d, fmt, decided, 0, 0, 0);
+				return fmt == ARX_FQSTD_STANDARD ? ARX_OK : ARX_E_ARG;
+			}
+		}
+		arx::FxMemSrc src;
+		src.st = st; src.t[0] = t1; src.t[1] = t2; src.n[0] = n1; src.n[1] = n2;
+		arx::FsMemSink sink;
+		sink.init(drv.st);
+		arx::FqsCounts c;
+		std::vector<int64_t> off1, off2;
+		c.off1 = &off1; c.off2 = &off2;
+		const int rc = arx::fqs_convert(drv, src, fmt, window, slab, sink, c);
+		if (rc != arx::FS_OK) return rc == arx::FS_E_TOO_LARGE ? ARX_E_TOO_LARGE : ARX_E_DEVICE;
+		sink.flush();
+		drv.pass_done();
+		const int64_t N = c.n_records;
+		if ((int64_t)sink.text[0].size() != c.bytes1 || (int64_t)sink.text[1].size() != c.bytes2 || (int64_t)off1.size() != N + 1 || (int64_t)off2.size() != N + 1) return ARX_E_DEVICE;
+		if (c.bytes1 > cap1 || c.bytes2 > cap2) return ARX_E_TOO_LARGE;
+		// everything is here: only now is anything of the caller's written
+		if (c.bytes1) memcpy(out1, sink.text[0].data(), (size_t)c.bytes1);
+		if (c.bytes2) memcpy(out2, sink.text[1].data(), (size_t)c.bytes2);
+		memcpy(rec_off1, off1.data(), (size_t)(N + 1) * 8); memcpy(rec_off2, off2.data(), (size_t)(N + 1) * 8);
+		out_len[0] = c.bytes1; out_len[1] = c.bytes2;
+		*n_records = N;
+		arx::fqs_stats(stats, drv, c, fmt, decided, sink.us_consume, 0, 0);
 	} catch (const arx::FsTooLarge &) {
 		return ARX_E_TOO_LARGE;
 	} catch (const arx::HipOutOfMemory &) {

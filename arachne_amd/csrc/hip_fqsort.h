@@ -84,7 +84,7 @@ struct FsHipDrv {
 	{
 		if (!strncmp(nm, "fq_", 3) || !strcmp(nm, "fs_window") || !strcmp(nm, "fs_store") || !strcmp(nm, "fs_scan32")) return FS_T_PARSE;
 		if (!strcmp(nm, "fs_sort")) return FS_T_SORT;
-		if (!strcmp(nm, "fs_gather") || !strcmp(nm, "fs_sizes") || !strcmp(nm, "fx_gather")) return FS_T_GATHER;
+		if (!strcmp(nm, "fs_gather") || !strcmp(nm, "fs_sizes") || !strcmp(nm, "fx_gather") || !strcmp(nm, "fqs_compose")) return FS_T_GATHER;
 		return FS_T_KEYS; // length and chunk keys, runs, their scans and reductions
 	}
 	template <class Fn> void booked(const char *nm, Fn fn)

@@ -246,6 +246,31 @@ def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "hos
     return out
 
 
+def standardize(r1: str, r2: str, out_dir: str, format="auto", bgzf: bool = False, device: int = 0, lib_path: str = api.LIB_PATH):
+    """The step in front of presort(): a haplotagging, stLFR or TELLseq pair with its headers rewritten on the GPU to the BX:Z: / VX:i: form the
+    feeder and the sort read (api.fastq_standardize; the reference's half-written standardize.go).  format "auto" detects from the first 200
+    records; a pair that is standard already is returned as it is.  The rewritten files go to out_dir under the inputs' base names
+    (+ ".std.fastq", ".gz" with bgzf).  -> (r1_std, r2_std, stats); stats["standardized"] says whether files were written."""
+    def name(p):
+        b = os.path.basename(p)
+        for ext in (".gz", ".bgz", ".fastq", ".fq"):
+            if b.endswith(ext):
+                b = b[:-len(ext)]
+        return os.path.join(out_dir, b + ".std.fastq" + (".gz" if bgzf else ""))
+    if api._fqstd_format(format) == 0:
+        st = api.fastq_standardize(r1, r2, detect=True, device=device, lib_path=lib_path)
+        if st["format"] == "standard":
+            return r1, r2, dict(st, standardized=False)
+        if st["format"] != "unknown":
+            format = st["format"]       # detected once; "unknown" goes on to the call, whose error says what to do
+    os.makedirs(out_dir, exist_ok=True)
+    o1, o2 = name(r1), name(r2)
+    if o1 == o2:
+        o2 = o2.replace(".std.", ".std.2.")
+    st = api.fastq_standardize(r1, r2, o1, o2, format=format, bgzf=bgzf, device=device, lib_path=lib_path)
+    return o1, o2, dict(st, standardized=True)
+
+
 def presort(r1: str, r2: str, out_dir: str, device: int = 0, bgzf: bool = False, if_needed: bool = True, lib_path: str = api.LIB_PATH, run_bytes: int = 0,
             tmp_dir: "str | None" = None):
     """The step in front of run(): the file pair sorted by barcode on the GPU (api.fastq_sort; the reference's `arachne preprocess`), which

@@ -457,6 +457,79 @@ int arx_fastq_sort_ex(int32_t device, const char *r1_in, const char *r2_in, cons
 int arx_selftest_fastq_sort_ext(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int64_t window_bytes, int64_t slab_bytes, int64_t run_bytes,
                                 uint8_t *out1, uint8_t *out2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2, int64_t *n_records, int64_t *stats);
 
+/* ---- in front of the sort: the headers of a haplotagging, stLFR or TELLseq FASTQ pair rewritten on the GPU to the form the feeder's barcode
+ * rule and the sort's key read, `@<id>/1\tBX:Z:<barcode>\tVX:i:<0|1>`.  The reference has this step half-written in
+ * src/preprocess/standardize.go (format detection on the first 200 records, three converters, the rewrite of both headers); that file does
+ * not compile (a dangling stdin.Write, convertFunc scoped inside its `if`, Valid concatenated as a string).  What is built is the intended
+ * behaviour, with the repairs and deviations named where they apply.  The contract:
+ *   record     exactly arx_fastq_sort's: lines exist only where they end in '\n'; R1 and R2 are walked in lockstep up to the shorter file's line
+ *              count; while searching, a pair whose R1 line is non-empty and starts with '@' opens a record of four line pairs, any other pair
+ *              is skipped; a record that the end of either file cuts off does not exist
+ *   H          the R1 header without its '@', the line's own '\n' standing as closing white space.  White space (\s, \S below) is the feeder's
+ *              set: ' ', \t, \n, \r, \v, \f, so that what this step calls a barcode is what the feeder will see; digits are 0-9.  R2's header
+ *              plays no part and is dropped
+ *   matchers   "the pattern matches at some position of H", each decidable by one forward scan from each candidate start:
+ *                standard      BX:Z:(\S+)\s matches somewhere AND VX:i:([01])\s matches somewhere
+ *                haplotagging  BX:Z:A\d\dC\d\dB\d\dD\d\d\s
+ *                stLFR         #[0-9]+_[0-9]+_[0-9]+(/[12])?\s     (repair: standardize.go:22 has no (/[12])?, so it cannot match the #1_2_3/1
+ *                                                                   that stLFR files carry)
+ *                TELLseq       :[ATCGN]+\s                         (upper case only)
+ *   detection  (findFastqFormat, standardize.go:102-127) records 0..199 in input order, fewer if the input has fewer; the first record that
+ *              matches any pattern decides, the order of trial being standard, haplotagging, stLFR, TELLseq; no such record: unknown.  The
+ *              reference applies the matchers to record.ReadInfo, which ParseHeader has stripped of its tags; the intended subject is H.
+ *              Detection is a pass of its own over the head of the input (it looks at 4 MiB of each file first and at a whole parse
+ *              window only where a record does not fit that, so its result does not depend on the window); files are opened again
+ *              for the conversion
+ *   conversion one format for the whole input.  barcode and v:
+ *                haplotagging  the value of the leftmost BX:Z:(\S+)\s, the feeder's own rule; v = 1 iff it has no two adjacent '0' bytes
+ *                              (repair: standardize.go:138 has the sense inverted)
+ *                stLFR         the n_n_n of the leftmost stLFR match, without /1; v = 1 iff it does not start with "0_", contain "_0_" or end
+ *                              in "_0" (stlfrInvalidRe: 00_1_2 and 10_2_3 are valid)
+ *                TELLseq       the letters of the leftmost TELLseq match; v = 1 iff it holds no 'N' (repair: standardize.go:182 tests the wrong
+ *                              variable)
+ *              a record without a match has the empty barcode and v = 0 (the reference would print 1 for stLFR and TELLseq; the feeder
+ *              reports such a record as not valid anyway)
+ *   id         the first white-space-delimited token of H, leading white space skipped, one trailing /1 or /2 removed when the token ends in
+ *              it; it may be empty; the token is otherwise kept whole, a #... or :ACGT part included
+ *   output     per record, in input order: R1 gets '@' id "/1\tBX:Z:" barcode "\tVX:i:" v '\n' and lines 2-4 of the R1 record verbatim, R2 the
+ *              same header with /2 and lines 2-4 of the R2 record verbatim; the header is 17 + |id| + |barcode| bytes.  (Deviations: the
+ *              reference writes a blank line after the header, which would break the four-line record, and a bare '+'; lines 2-4 verbatim
+ *              lose nothing.)  Skipped lines and the cut-off record are dropped
+ * The property this exists for: where the id contains neither BX:Z: nor VX:i:, the host feeder reads from the output every record with
+ * barcode and valid equal to the barcode and v above, info equal to the id (the feeder's own rule gives a record without a barcode no
+ * info) and the bases and qualities of the input, and arx_fastq_sort of the output orders by that barcode.
+ * format: ARX_FQSTD_AUTO detects first; 1..3 force a format and skip detection; anything else is ARX_E_ARG.  AUTO that finds standard
+ * returns ARX_OK and writes nothing -- no output file and no .tmp is created, stats[6] says so, the caller uses its inputs; AUTO that
+ * finds unknown is ARX_E_ARG (msg: no record of the first 200 names a format, pass one).  ARX_FQSTD_DETECT: only the detection runs, the
+ * output paths may be NULL, and unknown is a result (ARX_OK, stats[6] = 5).  A forced format on an input of zero records gives two empty outputs.
+ * Inputs may be plain text, gzip or BGZF, each file judged by itself; a BGZF file is inflated on the device.  Outputs are plain text, or with
+ * ARX_FQSTD_BGZF BGZF files (blocks cut every 65280 bytes, the 28-byte EOF block last); they are written as <path>.tmp and renamed at the end:
+ * a failing call leaves nothing behind.  The call streams: device memory holds the parse windows (32 MiB per file, twice), their carry and
+ * the output slabs (64 MiB per file, twice), never a file; there is no size limit and no max_bytes (csrc/hip_fqstd.h has the accounting).
+ * ARX_E_ARG: null paths without DETECT, unknown flag bits, a format outside 0..3, an output path that is an input or equals the other output;
+ * ARX_E_IO: a file cannot be read or written, or a block does not inflate (nothing is produced); ARX_E_TOO_LARGE: a line or record that a
+ * window does not hold; ARX_E_DEVICE: no GPU, or a HIP error -- there is no CPU fallback.
+ * stats[20] (may be NULL): [0] records written, [1] [2] inflated bytes read from R1, R2 (the call stops reading where the input ends: a file
+ * that goes on behind the other's last line is not read to its end), [3] [4] bytes written to R1, R2 as inflated text, [5] lines skipped,
+ * [6] the format used or found, [7] the record that decided the detection (-1: forced, or none), [8] records with a barcode, [9] records
+ * written with VX:i:1, [10] longest barcode, [11] parse windows, [12] output slabs, then microseconds: [13] waiting for the readers,
+ * [14] upload and inflate, [15] parse, [16] fields and sizes (TIMED only, otherwise under [17]), [17] compose, [18] compress and write of BGZF
+ * blocks, [19] fetch and write of plain text, last blocks, rename.  Not built: the step fused into the sort; other header formats. */
+enum { ARX_FQSTD_AUTO = 0, ARX_FQSTD_HAPLOTAGGING = 1, ARX_FQSTD_STLFR = 2, ARX_FQSTD_TELLSEQ = 3, ARX_FQSTD_STANDARD = 4, ARX_FQSTD_UNKNOWN = 5 }; /* 4, 5: results only */
+enum { ARX_FQSTD_BGZF = 1, ARX_FQSTD_DETECT = 2, ARX_FQSTD_TIMED = 0x100 };
+int arx_fastq_standardize(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t format, int32_t flags, int64_t *stats,
+                          char *msg, int32_t msg_cap);
+/* self-test of the same orchestration, detection pass included, on two texts in host memory (tests/test_fastq_standardize_gpu.py).
+ * window_bytes and slab_bytes as in arx_selftest_fastq_sort (0: the defaults; a window of at least 128 and at most 2^29 bytes, ARX_E_ARG
+ * outside).  out1[cap1], out2[cap2] receive the rewritten texts, out_len[2] their lengths, rec_off1 / rec_off2[*n_records + 1] where the
+ * records start in them (room for n1 / 5 + 2 entries always suffices); cap1 or cap2 too small is ARX_E_TOO_LARGE -- 2 n1 + 17 (n1 / 5 + 2)
+ * and 2 n1 + n2 + 17 (n1 / 5 + 2) always suffice, because id and barcode may overlap in H.  AUTO that finds unknown is ARX_E_ARG with
+ * stats[6] = 5.  On any error, and where AUTO finds standard (ARX_OK, stats[6] = 4), out1, out2, out_len, rec_off1, rec_off2 and n_records are
+ * untouched. */
+int arx_selftest_fastq_standardize(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int32_t format, int64_t window_bytes, int64_t slab_bytes,
+                                   uint8_t *out1, int64_t cap1, uint8_t *out2, int64_t cap2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2, int64_t *n_records,
+                                   int64_t *stats);
+
 /* ---- between the path and the sink: the placed candidate of every read of a super-batch as BAM records -- the part of DumpToBams /
  * AppendBam (src/aligner/bamwriter.go:283-568, 635-658) that decides flags, position, MAPQ, mate fields, template length, CIGAR op codes,
  * strand of bases and qualities and the RG / AS / XM / AM / XT / BX / VX tags of the primary record (csrc/bam_records.h lists what is left
