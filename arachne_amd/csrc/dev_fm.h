@@ -68,21 +68,6 @@ ARX_DEVI void block_occ4_w(const OccHead &h, uint64_t w, int n, uint64_t cnt[4])
 	cnt[3] = head_cum(h, 3) + (ck >> 24) + p3;
 }
 ARX_DEVI void block_occ4(const uint32_t *blk, const OccHead &h, int n, uint64_t cnt[4]) { block_occ4_w(h, load_quarter(blk, (n - 1) >> 5), n, cnt); }
-// The same counts modulo 2^32, and what the block itself adds to each (at most 128) -- all an extension needs but for ONE symbol: the sizes of
-// the four children are differences of two such counts and lie below 2^32 (an interval never holds more rows than the text has symbols of one
-// kind on both strands), so they are exact in 32 bits; only the new interval's own row wants the 40-bit count (ext_finish).
-ARX_DEVI void block_occ4_lo(const OccHead &h, uint64_t w, int n, uint32_t cnt[4], uint32_t add[4])
-{
-	const int q = (n - 1) >> 5, nj = n - 32 * q; // nj in 1..32
-	const uint64_t keep = ~0ull << (64 - 2 * nj);
-	const uint64_t lo = w & 0x5555555555555555ull & keep, hi = (w >> 1) & 0x5555555555555555ull & keep;
-	const uint32_t p3 = (uint32_t)__builtin_popcountll(hi & lo);
-	const uint32_t c2 = (uint32_t)__builtin_popcountll(hi) - p3, c1 = (uint32_t)__builtin_popcountll(lo) - p3;
-	const uint32_t c0 = (uint32_t)nj - c1 - c2 - p3;
-	const uint32_t ck = head_ck(h, q);
-	add[0] = (ck & 0xff) + c0; add[1] = ((ck >> 8) & 0xff) + c1; add[2] = ((ck >> 16) & 0xff) + c2; add[3] = (ck >> 24) + p3;
-	cnt[0] = h.lo.x + add[0]; cnt[1] = h.lo.y + add[1]; cnt[2] = h.lo.z + add[2]; cnt[3] = h.lo.w + add[3];
-}
 
 // bwt_occ4 (bwt.c:169-187): counts in B[0..k] of the $-removed BWT.  Touches exactly one 64-byte block.
 ARX_DEVI void occ4(const IndexView &ix, uint64_t k, uint64_t cnt[4])
@@ -163,6 +148,28 @@ ARX_DEVI void ext_issue(const IndexView &ix, const Biv &ik, int is_back, bool on
 	L.hl = load_head(bl); L.wl = load_quarter(bl, L.nl ? (L.nl - 1) >> 5 : 0);
 }
 ARX_DEVI uint32_t sel4u(const uint32_t v[4], int c) { return c == 0 ? v[0] : c == 1 ? v[1] : c == 2 ? v[2] : v[3]; }
+// a_i by the two bits of i (0..3), as three two-way selects: the compiler makes conditional moves of them, where the chained comparisons of
+// sel4u / head_ck come out as a branch around every alternative (k_seed_bwd_g: some twenty scalar instructions per select)
+template <class T> ARX_DEVI T pick4(T a0, T a1, T a2, T a3, int i) { const T lo = (i & 1) ? a1 : a0, hi = (i & 1) ? a3 : a2; return (i & 2) ? hi : lo; }
+// Counts modulo 2^32 of TWO symbols among the first n (1..128) symbols of the block, added to the cumulative counts: of c (lane-dependent) and
+// of y = 3 (y3) or 0; *add_c = what the block itself adds to c's.  One popcount per symbol, as block_occ1_at counts its one: the word's bit
+// planes flipped by the symbol, ANDed, cut off behind symbol n - 1.  w = the quarter word holding symbol n - 1.  Modulo 2^32 is enough but
+// for ONE count: the sizes of an extension's children are differences of two such counts and lie below 2^32 (an interval never holds more
+// rows than the text has symbols of one kind on both strands), so they are exact in 32 bits; only the new interval's own row wants the
+// 40-bit count (ext_finish).
+ARX_DEVI void block_occ2_lo(const OccHead &h, uint64_t w, int n, int c, bool y3, uint32_t *cnt_c, uint32_t *add_c, uint32_t *cnt_y)
+{
+	const int q = (n - 1) >> 5, nj = n - 32 * q; // nj in 1..32
+	const uint64_t keep = (~0ull << (64 - 2 * nj)) & 0x5555555555555555ull;
+	const uint64_t w1 = w >> 1, fy = y3 ? 0 : ~0ull;
+	const uint32_t rc = (uint32_t)__builtin_popcountll((w ^ ((c & 1) ? 0 : ~0ull)) & (w1 ^ ((c & 2) ? 0 : ~0ull)) & keep);
+	const uint32_t ry = (uint32_t)__builtin_popcountll((w ^ fy) & (w1 ^ fy) & keep);
+	const uint32_t ck = pick4(0u, h.hx.y, h.hx.z, h.hx.w, q);
+	*add_c = ((ck >> (8 * c)) & 0xff) + rc;
+	*cnt_c = pick4(h.lo.x, h.lo.y, h.lo.z, h.lo.w, c) + *add_c;
+	const uint32_t lo_y = y3 ? h.lo.w : h.lo.x, ck_y = y3 ? ck >> 24 : ck & 0xff;
+	*cnt_y = lo_y + ck_y + ry;
+}
 // every symbol occurs fewer than 2^32 times in the text (both strands): then no interval holds 2^32 rows and the sizes of an extension's children
 // are exact as 32-bit differences (GRCh38: 1.8 G at most); a uniform test on the index header, the general form stays for larger texts
 ARX_DEVI bool occ_counts_fit32(const IndexView &ix) { return (((ix.L2[1] - ix.L2[0]) | (ix.L2[2] - ix.L2[1]) | (ix.L2[3] - ix.L2[2]) | (ix.L2[4] - ix.L2[3])) >> 32) == 0; }
@@ -171,19 +178,27 @@ ARX_DEVI Biv ext_finish(const IndexView &ix, const Biv &ik, int is_back, int c, 
 {
 	const uint64_t a = is_back ? ik.k : ik.l, b = is_back ? ik.l : ik.k;
 	uint64_t x = b + (a <= ix.primary && a + ik.s - 1 >= ix.primary);
-	const uint64_t l2c = c == 0 ? ix.L2[0] : c == 1 ? ix.L2[1] : c == 2 ? ix.L2[2] : ix.L2[3];
+	const uint64_t l2c = FIT32 ? pick4(ix.L2[0], ix.L2[1], ix.L2[2], ix.L2[3], c) : c == 0 ? ix.L2[0] : c == 1 ? ix.L2[1] : c == 2 ? ix.L2[2] : ix.L2[3];
 	Biv ok;
 	uint64_t na;
 	if (FIT32) {
-		// counts modulo 2^32 for the four symbols at both ends: the children's sizes are their differences; the 40-bit count is put together
-		// for symbol c at the lower end only
-		uint32_t tk[4] = {0, 0, 0, 0}, tl[4] = {0, 0, 0, 0}, ak[4] = {0, 0, 0, 0}, al[4];
-		if (L.nk) block_occ4_lo(L.hk, L.wk, L.nk, tk, ak);
-		if (L.nl) block_occ4_lo(L.hl, L.wl, L.nl, tl, al);
-		const uint32_t s3 = tl[3] - tk[3], s2 = tl[2] - tk[2], s1 = tl[1] - tk[1];
-		x += (uint64_t)(c < 3 ? s3 : 0u) + (uint64_t)(c < 2 ? s2 : 0u) + (uint64_t)(c < 1 ? s1 : 0u); // (three sizes may pass 2^32 together)
-		na = l2c + 1 + (L.nk ? head_cum(L.hk, c) + sel4u(ak, c) : 0);
-		ok.s = (uint64_t)(uint32_t)(sel4u(tl, c) - sel4u(tk, c));
+		// Counts modulo 2^32 of two symbols at both ends, not of four.  With s_c' the size of child c' (a 32-bit difference, exact) and
+		// cond = (a <= primary && a + ik.s - 1 >= primary), rows a .. a + ik.s - 1 hold ik.s - cond real symbols (ik.s >= 1: the sweeps ask
+		// for no extension of an empty interval), so s_0 + s_1 + s_2 + s_3 = ik.s - cond and the position of child c on the other strand,
+		// b + cond + the sizes of the children above c, is
+		//   c = 3: b + cond            c = 1: b + ik.s - s_0 - s_1
+		//   c = 2: b + cond + s_3      c = 0: b + ik.s - s_0
+		// -- symbol c and one more, y = 0 for c = 1 and y = 3 for c = 2 (counted for c = 0 and 3 as well, and not used).  The 40-bit
+		// count is put together for symbol c at the lower end only.
+		const bool y3 = c >= 2;
+		uint32_t tkc = 0, tlc = 0, tky = 0, tly = 0, akc = 0, alc = 0;
+		if (L.nk) block_occ2_lo(L.hk, L.wk, L.nk, c, y3, &tkc, &akc, &tky);
+		if (L.nl) block_occ2_lo(L.hl, L.wl, L.nl, c, y3, &tlc, &alc, &tly);
+		const uint32_t sc = tlc - tkc, sy = tly - tky;
+		const uint64_t from = y3 ? x : b + ik.s, up = c == 2 ? sy : 0u, down = (uint64_t)(y3 ? 0u : sc) + (c == 1 ? sy : 0u); // (written as selects of values, not of paths)
+		x = from + up - down;
+		na = l2c + 1 + (L.nk ? ((uint64_t)(tkc - akc) | (uint64_t)((L.hk.hx.x >> (8 * c)) & 0xff) << 32) + akc : 0);
+		ok.s = (uint64_t)sc;
 	} else {
 		uint64_t tk[4] = {0, 0, 0, 0}, tl[4] = {0, 0, 0, 0};
 		if (L.nk) block_occ4_w(L.hk, L.wk, L.nk, tk);

@@ -17,6 +17,7 @@
 #include "hip_block.h"
 #include "hip_nw_coop.h"
 #include "hip_fm_coop.h"
+#include "hip_seed_lists.h"
 #include "index_build.h"
 #include "switches.h"
 
@@ -200,6 +201,22 @@ struct HipRT {
 		const long long total = (long long)n_reads * rw;
 		start("k_pack_reads", k_pack_reads, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, bases, base_off, lens, n_reads, rw, q);
 		seed_qn = q;
+	}
+	// the list passes of the seeding stage, one read per 16-lane group (hip_seed_lists.h); f is the functor of the thread-per-read form, which
+	// the group's first lane runs on a read with more than 16 entries and every launch runs under ARX_SEED_LISTS=0 or ARX_SW_SIMPLE
+	static dim3 list_grid(int n_reads) { return dim3((unsigned)(((long long)n_reads * LIST_GL + LIST_BLOCK - 1) / LIST_BLOCK)); }
+	bool seed_lists_ok() const { return sw.seed_lists && !sw.sw_simple; }
+	template <class F> void run_seed_merge(const char *nm, int n, const F &f)
+	{
+		if (n <= 0) return;
+		Scope sc(*this, nm, n);
+		start({"k_seed_merge_g16", nm}, k_seed_merge_g16<F>, list_grid(n), dim3(LIST_BLOCK), 0, f, n);
+	}
+	template <class F> void run_occ_fill(const char *nm, int n, const F &f)
+	{
+		if (n <= 0) return;
+		Scope sc(*this, nm, n);
+		start({"k_occ_fill_g16", nm}, k_occ_fill_g16<F>, list_grid(n), dim3(LIST_BLOCK), 0, f, n);
 	}
 
 	// Kernel timing: a pair of HIP events around each launch on the launch stream, recorded without blocking and

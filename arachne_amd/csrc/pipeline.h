@@ -268,6 +268,11 @@ struct KChain {
 template <class R, class = void> struct HasChainGroup { static constexpr bool value = false; };
 template <class R> struct HasChainGroup<R, decltype((void)std::declval<const R &>().chain_group_ok())> { static constexpr bool value = true; };
 
+// HipRT has the 16-lane group forms of seed_merge and occ_fill (seed_lists_ok / run_seed_merge / run_occ_fill: hip_seed_lists.h); the host test
+// double runs KSeedMerge and KOccFill one read per thread
+template <class R, class = void> struct HasSeedLists { static constexpr bool value = false; };
+template <class R> struct HasSeedLists<R, decltype((void)std::declval<const R &>().seed_lists_ok())> { static constexpr bool value = true; };
+
 // HipRT keeps the opt-in census of the heavy lists (heavy_census_*; arx_batch_debug_heavy_census); the host test double has none
 template <class R, class = void> struct HasHeavyCensus { static constexpr bool value = false; };
 template <class R> struct HasHeavyCensus<R, decltype((void)std::declval<R &>().heavy_census_on)> { static constexpr bool value = true; };
@@ -704,7 +709,10 @@ public:
 		KSeedStrat k3{ix, b.bases, b.base_off, b.lens, strat, n_strat};
 		rt.run_seed_strat("seed_strat", R, k3, w.counter);
 		KSeedMerge km{w.intv, w.n_intv, strat, n_strat, w.n_occ, w.err};
-		rt.launch_wide("seed_merge", R, km);
+		bool lists = false; // the list passes by 16-lane groups (ARX_SEED_LISTS, where the runtime has them)
+		if constexpr (HasSeedLists<RT>::value) lists = rt.seed_lists_ok();
+		if constexpr (HasSeedLists<RT>::value) { if (lists) rt.run_seed_merge("seed_merge", R, km); }
+		if (!lists) rt.launch_wide("seed_merge", R, km);
 		int64_t total = rt.exclusive_scan(w.n_occ, w.occ_off, R); // (waits for the stream: the seeding kernels are through)
 		rt.arena_rewind(seed_mark); // the seeding passes' memory goes back to the arena on both runtimes (the test double poisons and frees it: a later read shows under a sanitizer)
 		if (total >= (int64_t)1 << 30) return -2; // keep 32-bit pool indices; the caller splits the batch
@@ -712,7 +720,8 @@ public:
 		w.occ_seed = rt.template alloc<Seed>(w.T + 1); w.occ_rid = rt.template alloc<int32_t>(w.T + 1);
 		if (w.T) {
 			KOccFill kf{w.intv, w.n_intv, w.occ_off, w.occ_seed};
-			rt.launch_wide("occ_fill", R, kf);
+			if constexpr (HasSeedLists<RT>::value) { if (lists) rt.run_occ_fill("occ_fill", R, kf); }
+			if (!lists) rt.launch_wide("occ_fill", R, kf);
 			KLocate kl{ix, w.occ_seed};
 			rt.run_locate("locate", (int)w.T, kl, w.counter);
 			KOccRid kr{ix, w.occ_seed, w.occ_rid};

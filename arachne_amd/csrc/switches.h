@@ -92,6 +92,9 @@ struct BatchSwitches {
 	int seed_bwd2 = sw_int("ARX_SEED_BWD2", 2);
 	int seed_grant = sw_int("ARX_SEED_GRANT", 4);              // first forward pass: lanes parked for a pool slice that trigger the hand-out (5.36 ms with none, 5.17 at 16, 4.94 at 4, 5.08 at 1)
 	int seed_bwd_batch = sw_int("ARX_SEED_BWD_BATCH", 0);      // 0: seed_batch
+	// 0: the thread-per-read forms of the list passes seed_merge and occ_fill (KSeedMerge, KOccFill) instead of the 16-lane group forms of
+	// hip_seed_lists.h (A/B, and the test that holds the two forms together: tests/test_seed_lists_gpu.py)
+	bool seed_lists = sw_on_unless_zero("ARX_SEED_LISTS");
 	// -- heavy-item kernels (arx_cold.hip)
 	bool rescue_heavy = sw_on_unless_zero("ARX_RESCUE_HEAVY"); // 0: no wavefront replay of the pairs with long lists (A/B)
 	bool chain_heavy = sw_on_unless_zero("ARX_CHAIN_HEAVY");   // 0: no wavefront-per-read chaining of the reads with many occurrences (A/B)
