@@ -168,6 +168,10 @@ _SELFTEST_ARGS = {
     "arx_fastq_standardize": [C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_fastq_standardize": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] +
                                       [C.c_void_p] * 5,
+    # the two fused into one call
+    "arx_fastq_prepare": [C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int32],
+    "arx_selftest_fastq_prepare": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] +
+                                  [C.c_void_p] * 5,
     # the .bai of a coordinate-sorted BAM file
     "arx_bam_index": [C.c_int32, C.c_char_p, C.c_char_p, C.c_int64, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_bam_index": [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
@@ -459,6 +463,64 @@ def selftest_fastq_sort_ext(t1, t2, run_bytes: int, window_bytes: int = 0, slab_
     l1, l2 = (int(out_len[0]), int(out_len[1])) if rc == ARX_OK else (n1, n2)
     return dict(rc=rc, out1=out1[:l1].tobytes(), out2=out2[:l2].tobytes(), rest1=out1[l1:n1].tobytes(), rest2=out2[l2:n2].tobytes(), guard1=out1[n1:].tobytes(),
                 guard2=out2[n2:].tobytes(), rec_off1=off1, rec_off2=off2, n_records=int(n_rec.value), stats={k: int(st[i]) for i, k in enumerate(_FQSORT_EX_STATS)})
+
+
+_FQPREP_STATS = _FQSORT_EX_STATS + ("format", "decided_by", "with_barcode", "valid")
+
+
+def _fqprep_stats(st):
+    d = {k: int(st[i]) for i, k in enumerate(_FQPREP_STATS)}
+    d["format"] = FQSTD_FORMATS[d["format"]]
+    return d
+
+
+def fastq_prepare(r1: str, r2: str, r1_out: "str | None" = None, r2_out: "str | None" = None, format="auto", bgzf: bool = False, check: bool = False, timed: bool = False,
+                  max_bytes: int = 0, run_bytes: int = 0, tmp_dir: "str | None" = None, device: int = 0, lib_path: str = LIB_PATH):
+    """fastq_standardize and fastq_sort_ex in one call on the GPU, without the files between them (include/arachne_amd.h: arx_fastq_prepare): a
+    haplotagging, stLFR or TELLseq pair comes out with the headers `@<id>/1\tBX:Z:<barcode>\tVX:i:<0|1>`, ordered by barcode -- the very bytes
+    the two calls write one after the other.  format as in fastq_standardize; "auto" that finds the standard form sorts the inputs as they
+    are.  bgzf, check, timed, max_bytes, run_bytes and tmp_dir as in fastq_sort_ex (run_bytes counts raw text; the temporary files hold
+    standardized text).  -> the stats of fastq_sort_ex as a dict, with "format" (a name), "decided_by", "with_barcode", "valid";
+    ArachneError with .code on failure -- an unknown format under "auto" among them -- and nothing is left behind then."""
+    lib = _load(lib_path)
+    st, msg = np.zeros(28, dtype=np.int64), C.create_string_buffer(1024)
+    flags = (FQSORT_BGZF if bgzf else 0) | (FQSORT_CHECK if check else 0) | (FQSORT_TIMED if timed else 0)
+    enc = lambda p: None if p is None else os.fsencode(p)
+    rc = _selftest_fn(lib, "arx_fastq_prepare")(device, enc(r1), enc(r2), enc(r1_out), enc(r2_out), _fqstd_format(format), flags, int(max_bytes), int(run_bytes), enc(tmp_dir),
+                                                st.ctypes.data, msg, 1024)
+    if rc != 0:
+        e = ArachneError("arx_fastq_prepare: " + msg.value.decode(errors="replace"))
+        e.code = rc
+        e.stats = _fqprep_stats(st)
+        raise e
+    return _fqprep_stats(st)
+
+
+def selftest_fastq_prepare(t1, t2, format="auto", run_bytes: int = 0, window_bytes: int = 0, slab_bytes: int = 0, cap1: "int | None" = None, cap2: "int | None" = None,
+                           device: int = 0, fill: int = 0xA5, lib_path: str = LIB_PATH):
+    """arx_fastq_prepare's orchestration, detection included, on two texts in memory (include/arachne_amd.h: arx_selftest_fastq_prepare) -> the
+    dict of selftest_fastq_standardize, stats with the names of fastq_prepare.  rc is 0, ARX_E_TOO_LARGE = -4 (a line or record that a window
+    or a run does not hold, too many runs, an output longer than its room) or ARX_E_ARG = -2 where "auto" finds no format; on an error
+    everything is as it was filled: `fill`, -1."""
+    lib = _load(lib_path)
+    s1, s2 = np.frombuffer(bytes(t1), dtype=np.uint8), np.frombuffer(bytes(t2), dtype=np.uint8)
+    n1, n2 = len(s1), len(s2)
+    cap1 = 2 * n1 + 17 * (n1 // 5 + 2) if cap1 is None else int(cap1)
+    cap2 = 2 * n1 + n2 + 17 * (n1 // 5 + 2) if cap2 is None else int(cap2)
+    out1, out2 = np.full(cap1 + 8, fill, dtype=np.uint8), np.full(cap2 + 8, fill, dtype=np.uint8)
+    off1, off2 = np.full(n1 // 5 + 2, -1, dtype=np.int64), np.full(n1 // 5 + 2, -1, dtype=np.int64)
+    n_rec, out_len, st = C.c_int64(-1), np.full(2, -1, dtype=np.int64), np.zeros(28, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_fastq_prepare")(device, s1.ctypes.data if n1 else None, n1, s2.ctypes.data if n2 else None, n2, _fqstd_format(format), int(window_bytes),
+                                                         int(slab_bytes), int(run_bytes), out1.ctypes.data, cap1, out2.ctypes.data, cap2, out_len.ctypes.data, off1.ctypes.data,
+                                                         off2.ctypes.data, C.byref(n_rec), st.ctypes.data)
+    stats = _fqprep_stats(st)
+    if rc not in (ARX_OK, ARX_E_TOO_LARGE) and not (rc == ARX_E_ARG and stats["format"] == "unknown"):
+        e = ArachneError("arx_selftest_fastq_prepare: code %d" % rc)
+        e.code = rc
+        raise e
+    l1, l2 = (int(out_len[0]), int(out_len[1])) if rc == ARX_OK else (0, 0)
+    return dict(rc=rc, out1=out1[:l1].tobytes(), out2=out2[:l2].tobytes(), rest1=out1[l1:cap1].tobytes(), rest2=out2[l2:cap2].tobytes(), guard1=out1[cap1:].tobytes(),
+                guard2=out2[cap2:].tobytes(), rec_off1=off1, rec_off2=off2, n_records=int(n_rec.value), out_len=out_len, stats=stats)
 
 
 BAI_TIMED = 0x100

@@ -3,7 +3,7 @@
 // inflate kernel of hip_inflate.h (arx_selftest_inflate; the device feeder starts it through inflate_launch).  And what needs both: the coordinate
 // sort of a BAM file into an open writer (arx_bam_open_ex, arx_bam_sort_append, arx_selftest_bam_sort: dev_bamsort.h, hip_bamsort.h), and the sort
 // of a FASTQ file pair by barcode (arx_fastq_sort, arx_selftest_fastq_sort: dev_fqsort.h, hip_fqsort.h) with the header standardization in front of it (arx_fastq_standardize,
-// arx_selftest_fastq_standardize: dev_fqstd.h, hip_fqstd.h), and the .bai of a coordinate-sorted
+// arx_selftest_fastq_standardize: dev_fqstd.h, hip_fqstd.h) and the two fused into one call (arx_fastq_prepare, arx_selftest_fastq_prepare: dev_fqprep.h, hip_fqprep.h), and the .bai of a coordinate-sorted
 // BAM file (arx_bam_index, arx_selftest_bam_index: dev_bamindex.h, hip_bamindex.h).
 #include <map>
 #include <memory>
@@ -14,6 +14,7 @@
 #include "hip_bamsort.h"
 #include "hip_fqsort.h"
 #include "hip_fqstd.h"
+#include "hip_fqprep.h"
 #include "hip_bamindex.h"
 
 namespace arx {
@@ -526,6 +527,140 @@ extern "C" int arx_selftest_fastq_standardize(int32_t device, const uint8_t *t1,
 		out_len[0] = c.bytes1; out_len[1] = c.bytes2;
 		*n_records = N;
 		arx::fqs_stats(stats, drv, c, fmt, decided, sink.us_consume, 0, 0);
+	} catch (const arx::FsTooLarge &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::HipOutOfMemory &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}
+
+// ---- the two in one call: raw headers in, standardized records ordered by barcode out (dev_fqprep.h, hip_fqprep.h)
+extern "C" int arx_fastq_prepare(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t format, int32_t flags, int64_t max_bytes,
+                                 int64_t run_bytes, const char *tmp_dir, int64_t *stats, char *msg, int32_t msg_cap)
+{
+	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
+	if (stats) for (int k = 0; k < arx::FP_N_STATS; ++k) stats[k] = 0;
+	if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) { say("arx_fastq_prepare: unknown flag bits"); return ARX_E_ARG; }
+	if (format < ARX_FQSTD_AUTO || format > ARX_FQSTD_TELLSEQ) { say("arx_fastq_prepare: format is ARX_FQSTD_AUTO, _HAPLOTAGGING, _STLFR or _TELLSEQ"); return ARX_E_ARG; }
+	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
+	if (!r1_in || !r2_in || max_bytes < 0 || (!check && (!r1_out || !r2_out))) { say("arx_fastq_prepare: null argument"); return ARX_E_ARG; }
+	if (run_bytes < -1 || (run_bytes > 0 && run_bytes < arx::FS_MIN_WINDOW)) {
+		say("arx_fastq_prepare: run_bytes is -1, 0 or at least the " + std::to_string(arx::FS_MIN_WINDOW) + " bytes of the smallest parse window");
+		return ARX_E_ARG;
+	}
+	const char *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
+	if (!check) {
+		if (fs_same_file(r1_out, r2_out)) { say("arx_fastq_prepare: the two output paths are the same file"); return ARX_E_ARG; }
+		for (int i = 0; i < 2; ++i)
+			for (int o = 0; o < 2; ++o)
+				if (fs_same_file(in[i], out[o])) { say(std::string("arx_fastq_prepare: ") + out[o] + " is an input and an output"); return ARX_E_ARG; }
+	}
+	std::string err;
+	try {
+		const int rc = arx::fp_files(device, in, out, format, flags, max_bytes, run_bytes, tmp_dir, stats, err, arx::shared_device_bgzf);
+		if (rc != ARX_OK) say(err);
+		return rc;
+	} catch (const arx::FsTooLarge &e) {
+		say(e.what());
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::FsIoError &e) {
+		say(e.what());
+		return ARX_E_IO;
+	} catch (const arx::HipOutOfMemory &e) { // the texts, a run's buffers, or the tables of all records (hip_res.h)
+		say("the device memory does not hold these files, a run of them or the table of their records (" + std::to_string(e.wanted >> 20) + " MiB more were asked for, " +
+		    std::to_string(e.free_bytes >> 20) + " MiB are free): prepare in runs (run_bytes -1), or with a smaller run_bytes; where the table of all records is what does not fit, prepare per lane");
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &e) {
+		say(e.what());
+		return ARX_E_DEVICE;
+	}
+}
+
+extern "C" int arx_selftest_fastq_prepare(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int32_t format, int64_t window_bytes, int64_t slab_bytes,
+                                          int64_t run_bytes, uint8_t *out1, int64_t cap1, uint8_t *out2, int64_t cap2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2,
+                                          int64_t *n_records, int64_t *stats)
+{
+	const int64_t window = window_bytes ? window_bytes : run_bytes > 0 && run_bytes < arx::FS_WINDOW_DEFAULT ? run_bytes : arx::FS_WINDOW_DEFAULT; // 0: arx_fastq_prepare's
+	const int64_t slab = slab_bytes ? slab_bytes : arx::FS_SLAB_DEFAULT;
+	if (n1 < 0 || n2 < 0 || cap1 < 0 || cap2 < 0 || !out_len || !rec_off1 || !rec_off2 || !n_records || (n1 > 0 && !t1) || (n2 > 0 && !t2) || (cap1 > 0 && !out1) || (cap2 > 0 && !out2) ||
+	    slab_bytes < 0 || format < ARX_FQSTD_AUTO || format > ARX_FQSTD_TELLSEQ || window < arx::FS_MIN_WINDOW || window > arx::FS_MAX_WINDOW || run_bytes < 0 ||
+	    (run_bytes != 0 && run_bytes < window))
+		return ARX_E_ARG;
+	if (stats) for (int k = 0; k < arx::FP_N_STATS; ++k) stats[k] = 0;
+	try {
+		arx::select_device(device, arx::FP_NO_DEVICE);
+		arx::Stream st;
+		st.create();
+		arx::FpHipDrv drv; drv.st = st;
+		int fmt = format;
+		int64_t decided = -1;
+		arx::FpRows rows;
+		if (format == ARX_FQSTD_AUTO) {
+			arx::FxMemSrc src;
+			src.st = st; src.t[0] = t1; src.t[1] = t2; src.n[0] = n1; src.n[1] = n2;
+			arx::FqsCounts d;
+			const int rc = arx::fqs_detect(drv, src, window, d);
+			ARX_HIP_CHECK(hipStreamSynchronize(drv.st));
+			if (rc != arx::FS_OK) return rc == arx::FS_E_TOO_LARGE ? ARX_E_TOO_LARGE : ARX_E_DEVICE;
+			fmt = d.format; decided = d.decided;
+			if (fmt == ARX_FQSTD_UNKNOWN) {
+				arx::fp_stats(stats, fmt, -1, rows);
+				return ARX_E_ARG;
+			}
+			if (fmt == ARX_FQSTD_STANDARD) { // the sort itself, into room of its own: the caller's is written only when everything is here
+				std::vector<uint8_t> o1((size_t)n1 + 1), o2((size_t)n2 + 1);
+				std::vector<int64_t> off1((size_t)(n1 / 5 + 2)), off2((size_t)(n1 / 5 + 2));
+				int64_t len[2] = {0, 0}, N = 0, s[arx::FX_N_STATS] = {0};
+				const int rc2 = run_bytes == 0 ? arx_selftest_fastq_sort(device, t1, n1, t2, n2, window, slab, o1.data(), o2.data(), len, off1.data(), off2.data(), &N, s)
+				                               : arx_selftest_fastq_sort_ext(device, t1, n1, t2, n2, window, slab, run_bytes, o1.data(), o2.data(), len, off1.data(), off2.data(), &N, s);
+				if (rc2 != ARX_OK) return rc2;
+				if (len[0] > cap1 || len[1] > cap2) return ARX_E_TOO_LARGE;
+				if (len[0]) memcpy(out1, o1.data(), (size_t)len[0]);
+				if (len[1]) memcpy(out2, o2.data(), (size_t)len[1]);
+				memcpy(rec_off1, off1.data(), (size_t)(N + 1) * 8); memcpy(rec_off2, off2.data(), (size_t)(N + 1) * 8);
+				out_len[0] = len[0]; out_len[1] = len[1];
+				*n_records = N;
+				if (stats) memcpy(stats, s, sizeof s);
+				arx::fp_stats(stats, fmt, decided, rows);
+				return ARX_OK;
+			}
+		}
+		rows.format = fmt;
+		arx::FsMemSink sink;
+		sink.init(drv.st);
+		arx::FsCounts c{};
+		arx::FsSortMem m{};
+		arx::FxRuns S;
+		arx::FxIo io;
+		arx::FxMemStore store;
+		arx::DevBuf d1, d2;
+		if (run_bytes == 0) {
+			d1.alloc((size_t)n1); d2.alloc((size_t)n2);
+			if (n1) ARX_HIP_CHECK(hipMemcpyAsync(d1.p, t1, (size_t)n1, hipMemcpyHostToDevice, drv.st));
+			if (n2) ARX_HIP_CHECK(hipMemcpyAsync(d2.p, t2, (size_t)n2, hipMemcpyHostToDevice, drv.st));
+			const arx::FsText T = {d1.as<uint8_t>(), d2.as<uint8_t>(), n1, n2};
+			arx::fp_run(drv, T, window, slab, &sink, c, m, rows);
+		} else {
+			arx::FxMemSrc src;
+			src.st = st; src.t[0] = t1; src.t[1] = t2; src.n[0] = n1; src.n[1] = n2;
+			arx::fx_run_by(drv, src, &store, &sink, run_bytes, window, slab, c, m, S, io, rows);
+		}
+		const int64_t N = c.n_records;
+		std::vector<int64_t> off1((size_t)N + 1, 0), off2((size_t)N + 1, 0);
+		if (N) { drv.fetch(off1.data(), m.out1, (size_t)(N + 1) * 8); drv.fetch(off2.data(), m.out2, (size_t)(N + 1) * 8); }
+		if ((int64_t)sink.text[0].size() != c.bytes1 || (int64_t)sink.text[1].size() != c.bytes2) return ARX_E_DEVICE;
+		if (c.bytes1 > cap1 || c.bytes2 > cap2) return ARX_E_TOO_LARGE;
+		// everything is here: only now is anything of the caller's written
+		if (c.bytes1) memcpy(out1, sink.text[0].data(), (size_t)c.bytes1);
+		if (c.bytes2) memcpy(out2, sink.text[1].data(), (size_t)c.bytes2);
+		memcpy(rec_off1, off1.data(), (size_t)(N + 1) * 8); memcpy(rec_off2, off2.data(), (size_t)(N + 1) * 8);
+		out_len[0] = c.bytes1; out_len[1] = c.bytes2;
+		*n_records = N;
+		arx::fx_stats(stats, drv, c, n1, n2, true, S, io);
+		arx::fp_stats(stats, fmt, decided, rows);
 	} catch (const arx::FsTooLarge &) {
 		return ARX_E_TOO_LARGE;
 	} catch (const arx::HipOutOfMemory &) {

@@ -40,22 +40,23 @@ namespace arx {
 constexpr int64_t FS_MAX_RUNS = 1024; // the runs of one sort: every slab of the merge asks every run for its range
 enum { FS_E_RUN = 3, FS_E_RUNS = 4, FS_E_MERGE = 5 };
 
-struct FxKeyLenF {
-	const FsRec *tab; const uint32_t *vals; int64_t *len;
-	ARX_DEVI void operator()(int64_t j) const { len[j] = tab[vals[j]].bc_len; }
+template <class K> struct FxKeyLenF {
+	K key; const uint32_t *vals; int64_t *len;
+	ARX_DEVI void operator()(int64_t j) const { len[j] = key.len(vals[j]); }
 };
-// place j of a sorted run -> row j of the run's rows in the global table; the barcode byte by byte: it has no length cap and no alignment
-struct FxKeepF {
-	const uint8_t *t1; const FsRec *tab; const uint32_t *vals; const int64_t *out1, *out2, *koff; int64_t file1, file2, key0; FsRec *rows; uint8_t *keys;
+// place j of a sorted run -> row j of the run's rows in the global table; the key byte by byte through its accessor (dev_fqsort.h): it has no
+// length cap and no alignment, and need not lie in one piece
+template <class K> struct FxKeepF {
+	K key; const uint32_t *vals; const int64_t *out1, *out2, *koff; int64_t file1, file2, key0; FsRec *rows; uint8_t *keys;
 	ARX_DEVI void operator()(int64_t j) const
 	{
-		const FsRec &r = tab[vals[j]];
+		const int64_t row = vals[j], n = key.len(row);
 		FsRec o;
-		o.off1 = file1 + out1[j]; o.len1 = r.len1;
-		o.off2 = file2 + out2[j]; o.len2 = r.len2;
-		o.bc_off = key0 + koff[j]; o.bc_len = r.bc_len; o.pad = 0;
+		o.off1 = file1 + out1[j]; o.len1 = (int32_t)key.size1(row);
+		o.off2 = file2 + out2[j]; o.len2 = (int32_t)key.size2(row);
+		o.bc_off = key0 + koff[j]; o.bc_len = (int32_t)n; o.pad = 0;
 		rows[j] = o;
-		for (int32_t k = 0; k < r.bc_len; ++k) keys[o.bc_off + k] = t1[r.bc_off + k];
+		for (int64_t k = 0; k < n; ++k) keys[o.bc_off + k] = key.byte(row, k);
 	}
 };
 struct FxInvF {
@@ -123,9 +124,19 @@ template <class Drv> std::vector<uint8_t> fx_barcode(Drv &drv, const uint8_t *t1
 	if (r.bc_len) drv.fetch(b.data(), t1 + r.bc_off, (size_t)r.bc_len);
 	return b;
 }
+// what a run's records are to the sort: their key accessor, their gather, a key read by the host.  These are arx_fastq_sort's; dev_fqprep.h has
+// the ones of records whose header is composed on the way
+struct FxPlainRows {
+	template <class Drv> FsPlainKey key(Drv &, const FsText &T, const FsRec *tab, int64_t, FsSortMem &) { return FsPlainKey{T.t1, tab}; }
+	template <class Drv, class Sink> void gather(Drv &drv, const FsText &T, const FsPlainKey &key, int64_t n, const FsSortMem &m, int64_t slab, int64_t longest, Sink &sink, FsCounts &c)
+	{
+		fs_gather(drv, T, key.tab, n, m, slab, longest, sink, c);
+	}
+	template <class Drv> std::vector<uint8_t> key_bytes(Drv &drv, const FsPlainKey &key, int64_t row) { return fx_barcode(drv, key.t1, key.tab + row); }
+};
 
 // the runs: parsed, ordered, (io != null) appended to the run files, their keys kept.  FS_OK, or FS_E_*
-template <class Drv, class Src, class Io> int fx_runs(Drv &drv, Src &src, Io *io, int64_t run_bytes, int64_t window, int64_t slab, FxRuns &S)
+template <class Drv, class Src, class Io, class Rows> int fx_runs_by(Drv &drv, Src &src, Io *io, int64_t run_bytes, int64_t window, int64_t slab, FxRuns &S, Rows &rows)
 {
 	uint8_t *buf[2] = {(uint8_t *)drv.run_buf(0, run_bytes), (uint8_t *)drv.run_buf(1, run_bytes)};
 	int64_t have[2] = {0, 0};
@@ -147,21 +158,23 @@ template <class Drv, class Src, class Io> int fx_runs(Drv &drv, Src &src, Io *io
 			const FsRec *tab = drv.table(n);
 			FsSortMem m;
 			fs_sort_mem(drv, n, m);
-			const int64_t longest = fs_order(drv, T, tab, n, m, cr);
-			const std::vector<uint8_t> head = fx_barcode(drv, T.t1, tab);
+			const auto key = rows.key(drv, T, tab, n, m);
+			typedef decltype(rows.key(drv, T, tab, n, m)) K;
+			const int64_t longest = fs_order_by(drv, key, n, m, cr);
+			const std::vector<uint8_t> head = rows.key_bytes(drv, key, 0);
 			S.runs_in += cr.runs_in - (S.n_runs > 0 && head == S.last_bc ? 1 : 0);
-			S.last_bc = fx_barcode(drv, T.t1, tab + (n - 1));
+			S.last_bc = rows.key_bytes(drv, key, n - 1);
 			if (io) {
-				fs_gather(drv, T, tab, n, m, slab, longest, *io, cr);
+				rows.gather(drv, T, key, n, m, slab, longest, *io, cr);
 				io->end_run();
 			}
 			int64_t *koff = (int64_t *)drv.work(FS_W_KOFF, 8 * (n + 1));
-			drv.items("fx_key_len", n, FxKeyLenF{tab, m.vals[m.cur], (int64_t *)m.keys[0]});
+			drv.items("fx_key_len", n, FxKeyLenF<K>{key, m.vals[m.cur], (int64_t *)m.keys[0]});
 			drv.scan((const int64_t *)m.keys[0], koff, n);
 			const int64_t kb = drv.get(&koff[n]);
 			S.rows = (FsRec *)drv.keep(0, (S.N + n) * (int64_t)sizeof(FsRec), S.N * (int64_t)sizeof(FsRec));
 			S.keys = (uint8_t *)drv.keep(1, S.key_bytes + kb, S.key_bytes);
-			drv.items("fx_keep", n, FxKeepF{T.t1, tab, m.vals[m.cur], m.out1, m.out2, koff, S.file1, S.file2, S.key_bytes, S.rows + S.N, S.keys});
+			drv.items("fx_keep", n, FxKeepF<K>{key, m.vals[m.cur], m.out1, m.out2, koff, S.file1, S.file2, S.key_bytes, S.rows + S.N, S.keys});
 			S.N += n; S.key_bytes += kb; S.file1 += cr.bytes1; S.file2 += cr.bytes2;
 			++S.n_runs;
 			S.first.push_back(S.N);
@@ -170,6 +183,11 @@ template <class Drv, class Src, class Io> int fx_runs(Drv &drv, Src &src, Io *io
 		fx_to_front(drv, buf[0], p.a1, have[0] - p.a1); have[0] -= p.a1;
 		fx_to_front(drv, buf[1], p.a2, have[1] - p.a2); have[1] -= p.a2;
 	}
+}
+template <class Drv, class Src, class Io> int fx_runs(Drv &drv, Src &src, Io *io, int64_t run_bytes, int64_t window, int64_t slab, FxRuns &S)
+{
+	FxPlainRows rows;
+	return fx_runs_by(drv, src, io, run_bytes, window, slab, S, rows);
 }
 
 // the global order, the counts of the whole input, and (sink != null) the output, slab by slab as fs_gather makes it

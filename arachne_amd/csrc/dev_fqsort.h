@@ -22,7 +22,9 @@
 // That is the order of the tuple (chunk 0, chunk 1, ..., chunk C - 1, length), chunk c being bytes [8c, 8c + 8) big-endian and zero-padded:
 // a least-significant-digit chain of stable sorts, the length first, then the chunks from the last to the first, each chunk gathered through
 // the permutation so far.  The length pass is what tells AB from AB\0.  C = ceil(longest barcode / 8), by a reduction; a pass sorts only the
-// bits in which its keys differ (the OR over key ^ first key, by a reduction too) and is left out where they do not differ at all.
+// bits in which its keys differ (the OR over key ^ first key, by a reduction too) and is left out where they do not differ at all.  The
+// passes read a key through an accessor (fs_order_by; FsPlainKey: the barcode where it lies in R1's text), so that a key need not be one
+// substring of the input (dev_fqprep.h).
 //
 // Output.  The sorted sizes' prefix sums per file say where every record goes.  The output is made in slabs: a range of sorted records
 // whose bytes fit slab_bytes in both files, at least one record; FS_GATHER_LANES lanes copy one record of one file (bs_copy: the two
@@ -88,52 +90,63 @@ struct FsStoreF {
 	}
 };
 
-// ---- the order
+// ---- the order.  What is ordered is seen through a key accessor K (rows are numbered as the table's):
+//     K.len(row)       the key's length             K.byte(row, k)   its byte k, 0 <= k < len
+//     K.size1(row) / K.size2(row)                   the bytes the row's record takes in the two outputs
+// FsPlainKey is arx_fastq_sort's: the barcode where the parse found it in R1's text, the record's lines verbatim.  dev_fqprep.h has a key in
+// two pieces and records whose header is composed
 ARX_HDI int fs_bits(uint64_t x) { int b = 0; while (b < 64 && (x >> b) != 0) ++b; return b; }
-// chunk c of a barcode: bytes [8c, 8c + 8), the first one on top, zeros behind the barcode's end
-ARX_DEVI uint64_t fs_chunk(const uint8_t *t1, const FsRec &r, int64_t c)
+struct FsPlainKey {
+	const uint8_t *t1; const FsRec *tab;
+	ARX_DEVI int64_t len(int64_t row) const { return tab[row].bc_len; }
+	ARX_DEVI uint8_t byte(int64_t row, int64_t k) const { return t1[tab[row].bc_off + k]; }
+	ARX_DEVI int64_t size1(int64_t row) const { return tab[row].len1; }
+	ARX_DEVI int64_t size2(int64_t row) const { return tab[row].len2; }
+};
+// chunk c of a key: bytes [8c, 8c + 8), the first one on top, zeros behind the key's end
+template <class K> ARX_DEVI uint64_t fs_chunk(const K &key, int64_t row, int64_t c)
 {
 	uint64_t k = 0;
-	const uint8_t *p = t1 + r.bc_off;
-	for (int64_t x = 8 * c; x < 8 * c + 8; ++x) k = k << 8 | (x < r.bc_len ? p[x] : 0u);
+	const int64_t n = key.len(row);
+	for (int64_t x = 8 * c; x < 8 * c + 8; ++x) k = k << 8 | (x < n ? key.byte(row, x) : 0u);
 	return k;
 }
-struct FsLenKeyF { // the least significant key: the length; the permutation starts as the identity
-	const FsRec *tab; uint64_t *keys, *diff; uint32_t *vals;
+template <class K> struct FsLenKeyF { // the least significant key: the length; the permutation starts as the identity
+	K key; uint64_t *keys, *diff; uint32_t *vals;
 	ARX_DEVI void operator()(int64_t j) const
 	{
-		const uint64_t k = (uint64_t)(uint32_t)tab[j].bc_len;
-		keys[j] = k; diff[j] = k ^ (uint64_t)(uint32_t)tab[0].bc_len; vals[j] = (uint32_t)j;
+		const uint64_t k = (uint64_t)(uint32_t)key.len(j);
+		keys[j] = k; diff[j] = k ^ (uint64_t)(uint32_t)key.len(0); vals[j] = (uint32_t)j;
 	}
 };
-struct FsChunkKeyF { // keys[j]: chunk c of the record at place j of the permutation so far; diff[j]: the bits in which it differs from place 0's
-	const uint8_t *t1; const FsRec *tab; const uint32_t *vals; int64_t c; uint64_t *keys, *diff;
+template <class K> struct FsChunkKeyF { // keys[j]: chunk c of the record at place j of the permutation so far; diff[j]: the bits in which it differs from place 0's
+	K key; const uint32_t *vals; int64_t c; uint64_t *keys, *diff;
 	ARX_DEVI void operator()(int64_t j) const
 	{
-		const uint64_t k = fs_chunk(t1, tab[vals[j]], c);
-		keys[j] = k; diff[j] = k ^ fs_chunk(t1, tab[vals[0]], c);
+		const uint64_t k = fs_chunk(key, vals[j], c);
+		keys[j] = k; diff[j] = k ^ fs_chunk(key, vals[0], c);
 	}
 };
-// KRunFlag's rule (dev_fastq.h) on the table: place j opens a run iff its barcode (bytes and length) differs from place j - 1's.  vals: the
+// KRunFlag's rule (dev_fastq.h) on the table: place j opens a run iff its key (bytes and length) differs from place j - 1's.  vals: the
 // order the places are taken in; null: the input's
-struct FsRunF {
-	const uint8_t *t1; const FsRec *tab; const uint32_t *vals; int64_t *flag;
+template <class K> struct FsRunF {
+	K key; const uint32_t *vals; int64_t *flag;
 	ARX_DEVI void operator()(int64_t j) const
 	{
 		bool open = true;
 		if (j > 0) {
-			const FsRec &a = tab[vals ? (int64_t)vals[j] : j], &q = tab[vals ? (int64_t)vals[j - 1] : j - 1];
-			open = q.bc_len != a.bc_len;
-			for (int32_t k = 0; !open && k < a.bc_len; ++k) open = t1[q.bc_off + k] != t1[a.bc_off + k];
+			const int64_t a = vals ? (int64_t)vals[j] : j, q = vals ? (int64_t)vals[j - 1] : j - 1, n = key.len(a);
+			open = key.len(q) != n;
+			for (int64_t k = 0; !open && k < n; ++k) open = key.byte(q, k) != key.byte(a, k);
 		}
 		flag[j] = open;
 	}
 };
 
 // ---- gather
-struct FsSizesF {
-	const FsRec *tab; const uint32_t *vals; int64_t *s1, *s2;
-	ARX_DEVI void operator()(int64_t j) const { const FsRec &r = tab[vals[j]]; s1[j] = r.len1; s2[j] = r.len2; }
+template <class K> struct FsSizesF {
+	K key; const uint32_t *vals; int64_t *s1, *s2;
+	ARX_DEVI void operator()(int64_t j) const { s1[j] = key.size1(vals[j]); s2[j] = key.size2(vals[j]); }
 };
 struct FsGatherF { // item: one lane of one file of one sorted record of the slab that starts at sorted record j0
 	FsText t; const FsRec *tab; const uint32_t *vals; const int64_t *out1, *out2; int64_t j0; uint8_t *d1, *d2;
@@ -235,20 +248,20 @@ template <class Drv> void fs_sort_mem(Drv &drv, int64_t N, FsSortMem &m)
 	m.out1 = (int64_t *)drv.work(FS_W_OUT1, 8 * (N + 1)); m.out2 = (int64_t *)drv.work(FS_W_OUT2, 8 * (N + 1));
 	m.cur = 0;
 }
-template <class Drv> int64_t fs_count_runs(Drv &drv, const uint8_t *t1, const FsRec *tab, const uint32_t *vals, int64_t N, FsSortMem &m)
+template <class Drv, class K> int64_t fs_count_runs(Drv &drv, const K &key, const uint32_t *vals, int64_t N, FsSortMem &m)
 {
-	drv.items("fs_run", N, FsRunF{t1, tab, vals, (int64_t *)m.keys[0]});
+	drv.items("fs_run", N, FsRunF<K>{key, vals, (int64_t *)m.keys[0]});
 	drv.scan((const int64_t *)m.keys[0], m.out1, N);
 	return drv.get(&m.out1[N]);
 }
-// the runs of the input, the order (m.vals[m.cur]), the distinct barcodes, and m.out1 / m.out2[0 .. N]: where the sorted records start in
+// the runs of the input, the order (m.vals[m.cur]), the distinct keys, and m.out1 / m.out2[0 .. N]: where the sorted records start in
 // the two outputs.  -> the longest record of either file
-template <class Drv> int64_t fs_order(Drv &drv, const FsText &T, const FsRec *tab, int64_t N, FsSortMem &m, FsCounts &c)
+template <class Drv, class K> int64_t fs_order_by(Drv &drv, const K &key, int64_t N, FsSortMem &m, FsCounts &c)
 {
 	c.runs_in = c.distinct = c.max_bc = c.passes = c.bytes1 = c.bytes2 = 0;
 	if (N == 0) return 0;
-	c.runs_in = fs_count_runs(drv, T.t1, tab, nullptr, N, m);
-	drv.items("fs_len_key", N, FsLenKeyF{tab, m.keys[0], m.keys[1], m.vals[0]});
+	c.runs_in = fs_count_runs(drv, key, nullptr, N, m);
+	drv.items("fs_len_key", N, FsLenKeyF<K>{key, m.keys[0], m.keys[1], m.vals[0]});
 	c.max_bc = (int64_t)drv.max64(m.keys[0], N);
 	m.cur = 0;
 	if (const uint64_t differ = drv.or64(m.keys[1], N)) {
@@ -256,22 +269,27 @@ template <class Drv> int64_t fs_order(Drv &drv, const FsText &T, const FsRec *ta
 		m.cur = 1; ++c.passes;
 	}
 	for (int64_t ch = (c.max_bc + 7) / 8 - 1; ch >= 0; --ch) {
-		drv.items("fs_chunk_key", N, FsChunkKeyF{T.t1, tab, m.vals[m.cur], ch, m.keys[0], m.keys[1]});
+		drv.items("fs_chunk_key", N, FsChunkKeyF<K>{key, m.vals[m.cur], ch, m.keys[0], m.keys[1]});
 		const uint64_t differ = drv.or64(m.keys[1], N);
 		if (!differ) continue;
 		drv.sort_pairs(m.keys[0], m.keys[1], m.vals[m.cur], m.vals[m.cur ^ 1], N, fs_bits(differ));
 		m.cur ^= 1; ++c.passes;
 	}
-	c.distinct = fs_count_runs(drv, T.t1, tab, m.vals[m.cur], N, m);
-	drv.items("fs_sizes", N, FsSizesF{tab, m.vals[m.cur], (int64_t *)m.keys[0], (int64_t *)m.keys[1]});
+	c.distinct = fs_count_runs(drv, key, m.vals[m.cur], N, m);
+	drv.items("fs_sizes", N, FsSizesF<K>{key, m.vals[m.cur], (int64_t *)m.keys[0], (int64_t *)m.keys[1]});
 	const uint64_t big1 = drv.max64(m.keys[0], N), big2 = drv.max64(m.keys[1], N);
 	drv.scan((const int64_t *)m.keys[0], m.out1, N);
 	drv.scan((const int64_t *)m.keys[1], m.out2, N);
 	c.bytes1 = drv.get(&m.out1[N]); c.bytes2 = drv.get(&m.out2[N]);
 	return (int64_t)(big1 > big2 ? big1 : big2);
 }
-// the sorted records to the sink, slab by slab
-template <class Drv, class Sink> void fs_gather(Drv &drv, const FsText &T, const FsRec *tab, int64_t N, const FsSortMem &m, int64_t slab_bytes, int64_t longest, Sink &sink, FsCounts &c)
+template <class Drv> int64_t fs_order(Drv &drv, const FsText &T, const FsRec *tab, int64_t N, FsSortMem &m, FsCounts &c)
+{
+	return fs_order_by(drv, FsPlainKey{T.t1, tab}, N, m, c);
+}
+// the sorted records to the sink, slab by slab; make(j0, d1, d2): the functor that writes the slab that starts at sorted record j0, started
+// under `name` with FS_GATHER_LANES items per record and file
+template <class Drv, class Sink, class Make> void fs_gather_by(Drv &drv, int64_t N, const FsSortMem &m, int64_t slab_bytes, int64_t longest, Sink &sink, FsCounts &c, const char *name, Make make)
 {
 	const int64_t cap = slab_bytes > longest ? slab_bytes : longest;
 	c.slabs = 0;
@@ -286,11 +304,16 @@ template <class Drv, class Sink> void fs_gather(Drv &drv, const FsText &T, const
 		e1 = drv.get(&m.out1[lo]); e2 = drv.get(&m.out2[lo]);
 		uint8_t *d1 = nullptr, *d2 = nullptr;
 		sink.take(c.slabs, cap, e1 - at1, e2 - at2, &d1, &d2);
-		drv.items("fs_gather", (lo - j0) * 2 * FS_GATHER_LANES, FsGatherF{T, tab, m.vals[m.cur], m.out1, m.out2, j0, d1, d2});
+		drv.items(name, (lo - j0) * 2 * FS_GATHER_LANES, make(j0, d1, d2));
 		sink.give(c.slabs, j0, lo, e1 - at1, e2 - at2);
 		++c.slabs;
 		j0 = lo; at1 = e1; at2 = e2;
 	}
+}
+template <class Drv, class Sink> void fs_gather(Drv &drv, const FsText &T, const FsRec *tab, int64_t N, const FsSortMem &m, int64_t slab_bytes, int64_t longest, Sink &sink, FsCounts &c)
+{
+	fs_gather_by(drv, N, m, slab_bytes, longest, sink, c, "fs_gather",
+	             [&](int64_t j0, uint8_t *d1, uint8_t *d2) { return FsGatherF{T, tab, m.vals[m.cur], m.out1, m.out2, j0, d1, d2}; });
 }
 
 } // namespace arx

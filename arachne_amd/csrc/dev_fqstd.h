@@ -117,39 +117,45 @@ struct FqsMatchF {
 // what FqsFieldsF leaves per record: positions in the windows of id and barcode (window 1) and of lines 2-4 (their own window)
 struct FqsRec { int32_t id_pos, id_len, bc_pos, bc_len, body1, blen1, body2, blen2, v, pad; };
 
+// id, barcode and v of H = t[b, E) for `format` (1 .. 3) into o.id_pos .. o.bc_len and o.v, positions counted from t -> the header has a barcode
+ARX_DEVI bool fqs_fields(const uint8_t *t, int32_t b, int32_t E, int32_t format, FqsRec &o)
+{
+	// the id: the first token, one trailing /1 or /2 removed
+	int32_t p = b;
+	while (p < E && fq_is_space(t[p])) ++p;
+	o.id_pos = p;
+	while (p < E && !fq_is_space(t[p])) ++p;
+	o.id_len = p - o.id_pos;
+	if (o.id_len >= 2 && t[p - 2] == '/' && (t[p - 1] == '1' || t[p - 1] == '2')) o.id_len -= 2;
+	// the barcode: the leftmost match of the format's pattern
+	bool have = false;
+	o.bc_pos = b; o.bc_len = 0;
+	for (p = b; p < E && !have; ++p)
+		have = format == FQS_HAPLOTAGGING ? fqs_bx_at(t, p, E, &o.bc_pos, &o.bc_len) : format == FQS_STLFR ? fqs_stlfr_at(t, p, E, &o.bc_pos, &o.bc_len)
+		                                                                                                      : fqs_tell_at(t, p, E, &o.bc_pos, &o.bc_len);
+	const uint8_t *c = t + o.bc_pos;
+	const int32_t n = o.bc_len;
+	bool ok = have;
+	if (format == FQS_HAPLOTAGGING) { // no two adjacent '0'
+		for (int32_t k = 0; k + 1 < n; ++k) ok = ok && !(c[k] == '0' && c[k + 1] == '0');
+	} else if (format == FQS_STLFR) { // not ^0_ | _0_ | _0$
+		ok = ok && !(c[0] == '0' && c[1] == '_') && !(c[n - 2] == '_' && c[n - 1] == '0');
+		for (int32_t k = 0; k + 2 < n; ++k) ok = ok && !(c[k] == '_' && c[k + 1] == '0' && c[k + 2] == '_');
+	} else { // no N
+		for (int32_t k = 0; k < n; ++k) ok = ok && c[k] != 'N';
+	}
+	o.v = ok; o.pad = 0;
+	return have;
+}
+
 struct FqsFieldsF { // item: one record of a window, for the format of the call
 	FqLines ln; const int32_t *rec_line; int32_t format; FqsRec *fld; int64_t *s1, *s2; int64_t *cnt; uint64_t *bcl;
 	ARX_DEVI void operator()(int64_t r) const
 	{
 		const int j = rec_line[r];
-		const uint8_t *t = ln.t1;
 		const int32_t b = ln.start1(j) + 1, E = ln.nl1[j] + 1;
 		FqsRec o;
-		// the id: the first token, one trailing /1 or /2 removed
-		int32_t p = b;
-		while (p < E && fq_is_space(t[p])) ++p;
-		o.id_pos = p;
-		while (p < E && !fq_is_space(t[p])) ++p;
-		o.id_len = p - o.id_pos;
-		if (o.id_len >= 2 && t[p - 2] == '/' && (t[p - 1] == '1' || t[p - 1] == '2')) o.id_len -= 2;
-		// the barcode: the leftmost match of the format's pattern
-		bool have = false;
-		o.bc_pos = b; o.bc_len = 0;
-		for (p = b; p < E && !have; ++p)
-			have = format == FQS_HAPLOTAGGING ? fqs_bx_at(t, p, E, &o.bc_pos, &o.bc_len) : format == FQS_STLFR ? fqs_stlfr_at(t, p, E, &o.bc_pos, &o.bc_len)
-			                                                                                                      : fqs_tell_at(t, p, E, &o.bc_pos, &o.bc_len);
-		const uint8_t *c = t + o.bc_pos;
-		const int32_t n = o.bc_len;
-		bool ok = have;
-		if (format == FQS_HAPLOTAGGING) { // no two adjacent '0'
-			for (int32_t k = 0; k + 1 < n; ++k) ok = ok && !(c[k] == '0' && c[k + 1] == '0');
-		} else if (format == FQS_STLFR) { // not ^0_ | _0_ | _0$
-			ok = ok && !(c[0] == '0' && c[1] == '_') && !(c[n - 2] == '_' && c[n - 1] == '0');
-			for (int32_t k = 0; k + 2 < n; ++k) ok = ok && !(c[k] == '_' && c[k + 1] == '0' && c[k + 2] == '_');
-		} else { // no N
-			for (int32_t k = 0; k < n; ++k) ok = ok && c[k] != 'N';
-		}
-		o.v = ok; o.pad = 0;
+		const bool have = fqs_fields(ln.t1, b, E, format, o), ok = o.v != 0;
 		o.body1 = ln.start1(j + 1); o.blen1 = ln.nl1[j + 3] + 1 - o.body1;
 		o.body2 = ln.start2(j + 1); o.blen2 = ln.nl2[j + 3] + 1 - o.body2;
 		fld[r] = o;

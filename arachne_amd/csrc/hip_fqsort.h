@@ -84,7 +84,7 @@ struct FsHipDrv {
 	{
 		if (!strncmp(nm, "fq_", 3) || !strcmp(nm, "fs_window") || !strcmp(nm, "fs_store") || !strcmp(nm, "fs_scan32")) return FS_T_PARSE;
 		if (!strcmp(nm, "fs_sort")) return FS_T_SORT;
-		if (!strcmp(nm, "fs_gather") || !strcmp(nm, "fs_sizes") || !strcmp(nm, "fx_gather") || !strcmp(nm, "fqs_compose")) return FS_T_GATHER;
+		if (!strcmp(nm, "fs_gather") || !strcmp(nm, "fs_sizes") || !strcmp(nm, "fx_gather") || !strcmp(nm, "fqs_compose") || !strcmp(nm, "fp_gather")) return FS_T_GATHER;
 		return FS_T_KEYS; // length and chunk keys, runs, their scans and reductions
 	}
 	template <class Fn> void booked(const char *nm, Fn fn)
@@ -555,24 +555,26 @@ enum { FX_RUNS = 20, FX_TMP_BYTES, FX_T_RUN_WRITE, FX_T_RUN_READ };
 constexpr int64_t FX_AUTO_RESERVE = (int64_t)1 << 30, FX_AUTO_SHARE = 8, FX_AUTO_MOST = (int64_t)16 << 30;
 
 // run_bytes == -1: an eighth of the free device memory less 1 GiB, in whole MiB, 16 GiB at most (include/arachne_amd.h has the accounting)
-inline int64_t fx_auto_run_bytes(int64_t least)
+inline int64_t fx_auto_run_bytes(int64_t least, int64_t share = FX_AUTO_SHARE)
 {
 	size_t fr = 0, total = 0;
 	ARX_HIP_CHECK(hipMemGetInfo(&fr, &total));
-	int64_t rb = ((int64_t)fr - FX_AUTO_RESERVE) / FX_AUTO_SHARE;
+	int64_t rb = ((int64_t)fr - FX_AUTO_RESERVE) / share;
 	rb &= ~(((int64_t)1 << 20) - 1);
 	if (rb > FX_AUTO_MOST) rb = FX_AUTO_MOST;
 	return rb < least ? least : rb;
 }
 
-// runs, merge and (sink != null) output of what src delivers; store == null: CHECK, only the keys are kept
-template <class Src> void fx_run(FxHipDrv &drv, Src &src, FxRunStore *store, FsSink *sink, int64_t run_bytes, int64_t window, int64_t slab, FsCounts &c, FsSortMem &m, FxRuns &S, FxIo &io)
+// runs, merge and (sink != null) output of what src delivers; store == null: CHECK, only the keys are kept.  rows: what a run's records are
+// to the sort (dev_fqmerge.h: FxPlainRows; dev_fqprep.h: FpRows)
+template <class Src, class Rows> void fx_run_by(FxHipDrv &drv, Src &src, FxRunStore *store, FsSink *sink, int64_t run_bytes, int64_t window, int64_t slab, FsCounts &c, FsSortMem &m, FxRuns &S, FxIo &io,
+                                                Rows &rows)
 {
 	double t0 = bs_now_us();
 	io.store = store;
 	if (store) io.init(drv.st);
 	const double fed0 = drv.us[FS_T_READ] + drv.us[FS_T_INFLATE];
-	const int rc = fx_runs(drv, src, store ? &io : nullptr, run_bytes, window, slab, S);
+	const int rc = fx_runs_by(drv, src, store ? &io : nullptr, run_bytes, window, slab, S, rows);
 	if (rc == FS_E_RECORDS) throw FsTooLarge(std::string("more than 2^32 - 1 records") + FS_REMEDY);
 	if (rc == FS_E_TOO_LARGE) throw FsTooLarge("a line or a record is longer than the " + std::to_string(window) + " bytes of a parse window");
 	if (rc == FS_E_RUN) throw FsTooLarge("a line or a record does not fit a run of " + std::to_string(run_bytes) + " bytes per file: use a larger run_bytes");
@@ -586,6 +588,11 @@ template <class Src> void fx_run(FxHipDrv &drv, Src &src, FxRunStore *store, FsS
 	if (sink) sink->flush();
 	ARX_HIP_CHECK(hipStreamSynchronize(drv.st));
 	if (!drv.timed) drv.us[FS_T_GATHER] = bs_now_us() - t0 - io.us_read - (sink ? sink->us_consume : 0);
+}
+template <class Src> void fx_run(FxHipDrv &drv, Src &src, FxRunStore *store, FsSink *sink, int64_t run_bytes, int64_t window, int64_t slab, FsCounts &c, FsSortMem &m, FxRuns &S, FxIo &io)
+{
+	FxPlainRows rows;
+	fx_run_by(drv, src, store, sink, run_bytes, window, slab, c, m, S, io, rows);
 }
 inline void fx_stats(int64_t *stats, const FxHipDrv &drv, const FsCounts &c, int64_t n1, int64_t n2, bool written, const FxRuns &S, const FxIo &io)
 {

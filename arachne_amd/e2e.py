@@ -299,6 +299,33 @@ def presort(r1: str, r2: str, out_dir: str, device: int = 0, bgzf: bool = False,
     return o1, o2, dict(st, sorted=True)
 
 
+def prepare(r1: str, r2: str, out_dir: str, format="auto", bgzf: bool = False, device: int = 0, run_bytes: int = 0, tmp_dir: "str | None" = None, if_needed: bool = True,
+            lib_path: str = api.LIB_PATH):
+    """standardize() and presort() as one GPU call (api.fastq_prepare), without the files between them: the pair comes out with the headers the
+    feeder reads, ordered by barcode.  With if_needed the input is counted first (check=True) and returned as it is when its format is the
+    standard one and every key is one run already; a pair in another format is always written, its headers have to change.  The files go to
+    out_dir under the inputs' base names (+ ".prepared.fastq", ".gz" with bgzf).  run_bytes and tmp_dir as in presort().
+    -> (r1_out, r2_out, stats); stats["prepared"] says whether files were written."""
+    if if_needed:
+        st = api.fastq_prepare(r1, r2, format=format, check=True, run_bytes=run_bytes, device=device, lib_path=lib_path)
+        if st["format"] == "standard" and st["runs"] == st["distinct"]:
+            return r1, r2, dict(st, prepared=False)
+        format = st["format"]               # detected once
+    os.makedirs(out_dir, exist_ok=True)
+
+    def name(p):
+        b = os.path.basename(p)
+        for ext in (".gz", ".bgz", ".fastq", ".fq"):
+            if b.endswith(ext):
+                b = b[:-len(ext)]
+        return os.path.join(out_dir, b + ".prepared.fastq" + (".gz" if bgzf else ""))
+    o1, o2 = name(r1), name(r2)
+    if o1 == o2:
+        o2 = o2.replace(".prepared.", ".prepared.2.")
+    st = api.fastq_prepare(r1, r2, o1, o2, format="auto" if format == "standard" else format, bgzf=bgzf, run_bytes=run_bytes, tmp_dir=tmp_dir, device=device, lib_path=lib_path)
+    return o1, o2, dict(st, prepared=True)
+
+
 def _nothing():
     pass
 

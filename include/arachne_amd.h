@@ -514,7 +514,8 @@ int arx_selftest_fastq_sort_ext(int32_t device, const uint8_t *t1, int64_t n1, c
  * [6] the format used or found, [7] the record that decided the detection (-1: forced, or none), [8] records with a barcode, [9] records
  * written with VX:i:1, [10] longest barcode, [11] parse windows, [12] output slabs, then microseconds: [13] waiting for the readers,
  * [14] upload and inflate, [15] parse, [16] fields and sizes (TIMED only, otherwise under [17]), [17] compose, [18] compress and write of BGZF
- * blocks, [19] fetch and write of plain text, last blocks, rename.  Not built: the step fused into the sort; other header formats. */
+ * blocks, [19] fetch and write of plain text, last blocks, rename.  arx_fastq_prepare below is this step fused into the sort: one call, no
+ * files between the two.  Not built: other header formats. */
 enum { ARX_FQSTD_AUTO = 0, ARX_FQSTD_HAPLOTAGGING = 1, ARX_FQSTD_STLFR = 2, ARX_FQSTD_TELLSEQ = 3, ARX_FQSTD_STANDARD = 4, ARX_FQSTD_UNKNOWN = 5 }; /* 4, 5: results only */
 enum { ARX_FQSTD_BGZF = 1, ARX_FQSTD_DETECT = 2, ARX_FQSTD_TIMED = 0x100 };
 int arx_fastq_standardize(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t format, int32_t flags, int64_t *stats,
@@ -529,6 +530,51 @@ int arx_fastq_standardize(int32_t device, const char *r1_in, const char *r2_in, 
 int arx_selftest_fastq_standardize(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int32_t format, int64_t window_bytes, int64_t slab_bytes,
                                    uint8_t *out1, int64_t cap1, uint8_t *out2, int64_t cap2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2, int64_t *n_records,
                                    int64_t *stats);
+
+/* ---- the two steps in front of the feeder as one: a haplotagging, stLFR or TELLseq FASTQ pair standardized AND sorted by barcode on the GPU,
+ * without the files that arx_fastq_standardize writes and arx_fastq_sort_ex reads back (the reference means them as one preparation too:
+ * main.go:85, preprocess.go and standardize.go).  The rule: for every input and every run_bytes the two outputs inflate to exactly the
+ * bytes that arx_fastq_sort_ex writes for the files that arx_fastq_standardize(format) writes for the input.  So
+ *   record, id, barcode, v   arx_fastq_standardize's, word for word; skipped lines and the cut-off record are dropped
+ *   output      per record '@' id "/1\tBX:Z:" barcode "\tVX:i:" v '\n' ("/2" in R2) and lines 2-4 verbatim, ordered by the sort key as
+ *               unsigned bytes, a proper prefix first, equal keys in input order; it does not depend on run_bytes, on window or slab sizes
+ *               or on how the readers cut the input
+ *   sort key    what the feeder's rule reads from the composed R1 header, the value of its leftmost BX:Z:(\S+)\s.  Normally that is the
+ *               barcode.  Where the id itself contains BX:Z: it is the id's bytes behind its leftmost BX:Z: followed by "/1" (the id is the
+ *               one above, a trailing /1 or /2 removed; BX:Z: cannot straddle the id and "/1"; "/1" makes the value non-empty and the
+ *               '\t' closes it) -- a key in two pieces, the second not in the input: `xBX:Z:ab ...`, `y BX:Z:ab/1` and `zBX:Z:ab/1` all
+ *               sort under ab/1, in input order.  No BX:Z: in the id and an empty barcode: the empty key
+ *   detection   arx_fastq_standardize's, a pass of its own over the head of the input.  AUTO that finds standard: the call is exactly
+ *               arx_fastq_sort_ex on the inputs -- the sorted files are written, this is a sort and no no-op; stats[26] and [27] are 0
+ *               then.  AUTO that finds unknown: ARX_E_ARG, nothing is written, stats[24] = 5.  A forced format on zero records gives two
+ *               empty outputs
+ * flags are arx_fastq_sort_ex's: ARX_FQSORT_BGZF, ARX_FQSORT_TIMED, and ARX_FQSORT_CHECK -- nothing is written, the output paths may be
+ * NULL, no temporary file is made, only stats is filled, and stats[6] == stats[7] says that the standardized input would need no sort.
+ * max_bytes, run_bytes and tmp_dir are arx_fastq_sort_ex's too, with two differences: the run buffers hold RAW text while the temporary
+ * files hold standardized text (the disk needed is the output's size), and run_bytes == -1 is a TENTH of the free device memory less 1 GiB
+ * (whole MiB, at least 32 MiB, at most 16 GiB), because a record takes 120 bytes here where the sort has 80 (csrc/dev_fqprep.h: 40 more for
+ * id, barcode, key and header ends): a run is 2 run_bytes + 2.4 run_bytes at 100 bytes of text per record and file, and a tenth keeps
+ * the runs a little under half of the free memory as the sort's eighth does.  Nobody has measured which run size is fastest.  With
+ * run_bytes == 0 both raw texts and 120 bytes per record stay in device memory.
+ * Refusals are the union of the two calls'.  ARX_E_ARG: null paths without CHECK, unknown flag bits, a format outside 0..3, an output that
+ * is an input or equals the other output, run_bytes below 128 other than 0 and -1.  ARX_E_IO: a file cannot be read or written, a BGZF block
+ * does not inflate, tmp_dir is unusable.  ARX_E_TOO_LARGE: more than max_bytes; a line or record that a window or a run does not hold; more
+ * than 1024 runs; more than 2^32 - 1 records; more than the device memory -- msg names the remedy.  ARX_E_DEVICE: no GPU, or a HIP error;
+ * there is no CPU fallback.  After any error no output, .tmp or temporary run file is left, and the inputs are untouched.
+ * stats[28] (may be NULL): [0..23] as arx_fastq_sort_ex's -- [1] [2] the inflated bytes read from the raw inputs, [3] [4] the bytes written
+ * as inflated text, [5] lines skipped, [6] [7] [8] runs, distinct keys and the longest key, all by the sort key above --, [24] the format
+ * used or found, [25] the record that decided the detection (-1: forced, or none), [26] records with a barcode, [27] records written with
+ * VX:i:1. */
+int arx_fastq_prepare(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t format, int32_t flags, int64_t max_bytes,
+                      int64_t run_bytes, const char *tmp_dir, int64_t *stats, char *msg, int32_t msg_cap);
+/* self-test of the same orchestration, detection pass included, on two texts in host memory, the sorted runs held in host memory too
+ * (tests/test_fastq_prepare_gpu.py).  window_bytes and slab_bytes as in arx_selftest_fastq_sort; run_bytes 0 or at least 128 and at least
+ * window_bytes (ARX_E_ARG otherwise; window_bytes 0: min(run_bytes, 32 MiB)).  out1[cap1], out2[cap2], out_len, rec_off1, rec_off2 and
+ * n_records as in arx_selftest_fastq_standardize, the caps included; stats[28] as above.  AUTO that finds unknown is ARX_E_ARG with
+ * stats[24] = 5.  On any error every output argument is untouched. */
+int arx_selftest_fastq_prepare(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int32_t format, int64_t window_bytes, int64_t slab_bytes,
+                               int64_t run_bytes, uint8_t *out1, int64_t cap1, uint8_t *out2, int64_t cap2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2,
+                               int64_t *n_records, int64_t *stats);
 
 /* ---- between the path and the sink: the placed candidate of every read of a super-batch as BAM records -- the part of DumpToBams /
  * AppendBam (src/aligner/bamwriter.go:283-568, 635-658) that decides flags, position, MAPQ, mate fields, template length, CIGAR op codes,
