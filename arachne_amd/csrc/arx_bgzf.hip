@@ -266,48 +266,104 @@ extern "C" int arx_selftest_bam_sort(int32_t device, const uint8_t *stream, int6
 	return ARX_OK;
 }
 
-// ---- the sort of a FASTQ file pair by barcode (dev_fqsort.h, hip_fqsort.h)
-static bool fs_same_file(const char *a, const char *b)
-{
-	if (!strcmp(a, b)) return true;
-	struct stat sa, sb;
-	return stat(a, &sa) == 0 && stat(b, &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
-}
-
-extern "C" int arx_fastq_sort(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t flags, int64_t max_bytes, int64_t *stats,
-                              char *msg, int32_t msg_cap)
+// ---- the FASTQ file-pair calls (hip_fqsort.h, hip_fqstd.h, hip_fqprep.h): what their entries share at this edge
+// a file entry's body under the family's refusals: what it throws becomes the code and the text in msg.  oom_what, oom_remedy: the call's own
+// words around the figures of a device memory that does not suffice
+template <class Body> static int fq_file_call(char *msg, int32_t msg_cap, const char *oom_what, const char *oom_remedy, Body body)
 {
 	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
-	if (stats) for (int k = 0; k < arx::FS_N_STATS; ++k) stats[k] = 0;
-	if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) { say("arx_fastq_sort: unknown flag bits"); return ARX_E_ARG; }
-	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
-	if (!r1_in || !r2_in || max_bytes < 0 || (!check && (!r1_out || !r2_out))) { say("arx_fastq_sort: null argument"); return ARX_E_ARG; }
-	const char *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
-	if (!check) {
-		if (fs_same_file(r1_out, r2_out)) { say("arx_fastq_sort: the two output paths are the same file"); return ARX_E_ARG; }
-		for (int i = 0; i < 2; ++i)
-			for (int o = 0; o < 2; ++o)
-				if (fs_same_file(in[i], out[o])) { say(std::string("arx_fastq_sort: ") + out[o] + " is an input and an output"); return ARX_E_ARG; }
-	}
-	std::string err;
 	try {
-		const int rc = arx::fs_sort_files(device, in, out, flags, max_bytes, stats, err, arx::shared_device_bgzf);
-		if (rc != ARX_OK) say(err);
-		return rc;
+		body();
+		return ARX_OK;
+	} catch (const arx::FsBadArg &e) {
+		say(e.what());
+		return ARX_E_ARG;
 	} catch (const arx::FsTooLarge &e) {
 		say(e.what());
 		return ARX_E_TOO_LARGE;
 	} catch (const arx::FsIoError &e) {
 		say(e.what());
 		return ARX_E_IO;
-	} catch (const arx::HipOutOfMemory &e) { // any buffer of the sort (hip_res.h)
-		say("the device memory does not hold the sort of these files (" + std::to_string(e.wanted >> 20) + " MiB more were asked for, " + std::to_string(e.free_bytes >> 20) + " MiB are free)" +
-		    arx::FS_REMEDY);
+	} catch (const arx::HipOutOfMemory &e) { // any buffer of the call (hip_res.h)
+		say(std::string(oom_what) + " (" + std::to_string(e.wanted >> 20) + " MiB more were asked for, " + std::to_string(e.free_bytes >> 20) + " MiB are free)" + oom_remedy);
 		return ARX_E_TOO_LARGE;
 	} catch (const std::exception &e) {
 		say(e.what());
 		return ARX_E_DEVICE;
 	}
+}
+// a self-test's body: the codes alone
+template <class Body> static int fq_selftest_call(Body body)
+{
+	try {
+		return body();
+	} catch (const arx::FsTooLarge &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::HipOutOfMemory &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+}
+[[noreturn]] static void fq_bad(const char *call, const std::string &what) { throw arx::FsBadArg(std::string(call) + ": " + what); }
+
+static bool fs_same_file(const char *a, const char *b)
+{
+	if (!strcmp(a, b)) return true;
+	struct stat sa, sb;
+	return stat(a, &sa) == 0 && stat(b, &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
+}
+// the four paths of a call; need_out: the call writes (no CHECK, no DETECT), so the outputs are two files that are no inputs
+static void fq_check_paths(const char *call, const char *const in[2], const char *const out[2], bool need_out, bool rest_ok = true)
+{
+	if (!in[0] || !in[1] || !rest_ok || (need_out && (!out[0] || !out[1]))) fq_bad(call, "null argument");
+	if (!need_out) return;
+	if (fs_same_file(out[0], out[1])) fq_bad(call, "the two output paths are the same file");
+	for (int i = 0; i < 2; ++i)
+		for (int o = 0; o < 2; ++o)
+			if (fs_same_file(in[i], out[o])) fq_bad(call, std::string(out[o]) + " is an input and an output");
+}
+static void fq_check_run_bytes(const char *call, int64_t run_bytes)
+{
+	if (run_bytes < -1 || (run_bytes > 0 && run_bytes < arx::FS_MIN_WINDOW))
+		fq_bad(call, "run_bytes is -1, 0 or at least the " + std::to_string(arx::FS_MIN_WINDOW) + " bytes of the smallest parse window");
+}
+static void fq_check_format(const char *call, int32_t format)
+{
+	if (format < ARX_FQSTD_AUTO || format > ARX_FQSTD_TELLSEQ) fq_bad(call, "format is ARX_FQSTD_AUTO, _HAPLOTAGGING, _STLFR or _TELLSEQ");
+}
+// a self-test's texts and record offsets to the caller's room of cap[f] bytes; a text that is longer is refused with `over`.  Everything is here:
+// only now is anything of the caller's written
+static int fq_hand_out(const std::vector<uint8_t> text[2], const std::vector<int64_t> off[2], int64_t bytes1, int64_t bytes2, int64_t N, int64_t cap1, int64_t cap2, int over,
+                       uint8_t *out1, uint8_t *out2, int64_t *out_len, int64_t *rec_off1, int64_t *rec_off2, int64_t *n_records)
+{
+	if ((int64_t)text[0].size() != bytes1 || (int64_t)text[1].size() != bytes2 || (int64_t)off[0].size() != N + 1 || (int64_t)off[1].size() != N + 1) return ARX_E_DEVICE;
+	if (bytes1 > cap1 || bytes2 > cap2) return over;
+	if (bytes1) memcpy(out1, text[0].data(), (size_t)bytes1);
+	if (bytes2) memcpy(out2, text[1].data(), (size_t)bytes2);
+	memcpy(rec_off1, off[0].data(), (size_t)(N + 1) * 8); memcpy(rec_off2, off[1].data(), (size_t)(N + 1) * 8);
+	out_len[0] = bytes1; out_len[1] = bytes2;
+	*n_records = N;
+	return ARX_OK;
+}
+// the output offsets of a sort's N records
+static void fs_fetch_offsets(arx::FsHipDrv &drv, const arx::FsSortMem &m, int64_t N, std::vector<int64_t> off[2])
+{
+	for (int f = 0; f < 2; ++f) off[f].assign((size_t)N + 1, 0);
+	if (N) { drv.fetch(off[0].data(), m.out1, (size_t)(N + 1) * 8); drv.fetch(off[1].data(), m.out2, (size_t)(N + 1) * 8); }
+}
+
+// ---- the sort of a FASTQ file pair by barcode (dev_fqsort.h, hip_fqsort.h)
+extern "C" int arx_fastq_sort(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t flags, int64_t max_bytes, int64_t *stats,
+                              char *msg, int32_t msg_cap)
+{
+	if (stats) for (int k = 0; k < arx::FS_N_STATS; ++k) stats[k] = 0;
+	return fq_file_call(msg, msg_cap, "the device memory does not hold the sort of these files", arx::FS_REMEDY, [&]() {
+		const char *call = "arx_fastq_sort", *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
+		if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) fq_bad(call, "unknown flag bits");
+		fq_check_paths(call, in, out, !(flags & ARX_FQSORT_CHECK), max_bytes >= 0);
+		arx::fs_sort_files(device, in, out, flags, max_bytes, stats, arx::shared_device_bgzf);
+	});
 }
 
 extern "C" int arx_selftest_fastq_sort(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int64_t window_bytes, int64_t slab_bytes, uint8_t *out1,
@@ -317,7 +373,7 @@ extern "C" int arx_selftest_fastq_sort(int32_t device, const uint8_t *t1, int64_
 	    (window_bytes != 0 && (window_bytes < arx::FS_MIN_WINDOW || window_bytes > arx::FS_MAX_WINDOW)))
 		return ARX_E_ARG;
 	if (stats) for (int k = 0; k < arx::FS_N_STATS; ++k) stats[k] = 0;
-	try {
+	return fq_selftest_call([&]() -> int {
 		arx::select_device(device, arx::FS_NO_DEVICE);
 		arx::Stream st;
 		st.create();
@@ -331,67 +387,28 @@ extern "C" int arx_selftest_fastq_sort(int32_t device, const uint8_t *t1, int64_
 		arx::FsCounts c{};
 		arx::FsSortMem m{};
 		arx::fs_run(drv, T, window_bytes ? window_bytes : arx::FS_WINDOW_DEFAULT, slab_bytes ? slab_bytes : arx::FS_SLAB_DEFAULT, &sink, c, m);
-		const int64_t N = c.n_records;
-		std::vector<int64_t> off1((size_t)N + 1, 0), off2((size_t)N + 1, 0);
-		if (N) { drv.fetch(off1.data(), m.out1, (size_t)(N + 1) * 8); drv.fetch(off2.data(), m.out2, (size_t)(N + 1) * 8); }
-		if ((int64_t)sink.text[0].size() != c.bytes1 || (int64_t)sink.text[1].size() != c.bytes2 || c.bytes1 > n1 || c.bytes2 > n2) return ARX_E_DEVICE;
-		// everything is here: only now is anything of the caller's written
-		if (c.bytes1) memcpy(out1, sink.text[0].data(), (size_t)c.bytes1);
-		if (c.bytes2) memcpy(out2, sink.text[1].data(), (size_t)c.bytes2);
-		memcpy(rec_off1, off1.data(), (size_t)(N + 1) * 8); memcpy(rec_off2, off2.data(), (size_t)(N + 1) * 8);
-		out_len[0] = c.bytes1; out_len[1] = c.bytes2;
-		*n_records = N;
-		arx::fs_stats(stats, drv, c, n1, n2, true);
-	} catch (const arx::FsTooLarge &) {
-		return ARX_E_TOO_LARGE;
-	} catch (const arx::HipOutOfMemory &) {
-		return ARX_E_TOO_LARGE;
-	} catch (const std::exception &) {
-		return ARX_E_DEVICE;
-	}
-	return ARX_OK;
+		std::vector<int64_t> off[2];
+		fs_fetch_offsets(drv, m, c.n_records, off);
+		const int rc = fq_hand_out(sink.text, off, c.bytes1, c.bytes2, c.n_records, n1, n2, ARX_E_DEVICE, out1, out2, out_len, rec_off1, rec_off2, n_records);
+		if (rc == ARX_OK) arx::fs_stats(stats, drv, c, n1, n2, true);
+		return rc;
+	});
 }
 
 // ---- the same sort of a file pair that device memory does not hold: sorted runs in temporary files, merged on the device (dev_fqmerge.h)
 extern "C" int arx_fastq_sort_ex(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t flags, int64_t max_bytes, int64_t run_bytes,
                                  const char *tmp_dir, int64_t *stats, char *msg, int32_t msg_cap)
 {
-	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
 	if (stats) for (int k = 0; k < arx::FX_N_STATS; ++k) stats[k] = 0;
 	if (run_bytes == 0) return arx_fastq_sort(device, r1_in, r2_in, r1_out, r2_out, flags, max_bytes, stats, msg, msg_cap);
-	if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) { say("arx_fastq_sort_ex: unknown flag bits"); return ARX_E_ARG; }
-	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
-	if (!r1_in || !r2_in || max_bytes < 0 || (!check && (!r1_out || !r2_out))) { say("arx_fastq_sort_ex: null argument"); return ARX_E_ARG; }
-	if (run_bytes < -1 || (run_bytes > 0 && run_bytes < arx::FS_MIN_WINDOW)) {
-		say("arx_fastq_sort_ex: run_bytes is -1, 0 or at least the " + std::to_string(arx::FS_MIN_WINDOW) + " bytes of the smallest parse window");
-		return ARX_E_ARG;
-	}
-	const char *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
-	if (!check) {
-		if (fs_same_file(r1_out, r2_out)) { say("arx_fastq_sort_ex: the two output paths are the same file"); return ARX_E_ARG; }
-		for (int i = 0; i < 2; ++i)
-			for (int o = 0; o < 2; ++o)
-				if (fs_same_file(in[i], out[o])) { say(std::string("arx_fastq_sort_ex: ") + out[o] + " is an input and an output"); return ARX_E_ARG; }
-	}
-	std::string err;
-	try {
-		const int rc = arx::fx_sort_files(device, in, out, flags, max_bytes, run_bytes, tmp_dir, stats, err, arx::shared_device_bgzf);
-		if (rc != ARX_OK) say(err);
-		return rc;
-	} catch (const arx::FsTooLarge &e) {
-		say(e.what());
-		return ARX_E_TOO_LARGE;
-	} catch (const arx::FsIoError &e) {
-		say(e.what());
-		return ARX_E_IO;
-	} catch (const arx::HipOutOfMemory &e) { // a run's buffers, or the table of all records (hip_res.h)
-		say("the device memory does not hold a run of these files or the table of their records (" + std::to_string(e.wanted >> 20) + " MiB more were asked for, " +
-		    std::to_string(e.free_bytes >> 20) + " MiB are free): use a smaller run_bytes; where the table of all records is what does not fit, sort per lane");
-		return ARX_E_TOO_LARGE;
-	} catch (const std::exception &e) {
-		say(e.what());
-		return ARX_E_DEVICE;
-	}
+	return fq_file_call(msg, msg_cap, "the device memory does not hold a run of these files or the table of their records",
+	                    ": use a smaller run_bytes; where the table of all records is what does not fit, sort per lane", [&]() {
+		const char *call = "arx_fastq_sort_ex", *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
+		if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) fq_bad(call, "unknown flag bits");
+		fq_check_paths(call, in, out, !(flags & ARX_FQSORT_CHECK), max_bytes >= 0);
+		fq_check_run_bytes(call, run_bytes);
+		arx::fx_sort_files(device, in, out, flags, max_bytes, run_bytes, tmp_dir, stats, arx::shared_device_bgzf);
+	});
 }
 
 extern "C" int arx_selftest_fastq_sort_ext(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int64_t window_bytes, int64_t slab_bytes, int64_t run_bytes,
@@ -402,13 +419,12 @@ extern "C" int arx_selftest_fastq_sort_ext(int32_t device, const uint8_t *t1, in
 	    window < arx::FS_MIN_WINDOW || window > arx::FS_MAX_WINDOW || run_bytes < window)
 		return ARX_E_ARG;
 	if (stats) for (int k = 0; k < arx::FX_N_STATS; ++k) stats[k] = 0;
-	try {
+	return fq_selftest_call([&]() -> int {
 		arx::select_device(device, arx::FS_NO_DEVICE);
 		arx::Stream st;
 		st.create();
 		arx::FxHipDrv drv; drv.st = st;
-		arx::FxMemSrc src;
-		src.st = st; src.t[0] = t1; src.t[1] = t2; src.n[0] = n1; src.n[1] = n2;
+		arx::FxMemSrc src(st, t1, n1, t2, n2);
 		arx::FxMemStore store;
 		arx::FsMemSink sink;
 		sink.init(drv.st);
@@ -417,63 +433,26 @@ extern "C" int arx_selftest_fastq_sort_ext(int32_t device, const uint8_t *t1, in
 		arx::FsSortMem m{};
 		arx::FxRuns S;
 		arx::fx_run(drv, src, &store, &sink, run_bytes, window, slab_bytes ? slab_bytes : arx::FS_SLAB_DEFAULT, c, m, S, io);
-		const int64_t N = c.n_records;
-		std::vector<int64_t> off1((size_t)N + 1, 0), off2((size_t)N + 1, 0);
-		if (N) { drv.fetch(off1.data(), m.out1, (size_t)(N + 1) * 8); drv.fetch(off2.data(), m.out2, (size_t)(N + 1) * 8); }
-		if ((int64_t)sink.text[0].size() != c.bytes1 || (int64_t)sink.text[1].size() != c.bytes2 || c.bytes1 > n1 || c.bytes2 > n2) return ARX_E_DEVICE;
-		// everything is here: only now is anything of the caller's written
-		if (c.bytes1) memcpy(out1, sink.text[0].data(), (size_t)c.bytes1);
-		if (c.bytes2) memcpy(out2, sink.text[1].data(), (size_t)c.bytes2);
-		memcpy(rec_off1, off1.data(), (size_t)(N + 1) * 8); memcpy(rec_off2, off2.data(), (size_t)(N + 1) * 8);
-		out_len[0] = c.bytes1; out_len[1] = c.bytes2;
-		*n_records = N;
-		arx::fx_stats(stats, drv, c, n1, n2, true, S, io);
-	} catch (const arx::FsTooLarge &) {
-		return ARX_E_TOO_LARGE;
-	} catch (const arx::HipOutOfMemory &) {
-		return ARX_E_TOO_LARGE;
-	} catch (const std::exception &) {
-		return ARX_E_DEVICE;
-	}
-	return ARX_OK;
+		std::vector<int64_t> off[2];
+		fs_fetch_offsets(drv, m, c.n_records, off);
+		const int rc = fq_hand_out(sink.text, off, c.bytes1, c.bytes2, c.n_records, n1, n2, ARX_E_DEVICE, out1, out2, out_len, rec_off1, rec_off2, n_records);
+		if (rc == ARX_OK) arx::fx_stats(stats, drv, c, n1, n2, true, S, io);
+		return rc;
+	});
 }
 
 // ---- in front of the sort: haplotagging, stLFR and TELLseq headers rewritten to the feeder's form (dev_fqstd.h, hip_fqstd.h)
 extern "C" int arx_fastq_standardize(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t format, int32_t flags, int64_t *stats,
                                      char *msg, int32_t msg_cap)
 {
-	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
 	if (stats) for (int k = 0; k < arx::FQS_N_STATS; ++k) stats[k] = 0;
-	if (flags & ~(ARX_FQSTD_BGZF | ARX_FQSTD_DETECT | ARX_FQSTD_TIMED)) { say("arx_fastq_standardize: unknown flag bits"); return ARX_E_ARG; }
-	if (format < ARX_FQSTD_AUTO || format > ARX_FQSTD_TELLSEQ) { say("arx_fastq_standardize: format is ARX_FQSTD_AUTO, _HAPLOTAGGING, _STLFR or _TELLSEQ"); return ARX_E_ARG; }
-	const bool detect = (flags & ARX_FQSTD_DETECT) != 0;
-	if (!r1_in || !r2_in || (!detect && (!r1_out || !r2_out))) { say("arx_fastq_standardize: null argument"); return ARX_E_ARG; }
-	const char *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
-	if (!detect) {
-		if (fs_same_file(r1_out, r2_out)) { say("arx_fastq_standardize: the two output paths are the same file"); return ARX_E_ARG; }
-		for (int i = 0; i < 2; ++i)
-			for (int o = 0; o < 2; ++o)
-				if (fs_same_file(in[i], out[o])) { say(std::string("arx_fastq_standardize: ") + out[o] + " is an input and an output"); return ARX_E_ARG; }
-	}
-	std::string err;
-	try {
-		const int rc = arx::fqs_files(device, in, out, format, flags, stats, err, arx::shared_device_bgzf);
-		if (rc != ARX_OK) say(err);
-		return rc;
-	} catch (const arx::FsTooLarge &e) {
-		say(e.what());
-		return ARX_E_TOO_LARGE;
-	} catch (const arx::FsIoError &e) {
-		say(e.what());
-		return ARX_E_IO;
-	} catch (const arx::HipOutOfMemory &e) { // the windows or the slab buffers (hip_res.h)
-		say("the device memory does not hold the windows and slabs of the call (" + std::to_string(e.wanted >> 20) + " MiB more were asked for, " + std::to_string(e.free_bytes >> 20) +
-		    " MiB are free)");
-		return ARX_E_TOO_LARGE;
-	} catch (const std::exception &e) {
-		say(e.what());
-		return ARX_E_DEVICE;
-	}
+	return fq_file_call(msg, msg_cap, "the device memory does not hold the windows and slabs of the call", "", [&]() {
+		const char *call = "arx_fastq_standardize", *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
+		if (flags & ~(ARX_FQSTD_BGZF | ARX_FQSTD_DETECT | ARX_FQSTD_TIMED)) fq_bad(call, "unknown flag bits");
+		fq_check_format(call, format);
+		fq_check_paths(call, in, out, !(flags & ARX_FQSTD_DETECT));
+		arx::fqs_files(device, in, out, format, flags, stats, arx::shared_device_bgzf);
+	});
 }
 
 extern "C" int arx_selftest_fastq_standardize(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int32_t format, int64_t window_bytes, int64_t slab_bytes,
@@ -485,7 +464,7 @@ extern "C" int arx_selftest_fastq_standardize(int32_t device, const uint8_t *t1,
 		return ARX_E_ARG;
 	if (stats) for (int k = 0; k < arx::FQS_N_STATS; ++k) stats[k] = 0;
 	const int64_t window = window_bytes ? window_bytes : arx::FS_WINDOW_DEFAULT, slab = slab_bytes ? slab_bytes : arx::FS_SLAB_DEFAULT;
-	try {
+	return fq_selftest_call([&]() -> int {
 		arx::select_device(device, arx::FQS_NO_DEVICE);
 		arx::Stream st;
 		st.create();
@@ -493,12 +472,8 @@ extern "C" int arx_selftest_fastq_standardize(int32_t device, const uint8_t *t1,
 		int fmt = format;
 		int64_t decided = -1;
 		if (format == ARX_FQSTD_AUTO) {
-			arx::FxMemSrc src;
-			src.st = st; src.t[0] = t1; src.t[1] = t2; src.n[0] = n1; src.n[1] = n2;
 			arx::FqsCounts d;
-			const int rc = arx::fqs_detect(drv, src, window, d);
-			drv.pass_done();
-			if (rc != arx::FS_OK) return rc == arx::FS_E_TOO_LARGE ? ARX_E_TOO_LARGE : ARX_E_DEVICE;
+			arx::fqs_detect_mem(drv, t1, n1, t2, n2, window, d);
 			fmt = d.format; decided = d.decided;
 			if (fmt == ARX_FQSTD_STANDARD || fmt == ARX_FQSTD_UNKNOWN) {
 				d.n_records = 0; // nothing was written
@@ -506,77 +481,35 @@ extern "C" int arx_selftest_fastq_standardize(int32_t device, const uint8_t *t1,
 				return fmt == ARX_FQSTD_STANDARD ? ARX_OK : ARX_E_ARG;
 			}
 		}
-		arx::FxMemSrc src;
-		src.st = st; src.t[0] = t1; src.t[1] = t2; src.n[0] = n1; src.n[1] = n2;
+		arx::FxMemSrc src(st, t1, n1, t2, n2);
 		arx::FsMemSink sink;
 		sink.init(drv.st);
 		arx::FqsCounts c;
-		std::vector<int64_t> off1, off2;
-		c.off1 = &off1; c.off2 = &off2;
-		const int rc = arx::fqs_convert(drv, src, fmt, window, slab, sink, c);
-		if (rc != arx::FS_OK) return rc == arx::FS_E_TOO_LARGE ? ARX_E_TOO_LARGE : ARX_E_DEVICE;
+		std::vector<int64_t> off[2];
+		c.off1 = &off[0]; c.off2 = &off[1];
+		arx::fqs_throw(arx::fqs_convert(drv, src, fmt, window, slab, sink, c), window);
 		sink.flush();
 		drv.pass_done();
-		const int64_t N = c.n_records;
-		if ((int64_t)sink.text[0].size() != c.bytes1 || (int64_t)sink.text[1].size() != c.bytes2 || (int64_t)off1.size() != N + 1 || (int64_t)off2.size() != N + 1) return ARX_E_DEVICE;
-		if (c.bytes1 > cap1 || c.bytes2 > cap2) return ARX_E_TOO_LARGE;
-		// everything is here: only now is anything of the caller's written
-		if (c.bytes1) memcpy(out1, sink.text[0].data(), (size_t)c.bytes1);
-		if (c.bytes2) memcpy(out2, sink.text[1].data(), (size_t)c.bytes2);
-		memcpy(rec_off1, off1.data(), (size_t)(N + 1) * 8); memcpy(rec_off2, off2.data(), (size_t)(N + 1) * 8);
-		out_len[0] = c.bytes1; out_len[1] = c.bytes2;
-		*n_records = N;
-		arx::fqs_stats(stats, drv, c, fmt, decided, sink.us_consume, 0, 0);
-	} catch (const arx::FsTooLarge &) {
-		return ARX_E_TOO_LARGE;
-	} catch (const arx::HipOutOfMemory &) {
-		return ARX_E_TOO_LARGE;
-	} catch (const std::exception &) {
-		return ARX_E_DEVICE;
-	}
-	return ARX_OK;
+		const int rc = fq_hand_out(sink.text, off, c.bytes1, c.bytes2, c.n_records, cap1, cap2, ARX_E_TOO_LARGE, out1, out2, out_len, rec_off1, rec_off2, n_records);
+		if (rc == ARX_OK) arx::fqs_stats(stats, drv, c, fmt, decided, sink.us_consume, 0, 0);
+		return rc;
+	});
 }
 
 // ---- the two in one call: raw headers in, standardized records ordered by barcode out (dev_fqprep.h, hip_fqprep.h)
 extern "C" int arx_fastq_prepare(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t format, int32_t flags, int64_t max_bytes,
                                  int64_t run_bytes, const char *tmp_dir, int64_t *stats, char *msg, int32_t msg_cap)
 {
-	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
 	if (stats) for (int k = 0; k < arx::FP_N_STATS; ++k) stats[k] = 0;
-	if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) { say("arx_fastq_prepare: unknown flag bits"); return ARX_E_ARG; }
-	if (format < ARX_FQSTD_AUTO || format > ARX_FQSTD_TELLSEQ) { say("arx_fastq_prepare: format is ARX_FQSTD_AUTO, _HAPLOTAGGING, _STLFR or _TELLSEQ"); return ARX_E_ARG; }
-	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
-	if (!r1_in || !r2_in || max_bytes < 0 || (!check && (!r1_out || !r2_out))) { say("arx_fastq_prepare: null argument"); return ARX_E_ARG; }
-	if (run_bytes < -1 || (run_bytes > 0 && run_bytes < arx::FS_MIN_WINDOW)) {
-		say("arx_fastq_prepare: run_bytes is -1, 0 or at least the " + std::to_string(arx::FS_MIN_WINDOW) + " bytes of the smallest parse window");
-		return ARX_E_ARG;
-	}
-	const char *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
-	if (!check) {
-		if (fs_same_file(r1_out, r2_out)) { say("arx_fastq_prepare: the two output paths are the same file"); return ARX_E_ARG; }
-		for (int i = 0; i < 2; ++i)
-			for (int o = 0; o < 2; ++o)
-				if (fs_same_file(in[i], out[o])) { say(std::string("arx_fastq_prepare: ") + out[o] + " is an input and an output"); return ARX_E_ARG; }
-	}
-	std::string err;
-	try {
-		const int rc = arx::fp_files(device, in, out, format, flags, max_bytes, run_bytes, tmp_dir, stats, err, arx::shared_device_bgzf);
-		if (rc != ARX_OK) say(err);
-		return rc;
-	} catch (const arx::FsTooLarge &e) {
-		say(e.what());
-		return ARX_E_TOO_LARGE;
-	} catch (const arx::FsIoError &e) {
-		say(e.what());
-		return ARX_E_IO;
-	} catch (const arx::HipOutOfMemory &e) { // the texts, a run's buffers, or the tables of all records (hip_res.h)
-		say("the device memory does not hold these files, a run of them or the table of their records (" + std::to_string(e.wanted >> 20) + " MiB more were asked for, " +
-		    std::to_string(e.free_bytes >> 20) + " MiB are free): prepare in runs (run_bytes -1), or with a smaller run_bytes; where the table of all records is what does not fit, prepare per lane");
-		return ARX_E_TOO_LARGE;
-	} catch (const std::exception &e) {
-		say(e.what());
-		return ARX_E_DEVICE;
-	}
+	return fq_file_call(msg, msg_cap, "the device memory does not hold these files, a run of them or the table of their records",
+	                    ": prepare in runs (run_bytes -1), or with a smaller run_bytes; where the table of all records is what does not fit, prepare per lane", [&]() {
+		const char *call = "arx_fastq_prepare", *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
+		if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) fq_bad(call, "unknown flag bits");
+		fq_check_format(call, format);
+		fq_check_paths(call, in, out, !(flags & ARX_FQSORT_CHECK), max_bytes >= 0);
+		fq_check_run_bytes(call, run_bytes);
+		arx::fp_files(device, in, out, format, flags, max_bytes, run_bytes, tmp_dir, stats, arx::shared_device_bgzf);
+	});
 }
 
 extern "C" int arx_selftest_fastq_prepare(int32_t device, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int32_t format, int64_t window_bytes, int64_t slab_bytes,
@@ -590,7 +523,7 @@ extern "C" int arx_selftest_fastq_prepare(int32_t device, const uint8_t *t1, int
 	    (run_bytes != 0 && run_bytes < window))
 		return ARX_E_ARG;
 	if (stats) for (int k = 0; k < arx::FP_N_STATS; ++k) stats[k] = 0;
-	try {
+	return fq_selftest_call([&]() -> int {
 		arx::select_device(device, arx::FP_NO_DEVICE);
 		arx::Stream st;
 		st.create();
@@ -598,31 +531,25 @@ extern "C" int arx_selftest_fastq_prepare(int32_t device, const uint8_t *t1, int
 		int fmt = format;
 		int64_t decided = -1;
 		arx::FpRows rows;
+		std::vector<int64_t> off[2];
 		if (format == ARX_FQSTD_AUTO) {
-			arx::FxMemSrc src;
-			src.st = st; src.t[0] = t1; src.t[1] = t2; src.n[0] = n1; src.n[1] = n2;
 			arx::FqsCounts d;
-			const int rc = arx::fqs_detect(drv, src, window, d);
-			ARX_HIP_CHECK(hipStreamSynchronize(drv.st));
-			if (rc != arx::FS_OK) return rc == arx::FS_E_TOO_LARGE ? ARX_E_TOO_LARGE : ARX_E_DEVICE;
+			arx::fqs_detect_mem(drv, t1, n1, t2, n2, window, d);
 			fmt = d.format; decided = d.decided;
 			if (fmt == ARX_FQSTD_UNKNOWN) {
 				arx::fp_stats(stats, fmt, -1, rows);
 				return ARX_E_ARG;
 			}
 			if (fmt == ARX_FQSTD_STANDARD) { // the sort itself, into room of its own: the caller's is written only when everything is here
-				std::vector<uint8_t> o1((size_t)n1 + 1), o2((size_t)n2 + 1);
-				std::vector<int64_t> off1((size_t)(n1 / 5 + 2)), off2((size_t)(n1 / 5 + 2));
+				std::vector<uint8_t> o[2] = {std::vector<uint8_t>((size_t)n1 + 1), std::vector<uint8_t>((size_t)n2 + 1)};
+				for (int f = 0; f < 2; ++f) off[f].resize((size_t)(n1 / 5 + 2));
 				int64_t len[2] = {0, 0}, N = 0, s[arx::FX_N_STATS] = {0};
-				const int rc2 = run_bytes == 0 ? arx_selftest_fastq_sort(device, t1, n1, t2, n2, window, slab, o1.data(), o2.data(), len, off1.data(), off2.data(), &N, s)
-				                               : arx_selftest_fastq_sort_ext(device, t1, n1, t2, n2, window, slab, run_bytes, o1.data(), o2.data(), len, off1.data(), off2.data(), &N, s);
-				if (rc2 != ARX_OK) return rc2;
-				if (len[0] > cap1 || len[1] > cap2) return ARX_E_TOO_LARGE;
-				if (len[0]) memcpy(out1, o1.data(), (size_t)len[0]);
-				if (len[1]) memcpy(out2, o2.data(), (size_t)len[1]);
-				memcpy(rec_off1, off1.data(), (size_t)(N + 1) * 8); memcpy(rec_off2, off2.data(), (size_t)(N + 1) * 8);
-				out_len[0] = len[0]; out_len[1] = len[1];
-				*n_records = N;
+				int rc = run_bytes == 0 ? arx_selftest_fastq_sort(device, t1, n1, t2, n2, window, slab, o[0].data(), o[1].data(), len, off[0].data(), off[1].data(), &N, s)
+				                        : arx_selftest_fastq_sort_ext(device, t1, n1, t2, n2, window, slab, run_bytes, o[0].data(), o[1].data(), len, off[0].data(), off[1].data(), &N, s);
+				if (rc != ARX_OK) return rc;
+				for (int f = 0; f < 2; ++f) { o[f].resize((size_t)len[f]); off[f].resize((size_t)N + 1); }
+				rc = fq_hand_out(o, off, len[0], len[1], N, cap1, cap2, ARX_E_TOO_LARGE, out1, out2, out_len, rec_off1, rec_off2, n_records);
+				if (rc != ARX_OK) return rc;
 				if (stats) memcpy(stats, s, sizeof s);
 				arx::fp_stats(stats, fmt, decided, rows);
 				return ARX_OK;
@@ -642,33 +569,18 @@ extern "C" int arx_selftest_fastq_prepare(int32_t device, const uint8_t *t1, int
 			if (n1) ARX_HIP_CHECK(hipMemcpyAsync(d1.p, t1, (size_t)n1, hipMemcpyHostToDevice, drv.st));
 			if (n2) ARX_HIP_CHECK(hipMemcpyAsync(d2.p, t2, (size_t)n2, hipMemcpyHostToDevice, drv.st));
 			const arx::FsText T = {d1.as<uint8_t>(), d2.as<uint8_t>(), n1, n2};
-			arx::fp_run(drv, T, window, slab, &sink, c, m, rows);
+			arx::fs_run_by(drv, T, window, slab, &sink, c, m, rows);
 		} else {
-			arx::FxMemSrc src;
-			src.st = st; src.t[0] = t1; src.t[1] = t2; src.n[0] = n1; src.n[1] = n2;
+			arx::FxMemSrc src(st, t1, n1, t2, n2);
 			arx::fx_run_by(drv, src, &store, &sink, run_bytes, window, slab, c, m, S, io, rows);
 		}
-		const int64_t N = c.n_records;
-		std::vector<int64_t> off1((size_t)N + 1, 0), off2((size_t)N + 1, 0);
-		if (N) { drv.fetch(off1.data(), m.out1, (size_t)(N + 1) * 8); drv.fetch(off2.data(), m.out2, (size_t)(N + 1) * 8); }
-		if ((int64_t)sink.text[0].size() != c.bytes1 || (int64_t)sink.text[1].size() != c.bytes2) return ARX_E_DEVICE;
-		if (c.bytes1 > cap1 || c.bytes2 > cap2) return ARX_E_TOO_LARGE;
-		// everything is here: only now is anything of the caller's written
-		if (c.bytes1) memcpy(out1, sink.text[0].data(), (size_t)c.bytes1);
-		if (c.bytes2) memcpy(out2, sink.text[1].data(), (size_t)c.bytes2);
-		memcpy(rec_off1, off1.data(), (size_t)(N + 1) * 8); memcpy(rec_off2, off2.data(), (size_t)(N + 1) * 8);
-		out_len[0] = c.bytes1; out_len[1] = c.bytes2;
-		*n_records = N;
+		fs_fetch_offsets(drv, m, c.n_records, off);
+		const int rc = fq_hand_out(sink.text, off, c.bytes1, c.bytes2, c.n_records, cap1, cap2, ARX_E_TOO_LARGE, out1, out2, out_len, rec_off1, rec_off2, n_records);
+		if (rc != ARX_OK) return rc;
 		arx::fx_stats(stats, drv, c, n1, n2, true, S, io);
 		arx::fp_stats(stats, fmt, decided, rows);
-	} catch (const arx::FsTooLarge &) {
-		return ARX_E_TOO_LARGE;
-	} catch (const arx::HipOutOfMemory &) {
-		return ARX_E_TOO_LARGE;
-	} catch (const std::exception &) {
-		return ARX_E_DEVICE;
-	}
-	return ARX_OK;
+		return ARX_OK;
+	});
 }
 
 // ---- the .bai of a coordinate-sorted BAM file (dev_bamindex.h, hip_bamindex.h)

@@ -14,6 +14,13 @@
 // compressed and written (ARX_FQSORT_BGZF: DeviceBgzf::run_device, blocks cut every 65280 bytes, the 28-byte EOF block last), slab k + 1 is
 // gathered.  It goes to <out>.tmp, renamed when everything is written and removed otherwise.
 //
+// The host side is one path, shared with arx_fastq_standardize and arx_fastq_prepare (hip_fqstd.h, hip_fqprep.h).  In: FsInput::open and
+// fs_open_inputs / fs_probe_inputs; FxFileSrc::take acquires a reader's slab, checks it and has FsSlabUp bring it up to where its caller
+// points -- next(): the source's own slab text, which fills runs and windows; load(): its place in the whole text, no copy between.  Out:
+// FsFileSink::open / begin / end (both <out>.tmp, whose names a failed fopen forgets, so that nothing is removed that the call did not create;
+// the compressor; finish() with its times booked) and FxFileStore::create (the run files).  In core: fs_run_by over a row policy, as fx_run_by
+// for runs.  What is refused is thrown (FsBadArg, FsTooLarge, FsIoError) and becomes code and text in arx_bgzf.hip's fq_file_call.
+//
 // Device memory of a call: the two texts (a text that outgrows its buffer moves to one half as large again), four output slab buffers (256 MiB at
 // the default), per record 80 bytes (dev_fqsort.h: table, keys, values, output offsets), the parse's window buffers (FS_WINDOW_DEFAULT per file,
 // and about as much again for the line index), rocprim's scratch.  What does not fit is ARX_E_TOO_LARGE: sort per lane, or split the input.
@@ -66,6 +73,7 @@ template <class F> static __global__ void __launch_bounds__(256) k_fs_items(F f,
 
 struct FsTooLarge : std::runtime_error { using std::runtime_error::runtime_error; };
 struct FsIoError : std::runtime_error { using std::runtime_error::runtime_error; };
+struct FsBadArg : std::runtime_error { using std::runtime_error::runtime_error; }; // what only the files show: no format to detect
 struct FsOr { __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a | b; } };
 
 constexpr const char *FS_NO_DEVICE = "no such HIP device: the FASTQ sort runs on the GPU (there is no CPU fallback)";
@@ -213,13 +221,14 @@ struct FsMemSink : FsSink { // the self-test's: into host memory
 // an output file: written as <path>.tmp, renamed by commit(), removed where that was not reached
 struct FsOutFile {
 	FILE *f = nullptr;
-	std::string path, tmp;
+	std::string path, tmp; // tmp: empty unless this call created it -- nothing else is ever removed
 	int64_t bytes_out = 0;
 	bool open(const char *p)
 	{
 		path = p; tmp = path + ".tmp";
 		f = fopen(tmp.c_str(), "wb");
 		if (f) setvbuf(f, nullptr, _IOFBF, 1 << 20);
+		else tmp.clear();
 		return f != nullptr;
 	}
 	bool commit()
@@ -243,6 +252,17 @@ struct FsFileSink : FsSink {
 	std::vector<uint8_t> carry[2]; // BGZF: the bytes short of a block
 	PinnedBuf h;
 	double us_compress = 0, us_write = 0;
+	void open(const char *const out_path[2]) // both <out>.tmp
+	{
+		for (int f = 0; f < 2; ++f)
+			if (!file[f].open(out_path[f])) throw FsIoError(std::string("cannot write ") + out_path[f] + ".tmp");
+	}
+	// get_z: the device's compressor (arx_bgzf.hip keeps one per device)
+	void begin(hipStream_t gather_stream, int device, std::shared_ptr<DeviceBgzf> (*get_z)(int))
+	{
+		init(gather_stream);
+		if (bgzf) z = get_z(device);
+	}
 	void consume(int f, const uint8_t *d, int64_t n) override
 	{
 		if (n <= 0) return;
@@ -281,6 +301,11 @@ struct FsFileSink : FsSink {
 			if (!file[f].commit()) throw FsIoError(file[f].path + ": write failed");
 		us_write += bs_now_us() - t0;
 	}
+	template <class Drv> void end(Drv &drv) // finish(), its times booked
+	{
+		finish();
+		drv.us[FS_T_COMPRESS] = us_compress; drv.us[FS_T_WRITE] = us_write;
+	}
 };
 
 inline void fs_stats(int64_t *stats, const FsHipDrv &drv, const FsCounts &c, int64_t n1, int64_t n2, bool written)
@@ -291,9 +316,10 @@ inline void fs_stats(int64_t *stats, const FsHipDrv &drv, const FsCounts &c, int
 	for (int k = FS_T_READ; k < FS_N_STATS; ++k) stats[k] = (int64_t)drv.us[k];
 }
 
-// table, order and (sink != null) gather of two texts in device memory.  Without `timed` the phases are wall-clock times between their ends: keys
-// and sort passes together under FS_T_SORT; with it every launch group is awaited and booked on its own
-inline void fs_run(FsHipDrv &drv, const FsText &T, int64_t window, int64_t slab, FsSink *sink, FsCounts &c, FsSortMem &m)
+// table, order and (sink != null) gather of two texts in device memory.  rows: what the records are to the sort (dev_fqmerge.h: FxPlainRows;
+// dev_fqprep.h: FpRows, which composes the key and the header).  Without `timed` the phases are wall-clock times between their ends: keys and
+// sort passes together under FS_T_SORT; with it every launch group is awaited and booked on its own
+template <class Rows> void fs_run_by(FsHipDrv &drv, const FsText &T, int64_t window, int64_t slab, FsSink *sink, FsCounts &c, FsSortMem &m, Rows &rows)
 {
 	double t0 = bs_now_us();
 	const int rc = fs_parse(drv, T, window, c);
@@ -305,31 +331,40 @@ inline void fs_run(FsHipDrv &drv, const FsText &T, int64_t window, int64_t slab,
 	for (int s = FS_W_WIN1; s < FS_W_KEYS0; ++s) drv.work_[s].release(); // the parse's buffers make room for the sort's
 	const int64_t N = c.n_records;
 	fs_sort_mem(drv, N, m);
-	const int64_t longest = fs_order(drv, T, drv.tab_.as<FsRec>(), N, m, c);
+	const auto key = rows.key(drv, T, drv.tab_.as<FsRec>(), N, m);
+	const int64_t longest = fs_order_by(drv, key, N, m, c);
 	ARX_HIP_CHECK(hipStreamSynchronize(drv.st));
 	if (!drv.timed) drv.us[FS_T_SORT] = bs_now_us() - t0;
 	c.slabs = 0;
 	if (!sink) return;
 	t0 = bs_now_us();
-	fs_gather(drv, T, drv.tab_.as<FsRec>(), N, m, slab, longest, *sink, c);
+	rows.gather(drv, T, key, N, m, slab, longest, *sink, c);
 	sink->flush();
 	if (!drv.timed) drv.us[FS_T_GATHER] = bs_now_us() - t0 - sink->us_consume;
 }
+inline void fs_run(FsHipDrv &drv, const FsText &T, int64_t window, int64_t slab, FsSink *sink, FsCounts &c, FsSortMem &m)
+{
+	FxPlainRows rows;
+	fs_run_by(drv, T, window, slab, sink, c, m, rows);
+}
 
-// one input file into device memory
+// ---- the way in.  One input file: its reader, and (where a call holds the whole text) its text in device memory
 struct FsInput {
 	std::unique_ptr<SlabReader> rd;
 	bool bgzf = false, done = false;
 	DevBuf text;
 	int64_t len = 0;
-	bool open(const char *path)
+	template <class R> bool open_as(const char *path, size_t chunk)
 	{
-		bgzf = file_is_bgzf(path);
-		if (bgzf) { std::unique_ptr<BgzfChunkReader> r(new BgzfChunkReader()); const bool ok = r->open(path, FS_READ_CHUNK, FS_READ_CHUNKS); rd = std::move(r); return ok; }
-		std::unique_ptr<ChunkReader> r(new ChunkReader());
-		const bool ok = r->open(path, FS_READ_CHUNK, FS_READ_CHUNKS);
+		std::unique_ptr<R> r(new R());
+		const bool ok = r->open(path, chunk, FS_READ_CHUNKS);
 		rd = std::move(r);
 		return ok;
+	}
+	bool open(const char *path, size_t chunk = FS_READ_CHUNK)
+	{
+		bgzf = file_is_bgzf(path);
+		return bgzf ? open_as<BgzfChunkReader>(path, chunk) : open_as<ChunkReader>(path, chunk);
 	}
 	void room(int64_t need, hipStream_t st) // the text so far stays
 	{
@@ -340,85 +375,46 @@ struct FsInput {
 		text = std::move(t);
 	}
 };
-
-// -> ARX_*; err: the text
-// get_z: the device's compressor (arx_bgzf.hip keeps one per device)
-inline int fs_sort_files(int device, const char *const in_path[2], const char *const out_path[2], int flags, int64_t max_bytes, int64_t *stats, std::string &err,
-                         std::shared_ptr<DeviceBgzf> (*get_z)(int))
+inline void fs_open_inputs(FsInput in[2], const char *const path[2], size_t chunk = FS_READ_CHUNK)
 {
-	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
-	FsInput in[2];
 	for (int f = 0; f < 2; ++f)
-		if (!in[f].open(in_path[f])) { err = std::string("cannot read ") + in_path[f]; return ARX_E_IO; }
-	FsFileSink sink;
-	sink.bgzf = (flags & ARX_FQSORT_BGZF) != 0;
-	if (!check)
-		for (int f = 0; f < 2; ++f)
-			if (!sink.file[f].open(out_path[f])) { err = std::string("cannot write ") + sink.file[f].tmp; return ARX_E_IO; }
-	select_device(device, FS_NO_DEVICE);
-	Stream st; // the call's own; declared before the buffers, so that it has ended when they are freed
-	st.create();
-	FsHipDrv drv; drv.st = st; drv.timed = (flags & ARX_FQSORT_TIMED) != 0;
-	// ---- the two texts into device memory, slab by slab as the readers have them
-	{
-		DevBuf d_comp, d_rows, d_status;
-		for (int f = 0; f < 2; ++f) in[f].rd->start();
-		while (!in[0].done || !in[1].done) {
-			for (int f = 0; f < 2; ++f) {
-				FsInput &I = in[f];
-				if (I.done) continue;
-				double t0 = bs_now_us();
-				const SlabReader::Slab *s = I.rd->acquire();
-				drv.us[FS_T_READ] += bs_now_us() - t0;
-				if (!s) { I.done = true; continue; }
-				t0 = bs_now_us();
-				if (s->err) { err = std::string(in_path[f]) + (I.bgzf ? ": not a chain of whole BGZF blocks" : ": read error"); return ARX_E_IO; }
-				if (max_bytes > 0 && in[0].len + in[1].len + (int64_t)s->text > max_bytes) {
-					err = std::string(in_path[0]) + " and " + in_path[1] + " inflate to more than the " + std::to_string(max_bytes) + " bytes allowed" + FS_REMEDY;
-					return ARX_E_TOO_LARGE;
-				}
-				I.room(I.len + (int64_t)s->text, st);
-				uint8_t *dst = I.text.as<uint8_t>() + I.len;
-				if (!I.bgzf) {
-					if (s->len) ARX_HIP_CHECK(hipMemcpyAsync(dst, s->buf, s->len, hipMemcpyHostToDevice, st));
-				} else if (s->n_rows) {
-					const size_t nr = s->n_rows;
-					if (!d_comp.p || s->len > d_comp.bytes) d_comp.alloc(s->len + s->len / 4);
-					if (!d_rows.p || nr * sizeof(InfRow) > d_rows.bytes) { d_rows.alloc(2 * nr * sizeof(InfRow)); d_status.alloc(4 * (2 * nr + 2)); }
-					ARX_HIP_CHECK(hipMemcpyAsync(d_comp.p, s->buf, s->len, hipMemcpyHostToDevice, st));
-					ARX_HIP_CHECK(hipMemcpyAsync(d_rows.p, s->rows, nr * sizeof(InfRow), hipMemcpyHostToDevice, st));
-					ARX_HIP_CHECK(hipMemsetAsync(d_status.p, 0, 4 * (nr + 2), st));
-					int32_t *counts = d_status.as<int32_t>() + nr;
-					inflate_launch(st, d_comp.as<uint8_t>(), (int64_t)s->len, d_rows.as<InfRow>(), (int)nr, dst, (int64_t)s->text, d_status.as<int32_t>(), counts);
-					int32_t bad[2] = {0, 0};
-					ARX_HIP_CHECK(hipMemcpyAsync(bad, counts, 8, hipMemcpyDeviceToHost, st));
-					ARX_HIP_CHECK(hipStreamSynchronize(st));
-					if (bad[0] != 0) { err = std::string(in_path[f]) + ": a BGZF block does not inflate"; return ARX_E_IO; }
-				}
-				ARX_HIP_CHECK(hipStreamSynchronize(st)); // the reader may refill the slab
-				I.len += (int64_t)s->text;
-				if (s->eof) I.done = true;
-				I.rd->release();
-				drv.us[FS_T_INFLATE] += bs_now_us() - t0;
-			}
-		}
-		for (int f = 0; f < 2; ++f) in[f].rd.reset();
-	}
-	const FsText T = {in[0].text.as<uint8_t>(), in[1].text.as<uint8_t>(), in[0].len, in[1].len};
-	FsCounts c{};
-	FsSortMem m{};
-	if (!check) {
-		sink.init(st);
-		if (sink.bgzf) sink.z = get_z(device);
-	}
-	fs_run(drv, T, FS_WINDOW_DEFAULT, FS_SLAB_DEFAULT, check ? nullptr : &sink, c, m);
-	if (!check) {
-		sink.finish();
-		drv.us[FS_T_COMPRESS] = sink.us_compress; drv.us[FS_T_WRITE] = sink.us_write;
-	}
-	fs_stats(stats, drv, c, T.n1, T.n2, !check);
-	return ARX_OK;
+		if (!in[f].open(path[f], chunk)) throw FsIoError(std::string("cannot read ") + path[f]);
 }
+// for the calls that touch the device before they open their readers: a missing input is refused first
+inline void fs_probe_inputs(const char *const path[2])
+{
+	for (int f = 0; f < 2; ++f) {
+		FILE *p = fopen(path[f], "rb");
+		if (!p) throw FsIoError(std::string("cannot read ") + path[f]);
+		fclose(p);
+	}
+}
+
+// a reader's slab to dst in device memory: plain text goes up as it is, of a BGZF slab only the compressed bytes go up and are inflated there
+struct FsSlabUp {
+	DevBuf d_comp, d_rows, d_status;
+	void run(hipStream_t st, const SlabReader::Slab &s, bool bgzf, uint8_t *dst, const char *path)
+	{
+		if (!bgzf) {
+			if (s.len) ARX_HIP_CHECK(hipMemcpyAsync(dst, s.buf, s.len, hipMemcpyHostToDevice, st));
+		} else if (s.n_rows) {
+			const size_t nr = s.n_rows;
+			if (!d_comp.p || s.len > d_comp.bytes) d_comp.alloc(s.len + s.len / 4);
+			if (!d_rows.p || nr * sizeof(InfRow) > d_rows.bytes) { d_rows.alloc(2 * nr * sizeof(InfRow)); d_status.alloc(4 * (2 * nr + 2)); }
+			ARX_HIP_CHECK(hipMemcpyAsync(d_comp.p, s.buf, s.len, hipMemcpyHostToDevice, st));
+			ARX_HIP_CHECK(hipMemcpyAsync(d_rows.p, s.rows, nr * sizeof(InfRow), hipMemcpyHostToDevice, st));
+			ARX_HIP_CHECK(hipMemsetAsync(d_status.p, 0, 4 * (nr + 2), st));
+			int32_t *counts = d_status.as<int32_t>() + nr;
+			inflate_launch(st, d_comp.as<uint8_t>(), (int64_t)s.len, d_rows.as<InfRow>(), (int)nr, dst, (int64_t)s.text, d_status.as<int32_t>(), counts);
+			int32_t bad[2] = {0, 0};
+			ARX_HIP_CHECK(hipMemcpyAsync(bad, counts, 8, hipMemcpyDeviceToHost, st));
+			ARX_HIP_CHECK(hipStreamSynchronize(st));
+			if (bad[0] != 0) throw FsIoError(std::string(path) + ": a BGZF block does not inflate");
+		}
+		ARX_HIP_CHECK(hipStreamSynchronize(st)); // the reader may refill the slab
+	}
+	void release() { d_comp.release(); d_rows.release(); d_status.release(); }
+};
 
 // ---- the external sort (dev_fqmerge.h): arx_fastq_sort_ex with run_bytes != 0, arx_selftest_fastq_sort_ext
 struct FxHipDrv : FsHipDrv {
@@ -486,6 +482,13 @@ struct FxTmpFile {
 };
 struct FxFileStore : FxRunStore {
 	FxTmpFile file[2];
+	void create(const char *tmp_dir, const char *out1) // both run files, under tmp_dir or (null) in the directory of the first output
+	{
+		std::string dir = tmp_dir ? tmp_dir : out1;
+		if (!tmp_dir) { const size_t cut = dir.rfind('/'); dir = cut == std::string::npos ? "." : cut == 0 ? "/" : dir.substr(0, cut); }
+		for (int f = 0; f < 2; ++f)
+			if (!file[f].create(dir, f ? ".r2" : ".r1")) throw FsIoError("cannot write a temporary file under " + dir);
+	}
 	void append(int f, const void *p, int64_t n) override
 	{
 		for (int64_t done = 0; done < n;) {
@@ -604,9 +607,10 @@ inline void fx_stats(int64_t *stats, const FxHipDrv &drv, const FsCounts &c, int
 
 // two texts in host memory (the self-test's source)
 struct FxMemSrc {
-	hipStream_t st = nullptr;
-	const uint8_t *t[2] = {nullptr, nullptr};
-	int64_t n[2] = {0, 0}, at[2] = {0, 0};
+	hipStream_t st;
+	const uint8_t *t[2];
+	int64_t n[2], at[2] = {0, 0};
+	FxMemSrc(hipStream_t s, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2) : st(s), t{t1, t2}, n{n1, n2} {}
 	bool ended(int f) const { return at[f] == n[f]; }
 	int64_t fill(int f, uint8_t *dst, int64_t want)
 	{
@@ -619,52 +623,52 @@ struct FxMemSrc {
 		return k;
 	}
 };
-// the two files through their readers.  A reader's slab goes up (and, BGZF, is inflated) into a buffer of its own; the runs take their bytes from
-// there, so a slab that straddles a run's end is split and its rest opens the next run
+// the two files through their readers.  A reader's slab goes up (and, BGZF, is inflated: FsSlabUp) either into a buffer of its own -- the runs
+// and the windows take their bytes from there, so a slab that straddles a run's end is split and its rest opens the next run -- or, for a call
+// that holds both whole texts, straight to its place in them (load)
 struct FxFileSrc {
 	FsInput *in = nullptr;        // [2]
 	const char *const *path = nullptr;
 	FsHipDrv *drv = nullptr;
 	int64_t max_bytes = 0;
-	DevBuf text[2], d_comp, d_rows, d_status;
+	const char *remedy = "";      // the end of the max_bytes refusal, which is the call's own
+	DevBuf text[2];
+	FsSlabUp up;
 	int64_t have[2] = {0, 0}, at[2] = {0, 0}, total[2] = {0, 0};
+	void start(FsInput *inputs, const char *const *paths, FsHipDrv &d, int64_t most = 0, const char *most_remedy = "")
+	{
+		in = inputs; path = paths; drv = &d; max_bytes = most; remedy = most_remedy;
+		for (int f = 0; f < 2; ++f) in[f].rd->start();
+	}
 	bool ended(int f) const { return in[f].done && at[f] == have[f]; }
-	void next(int f) // the next slab of file f into text[f]
+	// the next slab of file f to dst(its bytes of text) -> those bytes; -1: the file has ended
+	template <class Dst> int64_t take(int f, Dst dst)
 	{
 		FsInput &I = in[f];
-		hipStream_t st = drv->st;
 		double t0 = bs_now_us();
 		const SlabReader::Slab *s = I.rd->acquire();
 		drv->us[FS_T_READ] += bs_now_us() - t0;
-		have[f] = at[f] = 0;
-		if (!s) { I.done = true; return; }
+		if (!s) { I.done = true; return -1; }
 		t0 = bs_now_us();
 		if (s->err) throw FsIoError(std::string(path[f]) + (I.bgzf ? ": not a chain of whole BGZF blocks" : ": read error"));
 		if (max_bytes > 0 && total[0] + total[1] + (int64_t)s->text > max_bytes)
-			throw FsTooLarge(std::string(path[0]) + " and " + path[1] + " inflate to more than the " + std::to_string(max_bytes) + " bytes allowed");
-		if (!text[f].p || s->text > text[f].bytes) { ARX_HIP_CHECK(hipStreamSynchronize(st)); text[f].alloc(s->text + 64); }
-		uint8_t *dst = text[f].as<uint8_t>();
-		if (!I.bgzf) {
-			if (s->len) ARX_HIP_CHECK(hipMemcpyAsync(dst, s->buf, s->len, hipMemcpyHostToDevice, st));
-		} else if (s->n_rows) {
-			const size_t nr = s->n_rows;
-			if (!d_comp.p || s->len > d_comp.bytes) d_comp.alloc(s->len + s->len / 4);
-			if (!d_rows.p || nr * sizeof(InfRow) > d_rows.bytes) { d_rows.alloc(2 * nr * sizeof(InfRow)); d_status.alloc(4 * (2 * nr + 2)); }
-			ARX_HIP_CHECK(hipMemcpyAsync(d_comp.p, s->buf, s->len, hipMemcpyHostToDevice, st));
-			ARX_HIP_CHECK(hipMemcpyAsync(d_rows.p, s->rows, nr * sizeof(InfRow), hipMemcpyHostToDevice, st));
-			ARX_HIP_CHECK(hipMemsetAsync(d_status.p, 0, 4 * (nr + 2), st));
-			int32_t *counts = d_status.as<int32_t>() + nr;
-			inflate_launch(st, d_comp.as<uint8_t>(), (int64_t)s->len, d_rows.as<InfRow>(), (int)nr, dst, (int64_t)s->text, d_status.as<int32_t>(), counts);
-			int32_t bad[2] = {0, 0};
-			ARX_HIP_CHECK(hipMemcpyAsync(bad, counts, 8, hipMemcpyDeviceToHost, st));
-			ARX_HIP_CHECK(hipStreamSynchronize(st));
-			if (bad[0] != 0) throw FsIoError(std::string(path[f]) + ": a BGZF block does not inflate");
-		}
-		ARX_HIP_CHECK(hipStreamSynchronize(st)); // the reader may refill the slab
-		have[f] = (int64_t)s->text; total[f] += have[f];
+			throw FsTooLarge(std::string(path[0]) + " and " + path[1] + " inflate to more than the " + std::to_string(max_bytes) + " bytes allowed" + remedy);
+		const int64_t n = (int64_t)s->text;
+		up.run(drv->st, *s, I.bgzf, dst(n), path[f]);
+		total[f] += n;
 		if (s->eof) I.done = true;
 		I.rd->release();
 		drv->us[FS_T_INFLATE] += bs_now_us() - t0;
+		return n;
+	}
+	void next(int f) // the next slab of file f into text[f]
+	{
+		have[f] = at[f] = 0;
+		const int64_t n = take(f, [&](int64_t bytes) {
+			if (!text[f].p || (size_t)bytes > text[f].bytes) { ARX_HIP_CHECK(hipStreamSynchronize(drv->st)); text[f].alloc((size_t)bytes + 64); }
+			return text[f].as<uint8_t>();
+		});
+		if (n > 0) have[f] = n;
 	}
 	int64_t fill(int f, uint8_t *dst, int64_t want)
 	{
@@ -678,26 +682,60 @@ struct FxFileSrc {
 		while (at[f] == have[f] && !in[f].done) next(f); // so that ended() knows of an end that lies right here
 		return got;
 	}
+	// both whole texts into device memory (in[f].text), slab by slab as the readers have them, every slab inflated straight to its place; the
+	// readers and the slab buffers are gone afterwards
+	FsText load()
+	{
+		while (!in[0].done || !in[1].done)
+			for (int f = 0; f < 2; ++f) {
+				FsInput &I = in[f];
+				if (I.done) continue;
+				const int64_t n = take(f, [&](int64_t bytes) { I.room(I.len + bytes, drv->st); return I.text.as<uint8_t>() + I.len; });
+				if (n > 0) I.len += n;
+			}
+		for (int f = 0; f < 2; ++f) { in[f].rd.reset(); text[f].release(); }
+		up.release();
+		return FsText{in[0].text.as<uint8_t>(), in[1].text.as<uint8_t>(), in[0].len, in[1].len};
+	}
 };
 
-// arx_fastq_sort_ex with run_bytes != 0 -> ARX_*; err: the text
-inline int fx_sort_files(int device, const char *const in_path[2], const char *const out_path[2], int flags, int64_t max_bytes, int64_t run_bytes, const char *tmp_dir, int64_t *stats,
-                         std::string &err, std::shared_ptr<DeviceBgzf> (*get_z)(int))
+// arx_fastq_sort.  What is refused is thrown: FsIoError, FsTooLarge
+inline void fs_sort_files(int device, const char *const in_path[2], const char *const out_path[2], int flags, int64_t max_bytes, int64_t *stats, std::shared_ptr<DeviceBgzf> (*get_z)(int))
 {
 	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
 	FsInput in[2];
-	for (int f = 0; f < 2; ++f)
-		if (!in[f].open(in_path[f])) { err = std::string("cannot read ") + in_path[f]; return ARX_E_IO; }
+	fs_open_inputs(in, in_path);
+	FsFileSink sink;
+	sink.bgzf = (flags & ARX_FQSORT_BGZF) != 0;
+	if (!check) sink.open(out_path);
+	select_device(device, FS_NO_DEVICE);
+	Stream st; // the call's own; declared before the buffers, so that it has ended when they are freed
+	st.create();
+	FsHipDrv drv; drv.st = st; drv.timed = (flags & ARX_FQSORT_TIMED) != 0;
+	FxFileSrc src;
+	src.start(in, in_path, drv, max_bytes, FS_REMEDY);
+	const FsText T = src.load();
+	FsCounts c{};
+	FsSortMem m{};
+	if (!check) sink.begin(st, device, get_z);
+	fs_run(drv, T, FS_WINDOW_DEFAULT, FS_SLAB_DEFAULT, check ? nullptr : &sink, c, m);
+	if (!check) sink.end(drv);
+	fs_stats(stats, drv, c, T.n1, T.n2, !check);
+}
+
+// arx_fastq_sort_ex with run_bytes != 0
+inline void fx_sort_files(int device, const char *const in_path[2], const char *const out_path[2], int flags, int64_t max_bytes, int64_t run_bytes, const char *tmp_dir, int64_t *stats,
+                          std::shared_ptr<DeviceBgzf> (*get_z)(int))
+{
+	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
+	FsInput in[2];
+	fs_open_inputs(in, in_path);
 	FsFileSink sink;
 	sink.bgzf = (flags & ARX_FQSORT_BGZF) != 0;
 	FxFileStore store;
 	if (!check) {
-		for (int f = 0; f < 2; ++f)
-			if (!sink.file[f].open(out_path[f])) { err = std::string("cannot write ") + sink.file[f].tmp; return ARX_E_IO; }
-		std::string dir = tmp_dir ? tmp_dir : out_path[0];
-		if (!tmp_dir) { const size_t cut = dir.rfind('/'); dir = cut == std::string::npos ? "." : cut == 0 ? "/" : dir.substr(0, cut); }
-		for (int f = 0; f < 2; ++f)
-			if (!store.file[f].create(dir, f ? ".r2" : ".r1")) { err = "cannot write a temporary file under " + dir; return ARX_E_IO; }
+		sink.open(out_path);
+		store.create(tmp_dir, out_path[0]);
 	}
 	select_device(device, FS_NO_DEVICE);
 	Stream st; // the call's own; declared before the buffers, so that it has ended when they are freed
@@ -709,20 +747,12 @@ inline int fx_sort_files(int device, const char *const in_path[2], const char *c
 	FxRuns S;
 	FxIo io;
 	FxFileSrc src;
-	src.in = in; src.path = in_path; src.drv = &drv; src.max_bytes = max_bytes;
-	for (int f = 0; f < 2; ++f) in[f].rd->start();
-	if (!check) {
-		sink.init(st);
-		if (sink.bgzf) sink.z = get_z(device);
-	}
+	src.start(in, in_path, drv, max_bytes);
+	if (!check) sink.begin(st, device, get_z);
 	fx_run(drv, src, check ? nullptr : &store, check ? nullptr : &sink, rb, rb < FS_WINDOW_DEFAULT ? rb : FS_WINDOW_DEFAULT, FS_SLAB_DEFAULT, c, m, S, io);
 	for (int f = 0; f < 2; ++f) in[f].rd.reset();
-	if (!check) {
-		sink.finish();
-		drv.us[FS_T_COMPRESS] = sink.us_compress; drv.us[FS_T_WRITE] = sink.us_write;
-	}
+	if (!check) sink.end(drv);
 	fx_stats(stats, drv, c, src.total[0], src.total[1], !check, S, io);
-	return ARX_OK;
 }
 
 } // namespace arx

@@ -4,9 +4,10 @@
 //
 // Everything it runs on is the sort's (hip_fqsort.h): k_fs_items<F> starts one item of a functor per thread through hip_launch under the
 // functor's name (fqs_match, fqs_fields, fqs_compose beside the feeder's fq_* and fs_window), FsHipDrv supplies scans, reductions and work
-// buffers, FsInput / FxFileSrc bring the files in slab by slab (a BGZF file inflated on the device by inflate_launch, anything else through zlib
-// on a reader thread), FsFileSink takes the output slabs from two pairs of buffers -- slab k is fetched and written, or compressed
-// (DeviceBgzf::run_device) and written, while slab k + 1 is composed -- into <out>.tmp, renamed at the end and removed otherwise.
+// buffers, FqsFiles (fs_open_inputs and an FxFileSrc) brings the files in slab by slab (a BGZF file inflated on the device by inflate_launch,
+// anything else through zlib on a reader thread), FsFileSink (open / begin / end) takes the output slabs from two pairs of buffers -- slab k is
+// fetched and written, or compressed (DeviceBgzf::run_device) and written, while slab k + 1 is composed -- into <out>.tmp, renamed at the end
+// and removed otherwise.  fqs_detect_files and fqs_detect_mem are the detection of every call that has one, arx_fastq_prepare's included.
 //
 // The call streams.  Device memory of a call, whatever the files' sizes: four window buffers (FS_WINDOW_DEFAULT each: two per file, the carry
 // moves from one to the other), the readers' slab text per file (32 MiB each), the line index of a window (about a window's size again), 88 bytes
@@ -70,32 +71,43 @@ inline void fqs_throw(int rc, int64_t window)
 struct FqsFiles {
 	FsInput in[2];
 	FxFileSrc src;
-	bool open(const char *const path[2], FsHipDrv &drv, std::string &err, size_t chunk = FS_READ_CHUNK)
+	void open(const char *const path[2], FsHipDrv &drv, size_t chunk = FS_READ_CHUNK, int64_t max_bytes = 0)
 	{
-		for (int f = 0; f < 2; ++f) { // FsInput::open with the chunk size of the caller's choice
-			FsInput &I = in[f];
-			I.bgzf = file_is_bgzf(path[f]);
-			bool ok = false;
-			if (I.bgzf) { std::unique_ptr<BgzfChunkReader> r(new BgzfChunkReader()); ok = r->open(path[f], chunk, FS_READ_CHUNKS); I.rd = std::move(r); }
-			else { std::unique_ptr<ChunkReader> r(new ChunkReader()); ok = r->open(path[f], chunk, FS_READ_CHUNKS); I.rd = std::move(r); }
-			if (!ok) { err = std::string("cannot read ") + path[f]; return false; }
-		}
-		src.in = in; src.path = path; src.drv = &drv; src.max_bytes = 0;
-		for (int f = 0; f < 2; ++f) in[f].rd->start();
-		return true;
+		fs_open_inputs(in, path, chunk);
+		src.start(in, path, drv, max_bytes);
 	}
 };
 
-// -> ARX_*; err: the text.  get_z: the device's compressor (arx_bgzf.hip keeps one per device)
-inline int fqs_files(int device, const char *const in_path[2], const char *const out_path[2], int format, int flags, int64_t *stats, std::string &err,
-                     std::shared_ptr<DeviceBgzf> (*get_z)(int))
+// the format of a file pair from its head: FQS_DETECT_WINDOW of each file first, through readers with small slabs, a whole window only where a
+// record does not fit that.  Drv: FqsHipDrv, or one with an empty phase() whose pass_done() only waits
+template <class Drv> void fqs_detect_files(Drv &drv, const char *const in_path[2], FqsCounts &d)
+{
+	for (const int64_t window : {FQS_DETECT_WINDOW, FS_WINDOW_DEFAULT}) {
+		FqsFiles files;
+		files.open(in_path, drv, window == FQS_DETECT_WINDOW ? FQS_DETECT_CHUNK : FS_READ_CHUNK);
+		d = FqsCounts();
+		const int rc = fqs_detect(drv, files.src, window, d);
+		drv.pass_done();
+		if (rc == FS_E_TOO_LARGE && window != FS_WINDOW_DEFAULT) continue; // a record of the head does not fit the small window
+		fqs_throw(rc, window);
+		break;
+	}
+}
+// the same of two texts in host memory (the self-tests')
+template <class Drv> void fqs_detect_mem(Drv &drv, const uint8_t *t1, int64_t n1, const uint8_t *t2, int64_t n2, int64_t window, FqsCounts &d)
+{
+	FxMemSrc src(drv.st, t1, n1, t2, n2);
+	const int rc = fqs_detect(drv, src, window, d);
+	drv.pass_done();
+	fqs_throw(rc, window);
+}
+inline std::string fqs_no_format() { return "no record of the first " + std::to_string(FQS_DETECT_RECORDS) + " names a format (standard, haplotagging, stLFR, TELLseq): pass the format"; }
+
+// arx_fastq_standardize.  What is refused is thrown: FsIoError, FsTooLarge, FsBadArg
+inline void fqs_files(int device, const char *const in_path[2], const char *const out_path[2], int format, int flags, int64_t *stats, std::shared_ptr<DeviceBgzf> (*get_z)(int))
 {
 	const bool detect_only = (flags & ARX_FQSTD_DETECT) != 0;
-	for (int f = 0; f < 2; ++f) { // a missing input is refused before the device is touched
-		FILE *p = fopen(in_path[f], "rb");
-		if (!p) { err = std::string("cannot read ") + in_path[f]; return ARX_E_IO; }
-		fclose(p);
-	}
+	fs_probe_inputs(in_path);
 	select_device(device, FQS_NO_DEVICE);
 	Stream st; // the call's own; declared before the buffers, so that it has ended when they are freed
 	st.create();
@@ -104,44 +116,31 @@ inline int fqs_files(int device, const char *const in_path[2], const char *const
 	int64_t decided = -1;
 	if (format == FQS_AUTO || detect_only) {
 		FqsCounts d;
-		for (const int64_t window : {FQS_DETECT_WINDOW, FS_WINDOW_DEFAULT}) {
-			FqsFiles files;
-			if (!files.open(in_path, drv, err, window == FQS_DETECT_WINDOW ? FQS_DETECT_CHUNK : FS_READ_CHUNK)) return ARX_E_IO;
-			d = FqsCounts();
-			const int rc = fqs_detect(drv, files.src, window, d);
-			drv.pass_done();
-			if (rc == FS_E_TOO_LARGE && window != FS_WINDOW_DEFAULT) continue; // a record of the head does not fit the small window
-			fqs_throw(rc, window);
-			break;
-		}
+		fqs_detect_files(drv, in_path, d);
 		fmt = d.format; decided = d.decided;
 		if (detect_only || fmt == FQS_STANDARD) {
 			d.n_records = 0; // nothing was written
 			fqs_stats(stats, drv, d, fmt, decided, 0, 0, 0);
-			return ARX_OK;
+			return;
 		}
 		if (fmt == FQS_UNKNOWN) {
 			if (stats) { stats[6] = fmt; stats[7] = -1; }
-			err = "no record of the first " + std::to_string(FQS_DETECT_RECORDS) + " names a format (standard, haplotagging, stLFR, TELLseq): pass the format";
-			return ARX_E_ARG;
+			throw FsBadArg(fqs_no_format());
 		}
 	}
 	FqsFiles files;
-	if (!files.open(in_path, drv, err)) return ARX_E_IO;
+	files.open(in_path, drv);
 	FsFileSink sink;
 	sink.bgzf = (flags & ARX_FQSTD_BGZF) != 0;
-	for (int f = 0; f < 2; ++f)
-		if (!sink.file[f].open(out_path[f])) { err = std::string("cannot write ") + sink.file[f].tmp; sink.file[f].tmp.clear(); return ARX_E_IO; }
-	sink.init(st);
-	if (sink.bgzf) sink.z = get_z(device);
+	sink.open(out_path);
+	sink.begin(st, device, get_z);
 	FqsCounts c;
 	const int rc = fqs_convert(drv, files.src, fmt, FS_WINDOW_DEFAULT, FS_SLAB_DEFAULT, sink, c);
 	fqs_throw(rc, FS_WINDOW_DEFAULT);
 	drv.phase(FQS_P_FILL); // the last blocks and the rename are the sink's own time
-	sink.finish();
+	sink.end(drv);
 	drv.pass_done();
 	fqs_stats(stats, drv, c, fmt, decided, sink.us_consume, sink.us_compress, sink.us_write);
-	return ARX_OK;
 }
 
 } // namespace arx
