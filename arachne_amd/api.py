@@ -152,6 +152,8 @@ _SELFTEST_ARGS = {
                              C.c_int64, C.c_int32],
     "arx_selftest_post": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                           C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32],
+    "arx_selftest_ext_stage": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 9 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_int32, C.c_int32],
     # the device BAM sink: bound when first used, for the same reason
     "arx_bam_open_device": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
     "arx_bam_write_encoded_device": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64],
@@ -818,6 +820,45 @@ def selftest_post(ref, batch, cand_off, cands, seqs, lens, bc_pair_off, penalty:
         raise e
     return dict(post=post, split=split, mm_ref=mm_ref[:n_mm.value].copy(), mm_read=mm_read[:n_mm.value].copy(),
                 table=None if table is None else table[:n_table.value].copy(), home=home if census else None)
+
+
+EXT_ROUND_W = 9   # csrc/selftest_ext.h: round number, chains still active after it, tasks queued per query-length class (7)
+
+
+def selftest_ext_stage(ref, seqs, lens, n_chain, chains, n_seed, seeds, frac_rep_bits, grid_cap: int = 0, order: int = 0):
+    """The extension stage on given chains (include/arachne_amd.h: arx_selftest_ext_stage), on a runtime of its own with ref's index and the ARX_*
+    switches as they are now.  seqs: the reads back to back (codes 0..4); n_chain / n_seed: chains and seeds per read; chains (8 columns) and seeds
+    (4 columns): the restatement's int64 rows, read after read, seed_off counting within the read; frac_rep_bits: one value per read
+    -> dict(ext_off, ext_regs (20-column rows: the regions after the gather), core_off, core_regs, core_clean (what the de-duplication leaves),
+    n_ext_tasks, ext_rounds, rounds (n x EXT_ROUND_W), done_round, n_regs (per chain), err).  grid_cap > 0: every launch on at most that many
+    workgroups; order: the host double's item order (0, 1, 2), which the library ignores."""
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    flat = np.ascontiguousarray(seqs, dtype=np.uint8).reshape(-1)
+    n_chain, n_seed = np.ascontiguousarray(n_chain, dtype=np.int32), np.ascontiguousarray(n_seed, dtype=np.int32)
+    chains = np.ascontiguousarray(chains, dtype=np.int64).reshape(-1, 8)
+    seeds = np.ascontiguousarray(seeds, dtype=np.int64).reshape(-1, 4)
+    frb = np.ascontiguousarray(frac_rep_bits, dtype=np.uint32)
+    R = len(lens)
+    if int(lens.sum()) != len(flat) or len(n_chain) != R or len(n_seed) != R or len(frb) != R or len(chains) != int(n_chain.sum()) or len(seeds) != int(n_seed.sum()):
+        raise ValueError("reads, chain rows and seed rows do not match")
+    cap = len(seeds) + 1
+    ext_off, core_off = np.zeros(R + 1, dtype=np.int32), np.zeros(R + 1, dtype=np.int32)
+    ext_regs, core_regs = np.zeros((cap, 20), dtype=np.int64), np.zeros((cap, 20), dtype=np.int64)
+    clean, stats = np.zeros(R, dtype=np.int32), np.zeros(4, dtype=np.int64)
+    rounds_cap = 4 * len(seeds) + len(chains) + 16                  # every round retires a DP or a chain
+    rounds = np.zeros((rounds_cap, EXT_ROUND_W), dtype=np.int32)
+    done, nreg, err = np.zeros(len(chains) + 1, dtype=np.int32), np.zeros(len(chains) + 1, dtype=np.int32), C.c_uint32(0)
+    rc = _selftest_fn(ref.lib, "arx_selftest_ext_stage")(ref.h, flat.ctypes.data, lens.ctypes.data, R, n_chain.ctypes.data, chains.ctypes.data, n_seed.ctypes.data,
+                                                         seeds.ctypes.data, frb.ctypes.data, ext_off.ctypes.data, ext_regs.ctypes.data, core_off.ctypes.data,
+                                                         core_regs.ctypes.data, cap, clean.ctypes.data, stats.ctypes.data, rounds.ctypes.data, rounds_cap,
+                                                         done.ctypes.data, nreg.ctypes.data, C.byref(err), int(grid_cap), int(order))
+    if rc != 0:
+        e = ArachneError("arx_selftest_ext_stage: code %d" % rc)
+        e.code = rc
+        raise e
+    return dict(ext_off=ext_off, ext_regs=ext_regs[:int(ext_off[-1])].copy(), core_off=core_off, core_regs=core_regs[:int(core_off[-1])].copy(), core_clean=clean,
+                n_ext_tasks=int(stats[0]), ext_rounds=int(stats[1]), rounds=rounds[:int(stats[2])].copy(), done_round=done[:len(chains)].copy(),
+                n_regs=nreg[:len(chains)].copy(), err=int(err.value))
 
 
 class _RecordsLayout(C.Structure):

@@ -8,6 +8,8 @@
 // that takes what they hand on, the one-thread path and compact() -- on regions the caller made up (tests/test_cigar_stage_gpu.py).
 // arx_selftest_post (selftest_post.h) runs PostStage::run -- the CIGAR walk, the duplicate table, the split pass -- on candidates the caller made up
 // (tests/test_post_stage_gpu.py).
+// arx_selftest_ext_stage (selftest_ext.h) runs stage 4 itself -- Pipeline::stage_extend with its chain state machines, the round loop, run_extend,
+// the gather and the de-duplication -- on chains and seeds the caller made up (tests/test_ext_stage_gpu.py).
 // Its own unit so that the unit of the list-bookkeeping kernels does not grow.
 #include <climits>
 #include <vector>
@@ -18,6 +20,7 @@
 #include "selftest_rfa.h"
 #include "selftest_reg2aln.h"
 #include "selftest_post.h"
+#include "selftest_ext.h"
 
 namespace arx {
 
@@ -114,7 +117,7 @@ extern "C" int arx_selftest_extend(int32_t device, const uint8_t *pac, int64_t l
 		if (qlen < 1 || qlen > MAX_READ_LEN || (qdir != 1 && qdir != -1) || (tdir != 1 && tdir != -1)) return ARX_E_ARG;
 		const int64_t qlast = qoff + (qlen - 1) * qdir;
 		if (qoff < 0 || qoff >= n_bases || qlast < 0 || qlast >= n_bases) return ARX_E_ARG;
-		if (tlen < 1 || tlen > 2 * l_pac || !one_strand(tpos, tpos + (tlen - 1) * tdir, l_pac)) return ARX_E_ARG;
+		if (tlen < 0 || tlen > 2 * l_pac || (tlen > 0 && !one_strand(tpos, tpos + (tlen - 1) * tdir, l_pac))) return ARX_E_ARG; // tlen == 0: a window that ends at the seed (a contig's edge)
 		if (w < 1 || w > INT_MAX || h0 < 1 || h0 > MAX_READ_LEN * OPT_A) return ARX_E_ARG;
 		ExtTask t;
 		t.tpos = tpos; t.owner = i; t.qoff = (int32_t)qoff; t.qlen = (int32_t)qlen; t.tlen = (int32_t)tlen;
@@ -399,6 +402,28 @@ extern "C" int arx_selftest_post(arx_ctx *ctx, int32_t n_reads, const int64_t *c
 		if (grid_cap > 0) { rt.n_cu = 1; rt.sw.bpc = grid_cap; rt.sw.wide = false; } // launch_wide's capped form on grid_cap workgroups: every lane strides through many items
 		return selftest_post_run(rt, *ix, n_reads, cand_off, cands, n_regs, regs, alns, cigars, n_cig, bases, lens, n_barcodes, bc_pair_off, penalty, cen_start, cen_end,
 		                         post, split, mm_ref, mm_read, mm_cap, n_mm, table, table_cap, n_table, home);
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+}
+
+// Stage 4 on the caller's chains: Pipeline::stage_extend on a runtime of its own, with ctx's index and the ARX_* switches as they are at the call.
+// (order: the host double's item order; a GPU's arrival order is not ours to choose)
+extern "C" int arx_selftest_ext_stage(arx_ctx *ctx, const uint8_t *bases, const int32_t *lens, int32_t n_reads, const int32_t *n_chain, const int64_t *chains, const int32_t *n_seed,
+                                      const int64_t *seeds, const uint32_t *frac_rep_bits, int32_t *ext_off, int64_t *ext_regs, int32_t *core_off, int64_t *core_regs,
+                                      int64_t reg_cap, int32_t *core_clean, int64_t *stats, int32_t *rounds, int64_t rounds_cap, int32_t *done_round, int32_t *chain_n_regs,
+                                      uint32_t *err, int32_t grid_cap, int32_t)
+{
+	using namespace arx;
+	const IndexView *ix = ctx_index_view(ctx);
+	if (!ix) return ARX_E_ARG;
+	try {
+		HipRT rt;
+		if (!rt.init(arx_ctx_device(ctx)).empty()) return ARX_E_DEVICE;
+		rt.timing = false;
+		if (grid_cap > 0) { rt.n_cu = 1; rt.sw.bpc = grid_cap; rt.sw.coop_bpc = grid_cap; rt.sw.wide = false; } // every launch of the stage on grid_cap workgroups: every lane strides through many items
+		return selftest_ext_run(rt, *ix, bases, lens, n_reads, n_chain, chains, n_seed, seeds, frac_rep_bits, ext_off, ext_regs, core_off, core_regs, reg_cap, core_clean, stats,
+		                        rounds, rounds_cap, done_round, chain_n_regs, err);
 	} catch (const std::exception &) {
 		return ARX_E_DEVICE;
 	}

@@ -289,6 +289,15 @@ struct Reg2AlnCensus {
 template <class R, class = void> struct HasNwPunts { static constexpr bool value = false; };
 template <class R> struct HasNwPunts<R, decltype((void)std::declval<R &>().nw_punts())> { static constexpr bool value = true; };
 
+// opt-in census of stage 4 (arx_selftest_ext_stage; Pipeline::ext_census): what the stage leaves in device memory anyway, copied home before the
+// de-duplication overwrites it in place.  Off (the default) nothing is copied and the stage issues the launches and copies it always did
+struct ExtCensus {
+	std::vector<int32_t> n_ext;              // per read: regions after ext_gather
+	std::vector<Reg> regs;                   // the gathered regions, T slots: read r's at occ_off[r]
+	std::vector<int32_t> rounds;             // per round: round number, chains still active after it, tasks per length class (2 + EXT_CLASSES numbers)
+	std::vector<int32_t> done_round, n_regs; // per chain, at the end
+};
+
 struct KChainMid { // the listed reads of KChain, one thread each; the list's length stays on the device
 	KChain f;
 	ARX_DEV void operator()(int i, int) const { const int n = *f.n_mid < f.mid_cap ? *f.n_mid : f.mid_cap; if (i < n) f.one(f.mid_list[i]); }
@@ -560,6 +569,7 @@ public:
 	explicit Pipeline(RT &rt_, const IndexView &ix_) : rt(rt_), ix(ix_) {}
 	Pipeline(RT &rt_, const IndexView &ix_, const PipelineSwitches &sw_) : rt(rt_), ix(ix_), sw(sw_) {} // the self-tests: switches from arguments, not the environment
 	Reg2AlnCensus *reg2aln_census = nullptr; // where stage_reg2aln reports (null: no census)
+	ExtCensus *ext_census = nullptr;         // where stage_extend reports (null: no census)
 
 	// device-resident input of one batch; the buffers are kept by the handle and reused by arx_batch_reset (cap_*: what they hold)
 	struct DeviceBatch { uint8_t *bases = 0; int32_t *base_off = 0, *lens = 0; int n_reads = 0; int64_t n_bases = 0; int max_len = 0; int64_t cap_bases = 0; int cap_reads = 0; };
@@ -792,6 +802,7 @@ public:
 			int nt = 0;
 			for (int c = 0; c < EXT_CLASSES; ++c) nt += cnt[c];
 			if (sw.trace) { fprintf(stderr, "[arx] ext round %d: %d chains active, %d DPs\n", round, n_act, nt); fflush(stderr); }
+			if (ext_census) { ext_census->rounds.push_back(round); ext_census->rounds.push_back(n_act); for (int c = 0; c < EXT_CLASSES; ++c) ext_census->rounds.push_back(cnt[c]); }
 			if (round > w.T + R + 8) { uint32_t e = ERR_INTERNAL; rt.h2d(w.err, &e, 4); break; } // cannot happen: every round retires a DP or a chain
 			if (nt == 0) continue;
 			out.n_ext_tasks += nt; ++out.ext_rounds;
@@ -800,6 +811,16 @@ public:
 		}
 		KExtGather kg{w.occ_off, w.n_chain, chain_off, w.cout, est, pool, w.regs, n_ext};
 		rt.launch_wide("ext_gather", R, kg);
+		if (ext_census) {
+			ExtCensus &c = *ext_census;
+			c.n_ext.resize((size_t)R); c.regs.resize((size_t)w.T); c.done_round.resize((size_t)NCH); c.n_regs.resize((size_t)NCH);
+			rt.sync();
+			rt.d2h(c.n_ext.data(), n_ext, 4 * (size_t)R);
+			rt.d2h(c.regs.data(), w.regs, sizeof(Reg) * (size_t)w.T);
+			std::vector<ExtState> st((size_t)NCH);
+			rt.d2h(st.data(), est, sizeof(ExtState) * (size_t)NCH);
+			for (int g = 0; g < NCH; ++g) { c.done_round[(size_t)g] = st[(size_t)g].done_round; c.n_regs[(size_t)g] = st[(size_t)g].n_regs; }
+		}
 		if (sw.trace) { fprintf(stderr, "[arx] dedup\n"); fflush(stderr); }
 		KDedup kd{ix, b.bases, b.base_off, b.lens, w.occ_off, n_ext, w.regs, rtmp, idx, eh, eh_words, w.n_core, w.core_clean, nullptr, nullptr,
 		          sw.dedup_heavy_min.value_or(DEDUP_HEAVY_MIN)};

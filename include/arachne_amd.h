@@ -804,6 +804,26 @@ int arx_selftest_post(arx_ctx *ctx, int32_t n_reads, const int64_t *cand_off, co
                       int32_t penalty, const int64_t *cen_start, const int64_t *cen_end, void *post, void *split, int32_t *mm_ref, int32_t *mm_read,
                       int64_t mm_cap, int64_t *n_mm, int32_t *table, int64_t table_cap, int32_t *n_table, int32_t *home, int32_t grid_cap, int32_t order);
 
+/* self-test of the extension stage (what arx_batch_run runs between chaining and mate rescue: one state machine per chain, the rounds of
+ * ext_step / run_extend, the gather in chain order, mem_sort_dedup_patch) on chains and seeds the caller made up, in the int64 row layouts of the CPU
+ * restatement (oracle/arx_oracle.h; ora_chain2aln takes the same rows): chains holds sum(n_chain) rows of 8 columns (pos rid n seed_off w kept first
+ * is_alt), read after read, seed_off counting within the read's seed rows; seeds holds sum(n_seed) rows of 4 columns (rbeg qbeg len score);
+ * frac_rep_bits: one value per read (mem_chain gives every chain of a read the same); bases: the reads back to back (codes 0..4).  The stage runs on
+ * a runtime of its own with ctx's index and the ARX_* switches as they are at the call.
+ * Checked before anything is uploaded (ARX_E_ARG), what mem_chain2aln's assert(c->rid == rid) and its fetches accept: 1 <= lens <= 255; every seed of
+ * a chain in one contig and strand, rid that contig; 0 <= qbeg, qbeg + len <= lens, len >= 1, score == len; the chains' seed rows follow each other
+ * inside the read's; at most 2^22 chain and seed slots.  A chain may be empty (n == 0), a read may have no chain.
+ * Out: ext_off[n_reads + 1] and ext_regs: the regions after the gather, before the de-duplication (rows of 20 columns as the restatement's, frac_rep as
+ * its bits); core_off[n_reads + 1], core_regs, core_clean[n_reads]: the lists the stage leaves (reg_cap rows each; sum(n_seed) suffice, ARX_E_TOO_LARGE
+ * below that); stats: [0] n_ext_tasks [1] ext_rounds [2] rounds of the loop [3] chains; rounds (rounds_cap rows of 9: round number, chains still
+ * active after it, tasks queued per query-length class); done_round and chain_n_regs per chain; *err: the batch's error word.
+ * grid_cap > 0: every launch of the stage on at most that many workgroups; 0: the launch shapes of arx_batch_run.  order: the item order of the host
+ * test double's launches (0 ascending, 1 descending, 2 a stride permutation); the library ignores it. */
+int arx_selftest_ext_stage(arx_ctx *ctx, const uint8_t *bases, const int32_t *lens, int32_t n_reads, const int32_t *n_chain, const int64_t *chains, const int32_t *n_seed,
+                           const int64_t *seeds, const uint32_t *frac_rep_bits, int32_t *ext_off, int64_t *ext_regs, int32_t *core_off, int64_t *core_regs,
+                           int64_t reg_cap, int32_t *core_clean, int64_t *stats, int32_t *rounds, int64_t rounds_cap, int32_t *done_round, int32_t *chain_n_regs,
+                           uint32_t *err, int32_t grid_cap, int32_t order);
+
 /* self-tests of the three DP kernel families on plain host arrays (csrc/arx_selftest.hip; tests/test_dp_kernels_gpu.py): each entry
  * uploads the tasks, launches the production code on them and returns one result row per task, in input order.  The reference text is
  * passed in bwa's .pac layout (pac: (l_pac + 3) / 4 bytes, 2 bits per base, first base in the top bits); coordinates are doubled, so a
@@ -812,7 +832,8 @@ int arx_selftest_post(arx_ctx *ctx, int32_t n_reads, const int64_t *cand_off, co
  *
  * arx_selftest_extend: ksw_extend2 (end bonus 5, z-drop 100) by HipRT::run_extend.  task8: n rows of (tpos, qoff, qlen, tlen, qdir, tdir,
  * w, h0); the query base j is bases[qoff + j * qdir], the target base i is at doubled coordinate tpos + i * tdir.  Contract: 1 <= qlen <= 255,
- * qdir, tdir = +1 / -1, the query inside bases[0, n_bases), tlen >= 1 with the whole target on one strand of [0, 2 * l_pac), w >= 1,
+ * qdir, tdir = +1 / -1, the query inside bases[0, n_bases), tlen >= 0 with the whole target on one strand of [0, 2 * l_pac) (tlen == 0: the window
+ * ends where the seed does, at a contig's edge; no target base is read and tpos may be any value), w >= 1,
  * 1 <= h0 <= 255.  mode 0: one launch per query-length class, 1: all classes in one launch, 2: round 2's kernel (per class), 3: the
  * one-thread form.  grid_cap > 0: at most that many workgroups per launch (the grid-stride loops then take several tasks per group).
  * res6: n rows of (score, qle, tle, gtle, gscore, max_off).

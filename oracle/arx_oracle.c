@@ -1520,6 +1520,26 @@ static inline int cal_max_gap(int qlen)
 
 static int u64_lt(const void *ctx, int a, int b) { const uint64_t *v = (const uint64_t*)ctx; return v[a] < v[b]; }
 
+/* ora_chain2aln: where chain2aln writes its ksw_extend2 calls and the chain's shape row (null: nowhere).  Counts only: nothing chain2aln
+ * computes depends on them */
+typedef struct { int64_t *calls; int cap_calls, n_calls, chain; int64_t *shape; } c2a_trace_t;
+static __thread c2a_trace_t *g_c2a;
+static void c2a_call(int seed, int side, int qlen, int tlen, int w, int h0, int score, int qle, int tle, int gtle, int gscore, int max_off, int band_try)
+{
+	c2a_trace_t *t = g_c2a;
+	if (t == 0) return;
+	if (t->n_calls < t->cap_calls) {
+		int64_t *r = t->calls + (size_t)ORA_C2A_CALL_W * t->n_calls;
+		r[0] = t->chain; r[1] = seed; r[2] = side; r[3] = qlen; r[4] = tlen; r[5] = w; r[6] = h0;
+		r[7] = score; r[8] = qle; r[9] = tle; r[10] = gtle; r[11] = gscore; r[12] = max_off;
+	}
+	++t->n_calls;
+	++t->shape[3 + side];
+	if (band_try > 0) ++t->shape[5 + side];
+	if (tlen == 0) ++t->shape[9];
+	else if (tlen < qlen) ++t->shape[10];
+}
+
 /* ref: bwamem.c:632-786 (mem_chain2aln) */
 static void chain2aln(const index_t *ix, int l_query, const uint8_t *query, const chain_t *c, regvec_t *av, ora_counters_t *cnt)
 {
@@ -1540,13 +1560,19 @@ static void chain2aln(const index_t *ix, int l_query, const uint8_t *query, cons
 		rmax[1] = rmax[1] > e? rmax[1] : e;
 		if (t->len > max) max = t->len;
 	}
+	if (g_c2a) g_c2a->shape[13] = (rmax[0] < 0? 1 : 0) | (rmax[1] > l_pac << 1? 4 : 0);
 	rmax[0] = rmax[0] > 0? rmax[0] : 0;
 	rmax[1] = rmax[1] < l_pac << 1? rmax[1] : l_pac << 1;
 	if (rmax[0] < l_pac && l_pac < rmax[1]) {
 		if (c->seeds[0].rbeg < l_pac) rmax[1] = l_pac;
 		else rmax[0] = l_pac;
+		if (g_c2a) g_c2a->shape[13] |= 2;
 	}
-	rseq = fetch_seq(ix, &rmax[0], c->seeds[0].rbeg, &rmax[1], &rid);
+	{
+		const int64_t b0 = rmax[0], e0 = rmax[1];
+		rseq = fetch_seq(ix, &rmax[0], c->seeds[0].rbeg, &rmax[1], &rid);
+		if (g_c2a) { if (rmax[0] != b0 || rmax[1] != e0) g_c2a->shape[13] |= 8; g_c2a->shape[11] = rmax[0]; g_c2a->shape[12] = rmax[1]; }
+	}
 	/* seeds are visited by score, highest first (keys score<<32|index are unique, so any sort agrees) */
 	srt = (uint64_t*)malloc(c->n * 8); order = (int*)malloc(c->n * sizeof(int));
 	for (i = 0; i < c->n; ++i) { srt[i] = (uint64_t)c->seeds[i].score << 32 | i; order[i] = i; }
@@ -1580,9 +1606,11 @@ static void chain2aln(const index_t *ix, int l_query, const uint8_t *query, cons
 				if (s->qbeg <= t->qbeg && s->qbeg + s->len - t->qbeg >= s->len >> 2 && t->qbeg - s->qbeg != t->rbeg - s->rbeg) break;
 				if (t->qbeg <= s->qbeg && t->qbeg + t->len - s->qbeg >= s->len >> 2 && s->qbeg - t->qbeg != s->rbeg - t->rbeg) break;
 			}
-			if (i == c->n) { srt[k] = 0; continue; }
+			if (i == c->n) { srt[k] = 0; if (g_c2a) ++g_c2a->shape[1]; continue; }
+			if (g_c2a) ++g_c2a->shape[2];
 		}
 		a = rv_pushp(av);
+		if (g_c2a) ++g_c2a->shape[0];
 		memset(a, 0, sizeof(reg_t));
 		a->w = aw[0] = aw[1] = OPT_W;
 		a->score = a->truesc = -1;
@@ -1599,10 +1627,11 @@ static void chain2aln(const index_t *ix, int l_query, const uint8_t *query, cons
 				int prev = a->score;
 				aw[0] = OPT_W << i;
 				a->score = ksw_extend2(s->qbeg, qs, (int)tmp, rs, aw[0], OPT_PEN_CLIP5, OPT_ZDROP, s->len * OPT_A, &qle, &tle, &gtle, &gscore, &max_off[0], cnt);
+				c2a_call((int)(s - c->seeds), 0, s->qbeg, (int)tmp, aw[0], s->len * OPT_A, a->score, qle, tle, gtle, gscore, max_off[0], i);
 				if (a->score == prev || max_off[0] < (aw[0] >> 1) + (aw[0] >> 2)) break;
 			}
 			if (gscore <= 0 || gscore <= a->score - OPT_PEN_CLIP5) { a->qb = s->qbeg - qle; a->rb = s->rbeg - tle; a->truesc = a->score; }
-			else { a->qb = 0; a->rb = s->rbeg - gtle; a->truesc = gscore; }
+			else { a->qb = 0; a->rb = s->rbeg - gtle; a->truesc = gscore; if (g_c2a) ++g_c2a->shape[7]; }
 			free(qs); free(rs);
 		} else { a->score = a->truesc = s->len * OPT_A; a->qb = 0; a->rb = s->rbeg; }
 		if (s->qbeg + s->len != l_query) { /* right extension */
@@ -1613,10 +1642,11 @@ static void chain2aln(const index_t *ix, int l_query, const uint8_t *query, cons
 				int prev = a->score;
 				aw[1] = OPT_W << i;
 				a->score = ksw_extend2(l_query - qe, query + qe, (int)(rmax[1] - rmax[0] - re), rseq + re, aw[1], OPT_PEN_CLIP3, OPT_ZDROP, sc0, &qle, &tle, &gtle, &gscore, &max_off[1], cnt);
+				c2a_call((int)(s - c->seeds), 1, l_query - qe, (int)(rmax[1] - rmax[0] - re), aw[1], sc0, a->score, qle, tle, gtle, gscore, max_off[1], i);
 				if (a->score == prev || max_off[1] < (aw[1] >> 1) + (aw[1] >> 2)) break;
 			}
 			if (gscore <= 0 || gscore <= a->score - OPT_PEN_CLIP3) { a->qe = qe + qle; a->re = rmax[0] + re + tle; a->truesc += a->score - sc0; }
-			else { a->qe = l_query; a->re = rmax[0] + re + gtle; a->truesc += gscore - sc0; }
+			else { a->qe = l_query; a->re = rmax[0] + re + gtle; a->truesc += gscore - sc0; if (g_c2a) ++g_c2a->shape[8]; }
 		} else { a->qe = l_query; a->re = s->rbeg + s->len; }
 		for (i = 0, a->seedcov = 0; i < c->n; ++i) {
 			const seed_t *t = &c->seeds[i];
@@ -1772,6 +1802,98 @@ int ora_align1(ora_ctx_t *c, int len, const uint8_t *seq, int64_t *regs, int cap
 	n = v.n;
 	for (i = 0; i < n && i < cap; ++i) put_reg(regs + (size_t)i * ORA_REG_W, &v.a[i]);
 	free(v.a); free(s);
+	return n;
+}
+
+static void get_reg(reg_t *p, const int64_t *r);
+
+/* rows as ora_chains hands them out -> chains; 0 where a row is not what mem_chain2aln accepts (arx_oracle.h: ora_chain2aln) */
+static chain_t *rows_to_chains(const index_t *ix, int l_query, int n_chains, const int64_t *chains, int n_seeds, const int64_t *seeds, uint32_t frac_rep_bits)
+{
+	chain_t *a;
+	int i, j;
+	if (l_query < 1 || n_chains < 0 || n_seeds < 0 || (n_chains > 0 && chains == 0) || (n_seeds > 0 && seeds == 0)) return 0;
+	for (i = 0; i < n_chains; ++i) {
+		const int64_t *r = chains + 8 * i;
+		int rev0 = 0;
+		if (r[2] < 0 || r[3] < 0 || r[3] + r[2] > n_seeds) return 0;
+		if (r[2] > 0 && (r[1] < 0 || r[1] >= ix->n_seqs)) return 0;
+		for (j = 0; j < r[2]; ++j) {
+			const int64_t *s = seeds + 4 * (r[3] + j);
+			int64_t b = s[0], e = s[0] + s[2], fb, fe;
+			int rev = b >= ix->l_pac;
+			if (s[2] < 1 || s[1] < 0 || s[1] + s[2] > l_query || s[3] != s[2]) return 0;
+			if (b < 0 || e > ix->l_pac << 1 || (b < ix->l_pac && e > ix->l_pac)) return 0;
+			if (j == 0) rev0 = rev; else if (rev != rev0) return 0;
+			fb = rev? (ix->l_pac << 1) - e : b; fe = rev? (ix->l_pac << 1) - b : e;
+			if (fb < ix->ann[r[1]].offset || fe > ix->ann[r[1]].offset + ix->ann[r[1]].len) return 0;
+		}
+	}
+	a = (chain_t*)calloc(n_chains + 1, sizeof(chain_t));
+	for (i = 0; i < n_chains; ++i) {
+		const int64_t *r = chains + 8 * i;
+		chain_t *p = &a[i];
+		p->pos = r[0]; p->rid = (int)r[1]; p->n = p->m = (int)r[2]; p->w = (int)r[4]; p->kept = (int)r[5]; p->first = (int)r[6]; p->is_alt = (int)r[7];
+		memcpy(&p->frac_rep, &frac_rep_bits, 4);
+		p->seeds = (seed_t*)calloc(p->n + 1, sizeof(seed_t));
+		for (j = 0; j < p->n; ++j) {
+			const int64_t *s = seeds + 4 * (r[3] + j);
+			p->seeds[j].rbeg = s[0]; p->seeds[j].qbeg = (int)s[1]; p->seeds[j].len = (int)s[2]; p->seeds[j].score = (int)s[3];
+		}
+	}
+	return a;
+}
+
+int ora_chain2aln(ora_ctx_t *c, int l_query, const uint8_t *query, int n_chains, const int64_t *chains, int n_seeds, const int64_t *seeds, uint32_t frac_rep_bits,
+                  int64_t *regs, int cap_r, int64_t *calls, int cap_calls, int *n_calls, int64_t *shapes)
+{
+	const index_t *ix = &c->ix;
+	chain_t *a;
+	regvec_t av = {0,0,0};
+	c2a_trace_t tr;
+	int64_t *sh;
+	int i, j, k, n;
+	if (query == 0 || n_calls == 0) return -1;
+	for (i = 0; i < l_query; ++i) if (query[i] > 4) return -1;
+	a = rows_to_chains(ix, l_query, n_chains, chains, n_seeds, seeds, frac_rep_bits);
+	if (a == 0) return -1;
+	sh = (int64_t*)calloc((size_t)ORA_C2A_SHAPE_W * (n_chains + 1), 8);
+	tr.calls = calls; tr.cap_calls = calls? cap_calls : 0; tr.n_calls = 0;
+	for (i = 0; i < n_chains; ++i) {
+		tr.chain = i; tr.shape = sh + (size_t)ORA_C2A_SHAPE_W * i;
+		tr.shape[15] = -1;
+		g_c2a = &tr;
+		chain2aln(ix, l_query, query, &a[i], &av, 0);
+		g_c2a = 0;
+		for (k = 0; k < i; ++k) { /* a seed of this chain inside an earlier chain's window: the product's chain waits for that chain */
+			const int64_t *w = sh + (size_t)ORA_C2A_SHAPE_W * k;
+			if (a[k].n == 0) continue;
+			for (j = 0; j < a[i].n; ++j) if (a[i].seeds[j].rbeg >= w[11] && a[i].seeds[j].rbeg + a[i].seeds[j].len <= w[12]) break;
+			if (j < a[i].n) { ++tr.shape[14]; tr.shape[15] = k; }
+		}
+	}
+	n = av.n;
+	for (i = 0; i < n && i < cap_r; ++i) put_reg(regs + (size_t)i * ORA_REG_W, &av.a[i]);
+	*n_calls = tr.n_calls;
+	if (shapes) memcpy(shapes, sh, (size_t)ORA_C2A_SHAPE_W * n_chains * 8);
+	for (i = 0; i < n_chains; ++i) free(a[i].seeds);
+	free(a); free(av.a); free(sh);
+	return n;
+}
+
+int ora_sort_dedup_patch(ora_ctx_t *c, int l_query, const uint8_t *query, int n, int64_t *regs)
+{
+	reg_t *a = (reg_t*)calloc(n + 1, sizeof(reg_t));
+	uint8_t *q = (uint8_t*)malloc(l_query + 1);
+	int i;
+	memcpy(q, query, l_query);
+	for (i = 0; i < n; ++i) get_reg(&a[i], regs + (size_t)i * ORA_REG_W);
+	n = sort_dedup_patch(&c->ix, q, n, a, 0);
+	for (i = 0; i < n; ++i) {
+		if (a[i].rid >= 0 && c->ix.ann[a[i].rid].is_alt) a[i].is_alt = 1;
+		put_reg(regs + (size_t)i * ORA_REG_W, &a[i]);
+	}
+	free(a); free(q);
 	return n;
 }
 

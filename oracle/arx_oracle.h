@@ -107,6 +107,25 @@ int64_t ora_fetch_seq(ora_ctx_t *c, int64_t *beg, int64_t mid, int64_t *end, int
 #define ORA_R2A_W 19
 int ora_reg2aln(ora_ctx_t *c, int l_query, const uint8_t *query, const int64_t *reg_row, int64_t *aln_row, uint32_t *cigar, int cap, int64_t *shape);
 
+/* mem_chain2aln (bwamem.c:632-786) over every chain of one read, in order, on chains the caller wrote: chain rows (8 int64) and seed rows (4 int64)
+ * as ora_chains hands them out, frac_rep as its bits.  mem_chain2aln is a pure function of its rows, the read and the index, so the seeds need not be
+ * what seeding would find.  Legal input is what the reference's assert(c->rid == rid) and its fetches accept: every seed of a chain in one contig and
+ * strand, rid that contig, 0 <= qbeg, qbeg + len <= l_query, len >= 1 (and score == len, as mem_chain sets it); anything else returns -1.
+ * regs: the regions after the last chain, BEFORE mem_sort_dedup_patch (returns their number; rows beyond cap_r are not stored).
+ * calls: one row of ORA_C2A_CALL_W numbers per ksw_extend2 call, in call order (*n_calls; rows beyond cap_calls are counted, not stored):
+ *  0 chain   1 seed (index within the chain)   2 side (0 left, 1 right)   3 qlen   4 tlen   5 w   6 h0   7 score   8 qle   9 tle   10 gtle   11 gscore   12 max_off.
+ * shapes (may be null): one row of ORA_C2A_SHAPE_W numbers per chain, from the same run:
+ *  0 regions appended   1 seeds skipped   2 seeds an earlier region explains but an overlapping off-diagonal seed keeps (bwamem.c:690-706)
+ *  3, 4 left, right DPs   5, 6 second-band tries, left, right   7, 8 to-end branches (gscore taken), left, right   9 calls with tlen == 0
+ *  10 calls with 0 < tlen < qlen   11, 12 the window [rmax0, rmax1)   13 what moved it, as bits: 1 the clamp at zero, 2 at l_pac, 4 at 2 * l_pac,
+ *  8 the contig's boundary   14 earlier non-empty chains whose window holds one of this chain's seeds   15 the last of them (-1: none). */
+#define ORA_C2A_CALL_W 13
+#define ORA_C2A_SHAPE_W 16
+int ora_chain2aln(ora_ctx_t *c, int l_query, const uint8_t *query, int n_chains, const int64_t *chains, int n_seeds, const int64_t *seeds, uint32_t frac_rep_bits,
+                  int64_t *regs, int cap_r, int64_t *calls, int cap_calls, int *n_calls, int64_t *shapes);
+/* mem_sort_dedup_patch (bwamem.c:437-489) and the is_alt marks of mem_align1_core on region rows, in place; returns the number left */
+int ora_sort_dedup_patch(ora_ctx_t *c, int l_query, const uint8_t *query, int n, int64_t *regs);
+
 /* the per-pair path */
 double ora_batch_run(ora_ctx_t *c, int64_t n_pairs, const uint8_t *seqs, const int32_t *lens, int score_delta, int n_threads);
 void ora_batch_get(ora_ctx_t *c, int64_t *n_reads, int64_t *n_regs, int64_t *n_cig, int64_t **reg_off, int64_t **regs, int64_t **alns, uint32_t **cigars);

@@ -216,6 +216,56 @@ int ref_align1(ref_ctx_t *c, int len, const uint8_t *seq, int64_t *regs, int cap
 	return n;
 }
 
+/* mem_chain2aln (bwamem.c:632) over every chain of one read, in order, on chain and seed rows as ref_chains hands them out; the regions
+ * after the last chain, before mem_sort_dedup_patch.  Returns their number, -1 for rows the reference's assert(c->rid == rid) and its
+ * fetches would not accept (the rule is stated at ora_chain2aln, oracle/arx_oracle.h) */
+int ref_chain2aln(ref_ctx_t *c, int l_query, const uint8_t *query, int n_chains, const int64_t *chains, int n_seeds, const int64_t *seeds, uint32_t frac_rep_bits,
+                  int64_t *regs, int cap_r)
+{
+	const bntseq_t *bns = c->idx->bns;
+	const int64_t L = bns->l_pac;
+	mem_alnreg_v av;
+	mem_seed_t *sd;
+	uint8_t *q;
+	int i, j, n;
+	if (l_query < 1 || query == 0 || n_chains < 0 || n_seeds < 0 || (n_chains > 0 && chains == 0) || (n_seeds > 0 && seeds == 0)) return -1;
+	for (i = 0; i < l_query; ++i) if (query[i] > 4) return -1;
+	for (i = 0; i < n_chains; ++i) {
+		const int64_t *r = chains + 8 * i;
+		int rev0 = 0;
+		if (r[2] < 0 || r[3] < 0 || r[3] + r[2] > n_seeds) return -1;
+		if (r[2] > 0 && (r[1] < 0 || r[1] >= bns->n_seqs)) return -1;
+		for (j = 0; j < r[2]; ++j) {
+			const int64_t *s = seeds + 4 * (r[3] + j);
+			const int64_t b = s[0], e = s[0] + s[2];
+			const int rev = b >= L;
+			int64_t fb, fe;
+			if (s[2] < 1 || s[1] < 0 || s[1] + s[2] > l_query || s[3] != s[2]) return -1;
+			if (b < 0 || e > L << 1 || (b < L && e > L)) return -1;
+			if (j == 0) rev0 = rev; else if (rev != rev0) return -1;
+			fb = rev? (L << 1) - e : b; fe = rev? (L << 1) - b : e;
+			if (fb < bns->anns[r[1]].offset || fe > bns->anns[r[1]].offset + bns->anns[r[1]].len) return -1;
+		}
+	}
+	q = (uint8_t*)malloc(l_query + 1);
+	memcpy(q, query, l_query);
+	sd = (mem_seed_t*)calloc(n_seeds + 1, sizeof(mem_seed_t));
+	for (i = 0; i < n_seeds; ++i) { sd[i].rbeg = seeds[4*i]; sd[i].qbeg = (int)seeds[4*i+1]; sd[i].len = (int)seeds[4*i+2]; sd[i].score = (int)seeds[4*i+3]; }
+	kv_init(av);
+	for (i = 0; i < n_chains; ++i) {
+		const int64_t *r = chains + 8 * i;
+		mem_chain_t ch;
+		memset(&ch, 0, sizeof ch);
+		ch.pos = r[0]; ch.rid = (int)r[1]; ch.n = ch.m = (int)r[2]; ch.seeds = sd + r[3]; ch.w = (uint32_t)r[4]; ch.kept = (uint32_t)r[5]; ch.first = (int)r[6]; ch.is_alt = (uint32_t)r[7];
+		memcpy(&ch.frac_rep, &frac_rep_bits, 4);
+		mem_chain2aln(c->opt, bns, c->idx->pac, l_query, q, &ch, &av);
+	}
+	n = av.n;
+	for (i = 0; i < n && i < cap_r; ++i) put_reg(regs + (size_t)i * ARX_REG_W, &av.a[i]);
+	free(av.a); free(sd); free(q);
+	return n;
+}
+
 /* bns_fetch_seq (bntseq.c:421): returns length, writes clamped beg/end/rid */
 int64_t ref_fetch_seq(ref_ctx_t *c, int64_t *beg, int64_t mid, int64_t *end, int *rid, uint8_t *out, int64_t cap)
 {

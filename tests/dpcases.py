@@ -196,6 +196,16 @@ def ext_cases(seed, n_random=1500, golden=None):
             q = rand_seq(rng, int(rng.choice([lo, hi])))
             t = np.concatenate([no_n(mutate(rng, q)), rand_seq(rng, tl)])[:tl]
             push(q, t, 100, int(rng.integers(1, 60)), "wave4")
+    # a window that ends at, or up to three bases beyond, the seed (fetch_clamp at a contig's edge; tlen == 0: rmax0 == seed.rbeg): at every class
+    # boundary, with the first target bases matching and not, both bands
+    for ql in QLEN_EDGES:
+        for tl in (0, 1, 2, 3):
+            for match in (0, 1):
+                q = rand_seq(rng, ql)
+                t = rand_seq(rng, tl)
+                if match:
+                    t[:min(tl, ql)] = q[:min(tl, ql)]
+                push(q, t, (100, 200)[(tl + match) & 1], int(rng.integers(1, 256)), "edge_t")
     return cases
 
 
@@ -230,6 +240,7 @@ def ext_coverage(cases, exp):
         per_class=[int((cls == c).sum()) for c in range(7)],
         qlen_edges=sorted(set(int(x) for x in ql) & set(QLEN_EDGES)),
         qlen_255=int((ql == 255).sum()),
+        tlen_0=int((tl == 0).sum()), tlen_0_classes=sorted(set(int(x) for x in cls[tl == 0])), tlen_2_3=int(((tl == 2) | (tl == 3)).sum()),
         tlen_1=int((tl == 1).sum()), tlen_511_513=sorted(set(int(x) for x in tl) & {511, 512, 513}), tlen_over_512=int((tl > EXT_T_CAP).sum()),
         both_dirs_strands=len({(c["qdir"], c["tdir"], c["strand"]) for c in cases}),
         w_100=int((w == 100).sum()), w_200=int((w == 200).sum()), w_small=int((w < 10).sum()), w_over_qlen=int((w > ql).sum()),

@@ -150,7 +150,7 @@ struct SimRT {
 	std::map<std::string, KernelTimer> &timers() { return tm; }
 	void timers_reset(bool) { tm.clear(); }
 	// the order in which a thread-per-item launch takes its items: 0 ascending, 1 descending, 2 SimBlock::pfor's stride permutation.  A GPU has every
-	// order by nature; only arx_selftest_post below sets it (a launch whose result depends on it is a race there)
+	// order by nature; only arx_selftest_post and arx_selftest_ext_stage below set it (a launch whose result depends on it is a race there)
 	int item_order = 0;
 	template <class F> void launch(const char *nm, int n, const F &f)
 	{
@@ -195,6 +195,7 @@ struct SimRT {
 #include "../../arachne_amd/csrc/selftest_rfa.h"
 #include "../../arachne_amd/csrc/selftest_reg2aln.h"
 #include "../../arachne_amd/csrc/selftest_post.h"
+#include "../../arachne_amd/csrc/selftest_ext.h"
 ARX_DEFINE_C_API(arx::SimRT)
 
 // test entry: the bytes of a batch's work arena that are live now (tests/test_arena_lifecycle.py: no phase grows from one cycle to the next, and
@@ -466,6 +467,21 @@ extern "C" int arx_selftest_post(arx_ctx *h, int32_t n_reads, const int64_t *can
 	rt.item_order = order;
 	return arx::selftest_post_run(rt, ((arx::Context<arx::SimRT> *)h)->ix, n_reads, cand_off, cands, n_regs, regs, alns, cigars, n_cig, bases, lens, n_barcodes, bc_pair_off,
 	                              penalty, cen_start, cen_end, post, split, mm_ref, mm_read, mm_cap, n_mm, table, table_cap, n_table, home);
+}
+
+// stage 4 on given chains runs here too: the same Pipeline::stage_extend, every DP on the one-thread ext2_task.  order: SimRT::item_order for every
+// launch of the stage -- within a round the chains of a read look at each other's done_round, and the dependency rule (dev_regs.h) says the answer
+// does not depend on who steps first.  (grid_cap: the double has no grid)
+extern "C" int arx_selftest_ext_stage(arx_ctx *h, const uint8_t *bases, const int32_t *lens, int32_t n_reads, const int32_t *n_chain, const int64_t *chains, const int32_t *n_seed,
+                                      const int64_t *seeds, const uint32_t *frac_rep_bits, int32_t *ext_off, int64_t *ext_regs, int32_t *core_off, int64_t *core_regs,
+                                      int64_t reg_cap, int32_t *core_clean, int64_t *stats, int32_t *rounds, int64_t rounds_cap, int32_t *done_round, int32_t *chain_n_regs,
+                                      uint32_t *err, int32_t, int32_t order)
+{
+	if (!h || order < 0 || order > 2) return ARX_E_ARG;
+	arx::SimRT rt;
+	rt.item_order = order;
+	return arx::selftest_ext_run(rt, ((arx::Context<arx::SimRT> *)h)->ix, bases, lens, n_reads, n_chain, chains, n_seed, seeds, frac_rep_bits, ext_off, ext_regs, core_off,
+	                             core_regs, reg_cap, core_clean, stats, rounds, rounds_cap, done_round, chain_n_regs, err);
 }
 
 // test entry: the one-thread extension (dev_sw.h ext2_task, what ARX_SW_SIMPLE runs) on tasks laid out as arx_selftest_extend takes them --

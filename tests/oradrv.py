@@ -189,6 +189,40 @@ class Oracle:
         assert 0 <= n <= cap
         return aln, cg[:n].copy(), sh
 
+    C2A_CALL_FIELDS = ["chain", "seed", "side", "qlen", "tlen", "w", "h0", "score", "qle", "tle", "gtle", "gscore", "max_off"]
+    C2A_SHAPE_FIELDS = ["regs", "skipped", "kept_overlap", "dp_left", "dp_right", "band2_left", "band2_right", "toend_left", "toend_right", "tlen0", "tlen_short",
+                        "rmax0", "rmax1", "clamp", "n_dep", "dep_last"]
+    CLAMP_ZERO, CLAMP_LPAC, CLAMP_2LPAC, CLAMP_CONTIG = 1, 2, 4, 8   # bits of the clamp column
+
+    def chain2aln(self, seq, chains, seeds, frac_rep_bits=0, cap_r=None, cap_calls=None):
+        """ora_chain2aln: mem_chain2aln over the chains of one read (rows as chains() hands them out) -> (region rows before mem_sort_dedup_patch,
+        rows of C2A_CALL_FIELDS, one per ksw_extend2 call in call order, rows of C2A_SHAPE_FIELDS, one per chain); None for rows it refuses."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        ch = np.ascontiguousarray(chains, dtype=np.int64).reshape(-1, 8)
+        sd = np.ascontiguousarray(seeds, dtype=np.int64).reshape(-1, 4)
+        cap_r = len(sd) + 1 if cap_r is None else cap_r
+        cap_calls = 4 * len(sd) + 4 if cap_calls is None else cap_calls     # at most two tries per side of a seed
+        regs = np.zeros((cap_r, REG_W), dtype=np.int64)
+        calls = np.zeros((cap_calls, len(self.C2A_CALL_FIELDS)), dtype=np.int64)
+        sh = np.zeros((len(ch) + 1, len(self.C2A_SHAPE_FIELDS)), dtype=np.int64)
+        nc = C.c_int(0)
+        self.lib.ora_chain2aln.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_void_p]
+        n = self.lib.ora_chain2aln(self.h, len(seq), seq.ctypes.data, len(ch), ch.ctypes.data, len(sd), sd.ctypes.data, int(frac_rep_bits), regs.ctypes.data, cap_r,
+                                   calls.ctypes.data, cap_calls, C.byref(nc), sh.ctypes.data)
+        if n < 0:
+            return None
+        assert n <= cap_r and nc.value <= cap_calls
+        return regs[:n].copy(), calls[:nc.value].copy(), sh[:len(ch)].copy()
+
+    def sort_dedup_patch(self, seq, regs):
+        """ora_sort_dedup_patch: mem_sort_dedup_patch and mem_align1_core's is_alt marks on region rows -> the rows left."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        rows = np.array(regs, dtype=np.int64).reshape(-1, REG_W)
+        self.lib.ora_sort_dedup_patch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        n = self.lib.ora_sort_dedup_patch(self.h, len(seq), seq.ctypes.data, len(rows), rows.ctypes.data)
+        return rows[:n].copy()
+
     def align1(self, seq, cap=4096):
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         out = np.zeros((cap, REG_W), dtype=np.int64)

@@ -174,6 +174,21 @@ class Ref:
         assert 0 <= n <= cap
         return aln, cg[:n].copy()
 
+    def chain2aln(self, seq, chains, seeds, frac_rep_bits=0, cap_r=None):
+        """ref_chain2aln: the reference's mem_chain2aln over the chains of one read (rows as chains() hands them out) -> region rows before
+        mem_sort_dedup_patch; None for rows it refuses."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        ch = np.ascontiguousarray(chains, dtype=np.int64).reshape(-1, 8)
+        sd = np.ascontiguousarray(seeds, dtype=np.int64).reshape(-1, 4)
+        cap_r = len(sd) + 1 if cap_r is None else cap_r
+        regs = np.zeros((cap_r, REG_W), dtype=np.int64)
+        self.lib.ref_chain2aln.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
+        n = self.lib.ref_chain2aln(self.h, len(seq), seq.ctypes.data, len(ch), ch.ctypes.data, len(sd), sd.ctypes.data, int(frac_rep_bits), regs.ctypes.data, cap_r)
+        if n < 0:
+            return None
+        assert n <= cap_r
+        return regs[:n].copy()
+
     def align1(self, seq, cap=4096):
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         out = np.zeros((cap, REG_W), dtype=np.int64)

@@ -25,6 +25,7 @@ def test_every_declared_symbol_is_exported(lib):
     assert {"arx_selftest_block", "arx_selftest_block_shape", "arx_selftest_rfa"} <= names   # the placement stage's self-test entries
     assert "arx_selftest_reg2aln" in names   # the CIGAR stage's self-test entry
     assert "arx_selftest_post" in names      # the post passes' self-test entry
+    assert "arx_selftest_ext_stage" in names  # the extension stage's self-test entry
     for n in sorted(names):
         assert hasattr(lib, n), n
 

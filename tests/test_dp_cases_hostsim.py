@@ -63,6 +63,7 @@ def test_serial_extension_on_the_generated_cases(env):
     cov = dpcases.ext_coverage(cases, exp)
     assert min(cov["per_class"]) >= 60, cov
     assert cov["qlen_edges"] == sorted(dpcases.QLEN_EDGES), cov
+    assert cov["tlen_0"] >= 40 and cov["tlen_0_classes"] == list(range(7)) and cov["tlen_2_3"] >= 80, cov
     assert cov["tlen_1"] >= 20 and cov["tlen_511_513"] == [511, 512, 513] and cov["tlen_over_512"] >= 60, cov
     assert cov["both_dirs_strands"] == 8, cov
     assert cov["w_100"] > 300 and cov["w_200"] > 200 and cov["w_small"] >= 100 and cov["w_over_qlen"] >= 150, cov
@@ -125,7 +126,7 @@ def test_selftest_entries_refuse_input_outside_the_contract(built):
     p, L = text.pos[h], text.l_pac
     q = dpcases.rand_seq(rng, 300)
     ok_ext = [p, 0, 100, 50, 1, 1, 100, 30]
-    bad_ext = [dict(), dict(qlen=256), dict(qlen=0), dict(h0=0), dict(h0=256), dict(w=0), dict(tlen=0), dict(qdir=0), dict(tdir=2),
+    bad_ext = [dict(), dict(qlen=256), dict(qlen=0), dict(h0=0), dict(h0=256), dict(w=0), dict(tlen=-1), dict(qdir=0), dict(tdir=2),
                dict(tpos=L - 10, tlen=20), dict(tpos=2 * L - 5, tlen=10), dict(tpos=5, tdir=-1, tlen=10), dict(qoff=250, qlen=60)]
     keys = ["tpos", "qoff", "qlen", "tlen", "qdir", "tdir", "w", "h0"]
     for k, d in enumerate(bad_ext):

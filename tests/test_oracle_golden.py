@@ -104,3 +104,31 @@ def test_pair_path(gold):
     assert (out["cigars"] == z["pair_cigars"]).all()
     c = o.counters()
     assert c["ext_same_block"] > 0 and c["sa_lookups"] > 0
+
+
+def test_chain2aln_on_the_planted_chains(built):
+    """ora_chain2aln against what the reference's mem_chain2aln gave for the planted rows of tests/extcases.py (tests/golden/ext_stage_v1.npz, recorded
+    from oracle/_ref/libbwaref.so by make_ext_stage_golden.py): the rows are the ones extcases plants today, and every region is the reference's."""
+    import subprocess
+    import extcases
+    import oradrv
+    z = np.load(os.path.join(workloads.GOLDEN_DIR, "ext_stage_v1.npz"))
+    sim = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim", "libarx_hostsim.so")
+    subprocess.check_call(["make", "-s", "-C", os.path.dirname(sim)])
+    c = extcases.build_all()
+    o = oradrv.Oracle(c["genome"].write_index(sim))
+    assert [str(x) for x in z["batches"]] == [b.name for b in c["batches"]]
+    n_regs = 0
+    for k, b in enumerate(c["batches"]):
+        rows = b.rows()
+        for key in ("seqs", "lens", "n_chain", "n_seed", "chains", "seeds", "frb"):
+            assert z[f"b{k}_{key}"].shape == rows[key].shape and (z[f"b{k}_{key}"] == rows[key]).all(), (b.name, key)
+        off, regs = z[f"b{k}_reg_off"], z[f"b{k}_regs"]
+        assert len(off) == len(b.reads) + 1
+        for i, rd in enumerate(b.reads):
+            got = o.chain2aln(rd["read"], rd["ch"], rd["sd"], extcases.FRAC_REP_BITS)[0]
+            exp = regs[off[i]:off[i + 1]]
+            assert got.shape == exp.shape and (got == exp).all(), (b.name, rd["name"])
+            n_regs += len(exp)
+    assert n_regs > 250
+    o.close()

@@ -56,3 +56,34 @@ def test_pair_path_matches_reference(built, seed):
     if r is not None:
         r.close()
     o.close()
+
+
+def test_chain2aln_on_the_planted_chains_matches_reference(built):
+    """ora_chain2aln against the reference's own mem_chain2aln (ref_chain2aln) on every planted read of tests/extcases.py, region for region and
+    bit for bit; both entry points refuse the same rows.  Runs where oracle/_ref can be built; tests/test_oracle_golden.py holds the same regions
+    from the committed fixture elsewhere."""
+    import subprocess
+    import extcases
+    import oradrv
+    refdrv.need("ref_chain2aln")
+    sim = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim", "libarx_hostsim.so")
+    subprocess.check_call(["make", "-s", "-C", os.path.dirname(sim)])
+    c = extcases.build_all()
+    fa = c["genome"].write_index(sim)
+    o, r = oradrv.Oracle(fa), refdrv.Ref(fa)
+    n = n_regs = 0
+    for b in c["batches"] + [c["big"]]:
+        b.rows()
+        for rd in b.reads:
+            a = o.chain2aln(rd["read"], rd["ch"], rd["sd"], extcases.FRAC_REP_BITS)
+            e = r.chain2aln(rd["read"], rd["ch"], rd["sd"], extcases.FRAC_REP_BITS)
+            assert a is not None and e is not None and a[0].shape == e.shape and (a[0] == e).all(), (b.name, rd["name"])
+            n += 1
+            n_regs += len(e)
+    assert n > 3800 and n_regs > 4000
+    read = c["genome"].seqs[0][1000:1150]
+    for ch, sd in (([[1040, 1, 1, 0, 30, 3, -1, 0]], [[1040, 40, 30, 30]]), ([[1040, 0, 1, 0, 30, 3, -1, 0]], [[1040, 130, 30, 30]]),
+                   ([[1040, 0, 1, 0, 30, 3, -1, 0]], [[int(c["genome"].off[1]) - 10, 40, 30, 30]])):
+        assert o.chain2aln(read, ch, sd) is None and r.chain2aln(read, ch, sd) is None
+    o.close()
+    r.close()
