@@ -178,6 +178,10 @@ _SELFTEST_ARGS = {
     "arx_bam_index": [C.c_int32, C.c_char_p, C.c_char_p, C.c_int64, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_bam_index": [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                C.c_void_p, C.c_void_p],
+    # and its .csi, for contigs above 2^29 bases
+    "arx_bam_index_csi": [C.c_int32, C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32],
+    "arx_selftest_bam_index_csi": [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                   C.c_int64, C.c_void_p, C.c_void_p],
 }
 
 
@@ -569,6 +573,50 @@ def selftest_bam_index(stream, hdr: int, ref_len, blk_at, blk_isize, seg_bytes: 
                                                      isize.ctypes.data if len(isize) else None, int(seg_bytes), int(slab_bytes), out.ctypes.data, cap, C.byref(out_len), st.ctypes.data)
     assert out[cap:].tobytes() == b"\xa5" * 8
     return rc, (out[:out_len.value].tobytes() if rc == 0 else b""), _bai_stats(st)
+
+
+CSI_MIN_SHIFT = 14                                                 # what min_shift = 0 means; [10, 24] is accepted
+_CSI_STATS = tuple("depth" if k == "linear" else k for k in _BAI_STATS) + ("min_shift",)
+
+
+def _csi_stats(st):
+    return {k: int(st[i]) for i, k in enumerate(_CSI_STATS)}
+
+
+def bam_index_csi(path: str, csi_path: "str | None" = None, min_shift: int = CSI_MIN_SHIFT, max_bytes: int = 0, timed: bool = False, device: int = 0, lib_path: str = LIB_PATH):
+    """The .csi (CSIv1) of a coordinate-sorted BAM file, built on the GPU by the machinery of bam_index: the index for headers with a contig
+    above 2^29 bases, which a .bai cannot hold (include/arachne_amd.h: arx_bam_index_csi, which states the rules).  csi_path defaults to
+    path + ".csi"; min_shift in [10, 24] (0: 14); the depth follows from the longest contig.  The file is BGZF; htslib's bin folding is not
+    done, so the bytes are not those of `samtools index -c`.  -> the stats as a dict (depth and min_shift as used among them); ArachneError
+    with .code on failure (no file is left behind then)."""
+    lib = _load(lib_path)
+    st, msg = np.zeros(20, dtype=np.int64), C.create_string_buffer(1024)
+    rc = _selftest_fn(lib, "arx_bam_index_csi")(device, os.fsencode(path), None if csi_path is None else os.fsencode(csi_path), int(min_shift), int(max_bytes),
+                                                BAI_TIMED if timed else 0, st.ctypes.data, msg, 1024)
+    if rc != 0:
+        e = ArachneError("arx_bam_index_csi: " + msg.value.decode(errors="replace"))
+        e.code = rc
+        raise e
+    return _csi_stats(st)
+
+
+def selftest_bam_index_csi(stream, hdr: int, ref_len, blk_at, blk_isize, seg_bytes: int = 1 << 18, slab_bytes: int = 0, min_shift: int = CSI_MIN_SHIFT,
+                           out_cap: "int | None" = None, device: int = 0, lib_path: str = LIB_PATH):
+    """selftest_bam_index for the .csi (include/arachne_amd.h: arx_selftest_bam_index_csi) -> (rc, the INFLATED bytes of the .csi (empty
+    unless rc is 0), stats)."""
+    lib = _load(lib_path)
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    n = len(src)
+    lens, at, isize = _arr(ref_len, np.int32), _arr(blk_at, np.int64), _arr(blk_isize, np.int32)
+    assert len(at) == len(isize) + 1
+    cap = 64 + 64 * len(lens) + 32 * (n // 36 + 1) if out_cap is None else out_cap       # a bin and a chunk per record at the most
+    out = np.full(cap + 8, 0xA5, dtype=np.uint8)
+    out_len, st = C.c_int64(-1), np.zeros(20, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_bam_index_csi")(device, src.ctypes.data if n else None, n, int(hdr), len(lens), lens.ctypes.data if len(lens) else None, len(isize),
+                                                         at.ctypes.data, isize.ctypes.data if len(isize) else None, int(seg_bytes), int(slab_bytes), int(min_shift), out.ctypes.data,
+                                                         cap, C.byref(out_len), st.ctypes.data)
+    assert out[cap:].tobytes() == b"\xa5" * 8
+    return rc, (out[:out_len.value].tobytes() if rc == 0 else b""), _csi_stats(st)
 
 
 INFLATE_STATUS = ("OK", "BAD_HEADER", "BAD_BTYPE", "BAD_STORED_LEN", "BAD_CODE_LENGTHS", "BAD_SYMBOL", "BAD_DISTANCE", "TRUNCATED", "SIZE_MISMATCH", "CRC_MISMATCH")

@@ -4,7 +4,7 @@
 // sort of a BAM file into an open writer (arx_bam_open_ex, arx_bam_sort_append, arx_selftest_bam_sort: dev_bamsort.h, hip_bamsort.h), and the sort
 // of a FASTQ file pair by barcode (arx_fastq_sort, arx_selftest_fastq_sort: dev_fqsort.h, hip_fqsort.h) with the header standardization in front of it (arx_fastq_standardize,
 // arx_selftest_fastq_standardize: dev_fqstd.h, hip_fqstd.h) and the two fused into one call (arx_fastq_prepare, arx_selftest_fastq_prepare: dev_fqprep.h, hip_fqprep.h), and the .bai of a coordinate-sorted
-// BAM file (arx_bam_index, arx_selftest_bam_index: dev_bamindex.h, hip_bamindex.h).
+// BAM file and its .csi (arx_bam_index, arx_bam_index_csi and their self-tests: dev_bamindex.h, hip_bamindex.h).
 #include <map>
 #include <memory>
 #include <mutex>
@@ -583,16 +583,18 @@ extern "C" int arx_selftest_fastq_prepare(int32_t device, const uint8_t *t1, int
 	});
 }
 
-// ---- the .bai of a coordinate-sorted BAM file (dev_bamindex.h, hip_bamindex.h)
-extern "C" int arx_bam_index(int32_t device, const char *bam_path, const char *bai_path, int64_t max_bytes, int32_t flags, int64_t *stats, char *msg, int32_t msg_cap)
+// ---- the .bai or the .csi of a coordinate-sorted BAM file (dev_bamindex.h, hip_bamindex.h).  csi_shift: 0 for the .bai, else the .csi's min_shift
+static int bam_index_file(const char *entry, int32_t device, const char *bam_path, const char *index_path, int32_t csi_shift, int64_t max_bytes, int32_t flags, int64_t *stats, char *msg,
+                          int32_t msg_cap)
 {
 	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
 	if (stats) for (int k = 0; k < arx::BI_N_STATS; ++k) stats[k] = 0;
-	if (flags & ~ARX_BAI_TIMED) { say("arx_bam_index: unknown flag bits"); return ARX_E_ARG; }
-	if (!bam_path || max_bytes < 0) { say("arx_bam_index: bad arguments"); return ARX_E_ARG; }
+	if (flags & ~ARX_BAI_TIMED) { say(std::string(entry) + ": unknown flag bits"); return ARX_E_ARG; }
+	if (!bam_path || max_bytes < 0) { say(std::string(entry) + ": bad arguments"); return ARX_E_ARG; }
+	if (csi_shift < 0) { say(std::string(entry) + ": min_shift lies outside [10, 24]"); return ARX_E_ARG; }
 	std::string err;
 	try {
-		const int rc = arx::bi_index_file(device, bam_path, bai_path, max_bytes, (flags & ARX_BAI_TIMED) != 0, stats, err);
+		const int rc = arx::bi_index_file(device, bam_path, index_path, max_bytes, (flags & ARX_BAI_TIMED) != 0, stats, err, csi_shift);
 		if (rc != ARX_OK) say(err);
 		return rc;
 	} catch (const arx::BsTooLarge &e) {
@@ -606,12 +608,19 @@ extern "C" int arx_bam_index(int32_t device, const char *bam_path, const char *b
 		return ARX_E_DEVICE;
 	}
 }
-
-extern "C" int arx_selftest_bam_index(int32_t device, const uint8_t *stream, int64_t n_bytes, int64_t hdr, int32_t n_ref, const int32_t *ref_len, int64_t n_blocks,
-                                      const int64_t *blk_at, const int32_t *blk_isize, int64_t seg_bytes, int64_t slab_bytes, uint8_t *out, int64_t out_cap, int64_t *out_len,
-                                      int64_t *stats)
+extern "C" int arx_bam_index(int32_t device, const char *bam_path, const char *bai_path, int64_t max_bytes, int32_t flags, int64_t *stats, char *msg, int32_t msg_cap)
 {
-	if (n_bytes < 0 || hdr < 0 || hdr > n_bytes || n_ref < 0 || (n_ref > 0 && !ref_len) || n_blocks < 0 || !blk_at || (n_blocks > 0 && !blk_isize) || seg_bytes < arx::BS_MIN_SEG ||
+	return bam_index_file("arx_bam_index", device, bam_path, bai_path, 0, max_bytes, flags, stats, msg, msg_cap);
+}
+extern "C" int arx_bam_index_csi(int32_t device, const char *bam_path, const char *csi_path, int32_t min_shift, int64_t max_bytes, int32_t flags, int64_t *stats, char *msg, int32_t msg_cap)
+{
+	return bam_index_file("arx_bam_index_csi", device, bam_path, csi_path, arx::bi_csi_shift(min_shift), max_bytes, flags, stats, msg, msg_cap);
+}
+
+static int selftest_bam_index(int32_t device, const uint8_t *stream, int64_t n_bytes, int64_t hdr, int32_t n_ref, const int32_t *ref_len, int64_t n_blocks, const int64_t *blk_at,
+                              const int32_t *blk_isize, int64_t seg_bytes, int64_t slab_bytes, int32_t csi_shift, uint8_t *out, int64_t out_cap, int64_t *out_len, int64_t *stats)
+{
+	if (csi_shift < 0 || n_bytes < 0 || hdr < 0 || hdr > n_bytes || n_ref < 0 || (n_ref > 0 && !ref_len) || n_blocks < 0 || !blk_at || (n_blocks > 0 && !blk_isize) || seg_bytes < arx::BS_MIN_SEG ||
 	    (seg_bytes & (seg_bytes - 1)) || slab_bytes < 0 || out_cap < 0 || (out_cap > 0 && !out) || !out_len || (n_bytes > 0 && !stream))
 		return ARX_E_ARG;
 	*out_len = 0;
@@ -621,9 +630,11 @@ extern "C" int arx_selftest_bam_index(int32_t device, const uint8_t *stream, int
 		if (blk_isize[b] < 0 || blk_isize[b] > arx::INF_MAX_OUT || blk_at[b] > blk_at[b + 1]) return ARX_E_ARG;
 		sum += blk_isize[b];
 	}
-	if (sum != n_bytes || arx::bi_long_contig(n_ref, ref_len) >= 0) return ARX_E_ARG;
+	const bool csi = csi_shift != 0;
+	if (sum != n_bytes || (!csi && arx::bi_long_contig(n_ref, ref_len) >= 0)) return ARX_E_ARG;
 	for (int32_t i = 0; i < n_ref; ++i)
 		if (ref_len[i] < 0) return ARX_E_ARG;
+	const arx::BiScheme sc = csi ? arx::bi_csi_scheme(csi_shift, n_ref, ref_len) : arx::BI_BAI;
 	arx::BiBlocks B;
 	if (!B.build(n_blocks, blk_at, blk_isize, slab_bytes)) return ARX_E_ARG;
 	try {
@@ -637,17 +648,18 @@ extern "C" int arx_selftest_bam_index(int32_t device, const uint8_t *stream, int
 		arx::BiIndex ix;
 		arx::BiMemSrc src{drv, d_s.as<uint8_t>(), B};
 		std::string err;
-		const int rc = arx::bi_result(arx::bi_run(drv, src, B, hdr, n_ref, ref_len, seg_bytes, ix), ix, "the stream", err);
+		const int rc = arx::bi_result(arx::bi_run(drv, src, B, hdr, n_ref, ref_len, seg_bytes, ix, sc), ix, "the stream", err);
 		if (rc != ARX_OK) {
 			if (stats) stats[9] = (int64_t)ix.err; // the first offending record's number << 8 | the rule, or -1
 			return rc;
 		}
-		const std::vector<uint8_t> bai = arx::bi_serialise(ix);
+		const std::vector<uint8_t> bai = csi ? arx::bi_serialise_csi(ix) : arx::bi_serialise(ix);
 		if ((int64_t)bai.size() > out_cap) return ARX_E_TOO_LARGE;
 		memcpy(out, bai.data(), bai.size());
 		*out_len = (int64_t)bai.size();
 		drv.us[arx::BI_T_TOTAL] = arx::bs_now_us() - t0;
 		arx::bi_stats(stats, drv, ix, n_bytes, n_blocks);
+		if (csi) arx::bi_stats_csi(stats, sc);
 	} catch (const arx::BsTooLarge &) {
 		return ARX_E_TOO_LARGE;
 	} catch (const arx::HipOutOfMemory &) {
@@ -656,4 +668,16 @@ extern "C" int arx_selftest_bam_index(int32_t device, const uint8_t *stream, int
 		return ARX_E_DEVICE;
 	}
 	return ARX_OK;
+}
+extern "C" int arx_selftest_bam_index(int32_t device, const uint8_t *stream, int64_t n_bytes, int64_t hdr, int32_t n_ref, const int32_t *ref_len, int64_t n_blocks,
+                                      const int64_t *blk_at, const int32_t *blk_isize, int64_t seg_bytes, int64_t slab_bytes, uint8_t *out, int64_t out_cap, int64_t *out_len,
+                                      int64_t *stats)
+{
+	return selftest_bam_index(device, stream, n_bytes, hdr, n_ref, ref_len, n_blocks, blk_at, blk_isize, seg_bytes, slab_bytes, 0, out, out_cap, out_len, stats);
+}
+extern "C" int arx_selftest_bam_index_csi(int32_t device, const uint8_t *stream, int64_t n_bytes, int64_t hdr, int32_t n_ref, const int32_t *ref_len, int64_t n_blocks,
+                                          const int64_t *blk_at, const int32_t *blk_isize, int64_t seg_bytes, int64_t slab_bytes, int32_t min_shift, uint8_t *out, int64_t out_cap,
+                                          int64_t *out_len, int64_t *stats)
+{
+	return selftest_bam_index(device, stream, n_bytes, hdr, n_ref, ref_len, n_blocks, blk_at, blk_isize, seg_bytes, slab_bytes, arx::bi_csi_shift(min_shift), out, out_cap, out_len, stats);
 }

@@ -12,17 +12,20 @@
 // CIGAR were not whole in it (at most the last one found), or a cut block_size field.  The chain enters the buffer where it left the last,
 // so a record is met exactly once, and one larger than a slab simply grows in the carry until its CIGAR is whole.  The rows of the blocks the
 // buffer's bytes lie in are uploaded with it (the host holds the whole table), so V(start) is a binary search over the buffer's own rows.
-//   per record    bi_rec: V(start); the rules on refID, pos and end; end from the CIGAR; bin = reg2bin(beg, end); the (mapped, unmapped) count
+//   per record    bi_rec: V(start); the rules on refID, pos and end; end from the CIGAR; bin = the scheme's bin of [beg, end); the (mapped, unmapped) count
 //                 word; the linear index by a 64-bit atomic minimum of V(start) over the record's windows, which no order can change
 //                 bi_flag: the order check against the predecessor and the run-start flag (the slab's first record against the carried last)
 //                 Offences go into one error word by an atomic minimum of (record number << 8 | rule): the first offending record wins
-//   runs          scans of the flags and of the count words; bi_runs compacts (refID << 16 | bin, V(begin), V(end), counts) at the run starts.
+//   runs          scans of the flags and of the count words; bi_runs compacts (refID << bin_bits | bin, V(begin), V(end), counts) at the run starts.
 //                 A run ends where the next begins; the slab's last run ends at V(the next chain offset), which the host knows
 //   chunks        a stable sort of the runs by (refID, bin); bi_head marks where a sorted run cannot join its predecessor (another bin, or
 //                 (earlier.end >> 16) < (later.beg >> 16)); a scan; bi_chunks compacts the joined chunks, which the host fetches and appends
 //                 bin by bin under the same rule (bi_append).  The rule relates two neighbours only and a run cut by a slab border ends where
 //                 its rest begins, so the chunks do not depend on where the slabs were cut
 // Records with refID = -1 form a run under refID = n_ref, which the host drops; their number is what the count words leave of the records.
+// The bins and the windows follow a scheme (BiScheme: min_shift, depth) that the functors carry as a value.  The BAI is (14, 5); under the
+// scheme of a CSI index (bi_csi_scheme) the same run serves contigs of up to 2^31 - 1 bases, the window table is what the bins' loffset is
+// read from (bi_serialise_csi), and the run key refID << bin_bits | bin widens with the depth.
 // Nothing here depends on the order of the items: every write goes to a slot of its own item, or is a minimum or a sum.
 #pragma once
 #include <stdint.h>
@@ -35,8 +38,9 @@
 
 namespace arx {
 
-constexpr int BI_LIN_SHIFT = 14;                       // a window of the linear index: 16384 bases
+constexpr int BI_LIN_SHIFT = 14;                       // a window of the BAI's linear index: 16384 bases
 constexpr uint32_t BI_PSEUDO_BIN = 37450;
+constexpr int BI_CSI_SHIFT_MIN = 10, BI_CSI_SHIFT_MAX = 24, BI_CSI_SHIFT_DEFAULT = 14;
 constexpr int64_t BI_MAX_REF = (int64_t)1 << 29;       // the BAI format's limit
 constexpr int64_t BI_MAX_AT = (int64_t)1 << 48;        // a virtual offset holds 48 bits of file offset
 constexpr uint64_t BI_UNSET = ~(uint64_t)0;
@@ -44,17 +48,33 @@ enum { BI_OK = 0, BI_E_CHAIN = 1, BI_E_INFLATE = 2, BI_E_RULE = 3 };
 enum { BI_R_FIELDS = 1, BI_R_REFID, BI_R_POS, BI_R_END, BI_R_ORDER };
 enum { BI_W_ERR = 0, BI_W_NP, BI_W_FROM, BI_W_CONT, BI_W_LASTKEY, BI_W_LASTRB, BI_W_RUNS, BI_N_WORDS };
 
-// the SAM specification, 5.3: the bin of the zero-based half-open interval [beg, end)
-ARX_HDI uint32_t bi_reg2bin(int64_t beg, int64_t end)
-{
-	--end;
-	if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
-	if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
-	if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
-	if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
-	if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
-	return 0;
-}
+// The bin scheme, a value the functors carry: levels 0 .. depth, a bin of level l spans 2^(min_shift + 3 (depth - l)) bases, the windows of the
+// offset table 2^min_shift (the leaf bins' width).  The BAI (the SAM specification, 5.3) is the instance (14, 5); a CSI index (CSIv1) states its
+// own.  depth <= 7 (min_shift >= 10 and 2^31 - 1 bases at most), so a bin number is below 2^22 and fits the 3 depth + 1 bits of the run key
+struct BiScheme {
+	int32_t min_shift, depth;
+	ARX_HDI int bin_bits() const { return 3 * depth + 1; }                                     // (8^(depth+1) - 1) / 7 < 2^(3 depth + 1)
+	ARX_HDI uint32_t first(int l) const { return (uint32_t)((((uint64_t)1 << (3 * l)) - 1) / 7); } // the first bin of level l
+	ARX_HDI uint32_t meta() const { return first(depth + 1) + 1; }                             // the pseudo-bin: 37450 at depth 5
+	// the bin of the zero-based half-open interval [beg, end): the deepest level at which beg and end - 1 lie in one bin
+	ARX_HDI uint32_t bin(int64_t beg, int64_t end) const
+	{
+		--end;
+		int s = min_shift;
+		for (int l = depth; l > 0; --l, s += 3)
+			if (beg >> s == end >> s) return first(l) + (uint32_t)(beg >> s);
+		return 0;
+	}
+	// the first window of a bin's interval
+	ARX_HDI int64_t first_window(uint32_t b) const
+	{
+		int l = depth;
+		while (first(l) > b) --l;
+		return (int64_t)(b - first(l)) << (3 * (depth - l));
+	}
+};
+constexpr BiScheme BI_BAI = {BI_LIN_SHIFT, 5};
+ARX_HDI uint32_t bi_reg2bin(int64_t beg, int64_t end) { return BI_BAI.bin(beg, end); } // the SAM specification, 5.3
 
 // the non-empty blocks a buffer's bytes lie in: ooff[i] is where block i's bytes start in the buffer (the first may start in front of it), at[i]
 // its file offset
@@ -71,7 +91,7 @@ ARX_HDI uint64_t bi_voff(const BiRows &r, int64_t o)
 }
 // ((uint32_t)refID, pos) in one word that orders as the pair does, pos as the signed number it is
 ARX_HDI uint64_t bi_key(const uint8_t *p) { return (uint64_t)bs_r32(p + 4) << 32 | (uint64_t)(bs_r32(p + 8) ^ 0x80000000u); }
-ARX_HDI int bi_key_bits(int32_t n_ref) { return bs_key_bits(n_ref) - 16; } // of refID << 16 | bin, refID up to n_ref
+ARX_HDI int bi_key_bits(int32_t n_ref, const BiScheme &sc) { return bs_key_bits(n_ref) - 32 + sc.bin_bits(); } // of refID << bin_bits | bin, refID up to n_ref
 
 // the last record found in an open buffer: whole (its fixed part, name and CIGAR are here, or all of it where block_size says less) or carried
 struct BiTailF {
@@ -94,14 +114,16 @@ struct BiRecF {
 	const uint8_t *s; int64_t n; const int64_t *rec_off; BiRows rows;
 	int32_t n_ref; const int32_t *ref_len; const int64_t *lin_base; uint64_t *lin;
 	int64_t rec0;                      // the number of the buffer's first record
-	uint64_t *rb, *vbeg; int64_t *cnt; // per record: refID << 16 | bin; V(start); mapped | unmapped << 32
+	uint64_t *rb, *vbeg; int64_t *cnt; // per record: refID << bin_bits | bin; V(start); mapped | unmapped << 32
 	int64_t *words;
+	BiScheme sc;
 	ARX_DEVI void fail(int64_t j, int rule) const { ARX_ATOMIC_MINU64((uint64_t *)&words[BI_W_ERR], (uint64_t)(rec0 + j) << 8 | (uint64_t)rule); }
 	ARX_DEVI void operator()(int64_t j) const
 	{
 		const int64_t o = rec_off[j];
 		const uint8_t *p = s + o; // at least 36 bytes: bi_run hands over whole records only
-		rb[j] = (uint64_t)(uint32_t)n_ref << 16; cnt[j] = 0;
+		const int bits = sc.bin_bits();
+		rb[j] = (uint64_t)(uint32_t)n_ref << bits; cnt[j] = 0;
 		vbeg[j] = bi_voff(rows, o);
 		const int64_t all = 4 + (int64_t)bs_r32(p), l_name = p[12], n_cig = (int64_t)p[16] | (int64_t)p[17] << 8, need = 36 + l_name + 4 * n_cig;
 		if (need > all || o + need > n) { fail(j, BI_R_FIELDS); return; }
@@ -120,11 +142,11 @@ struct BiRecF {
 		}
 		const int64_t beg = pos, end = beg + (len > 0 ? len : 1);
 		if (end > (int64_t)ref_len[rid]) { fail(j, BI_R_END); return; }
-		rb[j] = (uint64_t)(uint32_t)rid << 16 | bi_reg2bin(beg, end);
+		rb[j] = (uint64_t)(uint32_t)rid << bits | sc.bin(beg, end);
 		cnt[j] = flag & 4 ? (int64_t)1 << 32 : 1;
 		const uint64_t v = vbeg[j];
 		uint64_t *win = lin + lin_base[rid]; // end <= ref_len: every window lies in the contig's part of the table
-		for (int64_t w = beg >> BI_LIN_SHIFT; w <= (end - 1) >> BI_LIN_SHIFT; ++w)
+		for (int64_t w = beg >> sc.min_shift; w <= (end - 1) >> sc.min_shift; ++w)
 			if (ARX_LOAD_SHARED(&win[w]) > v) ARX_ATOMIC_MINU64(&win[w], v); // (values only fall: a read that is too old is too large, and the minimum is taken)
 	}
 };
@@ -133,6 +155,7 @@ struct BiFlagF {
 	const uint8_t *s; const int64_t *rec_off; const uint64_t *rb; int64_t np, rec0;
 	int32_t n_ref, have_prev; uint64_t prev_key, prev_rb; // the last record of the buffers before
 	int64_t *flag, *words;
+	BiScheme sc;
 	ARX_DEVI void operator()(int64_t j) const
 	{
 		const uint64_t key = bi_key(s + rec_off[j]);
@@ -141,7 +164,7 @@ struct BiFlagF {
 		if (has && key < kp) ARX_ATOMIC_MINU64((uint64_t *)&words[BI_W_ERR], (uint64_t)(rec0 + j) << 8 | (uint64_t)BI_R_ORDER);
 		const bool same = has && rb[j] == rp;
 		flag[j] = j == 0 || !same; // a buffer's first record opens a run of its own: the host joins it to the one it continues
-		if (!same && (rb[j] >> 16) < (uint64_t)(uint32_t)n_ref) ARX_ATOMIC_ADD64(&words[BI_W_RUNS], 1);
+		if (!same && (rb[j] >> sc.bin_bits()) < (uint64_t)(uint32_t)n_ref) ARX_ATOMIC_ADD64(&words[BI_W_RUNS], 1);
 		if (j == 0) words[BI_W_CONT] = same;
 		if (j == np - 1) { words[BI_W_LASTKEY] = (int64_t)key; words[BI_W_LASTRB] = (int64_t)rb[j]; }
 	}
@@ -231,6 +254,7 @@ struct BiRef {
 	std::vector<uint64_t> lin;
 };
 struct BiIndex {
+	BiScheme sc = BI_BAI;
 	std::vector<BiRef> refs;
 	int64_t n_no_coor = 0, n_records = 0, n_slabs = 0, n_runs = 0, n_chunks = 0, n_bins = 0, n_lin = 0;
 	uint64_t err = BI_UNSET; // BI_E_RULE: the first offending record's number << 8 | the rule
@@ -239,11 +263,12 @@ struct BiIndex {
 // a slab's joined chunks, in (refID, bin) order and file order within: appended bin by bin, joined to the bin's last by the rule of the device
 inline void bi_append(BiIndex &ix, int32_t n_ref, const uint64_t *key, const uint64_t *beg, const uint64_t *end, const int64_t *c0, int64_t n)
 {
+	const int bits = ix.sc.bin_bits();
 	for (int64_t k = 0; k < n; ++k) {
-		const uint64_t ref = key[k] >> 16;
+		const uint64_t ref = key[k] >> bits;
 		if (ref >= (uint64_t)n_ref) continue; // the records without a coordinate
 		BiRef &r = ix.refs[(size_t)ref];
-		std::vector<BiChunk> &v = r.bins[(uint32_t)(key[k] & 0xffff)];
+		std::vector<BiChunk> &v = r.bins[(uint32_t)(key[k] & (((uint64_t)1 << bits) - 1))];
 		if (!v.empty() && (v.back().end >> 16) >= (beg[k] >> 16)) v.back().end = end[k];
 		else v.push_back(BiChunk{beg[k], end[k]});
 		const int64_t c = c0[k + 1] - c0[k];
@@ -260,17 +285,36 @@ inline int32_t bi_long_contig(int32_t n_ref, const int32_t *ref_len)
 		if ((int64_t)ref_len[i] > BI_MAX_REF) return i;
 	return -1;
 }
-inline int64_t bi_windows(int32_t len) { return len > 0 ? ((int64_t)len + ((1 << BI_LIN_SHIFT) - 1)) >> BI_LIN_SHIFT : 0; }
+inline int64_t bi_windows(int32_t len, int min_shift) { return len > 0 ? ((int64_t)len + (((int64_t)1 << min_shift) - 1)) >> min_shift : 0; }
+// a CSI index's min_shift as used (0: 14), or -1 where it lies outside [10, 24]
+inline int32_t bi_csi_shift(int32_t min_shift)
+{
+	if (min_shift == 0) return BI_CSI_SHIFT_DEFAULT;
+	return min_shift >= BI_CSI_SHIFT_MIN && min_shift <= BI_CSI_SHIFT_MAX ? min_shift : -1;
+}
+// a CSI index's scheme for a header: the smallest depth, from the BAI's 5 on, at which bin 0 spans the longest contig.  No shallower than the
+// BAI's, so that at min_shift 14 every header the BAI can hold keeps the BAI's bins; 2^31 - 1 bases at min_shift 10 give the deepest, 7
+inline BiScheme bi_csi_scheme(int32_t min_shift, int32_t n_ref, const int32_t *ref_len)
+{
+	int64_t longest = 0;
+	for (int32_t i = 0; i < n_ref; ++i)
+		if (ref_len[i] > longest) longest = ref_len[i];
+	BiScheme sc = {min_shift, BI_BAI.depth};
+	while (((int64_t)1 << (sc.min_shift + 3 * sc.depth)) < longest) ++sc.depth;
+	return sc;
+}
 
-// -> BI_*.  Contigs of at most BI_MAX_REF bases; seg as in dev_bamsort.h.  BI_E_RULE: ix.err says which record and rule
-template <class Drv, class Src> int bi_run(Drv &drv, Src &src, const BiBlocks &B, int64_t hdr, int32_t n_ref, const int32_t *ref_len, int64_t seg, BiIndex &ix)
+// -> BI_*.  sc: the bin scheme, bin 0 of which spans every contig (BI_BAI: contigs of at most BI_MAX_REF bases); seg as in dev_bamsort.h.
+// BI_E_RULE: ix.err says which record and rule.  ix.refs[i].lin is the table of windows of 2^sc.min_shift bases, cut and backfilled
+template <class Drv, class Src> int bi_run(Drv &drv, Src &src, const BiBlocks &B, int64_t hdr, int32_t n_ref, const int32_t *ref_len, int64_t seg, BiIndex &ix, const BiScheme sc = BI_BAI)
 {
 	typedef typename Drv::Buf Buf;
 	ix = BiIndex();
+	ix.sc = sc;
 	ix.refs.resize((size_t)n_ref);
 	ix.n_slabs = B.n_slabs();
 	std::vector<int64_t> base((size_t)n_ref + 1, 0);
-	for (int32_t i = 0; i < n_ref; ++i) base[(size_t)i + 1] = base[(size_t)i] + bi_windows(ref_len[i]);
+	for (int32_t i = 0; i < n_ref; ++i) base[(size_t)i + 1] = base[(size_t)i] + bi_windows(ref_len[i], sc.min_shift);
 	const int64_t L = base[(size_t)n_ref];
 	Buf d_lin, d_base, d_len, d_words, buf, next, d_segs, d_off, d_rows, d_rec, d_scan, d_runs, d_chunks;
 	d_lin.alloc((size_t)L * 8);
@@ -325,8 +369,8 @@ template <class Drv, class Src> int bi_run(Drv &drv, Src &src, const BiBlocks &B
 			int64_t *cnt = (int64_t *)(vbeg + np), *flag = cnt + np;
 			d_scan.alloc((size_t)(np + 1) * 8 * 2);
 			int64_t *fx = d_scan.template as<int64_t>(), *cx = fx + np + 1;
-			drv.items("bi_rec", np, BiRecF{s, n, rec_off, R, n_ref, d_len.template as<int32_t>(), d_base.template as<int64_t>(), d_lin.template as<uint64_t>(), ix.n_records, rb, vbeg, cnt, words});
-			drv.items("bi_flag", np, BiFlagF{s, rec_off, rb, np, ix.n_records, n_ref, have_prev, prev_key, prev_rb, flag, words});
+			drv.items("bi_rec", np, BiRecF{s, n, rec_off, R, n_ref, d_len.template as<int32_t>(), d_base.template as<int64_t>(), d_lin.template as<uint64_t>(), ix.n_records, rb, vbeg, cnt, words, sc});
+			drv.items("bi_flag", np, BiFlagF{s, rec_off, rb, np, ix.n_records, n_ref, have_prev, prev_key, prev_rb, flag, words, sc});
 			const uint64_t err = (uint64_t)drv.get(&words[BI_W_ERR]);
 			if (err != BI_UNSET) { ix.err = err; return BI_E_RULE; }
 			drv.scan(flag, fx, np, "bi_scan");
@@ -342,7 +386,7 @@ template <class Drv, class Src> int bi_run(Drv &drv, Src &src, const BiBlocks &B
 			head = (int64_t *)q; q += n_runs; rc.c0 = (int64_t *)q; q += n_runs + 1; cs = (int64_t *)q; q += n_runs + 1; hx = (int64_t *)q; q += n_runs + 1;
 			sx = (int64_t *)q; q += n_runs + 1; rc.idx = (uint32_t *)q; idx = rc.idx + n_runs;
 			drv.items("bi_runs", np, BiRunsF{flag, fx, cx, rb, vbeg, np, B.voff(g0 + from), rc});
-			drv.sort_pairs(rc.key, skey, rc.idx, idx, n_runs, bi_key_bits(n_ref));
+			drv.sort_pairs(rc.key, skey, rc.idx, idx, n_runs, bi_key_bits(n_ref, sc));
 			drv.items("bi_head", n_runs, BiHeadF{skey, idx, rc, head, cs});
 			drv.scan(head, hx, n_runs, "bi_scan");
 			drv.scan(cs, sx, n_runs, "bi_scan");
@@ -396,6 +440,29 @@ inline std::vector<uint8_t> bi_serialise(const BiIndex &ix)
 		if (any) { put(BI_PSEUDO_BIN, 4); put(2, 4); put(r.vmin, 8); put(r.vmax, 8); put((uint64_t)r.n_mapped, 8); put((uint64_t)r.n_unmapped, 8); }
 		put((uint64_t)r.lin.size(), 4);
 		for (uint64_t v : r.lin) put(v, 8);
+	}
+	put((uint64_t)ix.n_no_coor, 8);
+	return o;
+}
+
+// the inflated bytes of the .csi (CSIv1) of an index built under a CSI scheme: bins ascending, each with its loffset -- the value of the first
+// window of its interval in the backfilled table, which a record of the bin has set at or behind it --, the meta-bin last in every contig that
+// holds a record, no aux block, no linear index, n_no_coor always.  Tens to thousands of bins: the lookup is the host's
+inline std::vector<uint8_t> bi_serialise_csi(const BiIndex &ix)
+{
+	std::vector<uint8_t> o;
+	auto put = [&](uint64_t v, int bytes) { for (int k = 0; k < bytes; ++k) o.push_back((uint8_t)(v >> (8 * k))); };
+	o.push_back('C'); o.push_back('S'); o.push_back('I'); o.push_back(1);
+	put((uint64_t)ix.sc.min_shift, 4); put((uint64_t)ix.sc.depth, 4); put(0, 4);
+	put((uint64_t)ix.refs.size(), 4);
+	for (const BiRef &r : ix.refs) {
+		const bool any = r.n_mapped + r.n_unmapped > 0;
+		put((uint64_t)r.bins.size() + (any ? 1 : 0), 4);
+		for (const auto &bn : r.bins) {
+			put(bn.first, 4); put(r.lin[(size_t)ix.sc.first_window(bn.first)], 8); put((uint64_t)bn.second.size(), 4);
+			for (const BiChunk &c : bn.second) { put(c.beg, 8); put(c.end, 8); }
+		}
+		if (any) { put(ix.sc.meta(), 4); put(0, 8); put(2, 4); put(r.vmin, 8); put(r.vmax, 8); put((uint64_t)r.n_mapped, 8); put((uint64_t)r.n_unmapped, 8); }
 	}
 	put((uint64_t)ix.n_no_coor, 8);
 	return o;

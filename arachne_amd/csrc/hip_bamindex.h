@@ -1,14 +1,15 @@
 // hip_bamindex.h -- dev_bamindex.h on the GPU, and the drivers behind arx_bam_index and arx_selftest_bam_index (arx_bgzf.hip): one coordinate-
 // sorted BAM file, its blocks inflated on the device slab by slab (inflate_launch over the rows of bgzf_walk, as the sort's copy mode), indexed
-// there by bi_run, and the .bai written as <path>.tmp and renamed.
+// there by bi_run, and the .bai written as <path>.tmp and renamed.  arx_bam_index_csi and arx_selftest_bam_index_csi are the same drivers under
+// the scheme of a CSI index (bi_csi_scheme), serialised by bi_serialise_csi and written as BGZF by the host sink's own zlib path (BamSink).
 //
 //   k_bs_items<F>    hip_bamsort.h's kernel: one item of a functor per thread (bi_tail: the one last record; bi_rec, bi_flag, bi_runs: a record;
 //                    bi_head, bi_chunks: a run), started through hip_launch under the functor's name
 // The run sort is rocprim::radix_sort_pairs over the key bits that can differ (bi_key_bits), the prefix sums are rocprim's scan.  The stream,
 // every buffer and rocprim's scratch are owners of hip_res.h.
 //
-// Memory: the compressed file in host memory whole (BsFile); on the device the linear table (8 bytes per 16384 bases of the contigs) for the
-// whole call, and one slab at a time: its compressed and inflated bytes, the carry in front, 16 bytes per block, 56 per record, about 100 per run.
+// Memory: the compressed file in host memory whole (BsFile); on the device the window table (8 bytes per 16384 bases of the contigs; per 2^min_shift
+// bases under a CSI scheme) for the whole call, and one slab at a time: its compressed and inflated bytes, the carry in front, 16 bytes per block, 56 per record, about 100 per run.
 #pragma once
 #include <stdio.h>
 #include "hip_bamsort.h"
@@ -85,7 +86,13 @@ inline void bi_stats(int64_t *stats, const BiHipDrv &drv, const BiIndex &ix, int
 
 inline std::string bi_long_text(int32_t i, int64_t len)
 {
-	return "contig " + std::to_string(i) + " has " + std::to_string(len) + " bases, more than the 2^29 a BAI index can hold (the CSI format is not built)";
+	return "contig " + std::to_string(i) + " has " + std::to_string(len) + " bases, more than the 2^29 a BAI index can hold (arx_bam_index_csi writes the CSI index of such a file)";
+}
+// under a CSI scheme: [7] the depth chosen in place of the linear entries, which a .csi does not hold, and [17] min_shift as used
+inline void bi_stats_csi(int64_t *stats, const BiScheme &sc)
+{
+	if (!stats) return;
+	stats[7] = sc.depth; stats[17] = sc.min_shift;
 }
 
 // a slab of the selftest: the stream lies in device memory already
@@ -135,8 +142,33 @@ inline int bi_result(int rc, const BiIndex &ix, const std::string &what, std::st
 	return ARX_E_IO;
 }
 
-// -> ARX_*; err: the text
-inline int bi_index_file(int device, const char *path, const char *bai_path, int64_t max_bytes, bool timed, int64_t *stats, std::string &err)
+// the index's bytes as <final_path>.tmp, renamed at the end; bgzf: as BGZF blocks of at most 65,280 input bytes with the EOF block last, compressed
+// by the host sink's zlib path
+inline bool bi_write_file(const std::vector<uint8_t> &out, const std::string &final_path, bool bgzf, std::string &err)
+{
+	const std::string tmp_path = final_path + ".tmp";
+	FILE *f = fopen(tmp_path.c_str(), "wb");
+	if (!f) { err = "cannot write " + tmp_path; return false; }
+	bool done;
+	if (bgzf) {
+		BamSink sink;
+		sink.f = f;
+		sink.pending = out;
+		done = sink.close(); // every block of what is pending, the EOF block, fclose
+	} else {
+		const bool wrote = fwrite(out.data(), 1, out.size(), f) == out.size();
+		done = (fclose(f) == 0) && wrote;
+	}
+	if (!done || rename(tmp_path.c_str(), final_path.c_str()) != 0) {
+		remove(tmp_path.c_str());
+		err = "cannot write " + final_path;
+		return false;
+	}
+	return true;
+}
+
+// -> ARX_*; err: the text.  csi_shift: 0 for the .bai, else the min_shift of the .csi (bi_csi_shift's result)
+inline int bi_index_file(int device, const char *path, const char *bai_path, int64_t max_bytes, bool timed, int64_t *stats, std::string &err, int32_t csi_shift = 0)
 {
 	const double t_begin = bs_now_us();
 	BsFile file;
@@ -157,7 +189,9 @@ inline int bi_index_file(int device, const char *path, const char *bai_path, int
 		if (!file.host_inflate(b, head)) { err = std::string(path) + ": BGZF block " + std::to_string(b) + " does not inflate"; return ARX_E_IO; }
 	}
 	if (hdr > file.total) { err = std::string(path) + ": the BAM header is cut short"; return ARX_E_IO; }
-	const int32_t too_long = bi_long_contig(n_ref, ref_len.data());
+	const bool csi = csi_shift != 0;
+	const BiScheme sc = csi ? bi_csi_scheme(csi_shift, n_ref, ref_len.data()) : BI_BAI;
+	const int32_t too_long = csi ? -1 : bi_long_contig(n_ref, ref_len.data());
 	if (too_long >= 0) { err = std::string(path) + ": " + bi_long_text(too_long, ref_len[(size_t)too_long]); return ARX_E_ARG; }
 	std::vector<int32_t> isize((size_t)nb);
 	for (int64_t b = 0; b < nb; ++b) isize[(size_t)b] = file.rows[(size_t)b].isize;
@@ -174,24 +208,17 @@ inline int bi_index_file(int device, const char *path, const char *bai_path, int
 	BiIndex ix;
 	{
 		BiFileSrc src{drv, file, B};
-		const int rc = bi_result(bi_run(drv, src, B, hdr, n_ref, ref_len.data(), BS_SEG_DEFAULT, ix), ix, path, err);
+		const int rc = bi_result(bi_run(drv, src, B, hdr, n_ref, ref_len.data(), BS_SEG_DEFAULT, ix, sc), ix, path, err);
 		if (rc != ARX_OK) return rc;
 	}
 	const double t_w = bs_now_us();
-	const std::vector<uint8_t> out = bi_serialise(ix);
-	const std::string final_path = bai_path ? std::string(bai_path) : std::string(path) + ".bai", tmp_path = final_path + ".tmp";
-	FILE *f = fopen(tmp_path.c_str(), "wb");
-	if (!f) { err = "cannot write " + tmp_path; return ARX_E_IO; }
-	const bool wrote = fwrite(out.data(), 1, out.size(), f) == out.size();
-	const bool closed = fclose(f) == 0;
-	if (!wrote || !closed || rename(tmp_path.c_str(), final_path.c_str()) != 0) {
-		remove(tmp_path.c_str());
-		err = "cannot write " + final_path;
-		return ARX_E_IO;
-	}
+	const std::vector<uint8_t> out = csi ? bi_serialise_csi(ix) : bi_serialise(ix);
+	const std::string final_path = bai_path ? std::string(bai_path) : std::string(path) + (csi ? ".csi" : ".bai");
+	if (!bi_write_file(out, final_path, csi, err)) return ARX_E_IO;
 	drv.us[BI_T_WRITE] = bs_now_us() - t_w;
 	drv.us[BI_T_TOTAL] = bs_now_us() - t_begin;
 	bi_stats(stats, drv, ix, file.total, nb);
+	if (csi) bi_stats_csi(stats, sc);
 	return ARX_OK;
 }
 

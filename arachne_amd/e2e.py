@@ -214,15 +214,19 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
 
 
 def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "host", chunk: int = 40_000_000, read_groups: str = "", bam_threads: int = 8,
-             level: int = 1, max_bytes: int = 0, lib_path: str = api.LIB_PATH, index: bool = False):
+             level: int = 1, max_bytes: int = 0, lib_path: str = api.LIB_PATH, index: "bool | str" = False):
     """The step the position buckets exist for: out_dir is a reference-layout directory (run(layout="reference") with the same chunk); every
     bucket of api.bucket_table that was written is sorted by coordinate on ref's GPU (BamWriter.sort_append) and appended, in table order, to ONE
     writer with reference_header(read_groups) and SO:coordinate; the unmapped file, which is its own sorted form (refID = pos = -1 throughout),
     is appended in copy mode.  Buckets hold disjoint, ascending ranges of (contig, position), so the concatenation is sorted.  sink as in run.
     -> dict(records, buckets, bytes, seconds, sort: the per-file stats).  index=True: the closed file's .bai is written beside it
-    (final_path + ".bai", api.bam_index on ref's device -- one more read of the file); the dict gains index (its stats) and index_seconds."""
+    (final_path + ".bai", api.bam_index on ref's device -- one more read of the file); the dict gains index (its stats) and index_seconds.
+    index="bai" is the same, and like the other names adds index_format ("bai" or "csi": what was written); "csi" writes final_path + ".csi" (api.bam_index_csi), the index that holds contigs above 2^29
+    bases, which api.bam_index refuses; "auto" writes the .csi where a contig exceeds 2^29 and the .bai otherwise."""
     if sink not in ("host", "device"):
         raise ValueError(f"unknown sink {sink!r}")
+    if not (index is False or index is True or index in ("bai", "csi", "auto")):
+        raise ValueError(f"unknown index {index!r}")
     names, offs, clens, alt, l_pac = ref.contigs()
     table = api.bucket_table(names, clens, chunk, lib_path=lib_path)
     t = time.time()
@@ -240,9 +244,14 @@ def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "hos
         st = w.close()
     out = dict(records=st["records"], buckets=len(per), bytes=st["bytes_out"], seconds=time.time() - t, sort=per)
     if index:
+        fmt = "bai" if index is True else index
+        if fmt == "auto":
+            fmt = "csi" if any(int(l) > api.BAI_MAX_CONTIG for l in clens) else "bai"
         t = time.time()
-        out["index"] = api.bam_index(final_path, device=ref.device, lib_path=lib_path)
+        out["index"] = (api.bam_index_csi if fmt == "csi" else api.bam_index)(final_path, device=ref.device, lib_path=lib_path)
         out["index_seconds"] = time.time() - t
+        if index is not True:               # a format that was asked for by name is named in the answer; True answers as it always has
+            out["index_format"] = fmt
     return out
 
 

@@ -362,7 +362,8 @@ int arx_selftest_bam_sort(int32_t device, const uint8_t *stream, int64_t n_bytes
  * Refused, with nothing written and no partial file left (the index is written as <bai>.tmp and renamed at the end):
  *   ARX_E_ARG  msg names the record (numbered from 0 in file order) and the rule: the keys ((uint32_t)refID, pos) are not non-decreasing, also
  *             across a slab border; a refID outside [-1, n_ref); refID >= 0 with pos < 0; an end beyond the record's contig length.  Also: a
- *             contig longer than 2^29, the BAI format's limit (the CSI format is not built); a file of 2^48 bytes or more; unknown flag bits
+ *             contig longer than 2^29, the BAI format's limit (the CSI index of such a file is arx_bam_index_csi's to write); a file of 2^48
+ *             bytes or more; unknown flag bits
  *   ARX_E_IO  the file is unreadable or not BGZF, a block does not inflate, there is no BAM header, the chain of block_size fields breaks or
  *             does not end with the stream, a record's name and CIGAR do not fit into its block_size, or the index cannot be written
  *   ARX_E_DEVICE  there is no such device, or a HIP error: there is no CPU fallback.  ARX_E_TOO_LARGE: a slab does not fit the device memory
@@ -384,6 +385,62 @@ int arx_selftest_bam_index(int32_t device, const uint8_t *stream, int64_t n_byte
                   int32_t n_ref, const int32_t *ref_len,
                   int64_t n_blocks, const int64_t *blk_at /* n_blocks + 1 file offsets */, const int32_t *blk_isize /* sum = n_bytes */,
                   int64_t seg_bytes, int64_t slab_bytes, uint8_t *out, int64_t out_cap, int64_t *out_len, int64_t *stats);
+
+/* ---- the same file's .csi (CSIv1, the companion of the SAM specification), for contigs of up to 2^31 - 1 bases: a sibling of arx_bam_index on
+ * the same device machinery (the functors of csrc/dev_bamindex.h carry the bin scheme as a value; the BAI is the scheme (14, 5)).  device, the
+ * sorted file, the slabs of max_bytes, the discovery and the lane per record are arx_bam_index's.  The contract:
+ *   virtual offsets  the file's blocks are b = 0 .. nb-1; at[b] is a block's file offset, ooff[b] where its bytes start in the inflated stream,
+ *             isize[b] its inflated size.  For an inflated offset o < total, b is the one block with ooff[b] <= o < ooff[b] + isize[b] (empty
+ *             blocks hold nothing) and V(o) = at[b] << 16 | (o - ooff[b]).  V(total) = at[b'] << 16 with b' the first block behind the last
+ *             non-empty one (normally the EOF block), or the file size where there is none.  A record that starts at o and is followed by one
+ *             at o' occupies [V(o), V(o')); the last record ends at V(total).  at must stay below 2^48
+ *   scheme    min_shift lies in [10, 24], 0 means 14, anything else is ARX_E_ARG.  depth is the smallest d >= 5 with 2^(min_shift + 3 d) >= the
+ *             longest contig of the header.  Every contig length up to 2^31 - 1 is accepted, so depth <= 7 and every bin number is below 2^22.
+ *             At min_shift 14 a header whose contigs are all <= 2^29 gives depth 5, the BAI's scheme; one contig of 2^29 + 1 gives depth 6.
+ *             The depth is never below the BAI's 5, whatever the contigs.  htslib adds 256 to the length before it chooses the depth and starts
+ *             from depth 0; we do neither: byte equality with `samtools index -c` is not claimed and was never checked
+ *   interval  beg = pos; end = pos + 1 where flag bit 4 is set, n_cigar_op is 0 or the operations consume no reference, otherwise pos + the
+ *             summed lengths of the operations M, D, N, = and X (0, 2, 3, 7, 8).  The record's own bin field is not read, and the CG-tag form
+ *             of CIGARs above 65,535 operations is not interpreted
+ *   bin       the first bin of level l is (8^l - 1) / 7.  bin(beg, end) is the deepest level l <= depth at which beg and end - 1 share
+ *             >> (min_shift + 3 (depth - l)), plus that shifted value; it is bin 0 where none does.  At (14, 5) this is the specification's
+ *             reg2bin (5.3) value for value
+ *   chunks    in file order a run is a maximal sequence of consecutive records with the same (refID, bin), from its first record's begin to
+ *             its last record's end; the runs of one bin, in file order, are its chunks; two neighbouring chunks are joined when
+ *             (earlier.end >> 16) >= (later.beg >> 16).  Bins are written in ascending order of their number.  htslib's folding of small bins
+ *             into their parents is NOT done
+ *   loffset   one table of windows of 2^min_shift bases per contig; a record sets the windows beg >> min_shift .. (end - 1) >> min_shift; a
+ *             window's value is the smallest V(start) among the records that set it; an unset window below the highest set one takes the
+ *             value of the next set window above it (the BAI's linear index at another window size).  A bin's loffset is the value of the
+ *             first window of the bin's interval, which is never above the highest set one: a record of the bin sets a window at or behind
+ *             it.  This is htslib's rule (update_loff), a valid lower bound for a reader that walks from the leaf bin of beg to earlier
+ *             siblings and parents until a bin exists, because the table does not decrease in a sorted file
+ *   meta-bin  number (8^(depth+1) - 1) / 7 + 1 -- 37450 at depth 5, 299594 at depth 6, 2396746 at depth 7 --, last in every contig that holds
+ *             a record, loffset 0, two chunks: (V(first record), end of the last record) and (records without flag bit 4, records with it)
+ *   bytes     "CSI\1", min_shift, depth, l_aux = 0, n_ref (int32 each); per contig n_bin; per bin: bin (uint32), loffset (uint64), n_chunk
+ *             (int32), the chunks (two uint64 each); then n_no_coor (uint64), always written.  A contig without records has n_bin = 0.  There
+ *             is no linear index and no tabix aux block in the file
+ *   file      those bytes as BGZF: blocks of at most 65,280 input bytes, the 28-byte EOF block last, compressed on the host by zlib (the host
+ *             sink's code).  The inflated bytes are what this contract pins; the compressed ones are not
+ * Refused, with nothing written and no partial file left (the index is written as <csi>.tmp and renamed at the end):
+ *   ARX_E_ARG  msg names the record (numbered from 0 in file order) and the rule: the keys ((uint32_t)refID, pos) are not non-decreasing, also
+ *             across a slab border; a refID outside [-1, n_ref); refID >= 0 with pos < 0; an end beyond the record's contig length.  Also: a
+ *             min_shift outside [10, 24] that is not 0; a file of 2^48 bytes or more; unknown flag bits
+ *   ARX_E_IO  the file is unreadable or not BGZF, a block does not inflate, there is no BAM header, the chain of block_size fields breaks or
+ *             does not end with the stream, a record's name and CIGAR do not fit into its block_size, or the index cannot be written
+ *   ARX_E_DEVICE  there is no such device, or a HIP error: there is no CPU fallback.  ARX_E_TOO_LARGE: a slab does not fit the device memory
+ * stats[20] (may be NULL) as arx_bam_index's, except: [7] the depth chosen, [17] min_shift as used. */
+int arx_bam_index_csi(int32_t device, const char *bam_path, const char *csi_path /* NULL: bam_path + ".csi" */, int32_t min_shift /* 0: 14 */,
+                  int64_t max_bytes /* inflated bytes of a slab; 0: 256 MiB */, int32_t flags /* ARX_BAI_TIMED or 0 */,
+                  int64_t *stats /* [20], may be NULL */, char *msg, int32_t msg_cap);
+/* self-test of the same indexing on an inflated stream in host memory (tests/test_bam_index_csi_gpu.py): arx_selftest_bam_index's arguments,
+ * with min_shift behind slab_bytes.  out[0..*out_len) receives the INFLATED bytes of the .csi, which arx_bam_index_csi compresses
+ * (ARX_E_TOO_LARGE: out_cap is too small, nothing is written).  Codes as above, without a text; on a refusal by a record rule stats[9] is
+ * the record's number << 8 | the rule (1 fields, 2 refID, 3 pos, 4 end, 5 order). */
+int arx_selftest_bam_index_csi(int32_t device, const uint8_t *stream, int64_t n_bytes, int64_t hdr,
+                  int32_t n_ref, const int32_t *ref_len,
+                  int64_t n_blocks, const int64_t *blk_at /* n_blocks + 1 file offsets */, const int32_t *blk_isize /* sum = n_bytes */,
+                  int64_t seg_bytes, int64_t slab_bytes, int32_t min_shift, uint8_t *out, int64_t out_cap, int64_t *out_len, int64_t *stats);
 
 /* ---- in front of the feeder: a FASTQ file pair sorted by barcode on the GPU -- the reference's `arachne preprocess`
  * (src/preprocess/preprocess.go:42-114: samtools import -T '*' | samtools sort -t BX | samtools fastq -T '*'), which the aligner needs: the

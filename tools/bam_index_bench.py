@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""The .bai of a coordinate-sorted BAM file on the GPU (arx_bam_index), phase by phase, next to the sort that made the file.
+"""The .bai or the .csi of a coordinate-sorted BAM file on the GPU (arx_bam_index, arx_bam_index_csi), phase by phase, next to the sort that
+made the file.
 
 The bucket of tools/bam_sort_bench.py (--records typical 2x150 bp records on random positions of one contig, written by the host sink) is
 sorted into one file by arx_bam_sort_append (host writer), and that file is indexed.  One JSON line per measurement:
   append   arx_bam_sort_append of the bucket into the host writer: the seconds of the call and of the close that follows
   index    arx_bam_index of the sorted file, plain and with ARX_BAI_TIMED (which waits for every launch): the phases in ms, the counts
-           of runs, chunks, bins and linear entries, and max_bytes (0: the 256 MiB default; --slab sets a second size)
-Usage: bam_index_bench.py [--records 2000000] [--repeats 3] [--slab 33554432]"""
+           of runs, chunks, bins and linear entries, and max_bytes (0: the 256 MiB default; --slab sets a second size).  --format csi:
+           arx_bam_index_csi of the same file at min_shift 14 (the BAI's scheme on these contigs): depth in place of the linear entries
+Usage: bam_index_bench.py [--records 2000000] [--repeats 3] [--slab 33554432] [--format bai|csi]"""
 import argparse
 import json
 import os
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--records", type=int, default=2_000_000)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--slab", type=int, default=32 << 20)
+    ap.add_argument("--format", choices=("bai", "csi"), default="bai")
     args = ap.parse_args()
     tmp = "/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir()
     d = tempfile.mkdtemp(prefix="arx_index_bench_", dir=tmp)
@@ -56,11 +59,13 @@ def main():
             for max_bytes in (0, args.slab):
                 for timed in (False, True):
                     t = time.time()
-                    st = api.bam_index(final, max_bytes=max_bytes, timed=timed, device=ref.device)
+                    st = (api.bam_index_csi if args.format == "csi" else api.bam_index)(final, max_bytes=max_bytes, timed=timed, device=ref.device)
                     dt = time.time() - t
                     assert st["records"] == args.records
-                    print(json.dumps(dict(what="index", counted=rep > 0, max_bytes=max_bytes, timed=timed, seconds=round(dt, 4), slabs=st["slabs"], blocks=st["blocks"],
-                                          runs=st["runs"], chunks=st["chunks"], bins=st["bins"], linear=st["linear"], bai_bytes=os.path.getsize(final + ".bai"),
+                    own = dict(depth=st["depth"], min_shift=st["min_shift"], csi_bytes=os.path.getsize(final + ".csi")) if args.format == "csi" else \
+                        dict(linear=st["linear"], bai_bytes=os.path.getsize(final + ".bai"))
+                    print(json.dumps(dict(what="index", format=args.format, counted=rep > 0, max_bytes=max_bytes, timed=timed, seconds=round(dt, 4), slabs=st["slabs"],
+                                          blocks=st["blocks"], runs=st["runs"], chunks=st["chunks"], bins=st["bins"], **own,
                                           ms={p: round(st[p + "_us"] / 1e3, 3) for p in PHASES})), flush=True)
         ref.close()
     finally:
