@@ -1068,6 +1068,17 @@ class Batch:
         self.ref._check(self.ref.lib.arx_batch_debug_chains(self.ref.h, self.h, off.ctypes.data, n.ctypes.data, ch.ctypes.data, sd.ctypes.data))
         return off, n, ch, sd
 
+    def debug_chain_class(self):
+        """arx_batch_debug_chain_class: the split chaining's classification of the last chaining stage -> (who per read, the heavy list, the
+        mid list as far as it was filled, reads that asked for a place on the mid list, its capacity)."""
+        who = np.zeros(self.n_reads, dtype=np.uint8)
+        heavy = np.zeros(self.n_reads, dtype=np.int32)
+        mid = np.zeros(self.n_reads // 4 + 64, dtype=np.int32)
+        n = np.zeros(3, dtype=np.int32)
+        self.ref.lib.arx_batch_debug_chain_class.argtypes = [C.c_void_p] * 6     # (here, not in _load: ARX_LIB may name a build from before this entry)
+        self.ref._check(self.ref.lib.arx_batch_debug_chain_class(self.ref.h, self.h, who.ctypes.data, heavy.ctypes.data, mid.ctypes.data, n.ctypes.data))
+        return who, heavy[:n[0]], mid[:min(int(n[1]), int(n[2]))], int(n[1]), int(n[2])
+
     def debug_core(self):
         T = self.counts()["n_occ"]
         n = np.zeros(self.n_reads, dtype=np.int32)
@@ -1528,6 +1539,13 @@ class MultiReference:
         if self.h:
             self.lib.arx_multi_close(self.h)
             self.h = None
+
+
+def side_streams_default(lib_path: str = LIB_PATH) -> bool:
+    """arx_side_streams_default: do batch handles of this process use their side streams when ARX_AUX_STREAM is unset?"""
+    lib = _load(lib_path)
+    lib.arx_side_streams_default.restype = C.c_int32
+    return bool(lib.arx_side_streams_default())
 
 
 def worth_running_rfa(barcode: str, n_pairs: int, unique: bool = True) -> bool:

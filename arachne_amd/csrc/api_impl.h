@@ -655,6 +655,19 @@ template <class RT> struct Batch {
 			b->rt.d2h(seeds, b->work.sout, sizeof(arx::Seed) * (size_t)b->work.T);)                                                 \
 		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
+	int arx_batch_debug_chain_class(arx_ctx *h, arx_batch *bh, uint8_t *who, int32_t *heavy_list, int32_t *mid_list, int32_t *n)    \
+	{                                                                                                                               \
+		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \
+		if (!b->work.cout || !b->work.chain_who) { c->set_error("arx_batch_debug_chain_class: the last chaining stage ran unsplit"); return ARX_E_ARG; } \
+		ARX_TRY(c, b->rt.bind();                                                                                                    \
+			const size_t R = (size_t)b->db.n_reads, cap = (size_t)b->work.chain_mid_cap;                                            \
+			n[0] = n[1] = 0; n[2] = (int32_t)cap;                                                                                   \
+			b->rt.d2h(who, b->work.chain_who, R);                                                                                   \
+			b->rt.d2h(heavy_list, b->work.chain_heavy_list, 4 * R);                                                                 \
+			b->rt.d2h(n, b->work.chain_heavy_list + R, 4);                                                                          \
+			if (cap) { b->rt.d2h(mid_list, b->work.chain_mid_list, 4 * cap); b->rt.d2h(n + 1, b->work.chain_mid_list + cap, 4); })  \
+		return ARX_OK;                                                                                                              \
+	}                                                                                                                               \
 	int arx_batch_debug_core(arx_ctx *h, arx_batch *bh, int32_t *n_core, arx_reg *regs)                                             \
 	{                                                                                                                               \
 		Ctx *c = (Ctx *)h; Bat *b = (Bat *)bh;                                                                                      \

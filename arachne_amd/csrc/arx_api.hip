@@ -24,6 +24,11 @@ template <> struct ItemsWpe<KReg2Aln> { static constexpr int v = ARX_WPE_REG2ALN
 #endif
 }
 
+// When the library is loaded, in front of the registration of this library's device code and of every HIP call it makes: the hardware queues
+// the batch handles' main and side streams need, and whether they will have them (switches.h sw_request_hw_queues)
+__attribute__((constructor(101))) static void arx_request_hw_queues() { arx::sw_request_hw_queues(); }
+extern "C" int32_t arx_side_streams_default(void) { return arx::sw_side_streams_have_queues() ? 1 : 0; }
+
 ARX_DEFINE_C_API(arx::HipRT)
 
 namespace arx { const IndexView *ctx_index_view(::arx_ctx *ctx) { return ctx ? &((Context<HipRT> *)ctx)->ix : nullptr; } }

@@ -99,7 +99,7 @@ template <> void HipRT::run_rescue_heavy<KRescueStep>(const char *nm, int n, con
 	allow_dynamic_lds(k_rescue_heavy, RESCUE_LDS_REGS * sizeof(Reg));
 	int32_t *cur = alloc<int32_t>(4);
 	memset0(cur, 16);
-	on_aux([&]() { // beside the thread-per-pair launch of the same round (the caller joins before it reads the round's task count)
+	on_aux(AUX_RESCUE, [&]() { // beside the thread-per-pair launch of the same round (the caller joins before it reads the round's task count)
 		Scope sc(*this, nm, n);
 		// footprints: 170 / 340 / 680 records = 15 / 30 / 60 KB of dynamic LDS beside the 17 KB of sort scratch: 5 / 3 / 2 workgroups per CU
 		const int caps[4] = {0, split ? 170 : 0, split ? 340 : 0, RESCUE_LDS_REGS};
@@ -191,9 +191,9 @@ template <> void HipRT::run_chain_heavy<KChain>(const char *nm, int n_reads, con
 	allow_dynamic_lds(k_chain_heavy, lds_l); // 128 KB
 	// f.n_heavy[0]: the list's length (stays on the device), [1] and [2]: the two launches' cursors into it
 	const int l_div = sw.chain_l_div; // the long ones' launch holds 128 KB of LDS per workgroup: on n_cu / l_div CUs
-	on_aux([&]() { start("k_chain_heavy (long)", k_chain_heavy, dim3(n_cu / (l_div > 0 ? l_div : 1)), dim3(64), lds_l, f, CHAIN_LDS_SMALL + 1, CHAIN_LDS_OCC, f.n_heavy + 2, wave); }); // the few long ones (beside the rest with ARX_AUX_STREAM=1)
+	// both on the launching stream, one after the other: the side stream is KChainMid's (Pipeline::stage_chain), behind which the long launch would queue
+	start("k_chain_heavy (long)", k_chain_heavy, dim3(n_cu / (l_div > 0 ? l_div : 1)), dim3(64), lds_l, f, CHAIN_LDS_SMALL + 1, CHAIN_LDS_OCC, f.n_heavy + 2, wave); // the few long ones
 	start("k_chain_heavy (short)", k_chain_heavy, dim3(n_cu * 4), dim3(64), lds_s, f, 0, CHAIN_LDS_SMALL, f.n_heavy + 1, wave); // (a third launch for reads of up to 128 occurrences at half the LDS changed nothing: round 3)
-	aux_join();
 #ifdef ARX_CHAIN_STATS
 	{ unsigned long long h[24], z[24] = {0}; hipStreamSynchronize(stream); hipMemcpyFromSymbol(h, HIP_SYMBOL(g_cstat), sizeof h); hipMemcpyToSymbol(HIP_SYMBOL(g_cstat), z, sizeof z);
 	  fprintf(stderr, "cstat reads %llu | sums (100 MHz ticks): chaining %llu traverse+weights %llu sort %llu filter %llu output %llu | worst read: total %llu = %llu %llu %llu %llu %llu, n_occ %llu kept %llu\n",
@@ -295,6 +295,18 @@ template <> void HipRT::run_dedup_heavy<KDedup>(const char *nm, int n_reads, con
 	int32_t *eh_pool = alloc<int32_t>((size_t)blocks * f.eh_words + 16);
 	start("k_dedup_heavy", k_dedup_heavy, dim3(blocks), dim3(64), 0, f, eh_pool);
 	wsort_report(stream, nm);
+}
+
+template <> bool HipRT::run_dedup_forked<KDedup>(const char *nm, const char *nm_heavy, int n_reads, const KDedup &f)
+{
+	if (!aux_on(AUX_DEDUP) || n_reads <= 0) return false;
+	Scope sc(*this, nm, n_reads); // one scope, as the unforked launch has: the listing pass is part of it
+	items_kernel(nm, n_reads, KDedupList{f}, INT_MAX);
+	on_aux(AUX_DEDUP, [&]() { run_dedup_heavy(nm_heavy, n_reads, f); });
+	KDedup light = f;
+	light.listed = 1;
+	items_kernel(nm, n_reads, light, max_blocks()); // (per-slot scratch: the capped grid, as launch_cold gives it)
+	return true;
 }
 
 template <class F> struct ColdUsesSlots { static const bool value = true; };

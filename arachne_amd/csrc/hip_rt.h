@@ -59,22 +59,42 @@ struct HipRT {
 	static BwtSaFn bwt_sa_fn() { return product_bwt_sa; } // arx_index_build: the suffix sort runs in HBM
 	Stream own_stream;      // declared before everything that is used on it: it is the last to go, and waits for what is on it
 	hipStream_t stream = 0; // the stream of the next launch: own_stream, or the side stream inside on_aux
-	// side stream for launches that are one wavefront's tail (the heavy-item kernels): they run beside the launches that follow on the main
-	// stream until aux_join().  Off unless sw.aux_stream
-	Stream aux; Event ev_fork, ev_join; bool aux_pending = false;
-	template <class L> void on_aux(L f)
+	// side streams for launches that keep a few wavefronts busy (the heavy-item kernels, the above-cap reads' chaining walk, one CIGAR band
+	// class): they run beside the launches that follow on the main stream until aux_join().  Several forks may precede one join: a side
+	// stream runs its forks in order and the join waits for the last of each.  There are two (`lane`), for the one stage with three launches
+	// side by side (the split chaining); every other fork is on the first.  A part whose switch is off (aux_on) runs f on the main stream.
+	// Lifetime rule: everything a side-stream launch touches is arena memory of the current stage, and aux_join() runs before the stage
+	// returns, before any arena_rewind and before any host read-back of what the launch wrote.
+	static constexpr int AUX_LANES = 2;
+	Stream aux[AUX_LANES]; Event ev_fork, ev_join[AUX_LANES]; bool aux_pending[AUX_LANES] = {false, false};
+	bool aux_on(AuxPart p) const { return sw.aux_stream && (p == AUX_CHAIN ? sw.aux_chain : p == AUX_DEDUP ? sw.aux_dedup : p == AUX_NW ? sw.aux_nw : sw.aux_rescue); }
+	template <class L> void on_aux(AuxPart part, L f, int lane = 0)
 	{
-		if (!sw.aux_stream) { f(); return; }
-		if (!aux) { aux.create(); ev_fork.create(hipEventDisableTiming); ev_join.create(hipEventDisableTiming); }
-		ARX_HIP_CHECK(hipEventRecord(ev_fork, stream)); ARX_HIP_CHECK(hipStreamWaitEvent(aux, ev_fork, 0));
+		if (!aux_on(part)) { f(); return; }
+		if (!ev_fork) ev_fork.create(hipEventDisableTiming);
+		if (!aux[lane]) { aux[lane].create(); ev_join[lane].create(hipEventDisableTiming); }
+		ARX_HIP_CHECK(hipEventRecord(ev_fork, stream)); ARX_HIP_CHECK(hipStreamWaitEvent(aux[lane], ev_fork, 0));
 		hipStream_t main_stream = stream;
-		stream = aux;
+		stream = aux[lane];
 		try { f(); } catch (...) { stream = main_stream; throw; } // (a launch that fails in f must not leave the runtime on the side stream)
 		stream = main_stream;
-		ARX_HIP_CHECK(hipEventRecord(ev_join, aux));
-		aux_pending = true;
+		ARX_HIP_CHECK(hipEventRecord(ev_join[lane], aux[lane]));
+		aux_pending[lane] = true;
 	}
-	void aux_join() { if (aux_pending) { ARX_HIP_CHECK(hipStreamWaitEvent(stream, ev_join, 0)); aux_pending = false; } }
+	void aux_join()
+	{
+		for (int l = 0; l < AUX_LANES; ++l) if (aux_pending[l]) { ARX_HIP_CHECK(hipStreamWaitEvent(stream, ev_join[l], 0)); aux_pending[l] = false; }
+	}
+	// one scope, two launches over the same n items with whatever `between` starts (forks with scopes of their own) in between: a pass that
+	// classifies the items and the launch that takes what the pass left
+	template <class FC, class FL, class B> void launch_classified(const char *nm, int n, const FC &classify, const FL &rest, B between)
+	{
+		if (n <= 0) return;
+		Scope sc(*this, nm, n);
+		items_kernel(nm, n, classify, INT_MAX);
+		between();
+		items_kernel(nm, n, rest, sw.wide ? INT_MAX : max_blocks());
+	}
 	// every launch of the runtime: on the current stream (the side stream inside on_aux), checked at once under its name (hip_launch.h)
 	template <class... P> void start(const LaunchName &name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, typename as_declared<P>::type... args) { hip_launch(name, kernel, grid, block, lds_bytes, stream, args...); }
 	// a kernel's opt-in to `bytes` of dynamic LDS.  It applies to the device that is current when it is made, so it is made once per runtime (=
@@ -298,6 +318,9 @@ struct HipRT {
 	template <class F> void run_chain_group(const char *nm, int n_reads, const F &f);
 	bool dedup_heavy_ok() const { return sw.dedup_heavy; }
 	template <class F> void run_dedup_heavy(const char *nm, int n_reads, const F &f); // likewise the region lists of such reads (f.eh_words ints of scratch per workgroup)
+	// the de-duplication with its heavy reads listed by a pass of their own (KDedupList), then k_dedup_heavy on the side stream beside the
+	// thread-per-read launch; false (nothing launched) where the side stream's dedup part is off.  The caller joins
+	template <class F> bool run_dedup_forked(const char *nm, const char *nm_heavy, int n_reads, const F &f);
 	template <class F> void launch_cold_impl(const char *nm, int n, const F &f, bool wide = false) { launch_items(nm, n, f, wide && sw.wide ? INT_MAX : max_blocks()); }
 	// one work item per BLOCK_LANES-lane workgroup (hip_block.h); f(item, HipBlock&)
 	// small (host, may be null): small[i] = 1 sends item i to a SMALL_LANES-lane workgroup
@@ -660,15 +683,24 @@ struct HipRT {
 		int32_t *punt = alloc<int32_t>((size_t)n + 4), *n_punt = punt + n;
 		memset0(n_punt, 16);
 		nw_n_punt = n_punt;
-		for (int c = 0; c < NW_CLASSES; ++c) {
+		auto run_class = [&](int c) {
 			const int nc = n_class[c];
-			if (nc <= 0) continue;
+			if (nc <= 0) return;
 			Scope sc(*this, nm, nc);
 			NwArgs A{f.ix, f.bases, f.base_off, f.lens, f.preg_off, f.n_regs, f.n_reads, f.pregs, f.alns, f.cig, f.cig_w, zbuf, z_off, f.nw_list, f.err,
 			         f.class_list + (size_t)c * f.class_stride, punt, n_punt};
 			static constexpr NwKernel by_class[NW_CLASSES] = {k_reg2aln_nw_g16<1, 2>, k_reg2aln_nw_g16<2, 4>, k_reg2aln_nw_g16<4, 8>, k_reg2aln_nw_g16<8, 16>, k_reg2aln_nw_g16<16, 16>};
 			start({"k_reg2aln_nw_g16", nm, c}, by_class[c], dim3(coop_blocks(nc)), dim3(64), 0, A, nc, nullptr);
-		}
+		};
+		// class 2 (<4, 8>) beside the others: 3.4 ms against 0.9 + 2.5 + 1.4 ms per batch for classes 0, 1 and 3 (class 4 is all but empty), the
+		// most even split of the measured class times.  A class touches its own regions' slots and appends to the punt list by atomics; the
+		// join comes before the launch that reads n_punt
+		constexpr int side_class = 2;
+		if (aux_on(AUX_NW)) {
+			if (n_class[side_class] > 0) on_aux(AUX_NW, [&]() { run_class(side_class); });
+			for (int c = 0; c < NW_CLASSES; ++c) if (c != side_class) run_class(c);
+		} else for (int c = 0; c < NW_CLASSES; ++c) run_class(c); // one stream: the classes in their order
+		aux_join();
 		{ // what the class kernels handed on (a third band, or a doubled band past the class's second tiling): all tilings, length read on the device
 			Scope sc(*this, nm, 0);
 			NwArgs A{f.ix, f.bases, f.base_off, f.lens, f.preg_off, f.n_regs, f.n_reads, f.pregs, f.alns, f.cig, f.cig_w, zbuf, z_off, f.nw_list, f.err, punt, punt, n_punt + 1};

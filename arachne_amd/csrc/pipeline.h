@@ -302,6 +302,25 @@ struct KChainMid { // the listed reads of KChain, one thread each; the list's le
 	KChain f;
 	ARX_DEV void operator()(int i, int) const { const int n = *f.n_mid < f.mid_cap ? *f.n_mid : f.mid_cap; if (i < n) f.one(f.mid_list[i]); }
 };
+// KChain's classification as a pass of its own (the split chaining: ARX_CHAIN_SPLIT=1).  It reads occ_off alone, fills heavy_list and
+// mid_list by KChain's rules -- a read the full mid list turns away is nobody's -- and writes who chains each read, so that the light reads'
+// launch (KChainLight), KChainMid and the heavy launches can start together
+constexpr uint8_t CHAIN_BY_LIGHT = 0, CHAIN_BY_HEAVY = 1, CHAIN_BY_MID = 2;
+struct KChainClass {
+	KChain f; uint8_t *who;
+	ARX_DEV void operator()(int r, int) const
+	{
+		const int n = f.occ_off[r + 1] - f.occ_off[r];
+		uint8_t w = CHAIN_BY_LIGHT;
+		if (f.heavy_list && n >= f.heavy_min && n <= CHAIN_LDS_OCC) { f.heavy_list[ARX_ATOMIC_ADD(f.n_heavy, 1)] = r; w = CHAIN_BY_HEAVY; }
+		else if (f.mid_list && n >= f.mid_min) { const int at = ARX_ATOMIC_ADD(f.n_mid, 1); if (at < f.mid_cap) { f.mid_list[at] = r; w = CHAIN_BY_MID; } }
+		who[r] = w;
+	}
+};
+struct KChainLight { // exactly the reads nobody listed
+	KChain f; const uint8_t *who;
+	ARX_DEV void operator()(int r, int) const { if (who[r] == CHAIN_BY_LIGHT) f.one(r); }
+};
 
 // per read: set up one state machine per chain (chain gid = chain_off[read] + index) and remember the chain's read
 struct KExtInit {
@@ -397,9 +416,11 @@ struct KDedup {
 	int32_t *clean; // what the rescue stage may assume about the list (matesw_apply): 2 = went through the pass with >= 2 regions and nothing was merged,
 	                // so it is a fixed point of the pass mem_matesw repeats; 1 = fewer than two regions; 0 = a merge happened, nothing is known
 	int32_t *heavy_list, *n_heavy; int32_t heavy_min; // null: every read by its own thread
+	int32_t listed = 0; // 1: KDedupList has filled heavy_list already (k_dedup_heavy runs beside this launch): the heavy reads are only skipped
+	ARX_DEV bool heavy(int r) const { return heavy_list && n_ext[r] >= heavy_min && n_ext[r] <= DEDUP_LDS_REGS; }
 	ARX_DEV void operator()(int r, int slot) const
 	{
-		if (heavy_list && n_ext[r] >= heavy_min && n_ext[r] <= DEDUP_LDS_REGS) { heavy_list[ARX_ATOMIC_ADD(n_heavy, 1)] = r; return; }
+		if (heavy(r)) { if (!listed) heavy_list[ARX_ATOMIC_ADD(n_heavy, 1)] = r; return; }
 		one_thread(r, eh + (size_t)slot * eh_words);
 	}
 	ARX_DEV void one_thread(int r, int32_t *eh_slot) const
@@ -414,6 +435,17 @@ struct KDedup {
 		n_core[r] = n;
 	}
 };
+
+// KDedup's rule for the heavy reads as a pass of its own: it reads n_ext alone, so the list is whole before KDedup starts and k_dedup_heavy
+// can run beside it (HipRT::run_dedup_forked)
+struct KDedupList {
+	KDedup f;
+	ARX_DEV void operator()(int r, int) const { if (f.heavy(r)) f.heavy_list[ARX_ATOMIC_ADD(f.n_heavy, 1)] = r; }
+};
+// HipRT has side streams (aux_on / on_aux / launch_classified / run_dedup_forked); the host test double has one stream's worth of order only:
+// there a fork runs where it stands (Pipeline::fork)
+template <class R, class = void> struct HasSideStream { static constexpr bool value = false; };
+template <class R> struct HasSideStream<R, decltype((void)std::declval<const R &>().aux_on(AUX_DEDUP))> { static constexpr bool value = true; };
 
 // capacity of each read's final region list: core regions + one rescue per eligible anchor of the mate (<= 50)
 struct KPairCap {
@@ -635,6 +667,9 @@ public:
 	struct Work {
 		Biv *intv = 0; int32_t *n_intv = 0, *n_occ = 0, *occ_off = 0; Seed *occ_seed = 0; int32_t *occ_rid = 0;  // seeding and locate
 		int32_t *n_chain = 0; Chain *cout = 0; Seed *sout = 0;                                                   // chaining
+		// the split chaining's classification (null: the stage ran unsplit), for arx_batch_debug_chain_class: who[r], and the two lists with
+		// their counters behind them (heavy_list[R] = its length; mid_list[mid_cap] = reads that asked for a place)
+		const uint8_t *chain_who = 0; const int32_t *chain_heavy_list = 0, *chain_mid_list = 0; int32_t chain_mid_cap = 0;
 		Reg *regs = 0; int32_t *n_core = 0, *core_clean = 0;                                                     // extension
 		int32_t *preg_off = 0, *n_regs = 0; Reg *pregs = 0;                                                      // rescue
 		Aln *alns = 0; uint32_t *cig = 0; int32_t *counter = 0; uint32_t *err = 0;                               // CIGARs; a counter and the error word for all
@@ -740,6 +775,9 @@ public:
 		return 0;
 	}
 
+	// a launch beside the ones that follow it, on the runtime's side stream `lane` where it has one (HipRT::on_aux, which has the lifetime rule)
+	template <class L> void fork(AuxPart part, L f, int lane = 0) { if constexpr (HasSideStream<RT>::value) rt.on_aux(part, f, lane); else f(); }
+
 	// ---- stage 3: chaining and chain filtering
 	void stage_chain(const DeviceBatch &b, Work &w)
 	{
@@ -763,10 +801,32 @@ public:
 		const int mid_min = sw.chain_mid_min; // 0: no launch of their own for the reads in between
 		const int mid_cap = R / 4 + 64; // the list holds a quarter of the reads; a read beyond that is chained where it is found
 		if (mid_min > 0 && k.heavy_list && !k.grp_max) { k.mid_list = rt.template alloc<int32_t>((size_t)mid_cap + 4); k.n_mid = k.mid_list + mid_cap; k.mid_min = mid_min; k.mid_cap = mid_cap; rt.memset0(k.n_mid, 16); }
+		w.chain_who = nullptr;
+		bool split = sw.chain_split && k.heavy_list && !k.grp_max; // on HipRT only where its launches then run side by side
+		if constexpr (HasSideStream<RT>::value) split = split && rt.aux_on(AUX_CHAIN);
+		if (split) {
+			// the split: a pass over occ_off makes both lists and says who chains each read; then the light reads on this stream, KChainMid on the
+			// first side stream and the heavy launches on the second start together.  Each writes the slices of its own reads only
+			uint8_t *who = rt.template alloc<uint8_t>((size_t)R + 8);
+			w.chain_who = who; w.chain_heavy_list = k.heavy_list; w.chain_mid_list = k.mid_list; w.chain_mid_cap = k.mid_list ? mid_cap : 0;
+			const KChainClass kc{k, who}; const KChainLight kl{k, who};
+			auto forks = [&]() {
+				if (k.mid_list) fork(AUX_CHAIN, [&]() { KChainMid km{k}; rt.launch_wide("chain", mid_cap, km); }, 0);
+				fork(AUX_CHAIN, [&]() { rt.run_chain_heavy("chain_heavy", R, k); }, 1);
+			};
+			if constexpr (HasSideStream<RT>::value) rt.launch_classified("chain", R, kc, kl, forks); // (one scope: the launch census counts scopes)
+			else { rt.launch_wide("chain", R, kc); forks(); rt.launch_wide("chain", R, kl); }
+			rt.aux_join();
+			if constexpr (HasHeavyCensus<RT>::value) rt.heavy_census_chain(R, k.heavy_list, k.n_heavy, w.occ_off, CHAIN_LDS_SMALL);
+			return;
+		}
 		rt.launch_wide("chain", R, k);
-		if (k.mid_list && !k.grp_max) { KChainMid km{k}; rt.launch_wide("chain", mid_cap, km); } // (the list's length is not on the host: threads beyond it return at once)
+		// KChain has made both lists.  KChainMid's length is the walk of the few reads above k_chain_heavy's cap, one thread each in HBM: on the
+		// side stream, so that the heavy launches (and nothing else of the batch) do not wait behind it.  The three write their own reads' slices
+		if (k.mid_list && !k.grp_max) fork(AUX_CHAIN, [&]() { KChainMid km{k}; rt.launch_wide("chain", mid_cap, km); }); // (the list's length is not on the host: threads beyond it return at once)
 		if constexpr (HasChainGroup<RT>::value) { if (k.grp_max) rt.run_chain_group("chain", R, k); }
 		if (k.heavy_list) rt.run_chain_heavy("chain_heavy", R, k); // the list's length stays on the device: no host round trip
+		rt.aux_join();
 		if constexpr (HasHeavyCensus<RT>::value) rt.heavy_census_chain(R, k.heavy_list, k.n_heavy, w.occ_off, CHAIN_LDS_SMALL);
 	}
 
@@ -825,8 +885,13 @@ public:
 		KDedup kd{ix, b.bases, b.base_off, b.lens, w.occ_off, n_ext, w.regs, rtmp, idx, eh, eh_words, w.n_core, w.core_clean, nullptr, nullptr,
 		          sw.dedup_heavy_min.value_or(DEDUP_HEAVY_MIN)};
 		if (rt.dedup_heavy_ok()) { kd.heavy_list = rt.template alloc<int32_t>(R + 4); kd.n_heavy = kd.heavy_list + R; rt.memset0(kd.n_heavy, 16); }
-		rt.launch_cold("dedup", R, kd);
-		if (kd.heavy_list) rt.run_dedup_heavy("dedup_heavy", R, kd);
+		bool forked = false; // the heavy reads listed first and k_dedup_heavy beside KDedup (the side stream's dedup part)
+		if constexpr (HasSideStream<RT>::value) { if (kd.heavy_list) forked = rt.run_dedup_forked("dedup", "dedup_heavy", R, kd); }
+		if (!forked) {
+			rt.launch_cold("dedup", R, kd);
+			if (kd.heavy_list) rt.run_dedup_heavy("dedup_heavy", R, kd);
+		}
+		rt.aux_join();
 		if constexpr (HasHeavyCensus<RT>::value) rt.heavy_census_dedup(kd.heavy_list ? kd.n_heavy : nullptr);
 	}
 

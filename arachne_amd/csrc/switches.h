@@ -16,7 +16,10 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <optional>
+#include <dirent.h>
+#include <unistd.h>
 
 namespace arx {
 
@@ -48,13 +51,60 @@ struct IndexBuildSwitches {
 	uint64_t slice = sw_u64("ARX_INDEX_SLICE", (uint64_t)256 << 20);  // rows per emitted slice; below 1: 1
 };
 
+// ---- the HIP runtime's hardware queues.  The runtime gives a process GPU_MAX_HW_QUEUES of them (4 unless set) and streams beyond that number
+// share one, where the packets of two streams run in order: a tail on one batch's side stream then sits in front of another batch's main
+// stream, and the side streams cost 10 % of the throughput instead of gaining 2.5 (profiles/side_stream/).  Three batch handles open three
+// main and three side streams beside the context's own, so the library asks for ARX_HW_QUEUES (8) when it is loaded, by raising the variable
+// where it is unset or lower, never above 32.  The runtime reads the variable once, when it is initialised: a process that has opened the
+// GPU before it loads the library (the HSA runtime holds /dev/kfd open from then on) keeps the queues it has.  So the request also records
+// whether the side streams will have their queues, and ARX_AUX_STREAM's default follows that: on where the variable already was high enough
+// or the request came in time, off (one stream per batch, the order before the side streams) in a process that had the GPU open with fewer.
+// ARX_HW_QUEUES=0, or ARX_AUX_STREAM=0 at load time, makes no request.  setenv is not safe against a getenv in another thread at the same
+// moment; the request runs once, in the loader's call of the library's constructors.
+inline bool sw_gpu_already_open() // does a descriptor of this process name /dev/kfd?  (no /proc: taken as not open)
+{
+	DIR *d = opendir("/proc/self/fd");
+	if (!d) return false;
+	bool open = false;
+	while (const dirent *e = readdir(d)) {
+		char to[64];
+		const ssize_t n = readlinkat(dirfd(d), e->d_name, to, sizeof to - 1);
+		if (n == 8 && memcmp(to, "/dev/kfd", 8) == 0) { open = true; break; }
+	}
+	closedir(d);
+	return open;
+}
+inline bool &sw_side_streams_have_queues() { static bool have = false; return have; } // per loaded library; false until the request has run
+inline void sw_request_hw_queues()
+{
+	bool &have = sw_side_streams_have_queues();
+	int need = sw_int("ARX_HW_QUEUES", 8);
+	if (need > 32) need = 32;
+	const char *e = getenv("GPU_MAX_HW_QUEUES");
+	if (e && atoi(e) >= (need > 0 ? need : 8)) { have = true; return; } // (as the process was started: taken to be what the runtime read or will read)
+	have = false;
+	if (need <= 0 || !sw_on_unless_zero("ARX_AUX_STREAM") || sw_gpu_already_open()) return;
+	char v[16];
+	snprintf(v, sizeof v, "%d", need);
+	have = setenv("GPU_MAX_HW_QUEUES", v, 1) == 0;
+}
+inline bool sw_aux_stream() { const char *e = getenv("ARX_AUX_STREAM"); return e ? atoi(e) != 0 : sw_side_streams_have_queues(); } // set: as it says (1 forces the side streams); unset: where they have their queues
+
 // ---- batch switches: everything the runtime (hip_rt.h, arx_cold.hip) looks at
 struct BatchSwitches {
 	// -- streams and launch shapes
-	// Off by default: beside each other the launches shorten one batch alone (62.2 -> 59.5 ms) but cost 5-6 % of the throughput with three
-	// batches in flight (7.1 against 7.6 M pairs/s, same box): the other batches' kernels already fill the chip while a tail runs, and the
-	// cross-stream waits add bubbles.  ARX_AUX_STREAM=1 turns it on (latency-bound use: one batch at a time).
-	bool aux_stream = sw_off_unless_nonzero("ARX_AUX_STREAM");
+	// The side stream (HipRT::on_aux): launches that keep a few wavefronts busy run beside the wide launch of the same stage instead of in
+	// front of it.  ARX_AUX_STREAM is the master switch (0: every launch on the batch's one stream; unset: on where the side streams have
+	// their hardware queues, sw_request_hw_queues above); each part has its own beneath it.
+	// Round 2 measured the side stream as a loss with three batches in flight (7.1 against 7.6 M pairs/s); profiles/side_stream/ has that
+	// measurement again with enough hardware queues for the streams (sw_request_hw_queues above) and the A/B of each part.
+	// A part is on by default where every run with it was faster than every run without it (three runs each, alternating, the default bench
+	// command; the table is in profiles/side_stream/README.md): the chaining fork and the rescue replay are, the others are not.
+	bool aux_stream = sw_aux_stream();
+	bool aux_chain = sw_on_unless_zero("ARX_AUX_CHAIN");         // KChainMid (the above-cap reads' walk) beside both k_chain_heavy launches: 74.7-75.1 -> 73.4-74.1 ms per step
+	bool aux_rescue = sw_on_unless_zero("ARX_AUX_RESCUE");       // k_rescue_heavy beside the thread-per-pair launch of its round (round 2's part): 73.4-74.1 -> 72.8-73.4
+	bool aux_dedup = sw_off_unless_nonzero("ARX_AUX_DEDUP");     // k_dedup_heavy beside KDedup, after a pass of its own that lists the heavy reads
+	bool aux_nw = sw_off_unless_nonzero("ARX_AUX_NW");           // CIGAR band class 2 beside the other classes
 	// 8 resident 64-thread blocks per CU give every SIMD two waves of these latency-bound kernels
 	int bpc = sw_int("ARX_BPC", 16);                       // resident 64-lane blocks per CU of the thread-per-item kernels (sizes their per-slot scratch)
 	int coop_bpc = sw_int("ARX_COOP_BPC", 64);             // grid cap of the 16-lane DP kernels (no per-slot scratch; grid-stride)
@@ -130,6 +180,10 @@ struct PipelineSwitches {
 	std::optional<int> chain_heavy_min = sw_int_if_set("ARX_CHAIN_HEAVY_MIN");   // occurrences from which a read is heavy (tests lower it; raised, k_chain_g16's LDS opt-in goes above 64 KB)
 	std::optional<int> dedup_heavy_min = sw_int_if_set("ARX_DEDUP_HEAVY_MIN");   // regions from which a read is heavy (tests)
 	std::optional<int> rescue_heavy_min = sw_int_if_set("ARX_RESCUE_HEAVY_MIN"); // regions of both reads together from which a pair is heavy (tests)
+	// beneath ARX_AUX_CHAIN: the classification of the reads as a pass of its own (KChainClass), then the light reads' chaining, KChainMid and
+	// the k_chain_heavy launches all three side by side (two side streams).  Off: 74.2-74.5 ms per step with it against 73.4-74.1 without
+	// (the seed phase of the batches beside it grows by more than the align phase shrinks)
+	bool chain_split = sw_off_unless_nonzero("ARX_CHAIN_SPLIT");
 	int chain_mid_min = sw_int("ARX_CHAIN_MID_MIN", 16);       // occurrences from which a read below the heavy threshold is listed for KChainMid; 0: no launch of their own for the reads in between
 	bool rescue_no_ahead = sw_present("ARX_RESCUE_NO_AHEAD");  // every rescue SW down the one-at-a-time path instead of queued ahead (tests)
 	// -- extension
@@ -159,5 +213,8 @@ struct FeederSwitches {
 // ms) through one static FILE * (HipRT::resolve_timers): it is opened once, the first time a runtime resolves its timers, and a change of the
 // variable after that goes unseen.  Diagnostics.
 inline FILE *sw_open_launch_log() { const char *e = getenv("ARX_LAUNCH_LOG"); return e ? fopen(e, "a") : nullptr; }
+
+// ---- the parts of the side stream (HipRT::on_aux): which switch of BatchSwitches, beneath ARX_AUX_STREAM, a fork belongs to
+enum AuxPart { AUX_RESCUE, AUX_CHAIN, AUX_DEDUP, AUX_NW };
 
 } // namespace arx

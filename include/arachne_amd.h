@@ -751,6 +751,14 @@ int arx_batch_debug_seed_census(arx_ctx *ctx, arx_batch *b, int32_t enable, int6
  * list.  The host test double keeps no census and reports zeros. */
 int arx_batch_debug_heavy_census(arx_ctx *ctx, arx_batch *b, int32_t enable, int64_t *census8);
 int arx_batch_debug_chains(arx_ctx *ctx, arx_batch *b, int32_t *occ_off /* n_reads+1 */, int32_t *n_chain, arx_chain *chains, arx_seed *seeds /* counts[3] each */);
+/* The split chaining's classification of the last chaining stage (tests): who[r] = 0 the light reads' launch, 1 the heavy launches, 2 the
+ * listed reads' launch; heavy_list (n_reads entries) with n[0] of them filled; mid_list (n_reads / 4 + 64 entries) with min(n[1], n[2]) of
+ * them filled, n[1] = reads that asked for a place, n[2] = the list's capacity (0: no such list).  ARX_E_ARG where the stage ran unsplit. */
+int arx_batch_debug_chain_class(arx_ctx *ctx, arx_batch *b, uint8_t *who /* n_reads */, int32_t *heavy_list, int32_t *mid_list, int32_t *n /* 3 */);
+/* 1: a batch handle created with ARX_AUX_STREAM unset runs its narrow launches on side streams -- GPU_MAX_HW_QUEUES was at least
+ * ARX_HW_QUEUES (8) when the library was loaded, or the library raised it before the process opened the GPU; 0: it runs on one stream,
+ * because the process had the GPU open with fewer queues.  libarachne_amd.so only. */
+int32_t arx_side_streams_default(void);
 int arx_batch_debug_core(arx_ctx *ctx, arx_batch *b, int32_t *n_core, arx_reg *regs /* counts[3] */);
 
 /* self-test of a device routine that has no host twin (tests): klib's introsort as a wavefront reproduces it (csrc/dev_regs_wave.h:
