@@ -27,7 +27,7 @@ struct Cand { // one candidate alignment of a read (aligner.go:65-114, the field
 	int32_t active, is_proper, mapq, mol, active_molecule, in_filtered, best_in_mol, pad;
 };
 
-struct RfaBarcodeOut { double dna_len; int32_t n_mol, pad; };
+struct RfaBarcodeOut { double dna_len; int32_t n_mol, pad; }; // pad: diagnostics, the fastScore sweeps the barcode ran (R5 + R6); only tests read it
 
 constexpr int RFA_P10_HALF = 1400; // table of 10^(x/2) for x in [-1400, 1400]; beyond it pow() underflows to 0 / overflows to inf
 
@@ -231,12 +231,13 @@ ARX_HDI ReadTags rfa_read_tags(const Cand *c, const int32_t *pair_best, int lo, 
 // Control flow around these calls is uniform over the workgroup: every value it depends on is read from memory after a barrier.
 // Sums that many lanes contribute to are integers (scores are half-units), so their order cannot be observed.
 struct RfaScratch {
-	int32_t *hdr;                 // [0] filtered candidates, [2..3] DNA length accumulator (int64)
+	int32_t *hdr;                 // [0] filtered candidates, [2..3] DNA length accumulator (int64), [4] molecules flagged in `multi`, [6..7] the first 64 of them as a bit mask
 	uint64_t *skey;               // P sort keys
 	int32_t *ord;                 // P: filtered candidates in (contig first seen, position, index) order
 	int32_t *flag, *excl;         // molecule starts / scans (n_c + 2 each)
 	int32_t *spot;                // n_c: molecule a candidate is the best alignment of its read in, or -1
 	int32_t *has_active;          // n_c + 2 (pre-scrap molecules)
+	int32_t *nspot, *multi;       // after scrapMolecules, in the words of excl / has_active: spots per read; per surviving molecule, reads of its group with two or more spots
 	int32_t *mol_goff, *mol_nact, *cursor, *grp_read; // surviving molecules: reads with a spot in them
 	int32_t *ach, *num, *scv;     // per sink molecule accumulators of one fastScore sweep
 	int32_t *mv, *act;            // per read
@@ -261,6 +262,7 @@ ARX_DEVI RfaScratch rfa_carve(int32_t *scratch, int n_c, int n_reads, int n_seqs
 	s.m_lo = (int64_t *)p; p += 2 * A; s.m_hi = (int64_t *)p; p += 2 * A; s.m_len = (int64_t *)p; p += 2 * A;
 	s.ord = p; p += P;
 	s.flag = p; p += A; s.excl = p; p += A; s.spot = p; p += A; s.has_active = p; p += A;
+	s.nspot = s.excl; s.multi = s.has_active; // n_reads <= n_c and cnt <= n_c; the renumbering of scrapMolecules is the last reader of excl and has_active
 	s.mol_goff = p; p += A; s.mol_nact = p; p += A; s.cursor = p; p += A; s.grp_read = p; p += A;
 	s.ach = p; p += A; s.num = p; p += A; s.scv = p; p += A; s.m_soft = p; p += A;
 	s.mv = p; p += n_reads + 2; s.act = p; p += n_reads + 2;
@@ -313,7 +315,7 @@ template <class B>
 #define ARX_RFA_T(k) do {} while (0)   // diagnostics hook: per-phase clock (tools builds)
 #endif
 ARX_DEV void rfa_barcode(B &blk, Cand *c, const int32_t *roff, int n_reads, int n_c, int read0, int do_rfa, int pen_int, int n_seqs,
-                         const double *p10h, int32_t *scratch, RfaBarcodeOut *out)
+                         const double *p10h, int32_t *scratch, RfaBarcodeOut *out, int skip_sweeps = 1)
 {
 	const RfaScratch s = rfa_carve(scratch, n_c, n_reads, n_seqs);
 	const int roff0 = roff[0], pen2 = 2 * pen_int; // roff holds batch-global candidate offsets, c is the barcode's slice
@@ -347,7 +349,7 @@ ARX_DEV void rfa_barcode(B &blk, Cand *c, const int32_t *roff, int n_reads, int 
 		if (cand_is_pair(c[ba], c[bm])) { c[ba].is_proper = 1; c[bm].is_proper = 1; }
 		act[r] = ba; act[r + 1] = bm;
 	});
-	if (!do_rfa) { blk.single([&]() { out->dna_len = 0; out->n_mol = 0; }); return; }
+	if (!do_rfa) { blk.single([&]() { out->dna_len = 0; out->n_mol = 0; out->pad = 0; }); return; }
 
 	ARX_RFA_T(1);
 	// R2 inferMolecules: filtered candidates, contigs in first-seen order, sorted by position, split at gaps > 50 kb
@@ -414,16 +416,43 @@ ARX_DEV void rfa_barcode(B &blk, Cand *c, const int32_t *roff, int n_reads, int 
 	});
 	blk.pfor(n_c > n_reads ? n_c : n_reads, [&](int i) {
 		if (i < n_c && s.spot[i] >= 0) ARX_ATOMIC_INC(&s.cursor[s.spot[i]]);
-		if (i < n_reads && c[act[i]].mol >= 0) ARX_ATOMIC_INC(&s.mol_nact[c[act[i]].mol]);
+		if (i < n_reads) {
+			if (c[act[i]].mol >= 0) ARX_ATOMIC_INC(&s.mol_nact[c[act[i]].mol]);
+			int ns = 0; // at most one spot per molecule: best_in_mol marks one candidate of a (read, molecule) group
+			for (int k = roff[i] - roff0; k < roff[i + 1] - roff0; ++k) ns += s.spot[k] >= 0;
+			s.nspot[i] = ns;
+		}
 	});
 	blk.pfor(cnt + 1, [&](int m) { s.flag[m] = m < cnt ? ARX_LOAD_SHARED(&s.cursor[m]) : 0; });
 	blk.exclusive_scan(s.flag, s.mol_goff, cnt + 1); // mol_goff[cnt] = number of (molecule, read) spots
-	blk.pfor(cnt, [&](int m) { s.cursor[m] = s.mol_goff[m]; });
-	blk.pfor(n_c, [&](int i) { if (s.spot[i] >= 0) s.grp_read[ARX_ATOMIC_ADD(&s.cursor[s.spot[i]], 1)] = c[i].read - read0; });
+	blk.pfor(cnt, [&](int m) { s.cursor[m] = s.mol_goff[m]; s.multi[m] = 0; });
+	// Which sources can move a read at all.  sweep(S) below reaches ach / num only through a read of S's group whose active candidate lies
+	// in S and which has a spot in some T != S; being in S's group it has a spot in S too, so nspot >= 2.  multi[S] != 0: some read of S's
+	// group has nspot >= 2.  Spots and grp_read do not change in Optimize (act, active and mol_nact do), so multi holds for every iteration:
+	//   R5, multi[S] == 0: every num[T] is 0, the arg-max key is 0, the iteration is `++idle; continue` -- the nact_s == 0 branch, no barrier;
+	//   R6, multi[S] == 0: scv is all zero and no read of S finds a T, so sum_move is written back as it was -- the source is skipped;
+	//   no molecule flagged: neither loop does anything.
+	// skip_sweeps == 0 (ARX_RFA_SKIP_SWEEPS=0) treats every molecule as flagged: every sweep runs, as before the flags existed.
+	uint64_t *multi_mask = (uint64_t *)(s.hdr + 6);
+	blk.pfor(n_c, [&](int i) {
+		const int m = s.spot[i], r = c[i].read - read0;
+		if (m < 0) return;
+		s.grp_read[ARX_ATOMIC_ADD(&s.cursor[m], 1)] = r;
+		if (s.nspot[r] >= 2 && ARX_ATOMIC_ADD(&s.multi[m], 1) == 0) { // the first such read of m: each bit is added once, so the sum is the mask
+			ARX_ATOMIC_INC(&s.hdr[4]);
+			if (m < 64) ARX_ATOMIC_ADD64(multi_mask, (uint64_t)1 << m);
+		}
+	});
+	// read after the barrier, so uniform over the workgroup; a source below 64 is looked up in a register (an idle iteration costs no trip to memory)
+	const int n_multi = skip_sweeps ? ARX_LOAD_SHARED(&s.hdr[4]) : cnt;
+	const uint64_t mask64 = skip_sweeps ? ARX_LOAD_SHARED(multi_mask) : ~(uint64_t)0;
+	auto can_move = [&](int S) -> bool { return S < 64 ? ((mask64 >> S) & 1) != 0 : (!skip_sweeps || ARX_LOAD_SHARED(&s.multi[S]) != 0); };
+	int n_sweeps = 0;
 
 	ARX_RFA_T(4);
 	// one sweep of fastScore(S, *) over the active reads of S: ach/num per sink molecule
 	auto sweep = [&](int S) {
+		++n_sweeps;
 		blk.pfor(cnt, [&](int T) { s.ach[T] = 0; s.num[T] = 0; });
 		blk.pfor(s.mol_goff[S + 1] - s.mol_goff[S], [&](int g) {
 			const int read = s.grp_read[s.mol_goff[S] + g], sa = act[read];
@@ -443,9 +472,12 @@ ARX_DEV void rfa_barcode(B &blk, Cand *c, const int32_t *roff, int n_reads, int 
 	};
 	// R5 Optimize(obj, 1, 2, 4*M): two sweeps of 4*M greedy moves, sources round robin.  The walk is deterministic, so once
 	// M consecutive sources in a row changed nothing the remaining iterations cannot change anything either.
+	// With no source flagged every iteration would be idle.  Otherwise `it`, the 8 * cnt bound and `idle` keep their meaning: an unflagged
+	// source is the idle iteration it always was, counted in its round-robin turn.
 	int idle = 0;
-	for (int it = 0; it < 8 * cnt && idle < cnt; ++it) {
+	for (int it = 0; n_multi > 0 && it < 8 * cnt && idle < cnt; ++it) {
 		const int S = it % cnt;
+		if (!can_move(S)) { ++idle; continue; }
 		const int nact_s = ARX_LOAD_SHARED(&s.mol_nact[S]);
 		if (nact_s == 0) { ++idle; continue; }
 		sweep(S);
@@ -478,8 +510,8 @@ ARX_DEV void rfa_barcode(B &blk, Cand *c, const int32_t *roff, int n_reads, int 
 	}
 	ARX_RFA_T(5);
 	// R6 method 2: sum_move += 10^fastScore(S, T), T ascending, for every active alignment of S that has a spot in T
-	for (int S = 0; S < cnt; ++S) {
-		if (ARX_LOAD_SHARED(&s.mol_nact[S]) == 0) continue;
+	for (int S = 0; n_multi > 0 && S < cnt; ++S) {
+		if (!can_move(S) || ARX_LOAD_SHARED(&s.mol_nact[S]) == 0) continue;
 		sweep(S);
 		blk.pfor(cnt, [&](int T) { const int num = ARX_LOAD_SHARED(&s.num[T]); s.scv[T] = (T != S && num > 0) ? score_of(S, T, num) : 0; });
 		blk.pfor(s.mol_goff[S + 1] - s.mol_goff[S], [&](int g) {
@@ -518,7 +550,7 @@ ARX_DEV void rfa_barcode(B &blk, Cand *c, const int32_t *roff, int n_reads, int 
 		else ARX_ATOMIC_ADD64(dna, ARX_LOAD_SHARED(&s.m_len[m]));
 	});
 	blk.pfor(m_c, [&](int t) { Cand &x = c[s.ord[t]]; if (x.mol >= 0) x.active_molecule = s.flag[x.mol]; });
-	blk.single([&]() { out->dna_len = cnt > 0 ? 1000.0 + (double)ARX_LOAD_SHARED(dna) : 0.0; out->n_mol = cnt; });
+	blk.single([&]() { out->dna_len = cnt > 0 ? 1000.0 + (double)ARX_LOAD_SHARED(dna) : 0.0; out->n_mol = cnt; out->pad = n_sweeps; });
 	ARX_RFA_T(7);
 }
 

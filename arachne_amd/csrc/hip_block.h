@@ -14,6 +14,12 @@ constexpr int BLOCK_LANES = ARX_BLOCK_LANES, SORT_LDS = 4096;
 // A barcode of TELLseq size (tens of pairs) does not need 1024 lanes and 60 KB of LDS: small barcodes run in workgroups of
 // SMALL_LANES lanes with a SMALL_SORT-entry sort buffer (15 KB: ten workgroups per CU instead of two).
 constexpr int SMALL_LANES = 256, SMALL_SORT = 1024;
+// Largest P that sort_kv orders by counting ranks instead of by the bitonic network, per class (at most the class's lanes: one entry per lane).
+// 0: never.  The rank sort has 2 barrier phases against the network's 38 at P = 256, but P * P comparisons against 36 * P / 2, and the network's
+// stages run in LDS at about 0.3 us each: per 4,096 sorts of 1,024-lane workgroups 0.32 / 0.68 / 1.89 ms by rank against 0.14 / 0.20 / 0.28 ms
+// by the network at P = 256 / 512 / 1,024, and 0.024 / 0.046 / 0.103 against 0.023 / 0.028 / 0.038 ms at P = 64 / 128 / 256 in the 256-lane class
+// (profiles/rfa_sweeps/README.md).  It loses at every size, so it stays behind ARX_BLOCK_RANK_SORT (switches.h), which overrides both constants.
+constexpr int RANK_SORT_MAX = 0, SMALL_RANK_SORT_MAX = 0;
 
 template <int BLOCK_LANES, int SORT_LDS> struct HipBlockT {
 	int tid;
@@ -58,10 +64,13 @@ template <int BLOCK_LANES, int SORT_LDS> struct HipBlockT {
 		__syncthreads();
 		return total;
 	}
-	// ascending bitonic sort of P = 2^k (key, value) pairs by (key, (uint32)value); up to SORT_LDS pairs are sorted in LDS
+	// ascending sort of P = 2^k (key, value) pairs by (key, (uint32)value): by rank for P <= rank_max, else the bitonic network, which sorts
+	// up to SORT_LDS pairs in LDS.  Entries equal in both words are interchangeable, so the two forms write the same arrays.
 	uint64_t *sk; int32_t *sv; // SORT_LDS entries of LDS each
+	int rank_max;              // <= BLOCK_LANES (launch_block clamps it)
 	__device__ void sort_kv(uint64_t *k, int32_t *v, int P)
 	{
+		if (P <= rank_max) { sort_kv_rank(k, v, P); return; }
 		if (P <= SORT_LDS) {
 			for (int t = tid; t < P; t += BLOCK_LANES) { sk[t] = k[t]; sv[t] = v[t]; }
 			__syncthreads();
@@ -69,6 +78,37 @@ template <int BLOCK_LANES, int SORT_LDS> struct HipBlockT {
 			for (int t = tid; t < P; t += BLOCK_LANES) { k[t] = sk[t]; v[t] = sv[t]; }
 			__syncthreads();
 		} else sort_kv_in(k, v, P);
+	}
+	// One entry per lane: its place is the number of entries that are smaller, or equal and in front of it (so entries that occur several times,
+	// the (~0, -1) padding among them, get places of their own).  Every lane reads the same LDS word at a time -- a broadcast, no bank conflict --
+	// and writes its entry once: two barrier phases instead of one per stage of the network.
+	__device__ void sort_kv_rank(uint64_t *k, int32_t *v, int P)
+	{
+		typedef __attribute__((address_space(3))) uint64_t lds_u64; // sk / sv are generic pointers: say that they point into LDS
+		typedef __attribute__((address_space(3))) int32_t lds_i32;
+		const lds_u64 *lk = (const lds_u64 *)sk; const lds_i32 *lv = (const lds_i32 *)sv;
+		uint64_t mk = 0; uint32_t mv = 0;
+		if (tid < P) { mk = k[tid]; mv = (uint32_t)v[tid]; sk[tid] = mk; sv[tid] = (int32_t)mv; }
+		__syncthreads(); // every lane has read its entry of k / v: they may be overwritten
+		if (tid < P) {
+			// Eight entries per round, all sixteen reads issued before the first comparison, and the comparison without a branch (| and &, not ||
+			// and &&): written with short-circuit operators every entry costs two LDS latencies one after the other, three times the network's time
+			constexpr int U = 8;
+			unsigned rank = 0;
+			for (int j0 = 0; j0 < P; j0 += U) {
+				uint64_t kj[U]; uint32_t vj[U];
+#pragma unroll
+				for (int u = 0; u < U; ++u) { const int j = j0 + u < P ? j0 + u : P - 1; kj[u] = lk[j]; vj[u] = (uint32_t)lv[j]; } // (P < U: the last entry again, not counted)
+#pragma unroll
+				for (int u = 0; u < U; ++u) {
+					const int j = j0 + u;
+					const unsigned before = (unsigned)(kj[u] < mk) | ((unsigned)(kj[u] == mk) & ((unsigned)(vj[u] < mv) | ((unsigned)(vj[u] == mv) & (unsigned)(j < tid))));
+					rank += before & (unsigned)(j < P);
+				}
+			}
+			k[rank] = mk; v[rank] = (int32_t)mv; // rank < P: the entry itself is not counted
+		}
+		__syncthreads();
 	}
 	__device__ void sort_kv_in(uint64_t *k, int32_t *v, int P)
 	{
@@ -106,13 +146,13 @@ template <int BLOCK_LANES, int SORT_LDS> struct HipBlockT {
 using HipBlock = HipBlockT<BLOCK_LANES, SORT_LDS>;
 
 // cls / want: only the items whose class byte equals `want` (cls == nullptr: all)
-template <class F, int LANES, int SORT> __global__ __launch_bounds__(LANES) void k_block_items(F f, int n, const uint8_t *cls, int want)
+template <class F, int LANES, int SORT> __global__ __launch_bounds__(LANES) void k_block_items(F f, int n, const uint8_t *cls, int want, int rank_max)
 {
 	__shared__ uint64_t l64[LANES];
 	__shared__ int32_t l32[LANES + 1];
 	__shared__ uint64_t sk[SORT];
 	__shared__ int32_t sv[SORT];
-	HipBlockT<LANES, SORT> blk{(int)threadIdx.x, l64, l32, sk, sv};
+	HipBlockT<LANES, SORT> blk{(int)threadIdx.x, l64, l32, sk, sv, rank_max < LANES ? rank_max : LANES};
 	for (int b = blockIdx.x; b < n; b += gridDim.x) {
 		if (cls && cls[b] != want) continue; // uniform over the workgroup
 		f(b, blk);

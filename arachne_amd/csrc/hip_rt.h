@@ -330,17 +330,18 @@ struct HipRT {
 		Scope sc(*this, nm, n);
 		int n_small = 0;
 		if (small) for (int i = 0; i < n; ++i) n_small += small[i] ? 1 : 0;
+		const int rank = sw.block_rank_sort.value_or(RANK_SORT_MAX), rank_small = sw.block_rank_sort.value_or(SMALL_RANK_SORT_MAX); // the kernel keeps them within its lanes
 		if (n_small == 0) {
 			int blocks = n < n_cu * 8 ? n : n_cu * 8;
-			start({"k_block_items<BLOCK_LANES>", nm}, k_block_items<F, BLOCK_LANES, SORT_LDS>, dim3(blocks), dim3(BLOCK_LANES), 0, f, n, nullptr, 0);
+			start({"k_block_items<BLOCK_LANES>", nm}, k_block_items<F, BLOCK_LANES, SORT_LDS>, dim3(blocks), dim3(BLOCK_LANES), 0, f, n, nullptr, 0, rank);
 		} else {
 			uint8_t *d = alloc<uint8_t>((size_t)n + 8);
 			h2d(d, small, (size_t)n);
 			int blocks = n_small < n_cu * 32 ? n_small : n_cu * 32;
-			start({"k_block_items<SMALL_LANES>", nm}, k_block_items<F, SMALL_LANES, SMALL_SORT>, dim3(blocks), dim3(SMALL_LANES), 0, f, n, d, 1);
+			start({"k_block_items<SMALL_LANES>", nm}, k_block_items<F, SMALL_LANES, SMALL_SORT>, dim3(blocks), dim3(SMALL_LANES), 0, f, n, d, 1, rank_small);
 			if (n_small < n) {
 				blocks = n - n_small < n_cu * 8 ? n - n_small : n_cu * 8;
-				start({"k_block_items<BLOCK_LANES>", nm}, k_block_items<F, BLOCK_LANES, SORT_LDS>, dim3(blocks), dim3(BLOCK_LANES), 0, f, n, d, 0);
+				start({"k_block_items<BLOCK_LANES>", nm}, k_block_items<F, BLOCK_LANES, SORT_LDS>, dim3(blocks), dim3(BLOCK_LANES), 0, f, n, d, 0, rank);
 			}
 		}
 	}

@@ -22,11 +22,11 @@ struct KCandBuild {
 };
 struct KRfa { // one barcode per workgroup
 	const int32_t *cand_off; const int32_t *bc_read_off; const uint8_t *do_rfa; const int64_t *scr_off; int pen_int, n_seqs;
-	const double *p10h; Cand *cands; int32_t *scratch; RfaBarcodeOut *out;
+	const double *p10h; Cand *cands; int32_t *scratch; RfaBarcodeOut *out; int skip_sweeps;
 	template <class B> ARX_DEV void operator()(int b, B &blk) const
 	{
 		const int r0 = bc_read_off[b], r1 = bc_read_off[b + 1];
-		rfa_barcode(blk, cands + cand_off[r0], cand_off + r0, r1 - r0, cand_off[r1] - cand_off[r0], r0, do_rfa[b], pen_int, n_seqs, p10h, scratch + scr_off[b], out + b);
+		rfa_barcode(blk, cands + cand_off[r0], cand_off + r0, r1 - r0, cand_off[r1] - cand_off[r0], r0, do_rfa[b], pen_int, n_seqs, p10h, scratch + scr_off[b], out + b, skip_sweeps);
 	}
 };
 
@@ -117,7 +117,13 @@ template <class RT> struct RfaStage {
 		KCandBuild kb{pipe.ix, w.preg_off, w.n_regs, w.c_reg_off, cand_off, w.pregs, w.alns, w.cig, w.cig_w, cands};
 		rt.launch_wide("cand_build", R, kb);
 		res.cand_off.resize(R + 1);
-		rt.d2h(res.cand_off.data(), cand_off, 4 * (size_t)(R + 1));
+		{ // 8 MB per 1 M-pair batch: landed in the runtime's page-locked staging buffer (free between a batch's upload and the next), so the copy is
+		  // DMA and not the HIP runtime's piecewise copy into pageable memory; the vector's users (fetch, host_mapq, the scratch offsets) see the same values
+			const size_t bytes = 4 * (size_t)(R + 1);
+			void *st = rt.stage(bytes);
+			rt.d2h(st, cand_off, bytes);
+			memcpy(res.cand_off.data(), st, bytes);
+		}
 		// per-barcode scratch offsets
 		std::vector<int32_t> bro(n_barcodes + 1);
 		std::vector<int64_t> so(n_barcodes + 1);
@@ -138,8 +144,8 @@ template <class RT> struct RfaStage {
 		RfaBarcodeOut *d_out = rt.template alloc<RfaBarcodeOut>(n_barcodes + 1);
 		rt.h2d(d_bro, bro.data(), 4 * (size_t)(n_barcodes + 1)); rt.h2d(d_so, so.data(), 8 * (size_t)(n_barcodes + 1));
 		rt.h2d(d_flags, do_rfa, n_barcodes); rt.h2d(d_p10, p10.data(), 8 * p10.size());
-		KRfa kr{cand_off, d_bro, d_flags, d_so, penalty, pipe.ix.n_seqs, d_p10, cands, d_scr, d_out};
-		// pipe.sw.rfa_small (experiments, off by default: switches.h has the measurement): barcodes of TELLseq size in 256-lane workgroups (hip_block.h)
+		KRfa kr{cand_off, d_bro, d_flags, d_so, penalty, pipe.ix.n_seqs, d_p10, cands, d_scr, d_out, pipe.sw.rfa_skip_sweeps ? 1 : 0};
+		// pipe.sw.rfa_small (on by default: switches.h has the measurement): barcodes of TELLseq size in 256-lane workgroups (hip_block.h)
 		std::vector<uint8_t> &small = res.cls;
 		small.assign(n_barcodes, 0);
 		const bool rfa_small = pipe.sw.rfa_small;

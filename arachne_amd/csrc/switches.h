@@ -160,6 +160,11 @@ struct BatchSwitches {
 	int rescue_lds_classes = sw_int("ARX_RESCUE_LDS_CLASSES", 0);
 	int chain_wave = sw_int("ARX_CHAIN_WAVE", 1);              // 0: lane 0 alone runs chain_and_filter() in k_chain_heavy (A/B)
 	int chain_l_div = sw_int("ARX_CHAIN_L_DIV", 1);            // the long ones' launch holds 128 KB of LDS per workgroup: on n_cu / l_div CUs
+	// -- workgroup-per-item kernels (hip_block.h: launch_block)
+	// largest P that sort_kv orders by counting ranks (one entry per lane, 2 barrier phases) instead of by the bitonic network; never above the
+	// class's lane count.  Unset: hip_block.h's RANK_SORT_MAX / SMALL_RANK_SORT_MAX, both 0 (the bitonic network for every P): the rank sort
+	// measured 2.3 to 6.7 times slower than the network at P = 256 to 1,024 (P * P comparisons; profiles/rfa_sweeps/)
+	std::optional<int> block_rank_sort = sw_int_if_set("ARX_BLOCK_RANK_SORT");
 	// -- diagnostics
 	bool trace_launches = sw_present("ARX_TRACE_LAUNCHES");    // name every launch on stderr and wait for it (a fault then names its kernel)
 	bool seed_stats = sw_present("ARX_SEED_STATS");            // lane utilisation of the persistent-lane seeding kernels, printed per launch
@@ -191,10 +196,16 @@ struct PipelineSwitches {
 	// most one differing pair, no ambiguous base, h0 >= 5, tlen >= qlen) and the chain goes on in the same round (profiles/ext_closed/)
 	bool ext_closed = sw_on_unless_zero("ARX_EXT_CLOSED");
 	// -- placement (pipeline_rfa.h)
-	// ARX_RFA_SMALL=1 (experiments): barcodes of TELLseq size in 256-lane workgroups (hip_block.h).  Measured at 4,333 barcodes x 77
-	// pairs per batch: 23.3 ms against 7.4 ms with 1,024 lanes for every barcode -- the per-barcode phases are latency chains whose
-	// length grows with the work per lane, and ten small workgroups per CU do not make up for it.  Default: off.
-	bool rfa_small = sw_off_unless_nonzero("ARX_RFA_SMALL");
+	// Barcodes of TELLseq size (at most 512 reads and 512 candidates) in 256-lane workgroups, ten per CU instead of two (hip_block.h);
+	// ARX_RFA_SMALL=0: 1,024 lanes for every barcode.  Round 2 measured the small class as a loss (23.3 ms against 7.4 ms per batch of 4,333
+	// barcodes x 77 pairs): a barcode was a chain of about a hundred barrier phases whose length grew with the work per lane.  With the idle
+	// sweeps gone (rfa_skip_sweeps below) the chain is a third shorter and the verdict turns: 70.7-71.5 ms per step with the small class against
+	// 71.9-72.5 without, eight alternating runs each, every run with it faster than every run without (profiles/rfa_sweeps/).  Default: on.
+	bool rfa_small = sw_on_unless_zero("ARX_RFA_SMALL");
+	// 0: the placement walk (R5) and the move sums (R6) sweep every source molecule.  Default: only the sources that hold a read with spots in
+	// two or more molecules -- no other sweep can add anything (dev_rfa.h states the rule); the results are the same bit for bit
+	// (tests/test_rfa_sweeps_hostsim.py, tests/test_rfa_sweeps_gpu.py hold the two forms together).  Measurement: profiles/rfa_sweeps/
+	bool rfa_skip_sweeps = sw_on_unless_zero("ARX_RFA_SKIP_SWEEPS");
 	std::optional<double> mapq_guard = sw_double_if_set("ARX_MAPQ_GUARD"); // unset: dev_rfa.h's RFA_MAPQ_GUARD; tests widen the guard to push every read through the host path
 	// -- diagnostics
 	bool trace = sw_present("ARX_TRACE");                      // per-round progress on stderr

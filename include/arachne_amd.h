@@ -809,7 +809,7 @@ int arx_selftest_block(int32_t device, int32_t klass, int32_t n_cases, const int
  * alignment, CIGAR words at column 8's offset; n_cig words in all).  ann_off[n_seqs], l_pac: the only things read of an index.  rfa_small and
  * mapq_guard (< 0: the default) stand for ARX_RFA_SMALL and ARX_MAPQ_GUARD, which this entry does not read.  cands: cand_cap records of 96
  * bytes (api.py CAND_DTYPE), cand_cap = one per region plus one per read without any (else ARX_E_ARG); cand_off[n_reads + 1]; bc_out:
- * n_barcodes x (double dna_len, int32 n_mol, int32 pad); cls[n_barcodes]: 1 where the barcode was given to the small workgroup class;
+ * n_barcodes x (double dna_len, int32 n_mol, int32 pad -- diagnostics: the fastScore sweeps the barcode ran); cls[n_barcodes]: 1 where the barcode was given to the small workgroup class;
  * *n_host_mapq: reads whose MAPQ the host re-evaluated.  Row values that a kernel would index with are checked first (ARX_E_ARG). */
 int arx_selftest_rfa(int32_t device, int32_t n_reads, const int64_t *reg_off, const int64_t *regs, const int64_t *alns, const uint32_t *cigars, int64_t n_cig,
                      const int32_t *lens, int32_t n_barcodes, const int64_t *bc_pair_off, const uint8_t *do_rfa, int32_t penalty, int64_t l_pac,
