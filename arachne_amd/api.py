@@ -182,6 +182,12 @@ _SELFTEST_ARGS = {
     "arx_bam_index_csi": [C.c_int32, C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_bam_index_csi": [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                    C.c_int64, C.c_void_p, C.c_void_p],
+    # the index written by the writer while it appends
+    "arx_bam_open_indexed": [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p,
+                             C.POINTER(C.c_void_p), C.c_char_p, C.c_int32],
+    "arx_bam_close_indexed": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32],
+    "arx_selftest_bam_index_feeds": [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
 }
 
 
@@ -617,6 +623,30 @@ def selftest_bam_index_csi(stream, hdr: int, ref_len, blk_at, blk_isize, seg_byt
                                                          cap, C.byref(out_len), st.ctypes.data)
     assert out[cap:].tobytes() == b"\xa5" * 8
     return rc, (out[:out_len.value].tobytes() if rc == 0 else b""), _csi_stats(st)
+
+
+BAM_DEVICE_SINK = 2                                                # arx_bam_open_indexed's flag: the blocks are compressed on the GPU
+BAM_INDEX_KINDS = {"bai": 1, "csi": 2, "auto": 3}
+
+
+def selftest_bam_index_feeds(stream, hdr: int, ref_len, blk_at, feed_end, seg_bytes: int = 1 << 18, piece_bytes: int = 0, min_shift: int = -1, n_blocks: "int | None" = None,
+                             out_cap: "int | None" = None, device: int = 0, lib_path: str = LIB_PATH):
+    """The index a writer builds of what it is handed, on a stream in memory (include/arachne_amd.h: arx_selftest_bam_index_feeds): the record
+    stream behind hdr fed in feeds that end at feed_end, each indexed in pieces of piece_bytes; blk_at: the file offsets of the writer's layout;
+    min_shift -1: the .bai -> (rc, the index's bytes -- the .csi's inflated -- (empty unless rc is 0), stats)."""
+    lib = _load(lib_path)
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    n = len(src)
+    lens, at, ends = _arr(ref_len, np.int32), _arr(blk_at, np.int64), _arr(feed_end, np.int64)
+    cap = 64 + 64 * len(lens) + 32 * (n // 36 + 1) + 8 * int(sum((int(l) + 16383) >> 14 for l in lens if 0 < l <= BAI_MAX_CONTIG)) if out_cap is None else out_cap
+    out = np.full(cap + 8, 0xA5, dtype=np.uint8)
+    out_len, st = C.c_int64(-1), np.zeros(20, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_bam_index_feeds")(device, src.ctypes.data if n else None, n, int(hdr), len(lens), lens.ctypes.data if len(lens) else None,
+                                                           len(at) - 1 if n_blocks is None else int(n_blocks), at.ctypes.data if len(at) else None, int(seg_bytes), len(ends),
+                                                           ends.ctypes.data if len(ends) else None, int(piece_bytes), int(min_shift), out.ctypes.data, cap, C.byref(out_len),
+                                                           st.ctypes.data)
+    assert out[cap:].tobytes() == b"\xa5" * 8
+    return rc, (out[:out_len.value].tobytes() if rc == 0 else b""), (_bai_stats(st) if min_shift == -1 else _csi_stats(st))
 
 
 INFLATE_STATUS = ("OK", "BAD_HEADER", "BAD_BTYPE", "BAD_STORED_LEN", "BAD_CODE_LENGTHS", "BAD_SYMBOL", "BAD_DISTANCE", "TRUNCATED", "SIZE_MISMATCH", "CRC_MISMATCH")
@@ -1330,16 +1360,40 @@ class BamWriter:
     deflated and checksummed by HIP kernels on that reference's GPU; the file inflates to the same bytes, `level` does not apply.
 
     coordinate=True: the header says SO:coordinate (arx_bam_open_ex, ARX_BAM_COORDINATE) -- for a file filled by sort_append; flags: the
-    entry's flag word as it is (0: byte for byte the file of the plain open)."""
+    entry's flag word as it is (0: byte for byte the file of the plain open).
+
+    index="bai" | "csi" | "auto": the writer indexes what it appends on index_device's GPU (a Reference; default: `device`) and writes
+    index_path (default: path + ".bai" / ".csi") when it is closed (arx_bam_open_indexed, which states the rules: the header says
+    SO:coordinate, an append that breaks a record rule is refused with .code ARX_E_ARG and appends nothing, and the index is all or nothing).
+    close() then returns the index's stats under "index"; min_shift is the .csi's (0: 14)."""
 
     def __init__(self, path: str, contig_names, contig_lens, extra_header: str = "", threads: int = 8, level: int = -1, lib_path: str = LIB_PATH,
-                 device: "Reference | None" = None, coordinate: bool = False, flags: "int | None" = None):
-        self.lib = device.lib if device is not None else _load(lib_path)
+                 device: "Reference | None" = None, coordinate: bool = False, flags: "int | None" = None, index: "str | None" = None, index_path: "str | None" = None,
+                 min_shift: int = 0, index_device: "Reference | None" = None):
+        on = index_device if index_device is not None else device
+        self.lib = on.lib if on is not None else _load(lib_path)
         self.h = C.c_void_p()
+        self.index = None
         n = len(contig_names)
         names = (C.c_char_p * n)(*[x.encode() for x in contig_names])
         lens = np.ascontiguousarray(contig_lens, dtype=np.int32)
         msg = C.create_string_buffer(512)
+        if index is not None:
+            if index not in BAM_INDEX_KINDS:
+                raise ValueError("index is None, 'bai', 'csi' or 'auto'")
+            if on is None:
+                raise ValueError("an indexing writer needs index_device or device: the index is built on a GPU")
+            if device is not None and device is not on and device.device != on.device:
+                raise ValueError("the device sink and the index must be on one GPU")
+            rc = _selftest_fn(self.lib, "arx_bam_open_indexed")(on.h, os.fsencode(path), n, names, lens.ctypes.data, extra_header.encode() if extra_header else None, threads, level,
+                                                                int(flags or 0) | 1 | (BAM_DEVICE_SINK if device is not None else 0), BAM_INDEX_KINDS[index], int(min_shift),
+                                                                None if index_path is None else os.fsencode(index_path), C.byref(self.h), msg, 512)
+            if rc != 0:
+                e = ArachneError("arx_bam_open_indexed: " + msg.value.decode(errors="replace"))
+                e.code = rc
+                raise e
+            self.index = "csi" if index == "csi" or (index == "auto" and len(lens) and int(lens.max()) > BAI_MAX_CONTIG) else "bai"
+            return
         if coordinate or flags is not None:
             rc = _selftest_fn(self.lib, "arx_bam_open_ex")(device.h if device is not None else None, path.encode(), n, names, lens.ctypes.data,
                                                            extra_header.encode() if extra_header else None, threads, level, int(flags or 0) | (1 if coordinate else 0),
@@ -1375,8 +1429,14 @@ class BamWriter:
         b = _BamBatch(n, name_off.ctypes.data, name_b.ctypes.data, keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data, keep[4].ctypes.data,
                       keep[5].ctypes.data, keep[6].ctypes.data, cig_off.ctypes.data, cig_w.ctypes.data, seq_off.ctypes.data, seq_b.ctypes.data, qual_b.ctypes.data, qual_offset,
                       aux_off.ctypes.data, aux_b.ctypes.data)
-        if self.lib.arx_bam_write(self.h, C.byref(b)) != 0:
-            raise ArachneError("arx_bam_write: " + self.lib.arx_bam_error(self.h).decode())
+        rc = self.lib.arx_bam_write(self.h, C.byref(b))
+        if rc != 0:
+            self._fail("arx_bam_write", rc)
+
+    def _fail(self, call, rc):
+        e = ArachneError(call + ": " + self.lib.arx_bam_error(self.h).decode(errors="replace"))
+        e.code = rc
+        raise e
 
     def write_view(self, view):
         """a _BamBatch as RecBuf.build returns it"""
@@ -1392,14 +1452,16 @@ class BamWriter:
     def write_encoded(self, stream, n_records):
         """arx_bam_write_encoded: n_records BAM-encoded records (Batch.records_fetch's stream: a uint8 array or bytes), any writer"""
         a = np.frombuffer(stream, dtype=np.uint8) if isinstance(stream, (bytes, bytearray, memoryview)) else np.ascontiguousarray(stream, dtype=np.uint8)
-        if self.lib.arx_bam_write_encoded(self.h, a.ctypes.data if len(a) else None, len(a), int(n_records)) != 0:
-            raise ArachneError("arx_bam_write_encoded: " + self.lib.arx_bam_error(self.h).decode())
+        rc = self.lib.arx_bam_write_encoded(self.h, a.ctypes.data if len(a) else None, len(a), int(n_records))
+        if rc != 0:
+            self._fail("arx_bam_write_encoded", rc)
 
     def write_encoded_device(self, ptr, n_bytes, n_records):
         """arx_bam_write_encoded_device: the same from device memory (Batch.records_view), writers opened with device= only; returns when the
         blocks are written -- the batch may then be reset"""
-        if _selftest_fn(self.lib, "arx_bam_write_encoded_device")(self.h, C.c_void_p(ptr), int(n_bytes), int(n_records)) != 0:
-            raise ArachneError("arx_bam_write_encoded_device: " + self.lib.arx_bam_error(self.h).decode())
+        rc = _selftest_fn(self.lib, "arx_bam_write_encoded_device")(self.h, C.c_void_p(ptr), int(n_bytes), int(n_records))
+        if rc != 0:
+            self._fail("arx_bam_write_encoded_device", rc)
 
     def sort_append(self, ref: "Reference", path: str, mode: str = "coordinate", max_bytes: int = 0, timed: bool = False):
         """arx_bam_sort_append: the records of the BAM file `path` appended on ref's GPU, ordered stably by ((uint32_t)refID, pos)
@@ -1416,6 +1478,16 @@ class BamWriter:
 
     def close(self):
         st = np.zeros(4, dtype=np.int64)
+        if self.h and self.index is not None:
+            ist, msg = np.zeros(20, dtype=np.int64), C.create_string_buffer(1024)
+            rc = _selftest_fn(self.lib, "arx_bam_close_indexed")(self.h, st.ctypes.data, ist.ctypes.data, msg, 1024)
+            self.h = C.c_void_p()
+            if rc != 0:
+                e = ArachneError("arx_bam_close_indexed: " + msg.value.decode(errors="replace"))
+                e.code = rc
+                raise e
+            return dict(records=int(st[0]), blocks=int(st[1]), bytes_in=int(st[2]), bytes_out=int(st[3]), index=_csi_stats(ist) if self.index == "csi" else _bai_stats(ist),
+                        index_format=self.index)
         if self.h:
             rc = self.lib.arx_bam_close(self.h, st.ctypes.data)
             self.h = C.c_void_p()

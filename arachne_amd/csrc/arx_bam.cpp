@@ -30,7 +30,7 @@ int arx_bam_write(arx_bam *h, const arx_bam_batch *batch)
 {
 	arx::BamSink *w = (arx::BamSink *)h;
 	try {
-		return w->write(*batch) ? ARX_OK : ARX_E_IO;
+		return w->write(*batch) ? ARX_OK : w->refused != ARX_OK ? w->refused : ARX_E_IO; // (refused: an indexing writer kept the batch out)
 	} catch (const std::exception &e) {
 		w->error = e.what();
 		return ARX_E_IO;
@@ -43,7 +43,7 @@ int arx_bam_write_select(arx_bam *h, const arx_bam_batch *batch, const int64_t *
 	if (n < 0 || (n > 0 && !idx)) { w->error = "bad record selection"; return ARX_E_ARG; }
 	try {
 		static const int64_t none = 0; // n = 0: an empty selection, not "all records"
-		return w->write(*batch, idx ? idx : &none, n) ? ARX_OK : ARX_E_IO;
+		return w->write(*batch, idx ? idx : &none, n) ? ARX_OK : w->refused != ARX_OK ? w->refused : ARX_E_IO;
 	} catch (const std::exception &e) {
 		w->error = e.what();
 		return ARX_E_IO;
@@ -61,15 +61,30 @@ int arx_bam_write_encoded(arx_bam *h, const uint8_t *stream, int64_t n_bytes, in
 	}
 }
 
-int arx_bam_close(arx_bam *h, int64_t *stats)
+// the close of either kind of writer: the BAM first, then -- an indexing writer (arx_bam_open_indexed, arx_bgzf.hip) -- the index from the table of
+// the blocks the sink recorded
+int arx_bam_close_indexed(arx_bam *h, int64_t *stats, int64_t *index_stats, char *msg, int32_t msg_cap)
 {
 	arx::BamSink *w = (arx::BamSink *)h;
+	if (index_stats) for (int k = 0; k < 20; ++k) index_stats[k] = 0;
+	if (!w) return ARX_E_ARG;
 	bool ok = false;
 	try { ok = w->close(); } catch (const std::exception &) {}
 	if (stats) { stats[0] = w->n_records; stats[1] = w->n_blocks; stats[2] = w->bytes_in; stats[3] = w->bytes_out + 28; }
+	int rc = ok ? ARX_OK : ARX_E_IO;
+	std::string text = ok ? std::string() : w->error;
+	if (w->tap) {
+		std::string err;
+		int irc;
+		try { irc = w->tap->finish(w->block_at, ok, index_stats, err); } catch (const std::exception &e) { irc = ARX_E_DEVICE; err = e.what(); }
+		if (rc == ARX_OK && irc != ARX_OK) { rc = irc; text = err; }
+	}
+	if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", text.c_str());
 	delete w;
-	return ok ? ARX_OK : ARX_E_IO;
+	return rc;
 }
+
+int arx_bam_close(arx_bam *h, int64_t *stats) { return arx_bam_close_indexed(h, stats, nullptr, nullptr, 0); }
 
 const char *arx_bam_error(arx_bam *h) { return ((arx::BamSink *)h)->error.c_str(); }
 

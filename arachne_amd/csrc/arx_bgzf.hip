@@ -73,20 +73,31 @@ extern "C" int arx_bam_open_device(arx_ctx *ctx, const char *path, int32_t n_con
 	return ARX_OK;
 }
 
-extern "C" int arx_bam_write_encoded_device(arx_bam *h, const uint8_t *d_stream, int64_t n_bytes, int64_t n_records)
+// d_stream[0, n_bytes) of the compressor's device, behind the writer's carry, through the device sink.  admitted: an indexing writer has seen
+// these bytes already (bs_hand_over); otherwise it is shown them here, before anything is appended
+static int bam_write_device(arx::BamSink *w, const uint8_t *d_stream, int64_t n_bytes, int64_t n_records, bool admitted)
 {
-	arx::BamSink *w = (arx::BamSink *)h;
 	if (!w) return ARX_E_ARG;
 	arx::DeviceBgzf *z = dynamic_cast<arx::DeviceBgzf *>(w->comp.get());
 	if (!z) { w->error = "arx_bam_write_encoded_device on a writer of arx_bam_open: only arx_bam_open_device's writers take a device stream"; return ARX_E_ARG; }
 	if (n_bytes < 0 || n_records < 0 || (n_bytes > 0 && !d_stream)) { w->error = "arx_bam_write_encoded_device: bad arguments"; return ARX_E_ARG; }
 	if (n_bytes == 0) { if (n_records) { w->error = "arx_bam_write_encoded_device: records without bytes"; return ARX_E_ARG; } return ARX_OK; }
 	try {
+		if (!admitted) {
+			const int rc = w->admit(d_stream, n_bytes, z->dev);
+			if (rc != ARX_OK) return rc;
+		}
 		// a write on the host side may have left whole blocks pending only if its flush failed; the carry handed on is always short of a block
 		if (!w->flush(false)) return ARX_E_IO;
 		std::vector<uint8_t> tail;
+		std::vector<int64_t> sizes;
 		size_t nb = 0;
-		if (!z->run_device(w->pending.data(), w->pending.size(), d_stream, (size_t)n_bytes, w->f, w->bytes_out, nb, tail, w->error)) return ARX_E_IO;
+		const int64_t from = w->bytes_out;
+		if (!z->run_device(w->pending.data(), w->pending.size(), d_stream, (size_t)n_bytes, w->f, w->bytes_out, nb, tail, w->error, w->record_blocks ? &sizes : nullptr)) return ARX_E_IO;
+		if (w->record_blocks) {
+			if (sizes.size() != nb) { w->error = "the compressor reported the sizes of " + std::to_string(sizes.size()) + " blocks, not " + std::to_string(nb); return ARX_E_IO; }
+			w->note_blocks(sizes, from);
+		}
 		w->n_blocks += (int64_t)nb; w->bytes_in += (int64_t)(nb * arx::BamSink::BLOCK_IN);
 		w->pending.swap(tail);
 		w->n_records += n_records;
@@ -95,6 +106,10 @@ extern "C" int arx_bam_write_encoded_device(arx_bam *h, const uint8_t *d_stream,
 		return ARX_E_IO;
 	}
 	return ARX_OK;
+}
+extern "C" int arx_bam_write_encoded_device(arx_bam *h, const uint8_t *d_stream, int64_t n_bytes, int64_t n_records)
+{
+	return bam_write_device((arx::BamSink *)h, d_stream, n_bytes, n_records, false);
 }
 
 extern "C" int arx_selftest_bgzf(int32_t device, const uint8_t *src, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, int64_t *stats)
@@ -196,6 +211,50 @@ extern "C" int arx_bam_open_ex(arx_ctx *ctx, const char *path, int32_t n_contigs
 	return ARX_OK;
 }
 
+// ---- the writer that indexes what it appends (hip_bamindex.h: BiWriterTap)
+extern "C" int arx_bam_open_indexed(arx_ctx *ctx, const char *path, int32_t n_contigs, const char *const *names, const int32_t *lens, const char *extra_header, int32_t threads,
+                                    int32_t level, int32_t flags, int32_t index, int32_t min_shift, const char *index_path, arx_bam **out, char *msg, int32_t msg_cap)
+{
+	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
+	if (out) *out = nullptr;
+	if (!ctx) { say("arx_bam_open_indexed: null context: the index is built on its GPU"); return ARX_E_ARG; }
+	if (!out || !path || n_contigs < 0 || (n_contigs > 0 && (!names || !lens))) { say("arx_bam_open_indexed: null argument"); return ARX_E_ARG; }
+	if (flags & ~(ARX_BAM_COORDINATE | ARX_BAM_DEVICE_SINK)) { say("arx_bam_open_indexed: unknown flag bits"); return ARX_E_ARG; }
+	if (index != ARX_BAM_INDEX_BAI && index != ARX_BAM_INDEX_CSI && index != ARX_BAM_INDEX_AUTO) { say("arx_bam_open_indexed: index is ARX_BAM_INDEX_BAI, _CSI or _AUTO"); return ARX_E_ARG; }
+	for (int32_t i = 0; i < n_contigs; ++i)
+		if (lens[i] < 0) { say("arx_bam_open_indexed: contig " + std::to_string(i) + " has a negative length"); return ARX_E_ARG; }
+	const int32_t too_long = arx::bi_long_contig(n_contigs, lens);
+	const bool csi = index == ARX_BAM_INDEX_CSI || (index == ARX_BAM_INDEX_AUTO && too_long >= 0);
+	if (!csi && too_long >= 0) { say(std::string(path) + ": " + arx::bi_long_text(too_long, lens[too_long])); return ARX_E_ARG; }
+	const int32_t shift = csi ? arx::bi_csi_shift(min_shift) : 0;
+	if (shift < 0) { say("arx_bam_open_indexed: min_shift lies outside [10, 24]"); return ARX_E_ARG; }
+	const arx::BiScheme sc = csi ? arx::bi_csi_scheme(shift, n_contigs, lens) : arx::BI_BAI;
+	const bool device_sink = (flags & ARX_BAM_DEVICE_SINK) != 0;
+	arx::BamSink *w = nullptr;
+	try {
+		const int device = arx_ctx_device(ctx);
+		std::unique_ptr<arx::BiWriterTap> tap(new arx::BiWriterTap());
+		w = new arx::BamSink();
+		w->coordinate = true;
+		w->record_blocks = true;
+		if (device_sink) w->comp = arx::shared_device_bgzf(device);
+		if (!w->open(path, n_contigs, names, lens, extra_header, threads, device_sink ? 1 : level)) {
+			const bool io = !device_sink || !w->f;
+			say(w->error);
+			delete w;
+			return io ? ARX_E_IO : ARX_E_DEVICE;
+		}
+		tap->begin(device, sc, csi, index_path ? std::string(index_path) : std::string(path) + (csi ? ".csi" : ".bai"), n_contigs, lens, w->bytes_in); // (the header is all that went in)
+		w->tap = std::move(tap);
+	} catch (const std::exception &e) {
+		say(e.what());
+		delete w;
+		return ARX_E_DEVICE;
+	}
+	*out = (arx_bam *)w;
+	return ARX_OK;
+}
+
 extern "C" int arx_bam_sort_append(arx_ctx *ctx, arx_bam *h, const char *in_path, int32_t mode, int64_t max_bytes, int64_t *stats, char *msg, int32_t msg_cap)
 {
 	auto say = [&](const std::string &m) { if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str()); };
@@ -212,7 +271,7 @@ extern "C" int arx_bam_sort_append(arx_ctx *ctx, arx_bam *h, const char *in_path
 		int64_t l_pac = 0;
 		if (arx_contigs(ctx, &n, &names, &offs, &lens, &alt, &l_pac) != ARX_OK) { say("arx_bam_sort_append: the context has no contigs"); return ARX_E_ARG; }
 		const bool device_writer = dynamic_cast<arx::DeviceBgzf *>(w->comp.get()) != nullptr;
-		const int rc = arx::bs_sort_append(arx_ctx_device(ctx), w, device_writer, [&](const uint8_t *d, int64_t bytes, int64_t recs) { return arx_bam_write_encoded_device(h, d, bytes, recs); },
+		const int rc = arx::bs_sort_append(arx_ctx_device(ctx), w, device_writer, [&](const uint8_t *d, int64_t bytes, int64_t recs) { return bam_write_device(w, d, bytes, recs, true); },
 		                                   in_path, mode, max_bytes, n, names, lens, stats, err);
 		if (rc != ARX_OK) say(err);
 		return rc;
@@ -680,4 +739,66 @@ extern "C" int arx_selftest_bam_index_csi(int32_t device, const uint8_t *stream,
                                           int64_t *out_len, int64_t *stats)
 {
 	return selftest_bam_index(device, stream, n_bytes, hdr, n_ref, ref_len, n_blocks, blk_at, blk_isize, seg_bytes, slab_bytes, arx::bi_csi_shift(min_shift), out, out_cap, out_len, stats);
+}
+
+// the index a writer builds of what it is handed (dev_bamindex.h: BiPush), on a stream in host memory and a table of the writer's layout
+extern "C" int arx_selftest_bam_index_feeds(int32_t device, const uint8_t *stream, int64_t n_bytes, int64_t hdr, int32_t n_ref, const int32_t *ref_len, int64_t n_blocks,
+                                            const int64_t *blk_at, int64_t seg_bytes, int64_t n_feeds, const int64_t *feed_end, int64_t piece_bytes, int32_t min_shift, uint8_t *out,
+                                            int64_t out_cap, int64_t *out_len, int64_t *stats)
+{
+	const bool csi = min_shift != -1;
+	const int32_t csi_shift = csi ? arx::bi_csi_shift(min_shift) : 0;
+	if (csi_shift < 0 || n_bytes < 0 || hdr < 0 || hdr > n_bytes || n_ref < 0 || (n_ref > 0 && !ref_len) || n_blocks < 0 || !blk_at || seg_bytes < arx::BS_MIN_SEG ||
+	    (seg_bytes & (seg_bytes - 1)) || n_feeds < 1 || !feed_end || piece_bytes < 0 || out_cap < 0 || (out_cap > 0 && !out) || !out_len || (n_bytes > 0 && !stream))
+		return ARX_E_ARG;
+	*out_len = 0;
+	if (stats) for (int k = 0; k < arx::BI_N_STATS; ++k) stats[k] = 0;
+	if (n_blocks != arx::bi_header_blocks(hdr) + (n_bytes - hdr + arx::BI_BLOCK - 1) / arx::BI_BLOCK) return ARX_E_ARG; // the writer's layout
+	for (int64_t b = 0; b <= n_blocks; ++b)
+		if (blk_at[b] < 0 || blk_at[b] >= arx::BI_MAX_AT || (b > 0 && blk_at[b] <= blk_at[b - 1])) return ARX_E_ARG;
+	for (int64_t k = 0; k < n_feeds; ++k)
+		if (feed_end[k] < 0 || feed_end[k] > n_bytes || (k > 0 && feed_end[k] < feed_end[k - 1])) return ARX_E_ARG;
+	if (feed_end[n_feeds - 1] != n_bytes || (!csi && arx::bi_long_contig(n_ref, ref_len) >= 0)) return ARX_E_ARG;
+	for (int32_t i = 0; i < n_ref; ++i)
+		if (ref_len[i] < 0) return ARX_E_ARG;
+	const arx::BiScheme sc = csi ? arx::bi_csi_scheme(csi_shift, n_ref, ref_len) : arx::BI_BAI;
+	try {
+		arx::select_device(device, arx::BI_NO_DEVICE);
+		arx::Stream st;
+		st.create();
+		arx::BiHipDrv drv; drv.st = st;
+		const double t0 = arx::bs_now_us();
+		arx::DevBuf d_s((size_t)n_bytes);
+		drv.upload(d_s.p, stream, (size_t)n_bytes);
+		arx::BiPush<arx::BiHipDrv> push;
+		push.begin(drv, n_ref, ref_len, sc, hdr, seg_bytes, piece_bytes);
+		int bi = arx::BI_OK;
+		int64_t at = hdr;
+		for (int64_t k = 0; k < n_feeds && bi == arx::BI_OK; ++k) {
+			if (feed_end[k] <= at) continue; // an end inside the header, or an empty feed
+			bi = push.feed(drv, d_s.as<uint8_t>() + at, feed_end[k] - at);
+			at = feed_end[k];
+		}
+		if (bi == arx::BI_OK) bi = push.finish(drv, blk_at);
+		std::string err;
+		const int rc = arx::bi_result(bi, push.ix, "the stream", err);
+		if (rc != ARX_OK) {
+			if (stats) stats[9] = (int64_t)push.ix.err; // the first offending record's number << 8 | the rule, or -1
+			return rc;
+		}
+		const std::vector<uint8_t> bytes = csi ? arx::bi_serialise_csi(push.ix) : arx::bi_serialise(push.ix);
+		if ((int64_t)bytes.size() > out_cap) return ARX_E_TOO_LARGE;
+		memcpy(out, bytes.data(), bytes.size());
+		*out_len = (int64_t)bytes.size();
+		drv.us[arx::BI_T_TOTAL] = arx::bs_now_us() - t0;
+		arx::bi_stats(stats, drv, push.ix, n_bytes, n_blocks);
+		if (csi) arx::bi_stats_csi(stats, sc);
+	} catch (const arx::BsTooLarge &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const arx::HipOutOfMemory &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
 }

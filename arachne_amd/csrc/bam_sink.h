@@ -29,10 +29,22 @@ namespace arx {
 
 // The seam behind flush(): something else that turns `total` bytes, cut every BamSink::BLOCK_IN bytes, into framed BGZF blocks and writes them to f
 // in order, adding what it wrote to bytes_out.  BamSink's own path (zlib on `threads` host threads) is the default; hip_bgzf.h holds the one
-// that compresses on the GPU (arx_bam_open_device).
+// that compresses on the GPU (arx_bam_open_device).  sizes: null, or where the framed size of every block written is appended, in order (a writer
+// that records where its blocks lie: BamSink::record_blocks).
 struct BlockCompressor {
 	virtual ~BlockCompressor() {}
-	virtual bool run(const uint8_t *src, size_t total, FILE *f, int64_t &bytes_out, std::string &error) = 0;
+	virtual bool run(const uint8_t *src, size_t total, FILE *f, int64_t &bytes_out, std::string &error, std::vector<int64_t> *sizes) = 0;
+};
+
+// What an indexing writer (arx_bam_open_indexed; arx_bgzf.hip holds the one implementation) hangs on its sink: it is shown every append before
+// the sink takes it, and is handed the table of the blocks once the file is closed.
+struct StreamTap {
+	virtual ~StreamTap() {}
+	// p[0, n): the next bytes of the record stream, in host memory (device < 0) or in the memory of that HIP device.  ARX_OK: the sink goes on
+	// and appends them; anything else: it appends nothing, error says why
+	virtual int take(const uint8_t *p, int64_t n, int device, std::string &error) = 0;
+	// the file is closed: block_at[0 .. n_blocks], the last entry the EOF block's.  bam_ok: every append and the close went well
+	virtual int finish(const std::vector<int64_t> &block_at, bool bam_ok, int64_t *index_stats, std::string &error) = 0;
 };
 
 struct BamSink {
@@ -43,6 +55,10 @@ struct BamSink {
 	std::string error;
 	std::vector<uint8_t> pending;         // uncompressed bytes not yet cut into a block
 	int64_t n_records = 0, n_blocks = 0, bytes_in = 0, bytes_out = 0;
+	bool record_blocks = false;           // set before open(): block_at keeps the file offset of every block written (8 bytes a block), the EOF block's last
+	std::vector<int64_t> block_at;
+	std::unique_ptr<StreamTap> tap;       // null: a plain writer
+	int refused = ARX_OK;                 // what the tap answered where it kept the last append out
 	static constexpr size_t BLOCK_IN = 0xff00; // BGZF: at most 64 KiB per block after compression; 65280 input bytes always fit
 
 	static void put32(std::vector<uint8_t> &v, uint32_t x) { for (int i = 0; i < 4; ++i) v.push_back((uint8_t)(x >> (8 * i))); }
@@ -127,6 +143,7 @@ struct BamSink {
 	{
 		const int64_t n = idx ? n_sel : b.n_records;
 		auto rec = [&](int64_t k) { return idx ? idx[k] : k; };
+		refused = ARX_OK;
 		for (int64_t k = 0; k < n; ++k) {
 			const int64_t i = rec(k);
 			if (i < 0 || i >= b.n_records) { error = "record index " + std::to_string(i) + " outside the batch"; return false; }
@@ -140,8 +157,30 @@ struct BamSink {
 		pending.resize(base + off[n]);
 		uint8_t *dst = pending.data() + base;
 		parallel((size_t)n, [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; ++k) encode(b, rec((int64_t)k), dst + off[k]); });
+		if (admit(dst, (int64_t)off[n], -1) != ARX_OK) { pending.resize(base); return false; } // (encoded where they would lie: nothing of them stays)
 		n_records += n;
 		return flush(false);
+	}
+
+	// The one hand-over: every append shows its bytes to the tap first, where there is one, and only then reaches the sink (put_raw, the device
+	// sink's run_device, or write() above, which encodes in place).  device: where p lies (StreamTap::take).  Not ARX_OK: nothing is to be appended
+	int admit(const uint8_t *p, int64_t n, int device)
+	{
+		refused = ARX_OK;
+		if (!tap || n <= 0) return ARX_OK;
+		return refused = tap->take(p, n, device, error);
+	}
+	// n admitted bytes of host memory behind what is pending
+	bool put_raw(const uint8_t *p, size_t n, int64_t recs)
+	{
+		pending.insert(pending.end(), p, p + n);
+		n_records += recs;
+		return flush(false);
+	}
+	// the file offset of the next block written, where the writer records them
+	void note_blocks(const std::vector<int64_t> &sizes, int64_t from)
+	{
+		for (int64_t z : sizes) { block_at.push_back(from); from += z; }
 	}
 
 	// arx_bam_write_encoded: records that are BAM-encoded already (what encode() writes, e.g. by the device: dev_records.h).  Checked is only what is
@@ -158,9 +197,9 @@ struct BamSink {
 			at += 4 + bs; ++seen;
 		}
 		if (seen != n) { error = "arx_bam_write_encoded: the stream holds " + std::to_string(seen) + " records, not " + std::to_string(n); return ARX_E_ARG; }
-		pending.insert(pending.end(), stream, stream + n_bytes);
-		n_records += n;
-		return flush(false) ? ARX_OK : ARX_E_IO;
+		const int rc = admit(stream, n_bytes, -1);
+		if (rc != ARX_OK) return rc;
+		return put_raw(stream, (size_t)n_bytes, n) ? ARX_OK : ARX_E_IO;
 	}
 
 	// compresses every whole block of `pending` (all of it when `all`), writes them in order
@@ -171,7 +210,13 @@ struct BamSink {
 		if (nb == 0) return true;
 		if (comp) {
 			const size_t used = all ? total : nb * BLOCK_IN;
-			if (!comp->run(pending.data(), used, f, bytes_out, error)) return false;
+			std::vector<int64_t> sizes;
+			const int64_t from = bytes_out;
+			if (!comp->run(pending.data(), used, f, bytes_out, error, record_blocks ? &sizes : nullptr)) return false;
+			if (record_blocks) {
+				if (sizes.size() != nb) { error = "the compressor reported the sizes of " + std::to_string(sizes.size()) + " blocks, not " + std::to_string(nb); return false; }
+				note_blocks(sizes, from);
+			}
 			n_blocks += (int64_t)nb; bytes_in += (int64_t)used;
 			pending.erase(pending.begin(), pending.begin() + used);
 			return true;
@@ -187,6 +232,7 @@ struct BamSink {
 		for (size_t k = 0; k < nb; ++k) {
 			if (!ok[k]) { error = "deflate failed"; return false; }
 			if (fwrite(out[k].data(), 1, out[k].size(), f) != out[k].size()) { error = "write failed"; return false; }
+			if (record_blocks) block_at.push_back(bytes_out);
 			bytes_out += (int64_t)out[k].size(); ++n_blocks;
 		}
 		const size_t used = all ? total : nb * BLOCK_IN;
@@ -227,6 +273,7 @@ struct BamSink {
 		if (f) {
 			ok = flush(true);
 			static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+			if (record_blocks) block_at.push_back(bytes_out);
 			if (fwrite(eof, 1, 28, f) != 28) { error = "write failed"; ok = false; }
 			if (fclose(f) != 0) { error = "close failed"; ok = false; }
 			f = nullptr;

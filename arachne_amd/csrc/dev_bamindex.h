@@ -27,6 +27,9 @@
 // scheme of a CSI index (bi_csi_scheme) the same run serves contigs of up to 2^31 - 1 bases, the window table is what the bins' loffset is
 // read from (bi_serialise_csi), and the run key refID << bin_bits | bin widens with the depth.
 // Nothing here depends on the order of the items: every write goes to a slot of its own item, or is a minimum or a sum.
+// The slab body is stated once (BiSlabs) and driven from two sides: bi_run pulls the slabs of a finished file from `src`; BiPush is handed the
+// record stream by a writer while it appends, feed by feed, with the closed form P in place of V until the writer's block table is known
+// (tests/bixsim/bam_index_feeds_sim.cpp runs that side on the host).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -89,6 +92,24 @@ ARX_HDI uint64_t bi_voff(const BiRows &r, int64_t o)
 	}
 	return (uint64_t)r.at[lo] << 16 | (uint64_t)(o - r.ooff[lo]);
 }
+// The second source of offsets, a closed form: a writer (bam_sink.h) lays its stream out before any compressed size is known -- the header ends
+// its own hb = ceil(H / BI_BLOCK) blocks, every block behind it but the last holds BI_BLOCK bytes -- so the byte r of the record stream lies in block
+// hb + r / BI_BLOCK at r % BI_BLOCK.  P(r) = block ordinal << 16 | offset within stands in for V until the writer has closed: file offsets grow
+// strictly with the ordinal, so P orders as V does, the join rule decides the same, and the windows' minima pick the same records.  BiPush::finish
+// turns P into V by one lookup in the table of block offsets
+constexpr int64_t BI_BLOCK = 0xff00; // BamSink::BLOCK_IN
+ARX_HDI int64_t bi_header_blocks(int64_t H) { return (H + BI_BLOCK - 1) / BI_BLOCK; }
+ARX_HDI uint64_t bi_poff(int64_t hb, int64_t r) { return (uint64_t)(hb + r / BI_BLOCK) << 16 | (uint64_t)(r % BI_BLOCK); }
+// where a buffer's bytes lie: rows.n > 0 -- in the rows of a file; else by the closed form, byte 0 of the buffer being byte `base` of the record stream
+struct BiOff { BiRows rows; int64_t base, hb; };
+ARX_HDI uint64_t bi_off(const BiOff &f, int64_t o) { return f.rows.n > 0 ? bi_voff(f.rows, o) : bi_poff(f.hb, f.base + o); }
+// P -> V, one item per window of the table; an unset window stays unset.  p_total: P(the stream's size), which no start equals -- the contract's
+// V(total) is the EOF block's offset << 16, not an offset inside the short last block (only the end of the last run ever takes it: bi_p2v)
+ARX_HDI uint64_t bi_p2v(const int64_t *at, uint64_t p_total, uint64_t v_total, uint64_t p) { return p == p_total ? v_total : (uint64_t)at[p >> 16] << 16 | (p & 0xffff); }
+struct BiXlatF {
+	uint64_t *lin; const int64_t *at; uint64_t p_total, v_total;
+	ARX_DEVI void operator()(int64_t i) const { if (lin[i] != BI_UNSET) lin[i] = bi_p2v(at, p_total, v_total, lin[i]); }
+};
 // ((uint32_t)refID, pos) in one word that orders as the pair does, pos as the signed number it is
 ARX_HDI uint64_t bi_key(const uint8_t *p) { return (uint64_t)bs_r32(p + 4) << 32 | (uint64_t)(bs_r32(p + 8) ^ 0x80000000u); }
 ARX_HDI int bi_key_bits(int32_t n_ref, const BiScheme &sc) { return bs_key_bits(n_ref) - 32 + sc.bin_bits(); } // of refID << bin_bits | bin, refID up to n_ref
@@ -111,10 +132,10 @@ struct BiTailF {
 };
 
 struct BiRecF {
-	const uint8_t *s; int64_t n; const int64_t *rec_off; BiRows rows;
+	const uint8_t *s; int64_t n; const int64_t *rec_off; BiOff off;
 	int32_t n_ref; const int32_t *ref_len; const int64_t *lin_base; uint64_t *lin;
 	int64_t rec0;                      // the number of the buffer's first record
-	uint64_t *rb, *vbeg; int64_t *cnt; // per record: refID << bin_bits | bin; V(start); mapped | unmapped << 32
+	uint64_t *rb, *vbeg; int64_t *cnt; // per record: refID << bin_bits | bin; V(start) (P(start) under the closed form); mapped | unmapped << 32
 	int64_t *words;
 	BiScheme sc;
 	ARX_DEVI void fail(int64_t j, int rule) const { ARX_ATOMIC_MINU64((uint64_t *)&words[BI_W_ERR], (uint64_t)(rec0 + j) << 8 | (uint64_t)rule); }
@@ -124,7 +145,7 @@ struct BiRecF {
 		const uint8_t *p = s + o; // at least 36 bytes: bi_run hands over whole records only
 		const int bits = sc.bin_bits();
 		rb[j] = (uint64_t)(uint32_t)n_ref << bits; cnt[j] = 0;
-		vbeg[j] = bi_voff(rows, o);
+		vbeg[j] = bi_off(off, o);
 		const int64_t all = 4 + (int64_t)bs_r32(p), l_name = p[12], n_cig = (int64_t)p[16] | (int64_t)p[17] << 8, need = 36 + l_name + 4 * n_cig;
 		if (need > all || o + need > n) { fail(j, BI_R_FIELDS); return; }
 		const int32_t rid = (int32_t)bs_r32(p + 4), pos = (int32_t)bs_r32(p + 8);
@@ -304,39 +325,50 @@ inline BiScheme bi_csi_scheme(int32_t min_shift, int32_t n_ref, const int32_t *r
 	return sc;
 }
 
-// -> BI_*.  sc: the bin scheme, bin 0 of which spans every contig (BI_BAI: contigs of at most BI_MAX_REF bases); seg as in dev_bamsort.h.
-// BI_E_RULE: ix.err says which record and rule.  ix.refs[i].lin is the table of windows of 2^sc.min_shift bases, cut and backfilled
-template <class Drv, class Src> int bi_run(Drv &drv, Src &src, const BiBlocks &B, int64_t hdr, int32_t n_ref, const int32_t *ref_len, int64_t seg, BiIndex &ix, const BiScheme sc = BI_BAI)
-{
+// The slab body, stated once: bi_run pulls its slabs from a source, BiPush is handed them.  begin(); slab() for the stream's bytes [a, b) in
+// order; table() at the end.  sc: the bin scheme, bin 0 of which spans every contig (BI_BAI: contigs of at most BI_MAX_REF bases); seg as in dev_bamsort.h
+template <class Drv> struct BiSlabs {
 	typedef typename Drv::Buf Buf;
-	ix = BiIndex();
-	ix.sc = sc;
-	ix.refs.resize((size_t)n_ref);
-	ix.n_slabs = B.n_slabs();
-	std::vector<int64_t> base((size_t)n_ref + 1, 0);
-	for (int32_t i = 0; i < n_ref; ++i) base[(size_t)i + 1] = base[(size_t)i] + bi_windows(ref_len[i], sc.min_shift);
-	const int64_t L = base[(size_t)n_ref];
+	BiIndex *ix = nullptr;
+	int32_t n_ref = 0;
+	int64_t seg = 0, L = 0;
+	BiScheme sc = BI_BAI;
+	std::vector<int64_t> base;
 	Buf d_lin, d_base, d_len, d_words, buf, next, d_segs, d_off, d_rows, d_rec, d_scan, d_runs, d_chunks;
-	d_lin.alloc((size_t)L * 8);
-	if (L) drv.fill(d_lin.p, 0xff, (size_t)L * 8);
-	d_base.alloc(base.size() * 8);
-	drv.upload(d_base.p, base.data(), base.size() * 8);
-	d_len.alloc((size_t)n_ref * 4);
-	if (n_ref) drv.upload(d_len.p, ref_len, (size_t)n_ref * 4);
-	d_words.alloc(BI_N_WORDS * 8);
-	int64_t *words = d_words.template as<int64_t>();
-	drv.fill(d_words.p, 0, BI_N_WORDS * 8);
-	drv.put(&words[BI_W_ERR], -1);
-
-	int64_t entry = hdr, g0 = 0, carry = 0, from = 0; // the buffer's first `carry` bytes are the last buffer's from `from` on
+	int64_t entry = 0, g0 = 0, carry = 0, from = 0; // the buffer's first `carry` bytes are the last buffer's from `from` on
 	int32_t have_prev = 0;
 	uint64_t prev_key = 0, prev_rb = 0;
-	for (int64_t k = 0; k < ix.n_slabs; ++k) {
-		const int64_t a = B.cut_o[(size_t)k], b = B.cut_o[(size_t)k + 1], n = carry + (b - a);
-		const bool closed = k + 1 == ix.n_slabs;
+
+	void begin(Drv &drv, BiIndex &x, int64_t hdr, int32_t n_ref_, const int32_t *ref_len, int64_t seg_, const BiScheme &sc_)
+	{
+		ix = &x; n_ref = n_ref_; seg = seg_; sc = sc_;
+		x = BiIndex();
+		x.sc = sc;
+		x.refs.resize((size_t)n_ref);
+		base.assign((size_t)n_ref + 1, 0);
+		for (int32_t i = 0; i < n_ref; ++i) base[(size_t)i + 1] = base[(size_t)i] + bi_windows(ref_len[i], sc.min_shift);
+		L = base[(size_t)n_ref];
+		d_lin.alloc((size_t)L * 8);
+		if (L) drv.fill(d_lin.p, 0xff, (size_t)L * 8);
+		d_base.alloc(base.size() * 8);
+		drv.upload(d_base.p, base.data(), base.size() * 8);
+		d_len.alloc((size_t)n_ref * 4);
+		if (n_ref) drv.upload(d_len.p, ref_len, (size_t)n_ref * 4);
+		d_words.alloc(BI_N_WORDS * 8);
+		drv.fill(d_words.p, 0, BI_N_WORDS * 8);
+		drv.put(&d_words.template as<int64_t>()[BI_W_ERR], -1);
+		entry = hdr; g0 = carry = from = 0; have_prev = 0; prev_key = prev_rb = 0;
+	}
+
+	// the stream's bytes [a, b), behind those of the call before.  load(dst): puts them at dst (false: BI_E_INFLATE); off(g0, b, d_rows): the BiOff of
+	// a buffer that holds the stream's [g0, b); vend(o): the offset word of the stream's byte o <= b.  closed: the chain ends with b
+	template <class Load, class Off, class End> int slab(Drv &drv, int64_t a, int64_t b, bool closed, Load load, Off off, End vend)
+	{
+		int64_t *words = d_words.template as<int64_t>();
+		const int64_t n = carry + (b - a);
 		next.alloc((size_t)n);
 		if (carry) drv.copy(next.p, buf.template as<uint8_t>() + from, (size_t)carry);
-		if (!src.load(k, next.template as<uint8_t>() + carry, b - a)) return BI_E_INFLATE;
+		if (!load(next.template as<uint8_t>() + carry)) return BI_E_INFLATE;
 		std::swap(buf, next);
 		next.release();
 		g0 = a - carry;
@@ -356,27 +388,22 @@ template <class Drv, class Src> int bi_run(Drv &drv, Src &src, const BiBlocks &B
 			drv.items("bi_tail", 1, BiTailF{s, n, rec_off, f.n_records, words});
 			np = drv.get(&words[BI_W_NP]); from = drv.get(&words[BI_W_FROM]);
 		}
+		++ix->n_slabs;
 		if (np > 0) {
-			// the rows of the blocks the buffer's bytes lie in
-			const int64_t r0 = B.row_of(g0), r1 = B.row_of(b - 1) + 1;
-			std::vector<int64_t> rows((size_t)(2 * (r1 - r0)));
-			for (int64_t r = r0; r < r1; ++r) { rows[(size_t)(r - r0)] = B.ooff[(size_t)r] - g0; rows[(size_t)(r1 - r0 + r - r0)] = B.at[(size_t)r]; }
-			d_rows.alloc(rows.size() * 8);
-			drv.upload(d_rows.p, rows.data(), rows.size() * 8);
-			const BiRows R = {d_rows.template as<int64_t>(), d_rows.template as<int64_t>() + (r1 - r0), r1 - r0};
+			const BiOff R = off(g0, b, d_rows);
 			d_rec.alloc((size_t)np * 8 * 4);
 			uint64_t *rb = d_rec.template as<uint64_t>(), *vbeg = rb + np;
 			int64_t *cnt = (int64_t *)(vbeg + np), *flag = cnt + np;
 			d_scan.alloc((size_t)(np + 1) * 8 * 2);
 			int64_t *fx = d_scan.template as<int64_t>(), *cx = fx + np + 1;
-			drv.items("bi_rec", np, BiRecF{s, n, rec_off, R, n_ref, d_len.template as<int32_t>(), d_base.template as<int64_t>(), d_lin.template as<uint64_t>(), ix.n_records, rb, vbeg, cnt, words, sc});
-			drv.items("bi_flag", np, BiFlagF{s, rec_off, rb, np, ix.n_records, n_ref, have_prev, prev_key, prev_rb, flag, words, sc});
+			drv.items("bi_rec", np, BiRecF{s, n, rec_off, R, n_ref, d_len.template as<int32_t>(), d_base.template as<int64_t>(), d_lin.template as<uint64_t>(), ix->n_records, rb, vbeg, cnt, words, sc});
+			drv.items("bi_flag", np, BiFlagF{s, rec_off, rb, np, ix->n_records, n_ref, have_prev, prev_key, prev_rb, flag, words, sc});
 			const uint64_t err = (uint64_t)drv.get(&words[BI_W_ERR]);
-			if (err != BI_UNSET) { ix.err = err; return BI_E_RULE; }
+			if (err != BI_UNSET) { ix->err = err; return BI_E_RULE; }
 			drv.scan(flag, fx, np, "bi_scan");
 			drv.scan(cnt, cx, np, "bi_scan");
 			const int64_t n_runs = drv.get(&fx[np]), placed = drv.get(&cx[np]);
-			ix.n_no_coor += np - (placed & 0xffffffff) - (placed >> 32);
+			ix->n_no_coor += np - (placed & 0xffffffff) - (placed >> 32);
 			prev_key = (uint64_t)drv.get(&words[BI_W_LASTKEY]); prev_rb = (uint64_t)drv.get(&words[BI_W_LASTRB]); have_prev = 1;
 			// runs, then chunks
 			d_runs.alloc((size_t)n_runs * (8 * 5 + 4 * 2) + (size_t)(n_runs + 1) * 8 * 4);
@@ -385,7 +412,7 @@ template <class Drv, class Src> int bi_run(Drv &drv, Src &src, const BiBlocks &B
 			rc.key = q; q += n_runs; rc.beg = q; q += n_runs; rc.end = q; q += n_runs; skey = q; q += n_runs;
 			head = (int64_t *)q; q += n_runs; rc.c0 = (int64_t *)q; q += n_runs + 1; cs = (int64_t *)q; q += n_runs + 1; hx = (int64_t *)q; q += n_runs + 1;
 			sx = (int64_t *)q; q += n_runs + 1; rc.idx = (uint32_t *)q; idx = rc.idx + n_runs;
-			drv.items("bi_runs", np, BiRunsF{flag, fx, cx, rb, vbeg, np, B.voff(g0 + from), rc});
+			drv.items("bi_runs", np, BiRunsF{flag, fx, cx, rb, vbeg, np, vend(g0 + from), rc});
 			drv.sort_pairs(rc.key, skey, rc.idx, idx, n_runs, bi_key_bits(n_ref, sc));
 			drv.items("bi_head", n_runs, BiHeadF{skey, idx, rc, head, cs});
 			drv.scan(head, hx, n_runs, "bi_scan");
@@ -397,31 +424,112 @@ template <class Drv, class Src> int bi_run(Drv &drv, Src &src, const BiBlocks &B
 			drv.items("bi_chunks", n_runs, BiChunksF{skey, idx, rc, head, hx, sx, n_runs, cc});
 			std::vector<uint64_t> h((size_t)(4 * n_ch + 1));
 			drv.fetch(h.data(), d_chunks.p, h.size() * 8);
-			bi_append(ix, n_ref, h.data(), h.data() + n_ch, h.data() + 2 * n_ch, (const int64_t *)(h.data() + 3 * n_ch), n_ch);
-			ix.n_records += np;
+			bi_append(*ix, n_ref, h.data(), h.data() + n_ch, h.data() + 2 * n_ch, (const int64_t *)(h.data() + 3 * n_ch), n_ch);
+			ix->n_records += np;
 		}
 		entry = g0 + from;
 		carry = from < n ? n - from : 0;
+		return BI_OK;
 	}
-	if (ix.n_slabs == 0 && hdr != B.total) return BI_E_CHAIN;
-	ix.n_runs = drv.get(&words[BI_W_RUNS]);
-	// the linear index: cut behind the highest window set, an unset window below takes the next set one's value
-	std::vector<uint64_t> lin((size_t)L);
-	if (L) drv.fetch(lin.data(), d_lin.p, (size_t)L * 8);
-	for (int32_t i = 0; i < n_ref; ++i) {
-		BiRef &r = ix.refs[(size_t)i];
-		const uint64_t *win = lin.data() + base[(size_t)i];
-		int64_t hi = base[(size_t)i + 1] - base[(size_t)i] - 1;
-		while (hi >= 0 && win[hi] == BI_UNSET) --hi;
-		r.lin.assign(win, win + (hi + 1));
-		for (int64_t x = hi - 1; x >= 0; --x)
-			if (r.lin[(size_t)x] == BI_UNSET) r.lin[(size_t)x] = r.lin[(size_t)x + 1];
-		ix.n_lin += hi + 1;
-		ix.n_bins += (int64_t)r.bins.size();
-		for (const auto &bn : r.bins) ix.n_chunks += (int64_t)bn.second.size();
+
+	// the linear index: cut behind the highest window set, an unset window below takes the next set one's value.  xlat(lin, L): what is still to
+	// be done to the table where it lies (BiPush: P -> V)
+	template <class Xlat> void table(Drv &drv, Xlat xlat)
+	{
+		ix->n_runs = drv.get(&d_words.template as<int64_t>()[BI_W_RUNS]);
+		if (L) xlat(d_lin.template as<uint64_t>(), L);
+		std::vector<uint64_t> lin((size_t)L);
+		if (L) drv.fetch(lin.data(), d_lin.p, (size_t)L * 8);
+		for (int32_t i = 0; i < n_ref; ++i) {
+			BiRef &r = ix->refs[(size_t)i];
+			const uint64_t *win = lin.data() + base[(size_t)i];
+			int64_t hi = base[(size_t)i + 1] - base[(size_t)i] - 1;
+			while (hi >= 0 && win[hi] == BI_UNSET) --hi;
+			r.lin.assign(win, win + (hi + 1));
+			for (int64_t x = hi - 1; x >= 0; --x)
+				if (r.lin[(size_t)x] == BI_UNSET) r.lin[(size_t)x] = r.lin[(size_t)x + 1];
+			ix->n_lin += hi + 1;
+			ix->n_bins += (int64_t)r.bins.size();
+			for (const auto &bn : r.bins) ix->n_chunks += (int64_t)bn.second.size();
+		}
 	}
+};
+
+// -> BI_*.  BI_E_RULE: ix.err says which record and rule.  ix.refs[i].lin is the table of windows of 2^sc.min_shift bases, cut and backfilled
+template <class Drv, class Src> int bi_run(Drv &drv, Src &src, const BiBlocks &B, int64_t hdr, int32_t n_ref, const int32_t *ref_len, int64_t seg, BiIndex &ix, const BiScheme sc = BI_BAI)
+{
+	typedef typename Drv::Buf Buf;
+	BiSlabs<Drv> S;
+	S.begin(drv, ix, hdr, n_ref, ref_len, seg, sc);
+	const int64_t n_slabs = B.n_slabs();
+	for (int64_t k = 0; k < n_slabs; ++k) {
+		const int64_t a = B.cut_o[(size_t)k], b = B.cut_o[(size_t)k + 1];
+		const int rc = S.slab(drv, a, b, k + 1 == n_slabs, [&](uint8_t *dst) { return src.load(k, dst, b - a); },
+		                      [&](int64_t g0, int64_t b_, Buf &d_rows) { // the rows of the blocks the buffer's bytes lie in
+			const int64_t r0 = B.row_of(g0), r1 = B.row_of(b_ - 1) + 1;
+			std::vector<int64_t> rows((size_t)(2 * (r1 - r0)));
+			for (int64_t r = r0; r < r1; ++r) { rows[(size_t)(r - r0)] = B.ooff[(size_t)r] - g0; rows[(size_t)(r1 - r0 + r - r0)] = B.at[(size_t)r]; }
+			d_rows.alloc(rows.size() * 8);
+			drv.upload(d_rows.p, rows.data(), rows.size() * 8);
+			return BiOff{BiRows{d_rows.template as<int64_t>(), d_rows.template as<int64_t>() + (r1 - r0), r1 - r0}, 0, 0};
+		}, [&](int64_t o) { return B.voff(o); });
+		if (rc != BI_OK) return rc;
+	}
+	if (n_slabs == 0 && hdr != B.total) return BI_E_CHAIN;
+	S.table(drv, [](uint64_t *, int64_t) {});
 	return BI_OK;
 }
+
+// bi_run with the direction reversed, for a writer that is handed its record stream piece by piece (the bytes behind the header; they end
+// anywhere -- inside a block_size field, the fixed part, a CIGAR: discovery with an open end, bi_tail and the carry see to that):
+// begin(), feed() any number of times, finish() with the table of the blocks the writer wrote.  Until then every offset is P (above).
+// Memory on top of the caller's bytes: the window table for the writer's life, and per feed one piece at a time -- the piece's bytes with the carry in
+// front, 56 bytes per record of the piece, about 100 per run; finish() adds 8 bytes per block for as long as it runs
+template <class Drv> struct BiPush {
+	BiSlabs<Drv> S;
+	BiIndex ix;
+	int64_t hb = 0, total = 0, piece = 0;
+	typename Drv::Buf d_at;
+
+	// H: the header's bytes in front of the record stream; piece_max: the most bytes of a feed indexed at once (0: all of them)
+	void begin(Drv &drv, int32_t n_ref, const int32_t *ref_len, const BiScheme &sc, int64_t H, int64_t seg, int64_t piece_max)
+	{
+		S.begin(drv, ix, 0, n_ref, ref_len, seg, sc);
+		hb = bi_header_blocks(H); total = 0; piece = piece_max;
+	}
+	// d[0, n): the next bytes of the record stream, in the launches' memory -> BI_*.  After anything but BI_OK the index is lost
+	int feed(Drv &drv, const uint8_t *d, int64_t n)
+	{
+		for (int64_t o = 0; o < n;) {
+			const int64_t len = piece > 0 && n - o > piece ? piece : n - o, a = total;
+			const int rc = S.slab(drv, a, a + len, false, [&](uint8_t *dst) { drv.copy(dst, d + o, (size_t)len); return true; },
+			                      [&](int64_t g0, int64_t, typename Drv::Buf &) { return BiOff{BiRows{nullptr, nullptr, 0}, g0, hb}; }, [&](int64_t at) { return bi_poff(hb, at); });
+			if (rc != BI_OK) return rc;
+			total += len; o += len;
+		}
+		return BI_OK;
+	}
+	int64_t n_blocks() const { return hb + (total + BI_BLOCK - 1) / BI_BLOCK; } // of the writer's layout, the EOF block not counted
+	// at[0 .. n_blocks()]: where the blocks lie in the file, the last entry the EOF block's -> BI_OK, or BI_E_CHAIN: the stream ends inside a record
+	int finish(Drv &drv, const int64_t *at)
+	{
+		if (S.carry != 0 || S.entry != total) return BI_E_CHAIN;
+		const int64_t nb = n_blocks();
+		const uint64_t p_total = bi_poff(hb, total), v_total = (uint64_t)at[nb] << 16;
+		S.table(drv, [&](uint64_t *lin, int64_t L) {
+			d_at.alloc((size_t)(nb + 1) * 8);
+			drv.upload(d_at.p, at, (size_t)(nb + 1) * 8);
+			drv.items("bi_xlat", L, BiXlatF{lin, d_at.template as<int64_t>(), p_total, v_total});
+		});
+		d_at.release();
+		for (BiRef &r : ix.refs) {
+			for (auto &bn : r.bins)
+				for (BiChunk &c : bn.second) { c.beg = bi_p2v(at, p_total, v_total, c.beg); c.end = bi_p2v(at, p_total, v_total, c.end); }
+			if (r.vmin != BI_UNSET) { r.vmin = bi_p2v(at, p_total, v_total, r.vmin); r.vmax = bi_p2v(at, p_total, v_total, r.vmax); }
+		}
+		return BI_OK;
+	}
+};
 
 // the bytes of the .bai (the SAM specification, 5.2): bins ascending, the pseudo-bin last in every contig that holds a record, n_no_coor always
 inline std::vector<uint8_t> bi_serialise(const BiIndex &ix)

@@ -2,6 +2,7 @@
 // sorted BAM file, its blocks inflated on the device slab by slab (inflate_launch over the rows of bgzf_walk, as the sort's copy mode), indexed
 // there by bi_run, and the .bai written as <path>.tmp and renamed.  arx_bam_index_csi and arx_selftest_bam_index_csi are the same drivers under
 // the scheme of a CSI index (bi_csi_scheme), serialised by bi_serialise_csi and written as BGZF by the host sink's own zlib path (BamSink).
+// BiWriterTap is the same index built by a writer of what it appends (arx_bam_open_indexed, arx_bam_close_indexed): BiPush behind the sink's tap.
 //
 //   k_bs_items<F>    hip_bamsort.h's kernel: one item of a functor per thread (bi_tail: the one last record; bi_rec, bi_flag, bi_runs: a record;
 //                    bi_head, bi_chunks: a run), started through hip_launch under the functor's name
@@ -166,6 +167,87 @@ inline bool bi_write_file(const std::vector<uint8_t> &out, const std::string &fi
 	}
 	return true;
 }
+
+// ---- the index a writer builds of what it is handed (arx_bam_open_indexed): BiPush behind the sink's tap (bam_sink.h: StreamTap).  Bytes that lie
+// in the memory of the writer's device are fed where they lie; host bytes go up in pieces of at most BI_UPLOAD.  The index is all or nothing: after an
+// append it refused, or an error of its own (which refuses nothing), the tap lets everything pass and the close writes no index
+constexpr int64_t BI_UPLOAD = (int64_t)64 << 20;
+struct BiWriterTap : StreamTap {
+	int device = 0;
+	bool csi = false, live = true;
+	int lost = ARX_E_ARG;        // what the close returns once the index is lost
+	std::string index_path, why; // why: what lost the index
+	Stream st;                   // declared before the buffers, so that it has ended when they are freed
+	BiHipDrv drv;
+	BiPush<BiHipDrv> push;
+	DevBuf stage;
+	int64_t header = 0;
+	double us_index = 0;
+
+	void begin(int device_, const BiScheme &sc, bool csi_, const std::string &path, int32_t n_ref, const int32_t *ref_len, int64_t H)
+	{
+		device = device_; csi = csi_; index_path = path; header = H;
+		select_device(device, BI_NO_DEVICE);
+		st.create();
+		drv.st = st;
+		push.begin(drv, n_ref, ref_len, sc, H, BS_SEG_DEFAULT, BS_SLAB_DEFAULT);
+	}
+	~BiWriterTap() override { (void)hipSetDevice(device); } // (the members are this device's)
+
+	int take(const uint8_t *p, int64_t n, int dev, std::string &error) override
+	{
+		if (!live) return ARX_OK;
+		if (dev >= 0 && dev != device) {
+			error = "the bytes lie on device " + std::to_string(dev) + ", the writer's index is built on device " + std::to_string(device) + ": append through a context of the writer's device";
+			return ARX_E_ARG; // nothing was fed: the index goes on
+		}
+		const double t0 = bs_now_us();
+		int rc = BI_OK;
+		try {
+			select_device(device, BI_NO_DEVICE);
+			if (dev >= 0) rc = push.feed(drv, p, n);
+			for (int64_t o = 0; dev < 0 && o < n && rc == BI_OK;) {
+				const int64_t len = n - o < BI_UPLOAD ? n - o : BI_UPLOAD;
+				stage.alloc((size_t)len);
+				drv.upload(stage.p, p + o, (size_t)len);
+				rc = push.feed(drv, stage.as<uint8_t>(), len);
+				o += len;
+			}
+			stage.release();
+			ARX_HIP_CHECK(hipStreamSynchronize(st));
+		} catch (const std::exception &e) { // the index's own trouble (device memory, say) keeps no append out: the BAM goes on, the close reports it
+			live = false; lost = ARX_E_DEVICE;
+			why = e.what();
+			return ARX_OK;
+		}
+		us_index += bs_now_us() - t0;
+		if (rc == BI_OK) return ARX_OK;
+		live = false;
+		const int code = bi_result(rc, push.ix, "the append was refused, nothing of it was written", error);
+		why = rc == BI_E_RULE ? bi_rule_text(push.ix.err) : "the chain of BAM records is broken";
+		return code;
+	}
+
+	int finish(const std::vector<int64_t> &block_at, bool bam_ok, int64_t *stats, std::string &error) override
+	{
+		if (!bam_ok) return ARX_OK; // the close's own error stands
+		if (!live) { error = "the BAM is complete, the index was not written: " + why; return lost; }
+		const double t0 = bs_now_us();
+		select_device(device, BI_NO_DEVICE);
+		const int64_t nb = push.n_blocks();
+		if ((int64_t)block_at.size() != nb + 1) { error = "the BAM is complete, the index was not written: the sink recorded " + std::to_string(block_at.size()) + " blocks where its layout has " + std::to_string(nb + 1); return ARX_E_DEVICE; }
+		if (block_at.back() >= BI_MAX_AT) { error = "the BAM is complete, the index was not written: the file is 2^48 bytes or longer, a virtual offset cannot address it"; return ARX_E_ARG; }
+		if (push.finish(drv, block_at.data()) != BI_OK) { error = "the BAM is complete, the index was not written: the record stream ends inside a record"; return ARX_E_IO; }
+		const double t_w = bs_now_us();
+		const std::vector<uint8_t> out = csi ? bi_serialise_csi(push.ix) : bi_serialise(push.ix);
+		if (!bi_write_file(out, index_path, csi, error)) return ARX_E_IO;
+		drv.us[BI_T_WRITE] = bs_now_us() - t_w;
+		drv.us[BI_T_TOTAL] = us_index + (bs_now_us() - t0);
+		bi_stats(stats, drv, push.ix, header + push.total, nb);
+		if (csi) bi_stats_csi(stats, push.ix.sc);
+		return ARX_OK;
+	}
+};
 
 // -> ARX_*; err: the text.  csi_shift: 0 for the .bai, else the min_shift of the .csi (bi_csi_shift's result)
 inline int bi_index_file(int device, const char *path, const char *bai_path, int64_t max_bytes, bool timed, int64_t *stats, std::string &err, int32_t csi_shift = 0)

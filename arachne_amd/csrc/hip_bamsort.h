@@ -180,24 +180,20 @@ struct BsFile { // the compressed file in host memory and the table of its block
 	}
 };
 
-// appends n bytes that are known to be whole records (sort) or a slab of a verified chain (copy) to a host writer
-inline bool bs_sink_raw(BamSink *w, const uint8_t *p, size_t n, int64_t n_records)
+// d_src[0, n) of the call's device -- whole records (sort) or a slab of a verified chain (copy) -- -> the writer, ARX_*.  An indexing writer is
+// shown the bytes where they lie first (BamSink::admit); then a device writer takes them there (write_dev: the body of
+// arx_bam_write_encoded_device behind its own admit), a host writer fetched
+template <class WriteDev> int bs_hand_over(BamSink *w, bool device_writer, int device, hipStream_t st, const uint8_t *d_src, int64_t n, int64_t n_records, WriteDev write_dev)
 {
-	w->pending.insert(w->pending.end(), p, p + n);
-	w->n_records += n_records;
-	return w->flush(false);
-}
-
-// d_src[0, n) of the call's device -> the writer: a device writer takes it where it lies (write_dev: arx_bam_write_encoded_device), a host writer fetched
-template <class WriteDev> bool bs_hand_over(BamSink *w, bool device_writer, hipStream_t st, const uint8_t *d_src, int64_t n, int64_t n_records, WriteDev write_dev)
-{
-	if (n <= 0) return true;
+	if (n <= 0) return ARX_OK;
 	ARX_HIP_CHECK(hipStreamSynchronize(st)); // the stream is complete
-	if (device_writer) return write_dev(d_src, n, n_records) == ARX_OK;
+	const int rc = w->admit(d_src, n, device);
+	if (rc != ARX_OK) return rc;
+	if (device_writer) return write_dev(d_src, n, n_records);
 	std::vector<uint8_t> h((size_t)n);
 	ARX_HIP_CHECK(hipMemcpyAsync(h.data(), d_src, (size_t)n, hipMemcpyDeviceToHost, st));
 	ARX_HIP_CHECK(hipStreamSynchronize(st));
-	return bs_sink_raw(w, h.data(), (size_t)n, n_records);
+	return w->put_raw(h.data(), (size_t)n, n_records) ? ARX_OK : ARX_E_IO;
 }
 
 // -> ARX_*; err: the text.  contigs: what the input's header must list
@@ -249,6 +245,9 @@ template <class WriteDev> int bs_sort_append(int device, BamSink *w, bool device
 	if (sort) {
 		size_t free_b = 0, total_b = 0;
 		ARX_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+		// An indexing writer (BamSink::tap) adds nothing to this: before the sorted stream is handed over, the inflated input and the sort's tables are
+		// released (below) -- more than the stream's size --, and the index then takes one piece of at most BS_SLAB_DEFAULT bytes of the stream with
+		// its carry, 56 bytes per record of the piece and about 100 per run; its window table (8 bytes per 2^min_shift bases) has been there since the open
 		const double need = 2.0 * (double)file.total + (double)file.raw.size() + 48.0 * ((double)file.total / 300.0) + 64e6;
 		if (need > (double)free_b) {
 			err = "sorting " + std::string(path) + " takes about " + std::to_string((int64_t)(need / 1048576.0)) + " MiB of device memory, " + std::to_string(free_b >> 20) + " MiB are free: use a smaller position bucket";
@@ -287,11 +286,11 @@ template <class WriteDev> int bs_sort_append(int device, BamSink *w, bool device
 		drv.us[BS_T_INFLATE] += bs_now_us() - t0;
 		return bad[0] == 0;
 	};
-	auto write = [&](const uint8_t *d, int64_t n, int64_t n_records) -> bool {
+	auto write = [&](const uint8_t *d, int64_t n, int64_t n_records) -> int {
 		const double t0 = bs_now_us();
-		const bool ok = bs_hand_over(w, device_writer, drv.st, d, n, n_records, write_dev);
+		const int rc = bs_hand_over(w, device_writer, device, drv.st, d, n, n_records, write_dev);
 		drv.us[BS_T_WRITE] += bs_now_us() - t0;
-		return ok;
+		return rc;
 	};
 	auto finish = [&](const BsFound &f) {
 		drv.us[BS_T_TOTAL] = bs_now_us() - t_begin;
@@ -303,7 +302,12 @@ template <class WriteDev> int bs_sort_append(int device, BamSink *w, bool device
 		if (!inflate_slab(0, a, b)) { err = std::string(path) + no_inflate; return ARX_E_IO; }
 		BsSorted s;
 		if (s.run(drv, d_out.as<uint8_t>(), file.total, hdr, BS_SEG_DEFAULT, n_ref, true) != BS_OK) { err = std::string(path) + no_chain; return ARX_E_IO; }
-		if (!write(s.out.as<uint8_t>(), file.total - hdr, s.found.n_records)) { err = w->error; return ARX_E_IO; }
+		if (w->tap) { // room for the index's piece: none of these is read again
+			ARX_HIP_CHECK(hipStreamSynchronize(drv.st));
+			d_out.release(); s.mem.release(); s.rec_off.release(); s.segs.release();
+		}
+		const int rc = write(s.out.as<uint8_t>(), file.total - hdr, s.found.n_records);
+		if (rc != ARX_OK) { err = w->error; return rc; }
 		finish(s.found);
 		return ARX_OK;
 	}
@@ -321,7 +325,10 @@ template <class WriteDev> int bs_sort_append(int device, BamSink *w, bool device
 				err = std::string(path) + no_chain; return ARX_E_IO;
 			}
 			const int64_t from = a < hdr ? (hdr < b ? hdr : b) : a; // the header's bytes are not records
-			if (pass == 1 && !write(d_out.as<uint8_t>() + keep + (from - a), b - from, carry.n_records - before)) { err = w->error; return ARX_E_IO; }
+			if (pass == 1) {
+				const int rc = write(d_out.as<uint8_t>() + keep + (from - a), b - from, carry.n_records - before);
+				if (rc != ARX_OK) { err = w->error; return rc; }
+			}
 		}
 	}
 	finish(BsFound{carry.n_records, carry.exit, carry.n_seg, carry.right, carry.repaired, carry.rounds});

@@ -17,6 +17,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <vector>
 #include "hip_res.h"
 #include "dev_bgzf.h"
 #include "hip_block.h"
@@ -118,8 +119,8 @@ struct DeviceBgzf : BlockCompressor {
 		ARX_HIP_CHECK(hipMemcpyAsync(h_meta[s].p, d_meta[s].p, (size_t)nb * 16, hipMemcpyDeviceToHost, st[s]));
 		ARX_HIP_CHECK(hipEventRecord(ev_meta[s], st[s]));
 	}
-	// the sizes of group g are known: its framed bytes on their way back -> their number
-	size_t fetch(size_t g, int nb)
+	// the sizes of group g are known: its framed bytes on their way back -> their number.  sizes: null, or where every block's framed size is appended
+	size_t fetch(size_t g, int nb, std::vector<int64_t> *sizes)
 	{
 		const int s = (int)(g & 1);
 		ARX_HIP_CHECK(hipEventSynchronize(ev_meta[s]));
@@ -128,6 +129,7 @@ struct DeviceBgzf : BlockCompressor {
 			const uint32_t *m = h_meta[s].as<uint32_t>() + 4 * (size_t)b;
 			if (m[0] > 5u + BGZF_IN || m[2] > 2u) throw std::runtime_error("the BGZF kernel reported an impossible block");
 			bytes += m[0] + 26; ++n_form[m[2]];
+			if (sizes) sizes->push_back((int64_t)m[0] + 26);
 		}
 		ARX_HIP_CHECK(hipMemcpyAsync(h_out[s].p, d_packed[s].p, bytes, hipMemcpyDeviceToHost, st[s]));
 		ARX_HIP_CHECK(hipEventRecord(ev_pay[s], st[s]));
@@ -135,7 +137,7 @@ struct DeviceBgzf : BlockCompressor {
 	}
 
 	// sink(bytes, n): n framed bytes, in order; stage: where a group's input comes from (submit)
-	template <class Stage, class Sink> void compress_from(size_t total, Stage stage, Sink sink)
+	template <class Stage, class Sink> void compress_from(size_t total, Stage stage, Sink sink, std::vector<int64_t> *sizes = nullptr)
 	{
 		if (!ready) throw std::runtime_error("the device compressor is not initialised");
 		if (!total) return;
@@ -143,7 +145,7 @@ struct DeviceBgzf : BlockCompressor {
 		const size_t per = (size_t)GROUP * BGZF_IN, ng = (total + per - 1) / per;
 		auto blocks_of = [&](size_t g) { const size_t bytes = total - g * per < per ? total - g * per : per; return (int)((bytes + BGZF_IN - 1) / BGZF_IN); };
 		auto drain = [&](size_t g) {
-			const size_t bytes = fetch(g, blocks_of(g));
+			const size_t bytes = fetch(g, blocks_of(g), sizes);
 			ARX_HIP_CHECK(hipEventSynchronize(ev_pay[g & 1]));
 			sink(h_out[g & 1].as<uint8_t>(), bytes);
 		};
@@ -157,15 +159,15 @@ struct DeviceBgzf : BlockCompressor {
 		}
 	}
 	// from host memory: through the page-locked staging of the group's stream
-	template <class Sink> void compress(const uint8_t *src, size_t total, Sink sink)
+	template <class Sink> void compress(const uint8_t *src, size_t total, Sink sink, std::vector<int64_t> *sizes = nullptr)
 	{
 		compress_from(total, [&](int s, size_t b0, size_t bytes) {
 			memcpy(h_in[s].p, src + b0, bytes);
 			ARX_HIP_CHECK(hipMemcpyAsync(d_in[s].p, h_in[s].p, bytes, hipMemcpyHostToDevice, st[s]));
-		}, sink);
+		}, sink, sizes);
 	}
 
-	bool run(const uint8_t *src, size_t total, FILE *f, int64_t &bytes_out, std::string &error) override
+	bool run(const uint8_t *src, size_t total, FILE *f, int64_t &bytes_out, std::string &error, std::vector<int64_t> *sizes) override
 	{
 		try {
 			std::lock_guard<std::mutex> lock(mu);
@@ -173,7 +175,7 @@ struct DeviceBgzf : BlockCompressor {
 			compress(src, total, [&](const uint8_t *p, size_t n) {
 				if (ok && fwrite(p, 1, n, f) != n) { ok = false; error = "write failed"; }
 				if (ok) bytes_out += (int64_t)n;
-			});
+			}, sizes);
 			return ok;
 		} catch (const std::exception &e) {
 			error = e.what();
@@ -183,9 +185,9 @@ struct DeviceBgzf : BlockCompressor {
 	// arx_bam_write_encoded_device: what is compressed is carry[0, n_carry) (host memory: the sink's pending bytes, fewer than a block) followed
 	// by d_stream[0, n_bytes) (device memory of this device, complete).  Every whole block of that concatenation goes through the same groups,
 	// kernels and framing as run(): the carry goes up to the front of group 0's input, the group's share of d_stream follows device to device.
-	// The tail short of a block is left in `tail` (the sink's next carry).  Returns when the blocks are written
+	// The tail short of a block is left in `tail` (the sink's next carry).  Returns when the blocks are written.  sizes: as run()'s
 	bool run_device(const uint8_t *carry, size_t n_carry, const uint8_t *d_stream, size_t n_bytes, FILE *f, int64_t &bytes_out, size_t &n_blocks, std::vector<uint8_t> &tail,
-	                std::string &error)
+	                std::string &error, std::vector<int64_t> *sizes = nullptr)
 	{
 		try {
 			if (n_carry >= (size_t)BGZF_IN) throw std::runtime_error("the device sink's carry is a whole block");
@@ -203,7 +205,7 @@ struct DeviceBgzf : BlockCompressor {
 			}, [&](const uint8_t *p, size_t n) {
 				if (ok && fwrite(p, 1, n, f) != n) { ok = false; error = "write failed"; }
 				if (ok) bytes_out += (int64_t)n;
-			});
+			}, sizes);
 			if (!ok) return false;
 			n_blocks = nb;
 			// the tail: what is left of the carry (only when no block was cut), then the end of the device stream, copied home

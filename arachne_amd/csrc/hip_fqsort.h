@@ -291,7 +291,7 @@ struct FsFileSink : FsSink {
 			if (bgzf) {
 				static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 				std::string err;
-				if (!carry[f].empty() && !z->run(carry[f].data(), carry[f].size(), file[f].f, file[f].bytes_out, err)) throw FsIoError(file[f].path + ": " + err);
+				if (!carry[f].empty() && !z->run(carry[f].data(), carry[f].size(), file[f].f, file[f].bytes_out, err, nullptr)) throw FsIoError(file[f].path + ": " + err);
 				carry[f].clear();
 				if (fwrite(eof, 1, 28, file[f].f) != 28) throw FsIoError(file[f].path + ": write failed");
 				file[f].bytes_out += 28;

@@ -214,7 +214,7 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
 
 
 def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "host", chunk: int = 40_000_000, read_groups: str = "", bam_threads: int = 8,
-             level: int = 1, max_bytes: int = 0, lib_path: str = api.LIB_PATH, index: "bool | str" = False):
+             level: int = 1, max_bytes: int = 0, lib_path: str = api.LIB_PATH, index: "bool | str" = False, index_pass: str = "separate"):
     """The step the position buckets exist for: out_dir is a reference-layout directory (run(layout="reference") with the same chunk); every
     bucket of api.bucket_table that was written is sorted by coordinate on ref's GPU (BamWriter.sort_append) and appended, in table order, to ONE
     writer with reference_header(read_groups) and SO:coordinate; the unmapped file, which is its own sorted form (refID = pos = -1 throughout),
@@ -222,16 +222,22 @@ def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "hos
     -> dict(records, buckets, bytes, seconds, sort: the per-file stats).  index=True: the closed file's .bai is written beside it
     (final_path + ".bai", api.bam_index on ref's device -- one more read of the file); the dict gains index (its stats) and index_seconds.
     index="bai" is the same, and like the other names adds index_format ("bai" or "csi": what was written); "csi" writes final_path + ".csi" (api.bam_index_csi), the index that holds contigs above 2^29
-    bases, which api.bam_index refuses; "auto" writes the .csi where a contig exceeds 2^29 and the .bai otherwise."""
+    bases, which api.bam_index refuses; "auto" writes the .csi where a contig exceeds 2^29 and the .bai otherwise.
+    index_pass="writer" (with an index): the writer itself indexes what it appends, on ref's GPU, and writes the index when it is closed
+    (api.BamWriter(index=...)) -- the same BAM and the same index bytes without the second read of the file; index, index_format and
+    index_seconds (the time the writer spent indexing) come from the close.  "separate", the default, is the pass described above."""
     if sink not in ("host", "device"):
         raise ValueError(f"unknown sink {sink!r}")
     if not (index is False or index is True or index in ("bai", "csi", "auto")):
         raise ValueError(f"unknown index {index!r}")
+    if index_pass not in ("separate", "writer"):
+        raise ValueError(f"unknown index_pass {index_pass!r}")
+    in_writer = bool(index) and index_pass == "writer"
     names, offs, clens, alt, l_pac = ref.contigs()
     table = api.bucket_table(names, clens, chunk, lib_path=lib_path)
     t = time.time()
     w = api.BamWriter(final_path, names, clens, extra_header=reference_header(read_groups), threads=bam_threads, level=level, lib_path=lib_path,
-                      device=ref if sink == "device" else None, coordinate=True)
+                      device=ref if sink == "device" else None, coordinate=True, **(dict(index="bai" if index is True else index, index_device=ref) if in_writer else {}))
     per = []
     try:
         for k, f in enumerate(table.files):
@@ -243,7 +249,11 @@ def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "hos
     finally:
         st = w.close()
     out = dict(records=st["records"], buckets=len(per), bytes=st["bytes_out"], seconds=time.time() - t, sort=per)
-    if index:
+    if in_writer:
+        out["index"], out["index_seconds"] = st["index"], st["index"]["total_us"] / 1e6
+        if index is not True:
+            out["index_format"] = st["index_format"]
+    elif index:
         fmt = "bai" if index is True else index
         if fmt == "auto":
             fmt = "csi" if any(int(l) > api.BAI_MAX_CONTIG for l in clens) else "bai"

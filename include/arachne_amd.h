@@ -442,6 +442,51 @@ int arx_selftest_bam_index_csi(int32_t device, const uint8_t *stream, int64_t n_
                   int64_t n_blocks, const int64_t *blk_at /* n_blocks + 1 file offsets */, const int32_t *blk_isize /* sum = n_bytes */,
                   int64_t seg_bytes, int64_t slab_bytes, int32_t min_shift, uint8_t *out, int64_t out_cap, int64_t *out_len, int64_t *stats);
 
+/* ---- the index written by the writer itself, while it appends: an opt-in coordinate writer that builds the .bai or the .csi of what it is
+ * given on ctx's GPU as the bytes pass through it, and writes the index when it is closed -- no second pass reads the file back.  The one rule:
+ * for every sequence of appends the writer accepts, the BAM is byte for byte the file the same appends give a writer without an index, and the
+ * index's bytes (the .csi's inflated ones) are exactly those arx_bam_index or arx_bam_index_csi (same min_shift) writes for that finished file:
+ * virtual offsets, interval, chunks and their join rule, pseudo-bin or meta-bin, linear table or loffset and trailer are stated there.
+ *   how       a writer's layout is known before any compressed size is: the header ends its own ceil(H / 65280) blocks, every block behind
+ *             holds 65280 bytes of the record stream but the last.  The kernels of arx_bam_index run on block ordinal << 16 | offset within in
+ *             place of V (the two order alike, and the join rule decides alike); the sink records the file offset of every block it writes (8
+ *             bytes a block), and the close turns the one into the other by a lookup.  What is appended from device memory
+ *             (arx_bam_sort_append in both modes, arx_bam_write_encoded_device) is indexed where it lies; what comes from the host
+ *             (arx_bam_write, arx_bam_write_select, arx_bam_write_encoded) is uploaded in pieces for it.  Device memory: the window table for
+ *             the writer's life, and per append one piece of at most 256 MiB of its bytes with 56 bytes per record and about 100 per run
+ *   open      arx_bam_open_ex's arguments; ctx is required.  flags: ARX_BAM_COORDINATE is implied; ARX_BAM_DEVICE_SINK compresses the blocks
+ *             on ctx's GPU (arx_bam_open_device; `level` is ignored), otherwise by zlib on the host.  index: ARX_BAM_INDEX_BAI, _CSI, or _AUTO
+ *             (the .csi where a contig is longer than 2^29, else the .bai); min_shift as arx_bam_index_csi's (read for a .csi only);
+ *             index_path NULL: path + ".bai" or ".csi".  ARX_E_ARG: a null ctx, unknown flag bits or index, a min_shift outside [10, 24] that is
+ *             not 0, or ARX_BAM_INDEX_BAI with a contig longer than 2^29 (msg names it); nothing is created then
+ *   appends   index first, then append.  An append that a record rule refuses -- the keys not non-decreasing, also across appends; a refID
+ *             outside [-1, n_ref); pos < 0 with a refID; an end beyond the contig -- appends nothing and returns ARX_E_ARG; the text
+ *             (arx_bam_error, or msg of arx_bam_sort_append) names the record, numbered from 0 over everything the writer has taken, and the rule.
+ *             (arx_bam_sort_append in copy mode hands a file over slab by slab: the slabs in front of the refused one are in the file.)  A
+ *             record whose name and CIGAR do not fit its block_size is ARX_E_IO.  The index is all or nothing: after a refused append the
+ *             writer goes on as a plain BAM writer.  arx_bam_sort_append with a ctx on another device than the writer's: ARX_E_ARG
+ *   close     arx_bam_close_indexed: stats as arx_bam_close's; index_stats[20] (may be NULL) as arx_bam_index's, the read and inflate times 0,
+ *             [15] serialise and write, [16] the time spent indexing, appends and close together ([12] .. [14] stay 0).
+ *             The index is written as <index>.tmp and renamed after the BAM has closed.  After a refused append: no index and no .tmp, and
+ *             ARX_E_ARG with a text that says that the BAM is complete and the index was not written.  ARX_E_IO: the BAM or the index cannot be
+ *             written, or the record stream ends inside a record.  arx_bam_close on such a writer does the same without the outputs; and
+ *             arx_bam_close_indexed on a plain writer is arx_bam_close. */
+enum { ARX_BAM_DEVICE_SINK = 2 };
+enum { ARX_BAM_INDEX_BAI = 1, ARX_BAM_INDEX_CSI = 2, ARX_BAM_INDEX_AUTO = 3 };
+int arx_bam_open_indexed(arx_ctx *ctx, const char *path, int32_t n_contigs, const char *const *names, const int32_t *lens, const char *extra_header, int32_t threads,
+                         int32_t level, int32_t flags, int32_t index, int32_t min_shift /* 0: 14 */, const char *index_path /* NULL: path + ".bai" / ".csi" */,
+                         arx_bam **out, char *msg, int32_t msg_cap);
+int arx_bam_close_indexed(arx_bam *w, int64_t *stats /* [4], may be NULL */, int64_t *index_stats /* [20], may be NULL */, char *msg, int32_t msg_cap);
+/* self-test of that indexing without files (tests/test_bam_index_feeds_gpu.py): arx_selftest_bam_index's stream, hdr, contigs and seg_bytes; the
+ * record stream behind hdr is fed in n_feeds feeds that end at the stream's offsets feed_end[] (ascending, anywhere -- an end inside the header
+ * feeds nothing --, the last n_bytes), every feed indexed in pieces of at most piece_bytes (0: whole); blk_at[n_blocks + 1] are the file offsets
+ * of the writer's layout (strictly ascending, the last the EOF block's; n_blocks must be ceil(hdr / 65280) + ceil((n_bytes - hdr) / 65280), else
+ * ARX_E_ARG); min_shift -1: the .bai, else the .csi's.  out, the codes and stats as the two self-tests above; a stream that ends inside a record
+ * is ARX_E_IO. */
+int arx_selftest_bam_index_feeds(int32_t device, const uint8_t *stream, int64_t n_bytes, int64_t hdr, int32_t n_ref, const int32_t *ref_len, int64_t n_blocks,
+                                 const int64_t *blk_at, int64_t seg_bytes, int64_t n_feeds, const int64_t *feed_end, int64_t piece_bytes, int32_t min_shift, uint8_t *out,
+                                 int64_t out_cap, int64_t *out_len, int64_t *stats);
+
 /* ---- in front of the feeder: a FASTQ file pair sorted by barcode on the GPU -- the reference's `arachne preprocess`
  * (src/preprocess/preprocess.go:42-114: samtools import -T '*' | samtools sort -t BX | samtools fastq -T '*'), which the aligner needs: the
  * feeder opens a new barcode set wherever the barcode changes, so a barcode that returns later in the file would be placed as several
