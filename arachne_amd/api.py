@@ -142,6 +142,8 @@ _SELFTEST_ARGS = {
     "arx_selftest_gen_cigar": [C.c_int32, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
     "arx_selftest_bgzf": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "arx_selftest_inflate": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
+    "arx_selftest_gunzip": [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "arx_fastq_gunzip_counters": [C.c_void_p, C.c_int32],
     "arx_selftest_rec_text": [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
     "arx_selftest_seed_bins": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64],
     "arx_selftest_block_shape": [C.c_int32, C.c_void_p, C.c_void_p],
@@ -316,9 +318,20 @@ def selftest_bam_sort(stream, n_ref: int, seg_bytes: int = 1 << 18, mode: str = 
     return dict(rc=rc, out=out[:n].tobytes(), guard=out[n:].tobytes(), rec_off=rec_off, n_records=int(n_rec.value), stats=_sort_stats(st))
 
 
-FQSORT_BGZF, FQSORT_CHECK, FQSORT_TIMED = 1, 2, 0x100
+FQSORT_BGZF, FQSORT_CHECK, FQSORT_GUNZIP_DEVICE, FQSORT_TIMED = 1, 2, 8, 0x100
 _FQSORT_STATS = ("records", "bytes_in_r1", "bytes_in_r2", "bytes_out_r1", "bytes_out_r2", "skipped_lines", "runs", "distinct", "longest_barcode", "sort_passes", "windows",
                  "slabs", "read_us", "inflate_us", "parse_us", "keys_us", "sort_us", "gather_us", "compress_us", "write_us")
+
+
+def _gunzip_flag(lib, gunzip, call):
+    """gunzip="host" | "device" of the file-pair calls -> the flag bit (ARX_FQSORT_GUNZIP_DEVICE and ARX_FQSTD_GUNZIP_DEVICE are the same bit)"""
+    if gunzip not in ("host", "device"):
+        raise ValueError('gunzip is "host" or "device"')
+    if gunzip == "host":
+        return 0
+    if not hasattr(lib, "arx_selftest_gunzip"):
+        raise ArachneError(call + ': gunzip="device": this library has no chunked gzip inflate (rebuild it)')
+    return FQSORT_GUNZIP_DEVICE
 
 
 def _fqsort_stats(st):
@@ -326,14 +339,15 @@ def _fqsort_stats(st):
 
 
 def fastq_sort(r1: str, r2: str, r1_out: "str | None" = None, r2_out: "str | None" = None, bgzf: bool = False, check: bool = False, timed: bool = False,
-               max_bytes: int = 0, device: int = 0, lib_path: str = LIB_PATH):
+               max_bytes: int = 0, device: int = 0, lib_path: str = LIB_PATH, gunzip: str = "host"):
     """A FASTQ file pair sorted by barcode on the GPU (include/arachne_amd.h: arx_fastq_sort, the reference's `preprocess`): the records the
     feeder recognises, verbatim, ordered by the barcode's bytes, equal barcodes in input order.  Inputs plain, gzip or BGZF; outputs plain, or
     BGZF with bgzf=True.  check=True writes nothing and only counts: stats["runs"] == stats["distinct"] says the input is sorted already.
+    gunzip="device" (ARX_FQSORT_GUNZIP_DEVICE): an ordinary gzip input is inflated on the GPU in chunks, not by zlib on a reader thread.
     -> the stats as a dict; ArachneError with .code on failure (nothing is left behind then)."""
     lib = _load(lib_path)
     st, msg = np.zeros(20, dtype=np.int64), C.create_string_buffer(1024)
-    flags = (FQSORT_BGZF if bgzf else 0) | (FQSORT_CHECK if check else 0) | (FQSORT_TIMED if timed else 0)
+    flags = (FQSORT_BGZF if bgzf else 0) | (FQSORT_CHECK if check else 0) | (FQSORT_TIMED if timed else 0) | _gunzip_flag(lib, gunzip, "fastq_sort")
     enc = lambda p: None if p is None else os.fsencode(p)
     rc = _selftest_fn(lib, "arx_fastq_sort")(device, enc(r1), enc(r2), enc(r1_out), enc(r2_out), flags, int(max_bytes), st.ctypes.data, msg, 1024)
     if rc != 0:
@@ -365,7 +379,7 @@ def selftest_fastq_sort(t1, t2, window_bytes: int = 0, slab_bytes: int = 0, devi
                 guard2=out2[n2:].tobytes(), rec_off1=off1, rec_off2=off2, n_records=int(n_rec.value), stats=_fqsort_stats(st))
 
 
-FQSTD_BGZF, FQSTD_DETECT, FQSTD_TIMED = 1, 2, 0x100
+FQSTD_BGZF, FQSTD_DETECT, FQSTD_GUNZIP_DEVICE, FQSTD_TIMED = 1, 2, 8, 0x100
 FQSTD_FORMATS = ("auto", "haplotagging", "stlfr", "tellseq", "standard", "unknown")      # ARX_FQSTD_*: the last two are results only
 _FQSTD_STATS = ("records", "bytes_in_r1", "bytes_in_r2", "bytes_out_r1", "bytes_out_r2", "skipped_lines", "format", "decided_by", "with_barcode", "valid", "longest_barcode",
                 "windows", "slabs", "read_us", "inflate_us", "parse_us", "fields_us", "compose_us", "compress_us", "write_us")
@@ -386,16 +400,17 @@ def _fqstd_format(format):
 
 
 def fastq_standardize(r1: str, r2: str, r1_out: "str | None" = None, r2_out: "str | None" = None, format="auto", bgzf: bool = False, detect: bool = False,
-                      timed: bool = False, device: int = 0, lib_path: str = LIB_PATH):
+                      timed: bool = False, device: int = 0, lib_path: str = LIB_PATH, gunzip: str = "host"):
     """The headers of a haplotagging, stLFR or TELLseq FASTQ pair rewritten on the GPU to `@<id>/1\tBX:Z:<barcode>\tVX:i:<0|1>`, the form the
     feeder and fastq_sort read (include/arachne_amd.h: arx_fastq_standardize has the contract).  format: "auto" detects from the first 200
     records, "haplotagging", "stlfr" or "tellseq" force one (a number is passed on as it is).  Inputs plain, gzip or BGZF; outputs plain, or
-    BGZF with bgzf=True.  detect=True only detects: nothing is written, the outputs may be None.  -> the stats as a dict, "format" as a name:
+    BGZF with bgzf=True.  detect=True only detects: nothing is written, the outputs may be None.  gunzip="device"
+    (ARX_FQSTD_GUNZIP_DEVICE): an ordinary gzip input is inflated on the GPU in chunks.  -> the stats as a dict, "format" as a name:
     "standard" under "auto" says that nothing was written and the inputs serve as they are.  ArachneError with .code on failure -- an
     unknown format under "auto" among them -- and nothing is left behind then."""
     lib = _load(lib_path)
     st, msg = np.zeros(20, dtype=np.int64), C.create_string_buffer(1024)
-    flags = (FQSTD_BGZF if bgzf else 0) | (FQSTD_DETECT if detect else 0) | (FQSTD_TIMED if timed else 0)
+    flags = (FQSTD_BGZF if bgzf else 0) | (FQSTD_DETECT if detect else 0) | (FQSTD_TIMED if timed else 0) | _gunzip_flag(lib, gunzip, "fastq_standardize")
     enc = lambda p: None if p is None else os.fsencode(p)
     rc = _selftest_fn(lib, "arx_fastq_standardize")(device, enc(r1), enc(r2), enc(r1_out), enc(r2_out), _fqstd_format(format), flags, st.ctypes.data, msg, 1024)
     if rc != 0:
@@ -438,14 +453,14 @@ _FQSORT_EX_STATS = _FQSORT_STATS + ("sorted_runs", "tmp_bytes", "run_write_us", 
 
 
 def fastq_sort_ex(r1: str, r2: str, r1_out: "str | None" = None, r2_out: "str | None" = None, bgzf: bool = False, check: bool = False, timed: bool = False,
-                  max_bytes: int = 0, run_bytes: int = 0, tmp_dir: "str | None" = None, device: int = 0, lib_path: str = LIB_PATH):
+                  max_bytes: int = 0, run_bytes: int = 0, tmp_dir: "str | None" = None, device: int = 0, lib_path: str = LIB_PATH, gunzip: str = "host"):
     """fastq_sort for a file pair that device memory does not hold (include/arachne_amd.h: arx_fastq_sort_ex): sorted runs of run_bytes of
     inflated text per file go to temporary files under tmp_dir (None: r1_out's directory) and are merged on the GPU; the same output
-    bytes.  run_bytes 0: fastq_sort itself; -1: chosen from the free device memory.  -> the stats as a dict, with "sorted_runs",
+    bytes.  run_bytes 0: fastq_sort itself; -1: chosen from the free device memory.  gunzip as in fastq_sort.  -> the stats as a dict, with "sorted_runs",
     "tmp_bytes", "run_write_us", "run_read_us"; ArachneError with .code on failure (nothing is left behind then)."""
     lib = _load(lib_path)
     st, msg = np.zeros(24, dtype=np.int64), C.create_string_buffer(1024)
-    flags = (FQSORT_BGZF if bgzf else 0) | (FQSORT_CHECK if check else 0) | (FQSORT_TIMED if timed else 0)
+    flags = (FQSORT_BGZF if bgzf else 0) | (FQSORT_CHECK if check else 0) | (FQSORT_TIMED if timed else 0) | _gunzip_flag(lib, gunzip, "fastq_sort_ex")
     enc = lambda p: None if p is None else os.fsencode(p)
     rc = _selftest_fn(lib, "arx_fastq_sort_ex")(device, enc(r1), enc(r2), enc(r1_out), enc(r2_out), flags, int(max_bytes), int(run_bytes), enc(tmp_dir), st.ctypes.data, msg, 1024)
     if rc != 0:
@@ -487,16 +502,16 @@ def _fqprep_stats(st):
 
 
 def fastq_prepare(r1: str, r2: str, r1_out: "str | None" = None, r2_out: "str | None" = None, format="auto", bgzf: bool = False, check: bool = False, timed: bool = False,
-                  max_bytes: int = 0, run_bytes: int = 0, tmp_dir: "str | None" = None, device: int = 0, lib_path: str = LIB_PATH):
+                  max_bytes: int = 0, run_bytes: int = 0, tmp_dir: "str | None" = None, device: int = 0, lib_path: str = LIB_PATH, gunzip: str = "host"):
     """fastq_standardize and fastq_sort_ex in one call on the GPU, without the files between them (include/arachne_amd.h: arx_fastq_prepare): a
     haplotagging, stLFR or TELLseq pair comes out with the headers `@<id>/1\tBX:Z:<barcode>\tVX:i:<0|1>`, ordered by barcode -- the very bytes
     the two calls write one after the other.  format as in fastq_standardize; "auto" that finds the standard form sorts the inputs as they
     are.  bgzf, check, timed, max_bytes, run_bytes and tmp_dir as in fastq_sort_ex (run_bytes counts raw text; the temporary files hold
-    standardized text).  -> the stats of fastq_sort_ex as a dict, with "format" (a name), "decided_by", "with_barcode", "valid";
+    standardized text).  gunzip as in fastq_sort.  -> the stats of fastq_sort_ex as a dict, with "format" (a name), "decided_by", "with_barcode", "valid";
     ArachneError with .code on failure -- an unknown format under "auto" among them -- and nothing is left behind then."""
     lib = _load(lib_path)
     st, msg = np.zeros(28, dtype=np.int64), C.create_string_buffer(1024)
-    flags = (FQSORT_BGZF if bgzf else 0) | (FQSORT_CHECK if check else 0) | (FQSORT_TIMED if timed else 0)
+    flags = (FQSORT_BGZF if bgzf else 0) | (FQSORT_CHECK if check else 0) | (FQSORT_TIMED if timed else 0) | _gunzip_flag(lib, gunzip, "fastq_prepare")
     enc = lambda p: None if p is None else os.fsencode(p)
     rc = _selftest_fn(lib, "arx_fastq_prepare")(device, enc(r1), enc(r2), enc(r1_out), enc(r2_out), _fqstd_format(format), flags, int(max_bytes), int(run_bytes), enc(tmp_dir),
                                                 st.ctypes.data, msg, 1024)
@@ -685,6 +700,46 @@ def selftest_inflate(chain, device: int = 0, fill: int = 0, lib_path: str = LIB_
         raise ArachneError("arx_selftest_inflate: code %d" % rc)
     return dict(rc=rc, out=out[:int(st[2])].tobytes(), out_len=int(out_len.value), status=[int(x) for x in status[:int(st[0])]], blocks=int(st[0]),
                 compressed_bytes=int(st[1]), inflated_bytes=int(st[2]), deflate_blocks=int(st[3]))
+
+
+GUNZIP_FALLBACK = ("NONE", "REFUTED", "OVERFLOW", "STATUS", "CHECK", "NO_BLOCK", "CUT_SHORT")
+GUNZIP_STATS = ("members", "compressed_bytes", "inflated_bytes", "launches", "chunks", "candidates", "accepted", "refuted", "deflate_blocks", "markers", "host_bytes",
+                "fallback", "ignored_bytes", "us_find", "us_decode", "us_resolve")
+
+
+def selftest_gunzip(data, chunk_bytes: int = 0, slab_bytes: int = 0, expand: int = 0, cap: int = None, device: int = 0, lib_path: str = LIB_PATH):
+    """The chunked inflate of a plain gzip file on bytes in memory (include/arachne_amd.h: arx_selftest_gunzip) -> dict(rc: the entry's return
+    value (0, ARX_E_IO = -5 where zlib's gzread reports an error, ARX_E_ARG = -2 for sizes outside their bounds or a `cap` that is too
+    small), out: the inflated bytes, and the entry's stats under the names of GUNZIP_STATS; fallback is an index into GUNZIP_FALLBACK).
+    cap: bytes of room for the output; None: 64 per compressed byte and 4 MiB at least (text that compresses better needs its size passed).  Raises where the library lacks the entry."""
+    lib = _load(lib_path)
+    if not hasattr(lib, "arx_selftest_gunzip"):
+        raise ArachneError("this libarachne_amd.so has no arx_selftest_gunzip: rebuild it")
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = len(src)
+    room = max(64 * n, 1 << 22) if cap is None else int(cap)
+    out = np.full(room + 8, 0xA5, dtype=np.uint8)
+    out_len, st = C.c_int64(-1), np.zeros(16, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_gunzip")(device, src.ctypes.data if n else None, n, int(chunk_bytes), int(slab_bytes), int(expand), out.ctypes.data, room,
+                                                  C.byref(out_len), st.ctypes.data)
+    if rc not in (0, -2, -4, -5):
+        raise ArachneError("arx_selftest_gunzip: code %d" % rc)
+    assert out[room:].tobytes() == b"\xa5" * 8
+    res = dict(rc=rc, out=out[:max(int(out_len.value), 0)].tobytes() if rc == 0 else b"")
+    res.update({k: int(v) for k, v in zip(GUNZIP_STATS, st)})
+    return res
+
+
+def fastq_gunzip_counters(reset: bool = False, lib_path: str = LIB_PATH):
+    """What the gzip inputs of the file-pair calls with gunzip="device" did since the process started or since the last reset
+    (include/arachne_amd.h: arx_fastq_gunzip_counters) -> dict(files, launches, accepted, bytes, host_bytes, fallbacks: {reason name: files})."""
+    lib = _load(lib_path)
+    c = np.zeros(12, dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_fastq_gunzip_counters")(c.ctypes.data, 1 if reset else 0)
+    if rc != 0:
+        raise ArachneError("arx_fastq_gunzip_counters: code %d" % rc)
+    return dict(files=int(c[0]), launches=int(c[1]), accepted=int(c[2]), bytes=int(c[3]), host_bytes=int(c[4]),
+                fallbacks={GUNZIP_FALLBACK[k]: int(c[5 + k]) for k in range(1, 7) if c[5 + k]})
 
 
 def index_build(fasta: str, prefix: str, lib_path: str = LIB_PATH) -> None:

@@ -11,6 +11,7 @@
 #include "../../include/arachne_amd.h"
 #include "hip_bgzf.h"
 #include "hip_inflate.h"
+#include "hip_gunzip.h"
 #include "hip_bamsort.h"
 #include "hip_fqsort.h"
 #include "hip_fqstd.h"
@@ -181,6 +182,63 @@ extern "C" int arx_selftest_inflate(int32_t device, const uint8_t *src, int64_t 
 		rc = ARX_E_DEVICE;
 	}
 	return rc;
+}
+
+// ---- the chunked inflate of a plain gzip file (dev_gunzip.h, hip_gunzip.h, gunzip_host.h)
+extern "C" int arx_selftest_gunzip(int32_t device, const uint8_t *src, int64_t n, int64_t chunk_bytes, int64_t slab_bytes, int32_t expand, uint8_t *out, int64_t cap,
+                                   int64_t *out_len, int64_t *stats)
+{
+	static_assert(ARX_GUNZIP_N_STATS == arx::GZ_N_STATS && ARX_GUNZIP_FB_CUT_SHORT == arx::GZ_FB_CUT_SHORT, "the public statistics are gunzip_host.h's");
+	const int64_t chunk = chunk_bytes ? chunk_bytes : arx::GZ_CHUNK_DEFAULT, slab = slab_bytes ? slab_bytes : arx::GZ_SLAB_DEFAULT < 2 * chunk ? 2 * chunk : arx::GZ_SLAB_DEFAULT > arx::GZ_MAX_CHUNKS * chunk ? arx::GZ_MAX_CHUNKS * chunk : arx::GZ_SLAB_DEFAULT;
+	const int32_t ex = expand ? expand : arx::GZ_EXPAND_DEFAULT;
+	if (n < 0 || cap < 0 || !out_len || (n > 0 && !src) || (cap > 0 && !out) || chunk_bytes < 0 || slab_bytes < 0 || chunk < arx::GZ_MIN_CHUNK || chunk > arx::GZ_MAX_SLAB / 2 ||
+	    slab < 2 * chunk || slab > arx::GZ_MAX_SLAB || slab > arx::GZ_MAX_CHUNKS * chunk || ex < 1 || ex > arx::GZ_MAX_EXPAND || slab * ex > arx::GZ_MAX_SYMBOLS)
+		return ARX_E_ARG;
+	*out_len = 0;
+	if (stats) for (int k = 0; k < arx::GZ_N_STATS; ++k) stats[k] = 0;
+	try {
+		arx::select_device(device, "no such HIP device");
+		arx::Stream st; // declared before the buffers, so that it has ended when they are freed
+		st.create();
+		arx::GzHip dev;
+		dev.init(st);
+		arx::GzMemSource in(src, n);
+		arx::GzReader<arx::GzHip> r(dev, in, chunk, slab, ex);
+		r.can_rewind = true;
+		arx::DevBuf d_text; // a piece at its place in device memory, then home
+		std::vector<uint8_t> text;
+		for (;;) {
+			const int64_t k = r.next();
+			if (k == arx::GZ_END) break;
+			if (k == arx::GZ_ERROR) return ARX_E_IO;
+			if (k == arx::GZ_REWIND) { text.resize((size_t)r.rewind_to); continue; }
+			if (!d_text.p || d_text.bytes < (size_t)k) d_text.alloc((size_t)k);
+			r.place(d_text.as<uint8_t>());
+			const size_t at = text.size();
+			text.resize(at + (size_t)k);
+			ARX_HIP_CHECK(hipMemcpyAsync(text.data() + at, d_text.p, (size_t)k, hipMemcpyDeviceToHost, st));
+			ARX_HIP_CHECK(hipStreamSynchronize(st));
+		}
+		if ((int64_t)text.size() > cap) return ARX_E_ARG;
+		if (!text.empty()) memcpy(out, text.data(), text.size());
+		*out_len = (int64_t)text.size();
+		if (stats) for (int k = 0; k < arx::GZ_N_STATS; ++k) stats[k] = r.stats[k];
+	} catch (const arx::HipOutOfMemory &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const std::bad_alloc &) {
+		return ARX_E_TOO_LARGE;
+	} catch (const std::exception &) {
+		return ARX_E_DEVICE;
+	}
+	return ARX_OK;
+}
+
+extern "C" int arx_fastq_gunzip_counters(int64_t *counters, int32_t reset)
+{
+	static_assert(ARX_GUNZIP_N_COUNTERS == arx::GZC_N, "the public counters are hip_fqsort.h's");
+	if (!counters) return ARX_E_ARG;
+	for (int k = 0; k < arx::GZC_N; ++k) counters[k] = reset ? arx::gz_counters()[k].exchange(0) : arx::gz_counters()[k].load();
+	return ARX_OK;
 }
 
 // ---- the coordinate sort of a BAM file into an open writer (dev_bamsort.h, hip_bamsort.h)
@@ -419,7 +477,7 @@ extern "C" int arx_fastq_sort(int32_t device, const char *r1_in, const char *r2_
 	if (stats) for (int k = 0; k < arx::FS_N_STATS; ++k) stats[k] = 0;
 	return fq_file_call(msg, msg_cap, "the device memory does not hold the sort of these files", arx::FS_REMEDY, [&]() {
 		const char *call = "arx_fastq_sort", *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
-		if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) fq_bad(call, "unknown flag bits");
+		if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_GUNZIP_DEVICE | ARX_FQSORT_TIMED)) fq_bad(call, "unknown flag bits");
 		fq_check_paths(call, in, out, !(flags & ARX_FQSORT_CHECK), max_bytes >= 0);
 		arx::fs_sort_files(device, in, out, flags, max_bytes, stats, arx::shared_device_bgzf);
 	});
@@ -463,7 +521,7 @@ extern "C" int arx_fastq_sort_ex(int32_t device, const char *r1_in, const char *
 	return fq_file_call(msg, msg_cap, "the device memory does not hold a run of these files or the table of their records",
 	                    ": use a smaller run_bytes; where the table of all records is what does not fit, sort per lane", [&]() {
 		const char *call = "arx_fastq_sort_ex", *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
-		if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) fq_bad(call, "unknown flag bits");
+		if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_GUNZIP_DEVICE | ARX_FQSORT_TIMED)) fq_bad(call, "unknown flag bits");
 		fq_check_paths(call, in, out, !(flags & ARX_FQSORT_CHECK), max_bytes >= 0);
 		fq_check_run_bytes(call, run_bytes);
 		arx::fx_sort_files(device, in, out, flags, max_bytes, run_bytes, tmp_dir, stats, arx::shared_device_bgzf);
@@ -507,7 +565,7 @@ extern "C" int arx_fastq_standardize(int32_t device, const char *r1_in, const ch
 	if (stats) for (int k = 0; k < arx::FQS_N_STATS; ++k) stats[k] = 0;
 	return fq_file_call(msg, msg_cap, "the device memory does not hold the windows and slabs of the call", "", [&]() {
 		const char *call = "arx_fastq_standardize", *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
-		if (flags & ~(ARX_FQSTD_BGZF | ARX_FQSTD_DETECT | ARX_FQSTD_TIMED)) fq_bad(call, "unknown flag bits");
+		if (flags & ~(ARX_FQSTD_BGZF | ARX_FQSTD_DETECT | ARX_FQSTD_GUNZIP_DEVICE | ARX_FQSTD_TIMED)) fq_bad(call, "unknown flag bits");
 		fq_check_format(call, format);
 		fq_check_paths(call, in, out, !(flags & ARX_FQSTD_DETECT));
 		arx::fqs_files(device, in, out, format, flags, stats, arx::shared_device_bgzf);
@@ -563,7 +621,7 @@ extern "C" int arx_fastq_prepare(int32_t device, const char *r1_in, const char *
 	return fq_file_call(msg, msg_cap, "the device memory does not hold these files, a run of them or the table of their records",
 	                    ": prepare in runs (run_bytes -1), or with a smaller run_bytes; where the table of all records is what does not fit, prepare per lane", [&]() {
 		const char *call = "arx_fastq_prepare", *in[2] = {r1_in, r2_in}, *out[2] = {r1_out, r2_out};
-		if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_TIMED)) fq_bad(call, "unknown flag bits");
+		if (flags & ~(ARX_FQSORT_BGZF | ARX_FQSORT_CHECK | ARX_FQSORT_GUNZIP_DEVICE | ARX_FQSORT_TIMED)) fq_bad(call, "unknown flag bits");
 		fq_check_format(call, format);
 		fq_check_paths(call, in, out, !(flags & ARX_FQSORT_CHECK), max_bytes >= 0);
 		fq_check_run_bytes(call, run_bytes);

@@ -59,7 +59,7 @@ constexpr int INF_LL = 288, INF_D = 32; // alphabet sizes as the fixed code has 
 enum { INF_OK = 0, INF_BAD_HEADER, INF_BAD_BTYPE, INF_BAD_STORED_LEN, INF_BAD_CODE_LENGTHS, INF_BAD_SYMBOL, INF_BAD_DISTANCE, INF_TRUNCATED, INF_SIZE_MISMATCH,
        INF_CRC_MISMATCH, INF_N_STATUS };
 // shared scalars of a stream
-enum { IS_BITPOS = 0, IS_OUTPOS, IS_STATUS, IS_FINAL, IS_BTYPE, IS_NDEFL, IS_HI, IS_ST_SRC, IS_ST_DST, IS_ST_LEN, IS_NLIT, IS_NM, IS_EOB, IS_NSYM_LL, IS_NSYM_D, IS_N_SCALARS };
+enum { IS_BITPOS = 0, IS_OUTPOS, IS_STATUS, IS_FINAL, IS_BTYPE, IS_NDEFL, IS_HI, IS_ST_SRC, IS_ST_DST, IS_ST_LEN, IS_NLIT, IS_NM, IS_EOB, IS_NSYM_LL, IS_NSYM_D, IS_BASE, IS_N_SCALARS };
 static_assert((INF_RING & (INF_RING - 1)) == 0 && INF_RING >= 2 * INF_TOK * 6 + INF_PAD + 600, "the ring holds a batch, and a dynamic header (at most 563 bytes)");
 
 struct InfWork {
@@ -285,8 +285,10 @@ ARX_DEV void inf_stored(InfWork &w, const uint8_t *src, int lane)
 	for (int i = lane; i < n; i += INF_LANES) w.out[d + i] = src[s + i];
 }
 
-// one lane: the next batch of tokens
-ARX_DEV void inf_decode(InfWork &w, int clen, int isize)
+// one lane: the next batch of tokens.  WINDOWED (dev_gunzip.h): the stream goes on from a place whose 32 KiB of history lie outside `out`, so a
+// distance may reach up to 32768 bytes before the first one; the offsets of the batch's tokens count from the output position the batch began
+// at (IS_BASE), and the batch ends before its output could span more than `span` bytes.  Otherwise (a BGZF block) they count from 0
+template <bool WINDOWED> ARX_DEV void inf_decode_t(InfWork &w, int clen, int isize, int span)
 {
 	int32_t *sh = w.sh;
 	const int hi = inf_ring_hi(sh[IS_BITPOS], clen);
@@ -295,7 +297,10 @@ ARX_DEV void inf_decode(InfWork &w, int clen, int isize)
 	InfBits b;
 	b.begin(w.ring, sh[IS_BITPOS]);
 	int o = sh[IS_OUTPOS], nl = 0, nm = 0, eob = 0, st = INF_OK;
+	const int base = WINDOWED ? o : 0;
+	sh[IS_BASE] = base;
 	while (nl < INF_TOK && nm < INF_TOK) { // every round takes at least one bit or ends the loop
+		if (WINDOWED && o - base + 258 > span) break; // (a token is at most 258 bytes)
 		const int pos = b.pos();
 		if (pos > 8 * clen) { st = INF_TRUNCATED; break; }
 		if (more && (pos >> 3) + INF_PAD > hi) break; // the ring is refilled first
@@ -306,7 +311,7 @@ ARX_DEV void inf_decode(InfWork &w, int clen, int isize)
 		if (s < 0 || s >= 286) { st = INF_BAD_SYMBOL; break; }
 		if (s < 256) {
 			if (o >= isize) { st = INF_SIZE_MISMATCH; break; }
-			w.lit_off[nl] = (uint16_t)o; w.lit_val[nl] = (uint8_t)s; ++nl; ++o;
+			w.lit_off[nl] = (uint16_t)(o - base); w.lit_val[nl] = (uint8_t)s; ++nl; ++o;
 			continue;
 		}
 		if (s == 256) { eob = 1; break; }
@@ -325,9 +330,9 @@ ARX_DEV void inf_decode(InfWork &w, int clen, int isize)
 		if (ds < 4) dist = ds + 1;
 		else { const int e = (ds >> 1) - 1; dist = 1 + ((2 + (ds & 1)) << e) + (int)b.get(e); }
 		if (b.pos() > 8 * clen) { st = INF_TRUNCATED; break; }
-		if (dist > o) { st = INF_BAD_DISTANCE; break; }
+		if (!WINDOWED && dist > o) { st = INF_BAD_DISTANCE; break; }
 		if (o + len > isize) { st = INF_SIZE_MISMATCH; break; }
-		w.m_off[nm] = (uint16_t)o; w.m_len[nm] = (uint16_t)len; w.m_dist[nm] = (uint16_t)(dist - 1); ++nm;
+		w.m_off[nm] = (uint16_t)(o - base); w.m_len[nm] = (uint16_t)len; w.m_dist[nm] = (uint16_t)(dist - 1); ++nm;
 		o += len;
 	}
 	if (st == INF_OK && b.pos() > 8 * clen) st = INF_TRUNCATED;
@@ -335,6 +340,7 @@ ARX_DEV void inf_decode(InfWork &w, int clen, int isize)
 	sh[IS_NLIT] = st == INF_OK ? nl : 0; sh[IS_NM] = st == INF_OK ? nm : 0; sh[IS_EOB] = eob;
 	sh[IS_OUTPOS] = o; sh[IS_BITPOS] = b.pos();
 }
+ARX_DEV void inf_decode(InfWork &w, int clen, int isize) { inf_decode_t<false>(w, clen, isize, 0); }
 ARX_DEV void inf_literals(InfWork &w, int lane)
 {
 	const int n = w.sh[IS_NLIT];
@@ -347,17 +353,20 @@ ARX_DEV void inf_match(InfWork &w, int k, int lane) // k < IS_NM <= INF_TOK; dis
 	for (int i = lane; i < len; i += INF_LANES) w.out[o + i] = from[dist >= len ? i : i % dist];
 }
 
+// what the bytes byte(s) .. byte(e - 1) of an n-byte message add to its CRC-32: their own CRC shifted by x^(8 * bytes behind them) mod P.  The
+// xor of these over ranges that tile [0, n) is the message's CRC
+template <class Byte> ARX_DEVI uint32_t inf_crc_range(const uint32_t *crc_tab, const uint32_t *x2n, Byte byte, int64_t s, int64_t e, int64_t n)
+{
+	if (s >= e) return 0;
+	uint32_t c = 0xFFFFFFFFu;
+	for (int64_t p = s; p < e; ++p) c = crc_tab[(c ^ byte(p)) & 0xFF] ^ (c >> 8);
+	c ^= 0xFFFFFFFFu;
+	return e < n ? bgzf_gf_mul(bgzf_x8n(x2n, (uint32_t)(n - e)), c) : c;
+}
 ARX_DEV void inf_crc(InfWork &w, int n, int lane)
 {
 	const int per = (n + INF_LANES - 1) / INF_LANES, s = lane * per < n ? lane * per : n, e = s + per < n ? s + per : n;
-	uint32_t part = 0;
-	if (s < e) {
-		uint32_t c = 0xFFFFFFFFu;
-		for (int p = s; p < e; ++p) c = w.crc_tab[(c ^ w.out[p]) & 0xFF] ^ (c >> 8);
-		c ^= 0xFFFFFFFFu;
-		part = e < n ? bgzf_gf_mul(bgzf_x8n(w.x2n, (uint32_t)(n - e)), c) : c;
-	}
-	w.crc_part[lane] = part;
+	w.crc_part[lane] = inf_crc_range(w.crc_tab, w.x2n, [&](int64_t p) { return w.out[p]; }, s, e, n);
 }
 // one lane: the block's status
 ARX_DEV void inf_finish(InfWork &w, int isize, uint32_t want_crc)

@@ -244,6 +244,46 @@ inline bool file_is_bgzf(const char *path)
 	return r == 1;
 }
 
+// true where the file starts with a gzip member that is no BGZF block: the magic 1f 8b and CM 8.  Such a file may be inflated on the device in
+// chunks (dev_gunzip.h); whether it is sound is not judged here
+inline bool file_is_gzip(const char *path)
+{
+	FILE *f = fopen(path, "rb");
+	if (!f) return false;
+	uint8_t h[3];
+	const size_t n = fread(h, 1, 3, f);
+	fclose(f);
+	return n == 3 && h[0] == 0x1F && h[1] == 0x8B && h[2] == 8 && !file_is_bgzf(path);
+}
+
+// reads a file as it is: a slab holds the next slab_bytes of it, still compressed; how many bytes of text they are nobody knows yet (text = 0).
+// For a gzip file that the device inflates in chunks (hip_fqsort.h: FsGunzip)
+class GzipRawReader : public SlabReader {
+public:
+	bool open(const char *path, size_t chunk_bytes, size_t)
+	{
+		f_ = fopen(path, "rb");
+		if (!f_) return false;
+		setvbuf(f_, nullptr, _IOFBF, 1 << 20);
+		return alloc_slabs(chunk_bytes);
+	}
+	~GzipRawReader() override
+	{
+		stop();
+		if (f_) fclose(f_);
+		free_slabs();
+	}
+protected:
+	void fill(int, Slab &s) override
+	{
+		s.len = fread(s.buf, 1, slab_cap(), f_);
+		if (ferror(f_)) s.err = true;
+		else if (s.len < slab_cap()) s.eof = true;
+	}
+private:
+	FILE *f_ = nullptr;
+};
+
 class BgzfChunkReader : public SlabReader {
 public:
 	// A chunk is the longest run of whole blocks that inflate to at most chunk_bytes, and always at least one block; a slab holds

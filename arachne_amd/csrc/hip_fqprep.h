@@ -45,7 +45,7 @@ inline void fp_stats(int64_t *stats, int format, int64_t decided, const FpRows &
 inline void fp_files(int device, const char *const in_path[2], const char *const out_path[2], int format, int flags, int64_t max_bytes, int64_t run_bytes, const char *tmp_dir,
                      int64_t *stats, std::shared_ptr<DeviceBgzf> (*get_z)(int))
 {
-	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
+	const bool check = (flags & ARX_FQSORT_CHECK) != 0, gunzip_device = (flags & ARX_FQSORT_GUNZIP_DEVICE) != 0;
 	fs_probe_inputs(in_path);
 	int fmt = format;
 	int64_t decided = -1;
@@ -57,7 +57,7 @@ inline void fp_files(int device, const char *const in_path[2], const char *const
 			st.create();
 			FpHipDrv drv; drv.st = st;
 			FqsCounts d;
-			fqs_detect_files(drv, in_path, d);
+			fqs_detect_files(drv, in_path, d, gunzip_device);
 			fmt = d.format; decided = d.decided;
 		}
 		if (fmt == FQS_UNKNOWN) {
@@ -84,7 +84,7 @@ inline void fp_files(int device, const char *const in_path[2], const char *const
 	st.create();
 	FpHipDrv drv; drv.st = st; drv.timed = (flags & ARX_FQSORT_TIMED) != 0;
 	FqsFiles files;
-	files.open(in_path, drv, FS_READ_CHUNK, max_bytes);
+	files.open(in_path, drv, FS_READ_CHUNK, max_bytes, gunzip_device);
 	FxFileSrc &src = files.src;
 	if (!check) sink.begin(st, device, get_z);
 	FsCounts c{};
@@ -97,7 +97,7 @@ inline void fp_files(int device, const char *const in_path[2], const char *const
 	} else {
 		const int64_t rb = run_bytes == -1 ? fx_auto_run_bytes(FS_WINDOW_DEFAULT, FP_AUTO_SHARE) : run_bytes;
 		fx_run_by(drv, src, check ? nullptr : &store, check ? nullptr : &sink, rb, rb < FS_WINDOW_DEFAULT ? rb : FS_WINDOW_DEFAULT, FS_SLAB_DEFAULT, c, m, S, io, rows);
-		for (int f = 0; f < 2; ++f) files.in[f].rd.reset();
+		for (int f = 0; f < 2; ++f) { files.in[f].gz.reset(); files.in[f].rd.reset(); }
 	}
 	if (!check) sink.end(drv);
 	fx_stats(stats, drv, c, src.total[0], src.total[1], !check, S, io);

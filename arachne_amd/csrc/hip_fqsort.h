@@ -9,6 +9,9 @@
 //
 // The files.  Each input is judged by its own first bytes: a BGZF file is read as it is, slab by slab (BgzfChunkReader), and inflated on the device
 // (inflate_launch: only compressed bytes go up); anything else -- plain text, ordinary gzip -- goes through zlib on a reader thread (ChunkReader).
+// With ARX_FQSORT_GUNZIP_DEVICE (ARX_FQSTD_GUNZIP_DEVICE) an ordinary gzip file (file_is_gzip) is read as it is too (GzipRawReader) and inflated
+// on the device in chunks (FsGunzip: gunzip_host.h's reader over hip_gunzip.h): its size is known only after the decode pass, so such a file
+// comes in two steps -- the size of the next piece, then room() or the caller's place, then the resolve straight into it.
 // Host memory holds two slabs per file, never a file.  The inflated texts of both files stay in device memory until the call ends.
 // The output leaves in slabs of FS_SLAB_DEFAULT bytes per file from two pairs of buffers: while slab k is fetched and written (plain text), or
 // compressed and written (ARX_FQSORT_BGZF: DeviceBgzf::run_device, blocks cut every 65280 bytes, the 28-byte EOF block last), slab k + 1 is
@@ -43,6 +46,7 @@
 #include <string.h>
 #include <sys/stat.h>
 #include <unistd.h>
+#include <atomic>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -55,6 +59,7 @@
 #include "dev_fqmerge.h"
 #include "hip_bgzf.h"
 #include "hip_bamsort.h"
+#include "hip_gunzip.h"
 
 namespace arx {
 
@@ -349,9 +354,67 @@ inline void fs_run(FsHipDrv &drv, const FsText &T, int64_t window, int64_t slab,
 }
 
 // ---- the way in.  One input file: its reader, and (where a call holds the whole text) its text in device memory
+// a gzip input that the device inflates: the reader thread's raw slabs as the compressed bytes of gunzip_host.h's reader
+struct FsGzSlabs : GzSource {
+	SlabReader *rd = nullptr;
+	const SlabReader::Slab *s = nullptr;
+	size_t at = 0;
+	bool err = false, ended = false;
+	size_t read(uint8_t *to, size_t n) override
+	{
+		size_t got = 0;
+		while (got < n && !ended) {
+			if (!s) {
+				s = rd->acquire();
+				at = 0;
+				if (!s || s->err) { err = s != nullptr; ended = true; break; }
+			}
+			const size_t k = n - got < s->len - at ? n - got : s->len - at;
+			if (k) memcpy(to + got, s->buf + at, k);
+			at += k; got += k;
+			if (at == s->len) {
+				if (s->eof) ended = true;
+				rd->release();
+				s = nullptr;
+			}
+		}
+		return got;
+	}
+};
+// What the gzip inputs of the file calls did on the device, summed over the process: a file call's own statistics have no room for it, and a
+// caller (or a test) must be able to see that the device took a file and why the host took over where it did.  arx_fastq_gunzip_counters
+enum { GZC_FILES = 0, GZC_LAUNCHES, GZC_ACCEPTED, GZC_BYTES, GZC_HOST_BYTES, GZC_FALLBACK /* + the reason, 1 .. 6 */, GZC_N = GZC_FALLBACK + 7 };
+inline std::atomic<int64_t> *gz_counters()
+{
+	static std::atomic<int64_t> c[GZC_N];
+	return c;
+}
+struct FsGunzip {
+	~FsGunzip() // however the reading ended
+	{
+		if (!rd) return;
+		std::atomic<int64_t> *c = gz_counters();
+		++c[GZC_FILES];
+		c[GZC_LAUNCHES] += rd->stats[GZS_LAUNCHES]; c[GZC_ACCEPTED] += rd->stats[GZS_ACCEPTED]; c[GZC_BYTES] += rd->delivered; c[GZC_HOST_BYTES] += rd->stats[GZS_HOST_BYTES];
+		const int64_t why = rd->stats[GZS_REASON];
+		if (why > 0 && why <= 6) ++c[GZC_FALLBACK + why];
+	}
+	GzHip dev;
+	FsGzSlabs src;
+	std::unique_ptr<GzReader<GzHip> > rd;
+	void begin(hipStream_t st, SlabReader *slabs)
+	{
+		dev.init(st);
+		src.rd = slabs;
+		const int64_t cap = (int64_t)slabs->slab_cap(), slab = cap < GZ_SLAB_DEFAULT ? (cap < 2 * GZ_CHUNK_DEFAULT ? 2 * GZ_CHUNK_DEFAULT : cap) : GZ_SLAB_DEFAULT;
+		rd.reset(new GzReader<GzHip>(dev, src, GZ_CHUNK_DEFAULT, slab, GZ_EXPAND_DEFAULT));
+	}
+};
+
 struct FsInput {
 	std::unique_ptr<SlabReader> rd;
-	bool bgzf = false, done = false;
+	bool bgzf = false, gunzip = false, done = false;
+	std::unique_ptr<FsGunzip> gz; // made by the first take(): the device is chosen by then
 	DevBuf text;
 	int64_t len = 0;
 	template <class R> bool open_as(const char *path, size_t chunk)
@@ -361,10 +424,11 @@ struct FsInput {
 		rd = std::move(r);
 		return ok;
 	}
-	bool open(const char *path, size_t chunk = FS_READ_CHUNK)
+	bool open(const char *path, size_t chunk = FS_READ_CHUNK, bool gunzip_device = false)
 	{
 		bgzf = file_is_bgzf(path);
-		return bgzf ? open_as<BgzfChunkReader>(path, chunk) : open_as<ChunkReader>(path, chunk);
+		gunzip = gunzip_device && !bgzf && file_is_gzip(path);
+		return bgzf ? open_as<BgzfChunkReader>(path, chunk) : gunzip ? open_as<GzipRawReader>(path, chunk) : open_as<ChunkReader>(path, chunk);
 	}
 	void room(int64_t need, hipStream_t st) // the text so far stays
 	{
@@ -375,10 +439,10 @@ struct FsInput {
 		text = std::move(t);
 	}
 };
-inline void fs_open_inputs(FsInput in[2], const char *const path[2], size_t chunk = FS_READ_CHUNK)
+inline void fs_open_inputs(FsInput in[2], const char *const path[2], size_t chunk = FS_READ_CHUNK, bool gunzip_device = false)
 {
 	for (int f = 0; f < 2; ++f)
-		if (!in[f].open(path[f], chunk)) throw FsIoError(std::string("cannot read ") + path[f]);
+		if (!in[f].open(path[f], chunk, gunzip_device)) throw FsIoError(std::string("cannot read ") + path[f]);
 }
 // for the calls that touch the device before they open their readers: a missing input is refused first
 inline void fs_probe_inputs(const char *const path[2])
@@ -645,6 +709,7 @@ struct FxFileSrc {
 	template <class Dst> int64_t take(int f, Dst dst)
 	{
 		FsInput &I = in[f];
+		if (I.gunzip) return take_gunzip(f, dst);
 		double t0 = bs_now_us();
 		const SlabReader::Slab *s = I.rd->acquire();
 		drv->us[FS_T_READ] += bs_now_us() - t0;
@@ -658,6 +723,22 @@ struct FxFileSrc {
 		total[f] += n;
 		if (s->eof) I.done = true;
 		I.rd->release();
+		drv->us[FS_T_INFLATE] += bs_now_us() - t0;
+		return n;
+	}
+	// the same of a gzip file that the device inflates: the next piece's size first, then its place, then the resolve straight into it
+	template <class Dst> int64_t take_gunzip(int f, Dst dst)
+	{
+		FsInput &I = in[f];
+		const double t0 = bs_now_us();
+		if (!I.gz) { I.gz.reset(new FsGunzip()); I.gz->begin(drv->st, I.rd.get()); }
+		const int64_t n = I.gz->rd->next();
+		if (n == GZ_ERROR || I.gz->src.err) throw FsIoError(std::string(path[f]) + ": read error");
+		if (n == GZ_END) { I.done = true; return -1; }
+		if (max_bytes > 0 && total[0] + total[1] + n > max_bytes)
+			throw FsTooLarge(std::string(path[0]) + " and " + path[1] + " inflate to more than the " + std::to_string(max_bytes) + " bytes allowed" + remedy);
+		I.gz->rd->place(dst(n));
+		total[f] += n;
 		drv->us[FS_T_INFLATE] += bs_now_us() - t0;
 		return n;
 	}
@@ -693,7 +774,7 @@ struct FxFileSrc {
 				const int64_t n = take(f, [&](int64_t bytes) { I.room(I.len + bytes, drv->st); return I.text.as<uint8_t>() + I.len; });
 				if (n > 0) I.len += n;
 			}
-		for (int f = 0; f < 2; ++f) { in[f].rd.reset(); text[f].release(); }
+		for (int f = 0; f < 2; ++f) { in[f].gz.reset(); in[f].rd.reset(); text[f].release(); }
 		up.release();
 		return FsText{in[0].text.as<uint8_t>(), in[1].text.as<uint8_t>(), in[0].len, in[1].len};
 	}
@@ -704,7 +785,7 @@ inline void fs_sort_files(int device, const char *const in_path[2], const char *
 {
 	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
 	FsInput in[2];
-	fs_open_inputs(in, in_path);
+	fs_open_inputs(in, in_path, FS_READ_CHUNK, (flags & ARX_FQSORT_GUNZIP_DEVICE) != 0);
 	FsFileSink sink;
 	sink.bgzf = (flags & ARX_FQSORT_BGZF) != 0;
 	if (!check) sink.open(out_path);
@@ -729,7 +810,7 @@ inline void fx_sort_files(int device, const char *const in_path[2], const char *
 {
 	const bool check = (flags & ARX_FQSORT_CHECK) != 0;
 	FsInput in[2];
-	fs_open_inputs(in, in_path);
+	fs_open_inputs(in, in_path, FS_READ_CHUNK, (flags & ARX_FQSORT_GUNZIP_DEVICE) != 0);
 	FsFileSink sink;
 	sink.bgzf = (flags & ARX_FQSORT_BGZF) != 0;
 	FxFileStore store;
@@ -750,7 +831,7 @@ inline void fx_sort_files(int device, const char *const in_path[2], const char *
 	src.start(in, in_path, drv, max_bytes);
 	if (!check) sink.begin(st, device, get_z);
 	fx_run(drv, src, check ? nullptr : &store, check ? nullptr : &sink, rb, rb < FS_WINDOW_DEFAULT ? rb : FS_WINDOW_DEFAULT, FS_SLAB_DEFAULT, c, m, S, io);
-	for (int f = 0; f < 2; ++f) in[f].rd.reset();
+	for (int f = 0; f < 2; ++f) { in[f].gz.reset(); in[f].rd.reset(); }
 	if (!check) sink.end(drv);
 	fx_stats(stats, drv, c, src.total[0], src.total[1], !check, S, io);
 }

@@ -71,20 +71,20 @@ inline void fqs_throw(int rc, int64_t window)
 struct FqsFiles {
 	FsInput in[2];
 	FxFileSrc src;
-	void open(const char *const path[2], FsHipDrv &drv, size_t chunk = FS_READ_CHUNK, int64_t max_bytes = 0)
+	void open(const char *const path[2], FsHipDrv &drv, size_t chunk = FS_READ_CHUNK, int64_t max_bytes = 0, bool gunzip_device = false)
 	{
-		fs_open_inputs(in, path, chunk);
+		fs_open_inputs(in, path, chunk, gunzip_device);
 		src.start(in, path, drv, max_bytes);
 	}
 };
 
 // the format of a file pair from its head: FQS_DETECT_WINDOW of each file first, through readers with small slabs, a whole window only where a
 // record does not fit that.  Drv: FqsHipDrv, or one with an empty phase() whose pass_done() only waits
-template <class Drv> void fqs_detect_files(Drv &drv, const char *const in_path[2], FqsCounts &d)
+template <class Drv> void fqs_detect_files(Drv &drv, const char *const in_path[2], FqsCounts &d, bool gunzip_device = false)
 {
 	for (const int64_t window : {FQS_DETECT_WINDOW, FS_WINDOW_DEFAULT}) {
 		FqsFiles files;
-		files.open(in_path, drv, window == FQS_DETECT_WINDOW ? FQS_DETECT_CHUNK : FS_READ_CHUNK);
+		files.open(in_path, drv, window == FQS_DETECT_WINDOW ? FQS_DETECT_CHUNK : FS_READ_CHUNK, 0, gunzip_device);
 		d = FqsCounts();
 		const int rc = fqs_detect(drv, files.src, window, d);
 		drv.pass_done();
@@ -106,7 +106,7 @@ inline std::string fqs_no_format() { return "no record of the first " + std::to_
 // arx_fastq_standardize.  What is refused is thrown: FsIoError, FsTooLarge, FsBadArg
 inline void fqs_files(int device, const char *const in_path[2], const char *const out_path[2], int format, int flags, int64_t *stats, std::shared_ptr<DeviceBgzf> (*get_z)(int))
 {
-	const bool detect_only = (flags & ARX_FQSTD_DETECT) != 0;
+	const bool detect_only = (flags & ARX_FQSTD_DETECT) != 0, gunzip_device = (flags & ARX_FQSTD_GUNZIP_DEVICE) != 0;
 	fs_probe_inputs(in_path);
 	select_device(device, FQS_NO_DEVICE);
 	Stream st; // the call's own; declared before the buffers, so that it has ended when they are freed
@@ -116,7 +116,7 @@ inline void fqs_files(int device, const char *const in_path[2], const char *cons
 	int64_t decided = -1;
 	if (format == FQS_AUTO || detect_only) {
 		FqsCounts d;
-		fqs_detect_files(drv, in_path, d);
+		fqs_detect_files(drv, in_path, d, gunzip_device);
 		fmt = d.format; decided = d.decided;
 		if (detect_only || fmt == FQS_STANDARD) {
 			d.n_records = 0; // nothing was written
@@ -129,7 +129,7 @@ inline void fqs_files(int device, const char *const in_path[2], const char *cons
 		}
 	}
 	FqsFiles files;
-	files.open(in_path, drv);
+	files.open(in_path, drv, FS_READ_CHUNK, 0, gunzip_device);
 	FsFileSink sink;
 	sink.bgzf = (flags & ARX_FQSTD_BGZF) != 0;
 	sink.open(out_path);

@@ -265,11 +265,12 @@ def finalize(ref: api.Reference, out_dir: str, final_path: str, sink: str = "hos
     return out
 
 
-def standardize(r1: str, r2: str, out_dir: str, format="auto", bgzf: bool = False, device: int = 0, lib_path: str = api.LIB_PATH):
+def standardize(r1: str, r2: str, out_dir: str, format="auto", bgzf: bool = False, device: int = 0, lib_path: str = api.LIB_PATH, gunzip: str = "host"):
     """The step in front of presort(): a haplotagging, stLFR or TELLseq pair with its headers rewritten on the GPU to the BX:Z: / VX:i: form the
     feeder and the sort read (api.fastq_standardize; the reference's half-written standardize.go).  format "auto" detects from the first 200
     records; a pair that is standard already is returned as it is.  The rewritten files go to out_dir under the inputs' base names
-    (+ ".std.fastq", ".gz" with bgzf).  -> (r1_std, r2_std, stats); stats["standardized"] says whether files were written."""
+    (+ ".std.fastq", ".gz" with bgzf).  gunzip="device": ordinary gzip inputs are inflated on the GPU (api.fastq_standardize).
+    -> (r1_std, r2_std, stats); stats["standardized"] says whether files were written."""
     def name(p):
         b = os.path.basename(p)
         for ext in (".gz", ".bgz", ".fastq", ".fq"):
@@ -277,7 +278,7 @@ def standardize(r1: str, r2: str, out_dir: str, format="auto", bgzf: bool = Fals
                 b = b[:-len(ext)]
         return os.path.join(out_dir, b + ".std.fastq" + (".gz" if bgzf else ""))
     if api._fqstd_format(format) == 0:
-        st = api.fastq_standardize(r1, r2, detect=True, device=device, lib_path=lib_path)
+        st = api.fastq_standardize(r1, r2, detect=True, device=device, lib_path=lib_path, gunzip=gunzip)
         if st["format"] == "standard":
             return r1, r2, dict(st, standardized=False)
         if st["format"] != "unknown":
@@ -286,21 +287,22 @@ def standardize(r1: str, r2: str, out_dir: str, format="auto", bgzf: bool = Fals
     o1, o2 = name(r1), name(r2)
     if o1 == o2:
         o2 = o2.replace(".std.", ".std.2.")
-    st = api.fastq_standardize(r1, r2, o1, o2, format=format, bgzf=bgzf, device=device, lib_path=lib_path)
+    st = api.fastq_standardize(r1, r2, o1, o2, format=format, bgzf=bgzf, device=device, lib_path=lib_path, gunzip=gunzip)
     return o1, o2, dict(st, standardized=True)
 
 
 def presort(r1: str, r2: str, out_dir: str, device: int = 0, bgzf: bool = False, if_needed: bool = True, lib_path: str = api.LIB_PATH, run_bytes: int = 0,
-            tmp_dir: "str | None" = None):
+            tmp_dir: "str | None" = None, gunzip: str = "host"):
     """The step in front of run(): the file pair sorted by barcode on the GPU (api.fastq_sort; the reference's `arachne preprocess`), which
     the feeder's barcode sets rely on.  With if_needed the input is counted first (check=True) and returned as it is when every barcode
     is one run already.  The sorted files go to out_dir under the inputs' base names (+ ".sorted.fastq", ".gz" with bgzf: a BGZF file is a
     gzip file).  run_bytes != 0 sorts in runs of that many bytes per file through temporary files under tmp_dir (api.fastq_sort_ex: a pair that
-    device memory does not hold; -1: the library chooses), the count before it included.
+    device memory does not hold; -1: the library chooses), the count before it included.  gunzip="device": ordinary gzip inputs are inflated on
+    the GPU (api.fastq_sort).
     -> (r1_sorted, r2_sorted, stats); stats["sorted"] says whether files were written."""
     sort = api.fastq_sort if run_bytes == 0 else functools.partial(api.fastq_sort_ex, run_bytes=run_bytes, tmp_dir=tmp_dir)
     if if_needed:
-        st = sort(r1, r2, check=True, device=device, lib_path=lib_path)
+        st = sort(r1, r2, check=True, device=device, lib_path=lib_path, gunzip=gunzip)
         if st["runs"] == st["distinct"]:
             return r1, r2, dict(st, sorted=False)
     os.makedirs(out_dir, exist_ok=True)
@@ -314,19 +316,19 @@ def presort(r1: str, r2: str, out_dir: str, device: int = 0, bgzf: bool = False,
     o1, o2 = name(r1), name(r2)
     if o1 == o2:
         o2 = o2.replace(".sorted.", ".sorted.2.")
-    st = sort(r1, r2, o1, o2, bgzf=bgzf, device=device, lib_path=lib_path)
+    st = sort(r1, r2, o1, o2, bgzf=bgzf, device=device, lib_path=lib_path, gunzip=gunzip)
     return o1, o2, dict(st, sorted=True)
 
 
 def prepare(r1: str, r2: str, out_dir: str, format="auto", bgzf: bool = False, device: int = 0, run_bytes: int = 0, tmp_dir: "str | None" = None, if_needed: bool = True,
-            lib_path: str = api.LIB_PATH):
+            lib_path: str = api.LIB_PATH, gunzip: str = "host"):
     """standardize() and presort() as one GPU call (api.fastq_prepare), without the files between them: the pair comes out with the headers the
     feeder reads, ordered by barcode.  With if_needed the input is counted first (check=True) and returned as it is when its format is the
     standard one and every key is one run already; a pair in another format is always written, its headers have to change.  The files go to
-    out_dir under the inputs' base names (+ ".prepared.fastq", ".gz" with bgzf).  run_bytes and tmp_dir as in presort().
+    out_dir under the inputs' base names (+ ".prepared.fastq", ".gz" with bgzf).  run_bytes, tmp_dir and gunzip as in presort().
     -> (r1_out, r2_out, stats); stats["prepared"] says whether files were written."""
     if if_needed:
-        st = api.fastq_prepare(r1, r2, format=format, check=True, run_bytes=run_bytes, device=device, lib_path=lib_path)
+        st = api.fastq_prepare(r1, r2, format=format, check=True, run_bytes=run_bytes, device=device, lib_path=lib_path, gunzip=gunzip)
         if st["format"] == "standard" and st["runs"] == st["distinct"]:
             return r1, r2, dict(st, prepared=False)
         format = st["format"]               # detected once
@@ -341,7 +343,8 @@ def prepare(r1: str, r2: str, out_dir: str, format="auto", bgzf: bool = False, d
     o1, o2 = name(r1), name(r2)
     if o1 == o2:
         o2 = o2.replace(".prepared.", ".prepared.2.")
-    st = api.fastq_prepare(r1, r2, o1, o2, format="auto" if format == "standard" else format, bgzf=bgzf, run_bytes=run_bytes, tmp_dir=tmp_dir, device=device, lib_path=lib_path)
+    st = api.fastq_prepare(r1, r2, o1, o2, format="auto" if format == "standard" else format, bgzf=bgzf, run_bytes=run_bytes, tmp_dir=tmp_dir, device=device, lib_path=lib_path,
+                           gunzip=gunzip)
     return o1, o2, dict(st, prepared=True)
 
 

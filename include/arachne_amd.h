@@ -504,7 +504,9 @@ int arx_selftest_bam_index_feeds(int32_t device, const uint8_t *stream, int64_t 
  * device: a HIP device index -- no context is needed, and none should be open beside a large sort: its index competes for the memory.
  * Inputs may be plain text, gzip or BGZF, each file judged by itself; a BGZF file is inflated on the device.  Outputs are plain text, or
  * with ARX_FQSORT_BGZF BGZF files (blocks cut every 65280 bytes, the 28-byte EOF block last) that inflate to the same bytes; they are
- * written as <path>.tmp and renamed at the end: a failing call leaves nothing behind.  ARX_FQSORT_CHECK: nothing is written, the output
+ * written as <path>.tmp and renamed at the end: a failing call leaves nothing behind.  ARX_FQSORT_GUNZIP_DEVICE: an input that is an ordinary gzip
+ * file (not BGZF) is inflated on the device in chunks (csrc/dev_gunzip.h) instead of by zlib on a reader thread; the same bytes come out, and a
+ * file on which zlib's gzread reports an error is ARX_E_IO as without the flag.  ARX_FQSORT_CHECK: nothing is written, the output
  * paths may be NULL, only stats is filled -- stats[6] == stats[7] says that the input needs no sort.  ARX_FQSORT_TIMED waits for every
  * launch and books the phases per launch group.  Both texts and 80 bytes per record stay in device memory (csrc/hip_fqsort.h); max_bytes
  * (0: no limit of its own) bounds the inflated bytes of both files together.  ARX_E_TOO_LARGE: more than max_bytes, or than the device
@@ -515,7 +517,7 @@ int arx_selftest_bam_index_feeds(int32_t device, const uint8_t *stream, int64_t 
  * [5] lines skipped, [6] barcode runs in the input, [7] distinct barcodes, [8] longest barcode, [9] sort passes, [10] parse windows,
  * [11] output slabs, then microseconds: [12] waiting for the readers, [13] upload and inflate, [14] parse, [15] keys (TIMED only: otherwise
  * under [16]), [16] sort passes, [17] gather, [18] compress and write of BGZF blocks, [19] fetch and write of plain text, last blocks, rename */
-enum { ARX_FQSORT_BGZF = 1, ARX_FQSORT_CHECK = 2, ARX_FQSORT_TIMED = 0x100 };
+enum { ARX_FQSORT_BGZF = 1, ARX_FQSORT_CHECK = 2, ARX_FQSORT_GUNZIP_DEVICE = 8, ARX_FQSORT_TIMED = 0x100 };
 int arx_fastq_sort(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t flags, int64_t max_bytes, int64_t *stats,
                    char *msg, int32_t msg_cap);
 /* self-test of the same orchestration (preprocess.go:42-114 as above) on two texts in host memory, no file and no index needed
@@ -544,7 +546,8 @@ int arx_selftest_fastq_sort(int32_t device, const uint8_t *t1, int64_t n1, const
  * the runs that the host reads back -- every temporary byte is written once and read once.
  * Temporary files: plain text, one per input file (arx_fqsort_XXXXXX.r1 / .r2, the name unique per call), under tmp_dir (NULL: the directory
  * of r1_out); the disk needed is the inflated size of both files; they are removed on every way out.  With ARX_FQSORT_CHECK no temporary
- * file is written and tmp_dir is not looked at: only the keys are kept, so an input of any size can be judged.
+ * file is written and tmp_dir is not looked at: only the keys are kept, so an input of any size can be judged.  ARX_FQSORT_GUNZIP_DEVICE as
+ * in arx_fastq_sort: a gzip file is inflated on the device.
  * ARX_E_TOO_LARGE: more than max_bytes; a line or record that a run does not hold with both buffers full, or more than 1024 runs (msg:
  * use a larger run_bytes); more than 2^32 - 1 records; buffers or a record table that the device does not hold.  ARX_E_IO as above, and a
  * tmp_dir in which no file can be made.  After any error neither outputs, .tmp files nor temporary files are left.
@@ -604,7 +607,8 @@ int arx_selftest_fastq_sort_ext(int32_t device, const uint8_t *t1, int64_t n1, c
  * returns ARX_OK and writes nothing -- no output file and no .tmp is created, stats[6] says so, the caller uses its inputs; AUTO that
  * finds unknown is ARX_E_ARG (msg: no record of the first 200 names a format, pass one).  ARX_FQSTD_DETECT: only the detection runs, the
  * output paths may be NULL, and unknown is a result (ARX_OK, stats[6] = 5).  A forced format on an input of zero records gives two empty outputs.
- * Inputs may be plain text, gzip or BGZF, each file judged by itself; a BGZF file is inflated on the device.  Outputs are plain text, or with
+ * Inputs may be plain text, gzip or BGZF, each file judged by itself; a BGZF file is inflated on the device, and with ARX_FQSTD_GUNZIP_DEVICE
+ * a gzip file is inflated on the device too (in chunks: csrc/dev_gunzip.h), the detection's reads included.  Outputs are plain text, or with
  * ARX_FQSTD_BGZF BGZF files (blocks cut every 65280 bytes, the 28-byte EOF block last); they are written as <path>.tmp and renamed at the end:
  * a failing call leaves nothing behind.  The call streams: device memory holds the parse windows (32 MiB per file, twice), their carry and
  * the output slabs (64 MiB per file, twice), never a file; there is no size limit and no max_bytes (csrc/hip_fqstd.h has the accounting).
@@ -619,7 +623,7 @@ int arx_selftest_fastq_sort_ext(int32_t device, const uint8_t *t1, int64_t n1, c
  * blocks, [19] fetch and write of plain text, last blocks, rename.  arx_fastq_prepare below is this step fused into the sort: one call, no
  * files between the two.  Not built: other header formats. */
 enum { ARX_FQSTD_AUTO = 0, ARX_FQSTD_HAPLOTAGGING = 1, ARX_FQSTD_STLFR = 2, ARX_FQSTD_TELLSEQ = 3, ARX_FQSTD_STANDARD = 4, ARX_FQSTD_UNKNOWN = 5 }; /* 4, 5: results only */
-enum { ARX_FQSTD_BGZF = 1, ARX_FQSTD_DETECT = 2, ARX_FQSTD_TIMED = 0x100 };
+enum { ARX_FQSTD_BGZF = 1, ARX_FQSTD_DETECT = 2, ARX_FQSTD_GUNZIP_DEVICE = 8, ARX_FQSTD_TIMED = 0x100 };
 int arx_fastq_standardize(int32_t device, const char *r1_in, const char *r2_in, const char *r1_out, const char *r2_out, int32_t format, int32_t flags, int64_t *stats,
                           char *msg, int32_t msg_cap);
 /* self-test of the same orchestration, detection pass included, on two texts in host memory (tests/test_fastq_standardize_gpu.py).
@@ -650,7 +654,7 @@ int arx_selftest_fastq_standardize(int32_t device, const uint8_t *t1, int64_t n1
  *               arx_fastq_sort_ex on the inputs -- the sorted files are written, this is a sort and no no-op; stats[26] and [27] are 0
  *               then.  AUTO that finds unknown: ARX_E_ARG, nothing is written, stats[24] = 5.  A forced format on zero records gives two
  *               empty outputs
- * flags are arx_fastq_sort_ex's: ARX_FQSORT_BGZF, ARX_FQSORT_TIMED, and ARX_FQSORT_CHECK -- nothing is written, the output paths may be
+ * flags are arx_fastq_sort_ex's: ARX_FQSORT_BGZF, ARX_FQSORT_TIMED, ARX_FQSORT_GUNZIP_DEVICE (a gzip file is inflated on the device), and ARX_FQSORT_CHECK -- nothing is written, the output paths may be
  * NULL, no temporary file is made, only stats is filled, and stats[6] == stats[7] says that the standardized input would need no sort.
  * max_bytes, run_bytes and tmp_dir are arx_fastq_sort_ex's too, with two differences: the run buffers hold RAW text while the temporary
  * files hold standardized text (the disk needed is the output's size), and run_bytes == -1 is a TENTH of the free device memory less 1 GiB
@@ -830,6 +834,36 @@ enum { ARX_INFLATE_OK = 0, ARX_INFLATE_BAD_HEADER, ARX_INFLATE_BAD_BTYPE, ARX_IN
        ARX_INFLATE_BAD_DISTANCE, ARX_INFLATE_TRUNCATED, ARX_INFLATE_SIZE_MISMATCH, ARX_INFLATE_CRC_MISMATCH };
 int arx_selftest_inflate(int32_t device, const uint8_t *src, int64_t n, uint8_t *out, int64_t cap, int64_t *out_len, int32_t *status, int32_t status_cap,
                          int64_t *stats);
+
+/* self-test of the chunked inflate of a plain gzip file (one DEFLATE stream per member, no BGZF framing) on bytes in host memory, no index and
+ * no file needed (tests/test_gunzip_gpu.py; csrc/dev_gunzip.h, hip_gunzip.h, gunzip_host.h).  src[0..n) is the file.  Its members' bodies are cut
+ * into chunks of chunk_bytes compressed bytes, slab_bytes of them to a launch; every chunk looks for a DEFLATE block start in its range and
+ * decodes from there into 16-bit symbols on the device, the windows are handed down the chain of chunks and the back-references into
+ * unknown history replaced.  The framing (member headers, trailers, CRC-32 and length, the next member) is the calling thread's.  Whatever the
+ * device does not take hands the rest of the file to zlib on the host.  The yardstick is zlib's gzread: out[0..*out_len) receives the bytes
+ * gzread reads from the same file (members one after the other; bytes behind the last member that do not start a gzip header are ignored; a
+ * file without the gzip magic comes back as it is), and where gzread reports an error the entry returns ARX_E_IO and *out_len is 0.
+ * chunk_bytes: 0 for the default (32 KiB: the fastest of 32 / 64 / 128 KiB in profiles/device_gunzip), else at least 64.  slab_bytes: 0 for the default (8 MiB; not measured), else at
+ * least 2 * chunk_bytes, at most 128 MiB and at most 16384 * chunk_bytes (a 32 KiB window is kept per chunk of a launch).  expand: 16-bit staging symbols per compressed byte, 0 for the default (8; not measured), at
+ * most 1032, and slab_bytes * expand at most 2^30; a chunk that inflates to more is an overflow and goes to the host.
+ * stats[ARX_GUNZIP_N_STATS] (may be NULL): [0] members, [1] compressed bytes consumed, [2] inflated bytes, [3] launches, [4] chunks, [5] chunks
+ * with a candidate block start, [6] chunks accepted, [7] candidates refuted, [8] DEFLATE blocks decoded on the device, [9] marker symbols
+ * replaced, [10] bytes inflated by the host, [11] why the host took over (ARX_GUNZIP_FB_*: the first reason; 0: it did not), [12] bytes
+ * ignored behind the last member, [13..15] microseconds of the launches' phases: find, decode, windows and resolve together.
+ * Returns ARX_OK, ARX_E_IO as said, ARX_E_ARG for sizes outside their bounds or a cap below the inflated size, ARX_E_TOO_LARGE where host or
+ * device memory does not hold a launch's buffers, ARX_E_DEVICE without a GPU. */
+enum { ARX_GUNZIP_FB_NONE = 0, ARX_GUNZIP_FB_REFUTED, ARX_GUNZIP_FB_OVERFLOW, ARX_GUNZIP_FB_STATUS, ARX_GUNZIP_FB_CHECK, ARX_GUNZIP_FB_NO_BLOCK, ARX_GUNZIP_FB_CUT_SHORT };
+enum { ARX_GUNZIP_N_STATS = 16 };
+int arx_selftest_gunzip(int32_t device, const uint8_t *src, int64_t n, int64_t chunk_bytes, int64_t slab_bytes, int32_t expand, uint8_t *out, int64_t cap, int64_t *out_len,
+                        int64_t *stats);
+
+/* What the gzip inputs of the file-pair calls did on the device (ARX_FQSORT_GUNZIP_DEVICE, ARX_FQSTD_GUNZIP_DEVICE), summed over the process
+ * since it started or since the last call with reset != 0; a file is booked when its reading ends, by the end of the file, an error or the end
+ * of a detection.  counters[ARX_GUNZIP_N_COUNTERS]: [0] gzip files the device was given, [1] launches, [2] chunks accepted, [3] bytes of text
+ * delivered, [4] of them inflated by the host's zlib, [5] unused, [6..11] files in which the host took over, by the first reason
+ * ARX_GUNZIP_FB_REFUTED .. ARX_GUNZIP_FB_CUT_SHORT.  No device is touched. */
+enum { ARX_GUNZIP_N_COUNTERS = 12 };
+int arx_fastq_gunzip_counters(int64_t *counters, int32_t reset);
 
 /* self-test of the decimal text the records phase writes on the device (csrc/dev_records_full.h), one input per lane: kind 0: "%d" of a[i]
  * (b is not read); kind 1: "%.6f" of (double)a[i] / (double)b[i], b[i] > 0 (else ARX_E_ARG).  out: n rows of 32 bytes, len[n]: the bytes
