@@ -172,6 +172,9 @@ _SELFTEST_ARGS = {
     "arx_fastq_standardize": [C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_fastq_standardize": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] +
                                       [C.c_void_p] * 5,
+    # the reference FASTA read and packed on the device
+    "arx_index_build_ex": [C.c_int32, C.c_char_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32],
+    "arx_selftest_fasta_pack": [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64],
     # the two fused into one call
     "arx_fastq_prepare": [C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int32],
     "arx_selftest_fastq_prepare": [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] +
@@ -742,12 +745,64 @@ def fastq_gunzip_counters(reset: bool = False, lib_path: str = LIB_PATH):
                 fallbacks={GUNZIP_FALLBACK[k]: int(c[5 + k]) for k in range(1, 7) if c[5 + k]})
 
 
-def index_build(fasta: str, prefix: str, lib_path: str = LIB_PATH) -> None:
-    """`bwa index` equivalent (host side): writes <prefix>.{bwt,sa,pac,ann,amb}, byte-identical to the reference's."""
+INDEX_PACK_ONLY = 1
+_INDEX_EX_STATS = ("l_pac", "contigs", "holes", "ambiguous", "text_bytes", "compressed_bytes", "windows", "read_wait_us", "upload_inflate_us", "pack_us", "pac_write_us",
+                   "ann_amb_us", "sort_us", "total_us")
+
+
+def index_build(fasta: str, prefix: str, lib_path: str = LIB_PATH, pack: str = "host", device: int = 0, pack_only: bool = False):
+    """`bwa index` equivalent: writes <prefix>.{bwt,sa,pac,ann,amb}, byte-identical to the reference's.  pack="host" (the default): the FASTA
+    is plain text, parsed and packed on the host (arx_index_build) -> None.  pack="device" (arx_index_build_ex, replaces bntseq.c:227-328):
+    the FASTA -- plain, gzip or BGZF -- is read, inflated (BGZF) and packed on GPU `device` and the suffix sorter takes the packed strand
+    where it lies; pack_only=True stops behind .pac, .ann and .amb -> the stats as a dict.  ArachneError (with .code on the device path) on
+    failure; the device path leaves nothing behind then."""
     lib = _load(lib_path)
-    msg = C.create_string_buffer(512)
-    if lib.arx_index_build(fasta.encode(), prefix.encode(), msg, 512) != 0:
-        raise ArachneError("arx_index_build: " + msg.value.decode())
+    if pack == "host":
+        if pack_only:
+            raise ValueError("pack_only needs pack=\"device\"")
+        msg = C.create_string_buffer(512)
+        if lib.arx_index_build(fasta.encode(), prefix.encode(), msg, 512) != 0:
+            raise ArachneError("arx_index_build: " + msg.value.decode())
+        return None
+    if pack != "device":
+        raise ValueError("pack is \"host\" or \"device\"")
+    st, msg = np.zeros(len(_INDEX_EX_STATS), dtype=np.int64), C.create_string_buffer(1024)
+    rc = _selftest_fn(lib, "arx_index_build_ex")(device, os.fsencode(fasta), os.fsencode(prefix), INDEX_PACK_ONLY if pack_only else 0, st.ctypes.data, msg, 1024)
+    if rc != 0:
+        e = ArachneError("arx_index_build_ex: " + msg.value.decode(errors="replace"))
+        e.code = rc
+        raise e
+    return {k: int(v) for k, v in zip(_INDEX_EX_STATS, st)}
+
+
+def index_build_times(lib_path: str = LIB_PATH):
+    """Where this thread's last index_build(pack="host") spent its time -> dict(pack_s, write_s, sort_s) (arx_index_build_times)."""
+    lib = _load(lib_path)
+    secs = np.zeros(3, dtype=np.float64)
+    lib.arx_index_build_times.argtypes = [C.c_void_p]
+    if lib.arx_index_build_times(secs.ctypes.data) != 0:
+        raise ArachneError("arx_index_build_times failed")
+    return dict(pack_s=float(secs[0]), write_s=float(secs[1]), sort_s=float(secs[2]))
+
+
+def selftest_fasta_pack(text, window_bytes: int = 0, device: int = 0, lib_path: str = LIB_PATH):
+    """arx_index_build_ex's pack on a text in memory, in windows of window_bytes (include/arachne_amd.h: arx_selftest_fasta_pack; replaces
+    bntseq.c:227-328) -> dict(rc: 0, or ARX_E_OPEN = -1 with refused = 1 (a base before the first '>') or 2 (no base); pac: the packed bases;
+    l_pac, n_amb, cnt_fwd, windows; contigs: rows (header begin, header end, offset, length, holes); holes: rows (offset, length, byte))."""
+    lib = _load(lib_path)
+    s = np.frombuffer(bytes(text), dtype=np.uint8)
+    n = len(s)
+    pac, out = np.zeros(n // 4 + 1, dtype=np.uint8), np.zeros(10, dtype=np.int64)
+    crow, hrow = np.zeros((n // 2 + 1, 5), dtype=np.int64), np.zeros((n + 1, 3), dtype=np.int64)
+    rc = _selftest_fn(lib, "arx_selftest_fasta_pack")(device, s.ctypes.data if n else None, n, int(window_bytes), pac.ctypes.data, len(pac), out.ctypes.data,
+                                                     crow.ctypes.data, len(crow), hrow.ctypes.data, len(hrow))
+    if rc not in (ARX_OK, ARX_E_OPEN):
+        e = ArachneError("arx_selftest_fasta_pack: code %d" % rc)
+        e.code = rc
+        raise e
+    l_pac, nc, nh = int(out[0]), int(out[1]), int(out[2])
+    return dict(rc=rc, refused=int(out[9]), pac=pac[:(l_pac + 3) // 4].tobytes(), l_pac=l_pac, n_amb=int(out[3]), cnt_fwd=[int(x) for x in out[4:8]], windows=int(out[8]),
+                contigs=[tuple(int(x) for x in r) for r in crow[:nc]], holes=[tuple(int(x) for x in r) for r in hrow[:nh]])
 
 
 def selftest_rec_text(a, b=None, device: int = 0, lib_path: str = LIB_PATH):

@@ -339,13 +339,21 @@ template <class RT> struct Batch {
 	using Ctx = arx::Context<RT>;                                                                                                   \
 	using Bat = arx::Batch<RT>;                                                                                                     \
 	static thread_local std::string g_open_error;                                                                                   \
+	static thread_local arx::BuildStats g_build_stats; /* of the calling thread's last arx_index_build */                           \
 	extern "C" {                                                                                                                    \
 	int arx_index_build(const char *fasta, const char *prefix, char *msg, int32_t msg_cap)                                          \
 	{                                                                                                                               \
 		std::string e;                                                                                                              \
-		try { e = arx::build_index(fasta, prefix, RT::bwt_sa_fn()); } catch (const std::exception &ex) { e = ex.what(); }                            \
+		g_build_stats = arx::BuildStats();                                                                                          \
+		try { e = arx::build_index(fasta, prefix, RT::bwt_sa_fn(), &g_build_stats); } catch (const std::exception &ex) { e = ex.what(); }       \
 		if (msg && msg_cap > 0) snprintf(msg, msg_cap, "%s", e.c_str());                                                            \
 		return e.empty() ? ARX_OK : ARX_E_OPEN;                                                                                     \
+	}                                                                                                                               \
+	int arx_index_build_times(double *secs)                                                                                         \
+	{                                                                                                                               \
+		if (!secs) return ARX_E_ARG;                                                                                                \
+		secs[0] = g_build_stats.secs_pack; secs[1] = g_build_stats.secs_write; secs[2] = g_build_stats.secs_sa;                     \
+		return ARX_OK;                                                                                                              \
 	}                                                                                                                               \
 	int arx_open(const char *prefix, int device, arx_ctx **out)                                                                     \
 	{                                                                                                                               \

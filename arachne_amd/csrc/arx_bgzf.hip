@@ -4,7 +4,8 @@
 // sort of a BAM file into an open writer (arx_bam_open_ex, arx_bam_sort_append, arx_selftest_bam_sort: dev_bamsort.h, hip_bamsort.h), and the sort
 // of a FASTQ file pair by barcode (arx_fastq_sort, arx_selftest_fastq_sort: dev_fqsort.h, hip_fqsort.h) with the header standardization in front of it (arx_fastq_standardize,
 // arx_selftest_fastq_standardize: dev_fqstd.h, hip_fqstd.h) and the two fused into one call (arx_fastq_prepare, arx_selftest_fastq_prepare: dev_fqprep.h, hip_fqprep.h), and the .bai of a coordinate-sorted
-// BAM file and its .csi (arx_bam_index, arx_bam_index_csi and their self-tests: dev_bamindex.h, hip_bamindex.h).
+// BAM file and its .csi (arx_bam_index, arx_bam_index_csi and their self-tests: dev_bamindex.h, hip_bamindex.h).  The FASTQ calls' readers also
+// serve the index build that reads and packs its FASTA on the device (arx_index_build_ex, arx_selftest_fasta_pack: dev_fapack.h, hip_fapack.h).
 #include <map>
 #include <memory>
 #include <mutex>
@@ -16,6 +17,7 @@
 #include "hip_fqsort.h"
 #include "hip_fqstd.h"
 #include "hip_fqprep.h"
+#include "hip_fapack.h"
 #include "hip_bamindex.h"
 
 namespace arx {
@@ -610,6 +612,59 @@ extern "C" int arx_selftest_fastq_standardize(int32_t device, const uint8_t *t1,
 		const int rc = fq_hand_out(sink.text, off, c.bytes1, c.bytes2, c.n_records, cap1, cap2, ARX_E_TOO_LARGE, out1, out2, out_len, rec_off1, rec_off2, n_records);
 		if (rc == ARX_OK) arx::fqs_stats(stats, drv, c, fmt, decided, sink.us_consume, 0, 0);
 		return rc;
+	});
+}
+
+// ---- the step that opens every run: the reference FASTA read and packed on the device (dev_fapack.h, hip_fapack.h; replaces bntseq.c:227-328)
+extern "C" int arx_index_build_ex(int32_t device, const char *fasta, const char *prefix, int32_t flags, int64_t *stats, char *msg, int32_t msg_cap)
+{
+	if (stats) for (int k = 0; k < arx::FA_N_STATS; ++k) stats[k] = 0;
+	std::string refused; // what arx_index_build refuses too: its code and its texts
+	const int rc = fq_file_call(msg, msg_cap, "the device memory does not hold the packed strand and the windows of the call", "", [&]() {
+		const char *call = "arx_index_build_ex";
+		if (!fasta || !prefix) fq_bad(call, "null argument");
+		if (flags & ~ARX_INDEX_PACK_ONLY) fq_bad(call, "unknown flag bits");
+		try {
+			arx::fa_build_files(device, fasta, prefix, flags, stats);
+		} catch (const arx::FaRefused &e) {
+			refused = e.what();
+		}
+	});
+	if (refused.empty()) return rc;
+	if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", refused.c_str());
+	return ARX_E_OPEN;
+}
+
+extern "C" int arx_selftest_fasta_pack(int32_t device, const uint8_t *text, int64_t n, int64_t window_bytes, uint8_t *pac, int64_t pac_cap, int64_t *out, int64_t *contig_rows,
+                                       int64_t contig_cap, int64_t *hole_rows, int64_t hole_cap)
+{
+	if (n < 0 || (n > 0 && !text) || !out || pac_cap < 0 || contig_cap < 0 || hole_cap < 0 || (pac_cap > 0 && !pac) || (contig_cap > 0 && !contig_rows) || (hole_cap > 0 && !hole_rows) ||
+	    (window_bytes != 0 && (window_bytes < arx::FA_MIN_WINDOW || window_bytes > arx::FA_MAX_WINDOW)))
+		return ARX_E_ARG;
+	for (int k = 0; k < 10; ++k) out[k] = 0;
+	return fq_selftest_call([&]() -> int {
+		arx::select_device(device, arx::FA_NO_DEVICE);
+		arx::Stream st;
+		st.create();
+		arx::FaHipDrv drv; drv.st = st;
+		arx::FaState S;
+		std::vector<arx::FaContig> contigs;
+		std::vector<arx::FaHole> holes;
+		std::vector<uint8_t> bytes;
+		arx::fa_pack_mem(drv, text, n, window_bytes ? window_bytes : arx::FA_WINDOW_DEFAULT, S, contigs, holes, bytes);
+		out[8] = S.windows;
+		if (S.bad_start || S.l_pac == 0) { out[9] = S.bad_start ? 1 : 2; return ARX_E_OPEN; }
+		if (S.contig_too_long || (int64_t)bytes.size() > pac_cap || (int64_t)contigs.size() > contig_cap || (int64_t)holes.size() > hole_cap) return ARX_E_TOO_LARGE;
+		if (!bytes.empty()) memcpy(pac, bytes.data(), bytes.size());
+		out[0] = S.l_pac; out[1] = S.n_contigs; out[2] = S.n_holes; out[3] = S.n_amb;
+		for (int c = 0; c < 4; ++c) out[4 + c] = (int64_t)S.cnt[c];
+		for (size_t c = 0; c < contigs.size(); ++c) {
+			const arx::FaContig &r = contigs[c];
+			const int64_t row[5] = {r.hdr_b, r.hdr_e, r.off, r.len, r.n_holes};
+			memcpy(contig_rows + 5 * c, row, sizeof row);
+		}
+		for (size_t h = 0; h < holes.size(); ++h) { hole_rows[3 * h] = holes[h].off; hole_rows[3 * h + 1] = holes[h].len; hole_rows[3 * h + 2] = holes[h].ch; }
+		return ARX_OK;
 	});
 }
 

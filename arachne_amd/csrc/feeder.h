@@ -220,10 +220,20 @@ protected:
 			const int got = gzread(f_, s.buf + s.len, (unsigned)chunk_);
 			if (got < 0) { s.err = true; break; }
 			if (got > 0) { s.len += (size_t)got; ++s.chunks; }
-			if ((size_t)got < chunk_) { s.eof = true; break; }
+			if ((size_t)got < chunk_) {
+				if (strict_end) { // a gzip stream that ends inside a member: gzread hands out what it has, only gzerror tells
+					int e = Z_OK;
+					(void)gzerror(f_, &e);
+					if (e != Z_OK && e != Z_STREAM_END) s.err = true;
+				}
+				s.eof = true;
+				break;
+			}
 		}
 		s.text = s.len;
 	}
+public:
+	bool strict_end = false; // set before start(): the end of the input is checked with gzerror (arx_index_build_ex; the FASTQ calls take what gzread gives)
 private:
 	gzFile f_ = nullptr;
 	size_t chunk_ = 0, cap_ = 0;

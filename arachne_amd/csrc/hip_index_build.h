@@ -271,11 +271,28 @@ inline void stream_to_file(FILE *o, const void *dev, size_t bytes, hipStream_t s
 
 struct DeviceBuildStats { double s_text = 0, s_bucket = 0, s_chunks = 0, s_rounds = 0, s_verify = 0, s_emit = 0; int n_chunks = 0, n_rounds = 0; u64 unresolved0 = 0; };
 
+// the packed strand where it lies in device memory (arx_index_build_ex: dev_fapack.h packs it there), with at least 8 bytes of room behind
+// pac_bytes; suffix: appended to the two file names
+struct DevicePac { const uint8_t *p; const char *suffix; };
+inline std::string build_bwt_sa_device(const DevicePac *on_device, const uint8_t *pac, size_t pac_bytes, int64_t l_pac_, const uint64_t cnt_fwd[4], const std::string &prefix,
+                                       const IndexBuildSwitches &sw, DeviceBuildStats *stats);
 // pac: forward strand (l_pac bases, 4 per byte); cnt_fwd[c]: occurrences of base c on the forward strand.
 // Writes <prefix>.bwt and <prefix>.sa.  Returns "" or an error message.
 inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int64_t l_pac_, const uint64_t cnt_fwd[4], const std::string &prefix,
                                        const IndexBuildSwitches &sw, DeviceBuildStats *stats = nullptr)
 {
+	return build_bwt_sa_device(nullptr, pac, pac_bytes, l_pac_, cnt_fwd, prefix, sw, stats);
+}
+// the same of a strand that is in device memory already: no upload
+inline std::string build_bwt_sa_device(const DevicePac &dpac, size_t pac_bytes, int64_t l_pac_, const uint64_t cnt_fwd[4], const std::string &prefix,
+                                       const IndexBuildSwitches &sw, DeviceBuildStats *stats = nullptr)
+{
+	return build_bwt_sa_device(&dpac, nullptr, pac_bytes, l_pac_, cnt_fwd, prefix, sw, stats);
+}
+inline std::string build_bwt_sa_device(const DevicePac *on_device, const uint8_t *pac, size_t pac_bytes, int64_t l_pac_, const uint64_t cnt_fwd[4], const std::string &prefix,
+                                       const IndexBuildSwitches &sw, DeviceBuildStats *stats)
+{
+	const std::string suffix = on_device ? on_device->suffix : "";
 	const u64 l_pac = (u64)l_pac_, n = 2 * l_pac;
 	const bool verbose = sw.verbose, verify = sw.verify;
 	const u64 chunk_cap = sw.chunk < 1 ? 1 : sw.chunk, slice_cap = sw.slice < 1 ? 1 : sw.slice;
@@ -292,9 +309,12 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 		const u64 n_tw = (n + 31) / 32 + 2;
 		DevBuf dT(n_tw * 8);
 		{
-			DevBuf dpac(pac_bytes + 8);
-			ARX_HIP_CHECK(hipMemcpy(dpac.p, pac, pac_bytes, hipMemcpyHostToDevice));
-			hip_launch("k_pack_text", k_pack_text, grid_for(n_tw), dim3(256), 0, st, dpac.as<uint8_t>(), l_pac, dT.as<u64>(), n_tw);
+			DevBuf dpac;
+			if (!on_device) {
+				dpac.alloc(pac_bytes + 8);
+				ARX_HIP_CHECK(hipMemcpy(dpac.p, pac, pac_bytes, hipMemcpyHostToDevice));
+			}
+			hip_launch("k_pack_text", k_pack_text, grid_for(n_tw), dim3(256), 0, st, on_device ? on_device->p : dpac.as<uint8_t>(), l_pac, dT.as<u64>(), n_tw);
 			ARX_HIP_CHECK(hipStreamSynchronize(st));
 		}
 		const u64 *T = dT.as<u64>();
@@ -457,7 +477,7 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 			ARX_HIP_CHECK(hipMemsetAsync(dout.p, 0, out_words * 4, st));
 			hip_launch("k_interleave", k_interleave, grid_for(n_blocks + 1), dim3(256), 0, st, dwords.as<uint32_t>(), n_words, n_blocks, c0.as<u64>(), c1.as<u64>(), c2.as<u64>(), c3.as<u64>(), dtot.as<u64>(), dout.as<uint32_t>());
 			ARX_HIP_CHECK(hipStreamSynchronize(st));
-			FILE *o = fopen((prefix + ".bwt").c_str(), "wb");
+			FILE *o = fopen((prefix + ".bwt" + suffix).c_str(), "wb");
 			if (!o) return "cannot write " + prefix + ".bwt";
 			fwrite(&primary, 8, 1, o); fwrite(L2 + 1, 8, 4, o);
 			try { stream_to_file(o, dout.p, out_words * 4, st); } catch (...) { fclose(o); throw; }
@@ -467,7 +487,7 @@ inline std::string build_bwt_sa_device(const uint8_t *pac, size_t pac_bytes, int
 			const u64 intv = 32, n_sa = (n + intv) / intv, seq_len = n;
 			DevBuf ds((n_sa ? n_sa : 1) * 8);
 			if (n_sa > 1) hip_launch("k_sa_sample", k_sa_sample, grid_for(n_sa - 1), dim3(256), 0, st, SA, n_sa, intv, ds.as<u64>());
-			FILE *o = fopen((prefix + ".sa").c_str(), "wb");
+			FILE *o = fopen((prefix + ".sa" + suffix).c_str(), "wb");
 			if (!o) return "cannot write " + prefix + ".sa";
 			fwrite(&primary, 8, 1, o); fwrite(L2 + 1, 8, 4, o); fwrite(&intv, 8, 1, o); fwrite(&seq_len, 8, 1, o);
 			try { stream_to_file(o, ds.p, (n_sa - 1) * 8, st); } catch (...) { fclose(o); throw; }

@@ -6,11 +6,13 @@
 // The BWT of a text is unique, so instead of the reference's two construction algorithms (IS for < 50 Mbp, ropes
 // above) any suffix sorter gives its bytes: induced sorting on the host below (32-bit, for builds without a GPU), prefix
 // doubling in HBM in hip_index_build.h (what libarachne_amd.so uses when a device is visible; GRCh38-size genomes); the
-// sampled SA is read straight off the suffix array instead of being recovered by n LF steps.
+// sampled SA is read straight off the suffix array instead of being recovered by n LF steps.  build_index below parses and packs the FASTA
+// on the host; arx_index_build_ex (dev_fapack.h, hip_fapack.h) does that on the device and shares the header text handling and the writers.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <time.h>
 #include <string>
 #include <vector>
 
@@ -165,15 +167,64 @@ inline std::string build_bwt_sa_host(const uint8_t *pac, size_t, int64_t l_pac, 
 	return "";
 }
 
+// ---- what the host builder below and the device builder (dev_fapack.h, hip_fapack.h: arx_index_build_ex) share: the text of a header and
+// the writers of <prefix>.pac/.ann/.amb.  `suffix` is appended to every file name (the device builder writes <file>.tmp and renames)
+struct FaAnn { std::string name, anno; int64_t offset; int32_t len, n_ambs; };
+struct FaAmb { int64_t offset; int32_t len; char amb; };
+// the contig that header text h (without its '>' and '\n') opens at `offset`: trailing '\r's dropped, the name up to the first blank, the
+// comment behind the blanks or "(null)"
+inline FaAnn fa_ann_of_header(std::string h, int64_t offset)
+{
+	while (!h.empty() && h.back() == '\r') h.pop_back();
+	FaAnn a; size_t i = 0;
+	while (i < h.size() && h[i] != ' ' && h[i] != '\t') ++i;
+	a.name = h.substr(0, i);
+	while (i < h.size() && (h[i] == ' ' || h[i] == '\t')) ++i;
+	a.anno = i < h.size() ? h.substr(i) : "(null)";
+	a.offset = offset; a.len = 0; a.n_ambs = 0;
+	return a;
+}
+// the end of .pac behind the packed bases: a zero byte when l_pac % 4 == 0, then l_pac % 4 (bntseq.c:306-319)
+inline void fa_write_pac_end(FILE *o, int64_t l_pac)
+{
+	uint8_t ct = 0;
+	if (l_pac % 4 == 0) fwrite(&ct, 1, 1, o);
+	ct = (uint8_t)(l_pac % 4);
+	fwrite(&ct, 1, 1, o);
+}
+inline std::string fa_write_ann_amb(const std::string &prefix, const char *suffix, int64_t l_pac, const std::vector<FaAnn> &anns, const std::vector<FaAmb> &ambs)
+{
+	FILE *o = fopen((prefix + ".ann" + suffix).c_str(), "w");
+	if (!o) return "cannot write " + prefix + ".ann";
+	fprintf(o, "%lld %d %u\n", (long long)l_pac, (int)anns.size(), 11u);
+	for (auto &a : anns) {
+		fprintf(o, "%d %s", 0, a.name.c_str());
+		if (!a.anno.empty()) fprintf(o, " %s\n", a.anno.c_str()); else fprintf(o, "\n");
+		fprintf(o, "%lld %d %d\n", (long long)a.offset, a.len, a.n_ambs);
+	}
+	if (fclose(o) != 0) return "cannot write " + prefix + ".ann";
+	o = fopen((prefix + ".amb" + suffix).c_str(), "w");
+	if (!o) return "cannot write " + prefix + ".amb";
+	fprintf(o, "%lld %d %u\n", (long long)l_pac, (int)anns.size(), (unsigned)ambs.size());
+	for (auto &h : ambs) fprintf(o, "%lld %d %c\n", (long long)h.offset, h.len, h.amb);
+	if (fclose(o) != 0) return "cannot write " + prefix + ".amb";
+	return "";
+}
+inline double fa_now_s()
+{
+	struct timespec ts;
+	clock_gettime(CLOCK_MONOTONIC, &ts);
+	return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
 // Build all index files from a plain-text FASTA.  Returns "" or an error message.
 inline std::string build_index(const std::string &fasta, const std::string &prefix, BwtSaFn bwt_sa = build_bwt_sa_host, BuildStats *stats = nullptr)
 {
+	const double t_start = fa_now_s();
 	FILE *f = fopen(fasta.c_str(), "rb");
 	if (!f) return "cannot open " + fasta;
-	struct Ann { std::string name, anno; int64_t offset; int32_t len, n_ambs; };
-	struct Amb { int64_t offset; int32_t len; char amb; };
-	std::vector<Ann> anns;
-	std::vector<Amb> ambs;
+	std::vector<FaAnn> anns;
+	std::vector<FaAmb> ambs;
 	std::vector<uint8_t> pac; // forward strand, 4 bases per byte (first base in the top bits), N already randomised
 	int64_t l_pac = 0;
 	uint64_t cnt_fwd[4] = {0, 0, 0, 0};
@@ -188,33 +239,23 @@ inline std::string build_index(const std::string &fasta, const std::string &pref
 		bool in_hdr = false;
 		std::string hdr;
 		uint8_t acc = 0; // the byte being filled
-		auto start_seq = [&](const std::string &h) {
-			Ann a; size_t i = 0;
-			while (i < h.size() && h[i] != ' ' && h[i] != '\t') ++i;
-			a.name = h.substr(0, i);
-			while (i < h.size() && (h[i] == ' ' || h[i] == '\t')) ++i;
-			a.anno = i < h.size() ? h.substr(i) : "(null)";
-			a.offset = l_pac; a.len = 0; a.n_ambs = 0;
-			anns.push_back(a);
-			lasts = 0;
-		};
 		size_t got;
 		while ((got = fread(buf.data(), 1, buf.size(), f)) > 0) {
 			for (size_t k = 0; k < got; ++k) {
 				const char ch = buf[k];
 				if (in_hdr) {
-					if (ch == '\n') { in_hdr = false; while (!hdr.empty() && hdr.back() == '\r') hdr.pop_back(); start_seq(hdr); hdr.clear(); }
+					if (ch == '\n') { in_hdr = false; anns.push_back(fa_ann_of_header(hdr, l_pac)); lasts = 0; hdr.clear(); }
 					else hdr.push_back(ch);
 					continue;
 				}
 				if (ch == '>') { in_hdr = true; continue; }
 				if (ch == '\n' || ch == '\r' || ch == ' ' || ch == '\t') continue;
 				if (anns.empty()) { fclose(f); return "FASTA does not start with '>'"; }
-				Ann &a = anns.back();
+				FaAnn &a = anns.back();
 				int c = kNt4[(unsigned char)ch];
 				if (c >= 4) { // runs of the same ambiguous character form one hole (bntseq.c:245-259)
 					if (lasts == ch) ++ambs.back().len;
-					else { ambs.push_back(Amb{a.offset + a.len, 1, ch}); ++a.n_ambs; }
+					else { ambs.push_back(FaAmb{a.offset + a.len, 1, ch}); ++a.n_ambs; }
 					c = rng.lrand() & 3;
 				}
 				lasts = ch;
@@ -229,36 +270,26 @@ inline std::string build_index(const std::string &fasta, const std::string &pref
 		fclose(f);
 	}
 	if (l_pac == 0) return "empty FASTA";
-	if (stats) { stats->l_pac = l_pac; stats->n_seqs = (int)anns.size(); stats->n_holes = (int)ambs.size(); }
+	const double t_packed = fa_now_s();
+	if (stats) { stats->l_pac = l_pac; stats->n_seqs = (int)anns.size(); stats->n_holes = (int)ambs.size(); stats->secs_pack = t_packed - t_start; }
 	// .pac: forward strand only, (l_pac/4 + 1 + 1) bytes; the last byte is l_pac % 4 (bntseq.c:306-319)
 	{
 		FILE *o = fopen((prefix + ".pac").c_str(), "wb");
 		if (!o) return "cannot write " + prefix + ".pac";
 		fwrite(pac.data(), 1, pac.size(), o);
-		uint8_t ct = 0;
-		if (l_pac % 4 == 0) fwrite(&ct, 1, 1, o);
-		ct = (uint8_t)(l_pac % 4);
-		fwrite(&ct, 1, 1, o);
+		fa_write_pac_end(o, l_pac);
 		fclose(o);
 	}
 	{
-		FILE *o = fopen((prefix + ".ann").c_str(), "w");
-		if (!o) return "cannot write " + prefix + ".ann";
-		fprintf(o, "%lld %d %u\n", (long long)l_pac, (int)anns.size(), 11u);
-		for (auto &a : anns) {
-			fprintf(o, "%d %s", 0, a.name.c_str());
-			if (!a.anno.empty()) fprintf(o, " %s\n", a.anno.c_str()); else fprintf(o, "\n");
-			fprintf(o, "%lld %d %d\n", (long long)a.offset, a.len, a.n_ambs);
-		}
-		fclose(o);
-		o = fopen((prefix + ".amb").c_str(), "w");
-		if (!o) return "cannot write " + prefix + ".amb";
-		fprintf(o, "%lld %d %u\n", (long long)l_pac, (int)anns.size(), (unsigned)ambs.size());
-		for (auto &h : ambs) fprintf(o, "%lld %d %c\n", (long long)h.offset, h.len, h.amb);
-		fclose(o);
+		const std::string e = fa_write_ann_amb(prefix, "", l_pac, anns, ambs);
+		if (!e.empty()) return e;
 	}
+	const double t_written = fa_now_s();
+	if (stats) stats->secs_write = t_written - t_packed;
 	pac.resize(pac.size() + 16, 0); // readers below may look a few bytes past the end
-	return bwt_sa(pac.data(), pac.size() - 16, l_pac, cnt_fwd, prefix);
+	const std::string e = bwt_sa(pac.data(), pac.size() - 16, l_pac, cnt_fwd, prefix);
+	if (stats) stats->secs_sa = fa_now_s() - t_written;
+	return e;
 }
 
 } // namespace arx

@@ -56,6 +56,35 @@ typedef struct { int64_t rbeg; int32_t qbeg, len; } arx_seed;                   
  * in HBM when a HIP device is visible (any genome size the HBM holds: GRCh38 in ~10 s) and by a 32-bit host sorter otherwise (2 * l_pac < 2^31;
  * ARX_INDEX_HOST=1 forces it, ARX_INDEX_DEVICE=k picks the device) -- same bytes either way.  msg (may be NULL) receives the error text. */
 int arx_index_build(const char *fasta, const char *prefix, char *msg, int32_t msg_cap);
+/* Where the calling thread's last arx_index_build spent its time, in seconds: secs[0] the FASTA loop (parse and pack), secs[1] writing .pac,
+ * .ann and .amb, secs[2] the suffix sort with .bwt and .sa.  Timing only; a call that failed leaves what it reached. */
+int arx_index_build_times(double *secs);
+
+/* The same five files, the FASTA read and packed on the GPU (replaces the host loop of bns_fasta2bntseq, bntseq.c:227-328; dev_fapack.h,
+ * hip_fapack.h).  The FASTA may be plain text, ordinary gzip (both through zlib on a reader thread) or BGZF (read as it is and inflated on the
+ * device), as the reference's gzopen takes them.  The packed forward strand, the contig table and the hole table are made on `device` window by
+ * window and the suffix sorter takes the strand where it lies.  The bytes are arx_index_build's for the plain-text form of the same FASTA.
+ *   flags   ARX_INDEX_PACK_ONLY: .pac, .ann and .amb only.  Unknown bits: ARX_E_ARG.
+ *   stats   (may be NULL) ARX_INDEX_N_STATS values: [0] l_pac  [1] contigs  [2] holes  [3] ambiguous bases  [4] text bytes  [5] compressed bytes
+ *           read (the file's size)  [6] windows; microseconds: [7] waiting for the reader  [8] upload + inflate  [9] pack  [10] .pac fetch + write
+ *           [11] .ann / .amb  [12] suffix sort + .bwt / .sa  [13] total.
+ * Every file is written as <file>.tmp and renamed when all are complete; a failing call leaves nothing.  There is no CPU fallback: no such
+ * device is ARX_E_DEVICE with a text.  ARX_E_ARG: null paths, unknown flags; ARX_E_IO: the FASTA cannot be read, a BGZF block does not
+ * inflate, zlib reports an error (a truncated gzip stream), a file cannot be written; ARX_E_OPEN, with arx_index_build's texts: a base
+ * before the first '>', no base at all; ARX_E_TOO_LARGE: a contig of more than 2^31 - 1 bases, more than 2^31 - 1 contigs or holes (the host
+ * loop overflows silently there), or buffers the device does not hold.  msg (may be NULL) receives the text. */
+enum { ARX_INDEX_PACK_ONLY = 1 };
+enum { ARX_INDEX_N_STATS = 14 };
+int arx_index_build_ex(int32_t device, const char *fasta, const char *prefix, int32_t flags, int64_t *stats, char *msg, int32_t msg_cap);
+
+/* The pack of arx_index_build_ex on a text in host memory, in windows of window_bytes (0: the default, 2^24; otherwise at least 64 and at
+ * most 2^24, ARX_E_ARG outside).  pac[pac_cap] receives the packed bases, (l_pac + 3) / 4 bytes (n / 4 + 1 always suffice);
+ * out[0] = l_pac, out[1] = contigs, out[2] = holes, out[3] = ambiguous bases, out[4..7] = cnt_fwd, out[8] = windows; contig_rows: five values
+ * per contig (header text [begin, end) in the text, '\r's included; offset; length; holes), contig_cap rows; hole_rows: three per hole (offset,
+ * length, byte), hole_cap rows.  A cap that is too small is ARX_E_TOO_LARGE and nothing is written.  Returns ARX_OK; ARX_E_OPEN for what
+ * arx_index_build refuses (out[9] = 1: a base before the first '>', 2: no base); ARX_E_DEVICE without the GPU. */
+int arx_selftest_fasta_pack(int32_t device, const uint8_t *text, int64_t n, int64_t window_bytes, uint8_t *pac, int64_t pac_cap, int64_t *out,
+                            int64_t *contig_rows, int64_t contig_cap, int64_t *hole_rows, int64_t hole_cap);
 
 /* Loads <prefix>.{bwt,sa,pac,ann,amb,alt} (files written by `bwa index`) into HBM of `device`; derives there, once, what the kernels use
  * beside the files' content: the Occ blocks re-packed for one popcount per count; the k-mer tables of the seeding passes (ARX_KMER_K /
