@@ -113,6 +113,8 @@ def _load(path):
         lib.arx_feeder_open_device_ex.argtypes = [vp, C.c_char_p, C.c_char_p, i64, i32, i32, C.POINTER(vp), C.c_char_p, i32]
     lib.arx_feeder_device_reads.argtypes = [vp, vp, vp, vp]
     lib.arx_feeder_stats.argtypes = [vp, vp]
+    if hasattr(lib, "arx_feeder_gunzip_stats"):        # (a library built before the gzip arm: Feeder(gunzip="device") says so)
+        lib.arx_feeder_gunzip_stats.argtypes = [vp, vp]
     lib.arx_bam_open.argtypes = [C.c_char_p, i32, vp, vp, C.c_char_p, i32, i32, C.POINTER(vp), C.c_char_p, i32]
     lib.arx_bam_write.argtypes = [vp, vp]
     lib.arx_bam_close.argtypes = [vp, vp]
@@ -1356,23 +1358,35 @@ class Feeder:
     super-batches are byte for byte the host feeder's.  chunk_bytes: bytes of each file's inflated stream per chunk (0: the default);
     depth: the arrays of call k stay valid until call k + depth returns (next_raw's views and device_reads).
     inflate="device" (device feeder only; arx_feeder_open_device_ex with ARX_FEEDER_INFLATE_DEVICE): a file that is BGZF is inflated by a
-    HIP kernel instead of zlib on its reader thread; "host" (the default): zlib for every file."""
+    HIP kernel instead of zlib on its reader thread; "host" (the default): zlib for every file.
+    gunzip="device" (device feeder only; ARX_FEEDER_GUNZIP_DEVICE): a file that is ordinary gzip is inflated on the GPU in chunks, both files'
+    launches in flight together; "host" (the default): zlib on its reader thread.  gunzip_stats() says what the device took."""
 
     INFLATE_DEVICE = 1           # ARX_FEEDER_INFLATE_DEVICE
+    GUNZIP_DEVICE = 8            # ARX_FEEDER_GUNZIP_DEVICE
 
-    def __init__(self, r1: str, r2: str, lib_path: str = LIB_PATH, device: "Reference | None" = None, chunk_bytes: int = 0, depth: int = 1, inflate: str = "host"):
+    def __init__(self, r1: str, r2: str, lib_path: str = LIB_PATH, device: "Reference | None" = None, chunk_bytes: int = 0, depth: int = 1, inflate: str = "host",
+                 gunzip: str = "host"):
         self.h = C.c_void_p()
         msg = C.create_string_buffer(512)
         self.device = device
+        self.gunzip = gunzip
         if inflate not in ("host", "device"):
             raise ValueError("inflate is 'host' or 'device'")
+        if gunzip not in ("host", "device"):
+            raise ValueError("gunzip is 'host' or 'device'")
         if inflate == "device" and device is None:
             raise ValueError("inflate='device' needs the device feeder (device=<Reference>): the host feeder inflates with zlib")
-        if device is not None and inflate == "device":
+        if gunzip == "device" and device is None:
+            raise ValueError("gunzip='device' needs the device feeder (device=<Reference>): the host feeder inflates with zlib")
+        flags = (self.INFLATE_DEVICE if inflate == "device" else 0) | (self.GUNZIP_DEVICE if gunzip == "device" else 0)
+        if device is not None and flags:
             self.lib = device.lib
             if not hasattr(self.lib, "arx_feeder_open_device_ex"):
-                raise ArachneError("inflate='device': this library has no arx_feeder_open_device_ex (rebuild it)")
-            rc = self.lib.arx_feeder_open_device_ex(device.h, r1.encode(), r2.encode(), int(chunk_bytes), int(depth), self.INFLATE_DEVICE, C.byref(self.h), msg, 512)
+                raise ArachneError("%s='device': this library has no arx_feeder_open_device_ex (rebuild it)" % ("inflate" if inflate == "device" else "gunzip"))
+            if gunzip == "device" and not hasattr(self.lib, "arx_feeder_gunzip_stats"):
+                raise ArachneError("gunzip='device': this library has no ARX_FEEDER_GUNZIP_DEVICE (rebuild it)")
+            rc = self.lib.arx_feeder_open_device_ex(device.h, r1.encode(), r2.encode(), int(chunk_bytes), int(depth), flags, C.byref(self.h), msg, 512)
             if rc != 0:
                 raise ArachneError("arx_feeder_open_device_ex: " + msg.value.decode())
             return
@@ -1398,6 +1412,17 @@ class Feeder:
         if self.lib.arx_feeder_stats(self.h, st) != 0:
             raise ArachneError("arx_feeder_stats: not a device feeder")
         return dict(chunks=st[0], bytes=st[1], records=st[2], bad_lines=st[3], runs=st[4], fallback_chunks=st[5], device_blocks=st[6], compressed_bytes=st[7])
+
+    def gunzip_stats(self):
+        """arx_feeder_gunzip_stats of a device feeder -> (R1's, R2's) dicts under the names of GUNZIP_STATS, as far as the reading has come;
+        all zeros for a file the device was not given"""
+        if not hasattr(self.lib, "arx_feeder_gunzip_stats"):
+            raise ArachneError("this library has no arx_feeder_gunzip_stats (rebuild it)")
+        n = len(GUNZIP_STATS)
+        st = (C.c_int64 * (2 * n))()
+        if self.lib.arx_feeder_gunzip_stats(self.h, st) != 0:
+            raise ArachneError("arx_feeder_gunzip_stats: not a device feeder")
+        return tuple({k: int(st[f * n + i]) for i, k in enumerate(GUNZIP_STATS)} for f in range(2))
 
     def next(self, target_pairs: int):
         """-> dict (numpy copies) or None at the end of the input"""

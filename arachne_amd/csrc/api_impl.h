@@ -696,7 +696,7 @@ template <class RT> struct Batch {
 		int rc = ARX_OK;                                                                                                               \
 		if (!c || !r1 || !r2 || depth < 1 || depth > 64 || chunk_bytes < 0 || chunk_bytes > (int64_t)arx::DeviceFeeder<RT>::MAX_CHUNK) {\
 			e = "arx_feeder_open_device: 1 <= depth <= 64 and 0 <= chunk_bytes <= 2^28"; rc = ARX_E_ARG;                                  \
-		} else if (flags & ~ARX_FEEDER_INFLATE_DEVICE) {                                                                               \
+		} else if (flags & ~(ARX_FEEDER_INFLATE_DEVICE | ARX_FEEDER_GUNZIP_DEVICE)) {                                                  \
 			e = "arx_feeder_open_device_ex: unknown flag bits"; rc = ARX_E_ARG;                                                           \
 		} else try {                                                                                                                   \
 			f = new arx::DeviceFeeder<RT>(c->device, (size_t)chunk_bytes, depth, flags);                                                  \

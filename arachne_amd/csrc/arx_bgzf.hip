@@ -48,6 +48,42 @@ void inflate_launch(hipStream_t stream, const uint8_t *d_src, int64_t src_bytes,
 	hip_launch("k_bgzf_inflate", k_bgzf_inflate, dim3(n_blocks), dim3(INF_LANES), INF_LDS_BYTES, stream, d_src, src_bytes, d_rows, n_blocks, d_out, out_bytes, d_status, d_counts);
 }
 
+// The device feeder's backend for a gzip file (device_feeder.h declares these and calls them from arx_api.hip): a GzHip on a stream of its own,
+// so that R1's and R2's launches run side by side.  The calling thread's device is the feeder's
+struct GzFeedDev {
+	Stream st; // declared before the backend: its buffers are freed first, behind the wait of gz_feed_close
+	GzHip dev;
+};
+GzFeedDev *gz_feed_open()
+{
+	std::unique_ptr<GzFeedDev> d(new GzFeedDev());
+	d->st.create();
+	d->dev.init(d->st);
+	return d.release();
+}
+void gz_feed_close(GzFeedDev *d)
+{
+	if (!d) return;
+	(void)hipStreamSynchronize(d->st);
+	delete d;
+}
+void gz_feed_decode_begin(GzFeedDev *d, const uint8_t *src, int clen, int start_bit, const uint8_t *window, int have, int chunk_bytes, int expand)
+{
+	d->dev.decode_begin(src, clen, start_bit, window, have, chunk_bytes, expand);
+}
+void gz_feed_decode_end(GzFeedDev *d, GzLaunch &L) { d->dev.decode_end(L); }
+void gz_feed_resolve_begin(GzFeedDev *d, GzLaunch &L, uint8_t *text, hipStream_t after) { d->dev.resolve_begin(L, text, after); }
+void gz_feed_resolve_end(GzFeedDev *d, GzLaunch &L) { d->dev.resolve_end(L); }
+// a piece of the host's to its place behind the carry: behind what the feeder's stream holds for the window, and waited for
+void gz_feed_upload(GzFeedDev *d, uint8_t *dst, const uint8_t *host, size_t bytes, hipStream_t after)
+{
+	if (!bytes) return;
+	Event made(hipEventDisableTiming);
+	ARX_HIP_CHECK(hipEventRecord(made, after));
+	ARX_HIP_CHECK(hipStreamWaitEvent(d->st, made, 0));
+	d->dev.upload(dst, host, bytes);
+}
+
 } // namespace arx
 
 extern "C" int arx_bam_open_device(arx_ctx *ctx, const char *path, int32_t n_contigs, const char *const *names, const int32_t *lens, const char *extra_header,

@@ -45,4 +45,6 @@ int arx_feeder_device_reads(arx_feeder *h, const uint8_t **d_bases, const int32_
 
 int arx_feeder_stats(arx_feeder *h, int64_t *stats) { return h && stats ? ((arx::FeederBase *)h)->stats(stats) : ARX_E_ARG; }
 
+int arx_feeder_gunzip_stats(arx_feeder *h, int64_t *stats) { return h && stats ? ((arx::FeederBase *)h)->gunzip_stats(stats) : ARX_E_ARG; }
+
 }

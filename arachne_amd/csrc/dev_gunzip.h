@@ -110,7 +110,9 @@ ARX_DEVI bool gz_cheap(const uint8_t *ring, int pos, int clen)
 	return kraft == 128;
 }
 
-// the first bit of [lo, hi) at which a non-final dynamic block passes inf_header and inf_codes; -1: none
+// The first bit of [lo, hi) at which a non-final dynamic block passes inf_header and inf_codes; -1: none.  The reference form of the search: 64
+// consecutive positions a round through gz_cheap, the survivors of a round one at a time.  gz_chunk_find calls gz_find_runs below, which gives
+// the same position by definition (tests/gzfindsim holds the two together on every chunk's range)
 template <class Drv> ARX_DEV int gz_find(Drv &drv, GzWork &w, const uint8_t *src, int clen, int lo, int hi)
 {
 	InfWork &f = w.inf;
@@ -145,6 +147,76 @@ template <class Drv> ARX_DEV int gz_find(Drv &drv, GzWork &w, const uint8_t *src
 				if (sh[IS_STATUS] == INF_OK && sh[IS_BTYPE] == 2 && sh[IS_FINAL] == 0) return round + pick;
 				from = pick + 1;
 			}
+		}
+	}
+	return -1;
+}
+
+// ---- the same search with a prefilter in front.  A lane takes a run of GZ_RUN consecutive bit positions of the piece in the ring: it reads the
+// run's words once, one 32-bit word per 32 positions (the run may start at any bit; a position looks 12 bits ahead), and tests every position in
+// registers against the header fields that need no table -- BFINAL 0, BTYPE 2, HLIT <= 29, HDIST <= 29: the first 13 bits, which one position in
+// nine passes -- and only a position that passes goes on to gz_cheap's Kraft sum.  What a lane hands on is its first survivor, one word per lane;
+// the runs ascend with the lanes, so the least of them is the first survivor of the piece, and one hand-off per piece replaces 256 rounds with
+// two each.  The survivors then go to inf_header / inf_codes in ascending order as before; after a refuted one only its lane scans again, from
+// the next position (the ring then holds the stream from the refuted position on, which covers the rest of the piece).
+constexpr int GZ_RUN = 8 * GZ_PIECE / INF_LANES; // 256 positions
+constexpr int GZ_NONE = 0x7FFFFFFF;
+static_assert(GZ_RUN * INF_LANES == 8 * GZ_PIECE && GZ_RUN % 32 == 0, "the lanes' runs tile a piece");
+// one lane: the first position of [lo, hi) that passes the prefilter and gz_cheap; hi - lo <= GZ_RUN.  GZ_NONE: none
+ARX_DEVI int gz_scan(const uint8_t *ring, int lo, int hi, int clen)
+{
+	if (lo >= hi) return GZ_NONE;
+	const uint32_t *r = (const uint32_t *)ring;
+	int wpos = lo >> 5;
+	uint64_t buf = (uint64_t)r[wpos & (INF_RING / 4 - 1)] | (uint64_t)r[(wpos + 1) & (INF_RING / 4 - 1)] << 32;
+	int found = GZ_NONE;
+	for (int p0 = 32 * wpos; p0 < hi && found == GZ_NONE; p0 += 32) { // a word of positions at a time, 12 bits of the next word behind them
+		for (int b = 0; b < 32; ++b) {
+			const int p = p0 + b;
+			const uint32_t v = (uint32_t)(buf >> b);
+			if (p < lo || p >= hi || found != GZ_NONE || (v & 7u) != 4u || ((v >> 3) & 31u) > 29u || ((v >> 8) & 31u) > 29u) continue;
+			if (gz_cheap(ring, p, clen)) found = p;
+		}
+		++wpos;
+		buf = buf >> 32 | (uint64_t)r[(wpos + 1) & (INF_RING / 4 - 1)] << 32;
+	}
+	return found;
+}
+template <class Drv> ARX_DEV int gz_find_runs(Drv &drv, GzWork &w, const uint8_t *src, int clen, int lo, int hi)
+{
+	InfWork &f = w.inf;
+	int32_t *sh = f.sh;
+	int32_t *first = (int32_t *)f.crc_part; // INF_LANES words the search has no other use for: each lane's first survivor
+	for (int piece = lo; piece < hi; piece += 8 * GZ_PIECE) {
+		const int piece_end = piece + 8 * GZ_PIECE < hi ? piece + 8 * GZ_PIECE : hi;
+		drv.lanes([&](int lane) { if (lane == 0) { sh[IS_BITPOS] = piece; sh[IS_HI] = 0; } });
+		drv.lanes([&](int lane) { inf_fill(f, src, clen, lane); });
+		drv.lanes([&](int lane) {
+			const int a = piece + GZ_RUN * lane, b = a + GZ_RUN < piece_end ? a + GZ_RUN : piece_end;
+			first[lane] = gz_scan(f.ring, a, b, clen);
+		});
+		for (int tries = 0; tries <= 8 * GZ_PIECE; ++tries) { // every refuted survivor moves its lane's entry forward
+			drv.lanes([&](int lane) {
+				if (lane != 0) return;
+				int least = GZ_NONE;
+				for (int l = 0; l < INF_LANES; ++l) if (first[l] < least) least = first[l];
+				w.gs[GS_PICK] = least;
+			});
+			const int pick = w.gs[GS_PICK];
+			if (pick == GZ_NONE) break;
+			drv.lanes([&](int lane) { if (lane == 0) { sh[IS_BITPOS] = pick; sh[IS_HI] = 0; sh[IS_STATUS] = INF_OK; sh[IS_OUTPOS] = 0; } });
+			drv.lanes([&](int lane) { inf_fill(f, src, clen, lane); });
+			drv.lanes([&](int lane) {
+				if (lane != 0) return;
+				inf_header(f, clen, 0);
+				if (sh[IS_STATUS] == INF_OK && sh[IS_BTYPE] == 2 && sh[IS_FINAL] == 0) inf_codes(f);
+			});
+			if (sh[IS_STATUS] == INF_OK && sh[IS_BTYPE] == 2 && sh[IS_FINAL] == 0) return pick;
+			drv.lanes([&](int lane) { // the ring holds the stream from the refuted position on: the rest of its lane's run lies in it
+				if (first[lane] != pick) return;
+				const int a = piece + GZ_RUN * lane, b = a + GZ_RUN < piece_end ? a + GZ_RUN : piece_end;
+				first[lane] = gz_scan(f.ring, pick + 1, b, clen);
+			});
 		}
 	}
 	return -1;
@@ -228,7 +300,7 @@ template <class Drv> ARX_DEV void gz_decode(Drv &drv, GzWork &w, const uint8_t *
 template <class Drv> ARX_DEV void gz_chunk_find(Drv &drv, GzWork &w, const uint8_t *src, int clen, int chunk_bytes, int start_bit, int k, GzChunk &c)
 {
 	const int64_t lo = 8 * (int64_t)k * chunk_bytes, hi = lo + 8 * (int64_t)chunk_bytes < 8 * (int64_t)clen ? lo + 8 * (int64_t)chunk_bytes : 8 * (int64_t)clen;
-	c.cand = k == 0 ? start_bit : gz_find(drv, w, src, clen, (int)lo, (int)hi);
+	c.cand = k == 0 ? start_bit : gz_find_runs(drv, w, src, clen, (int)lo, (int)hi);
 	c.next = 0; c.end_bit = c.cand; c.count = 0; c.status = GZ_NO_CANDIDATE; c.inf = 0; c.flags = 0; c.blocks = 0; c.order = -1; c.bad_markers = 0; c.crc = 0; c.markers = 0; c.have = 0; c.pad = 0;
 	c.stage_off = c.stage_cap = c.text_off = 0;
 }

@@ -4,6 +4,8 @@
 //   two reader threads (feeder.h)        ChunkReader: inflate R1 and R2 side by side into page-locked buffers, chunk by chunk; or, for a
 //                                         BGZF file of a feeder opened with ARX_FEEDER_INFLATE_DEVICE, BgzfChunkReader: whole blocks as
 //                                         they are in the file, with one table row per block
+//                                         or, for an ordinary gzip file of a feeder opened with ARX_FEEDER_GUNZIP_DEVICE, GzipRawReader: the
+//                                         next bytes of the file as they are, which a GzReader (gunzip_host.h) takes a launch at a time
 //   step()                                uploads what both readers have; a BGZF slab's blocks are inflated on the device (dev_inflate.h),
 //                                         straight into the window behind the carry, so that the parse sees text either way
 //   parse_window()                        uploads what both readers have, runs dev_fastq.h's functors on the raw text (line index, record
@@ -16,6 +18,18 @@
 // so every parse starts in the search state).  What the host waits for per parse, whatever the number of chunks it takes in: the upload,
 // the two line counts, the record count, the output sizes and the output blob (each of the three scans is two waits inside the runtime).
 //
+// Ordinary gzip on the device (ARX_FEEDER_GUNZIP_DEVICE).  Each such file has a GzReader over its raw slabs and a backend with a stream of its
+// own; a piece of text is what one launch accepts, resolved straight into the window behind the carry, and a file is asked for pieces while
+// its window holds less than chunk_bytes.  step() enqueues find / decode / windows of every file that wants a piece before it waits for any
+// (GzReader::begin), makes room for the texts, enqueues the resolves (place_begin), waits, and parses.  Whatever the device does not take
+// is the host's inside GzReader (zlib), as in the file calls; where the reader reports an error the input ends there like at a read error.
+// A piece that has entered a parse cannot be taken back: can_rewind stays false, a member whose trailer does not match is an error.
+//   The compressed bytes per launch (the slab): a launch runs one wavefront per 32 KiB chunk, so the slab is as large as chunk_bytes lets it
+// be -- chunk_bytes itself, at least two chunks, at most GZ_SLAB_DEFAULT (8 MiB) and gunzip_host.h's other bounds.  At FASTQ's usual ratio a
+// piece is then three to four times chunk_bytes of text, which the window takes (its 2^30 check applies as before).  No value of the slab or
+// of the chunk has been measured through the feeder.  ARX_FEEDER_GUNZIP_CHUNK / ARX_FEEDER_GUNZIP_SLAB set the two (tests: many chunks and
+// launches in a small file); values outside arx_selftest_gunzip's bounds are refused at open.
+//
 // Compiled for the GPU into arx_api.hip and, with the sequential runtime, into the host test double: the same code either way.
 #pragma once
 #include <chrono>
@@ -27,6 +41,7 @@
 #include "feeder.h"
 #include "dev_fastq.h"
 #include "switches.h"
+#include "gunzip_host.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -66,11 +81,123 @@ template <class RT> inline void inflate_rows(RT &, const uint8_t *src, int64_t s
 }
 #endif
 
+// The backend of a gzip file's GzReader, in the halves gunzip_host.h describes.  With the HIP runtime: hip_gunzip.h's GzHip on a stream of its
+// own, behind functions that arx_bgzf.hip defines next to the kernels (as inflate_launch); `after` is the feeder's stream, on which the
+// window is made and parsed.  With the sequential runtime of the host test double: dev_gunzip.h's functions with lanes and chunks in a loop.
+#if defined(__HIPCC__)
+struct GzFeedDev;
+GzFeedDev *gz_feed_open();
+void gz_feed_close(GzFeedDev *d);
+void gz_feed_decode_begin(GzFeedDev *d, const uint8_t *src, int clen, int start_bit, const uint8_t *window, int have, int chunk_bytes, int expand);
+void gz_feed_decode_end(GzFeedDev *d, GzLaunch &L);
+void gz_feed_resolve_begin(GzFeedDev *d, GzLaunch &L, uint8_t *text, hipStream_t after);
+void gz_feed_resolve_end(GzFeedDev *d, GzLaunch &L);
+void gz_feed_upload(GzFeedDev *d, uint8_t *dst, const uint8_t *host, size_t bytes, hipStream_t after);
+struct GzFeed {
+	GzFeedDev *d = nullptr;
+	hipStream_t after = nullptr;
+	template <class RT> void open(RT &rt) { d = gz_feed_open(); after = rt.stream; }
+	void close() { if (d) gz_feed_close(d); d = nullptr; }
+	void decode_begin(const uint8_t *src, int clen, int start_bit, const uint8_t *window, int have, int chunk_bytes, int expand) { gz_feed_decode_begin(d, src, clen, start_bit, window, have, chunk_bytes, expand); }
+	void decode_end(GzLaunch &L) { gz_feed_decode_end(d, L); }
+	// Two orderings that no test on a sequential double can see, both kept by events inside gz_feed_resolve_begin (GzHip::resolve_begin):
+	// (i) the window may have been reallocated and copied on the feeder's stream (ensure_keep) just before: the resolve on the file's stream
+	// waits for an event recorded on the feeder's stream; (ii) the feeder's stream waits for the event behind the resolve, so the parse that
+	// is enqueued on it next starts only after both files' resolves (step() has also waited for both on the host by then)
+	void resolve_begin(GzLaunch &L, uint8_t *text) { gz_feed_resolve_begin(d, L, text, after); }
+	void resolve_end(GzLaunch &L) { gz_feed_resolve_end(d, L); }
+	void decode(const uint8_t *src, int clen, int start_bit, const uint8_t *window, int have, int chunk_bytes, int expand, GzLaunch &L) { decode_begin(src, clen, start_bit, window, have, chunk_bytes, expand); decode_end(L); }
+	void resolve(GzLaunch &L, uint8_t *text) { resolve_begin(L, text); resolve_end(L); }
+	void upload(uint8_t *dst, const uint8_t *host, size_t bytes) { gz_feed_upload(d, dst, host, bytes, after); }
+};
+#else
+struct GzFeed {
+	std::vector<uint16_t> stage;
+	std::vector<uint8_t> windows, src_;
+	std::vector<GzChunk> chunks;
+	GzChain chain;
+	template <class RT> void open(RT &) {}
+	void close() {}
+	void decode_begin(const uint8_t *src, int clen, int start_bit, const uint8_t *window, int have, int chunk_bytes, int expand)
+	{
+		const int n = (int)(((int64_t)clen + chunk_bytes - 1) / chunk_bytes);
+		src_.assign(src, src + clen);
+		stage.assign((size_t)gz_stage_at(8 * (int64_t)clen, expand), 0);
+		windows.assign((size_t)(n + 1) * GZ_WIN, 0);
+		memcpy(windows.data(), window, GZ_WIN);
+		std::vector<uint32_t> mem(GZ_WORK_BYTES / 4);
+		chunks.assign((size_t)n, GzChunk());
+		InfLoopDrv drv;
+		GzWork w;
+		gz_carve(w, (uint8_t *)mem.data());
+		for (int k = 0; k < n; ++k) gz_chunk_find(drv, w, src_.data(), clen, chunk_bytes, start_bit, k, chunks[(size_t)k]);
+		for (int k = 0; k < n; ++k) gz_chunk_decode(drv, w, src_.data(), clen, expand, k, n, chunks.data(), stage.data());
+		gz_chain(chunks.data(), n, have, chain);
+		for (int m = 0, k = 0; m < chain.n_accepted; ++m) {
+			GzChunk &c = chunks[(size_t)k];
+			if (c.have < GZ_WIN) for (int64_t i = 0; i < c.count; ++i) c.bad_markers += gz_bad_marker_at(stage.data() + c.stage_off, c.have, i);
+			for (int i = 0; i < GZ_WIN; ++i) gz_window_at(windows.data() + (size_t)m * GZ_WIN, windows.data() + (size_t)(m + 1) * GZ_WIN, stage.data() + c.stage_off, c.count, i);
+			k = c.next;
+		}
+	}
+	void decode_end(GzLaunch &L)
+	{
+		L.chunks = chunks; L.chain = chain;
+		for (double &u : L.us) u = 0;
+	}
+	void resolve_begin(GzLaunch &L, uint8_t *text)
+	{
+		uint32_t crc_tab[256], x2n[32];
+		for (int lane = 0; lane < 64; ++lane) gz_crc_tables(crc_tab, x2n, lane, 64);
+		for (GzChunk &c : L.chunks) {
+			if (!(c.flags & GZ_F_ACCEPTED)) continue;
+			uint8_t *out = text + c.text_off;
+			for (int64_t i = 0; i < c.count; ++i) c.markers += gz_resolve_at(windows.data() + (size_t)c.order * GZ_WIN, stage.data() + c.stage_off, out, i);
+			c.crc = 0;
+			for (int t = 0; t < 256; ++t) c.crc ^= gz_crc_part(crc_tab, x2n, out, c.count, t, 256);
+		}
+	}
+	void resolve_end(GzLaunch &L) { memcpy(L.window, windows.data() + (size_t)L.chain.n_accepted * GZ_WIN, GZ_WIN); }
+	void decode(const uint8_t *src, int clen, int start_bit, const uint8_t *window, int have, int chunk_bytes, int expand, GzLaunch &L) { decode_begin(src, clen, start_bit, window, have, chunk_bytes, expand); decode_end(L); }
+	void resolve(GzLaunch &L, uint8_t *text) { resolve_begin(L, text); resolve_end(L); }
+	void upload(uint8_t *dst, const uint8_t *host, size_t bytes) { if (bytes) memcpy(dst, host, bytes); }
+};
+#endif
+
+// a gzip file's raw slabs as the compressed bytes of its GzReader (hip_fqsort.h's FsGzSlabs, for the feeder's two translation units)
+struct FeederGzSlabs : GzSource {
+	SlabReader *rd = nullptr;
+	const SlabReader::Slab *s = nullptr;
+	size_t at = 0;
+	bool err = false, ended = false;
+	size_t read(uint8_t *to, size_t n) override
+	{
+		size_t got = 0;
+		while (got < n && !ended) {
+			if (!s) {
+				s = rd->acquire();
+				at = 0;
+				if (!s || s->err) { err = s != nullptr; ended = true; break; }
+			}
+			const size_t k = n - got < s->len - at ? n - got : s->len - at;
+			if (k) memcpy(to + got, s->buf + at, k);
+			at += k; got += k;
+			if (at == s->len) {
+				if (s->eof) ended = true;
+				rd->release();
+				s = nullptr;
+			}
+		}
+		return got;
+	}
+};
+
 template <class RT> class DeviceFeeder : public FeederBase {
 public:
 	static constexpr size_t DEFAULT_CHUNK = (size_t)8 << 20, MAX_CHUNK = (size_t)256 << 20, SLAB_TARGET = (size_t)8 << 20;
 
-	// flags: ARX_FEEDER_INFLATE_DEVICE -- a file that is BGZF is read as it is and inflated on the device
+	// flags: ARX_FEEDER_INFLATE_DEVICE -- a file that is BGZF is read as it is and inflated on the device; ARX_FEEDER_GUNZIP_DEVICE -- a file that
+	// is ordinary gzip is (a BGZF file goes as without this flag: hip_fqsort.h's FsInput::open has the same rule)
 	DeviceFeeder(int device, size_t chunk_bytes, int depth, int flags = 0) : device_(device), flags_(flags), chunk_(chunk_bytes ? chunk_bytes : DEFAULT_CHUNK), slots_((size_t)depth + 2) {}
 
 	// ARX_OK, ARX_E_IO (a file cannot be opened) or ARX_E_DEVICE (no GPU); `error` says which
@@ -82,10 +209,26 @@ public:
 		per = per < 1 ? 1 : per > 64 ? 64 : per;
 		if (sw_.parse_chunks) { const long v = *sw_.parse_chunks; if (v >= 1 && (size_t)v * chunk_ <= MAX_CHUNK) per = (size_t)v; }
 		const char *path[2] = {r1, r2};
+		// the gzip inflate's sizes (the rule is at the top of the file), inside arx_selftest_gunzip's bounds
+		const int64_t gchunk = sw_.gunzip_chunk ? (int64_t)*sw_.gunzip_chunk : GZ_CHUNK_DEFAULT;
+		int64_t gslab = (int64_t)chunk_ < 2 * gchunk ? 2 * gchunk : (int64_t)chunk_;
+		if (gslab > GZ_SLAB_DEFAULT) gslab = GZ_SLAB_DEFAULT < 2 * gchunk ? 2 * gchunk : GZ_SLAB_DEFAULT;
+		if (gslab > GZ_MAX_CHUNKS * gchunk) gslab = GZ_MAX_CHUNKS * gchunk;
+		if (sw_.gunzip_slab) gslab = (int64_t)*sw_.gunzip_slab;
+		if ((flags_ & ARX_FEEDER_GUNZIP_DEVICE) && (gchunk < GZ_MIN_CHUNK || gchunk > GZ_MAX_SLAB / 2 || gslab < 2 * gchunk || gslab > GZ_MAX_SLAB || gslab > GZ_MAX_CHUNKS * gchunk ||
+		                                            gslab * GZ_EXPAND_DEFAULT > GZ_MAX_SYMBOLS)) {
+			error = "ARX_FEEDER_GUNZIP_CHUNK / ARX_FEEDER_GUNZIP_SLAB outside the bounds of the gzip inflate";
+			return ARX_E_ARG;
+		}
 		for (int f = 0; f < 2; ++f) { // each file by its own first bytes: R1 may be BGZF where R2 is ordinary gzip or plain text
 			bool ok;
-			bgzf_[f] = (flags_ & ARX_FEEDER_INFLATE_DEVICE) && file_is_bgzf(path[f]);
-			if (bgzf_[f]) { std::unique_ptr<BgzfChunkReader> r(new BgzfChunkReader()); ok = r->open(path[f], chunk_, per); rd_[f] = std::move(r); }
+			const bool is_bgzf = file_is_bgzf(path[f]);
+			bgzf_[f] = (flags_ & ARX_FEEDER_INFLATE_DEVICE) && is_bgzf;
+			const bool gunzip = (flags_ & ARX_FEEDER_GUNZIP_DEVICE) && !is_bgzf && file_is_gzip(path[f]);
+			if (gunzip) {
+				std::unique_ptr<GzipRawReader> r(new GzipRawReader()); ok = r->open(path[f], (size_t)gslab, 1); rd_[f] = std::move(r);
+				gz_[f].reset(new GzFile());
+			} else if (bgzf_[f]) { std::unique_ptr<BgzfChunkReader> r(new BgzfChunkReader()); ok = r->open(path[f], chunk_, per); rd_[f] = std::move(r); }
 			else { std::unique_ptr<ChunkReader> r(new ChunkReader()); ok = r->open(path[f], chunk_, per); rd_[f] = std::move(r); }
 			if (!ok) { error = std::string("cannot open ") + path[f]; return ARX_E_IO; }
 		}
@@ -96,6 +239,13 @@ public:
 		for (int f = 0; f < 2; ++f)
 			for (int i = 0; i < 2; ++i) registered_[f][i] = RT::host_register(rd_[f]->slab(i), rd_[f]->slab_cap()) == 0;
 		meta_ = rt.template palloc<int32_t>(16);
+		for (int f = 0; f < 2; ++f) {
+			if (!gz_[f]) continue;
+			rt.bind();
+			gz_[f]->dev.open(rt);
+			gz_[f]->src.rd = rd_[f].get();
+			gz_[f]->rd.reset(new GzReader<GzFeed>(gz_[f]->dev, gz_[f]->src, gchunk, gslab, GZ_EXPAND_DEFAULT));
+		}
 		if (bgzf_[0] || bgzf_[1]) {
 			icnt_ = rt.template palloc<int32_t>(4);
 			if (posix_memalign((void **)&hcnt_, 4096, 4096)) { hcnt_ = nullptr; throw std::bad_alloc(); }
@@ -117,6 +267,7 @@ public:
 		}
 		rt.bind();
 		try { rt.sync(); } catch (...) {}
+		for (int f = 0; f < 2; ++f) if (gz_[f]) { try { gz_[f]->dev.close(); } catch (...) {} gz_[f]->rd.reset(); } // the device first: it waits for a launch that may still read the reader's bytes
 		for (int f = 0; f < 2; ++f)
 			for (int i = 0; i < 2; ++i) {
 				if (registered_[f][i]) RT::host_unregister(rd_[f]->slab(i));
@@ -199,6 +350,21 @@ public:
 	int stats(int64_t *st) override
 	{
 		st[0] = n_chunks_; st[1] = n_bytes_; st[2] = n_records_; st[3] = bad_base_; st[4] = n_runs_; st[5] = 0; st[6] = n_dev_blocks_; st[7] = n_cbytes_;
+		return ARX_OK;
+	}
+
+	// each file's GzReader::stats in arx_selftest_gunzip's layout, as far as the reading has come; zeros for a file the device was not given
+	int gunzip_stats(int64_t *st) override
+	{
+		for (int f = 0; f < 2; ++f) {
+			int64_t *o = st + (size_t)f * GZ_N_STATS;
+			for (int k = 0; k < GZ_N_STATS; ++k) o[k] = 0;
+			if (!gz_[f] || !gz_[f]->rd) continue;
+			const GzReader<GzFeed> &r = *gz_[f]->rd;
+			for (int k = 0; k < GZ_N_STATS; ++k) o[k] = r.stats[k];
+			o[GZS_CONSUMED] = r.buf_at - r.stats[GZS_IGNORED]; o[GZS_INFLATED] = r.delivered;
+			o[GZS_US_FIND] = (int64_t)r.us[0]; o[GZS_US_DECODE] = (int64_t)r.us[1]; o[GZS_US_RESOLVE] = (int64_t)(r.us[2] + r.us[3]);
+		}
 		return ARX_OK;
 	}
 
@@ -288,7 +454,34 @@ private:
 		for (int f = 0; f < 2; ++f) want[f] = !eof_[f] && (lim_[f] || wlen_[f] < chunk_);
 		const SlabReader::Slab *sl[2] = {nullptr, nullptr};
 		double t0 = now();
-		for (int f = 0; f < 2; ++f) if (want[f]) { sl[f] = rd_[f]->acquire(); if (!sl[f]) eof_[f] = true; }
+		// The gzip files first, a piece of each per round, while one that wants text holds less than chunk_bytes: (1) find / decode / windows of
+		// both enqueued, each on its file's stream, (2) both waited for, (3) room for both texts, (4) both resolves enqueued, (5) both waited for
+		for (bool first = true;; first = false) {
+			bool ask[2];
+			for (int f = 0; f < 2; ++f) ask[f] = gz_[f] && want[f] && !eof_[f] && (first || wlen_[f] < chunk_);
+			if (!ask[0] && !ask[1]) break;
+			for (int f = 0; f < 2; ++f) if (ask[f]) gz_[f]->rd->begin();
+			int64_t piece[2] = {0, 0};
+			for (int f = 0; f < 2; ++f) {
+				if (!ask[f]) continue;
+				const int64_t k = gz_[f]->rd->next();
+				if (k > 0) piece[f] = k;
+				else { eof_[f] = true; if (k != GZ_END) err_ = true; } // (GZ_REWIND is never offered: can_rewind is false)
+				if (gz_[f]->src.err) err_ = true; // a read error of the file is one wherever it fell: behind a member's trailer the reader sees only an end
+			}
+			for (int f = 0; f < 2; ++f) {
+				if (!piece[f]) continue;
+				if (wlen_[f] + (size_t)piece[f] >= ((size_t)1 << 30)) throw std::runtime_error("FASTQ input: a record of more than 2^30 bytes");
+				ensure_keep(win_[f][wcur_[f]], wlen_[f] + (size_t)piece[f] + 64, wlen_[f]);
+			}
+			for (int f = 0; f < 2; ++f) if (piece[f]) gz_[f]->rd->place_begin(win_[f][wcur_[f]].p + wlen_[f]);
+			for (int f = 0; f < 2; ++f) {
+				if (!piece[f]) continue;
+				gz_[f]->rd->place(win_[f][wcur_[f]].p + wlen_[f]);
+				wlen_[f] += (size_t)piece[f]; n_bytes_ += piece[f]; ++n_chunks_;
+			}
+		}
+		for (int f = 0; f < 2; ++f) if (want[f] && !gz_[f]) { sl[f] = rd_[f]->acquire(); if (!sl[f]) eof_[f] = true; }
 		t_[0] += now() - t0; t0 = now();
 		// the tables of both files' BGZF slabs go up through the runtime's page-locked staging (the stream is idle here: stage() does not wait)
 		size_t row_at[2] = {0, 0}, row_bytes = 0;
@@ -449,6 +642,8 @@ private:
 	size_t chunk_;
 	std::unique_ptr<SlabReader> rd_[2];
 	bool bgzf_[2] = {false, false};                 // the file's blocks are inflated on the device
+	struct GzFile { GzFeed dev; FeederGzSlabs src; std::unique_ptr<GzReader<GzFeed> > rd; }; // an ordinary gzip file that the device inflates
+	std::unique_ptr<GzFile> gz_[2];
 	DBuf<uint8_t> cin_[2]; DBuf<InfRow> rows_[2]; DBuf<int32_t> ist_[2]; // a BGZF slab on the device: its bytes, its table, the blocks' statuses
 	int32_t *icnt_ = nullptr, *hcnt_ = nullptr; bool hcnt_reg_ = false;  // per file: bad blocks, DEFLATE blocks read; device and page-locked host
 	int64_t n_dev_blocks_ = 0, n_cbytes_ = 0;

@@ -121,6 +121,7 @@ public:
 	// the device feeder's extras; the host feeder has neither
 	virtual int device_reads(const uint8_t **, const int32_t **, int64_t *) { return ARX_E_ARG; }
 	virtual int stats(int64_t *) { return ARX_E_ARG; }
+	virtual int gunzip_stats(int64_t *) { return ARX_E_ARG; }
 };
 
 // One file of the device feeder: a thread of its own reads it slab by slab into one of two buffers while the other one is uploaded and

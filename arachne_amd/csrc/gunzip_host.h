@@ -18,11 +18,17 @@
 // trailer does not match what the device produced is read again from its header by the host where the source can go back and the caller can
 // drop the member's bytes (GZ_REWIND; the self-test); a caller that has passed them on gets an error instead (the file calls).
 //
+// A backend may offer its two calls in halves (decode_begin / decode_end, resolve_begin / resolve_end: hip_gunzip.h's GzHip does): begin() and
+// place_begin() then enqueue what next() and place() would start and only wait for, so that a caller with several files (device_feeder.h) has
+// every file's launch in flight before it waits for any.  Without the halves they do nothing, and without a call of them nothing changes.
+//
 // Out of scope: decoding on from a member end inside the same launch (the launch behind a member end starts behind the trailer and the next
 // header, with an empty window), fixed or stored blocks as chunk starts.
 #pragma once
 #include <stdint.h>
 #include <string.h>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include <zlib.h>
 #include "dev_gunzip.h"
@@ -68,7 +74,11 @@ struct GzMemSource : GzSource {
 	bool seek(int64_t to) override { if (to < 0 || to > n) return false; at = to; return true; }
 };
 
+template <class B, class = void> struct gz_has_halves : std::false_type {};
+template <class B> struct gz_has_halves<B, std::void_t<decltype(&B::decode_begin), decltype(&B::decode_end), decltype(&B::resolve_begin), decltype(&B::resolve_end)> > : std::true_type {};
+
 template <class Backend> struct GzReader {
+	static constexpr bool HALVES = gz_has_halves<Backend>::value;
 	Backend &dev;
 	GzSource &src;
 	int64_t chunk_bytes, slab_bytes; int32_t expand;
@@ -95,6 +105,9 @@ template <class Backend> struct GzReader {
 	int64_t piece_n = 0, launch_n = 0;
 	std::vector<uint8_t> host_piece;
 	int64_t delivered = 0, rewind_to = 0;
+	// the halves: a launch that begin() enqueued, what begin() met instead of one, a resolve that place_begin() enqueued
+	bool launched = false, held = false, resolving = false;
+	int64_t held_value = 0;
 
 	GzReader(Backend &dev_, GzSource &src_, int64_t chunk, int64_t slab, int32_t expand_) : dev(dev_), src(src_), chunk_bytes(chunk), slab_bytes(slab), expand(expand_)
 	{
@@ -199,14 +212,22 @@ template <class Backend> struct GzReader {
 
 	// One launch on the bytes in buf, up to the windows.  -> true: a chain was accepted and awaits its resolve (accept()); false: the device did
 	// not take it, and `host` is set
-	bool device_step()
+	bool device_step(bool begin_only = false)
 	{
-		if (n_short >= 2) { to_host(GZ_FB_CUT_SHORT); return false; } // two such launches in a row: whatever follows is the host's
-		fill((size_t)slab_bytes);
-		const int64_t n = (int64_t)buf.size() < slab_bytes ? (int64_t)buf.size() : slab_bytes;
-		if (n == 0 || bit >= 8 * n) { to_host(GZ_FB_NO_BLOCK); return false; }
-		dev.decode(buf.data(), (int)n, bit, window, have, (int)chunk_bytes, expand, L);
-		launch_n = n;
+		if (!launched) {
+			if (n_short >= 2) { to_host(GZ_FB_CUT_SHORT); return false; } // two such launches in a row: whatever follows is the host's
+			fill((size_t)slab_bytes);
+			const int64_t n = (int64_t)buf.size() < slab_bytes ? (int64_t)buf.size() : slab_bytes;
+			if (n == 0 || bit >= 8 * n) { to_host(GZ_FB_NO_BLOCK); return false; }
+			launch_n = n;
+			if constexpr (HALVES) {
+				dev.decode_begin(buf.data(), (int)n, bit, window, have, (int)chunk_bytes, expand); // (buf, bit and window stay as they are until decode_end)
+				launched = true;
+				if (begin_only) return true;
+			} else dev.decode(buf.data(), (int)n, bit, window, have, (int)chunk_bytes, expand, L);
+		}
+		if constexpr (HALVES) { launched = false; dev.decode_end(L); }
+		const int64_t n = launch_n;
 		++stats[GZS_LAUNCHES]; stats[GZS_CHUNKS] += (int64_t)L.chunks.size();
 		for (int p = 0; p < 3; ++p) us[p] += L.us[p];
 		const int nc = (int)L.chunks.size();
@@ -278,6 +299,19 @@ template <class Backend> struct GzReader {
 	// an error, GZ_REWIND (can_rewind only): the bytes delivered behind the first rewind_to are dropped, the reading goes on
 	int64_t next()
 	{
+		if (held) { held = false; return held_value; }
+		return run(false);
+	}
+	// the enqueue half of next(): where the next piece is the device's its launch is started and next() waits for it; anything else next()
+	// would have met on the way (a piece of the host's, the end, an error) is kept for it
+	void begin()
+	{
+		if (!HALVES || held || launched || piece) return;
+		const int64_t r = run(true);
+		if (!launched) { held = true; held_value = r; }
+	}
+	int64_t run(bool begin_only)
+	{
 		for (;;) {
 			if (state == S_END) return GZ_END;
 			if (state == S_COPY) { // no gzip file: gzread hands the bytes on as they are
@@ -309,6 +343,7 @@ template <class Backend> struct GzReader {
 					piece = 2;
 					return piece_n = (int64_t)host_piece.size();
 				}
+				if (begin_only && !launched) { if (!device_step(true)) continue; return 0; }
 				if (!device_step()) continue;
 				if (L.chain.text_bytes == 0) { dev.resolve(L, nullptr); accept(); continue; } // (the chunks' CRCs of no bytes, and the window)
 				piece = 1;
@@ -332,9 +367,19 @@ template <class Backend> struct GzReader {
 		}
 	}
 	// the piece next() announced to dst[0, its bytes): the backend's memory
+	// the enqueue half of place(dst) for a piece of the device's: place(dst) then waits for it
+	void place_begin(uint8_t *dst)
+	{
+		if constexpr (HALVES) { if (piece == 1 && !resolving) { dev.resolve_begin(L, dst); resolving = true; } }
+		(void)dst;
+	}
 	void place(uint8_t *dst)
 	{
-		if (piece == 1) { dev.resolve(L, dst); accept(); }
+		if (piece == 1) {
+			if constexpr (HALVES) { if (!resolving) dev.resolve_begin(L, dst); resolving = false; dev.resolve_end(L); }
+			else dev.resolve(L, dst);
+			accept();
+		}
 		else if (piece == 2) dev.upload(dst, host_piece.data(), host_piece.size());
 		delivered += piece_n;
 		piece = 0; piece_n = 0;

@@ -1,6 +1,7 @@
 // hip_gunzip.h -- dev_gunzip.h on the GPU: the chunked inflate of one plain DEFLATE stream behind arx_selftest_gunzip.  Included by
 // arx_bgzf.hip, next to hip_inflate.h.  GzHip is the backend gunzip_host.h's reader drives: per slab of compressed bytes one decode(), which ends
-// with the sizes, and one resolve() to the place the caller has made for the text.
+// with the sizes, and one resolve() to the place the caller has made for the text.  Each of the two also exists as an enqueue half and a wait
+// half (decode_begin / decode_end, resolve_begin / resolve_end) for the device feeder, which keeps two files' launches in flight at once.
 //
 //   k_gunzip_find     one wavefront per chunk: its candidate (dev_gunzip.h: gz_chunk_find).  About 13 KB of LDS
 //   k_gunzip_decode   one wavefront per chunk with a candidate: its blocks as 16-bit symbols into its span of the staging buffer; the ring of
@@ -108,11 +109,15 @@ struct GzHip {
 		d_chain.alloc(sizeof(GzChain));
 	}
 	static void room(DevBuf &b, size_t bytes) { if (!b.p || b.bytes < bytes) b.alloc(bytes + (bytes >> 2)); }
-	// find, decode, windows: the chunks and the chain, and with them the size of the text
-	void decode(const uint8_t *src, int clen, int start_bit, const uint8_t *window, int have, int chunk_bytes, int expand, GzLaunch &L)
+	// find, decode, windows: the chunks and the chain, and with them the size of the text.  In two halves, so that a caller with several files
+	// (device_feeder.h) has every file's launches in flight before it waits for any: decode_begin enqueues the upload and the three kernels and
+	// returns; decode_end brings the chunks and the chain home and waits.  (The copies home are the wait half's: into pageable memory the
+	// runtime makes them wait for the stream.)  decode() is the two in a row
+	int64_t stage_n = 0;
+	void decode_begin(const uint8_t *src, int clen, int start_bit, const uint8_t *window, int have, int chunk_bytes, int expand)
 	{
 		n = (int)(((int64_t)clen + chunk_bytes - 1) / chunk_bytes);
-		const int64_t stage_n = gz_stage_at(8 * (int64_t)clen, expand);
+		stage_n = gz_stage_at(8 * (int64_t)clen, expand);
 		room(d_src, (size_t)clen); room(d_chunks, sizeof(GzChunk) * (size_t)n); room(d_stage, 2 * (size_t)stage_n); room(d_windows, (size_t)(n + 1) * GZ_WIN);
 		GzChunk *chunks = d_chunks.as<GzChunk>();
 		ARX_HIP_CHECK(hipMemcpyAsync(d_src.p, src, (size_t)clen, hipMemcpyHostToDevice, st));
@@ -126,8 +131,11 @@ struct GzHip {
 		ARX_HIP_CHECK(hipEventRecord(ev[2], st));
 		hip_launch("k_gunzip_windows", k_gunzip_windows, dim3(1), dim3(GZ_WINDOW_THREADS), 0, st, chunks, n, have, d_stage.as<uint16_t>(), d_windows.as<uint8_t>(), d_chain.as<GzChain>());
 		ARX_HIP_CHECK(hipEventRecord(ev[3], st));
+	}
+	void decode_end(GzLaunch &L)
+	{
 		L.chunks.resize((size_t)n);
-		ARX_HIP_CHECK(hipMemcpyAsync(L.chunks.data(), chunks, sizeof(GzChunk) * (size_t)n, hipMemcpyDeviceToHost, st));
+		ARX_HIP_CHECK(hipMemcpyAsync(L.chunks.data(), d_chunks.p, sizeof(GzChunk) * (size_t)n, hipMemcpyDeviceToHost, st));
 		ARX_HIP_CHECK(hipMemcpyAsync(&L.chain, d_chain.p, sizeof(GzChain), hipMemcpyDeviceToHost, st));
 		ARX_HIP_CHECK(hipStreamSynchronize(st));
 		if (L.chain.n_accepted < 0 || L.chain.n_accepted > n || L.chain.text_bytes < 0 || L.chain.text_bytes > stage_n) throw HipError("k_gunzip_windows: a chain outside the launch");
@@ -138,19 +146,43 @@ struct GzHip {
 		}
 		L.us[3] = 0;
 	}
-	// resolve: the accepted chunks' bytes to text[0, L.chain.text_bytes) in device memory, their CRCs, and the window behind them
-	void resolve(GzLaunch &L, uint8_t *text)
+	void decode(const uint8_t *src, int clen, int start_bit, const uint8_t *window, int have, int chunk_bytes, int expand, GzLaunch &L)
 	{
-		GzChunk *chunks = d_chunks.as<GzChunk>();
+		decode_begin(src, clen, start_bit, window, have, chunk_bytes, expand);
+		decode_end(L);
+	}
+	// resolve: the accepted chunks' bytes to text[0, L.chain.text_bytes) in device memory, their CRCs, and the window behind them; in the same
+	// two halves.  Where the place of the text was made on another stream (`after`), the kernel waits for what that stream holds (evo[0]), and
+	// that stream for the kernel (evo[1]): what it is given next reads the text
+	Event evo[2];
+	void resolve_begin(GzLaunch &, uint8_t *text, hipStream_t after = nullptr)
+	{
+		if (after) {
+			if (!evo[0].e) for (Event &e : evo) e.create(hipEventDisableTiming);
+			ARX_HIP_CHECK(hipEventRecord(evo[0], after));
+			ARX_HIP_CHECK(hipStreamWaitEvent(st, evo[0], 0));
+		}
 		ARX_HIP_CHECK(hipEventRecord(ev[3], st));
-		hip_launch("k_gunzip_resolve", k_gunzip_resolve, dim3(n), dim3(GZ_RESOLVE_THREADS), 0, st, chunks, n, d_stage.as<uint16_t>(), d_windows.as<uint8_t>(), text);
+		hip_launch("k_gunzip_resolve", k_gunzip_resolve, dim3(n), dim3(GZ_RESOLVE_THREADS), 0, st, d_chunks.as<GzChunk>(), n, d_stage.as<uint16_t>(), d_windows.as<uint8_t>(), text);
 		ARX_HIP_CHECK(hipEventRecord(ev[4], st));
-		ARX_HIP_CHECK(hipMemcpyAsync(L.chunks.data(), chunks, sizeof(GzChunk) * (size_t)n, hipMemcpyDeviceToHost, st));
+		if (after) {
+			ARX_HIP_CHECK(hipEventRecord(evo[1], st));
+			ARX_HIP_CHECK(hipStreamWaitEvent(after, evo[1], 0));
+		}
+	}
+	void resolve_end(GzLaunch &L)
+	{
+		ARX_HIP_CHECK(hipMemcpyAsync(L.chunks.data(), d_chunks.p, sizeof(GzChunk) * (size_t)n, hipMemcpyDeviceToHost, st));
 		ARX_HIP_CHECK(hipMemcpyAsync(L.window, d_windows.as<uint8_t>() + (size_t)L.chain.n_accepted * GZ_WIN, GZ_WIN, hipMemcpyDeviceToHost, st));
 		ARX_HIP_CHECK(hipStreamSynchronize(st));
 		float ms = 0;
 		ARX_HIP_CHECK(hipEventElapsedTime(&ms, ev[3], ev[4]));
 		L.us[3] = 1000.0 * ms;
+	}
+	void resolve(GzLaunch &L, uint8_t *text)
+	{
+		resolve_begin(L, text);
+		resolve_end(L);
 	}
 	void upload(uint8_t *dst, const uint8_t *host, size_t bytes)
 	{

@@ -217,6 +217,11 @@ struct FeederSwitches {
 	// chunks a parse takes from each file (default: as many as fill SLAB_TARGET, at most 64); 1 makes every chunk boundary a boundary between
 	// parses.  Quirk: a value below 1, or one whose chunks together exceed MAX_CHUNK, is ignored without a word (DeviceFeeder::open)
 	std::optional<long> parse_chunks = sw_long_if_set("ARX_FEEDER_PARSE_CHUNKS");
+	// the gzip inflate of ARX_FEEDER_GUNZIP_DEVICE: compressed bytes per chunk (default: gunzip_host.h's GZ_CHUNK_DEFAULT) and per launch (default:
+	// the rule at the top of device_feeder.h).  Tests put many chunks and launches into a small file with them; a value outside
+	// arx_selftest_gunzip's bounds makes the open fail (ARX_E_ARG)
+	std::optional<long> gunzip_chunk = sw_long_if_set("ARX_FEEDER_GUNZIP_CHUNK");
+	std::optional<long> gunzip_slab = sw_long_if_set("ARX_FEEDER_GUNZIP_SLAB");
 	bool times = sw_present("ARX_FEEDER_TIMES");               // diagnostics: where the feeder thread's time went, and the kernels' own times (HIP events)
 };
 

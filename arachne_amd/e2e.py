@@ -41,12 +41,14 @@ _COUNTERS = dict(pairs=0, records=0, batches=0, feeder_s=0.0, device_s=0.0, fetc
 def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int = 250_000, bam_threads: int = 8, rec_threads: int = 8, level: int = 1,
         penalty: float = -4, lib_path: str = api.LIB_PATH, warm_passes: int = 0, layout: str = "workers", chunk: int = 40_000_000,
         read_groups: str = "", sample_id: str = "", feeder: str = "host", workers: int = 3, chunk_bytes: int = 0,
-        sink: str = "host", records: str = "host", inflate: str = "host", final_bam: str | None = None):
+        sink: str = "host", records: str = "host", inflate: str = "host", final_bam: str | None = None, gunzip: str = "host"):
     """fastq_pairs: [(r1, r2), ...] barcode-sorted files (plain or gzip).  -> stats dict (pairs, records, batches, seconds, pairs/s, bam_bytes,
     workers, files, per-stage seconds summed over workers; bam_s: the writes and the closing of the writers).  One loop with four axes (the module docstring has them):
     feeder="host" (default): one host feeder and one worker per file pair.  feeder="device": ONE file pair, parsed on the GPU by one feeder
     thread (arx_feeder_open_device) that hands super-batches to `workers` worker threads; stats["feeder"] are the feeder's own counts.
     inflate="device" (feeder="device" only): BGZF files are inflated by a HIP kernel instead of zlib on the reader threads (api.Feeder).
+    gunzip="device" (feeder="device" only): ordinary gzip files are inflated on the GPU in chunks, both files at once (api.Feeder); stats["gunzip"]
+    are the two files' counts then.
     layout="workers" (default): out_prefix.k.bam per worker.  layout="reference": out_prefix is the output directory of the reference's layout
     (chunk = -p/--partitions, read_groups / sample_id as the reference's flags).
     records="host" (default): the records are built on host threads from the fetched result slabs.  records="device" (layout="workers" only):
@@ -80,6 +82,10 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
         raise ValueError(f"unknown inflate {inflate!r}")
     if inflate == "device" and feeder != "device":
         raise ValueError("inflate='device' is the device feeder's: it needs feeder='device' (the host feeder inflates with zlib)")
+    if gunzip not in ("host", "device"):
+        raise ValueError(f"unknown gunzip {gunzip!r}")
+    if gunzip == "device" and feeder != "device":
+        raise ValueError("gunzip='device' is the device feeder's: it needs feeder='device' (the host feeder inflates with zlib)")
     if layout not in ("workers", "reference"):
         raise ValueError(f"unknown layout {layout!r}")
     if warm_passes and feeder == "device":
@@ -116,7 +122,7 @@ def run(ref: api.Reference, fastq_pairs, out_prefix: str, pairs_per_batch: int =
         take = producer = fd = None
         try:
             if feeder == "device":
-                fd = api.Feeder(*fastq_pairs[0], device=ref, chunk_bytes=chunk_bytes, depth=n_workers + 2, inflate=inflate)
+                fd = api.Feeder(*fastq_pairs[0], device=ref, chunk_bytes=chunk_bytes, depth=n_workers + 2, inflate=inflate, gunzip=gunzip)
                 take, producer = _device_source(ref, fd, pairs_per_batch, n_workers, errors, stats, lock)
 
             def work(k):
@@ -406,6 +412,8 @@ def _device_source(ref, fd, pairs_per_batch, workers, errors, stats, lock):
                     except queue.Full:
                         pass
             stats["feeder"].update(fd.stats())
+            if fd.gunzip == "device":
+                stats["gunzip"] = list(fd.gunzip_stats())
         except BaseException as e:  # noqa: BLE001 -- reported by the caller's thread
             errors.append(e)
         finally:

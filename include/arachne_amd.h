@@ -259,15 +259,33 @@ int arx_feeder_open_device(arx_ctx *ctx, const char *r1_path, const char *r2_pat
  * does: the sets that are complete are delivered, then arx_feeder_next returns < 0.  A missing EOF block is no error.  The super-batches
  * are byte for byte those of the plain text.  flags = 0 is arx_feeder_open_device exactly; unknown bits: ARX_E_ARG. */
 #define ARX_FEEDER_INFLATE_DEVICE 1
+/* ARX_FEEDER_GUNZIP_DEVICE (the bit of ARX_FQSORT_GUNZIP_DEVICE and ARX_FQSTD_GUNZIP_DEVICE): a file that is ordinary gzip -- the magic 1f 8b,
+ * CM 8, and no BGZF block first -- is read as it is and inflated on the device in chunks (csrc/dev_gunzip.h, gunzip_host.h: one DEFLATE stream
+ * per member, a wavefront per 32 KiB of it), a launch at a time, straight into the text the parse kernels read; the two files' launches are in
+ * flight together, each on a stream of its own.  R1 and R2 are looked at separately; a BGZF file goes as without this flag (its kernel with
+ * ARX_FEEDER_INFLATE_DEVICE, zlib without), plain text as ever.  For such a file a piece of text is what one launch accepts, and the feeder
+ * asks for another while the file's window holds less than chunk_bytes; the compressed bytes per launch follow from chunk_bytes
+ * (csrc/device_feeder.h states the rule).  Whatever the device does not take -- a refuted candidate, an overflow, a stored block in the way,
+ * members cut short -- is inflated by zlib on the feeder's thread from there on; the device never declares a file bad.  Where zlib or a
+ * member's trailer (CRC-32, ISIZE) reports an error the input ends there like at a read error: the sets that are complete are delivered, then
+ * arx_feeder_next returns < 0.  The super-batches are byte for byte those of the plain text.  Two environment switches, read at open, for
+ * tests: ARX_FEEDER_GUNZIP_CHUNK=n (compressed bytes per chunk) and ARX_FEEDER_GUNZIP_SLAB=n (per launch), within arx_selftest_gunzip's bounds
+ * (ARX_E_ARG otherwise).  Off by default. */
+#define ARX_FEEDER_GUNZIP_DEVICE 8
 int arx_feeder_open_device_ex(arx_ctx *ctx, const char *r1_path, const char *r2_path, int64_t chunk_bytes, int32_t depth, int32_t flags, arx_feeder **out,
                               char *msg, int32_t msg_cap);
 /* the reads of the super-batch the last arx_feeder_next delivered, in device memory, for arx_batch_reset_device (same validity as its host
  * arrays; the feeder's stream is done with them).  ARX_E_ARG for a host feeder or before the first super-batch. */
 int arx_feeder_device_reads(arx_feeder *f, const uint8_t **d_bases, const int32_t **d_lens, int64_t *n_bases);
 /* stats[8] of a device feeder since open: chunks read (both files), bytes of text that entered the parse (the same for the plain, gzip and
- * BGZF form of a text), records parsed, lines skipped, barcode runs, chunks that took a host fallback (always 0: there is none), BGZF blocks
- * inflated on the device, compressed bytes uploaded for them (both 0 without ARX_FEEDER_INFLATE_DEVICE).  ARX_E_ARG for a host feeder. */
+ * BGZF form of a text), records parsed, lines skipped, barcode runs, chunks that took a host fallback (always 0: a BGZF block has none, and what zlib
+ * took over of a gzip file under ARX_FEEDER_GUNZIP_DEVICE is reported by arx_feeder_gunzip_stats), BGZF blocks inflated on the device, compressed
+ * bytes uploaded for them (both 0 without ARX_FEEDER_INFLATE_DEVICE).  A gzip file's pieces count as chunks.  ARX_E_ARG for a host feeder. */
 int arx_feeder_stats(arx_feeder *f, int64_t *stats);
+/* stats[2 * ARX_GUNZIP_N_STATS] of a device feeder: for R1, then for R2, what the gzip inflate on the device has done so far, in the layout of
+ * arx_selftest_gunzip's stats (launches, accepted chunks, the bytes zlib inflated, why it took over, ...).  All zero for a file the device was
+ * not given (no ARX_FEEDER_GUNZIP_DEVICE, or not an ordinary gzip file).  ARX_E_ARG for a host feeder. */
+int arx_feeder_gunzip_stats(arx_feeder *f, int64_t *stats);
 
 /* ---- behind the path: the BAM sink.  The reference builds one biogo sam.Record per alignment on a single goroutine and
  * writes it twice (BamThread / AppendBams, src/aligner/bamwriter.go:615-627,279-282), two BGZF goroutines per writer (:118).  Here records
